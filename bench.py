@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the SVO ray-march on BASELINE.json's headline config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,9 @@ at rest: its tiles are launched longest first; `--frames-in-flight 1` gives the 
 N > 1: the frame is sharded by interleaved 8x8 screen tiles (total work fixed: "strong" scaling), one process per GPU
 over RCCL (under torch.distributed.run, or started by this script itself when WORLD_SIZE is not set), or — with
 --single-process — one process driving N devices through the C ABI's own multi-device context (vrt_config.device_ids).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line; `ms_per_step` is the time of one of the K timed steps.  --dump-outputs DIR writes the last
+timed frame as rank 0 holds it (rgb.npy float32, ids.npy float64) — for the same arguments the frames' inputs are the same
+from run to run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,7 +36,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 N_SIMD = 1024               # 256 CUs x 4 SIMD-32
 NOMINAL_GHZ = 2.4
-MIN_TIMED_SECONDS = 0.05    # a timed window shorter than this is followed by a second, longer one (see `steps_timed`)
+DUMP_MAX_BYTES = 64_000_000   # --dump-outputs: whole frames up to this size, a fixed sample of pixels beyond it
 
 
 def parse_args():
@@ -55,7 +57,10 @@ def parse_args():
                     help="frames the backend keeps in flight (vrt_set_frames_in_flight; 1 = one launch at a time)")
     ap.add_argument("--fixed-camera", action="store_true", help="headline loop with a standing camera and no per-frame seam calls")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (fixed camera, 1 in flight, clock probe)")
-    ap.add_argument("--exact-steps", action="store_true", help="time the requested steps only, however short (no second, >= 50 ms window)")
+    ap.add_argument("--exact-steps", action="store_true", help="accepted for old command lines: the K requested steps are always the timed window")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame to DIR/<name>.npy (rgb float32, ids float64; a seeded "
+                         "sample of pixels with their indices when the frame is over 64 MB)")
     ap.add_argument("--settle-seconds", type=float, default=2.0, help="upper bound of the clock-settling frames before the warm-up (0 = none)")
     ap.add_argument("--root-weight", type=int, default=0,
                     help="N > 1: tiles per period dealt to the gather root (vrt_config.shard_root_weight); 0 = measure "
@@ -443,20 +448,10 @@ def main():
     dt = timed(gpu, fg, args.steps, fixed)   # every timed frame is gathered and assembled on rank 0 before the clock stops
     host_submit_ms = submit[0] / args.steps * 1e3
     rays_total = rays_fixed * args.steps if fixed else int(sum(int(orbit_rays[i % ORBIT]) for i in range(args.steps)))
-    # A short request (the driver's 20 steps are 1.9 ms of frames: two of them pipeline fill and drain, and one scheduling hiccup
-    # of the host is a tenth of it) is followed by a second timed window of the same loop, long enough for >= 50 ms of frames,
-    # bracketed like the first (barrier + synchronise on both sides, maximum over ranks).  `value` / `ms_per_step` are then the
-    # LONG window's, `steps_timed` its length; the requested K steps alone stay in `value_requested_steps` /
-    # `ms_per_step_requested_steps`.  A request that is itself >= 50 ms of frames is timed once, as before.
-    requested = {"steps": args.steps, "value": rays_total / dt / 1e6, "ms_per_step": dt / args.steps * 1e3, "host_submit_ms_per_step": host_submit_ms}
-    steps_timed = args.steps
-    if dt < MIN_TIMED_SECONDS and not args.exact_steps:
-        steps_timed = max(args.steps, int(np.ceil(MIN_TIMED_SECONDS / (dt / args.steps))))
-        first = frame_no[0]
-        dt = timed(gpu, fg, steps_timed, fixed)
-        host_submit_ms = submit[0] / steps_timed * 1e3
-        rays_total = rays_fixed * steps_timed if fixed else int(sum(int(orbit_rays[(first + i) % ORBIT]) for i in range(steps_timed)))
-    kst = gpu.stats()   # per-kernel durations over the timed frames (both windows): HIP events on the streams the kernels ran on
+    steps_timed = args.steps   # exactly the requested steps: `ms_per_step` is one of them
+    requested = {"value": rays_total / dt / 1e6, "ms_per_step": dt / args.steps * 1e3}
+    dumped = dump_outputs(args, gpu, fg, sharded, rank) if args.dump_outputs else None
+    kst = gpu.stats()   # per-kernel durations over the timed frames: HIP events on the streams the kernels ran on
     issue = gpu.issue_profile()                                   # what issuing those frames cost this rank's host thread
     gather_host = fg.host_profile() if fg is not None else None   # ... and its collectives
 
@@ -792,14 +787,10 @@ def main():
         "value": rays_total / dt / 1e6,
         "unit": "Mrays/s",
         "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-        # frames inside the timed window `value` comes from (> steps when the request was under 50 ms of frames: see
-        # `value_requested_steps` for the K steps alone)
+        # frames inside the timed window `value` comes from: the requested steps
         "steps_timed": steps_timed,
         "value_requested_steps": requested["value"], "ms_per_step_requested_steps": requested["ms_per_step"],
-        "value_is": ("the rate over exactly the requested steps" if steps_timed == args.steps else
-                     f"the rate over a second timed window of {steps_timed} frames of the same loop (the requested {args.steps} steps are "
-                     f"{requested['ms_per_step'] * args.steps:.2f} ms of frames, under the {MIN_TIMED_SECONDS * 1e3:.0f} ms a window needs to be more than pipeline fill and drain); "
-                     "the requested steps alone: value_requested_steps"),
+        "value_is": "the rate over exactly the requested steps",
         "ranks_seen": ranks_seen,   # an all-reduce of ones over the process group (1: no group)
         "links": links,
         "ms_per_step": period_s * 1e3,
@@ -829,7 +820,7 @@ def main():
                    "frames_in_flight": args.frames_in_flight, "clock_settle": settle,
                    # (scalars, so that they survive in the driver's `parsed.config`: which window `value` / `ms_per_step` are of)
                    "steps_requested": args.steps, "steps_timed": steps_timed, "value_requested_steps": requested["value"],
-                   "ms_per_step_requested_steps": requested["ms_per_step"], "value_window": "requested steps" if steps_timed == args.steps else "second window of steps_timed frames",
+                   "ms_per_step_requested_steps": requested["ms_per_step"], "value_window": "requested steps",
                    "kernel_variant": args.variant, "derived_tables": derived,
                    # N > 1: what this split should give, term by term, from the unsharded frame timed on this GPU in this run —
                    # stated so that the measured line can be read against it (shard.expected_scaling)
@@ -917,6 +908,8 @@ def main():
         out["config"].update(expected_ms=es["predicted_ms"], expected_speedup=es["speedup"], expected_bound=es["bound"], host_us_per_frame_measured=host_us,
                              predicted_faster_mode=es["modes"]["predicted_faster"], root_share_of_tiles=root_share, degenerate_scaling_point=bool(root_share > 0.8),
                              frame_ms_1gpu_same_run=one_gpu_ms[0])
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if gather_host is not None:
         out["gather_host_profile"] = dict(gather_host, render_call_us=issue["render_us"])   # (this rank's host time per collective / per render call)
     out.update(extras)
@@ -932,6 +925,36 @@ def main():
         real_stdout.write(json.dumps(out) + "\n")
     if sharded:
         dist.destroy_process_group()
+
+
+def dump_outputs(args, gpu, fg, sharded, rank):
+    """The last timed frame as the caller of the timed path receives it — rank 0's assembled frame when N > 1 — written to
+    args.dump_outputs: rgb.npy (float32 [h, w, 3]) and ids.npy (the id words, float64 [h, w]: exact).  A frame over
+    DUMP_MAX_BYTES is written as a fixed sample of its pixels (seed 0, sorted), rgb [k, 3] and ids [k], with their row-major
+    indices in pixel_index.npy.  Returns {name: shape} of what was written (None on the ranks that write nothing)."""
+    import numpy as np
+    if sharded:
+        if rank != 0:
+            return None
+        from voxelraytracing_amd.shard import texels_to_frame
+        import torch
+        torch.cuda.synchronize()
+        rgb, ids = texels_to_frame(fg.frame.cpu().numpy().view(np.uint32))
+    else:
+        rgb, ids, _ = gpu.read_output()
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(args.height, args.width, 3)
+    ids = np.ascontiguousarray(ids).reshape(args.height, args.width).astype(np.float64)
+    arrays = {"rgb": rgb, "ids": ids}
+    n = args.height * args.width
+    budget = DUMP_MAX_BYTES - 4096   # (room for the .npy headers)
+    if rgb.nbytes + ids.nbytes > budget:
+        k = budget // (12 + 8 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {"rgb": rgb.reshape(n, 3)[idx], "ids": ids.reshape(n)[idx], "pixel_index": idx.astype(np.float64)}
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def usable_cores():

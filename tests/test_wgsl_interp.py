@@ -309,14 +309,33 @@ def test_module_scope_bindings_and_storage_arrays():
 
 # ---- the reference's own helper functions, against values worked out from their text ----
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/clientdesktop/src/graphics/path_tracer.wgsl"), reason="needs the reference's shader text")
-def test_rng_next_of_the_reference_by_hand():
-    """path_tracer.wgsl:56-61 on state 0, worked with Python integers: the interpreter executes the text, the test the arithmetic."""
-    m = W.Module(open("/root/reference/clientdesktop/src/graphics/path_tracer.wgsl").read())
-    s = (0 * 747796405 + 2891336453) % 2**32
+PATH_SHADER = "/root/reference/clientdesktop/src/graphics/path_tracer.wgsl"   # (tests/golden/make_wgsl_fixtures.py's)
+
+
+def rng_next_by_hand(s):
+    """path_tracer.wgsl:56-61 worked with Python integers: (next state, uniform)."""
+    s = (s * 747796405 + 2891336453) % 2**32
     r = (((s >> ((s >> 28) + 4)) ^ s) * 277803737) % 2**32
     r = (r >> 22) ^ r
+    return s, F32(F32(r) / F32(4294967296.0))
+
+
+def test_rng_next_of_the_reference_by_hand():
+    """path_tracer.wgsl:56-61: the interpreter executes the text, the test the arithmetic.  What the interpreter computed from
+    the text is stored in tests/golden/wgsl_rng.npz (tests/golden/make_wgsl_fixtures.py: 7 seeds x 16 draws); where the
+    reference's shader text is present it is executed once more, on state 0."""
+    f = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgsl_rng.npz"))
+    for k, seed in enumerate(f["seeds"]):
+        s = int(seed)
+        for j in range(16):
+            s, u = rng_next_by_hand(s)
+            assert s == int(f["states"][k, j]), (int(seed), j)
+            assert bits(u) == bits(f["uniforms"][k, j]), (int(seed), j)
+    if not os.path.exists(PATH_SHADER):
+        return
+    m = W.Module(open(PATH_SHADER).read())
+    s, u = rng_next_by_hand(0)
     scope = {"rng": U32(0)}
     got = m.call("rng_next", W.Ref(scope, "rng"))
     assert int(scope["rng"]) == s
-    assert float(got) == float(F32(F32(r) / F32(4294967296.0)))
+    assert float(got) == float(u)
