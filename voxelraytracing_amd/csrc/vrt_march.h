@@ -627,7 +627,9 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             // (r) The inner loop as the instructions themselves.  What the compiler makes of the C++ below is the same vector
             // instructions, but it wraps every step in seven scalar instructions, four branches (three taken) and six s_nop /
             // s_waitcnt: its loop exits become 64-bit flag registers that are set, selected, and-ed with exec and copied to vcc, and
-            // around the helpers above — one-instruction asm statements — it pads for hazards they do not have.  The scalar unit
+            // around the helpers above — one-instruction asm statements it cannot see into — it pads at every boundary.  Inside this
+            // string nothing is padded: it carries its own wait states (the axis selects below), and tests/test_isa_hazards.py holds
+            // every asm string of the product to gfx950's wait-state rules, each rule to what hipcc pads in its own code.  The scalar unit
             // is shared by a CU's four SIMDs, and the step's scalar work showed as its price (profiles/r06_step_asm.txt).  Here:
             // one scalar instruction (the trip count, as iter - kMaxSteps: its carry is the exit), three branches of which the
             // loop's own is the only one taken, one s_waitcnt; 34 vector instructions.
@@ -635,7 +637,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             // still uses; tests/test_gpu_parity.py holds both against the oracle bit for bit.
             // Leaves with `e` = the entry some lane has to decide about (nothing of that step done), or after kMaxSteps lookups.
             uint32_t t0, t1, t2;
-            unsigned long long sa, sb, sx, sd, sn, sw;
+            unsigned long long sa, sb, sx, sd, sn, sw, fy, fz;
             uint32_t parked;
             uint32_t trips = __builtin_amdgcn_readfirstlane(iter) - kMaxSteps;   // (wave-uniform already: tells the compiler)
             asm volatile(
@@ -671,22 +673,24 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
                 ".Lvrt_move_%=:\n\t"
                 // (the half-rate instructions — compares, selects, conversions — each between two plain ones: next to a plain instruction
                 // a half-rate one issues in a plain one's time, next to another half-rate one it takes its own: tools/valu_rates.hip k_mix_*)
-                "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t"                // step + 0.001
+                // (a VALU's write of vcc or of an SGPR pair is read by a VALU two wait states later at the earliest — nothing pads
+                // inside this string: each compare has its own flags, three instructions or more ahead of its select)
                 "v_cmp_eq_f32_e32 vcc, %[st], %[ax]\n\t"
+                "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t"                // step + 0.001
+                "v_cmp_eq_f32_e64 %[fy], %[st], %[ay]\n\t"
                 "v_add_f32_e32 %[tl], %[tl], %[st]\n\t"
                 "v_cndmask_b32_e32 %[t1], %[st], %[t0], vcc\n\t"
                 "v_mul_f32_e32 %[t1], %[dx], %[t1]\n\t"
-                "v_cmp_eq_f32_e32 vcc, %[st], %[ay]\n\t"
+                "v_cmp_eq_f32_e64 %[fz], %[st], %[az]\n\t"
                 "v_add_f32_e32 %[px], %[px], %[t1]\n\t"
-                "v_cndmask_b32_e32 %[t2], %[st], %[t0], vcc\n\t"
+                "v_cndmask_b32_e64 %[t2], %[st], %[t0], %[fy]\n\t"
                 "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t"
-                "v_cmp_eq_f32_e32 vcc, %[st], %[az]\n\t"
+                "v_cndmask_b32_e64 %[t0], %[st], %[t0], %[fz]\n\t"
                 "v_add_f32_e32 %[py], %[py], %[t2]\n\t"
-                "v_cndmask_b32_e32 %[t0], %[st], %[t0], vcc\n\t"
-                "v_mul_f32_e32 %[t0], %[dz], %[t0]\n\t"
                 "v_cvt_flr_i32_f32_e32 %[vx], %[px]\n\t"
-                "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t"
+                "v_mul_f32_e32 %[t0], %[dz], %[t0]\n\t"
                 "v_cvt_flr_i32_f32_e32 %[vy], %[py]\n\t"
+                "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t"
                 "v_cvt_flr_i32_f32_e32 %[vz], %[pz]\n\t"
                 "s_add_u32 %[it], %[it], 1\n\t"                              // (carries when the count reaches kMaxSteps, :220)
                 "s_cbranch_scc0 .Lvrt_step_%=\n\t"
@@ -754,6 +758,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
                 : [px] "+v"(pos.x), [py] "+v"(pos.y), [pz] "+v"(pos.z), [tl] "+v"(total_len), [vx] "+v"(vx), [vy] "+v"(vy), [vz] "+v"(vz),
                   [st] "+v"(step), [ax] "+v"(adx), [ay] "+v"(ady), [az] "+v"(adz), [e] "=&v"(e), [it] "+s"(trips),
                   [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [sa] "=&s"(sa), [sb] "=&s"(sb), [sx] "=&s"(sx), [sd] "=&s"(sd), [sn] "=&s"(sn), [sw] "=&s"(sw),
+                  [fy] "=&s"(fy), [fz] "=&s"(fz),
                   [vox] "+v"(voxel), [parked] "=&v"(parked)
                 : [mx] "v"(mxm), [my] "v"(mym), [mz] "v"(mzm), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [ux] "v"(ux), [uy] "v"(uy), [uz] "v"(uz),
                   [dx] "v"(dir.x), [dy] "v"(dir.y), [dz] "v"(dir.z), [below] "v"(slow_below), [desc] "s"(gb), [row] "s"(row_bytes), [slab] "s"(slab_bytes),

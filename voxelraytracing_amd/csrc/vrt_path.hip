@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
                 // four vector ones of control flow per step, its `marching` flag a register that is compared, counted and selected.
                 const uint32_t leave_at = next < n ? 64u - refill_at : 0u;   // leave when no more lanes than this still march
                 uint32_t t0, t1, t2, t3, u;
-                unsigned long long sx = __ballot(marching), sa;   // sx: the lanes that march, then — inside — the lanes the loop was entered with
+                unsigned long long sx = __ballot(marching), sa, fy, fz;   // sx: the lanes that march, then — inside — the lanes the loop was entered with
 // the lanes that march (exec is saved in the register that named them); the cell inside its line of 2 x 2 x 2 (bits 2 of x, y, z: [.. z2 y2 x2] in t0) ...
 #define VBM_HEAD \
                     "s_and_saveexec_b64 %[sx], %[sx]\n" \
@@ -373,6 +373,8 @@ __global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
 // one 16-byte load answers the step — behind it, while it is in flight: u = (x&3) | (y&3) << 2 | (z&3) << 4 under z's upper bits, the
 // shift that brings u's bit of .z .w to the top (does a ray pass the voxel?  the sign says), the position of the size-2 bit.  The lanes
 // that stop are off from there; the others: the selector (lo, or the size-2 bit of a split cell's voxel, under nine set bits), the step
+// (the axis selects: each compare writes flags of its own — vcc, %[fy], %[fz] — two instructions or more ahead of the v_cndmask that reads
+// them, the wait states a VALU's SGPR write needs before a VALU reads it; nothing pads inside the string: tests/test_isa_hazards.py)
 #define VBM_BODY \
                     "v_bitop3_b32 %[u], 3, %[vx], %[u] bitop3:0xca\n\t" \
                     "v_bitop3_b32 %[u], 15, %[u], %[t3] bitop3:0xca\n\t" \
@@ -404,21 +406,21 @@ __global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
                     "v_cmp_nlt_f32_e32 vcc, 0, %[st]\n\t" \
                     "s_cbranch_vccnz .Lvbm_zero_%=\n" \
                     ".Lvbm_move_%=:\n\t" \
-                    "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t" \
                     "v_cmp_eq_f32_e32 vcc, %[st], %[ax]\n\t" \
+                    "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t" \
+                    "v_cmp_eq_f32_e64 %[fy], %[st], %[ay]\n\t" \
+                    "v_cmp_eq_f32_e64 %[fz], %[st], %[az]\n\t" \
                     "v_cndmask_b32_e32 %[t1], %[st], %[t0], vcc\n\t" \
-                    "v_cmp_eq_f32_e32 vcc, %[st], %[ay]\n\t" \
-                    "v_cndmask_b32_e32 %[t2], %[st], %[t0], vcc\n\t" \
-                    "v_cmp_eq_f32_e32 vcc, %[st], %[az]\n\t" \
-                    "v_cndmask_b32_e32 %[t0], %[st], %[t0], vcc\n\t" \
                     "v_mul_f32_e32 %[t1], %[dx], %[t1]\n\t" \
+                    "v_cndmask_b32_e64 %[t2], %[st], %[t0], %[fy]\n\t" \
                     "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t" \
+                    "v_cndmask_b32_e64 %[t0], %[st], %[t0], %[fz]\n\t" \
                     "v_mul_f32_e32 %[t0], %[dz], %[t0]\n\t" \
                     "v_add_f32_e32 %[px], %[px], %[t1]\n\t" \
-                    "v_add_f32_e32 %[py], %[py], %[t2]\n\t" \
-                    "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t" \
                     "v_cvt_flr_i32_f32_e32 %[vx], %[px]\n\t" \
+                    "v_add_f32_e32 %[py], %[py], %[t2]\n\t" \
                     "v_cvt_flr_i32_f32_e32 %[vy], %[py]\n\t" \
+                    "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t" \
                     "v_cvt_flr_i32_f32_e32 %[vz], %[pz]\n\t" \
                     "v_cmp_lt_u32_e32 vcc, 0x1f3, %[it]\n\t" \
                     "s_cbranch_vccnz .Lvbm_out_%=\n\t" \
@@ -440,7 +442,7 @@ __global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
 #define VBM_OUTPUTS \
                     [px] "+v"(pos.x), [py] "+v"(pos.y), [pz] "+v"(pos.z), [vx] "+v"(vx), [vy] "+v"(vy), [vz] "+v"(vz), [st] "+v"(step), [ax] "+v"(adx), \
                     [ay] "+v"(ady), [az] "+v"(adz), [ref] "+v"(ref), [it] "+v"(iter), [t0] "=&v"(t0), \
-                    [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [u] "=&v"(u), [sx] "+s"(sx)
+                    [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [u] "=&v"(u), [sx] "+s"(sx), [fy] "=&s"(fy), [fz] "=&s"(fz)
 #define VBM_OUTPUTS_DIRECTORY , [ckey] "+v"(ckey), [cblock] "+v"(cblock), [sa] "=&s"(sa)
 #define VBM_INPUTS \
                     [mx] "v"(mxm), [my] "v"(mym), [mz] "v"(mzm), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [ux] "v"(ux), [uy] "v"(uy), [uz] "v"(uz), \
