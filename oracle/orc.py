@@ -82,6 +82,8 @@ def lib() -> C.CDLL:
         L.orc_render.restype = None
         L.orc_trace_pixel.argtypes = [C.POINTER(Scene), C.c_int, u32, u32, f32p, f32p, f32p]
         L.orc_trace_pixel.restype = u32
+        L.orc_trace_segments.argtypes = [C.POINTER(Scene), C.c_int, u32, u32, u32, u32, u32, u32, C.POINTER(u32), u32]
+        L.orc_trace_segments.restype = u32
         L.orc_ray_world.argtypes = [C.POINTER(Scene), f32p, f32p, f32p, f32p]
         L.orc_ray_world.restype = u32
         L.orc_get_node.argtypes = [vp, u32]
@@ -164,6 +166,14 @@ class OracleScene:
         rgb, d, out = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 8)()
         idw = lib().orc_trace_pixel(C.byref(self.c), mode, px, py, rgb, d, out)
         return idw, tuple(rgb), tuple(d), tuple(out)
+
+    def trace_segments(self, mode: int, px: int, py: int, w: int = 0, h: int = 0, sample: int = 0, seed: int = 0, cap: int = 16):
+        """Every segment the pixel's trace marches (primary, its shadow ray; or a path's segments, of sample `sample` of a w x h
+        frame rendered with `seed`): a list of dicts {steps, voxel, hit, solid, water, depth} — depth of the last lookup's leaf."""
+        out = (C.c_uint32 * (4 * cap))()
+        n = lib().orc_trace_segments(C.byref(self.c), mode, px, py, w, h, sample, seed, out, cap)
+        return [dict(steps=out[4 * i], voxel=out[4 * i + 1], hit=bool(out[4 * i + 2] & 1), solid=bool(out[4 * i + 2] & 2),
+                     water=bool(out[4 * i + 2] & 4), depth=out[4 * i + 3]) for i in range(min(n, cap))]
 
     def ray_world(self, origin, direction):
         col, out = (C.c_float * 3)(), (C.c_float * 8)()

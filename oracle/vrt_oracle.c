@@ -159,6 +159,7 @@ typedef struct {
     float water_dist;
     uint32_t voxel;
     uint32_t iter_count;
+    uint32_t last_depth; /* depth of the leaf of the last lookup (>= 4: inside a depth-3 cell that is split); not in the WGSL struct */
     uint64_t node_visits;
 } hit_result;
 
@@ -206,6 +207,7 @@ static hit_result ray_world(const orc_scene *s, v3 origin, v3 dir) {
         found_node fn = find_node(s, ray_pos, 5u);
         voxel = node_voxel(node_at(s, fn.root + fn.idx));
         result.node_visits += fn.depth + 1;
+        result.last_depth = fn.depth;
 
         int is_liquid = mat_at(s, voxel)->is_liquid == 1u;
 
@@ -581,8 +583,30 @@ typedef struct {
     int primary_hit;
 } path_result;
 
-/* ray_color, path_tracer.wgsl:149-194 (see the block comment above for the deliberate differences) */
+/* orc_trace_segments: where each segment of one pixel's trace ended (test infrastructure; NULL everywhere else) */
+typedef struct {
+    uint32_t *out;
+    uint32_t cap, n;
+} segment_sink;
+
+static void sink_put(segment_sink *k, const orc_scene *s, const hit_result *r) {
+    if (!k || k->n >= k->cap) return;
+    uint32_t *o = k->out + (size_t)k->n * 4u;
+    o[0] = r->iter_count;
+    o[1] = r->voxel;
+    o[2] = (r->hit ? 1u : 0u) | (is_solid_hit(s, r) ? 2u : 0u) | (r->water_dist != 0.0f ? 4u : 0u);
+    o[3] = r->last_depth;
+    k->n += 1u;
+}
+
+static path_result trace_path_into(const orc_scene *s, uint32_t px, uint32_t py, uint32_t rng, segment_sink *sink);
+
 static path_result trace_path(const orc_scene *s, uint32_t px, uint32_t py, uint32_t rng) {
+    return trace_path_into(s, px, py, rng, NULL);
+}
+
+/* ray_color, path_tracer.wgsl:149-194 (see the block comment above for the deliberate differences) */
+static path_result trace_path_into(const orc_scene *s, uint32_t px, uint32_t py, uint32_t rng, segment_sink *sink) {
     path_result pr;
     memset(&pr, 0, sizeof pr);
     v3 origin, dir;
@@ -590,6 +614,7 @@ static path_result trace_path(const orc_scene *s, uint32_t px, uint32_t py, uint
     v3 thr = V3(1.0f, 1.0f, 1.0f);
     for (uint32_t bounce = 0; bounce < s->settings.max_ray_bounces; bounce++) {
         hit_result rs = ray_world(s, origin, dir);
+        sink_put(sink, s, &rs);
         pr.segments += 1;
         pr.steps += rs.iter_count;
         pr.visits += rs.node_visits;
@@ -622,6 +647,23 @@ static path_result trace_path(const orc_scene *s, uint32_t px, uint32_t py, uint
 /* seed of sample s of pixel (px,py): path_tracer.wgsl:328 plus the per-sample stride of SURVEY §8d */
 static uint32_t path_seed(uint32_t px, uint32_t py, uint32_t w, uint32_t h, uint32_t sample, uint32_t seed) {
     return py * w + px + sample * (w * h) + seed * 0x9E3779B9u;
+}
+
+uint32_t orc_trace_segments(const orc_scene *scene, int mode, uint32_t px, uint32_t py, uint32_t w, uint32_t h,
+                            uint32_t sample, uint32_t seed, uint32_t *out, uint32_t cap) {
+    segment_sink k = {out, cap, 0u};
+    if (mode == ORC_MODE_PATH) {
+        trace_path_into(scene, px, py, path_seed(px, py, w, h, sample, seed), &k);
+        return k.n;
+    }
+    pixel_result pr = trace_pixel(scene, mode, px, py);
+    sink_put(&k, scene, &pr.prim);
+    if (pr.shadow_launched) {   /* the shadow ray again, as trace_pixel marched it */
+        hit_result sh;
+        shadow_ray(scene, &pr.prim, &sh);
+        sink_put(&k, scene, &sh);
+    }
+    return k.n;
 }
 
 uint32_t orc_trace_pixel(const orc_scene *scene, int mode, uint32_t px, uint32_t py,

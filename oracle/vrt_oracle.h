@@ -133,6 +133,13 @@ void orc_render(const orc_scene *scene, int mode, uint32_t w, uint32_t h,
 uint32_t orc_trace_pixel(const orc_scene *scene, int mode, uint32_t px, uint32_t py,
                          float *rgb, float *dir, float *out);
 
+/* Every segment one pixel's trace marches, in order — the primary ray, then its shadow ray (MODE_PRIMARY_SHADOW), or the
+ * path's segments (MODE_PATH: sample `sample` of a frame of w x h rendered with `seed`) — as out[4 * i ..] = {lookups,
+ * voxel of the last lookup, flags (1 hit, 2 stopped on a solid voxel, 4 water crossed), depth of the last lookup's leaf}.
+ * Returns the number of segments written (at most cap). */
+uint32_t orc_trace_segments(const orc_scene *scene, int mode, uint32_t px, uint32_t py, uint32_t w, uint32_t h,
+                            uint32_t sample, uint32_t seed, uint32_t *out, uint32_t cap);
+
 /* March one arbitrary ray (ray_world, ray_tracer.wgsl:182-316). origin is world-local.
  * out[8] as above. Returns the id word (without shadow bits). */
 uint32_t orc_ray_world(const orc_scene *scene, const float origin[3], const float dir[3],

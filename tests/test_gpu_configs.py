@@ -22,6 +22,13 @@ pytestmark = pytest.mark.gpu
 ID = g._ffi
 
 
+def _exhausted(sc, ids, steps):
+    """Pixels whose primary ray ran out of lookups: 500 of them and no solid voxel (the hit is on air or a liquid)."""
+    liquid = np.array([sc.materials[i].is_liquid for i in range(256)], dtype=bool)
+    voxel = np.minimum(ids & 0x7FFF, 255)
+    return int((((steps & 0xFFFF) == 500) & ((voxel == 0) | liquid[voxel])).sum())
+
+
 @pytest.fixture(scope="module")
 def c3():
     return scenes.c3()
@@ -51,6 +58,8 @@ def test_c3_full_size_matches_oracle(c3, c3_frame, orc):
         s = gpu.stats()
         assert (s.primary_rays, s.secondary_rays, s.hits, s.steps, s.node_visits) == \
                (st.primary_rays, st.secondary_rays, st.hits, st.steps, st.node_visits)
+    print(f"C3: {_exhausted(c3, r_ids, r_steps)} primary rays run out of lookups (500, no solid voxel); "
+          f"{int(((r_steps >> 16) == 500).sum())} shadow rays take 500 lookups")
     ai = gpu.accel_info()
     assert ai.available and ai.world_size_chunks == 16 and ai.cells == 128 ** 3
     # the timed kernels (no stats, frames in flight) give the same frame
@@ -164,8 +173,10 @@ def test_c5_full_size_bands_match_oracle(c5, orc):
     rgb, ids, _ = gpu.read_output()
     o = orc.from_package_scene(c5)
     for y0 in (200, 1072, 1900):
-        r_rgb, r_ids, _, _ = o.render(orc.MODE_PATH, 3840, 2160, rect=(0, y0, 3840, y0 + 16), spp=16, seed=3)
+        r_rgb, r_ids, r_steps, _ = o.render(orc.MODE_PATH, 3840, 2160, rect=(0, y0, 3840, y0 + 16), spp=16, seed=3, want_steps=True)
         assert_frame_parity(rgb[y0:y0 + 16], ids[y0:y0 + 16], r_rgb[y0:y0 + 16], r_ids[y0:y0 + 16], f"C5 rows {y0}..{y0 + 16}")
+        band = slice(y0, y0 + 16)
+        print(f"C5 rows {y0}..{y0 + 16}: {_exhausted(c5, r_ids[band], r_steps[band])} primary rays (sample 0) run out of lookups")
     gpu.close()
 
 

@@ -43,8 +43,9 @@ def _mix(a, b, t):
     return a * (F(1.0) - t) + b * t
 
 
-def render_primary(nodes_u16, chunk_roots, materials, cam, settings, world, w, h):
-    """-> rgb [h, w, 3] f32, id words [h, w] u32 (the oracle's layout: voxel | hit | normal axes | water), iterations [h, w]."""
+def render_primary(nodes_u16, chunk_roots, materials, cam, settings, world, w, h, max_steps=500):
+    """-> rgb [h, w, 3] f32, id words [h, w] u32 (the oracle's layout: voxel | hit | normal axes | water), iterations [h, w].
+    max_steps: the shader's limit (:220) is 500; a higher one tells where a ray that runs out would have stopped."""
     nodes_u16 = np.asarray(nodes_u16, dtype=np.uint16)
     # binding 6 is array<u32>: two 16-bit nodes per word, even index in the low half (:38-42; shader.rs:22-40 writes the
     # pool as little-endian u32 pairs)
@@ -105,7 +106,7 @@ def render_primary(nodes_u16, chunk_roots, materials, cam, settings, world, w, h
     total_len = np.zeros(n, dtype=F)
     iters = np.zeros(n, dtype=np.uint32)
     live = ~outside                                               # lanes still inside the while loop
-    for _ in range(500):                                          # :221
+    for _ in range(max_steps):                                    # :221
         a = np.flatnonzero(live)
         if a.size == 0:
             break
