@@ -149,6 +149,33 @@ pub struct vrt_accel_info {
     pub ordered_frames: u32,
 }
 
+/// One `common::math::cast_ray(start, dir, max_dist, ..)` query (vrt_cast_rays).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_ray_query {
+    pub start: [f32; 3],
+    pub max_dist: f32,
+    pub dir: [f32; 3],
+    pub _reserved: u32,
+}
+
+pub const VRT_RAY_MISS: u32 = 0;
+pub const VRT_RAY_HIT: u32 = 1;
+pub const VRT_RAY_REJECTED: u32 = 2;
+
+/// Its answer: `Option<HitResult>` as `status` (VRT_RAY_*) plus `pos` / `face`, and the DDA's `dist` at the hit.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_ray_hit {
+    pub pos: [i32; 3],
+    pub face: [i32; 3],
+    pub dist: f32,
+    pub status: u32,
+}
+
+const _: () = assert!(core::mem::size_of::<vrt_ray_query>() == 32);
+const _: () = assert!(core::mem::size_of::<vrt_ray_hit>() == 32);
+
 /// What issuing a frame costs the host (vrt_get_issue_profile), microseconds per vrt_render call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -208,6 +235,8 @@ extern "C" {
     pub fn vrt_shard_info(ctx: *mut vrt_ctx, tiles_local: *mut u32, tiles_padded: *mut u32, tiles_total: *mut u32) -> c_int;
     pub fn vrt_assemble(ctx: *mut vrt_ctx, gathered: *const c_void, rank_stride_bytes: u64, dst: *mut c_void) -> c_int;
     pub fn vrt_assemble_compact(ctx: *mut vrt_ctx, gathered: *const c_void, rank_stride_bytes: u64, dst: *mut c_void) -> c_int;
+    pub fn vrt_cast_rays(ctx: *mut vrt_ctx, queries: *const vrt_ray_query, n: u32, out: *mut vrt_ray_hit) -> c_int;
+    pub fn vrt_cast_rays_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
 }
 
 #[cfg(test)]

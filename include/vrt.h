@@ -370,6 +370,42 @@ int vrt_read_march_cells(vrt_ctx *ctx, uint32_t *cells, uint32_t *direct);
  * (main.rs:368-370, ray_tracer.wgsl:311-314). */
 int vrt_read_steps(vrt_ctx *ctx, uint32_t *steps);
 
+/* ---- world queries ---- */
+
+/* The client's voxel pick (clientdesktop/src/main.rs:320-325): common::math::cast_ray (common/src/math.rs:153-226) with
+ * collides(p) = world.get_voxel(p) is a non-empty voxel (client/src/world.rs:352-357), batched, one ray per lane, bit for bit.
+ * "Collides": p lies inside [min, min + 32 * size_in_chunks) of the context's vrt_world_data on every axis, its chunk's
+ * chunk_roots entry is not 0 (0 = no chunk) and the leaf find_node reaches there holds a voxel other than 0 (liquids collide).
+ * The DDA is the reference's in strict binary32, quirks included: a component of dir that is zero or -0 makes its unit step
+ * NaN or inf, ties take the y branch, a NaN or negative max_dist takes no step.  Where the reference would loop forever or
+ * overflow i32 the query is REJECTED instead of run: max_dist +inf or above 2^20, a start component that is not finite or
+ * whose magnitude is 2^24 or more.  Nothing else is rejected. */
+typedef struct {
+    float start[3];
+    float max_dist;
+    float dir[3];
+    uint32_t _reserved;
+} vrt_ray_query;  /* 32 B */
+
+#define VRT_RAY_MISS 0u
+#define VRT_RAY_HIT 1u
+#define VRT_RAY_REJECTED 2u
+typedef struct {
+    int32_t pos[3];   /* HitResult.pos: the voxel hit */
+    int32_t face[3];  /* HitResult.face: the voxel before it minus pos (the face the ray entered through) */
+    float dist;       /* the DDA's dist at the hit, inf included; a NaN is stored as 0x7FC00000 (f32::NAN: the sign and payload
+                       * of a NaN that a division makes are the platform's — x86 makes 0xFFC00000 — not the reference's) */
+    uint32_t status;  /* VRT_RAY_*; every other field is 0 for a miss or a rejected query */
+} vrt_ray_hit;  /* 32 B */
+
+/* n queries from host memory, n results into host memory.  Ordered on the context's stream (vrt_set_stream) behind every
+ * earlier call — a cast sees every vrt_write_* before it, with no frame in between — and waits for its own work only.  A cast
+ * changes nothing a frame left behind (vrt_read_output, vrt_present*, vrt_get_stats).  n = 0 does nothing.  A multi-device
+ * context casts on device_ids[0]. */
+int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *queries, uint32_t n, vrt_ray_hit *out);
+/* The same with device memory (n vrt_ray_query in, n vrt_ray_hit out, 4-byte aligned), asynchronous on the context's stream. */
+int vrt_cast_rays_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
+
 /* ---- device-side plumbing for a host that owns streams / device memory (torch, RCCL) ---- */
 
 /* Use the caller's hipStream_t for all subsequent work (NULL = the context's own stream). */

@@ -84,6 +84,13 @@ void vrth_std_materials(vrt_material *out256);
 /* Name of standard voxel id, or NULL */
 const char *vrth_std_voxel_name(uint32_t id);
 
+/* common::math::cast_ray (common/src/math.rs:153-226) over this world's get_voxel, as the client's pick calls it
+ * (clientdesktop/src/main.rs:320-325), in strict binary32: the CPU twin of vrt_cast_rays (include/vrt.h), with the same
+ * rejection rule and the same result record.  Returns out->status. */
+int vrth_world_cast_ray(const vrth_world *w, const float start[3], const float dir[3], float max_dist, vrt_ray_hit *out);
+/* n of them; threads <= 0: all cores.  The world must not change meanwhile. */
+void vrth_world_cast_rays(const vrth_world *w, const vrt_ray_query *queries, uint32_t n, vrt_ray_hit *out, int threads);
+
 /* ---- SVO construction ---- */
 /* Svo::set_node driven the way server/src/world/gen.rs:171-286 drives it (x, z, y ascending, air
  * skipped) from dense[x + 32*(y + 32*z)]. Returns nodes in use (last_used_addr + 1), 0 on OOM. */

@@ -12,6 +12,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -81,7 +83,25 @@ class IssueProfile(C.Structure):
                 ("join_wait_us", C.c_double), ("tail_us", C.c_double), ("message_waits_us", C.c_double)]
 
 
+class RayQuery(C.Structure):
+    """include/vrt.h vrt_ray_query: common::math::cast_ray's arguments (common/src/math.rs:153-158)"""
+    _fields_ = [("start", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("_reserved", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    """include/vrt.h vrt_ray_hit: Option<HitResult> (math.rs:148-152) plus the DDA's dist and a status"""
+    _fields_ = [("pos", C.c_int32 * 3), ("face", C.c_int32 * 3), ("dist", C.c_float), ("status", C.c_uint32)]
+
+
+RAY_MISS, RAY_HIT, RAY_REJECTED = 0, 1, 2
+# the same records as numpy structured dtypes (32 bytes each)
+RAY_QUERY_DTYPE = np.dtype([("start", "<f4", 3), ("max_dist", "<f4"), ("dir", "<f4", 3), ("_reserved", "<u4")])
+RAY_HIT_DTYPE = np.dtype([("pos", "<i4", 3), ("face", "<i4", 3), ("dist", "<f4"), ("status", "<u4")])
+
+
 assert C.sizeof(Material) == 32 and C.sizeof(CamData) == 160
+assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 32
+assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
@@ -125,6 +145,8 @@ VRT_SYMBOLS = {
     "vrt_shard_info": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrt_assemble": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "vrt_assemble_compact": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "vrt_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_cast_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
 }
 
 
@@ -247,6 +269,8 @@ VRTH_SYMBOLS = {
     "vrth_world_chunk_state": (C.c_int, [_P, _I32P, _U32P, _U32P, _U32P, _P, C.c_uint32]),
     "vrth_world_highest_vox_at": (C.c_int, [_P, C.c_int32, C.c_int32, _I32P]),
     "vrth_world_data_from": (None, [_P, C.POINTER(WorldData)]),
+    "vrth_world_cast_ray": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(RayHit)]),
+    "vrth_world_cast_rays": (None, [_P, _P, C.c_uint32, _P, C.c_int]),
     "vrth_cam_data_create": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(CamData)]),
     "vrth_axis_rot_to_ray": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vrth_std_materials": (None, [_P]),

@@ -1,5 +1,7 @@
 // host_capi.cpp — include/vrt_host.h over the C++ host mirror (world.hpp, graphics.hpp, worldgen.hpp).
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <atomic>
 #include <system_error>
 #include <thread>
@@ -59,6 +61,101 @@ int vrth_world_get_voxel(const vrth_world *w, const int32_t p[3], uint16_t *voxe
     const SetVoxelErr e = w->w.get_voxel(cp3(p), v);
     if (e == SetVoxelErr::Ok && voxel_out) *voxel_out = v.as_data();
     return (int)e;
+}
+
+// common::math::cast_ray, common/src/math.rs:153-226, with the client's collides (clientdesktop/src/main.rs:320-325).  This file is
+// built with -ffp-contract=off (Makefile): every float operation below is one correctly rounded binary32 operation, in the order
+// the reference writes it.
+int vrth_world_cast_ray(const vrth_world *w, const float start[3], const float dir[3], float max_dist, vrt_ray_hit *out) {
+    vrt_ray_hit r;
+    memset(&r, 0, sizeof r);
+    // The reference loops forever on max_dist = inf, and start.floor().as_ivec3() / map_check += step leave i32 (or the exact
+    // integers of f32) beyond 2^24: such a query is rejected, not run (include/vrt.h).
+    if (max_dist > 1048576.0f || !(std::fabs(start[0]) < 16777216.0f) || !(std::fabs(start[1]) < 16777216.0f) ||
+        !(std::fabs(start[2]) < 16777216.0f)) {
+        r.status = VRT_RAY_REJECTED;
+        if (out) *out = r;
+        return (int)r.status;
+    }
+    const float dx = dir[0], dy = dir[1], dz = dir[2];
+    const float usx = std::sqrt(1.0f + (dy / dx) * (dy / dx) + (dz / dx) * (dz / dx));
+    const float usy = std::sqrt(1.0f + (dx / dy) * (dx / dy) + (dz / dy) * (dz / dy));
+    const float usz = std::sqrt(1.0f + (dx / dz) * (dx / dz) + (dy / dz) * (dy / dz));
+    int32_t m[3] = {(int32_t)std::floor(start[0]), (int32_t)std::floor(start[1]), (int32_t)std::floor(start[2])};
+    int32_t step[3];
+    float len[3];
+    const float us[3] = {usx, usy, usz};
+    for (int a = 0; a < 3; a++) {
+        if (dir[a] < 0.0f) {
+            step[a] = -1;
+            len[a] = (start[a] - (float)m[a]) * us[a];
+        } else {
+            step[a] = 1;
+            len[a] = ((float)(m[a] + 1) - start[a]) * us[a];
+        }
+    }
+    const VoxelPos lo = w->w.min_voxel(), hi = w->w.max_voxel();
+    const int32_t lo3[3] = {lo.x, lo.y, lo.z}, hi3[3] = {hi.x, hi.y, hi.z};
+    float dist = 0.0f;
+    while (dist < max_dist) {
+        const int32_t prev[3] = {m[0], m[1], m[2]};
+        if (len[0] < len[1] && len[0] < len[2]) {
+            m[0] += step[0];
+            dist = len[0];
+            len[0] += usx;
+        } else if (len[2] < len[0] && len[2] < len[1]) {
+            m[2] += step[2];
+            dist = len[2];
+            len[2] += usz;
+        } else {
+            m[1] += step[1];
+            dist = len[1];
+            len[1] += usy;
+        }
+        Voxel v;
+        if (w->w.get_voxel(VoxelPos{m[0], m[1], m[2]}, v) == SetVoxelErr::Ok && !v.is_empty()) {
+            r.pos[0] = m[0]; r.pos[1] = m[1]; r.pos[2] = m[2];
+            r.face[0] = prev[0] - m[0]; r.face[1] = prev[1] - m[1]; r.face[2] = prev[2] - m[2];
+            r.dist = dist == dist ? dist : NAN;   // (one NaN for every platform: include/vrt.h)
+            r.status = VRT_RAY_HIT;
+            break;
+        }
+        // Not in the reference, and no change to any result: an axis moves only by its own step, so a voxel outside the world
+        // on an axis whose step leads away from it is followed by voxels outside on that axis, none of which collides.  (The
+        // x and z branches need len < the others: a len that is NaN or inf never takes them, that axis never moves at all.)
+        bool gone = false;
+        for (int a = 0; a < 3; a++) {
+            const bool below = m[a] < lo3[a], above = m[a] >= hi3[a];
+            const bool frozen = a != 1 && !(len[a] < INFINITY);
+            gone = gone || (below && (step[a] < 0 || frozen)) || (above && (step[a] > 0 || frozen));
+        }
+        if (gone) break;
+    }
+    if (out) *out = r;
+    return (int)r.status;
+}
+
+void vrth_world_cast_rays(const vrth_world *w, const vrt_ray_query *q, uint32_t n, vrt_ray_hit *out, int threads) {
+    if (!w || !q || !out || !n) return;
+    unsigned nt = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+    nt = (unsigned)std::min<uint64_t>(nt, (n + 1023u) / 1024u);
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (;;) {
+            const uint32_t i0 = next.fetch_add(1024u);
+            if (i0 >= n) return;
+            const uint32_t i1 = std::min<uint64_t>((uint64_t)i0 + 1024u, n);
+            for (uint32_t i = i0; i < i1; i++) vrth_world_cast_ray(w, q[i].start, q[i].dir, q[i].max_dist, &out[i]);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
+    } catch (const std::system_error &) {
+        // no more threads to be had: the ones that started (and this one) do the work
+    }
+    work();
+    for (auto &t : pool) t.join();
 }
 
 uint32_t vrth_world_center_chunks(vrth_world *w, const int32_t anchor_chunk[3]) {

@@ -319,6 +319,11 @@ struct vrt_ctx {
     uint32_t ndc_w = 0, ndc_h = 0;
     float ndc_proj[2] = {0.f, 0.f};
 
+    // vrt_cast_rays (vrt_cast.hip): the device copy of a host batch, queries then results, for cast_cap rays
+    void *d_cast = nullptr;
+    uint32_t cast_cap = 0;
+    hipEvent_t ev_cast = nullptr;
+
     vrt_material h_mats[256];
     uint32_t liquid_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit v <=> h_mats[v].is_liquid == 1 (kept by vrt_write_materials)
     bool liquid_is_range = true;                          // the liquid ids are one range below 255, or none

@@ -249,6 +249,21 @@ class Gpu:
         fn = self._lib.vrt_assemble_compact if compact else self._lib.vrt_assemble
         self._ck(fn(self._h, C.c_void_p(gathered_ptr), rank_stride_bytes, C.c_void_p(dst_ptr)))
 
+    # --- world queries (include/vrt.h vrt_cast_rays) ---
+    def cast_rays(self, starts, dirs, max_dist) -> np.ndarray:
+        """common::math::cast_ray (math.rs:153-226) for every ray at once on the GPU, against the world as of every write so far:
+        (n,3) starts and dirs, a scalar or (n,) max_dist.  Returns _ffi.RAY_HIT_DTYPE records (pos, face, dist, status)."""
+        from .world import ray_queries
+        q = ray_queries(starts, dirs, max_dist)
+        out = np.zeros(q.size, _ffi.RAY_HIT_DTYPE)
+        self._ck(self._lib.vrt_cast_rays(self._h, q.ctypes.data, q.size, out.ctypes.data))
+        return out
+
+    def cast_rays_device(self, queries_ptr: int, n: int, out_ptr: int):
+        """vrt_cast_rays_device: n vrt_ray_query records at a device address in, n vrt_ray_hit records out, enqueued on the
+        context's stream (vrt_set_stream) without waiting."""
+        self._ck(self._lib.vrt_cast_rays_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
+
     # --- convenience: what join_game does (main.rs:211-223) ---
     def upload_world(self, world, materials=None):
         """Upload the whole pool, chunk_roots, WorldData and materials of a ClientWorld."""

@@ -109,6 +109,33 @@ class ClientWorld:
             raise SetVoxelErr(rc)
         return v.value
 
+    def cast_ray(self, start, dir, max_dist: float):
+        """common::math::cast_ray(start, dir, max_dist, |p| get_voxel(p) is solid) — math.rs:153-226, as the client's pick calls
+        it (clientdesktop/src/main.rs:320-325): None, or (pos, face) like Option<HitResult>.  Strict binary32 (vrth_world_cast_ray);
+        a query the reference would loop forever or overflow on (include/vrt.h) raises ValueError."""
+        h = self.cast_ray_record(start, dir, max_dist)
+        if h.status == _ffi.RAY_REJECTED:
+            raise ValueError(f"cast_ray rejected: start {tuple(start)} / max_dist {max_dist} (|start| < 2^24, max_dist <= 2^20)")
+        if h.status != _ffi.RAY_HIT:
+            return None
+        return tuple(h.pos), tuple(h.face)
+
+    def cast_ray_record(self, start, dir, max_dist: float) -> _ffi.RayHit:
+        """The same as the whole vrt_ray_hit record (the DDA's dist and the status included)."""
+        out = _ffi.RayHit()
+        self._lib.vrth_world_cast_ray(self._h, (C.c_float * 3)(*[float(v) for v in start]), (C.c_float * 3)(*[float(v) for v in dir]),
+                                      float(max_dist), C.byref(out))
+        return out
+
+    def cast_rays(self, starts, dirs, max_dist, threads: int = 0) -> np.ndarray:
+        """Many casts on the CPU (vrth_world_cast_rays): (n,3) starts and dirs, a scalar or (n,) max_dist; returns the
+        _ffi.RAY_HIT_DTYPE records."""
+        q = ray_queries(starts, dirs, max_dist)
+        out = np.zeros(q.size, _ffi.RAY_HIT_DTYPE)
+        if q.size:
+            self._lib.vrth_world_cast_rays(self._h, q.ctypes.data, q.size, out.ctypes.data, threads)
+        return out
+
     def center_chunks(self, anchor) -> int:
         return self._lib.vrth_world_center_chunks(self._h, _i3(anchor))
 
@@ -253,6 +280,19 @@ class ClientWorld:
 
 
 # ---- SVO construction helpers (server/src/world/gen.rs:171-286 and the build's bottom-up builder) ----
+
+def ray_queries(starts, dirs, max_dist) -> np.ndarray:
+    """vrt_ray_query records (_ffi.RAY_QUERY_DTYPE) from (n,3) starts and dirs and a scalar or (n,) max_dist, all as float32."""
+    starts = np.asarray(starts, np.float32).reshape(-1, 3)
+    dirs = np.asarray(dirs, np.float32).reshape(-1, 3)
+    if starts.shape != dirs.shape:
+        raise ValueError(f"starts {starts.shape} and dirs {dirs.shape} differ")
+    q = np.zeros(starts.shape[0], _ffi.RAY_QUERY_DTYPE)
+    q["start"] = starts
+    q["dir"] = dirs
+    q["max_dist"] = np.broadcast_to(np.asarray(max_dist, np.float32), (starts.shape[0],))
+    return q
+
 
 def svo_build_by_set_node(dense: np.ndarray, cap: int = NODES_PER_CHUNK + 64) -> np.ndarray:
     dense = np.ascontiguousarray(dense, dtype=np.uint16).reshape(-1)
