@@ -237,6 +237,9 @@ extern "C" {
     pub fn vrt_assemble_compact(ctx: *mut vrt_ctx, gathered: *const c_void, rank_stride_bytes: u64, dst: *mut c_void) -> c_int;
     pub fn vrt_cast_rays(ctx: *mut vrt_ctx, queries: *const vrt_ray_query, n: u32, out: *mut vrt_ray_hit) -> c_int;
     pub fn vrt_cast_rays_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
+    pub fn vrt_generate_chunks(ctx: *mut vrt_ctx, seed: u32, chunk_pos: *const i32, n: u32, nodes: *mut u16, cap_nodes: u64,
+                               offsets: *mut u64) -> c_int;
+    pub fn vrt_build_chunks(ctx: *mut vrt_ctx, dense: *const u16, n: u32, nodes: *mut u16, cap_nodes: u64, offsets: *mut u64) -> c_int;
 }
 
 #[cfg(test)]

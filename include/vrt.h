@@ -406,6 +406,28 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *queries, uint32_t n, vrt_ra
 /* The same with device memory (n vrt_ray_query in, n vrt_ray_hit out, 4-byte aligned), asynchronous on the context's stream. */
 int vrt_cast_rays_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
 
+/* ---- the chunk source: world generation on the device ---- */
+
+/* What the server answers request_missing_chunks with (client/src/lib.rs:80-118: GiveChunkData -> create_chunk), built on
+ * the device.  The specification is the host generator, csrc/host/worldgen.hpp: chunk i's nodes are, word for word,
+ * build_svo_bottom_up(WorldGen{seed}.fill_dense(chunk_pos[i])) — vrth_svo_build_bottom_up(vrth_gen_dense(seed, pos)) of
+ * include/vrt_host.h; a uniform chunk is its one node.  chunk_pos: n x int32[3], every coordinate in (-2^26, 2^26) (fill_dense
+ * computes pos * 32 in int32), else VRT_ERR_INVALID_ARG before any work.  nodes: cap_nodes u16 words; offsets: n + 1 entries,
+ * chunk i's nodes are nodes[offsets[i] .. offsets[i+1]).
+ *  - n = 0: offsets[0] = 0, VRT_OK.
+ *  - A chunk whose tree build_svo_bottom_up refuses (4096 mixed cells or more: a node index past 32767) gets an empty range; the
+ *    others are still produced, and the call returns VRT_ERR_OUT_OF_RANGE.
+ *  - cap_nodes too small: VRT_ERR_OOM with every offset written (offsets[n] = the words needed) and nodes untouched.
+ * Runs on the context's stream behind every earlier call, in batches of 2048 chunks, and waits for its own results.  It touches
+ * nothing else of the context: the node pool, chunk_roots, the derived tables and frames in flight stay as they are — the ranges
+ * go to the pool through create_chunk on the host and vrt_write_nodes, as the reference's flow has it.  A
+ * multi-device context generates on device_ids[0]. */
+int vrt_generate_chunks(vrt_ctx *ctx, uint32_t seed, const int32_t *chunk_pos, uint32_t n, uint16_t *nodes, uint64_t cap_nodes,
+                        uint64_t *offsets);
+/* The builder alone: n caller blocks dense[x + 32*(y + 32*z)] (n x 32768 u16, any id 0..0xFFFF) -> their nodes, word for word
+ * vrth_svo_build_bottom_up.  Results and errors as vrt_generate_chunks's. */
+int vrt_build_chunks(vrt_ctx *ctx, const uint16_t *dense, uint32_t n, uint16_t *nodes, uint64_t cap_nodes, uint64_t *offsets);
+
 /* ---- device-side plumbing for a host that owns streams / device memory (torch, RCCL) ---- */
 
 /* Use the caller's hipStream_t for all subsequent work (NULL = the context's own stream). */

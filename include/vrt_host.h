@@ -113,6 +113,14 @@ int vrth_world_generate(vrth_world *w, uint32_t kind, uint32_t seed, int threads
  * at most cap pairs are written), *n_ranges = how many were created — the ranges to hand to vrt_write_nodes
  * (main.rs:289-295).  All-air chunks stay empty cells. */
 int vrth_world_generate_missing(vrth_world *w, uint32_t kind, uint32_t seed, int threads, uint32_t *ranges, uint32_t cap, uint32_t *n_ranges);
+/* create_chunk for each chunk i in the given order, from nodes[offsets[i] .. offsets[i+1]) (n x int32[3] positions, n + 1
+ * offsets: vrt_generate_chunks's output, include/vrt.h); a chunk that is exactly one node of word 0 (all air) is skipped, as
+ * vrth_world_generate skips it; ranges as vrth_world_generate_missing's.  An empty range anywhere (a chunk the builder refused)
+ * returns 2 (OutOfMemory, as vrth_world_generate returns for it) before anything is created; other errors are create_chunk's.
+ * Fed the nodes of the grid's cells (or of its empty cells) in grid order, it makes what vrth_world_generate (or
+ * vrth_world_generate_missing) makes with kind 0, byte for byte. */
+int vrth_world_create_chunks(vrth_world *w, const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes, const uint64_t *offsets,
+                             uint32_t *ranges, uint32_t cap, uint32_t *n_ranges);
 
 /* ---- region files of the reference server (servercli/src/main.rs:25-73; format in csrc/host/regionfile.hpp) ---- */
 /* Parse one `regions/r_X_Y_Z_.data` image and create_chunk every chunk of it that lies inside the world's grid.

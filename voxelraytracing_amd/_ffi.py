@@ -105,6 +105,8 @@ assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
+# include/vrt.h vrt_status
+VRT_OK, VRT_ERR_INVALID_ARG, VRT_ERR_OUT_OF_RANGE, VRT_ERR_DEVICE, VRT_ERR_OOM, VRT_ERR_STATE = 0, -1, -2, -3, -4, -5
 
 ID_VOXEL_MASK = 0x7FFF
 ID_HIT, ID_NX, ID_NY, ID_NZ = 1 << 16, 1 << 17, 1 << 18, 1 << 19
@@ -147,6 +149,8 @@ VRT_SYMBOLS = {
     "vrt_assemble_compact": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "vrt_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_cast_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_generate_chunks": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P]),
+    "vrt_build_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P]),
 }
 
 
@@ -271,6 +275,7 @@ VRTH_SYMBOLS = {
     "vrth_world_data_from": (None, [_P, C.POINTER(WorldData)]),
     "vrth_world_cast_ray": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(RayHit)]),
     "vrth_world_cast_rays": (None, [_P, _P, C.c_uint32, _P, C.c_int]),
+    "vrth_world_create_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _U32P]),
     "vrth_cam_data_create": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(CamData)]),
     "vrth_axis_rot_to_ray": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vrth_std_materials": (None, [_P]),

@@ -355,6 +355,31 @@ int vrth_world_generate_missing(vrth_world *w, uint32_t kind, uint32_t seed, int
     return generate_impl(w, kind, seed, threads, true, ranges, cap, n_ranges);
 }
 
+// The other half of generate_impl, for nodes built elsewhere (vrt_generate_chunks): create_chunk in the order given, all-air
+// chunks skipped, ranges as above.  A refused chunk (an empty range) fails the whole call first, as generate_impl's builder does.
+int vrth_world_create_chunks(vrth_world *w, const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes, const uint64_t *offsets,
+                             uint32_t *ranges, uint32_t cap, uint32_t *n_ranges) {
+    if (n_ranges) *n_ranges = 0;
+    if (n == 0) return 0;
+    for (uint32_t i = 0; i < n; i++)
+        if (offsets[i + 1] <= offsets[i]) return (int)SetVoxelErr::OutOfMemory;
+    const Node *src = reinterpret_cast<const Node *>(nodes);
+    uint32_t count = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t cnt = offsets[i + 1] - offsets[i];
+        const Node *c = src + offsets[i];
+        if (cnt == 1 && c[0].w == 0) continue;
+        if (cnt > 0xFFFFFFFFull) return (int)SetVoxelErr::BadChunkData;
+        SetVoxelErr err;
+        const NodeAddr root = w->w.create_chunk(cp3(chunk_pos + 3ull * i), c, (uint32_t)cnt, err);
+        if (err != SetVoxelErr::Ok) return (int)err;
+        if (ranges && count < cap) { ranges[2 * count] = root; ranges[2 * count + 1] = (uint32_t)cnt; }
+        count++;
+    }
+    if (n_ranges) *n_ranges = count;
+    return 0;
+}
+
 
 // ---- region files (servercli/src/main.rs:25-73) ----
 

@@ -324,6 +324,16 @@ struct vrt_ctx {
     uint32_t cast_cap = 0;
     hipEvent_t ev_cast = nullptr;
 
+    // vrt_generate_chunks / vrt_build_chunks (vrt_gen.hip): one batch's staging slots, node counts, offsets and inputs (made on
+    // first use), and the compacted nodes of a whole call (grown as needed)
+    uint16_t *d_gen_stage = nullptr;
+    uint32_t *d_gen_counts = nullptr;
+    uint64_t *d_gen_offs = nullptr;
+    int32_t *d_gen_pos = nullptr;
+    uint16_t *d_gen_dense = nullptr;
+    uint16_t *d_gen_out = nullptr;
+    uint64_t gen_out_cap = 0;
+
     vrt_material h_mats[256];
     uint32_t liquid_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit v <=> h_mats[v].is_liquid == 1 (kept by vrt_write_materials)
     bool liquid_is_range = true;                          // the liquid ids are one range below 255, or none

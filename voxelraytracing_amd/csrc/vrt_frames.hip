@@ -604,6 +604,8 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->d_blk_counts); (void)hipFree(c->d_clock);
     (void)hipFree(c->d_cast);
     if (c->ev_cast) (void)hipEventDestroy(c->ev_cast);
+    (void)hipFree(c->d_gen_stage); (void)hipFree(c->d_gen_counts); (void)hipFree(c->d_gen_offs); (void)hipFree(c->d_gen_pos);
+    (void)hipFree(c->d_gen_dense); (void)hipFree(c->d_gen_out);
     for (auto &T : c->tabs) {
         (void)free_tables(c, T);
         if (T.ev_updated) (void)hipEventDestroy(T.ev_updated);

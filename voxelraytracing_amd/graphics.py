@@ -264,6 +264,33 @@ class Gpu:
         context's stream (vrt_set_stream) without waiting."""
         self._ck(self._lib.vrt_cast_rays_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
 
+    # --- the chunk source (include/vrt.h vrt_generate_chunks / vrt_build_chunks) ---
+    def generate_chunks(self, seed: int, positions, strict: bool = True):
+        """The build's world generator on the GPU (csrc/host/worldgen.hpp): (n,3) chunk positions -> (nodes, offsets), chunk i's
+        nodes being nodes[offsets[i]:offsets[i+1]], word for word svo_build_bottom_up(gen_dense(seed, pos)).  A chunk whose tree
+        the builder refuses has an empty range; strict=True raises VrtError for it (VRT_ERR_OUT_OF_RANGE), strict=False
+        returns the other chunks' nodes."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        return self._chunks(lambda nodes, cap, offs: self._lib.vrt_generate_chunks(
+            self._h, seed & 0xFFFFFFFF, pos.ctypes.data, pos.shape[0], nodes, cap, offs), pos.shape[0], strict)
+
+    def build_chunks(self, dense, strict: bool = True):
+        """build_svo_bottom_up on the GPU for (n, 32768) u16 blocks, dense[x + 32*(y + 32*z)]: (nodes, offsets) as generate_chunks."""
+        d = np.ascontiguousarray(np.asarray(dense, np.uint16).reshape(-1, 32768))
+        return self._chunks(lambda nodes, cap, offs: self._lib.vrt_build_chunks(self._h, d.ctypes.data, d.shape[0], nodes, cap, offs),
+                            d.shape[0], strict)
+
+    def _chunks(self, call, n: int, strict: bool):
+        offs = np.zeros(n + 1, np.uint64)
+        nodes = np.empty(max(1, 2048 * n), np.uint16)   # a guess (a generated chunk averages ~1 000 nodes); OOM tells the need
+        rc = call(nodes.ctypes.data, nodes.size, offs.ctypes.data)
+        if rc == _ffi.VRT_ERR_OOM and int(offs[n]) > nodes.size:
+            nodes = np.empty(int(offs[n]), np.uint16)
+            rc = call(nodes.ctypes.data, nodes.size, offs.ctypes.data)
+        if rc and not (rc == _ffi.VRT_ERR_OUT_OF_RANGE and not strict):
+            self._ck(rc)
+        return nodes[:int(offs[n])].copy(), offs
+
     # --- convenience: what join_game does (main.rs:211-223) ---
     def upload_world(self, world, materials=None):
         """Upload the whole pool, chunk_roots, WorldData and materials of a ClientWorld."""

@@ -142,14 +142,22 @@ class ClientWorld:
     def resize(self, size: int) -> None:
         self._lib.vrth_world_resize(self._h, size)
 
-    def generate(self, kind: int = 0, seed: int = 1, threads: int = 0) -> None:
+    def generate(self, kind: int = 0, seed: int = 1, threads: int = 0, gpu=None) -> None:
+        """Every cell of the grid.  gpu: a Gpu that builds the chunks (kind 0 only; Gpu.generate_chunks), then create_chunks —
+        the same world as the CPU path, byte for byte."""
+        if gpu is not None:
+            self._generate_on(gpu, kind, seed, self.grid_positions())
+            return
         rc = self._lib.vrth_world_generate(self._h, kind, seed, threads)
         if rc:
             raise SetVoxelErr(rc)
 
-    def generate_missing(self, kind: int = 0, seed: int = 1, threads: int = 0) -> np.ndarray:
+    def generate_missing(self, kind: int = 0, seed: int = 1, threads: int = 0, gpu=None) -> np.ndarray:
         """Fill the grid's empty cells (what the server answers request_missing_chunks with, client/src/lib.rs:80-108).
-        -> u32[n, 2] of (root, node count): the ranges to upload, as GameState::process_cmd returns them."""
+        -> u32[n, 2] of (root, node count): the ranges to upload, as GameState::process_cmd returns them.  gpu: as generate's."""
+        if gpu is not None:
+            pos = self.grid_positions()
+            return self._generate_on(gpu, kind, seed, pos[self.chunk_roots() == 0])
         cap = self.size_in_chunks() ** 3
         out = np.zeros((cap, 2), dtype=np.uint32)
         n = C.c_uint32()
@@ -157,6 +165,36 @@ class ClientWorld:
         if rc:
             raise SetVoxelErr(rc)
         return out[:n.value].copy()
+
+    def create_chunks(self, positions, nodes: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        """create_chunk(positions[i], nodes[offsets[i]:offsets[i+1]]) in order, all-air chunks skipped (vrth_world_create_chunks):
+        -> u32[n, 2] of (root, node count) of the chunks created, as generate_missing returns them."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint16)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = pos.shape[0]
+        if offsets.size != n + 1 or (n and int(offsets[n]) > nodes.size):
+            raise ValueError(f"{n} positions need {n + 1} offsets within the {nodes.size} nodes")
+        out = np.zeros((max(n, 1), 2), dtype=np.uint32)
+        cnt = C.c_uint32()
+        rc = self._lib.vrth_world_create_chunks(self._h, pos.ctypes.data, n, nodes.ctypes.data, offsets.ctypes.data,
+                                                out.ctypes.data, n, C.byref(cnt))
+        if rc:
+            raise SetVoxelErr(rc)
+        return out[:cnt.value].copy()
+
+    def grid_positions(self) -> np.ndarray:
+        """The chunk position of every cell of the grid, (S^3, 3) int32 in grid order (x fastest), as chunk_roots() lists them."""
+        S = self.size_in_chunks()
+        mn = np.asarray(self.min_voxel(), np.int64) // CHUNK_SIZE
+        i = np.arange(S ** 3, dtype=np.int64)
+        return np.stack([mn[0] + i % S, mn[1] + (i // S) % S, mn[2] + i // (S * S)], axis=1).astype(np.int32)
+
+    def _generate_on(self, gpu, kind: int, seed: int, positions) -> np.ndarray:
+        if kind != 0:
+            raise ValueError(f"generate kind {kind} on the GPU: only kind 0 (the procedural generator) is built there")
+        nodes, offs = gpu.generate_chunks(seed, positions, strict=False)
+        return self.create_chunks(positions, nodes, offs)   # (a refused chunk: SetVoxelErr OutOfMemory, as the CPU path)
 
     # --- views ---
     def nodes(self) -> np.ndarray:
