@@ -101,6 +101,7 @@ pub const VRT_MODE_PATH: u32 = 2;
 
 pub const VRT_RENDER_OWN_STREAMS: u32 = 1;
 pub const VRT_RENDER_TIMED: u32 = 2;
+pub const VRT_RENDER_ACCUMULATE: u32 = 4;
 
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -217,6 +218,8 @@ extern "C" {
     pub fn vrt_resize_output(ctx: *mut vrt_ctx, width: u32, height: u32) -> c_int;
     pub fn vrt_render(ctx: *mut vrt_ctx, opts: *const vrt_render_opts) -> c_int;
     pub fn vrt_set_frames_in_flight(ctx: *mut vrt_ctx, n: u32) -> c_int;
+    pub fn vrt_reset_accumulation(ctx: *mut vrt_ctx) -> c_int;
+    pub fn vrt_get_accumulation(ctx: *mut vrt_ctx, samples: *mut u32, seed: *mut u32) -> c_int;
     pub fn vrt_synchronize(ctx: *mut vrt_ctx) -> c_int;
     pub fn vrt_read_output(ctx: *mut vrt_ctx, rgb: *mut f32, ids: *mut u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_present(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8: *mut u8) -> c_int;

@@ -167,6 +167,15 @@ typedef struct {
 /* This frame's launches carry timing events (vrt_stats.frames / sum_ms_*) whatever the context's sampling of plain frames
  * is (every 8th: a launch with events costs the host three times one without). */
 #define VRT_RENDER_TIMED 2u
+/* VRT_MODE_PATH only (any other mode: VRT_ERR_INVALID_ARG, nothing enqueued): progressive accumulation.  With n samples
+ * accumulated so far the frame traces samples n .. n + spp - 1, adds them in sample order to the context's running sum
+ * (never divided) and stores sum / (n + spp) in its output texels, with the id word a plain path frame writes: K frames of
+ * s spp are, bit for bit, one frame of K * s spp with the same seed.  The sum starts again at n = 0 (without a device
+ * step: the first frame stores it) after vrt_reset_accumulation, or when anything the image depends on has changed since
+ * the previous accumulating frame: the camera, settings or world (byte-wise), any vrt_write_materials, a non-empty
+ * vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
+ * Non-accumulating frames in between change nothing.  n + spp > 2^24: VRT_ERR_OUT_OF_RANGE, nothing enqueued. */
+#define VRT_RENDER_ACCUMULATE 4u
 
 /* New relative to the reference (it presents to a swapchain and never reads back). */
 typedef struct {
@@ -255,6 +264,12 @@ int vrt_render(vrt_ctx *ctx, const vrt_render_opts *opts);
  * stops asking.  Any other change of the view returns to screen order.  The frame is the same whatever the order;
  * VRT_TILE_ORDER=0 keeps screen order always, VRT_TILE_ORDER_MOVING=0 while the camera moves (profiles/r05_tile_order_moving.txt). */
 int vrt_set_frames_in_flight(vrt_ctx *ctx, uint32_t n);
+
+/* VRT_RENDER_ACCUMULATE: the next accumulating frame starts again at n = 0. */
+int vrt_reset_accumulation(vrt_ctx *ctx);
+/* VRT_RENDER_ACCUMULATE: the samples in the last accumulating frame's mean (0 before the first) and its seed.  Host-side
+ * state: never synchronises.  Either pointer may be NULL. */
+int vrt_get_accumulation(vrt_ctx *ctx, uint32_t *samples, uint32_t *seed);
 
 /* Block until everything enqueued on the context's stream has finished. */
 int vrt_synchronize(vrt_ctx *ctx);

@@ -105,6 +105,7 @@ assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
+RENDER_OWN_STREAMS, RENDER_TIMED, RENDER_ACCUMULATE = 1, 2, 4   # vrt_render_opts.flags (VRT_RENDER_*)
 # include/vrt.h vrt_status
 VRT_OK, VRT_ERR_INVALID_ARG, VRT_ERR_OUT_OF_RANGE, VRT_ERR_DEVICE, VRT_ERR_OOM, VRT_ERR_STATE = 0, -1, -2, -3, -4, -5
 
@@ -129,6 +130,8 @@ VRT_SYMBOLS = {
     "vrt_resize_output": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "vrt_render": (C.c_int, [_P, C.POINTER(RenderOpts)]),
     "vrt_set_frames_in_flight": (C.c_int, [_P, C.c_uint32]),
+    "vrt_reset_accumulation": (C.c_int, [_P]),
+    "vrt_get_accumulation": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrt_synchronize": (C.c_int, [_P]),
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),

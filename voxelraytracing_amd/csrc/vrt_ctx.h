@@ -44,7 +44,9 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
-void launch_path_chain_finish(Texel *out, const Texel *acc, uint32_t n, uint32_t chain, bool first, bool last, uint32_t spp, hipStream_t st);
+void launch_path_chain_finish(Texel *sum, Texel *mean, const Texel *acc, uint32_t n, uint32_t chain, bool first, bool last, uint32_t count,
+                              hipStream_t st);
+void launch_path_accum_resolve(Texel *out, Texel *sum, uint32_t n, bool first, bool last, uint32_t count, hipStream_t st);
 void launch_quantize(const Texel *out, uint8_t *rgba8, uint32_t w, uint32_t h, hipStream_t st);
 void launch_assemble(const Texel *gathered, Texel *dst, uint32_t width, uint32_t tiles_x, uint32_t tiles_total,
                      uint32_t root_weight, uint32_t period, bool skip_root, uint64_t rank_stride, hipStream_t st);
@@ -347,6 +349,14 @@ struct vrt_ctx {
     uint32_t prof_frames = 0;
 
     uint32_t last_spp = 1;
+    // VRT_RENDER_ACCUMULATE: the running sum (one texel per slot, never divided; allocated by the first accumulating frame,
+    // dropped by alloc_output), the samples in it and their seed, whether the next accumulating frame starts again at 0,
+    // and the event behind the last step that wrote the sum (the next frame's first step that touches it waits for it)
+    vrt::Texel *d_accum = nullptr;
+    uint32_t accum_n = 0, accum_seed = 0;
+    bool accum_restart = true;
+    hipEvent_t ev_accum = nullptr;
+    bool accum_ev_recorded = false;
     bool rendered = false;
     bool last_stats = false;
     uint32_t last_mode = 0;
@@ -409,6 +419,7 @@ VRT_HIDDEN int quiesce(vrt_ctx *c);   // wait for the frames that may still be r
 VRT_HIDDEN bool ragged_output(const vrt_ctx *c);
 VRT_HIDDEN hipError_t zero_now(vrt_ctx *c, void *p, size_t bytes);
 VRT_HIDDEN int validate_frame(vrt_ctx *c);
+VRT_HIDDEN int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from);
 VRT_HIDDEN int ensure_ndc(vrt_ctx *c);
 VRT_HIDDEN void fill_uniforms(const vrt_ctx *c, vrt::FrameParams &P);
 // vrt_present.hip: whether this frame can store its own window pixels (vrt_set_presentation) and, then, its screen buffer

@@ -74,6 +74,8 @@ struct FrameParams {
     Texel *acc;              // null: one sample per chain, radiance accumulates in `out` itself
     uint32_t chain, acc_slots;
     uint32_t last_bounce;    // 1: paths that hit on this segment end (max_ray_bounces reached)
+    uint32_t sample_base;    // VRT_RENDER_ACCUMULATE: the samples accumulated before this frame (sample s seeds as sample_base + s;
+                             // in what was padding before grp_counts: the other fields keep their offsets)
     // the window bounce launch (vrt_path_window.hip): the primary launch's workgroup b compacts its survivors into records
     // [b * grp_cap, b * grp_cap + grp_counts[b]) of path_out instead of appending to a segment
     uint32_t *grp_counts;

@@ -75,6 +75,8 @@ static int alloc_output(vrt_ctx *c) {
     c->tile_order_valid = false;
     for (auto &n : c->path_acc_texels) n = 0;
     for (auto &n : c->path_buf_records) n = 0;
+    (void)hipFree(c->d_accum); c->d_accum = nullptr;
+    c->accum_restart = true;
     layout_tiles(c);
     const size_t n = c->slots ? c->slots : 1;
     HIP_TRY(c, hipMalloc(&c->own_out, n * sizeof(vrt::Texel)));
@@ -335,9 +337,24 @@ static int next_events(vrt_ctx *c, std::array<hipEvent_t, 4> **ev, uint8_t **kin
     return VRT_OK;
 }
 
-// Wavefront path trace: per sample one launch per bounce over the compacted live-path buffer.
+// VRT_RENDER_ACCUMULATE: is the frame allowed, and how many samples does the sum hold before it (0: it starts again)?
+// Checked before anything is enqueued.
+int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from) {
+    *from = 0;
+    if (!(o.flags & VRT_RENDER_ACCUMULATE)) return VRT_OK;
+    if (o.mode != VRT_MODE_PATH) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: VRT_RENDER_ACCUMULATE is for VRT_MODE_PATH frames (mode %u)", o.mode);
+    const uint32_t spp = o.spp ? o.spp : 1u;
+    const uint32_t n = (c->accum_restart || o.seed != c->accum_seed) ? 0u : c->accum_n;
+    if ((uint64_t)n + spp > (1ull << 24))
+        return fail(c, VRT_ERR_OUT_OF_RANGE, "vrt_render: %u accumulated + %u samples > 2^24 (past it the count is not exact in f32)", n, spp);
+    *from = n;
+    return VRT_OK;
+}
+
+// Wavefront path trace: per sample one launch per bounce over the compacted live-path buffer.  accum: an accumulating frame
+// (VRT_RENDER_ACCUMULATE) with accum_from samples in the context's sum before it.
 static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt_render_opts &o, bool kstats, bool literal,
-                             std::array<hipEvent_t, 4> &ev, uint8_t &ev_kind) {
+                             bool accum, uint32_t accum_from, std::array<hipEvent_t, 4> &ev, uint8_t &ev_kind) {
     const uint32_t spp = o.spp ? o.spp : 1u, bounces = c->settings.max_ray_bounces;
     // Several samples per launch chain (plain frames, spp > 1): every launch of the chain carries `samples` times the rays —
     // 2.7 rays per lane are not enough to cover a bounce launch's tail — and a frame of 16 spp is 4 x 4
@@ -361,6 +378,21 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
         c->path_acc_texels[f.slot] = (size_t)samples * c->slots;
     }
+    if (accum && !c->d_accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
+        const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
+        HIP_TRY(c, hipMalloc(&c->d_accum, bytes));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->d_accum, bytes));
+        if (!c->ev_accum) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
+    }
+    // Only the steps that read and write the sum are ordered behind the previous accumulating frame's (it may be in flight on
+    // another frame set's stream); this frame's launches before them overlap it
+    bool sum_waited = false;
+    auto sum_step = [&]() -> int {
+        if (!sum_waited && c->accum_ev_recorded) HIP_TRY(c, hipStreamWaitEvent(f.st, c->ev_accum, 0));
+        sum_waited = true;
+        return VRT_OK;
+    };
+    const uint32_t accum_count = accum_from + spp;   // the samples in this frame's mean (<= 2^24: vrt_render)
     vrt::Texel *const frame_out = P.out;
     P.hit_seg_cap = seg_cap;
     P.acc = planes ? c->path_acc[f.slot] : nullptr;
@@ -375,6 +407,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     P.in_seg_cap = seg_cap;
     P.spp = spp;
     P.seed = o.seed;
+    P.sample_base = accum ? accum_from : 0u;
     // Bounce launches over the derived tables with march cells: every later segment of the frame in ONE launch of the pool
     // kernel (vrt_path.hip); worlds without march cells, stats frames and the literal march: one lane = path launch per bounce.
     const bool pool = !kstats && !literal && P.grid && bounces > 1 && c->path_pool;
@@ -433,16 +466,29 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             HIP_TRY(c, hipGetLastError());
             if (first) { if (timed) HIP_TRY(c, hipEventRecord(ev[1], f.st)); first = false; }
         }
+        if (accum) {
+            const int rc = sum_step();
+            if (rc) return rc;
+        }
         if (planes) {
-            vrt::launch_path_chain_finish(frame_out, c->path_acc[f.slot], c->slots, P.chain, smp == 0u, smp + P.chain >= spp, spp, f.st);
+            if (accum) vrt::launch_path_chain_finish(c->d_accum, frame_out, c->path_acc[f.slot], c->slots, P.chain, accum_from + smp == 0u,
+                                                     smp + P.chain >= spp, accum_count, f.st);
+            else vrt::launch_path_chain_finish(frame_out, frame_out, c->path_acc[f.slot], c->slots, P.chain, smp == 0u, smp + P.chain >= spp, spp, f.st);
+            HIP_TRY(c, hipGetLastError());
+        } else if (accum) {   // one sample per chain: the sample joins the sum (bit-exact only one sample at a time)
+            vrt::launch_path_accum_resolve(frame_out, c->d_accum, c->slots, accum_from + smp == 0u, smp + 1u >= spp, accum_count, f.st);
             HIP_TRY(c, hipGetLastError());
         }
     }
     P.out = frame_out;
     if (first && timed) HIP_TRY(c, hipEventRecord(ev[1], f.st));
-    if (bounces > 0 && spp > 1u && !planes) {
+    if (bounces > 0 && spp > 1u && !planes && !accum) {
         vrt::launch_path_finish(f.out, c->slots, spp, f.st);
         HIP_TRY(c, hipGetLastError());
+    }
+    if (accum && sum_waited) {
+        HIP_TRY(c, hipEventRecord(c->ev_accum, f.st));
+        c->accum_ev_recorded = true;
     }
     if (timed) {
         HIP_TRY(c, hipEventRecord(ev[3], f.st));
@@ -598,6 +644,8 @@ void vrt_destroy(vrt_ctx *c) {
     for (auto p : c->extra_counters) (void)hipFree(p);
     for (auto p : c->path_acc) (void)hipFree(p);
     for (auto p : c->path_grp_counts) (void)hipFree(p);
+    (void)hipFree(c->d_accum);
+    if (c->ev_accum) (void)hipEventDestroy(c->ev_accum);
     (void)hipFree(c->d_tile_cost); (void)hipFree(c->d_tile_order); (void)hipFree(c->d_tile_scratch);
     (void)hipFree(c->d_nodes); (void)hipFree(c->d_roots); (void)hipFree(c->d_mats); (void)hipFree(c->own_out);
     (void)hipFree(c->d_hits); (void)hipFree(c->d_counters); (void)hipFree(c->d_steps); (void)hipFree(c->d_rgba8); (void)hipFree(c->d_path);
@@ -634,7 +682,7 @@ const char *vrt_last_error(const vrt_ctx *ctx) { return ctx ? ctx->err.c_str() :
 int vrt_set_camera(vrt_ctx *c, const vrt_cam_data *cam) {
     GRP_EACH(c, vrt_set_camera(d, cam));
     if (!c || !cam) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_camera: null argument");
-    if (memcmp(&c->cam, cam, sizeof *cam) != 0) { c->view_gen++; c->cam_gen++; }
+    if (memcmp(&c->cam, cam, sizeof *cam) != 0) { c->view_gen++; c->cam_gen++; c->accum_restart = true; }
     c->cam = *cam;
     return VRT_OK;
 }
@@ -642,7 +690,7 @@ int vrt_set_camera(vrt_ctx *c, const vrt_cam_data *cam) {
 int vrt_set_settings(vrt_ctx *c, const vrt_settings *s) {
     GRP_EACH(c, vrt_set_settings(d, s));
     if (!c || !s) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_settings: null argument");
-    if (memcmp(&c->settings, s, sizeof *s) != 0) c->view_gen++;
+    if (memcmp(&c->settings, s, sizeof *s) != 0) { c->view_gen++; c->accum_restart = true; }
     c->settings = *s;
     return VRT_OK;
 }
@@ -650,7 +698,7 @@ int vrt_set_settings(vrt_ctx *c, const vrt_settings *s) {
 int vrt_set_world(vrt_ctx *c, const vrt_world_data *w) {
     GRP_EACH(c, vrt_set_world(d, w));
     if (!c || !w) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_world: null argument");
-    if (memcmp(&c->world, w, sizeof *w) != 0) c->view_gen++;
+    if (memcmp(&c->world, w, sizeof *w) != 0) { c->view_gen++; c->accum_restart = true; }
     c->world = *w;
     return VRT_OK;
 }
@@ -689,6 +737,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (o.stats == 2u && (o.mode != VRT_MODE_PRIMARY_SHADOW || (o.variant != 0u)))
         return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: the clock probe (stats = 2) is a build of the default primary + shadow kernel");
     if (!vrt::variant_supported(o.variant)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: unknown kernel variant %u", o.variant);
+    const bool accum = (o.flags & VRT_RENDER_ACCUMULATE) != 0u;
+    uint32_t accum_from = 0;
+    {
+        const int rc_ = accum_frame_start(c, o, &accum_from);
+        if (rc_) return rc_;
+    }
     int rc;
     {
         VRT_PROF(7, "  validate + hipSetDevice");
@@ -856,9 +910,17 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (kstats || o.mode == VRT_MODE_PATH) HIP_TRY(c, hipMemsetAsync(f.counters, 0, kCounterBytes, f.st));
     {
         VRT_PROF(13, "  the launch(es)");
-        if (o.mode == VRT_MODE_PATH) rc = launch_path_frame(c, P, f, o, kstats, air_liquid, *ev, *ev_kind);
+        if (o.mode == VRT_MODE_PATH) rc = launch_path_frame(c, P, f, o, kstats, air_liquid, accum, accum_from, *ev, *ev_kind);
         else rc = launch_march_frame(c, P, f, o.mode == VRT_MODE_PRIMARY_SHADOW, variant, kstats, *ev, *ev_kind);
-        if (rc) return rc;
+        if (rc) {
+            if (accum) c->accum_restart = true;   // (what the sum holds is not known)
+            return rc;
+        }
+    }
+    if (accum) {
+        c->accum_n = accum_from + (o.spp ? o.spp : 1u);
+        c->accum_seed = o.seed;
+        c->accum_restart = false;
     }
     rc = tile_order_after_frame(c, P, f.st, order_plan);   // (the sort behind the frame that noted its trips)
     if (rc) return rc;
@@ -867,6 +929,21 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     c->last_stats = o.stats == 1u;
     c->last_mode = o.mode;
     c->timing_pending = true;
+    return VRT_OK;
+}
+
+int vrt_reset_accumulation(vrt_ctx *c) {
+    GRP_EACH(c, vrt_reset_accumulation(d));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    c->accum_restart = true;
+    return VRT_OK;
+}
+
+int vrt_get_accumulation(vrt_ctx *c, uint32_t *samples, uint32_t *seed) {
+    GRP_ROOT(c, vrt_get_accumulation(d, samples, seed));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    if (samples) *samples = c->accum_n;
+    if (seed) *seed = c->accum_seed;
     return VRT_OK;
 }
 

@@ -176,6 +176,11 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
         return fail(c, VRT_ERR_STATE, "vrt_render: this multi-device context exchanges 8-byte records (primary(+shadow) frames of the default "
                     "march); create it with VRT_FLAG_TEXEL_MESSAGES for the path trace and the other marches");
     if (o.stats == 2u) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: no clock probe on a multi-device context");
+    {   // VRT_RENDER_ACCUMULATE: every device accumulates its own share; refused here, before any device has a frame of it
+        uint32_t from;
+        const int rc = accum_frame_start(root, o, &from);
+        if (rc) { c->err = root->err; return rc; }
+    }
     const uint32_t n = (uint32_t)g->dev.size();
     const bool plain = o.stats == 0u && root->settings.show_step_count != 1u;
     if (!plain || g->in_flight == 1u || g->last_was_stats) {   // a stats frame (counters are read back) stands alone

@@ -574,14 +574,17 @@ __global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
 }
 
 
-// The end of a launch chain of several samples: the frame's running sum plus the chain's planes, in sample order — the
-// order the one-sample-per-chain launches add them in and the oracle's — and the division once the last chain is in.
-__global__ void path_chain_finish_kernel(Texel *out, const Texel *acc, uint32_t n, uint32_t chain, uint32_t first, uint32_t last, float spp) {
+// The end of a launch chain of several samples: the running sum plus the chain's planes, in sample order — the order the
+// one-sample-per-chain launches add them in and the oracle's — and the division once the last chain is in.  A plain frame's
+// sum is its output (mean == sum: divided in place); an accumulating frame's is the context's (VRT_RENDER_ACCUMULATE), kept
+// undivided, and the last chain also stores the mean into the frame's output.  first: the chain holds the sum's first sample.
+__global__ void path_chain_finish_kernel(Texel *sum, Texel *mean, const Texel *acc, uint32_t n, uint32_t chain, uint32_t first, uint32_t last,
+                                         float count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint4 t = acc[i];   // the chain's first sample: the frame's first (light and id word as they are), or one more term
+    uint4 t = acc[i];   // the chain's first sample: the sum's first (light and id word as they are), or one more term
     if (!first) {
-        const uint4 o = out[i];
+        const uint4 o = sum[i];
         t.x = __float_as_uint(__uint_as_float(o.x) + __uint_as_float(t.x));
         t.y = __float_as_uint(__uint_as_float(o.y) + __uint_as_float(t.y));
         t.z = __float_as_uint(__uint_as_float(o.z) + __uint_as_float(t.z));
@@ -593,12 +596,46 @@ __global__ void path_chain_finish_kernel(Texel *out, const Texel *acc, uint32_t 
         t.y = __float_as_uint(__uint_as_float(t.y) + __uint_as_float(a.y));
         t.z = __float_as_uint(__uint_as_float(t.z) + __uint_as_float(a.z));
     }
+    if (!last || mean != sum) sum[i] = t;
     if (last) {
-        t.x = __float_as_uint(__uint_as_float(t.x) / spp);
-        t.y = __float_as_uint(__uint_as_float(t.y) / spp);
-        t.z = __float_as_uint(__uint_as_float(t.z) / spp);
+        t.x = __float_as_uint(__uint_as_float(t.x) / count);
+        t.y = __float_as_uint(__uint_as_float(t.y) / count);
+        t.z = __float_as_uint(__uint_as_float(t.z) / count);
+        mean[i] = t;
     }
-    out[i] = t;
+}
+
+// An accumulating frame of one-sample chains (VRT_RENDER_ACCUMULATE; spp 1, stats, literal, no march cells): behind each of its
+// samples, the sample's light (its own in `out`: the sample's first segment stored the texel, or added to the zeros left here)
+// joins the context's sum — stored when it is the sum's first, else added: the order a frame of all the samples adds them in.
+// The frame's last sample leaves the mean in `out`; an earlier one leaves zero light for the next sample to add to.  The id word
+// is the frame's own, in both.  64 bytes a pixel, all of them NON-TEMPORAL (store_streaming, vrt_device.h): the pass runs beside
+// the next frame's march, whose table loads hit the L2 only while 133 MB of texels (1080p) do not push their lines out.
+__device__ __forceinline__ uint4 load_streaming(const Texel *p) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+    return make_uint4(t.x, t.y, t.z, t.w);
+}
+
+__global__ void path_accum_resolve_kernel(Texel *out, Texel *sum, uint32_t n, uint32_t first, uint32_t last, float count) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint4 t = load_streaming(out + i);
+    if (!first) {
+        const uint4 o = load_streaming(sum + i);
+        t.x = __float_as_uint(__uint_as_float(o.x) + __uint_as_float(t.x));
+        t.y = __float_as_uint(__uint_as_float(o.y) + __uint_as_float(t.y));
+        t.z = __float_as_uint(__uint_as_float(o.z) + __uint_as_float(t.z));
+    }
+    store_streaming(sum + i, t);
+    if (last) {
+        t.x = __float_as_uint(__uint_as_float(t.x) / count);
+        t.y = __float_as_uint(__uint_as_float(t.y) / count);
+        t.z = __float_as_uint(__uint_as_float(t.z) / count);
+    } else {
+        t.x = t.y = t.z = 0u;
+    }
+    store_streaming(out + i, t);
 }
 
 // rgb /= spp after the last sample
@@ -666,10 +703,17 @@ void launch_path_bounce(const FrameParams &P, bool stats, bool literal, hipStrea
 }
 #undef VRT_PATH_LAUNCH
 
-void launch_path_chain_finish(Texel *out, const Texel *acc, uint32_t n, uint32_t chain, bool first, bool last, uint32_t spp, hipStream_t st) {
+void launch_path_chain_finish(Texel *sum, Texel *mean, const Texel *acc, uint32_t n, uint32_t chain, bool first, bool last, uint32_t count,
+                              hipStream_t st) {
     if (!n) return;
-    hipLaunchKernelGGL(path_chain_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, out, acc, n, chain, first ? 1u : 0u, last ? 1u : 0u,
-                       (float)spp);
+    hipLaunchKernelGGL(path_chain_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, sum, mean, acc, n, chain, first ? 1u : 0u,
+                       last ? 1u : 0u, (float)count);
+}
+
+void launch_path_accum_resolve(Texel *out, Texel *sum, uint32_t n, bool first, bool last, uint32_t count, hipStream_t st) {
+    if (!n) return;
+    hipLaunchKernelGGL(path_accum_resolve_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, out, sum, n, first ? 1u : 0u, last ? 1u : 0u,
+                       (float)count);
 }
 
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st) {

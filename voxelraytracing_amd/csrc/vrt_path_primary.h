@@ -93,8 +93,9 @@ __global__ void __launch_bounds__(256) path_primary_kernel(FrameParams P) {
             st.origin = origin;
             st.dir = dir;
             st.thr = V3{1.0f, 1.0f, 1.0f};
-            // seed: path_tracer.wgsl:328 (y*W + x) + the per-sample stride and frame seed of SURVEY §8d
-            st.rng = py * P.width + px + sample * (P.width * P.height) + P.seed * 0x9E3779B9u;
+            // seed: path_tracer.wgsl:328 (y*W + x) + the per-sample stride and frame seed of SURVEY §8d; an accumulating frame's
+            // samples continue the accumulation's (P.sample_base: 0 otherwise)
+            st.rng = py * P.width + px + (P.sample_base + sample) * (P.width * P.height) + P.seed * 0x9E3779B9u;
             V3 light{0.f, 0.f, 0.f};
             bool missed;
             const bool alive = path_after_march(P, st, R, light, missed) && !P.last_bounce;

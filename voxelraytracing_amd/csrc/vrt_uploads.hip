@@ -668,6 +668,7 @@ int vrt_write_nodes(vrt_ctx *c, const uint16_t *pool, uint32_t start, uint32_t e
     const int rc = stage_upload(c, c->d_nodes + root, pool + root, (size_t)count * sizeof(uint16_t), true);
     if (rc) return rc;
     mark_node_range_dirty(c, start, end);   // (the widening repeats a neighbour's node: nothing of its octree changes)
+    if (end > start) c->accum_restart = true;
     return VRT_OK;
 }
 
@@ -696,6 +697,7 @@ int vrt_write_chunk_roots_tagged(vrt_ctx *c, uint32_t offset, const uint32_t *ro
         if (c->h_roots[offset + i] != roots[i]) mark_chunk_dirty(c, offset + i);
     memcpy(c->h_roots.data() + offset, roots, (size_t)cut * sizeof(uint32_t));
     c->roots_index_stale = true;
+    c->accum_restart = true;
     remember();
     return VRT_OK;
 }
@@ -706,6 +708,7 @@ int vrt_resize_world(vrt_ctx *c, uint32_t world_size_chunks) {
     HIP_TRY(c, hipSetDevice(c->device));
     QUIESCE(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->accum_restart = true;
     return alloc_roots(c, world_size_chunks);
 }
 
@@ -715,6 +718,7 @@ int vrt_write_materials(vrt_ctx *c, uint32_t first, const vrt_material *mats, ui
     if ((uint64_t)first + n > 256) return fail(c, VRT_ERR_OUT_OF_RANGE, "vrt_write_materials: %u+%u > 256", first, n);
     if (n == 0) return VRT_OK;
     c->view_gen++;
+    c->accum_restart = true;
     memcpy(c->h_mats + first, mats, (size_t)n * sizeof(vrt_material));
     uint32_t old_mask[8];
     memcpy(old_mask, c->liquid_mask, sizeof old_mask);

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import (CamData, Material, Settings, WorldData, Stats, RenderOpts,  # noqa: F401  (re-exported)
-                   MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH)
+                   MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH, RENDER_OWN_STREAMS, RENDER_TIMED, RENDER_ACCUMULATE)
 
 
 class VrtError(RuntimeError):
@@ -136,10 +136,12 @@ class Gpu:
 
     # --- PixelShader (shader.rs:295-380) ---
     def encode_pass(self, mode: int = MODE_PRIMARY, variant: int = 0, stats: bool = False, spp: int = 1, seed: int = 0,
-                    own_streams: bool = False, timed: bool = False):
+                    own_streams: bool = False, timed: bool = False, accumulate: bool = False):
         """PixelShader::encode_pass + queue.submit (shader.rs:371-379, main.rs:453,565). Asynchronous.
-        own_streams: VRT_RENDER_OWN_STREAMS (include/vrt.h)."""
-        o = RenderOpts(mode, variant, int(stats), spp, seed, (1 if own_streams else 0) | (2 if timed else 0))   # stats: False/True, or 2 = clock probe; timed: VRT_RENDER_TIMED
+        own_streams: VRT_RENDER_OWN_STREAMS; accumulate: VRT_RENDER_ACCUMULATE, MODE_PATH only — the output is the mean of
+        every sample since the accumulation last started again (include/vrt.h)."""
+        flags = (RENDER_OWN_STREAMS if own_streams else 0) | (RENDER_TIMED if timed else 0) | (RENDER_ACCUMULATE if accumulate else 0)
+        o = RenderOpts(mode, variant, int(stats), spp, seed, flags)   # stats: False/True, or 2 = clock probe
         self._ck(self._lib.vrt_render(self._h, C.byref(o)))
 
     render = encode_pass
@@ -147,6 +149,16 @@ class Gpu:
     def set_frames_in_flight(self, n: int):
         """1..4 frames in flight (default 2); see vrt_set_frames_in_flight in include/vrt.h."""
         self._ck(self._lib.vrt_set_frames_in_flight(self._h, n))
+
+    def reset_accumulation(self):
+        """The next accumulating frame starts again at sample 0 (vrt_reset_accumulation)."""
+        self._ck(self._lib.vrt_reset_accumulation(self._h))
+
+    def accumulation(self):
+        """(samples, seed) of the last accumulating frame's mean (vrt_get_accumulation; no synchronisation)."""
+        n, seed = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._lib.vrt_get_accumulation(self._h, C.byref(n), C.byref(seed)))
+        return n.value, seed.value
 
     def synchronize(self):
         self._ck(self._lib.vrt_synchronize(self._h))
