@@ -173,7 +173,7 @@ typedef struct {
  * s spp are, bit for bit, one frame of K * s spp with the same seed.  The sum starts again at n = 0 (without a device
  * step: the first frame stores it) after vrt_reset_accumulation, or when anything the image depends on has changed since
  * the previous accumulating frame: the camera, settings or world (byte-wise), any vrt_write_materials, a non-empty
- * vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
+ * vrt_write_emission that is not refused, a non-empty vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
  * Non-accumulating frames in between change nothing.  n + spp > 2^24: VRT_ERR_OUT_OF_RANGE, nothing enqueued. */
 #define VRT_RENDER_ACCUMULATE 4u
 
@@ -238,6 +238,22 @@ int vrt_resize_world(vrt_ctx *ctx, uint32_t world_size_chunks);
 
 /* SimpleBuffer<[Material;256]>::write_slice(first, mats) — shader.rs:108-115, main.rs:219-223. */
 int vrt_write_materials(vrt_ctx *ctx, uint32_t first, const vrt_material *mats, uint32_t n);
+
+/* New relative to the live reference: the emission of path_tracer.wgsl's Material (:27, :183-184), kept in a table of its
+ * own beside the material table (vrt_material stays the reference's 32 bytes; its _padding is not read).  256 floats per
+ * context, indexed like the material table (voxel ids >= 255 use entry 255), all 0 until written; entries [first,
+ * first + n) are copied at call time.  VRT_MODE_PATH only: the primary (+ shadow) modes are the live ray_tracer.wgsl,
+ * which has no emission, and ignore the table.
+ * On every hit of a path (the hit of its last allowed segment included) whose voxel's entry e is not 0, the sample's light
+ * gains (mc * e) * thr per channel in f32 — mc the colour the throughput is then multiplied by (face shading, and the
+ * step-count grey under show_step_count), thr the throughput before the hit — ahead of thr *= mc, as :183-186 order it.
+ * A hit with e == 0 adds nothing.  A sample's light is its terms summed in segment order (the sky's, on a miss, last); the
+ * frame's is the sum of its samples' lights in sample order, / spp, and VRT_RENDER_ACCUMULATE keeps its identity.  Id words,
+ * step counts, the RNG stream and every path direction are those of the same frame without emission.
+ * first + n > 256: VRT_ERR_OUT_OF_RANGE; emission NULL with n > 0, or an entry that is negative, NaN or infinite:
+ * VRT_ERR_INVALID_ARG — nothing written either way.  n == 0 is a no-op; any other write restarts the accumulation.  A table
+ * that is all zero (never written, or written back to zeros) renders exactly as a context without one. */
+int vrt_write_emission(vrt_ctx *ctx, uint32_t first, const float *emission, uint32_t n);
 
 /* SimpleBuffer<T>::write — shader.rs:101-106; callers main.rs:428,439,447-449. */
 int vrt_set_camera(vrt_ctx *ctx, const vrt_cam_data *cam);

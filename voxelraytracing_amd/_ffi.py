@@ -124,6 +124,7 @@ VRT_SYMBOLS = {
     "vrt_write_chunk_roots_tagged": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.c_uint64]),
     "vrt_resize_world": (C.c_int, [_P, C.c_uint32]),
     "vrt_write_materials": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
+    "vrt_write_emission": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     "vrt_set_camera": (C.c_int, [_P, C.POINTER(CamData)]),
     "vrt_set_settings": (C.c_int, [_P, C.POINTER(Settings)]),
     "vrt_set_world": (C.c_int, [_P, C.POINTER(WorldData)]),

@@ -38,9 +38,10 @@ bool variant_supported(uint32_t variant);
 void launch_primary(const FrameParams &P, uint32_t variant, bool stats, bool shadow, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_shadow(const FrameParams &P, uint32_t variant, bool stats, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_primary_shadow_fused(const FrameParams &P, uint32_t march, bool stats, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
-void launch_path_primary(const FrameParams &P, bool stats, bool literal, hipStream_t st);
-void launch_path_bounce(const FrameParams &P, bool stats, bool literal, hipStream_t st);
-void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, hipStream_t st);
+// emit: the kernels that add the light of emissive hits (vrt_write_emission; the table is the 256 floats after P.mats)
+void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, hipStream_t st);
+void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, hipStream_t st);
+void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -150,7 +151,7 @@ struct vrt_ctx {
 
     uint16_t *d_nodes = nullptr;
     uint32_t *d_roots = nullptr;
-    vrt_material *d_mats = nullptr;
+    vrt_material *d_mats = nullptr;   // the 256 materials, then the 256 floats of the emission table (vrt::emission_table)
     vrt::Texel *d_out = nullptr;    // where frames are written: own_out or caller-bound memory
     vrt::Texel *own_out = nullptr;
     vrt::Texel *last_out = nullptr;  // the buffer holding the most recent frame
@@ -337,6 +338,8 @@ struct vrt_ctx {
     uint64_t gen_out_cap = 0;
 
     vrt_material h_mats[256];
+    float h_emission[256];    // vrt_write_emission's table (zeros at creation) and how many of its entries are not 0: a frame
+    uint32_t n_emissive = 0;  // of a context with none runs the kernels without the emission term
     uint32_t liquid_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit v <=> h_mats[v].is_liquid == 1 (kept by vrt_write_materials)
     bool liquid_is_range = true;                          // the liquid ids are one range below 255, or none
     uint32_t liquid_lo = 0x80000000u, liquid_span = 0u;   // (none: no 15-bit voxel id is 0x80000000)

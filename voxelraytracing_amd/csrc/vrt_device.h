@@ -34,6 +34,10 @@ __host__ __device__ inline uint32_t grid_entry(uint32_t x) { return x - 1u < 31u
 // One output texel: {r, g, b as f32 bits, id word}. 16 B so that a wave stores 1 KiB contiguously.
 using Texel = uint4;
 
+// vrt_write_emission's table: 256 floats right behind the 256 materials, in the same allocation (no field of FrameParams of its own)
+constexpr uint32_t kMaterials = 256u;
+__host__ __device__ inline const float *emission_table(const vrt_material *mats) { return reinterpret_cast<const float *>(mats + kMaterials); }
+
 // Everything a frame's kernels read, passed by value (kernarg -> SGPRs).
 struct FrameParams {
     const uint16_t *nodes;   // flat node pool, little-endian u16 == the reference's packed u32 pairs

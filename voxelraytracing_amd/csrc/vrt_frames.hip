@@ -362,6 +362,13 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     // to the frame in sample order, which is the order one sample per chain adds them in.
     const uint32_t samples = (spp > 1u && !kstats && !literal && P.grid && bounces > 0) ? (spp < c->path_samples ? spp : c->path_samples) : 1u;
     const bool planes = samples > 1u;
+    // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
+    // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
+    // frame's (path_accum_resolve_kernel takes it into the sum behind every sample) and — own_sum — an emissive frame's of
+    // several samples, which takes the same pass into a sum of its own (the frame set's first plane).  Without emission a
+    // sample is one term, added straight to the texel, and a 1-spp frame's texel is its one sample either way.
+    const bool emit = c->n_emissive != 0u;
+    const bool own_sum = emit && !planes && !accum && spp > 1u && bounces > 0;
     const uint32_t seg_cap = c->hit_seg_cap * samples;
     const size_t cap = (size_t)vrt::kHitSegments * seg_cap;
     if (c->path_buf_records[f.slot] < cap) {   // (grows only; hipFree waits for whatever still uses the old one)
@@ -371,7 +378,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         HIP_TRY(c, hipMalloc(f.path_buf, (2 * 3 + (vrt::g_exp.path_bounce_window ? 2 : 0)) * cap * sizeof(uint4)));
         c->path_buf_records[f.slot] = cap;
     }
-    if (planes && c->path_acc_texels[f.slot] < (size_t)samples * c->slots) {
+    if ((planes || own_sum) && c->path_acc_texels[f.slot] < (size_t)samples * c->slots) {
         (void)hipFree(c->path_acc[f.slot]);
         c->path_acc[f.slot] = nullptr; c->path_acc_texels[f.slot] = 0;
         HIP_TRY(c, hipMalloc(&c->path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
@@ -415,7 +422,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     // ... and among those the window launch (vrt_path_window.hip): the primary launch compacts each workgroup's survivors into
     // the workgroup's own region (256 records per sample of the chain), the bounce launch stages the march cells around a
     // group of four regions in LDS
-    const bool window = cells && c->path_window && vrt::g_exp.path_bounce_window;   // (the window launch: the experiments build)
+    const bool window = cells && c->path_window && vrt::g_exp.path_bounce_window && !emit;   // (the window launch: the experiments build; no emission)
     const uint32_t n_regions = (c->tiles_local + 3u) / 4u;
     if (window) {
         if (c->path_grp_regions[f.slot] < n_regions) {
@@ -451,17 +458,18 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             // one sample per pixel: the lane that ends a path has the pixel's final value (x / 1 = x) — no finishing pass
             if (b == 0) {
                 if (window) vrt::g_exp.path_primary_grouped(P, f.st);
-                else vrt::launch_path_primary(P, kstats, literal, f.st);
+                else vrt::launch_path_primary(P, kstats, literal, emit, f.st);
             } else if (cells) {
                 // every bounce segment that is left in ONE launch: the waves carry their own survivors from one to the next
                 // (one cursor set, one swap of the path buffers per LAUNCH: g counts launches)
                 const uint32_t segments = bounces - b;
                 P.last_bounce = 1u;
                 if (window) vrt::g_exp.path_bounce_window(P, segments, n_regions, samples, c->path_window_shape, c->path_window_lift, f.st);
-                else vrt::launch_path_bounce_cells(P, c->path_refill, segments, c->path_pool_batches ? c->path_pool_batches : (c->in_flight > 1u ? 5u : 4u), f.st);
+                else vrt::launch_path_bounce_cells(P, c->path_refill, segments, c->path_pool_batches ? c->path_pool_batches : (c->in_flight > 1u ? 5u : 4u), emit,
+                                                   f.st);
                 b += segments - 1u;
             } else {
-                vrt::launch_path_bounce(P, kstats, literal, f.st);   // (no march cells, a stats frame, the literal march: lane = path)
+                vrt::launch_path_bounce(P, kstats, literal, emit, f.st);   // (no march cells, a stats frame, the literal march: lane = path)
             }
             HIP_TRY(c, hipGetLastError());
             if (first) { if (timed) HIP_TRY(c, hipEventRecord(ev[1], f.st)); first = false; }
@@ -478,11 +486,14 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         } else if (accum) {   // one sample per chain: the sample joins the sum (bit-exact only one sample at a time)
             vrt::launch_path_accum_resolve(frame_out, c->d_accum, c->slots, accum_from + smp == 0u, smp + 1u >= spp, accum_count, f.st);
             HIP_TRY(c, hipGetLastError());
+        } else if (own_sum) {   // (emission) the same into this frame's own sum
+            vrt::launch_path_accum_resolve(frame_out, c->path_acc[f.slot], c->slots, smp == 0u, smp + 1u >= spp, spp, f.st);
+            HIP_TRY(c, hipGetLastError());
         }
     }
     P.out = frame_out;
     if (first && timed) HIP_TRY(c, hipEventRecord(ev[1], f.st));
-    if (bounces > 0 && spp > 1u && !planes && !accum) {
+    if (bounces > 0 && spp > 1u && !planes && !accum && !own_sum) {
         vrt::launch_path_finish(f.out, c->slots, spp, f.st);
         HIP_TRY(c, hipGetLastError());
     }
@@ -590,6 +601,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     if (const char *e = getenv("VRT_PATH_SAMPLES_PER_CHAIN")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->path_samples = (uint32_t)v; }
     if (const char *e = getenv("VRT_TIMING_EVERY")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 1000000) c->timing_every = (uint32_t)v; }
     memset(c->h_mats, 0, sizeof c->h_mats);
+    memset(c->h_emission, 0, sizeof c->h_emission);
     memset(&c->cam, 0, sizeof c->cam);
     memset(&c->settings, 0, sizeof c->settings);
     memset(&c->world, 0, sizeof c->world);
@@ -608,8 +620,9 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pool_upload, hipEventDisableTiming));
         HIP_TRY(c, hipHostMalloc((void **)&c->h_ring, vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs, hipHostMallocMapped));
         HIP_TRY(c, hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0));
-        HIP_TRY(c, hipMalloc(&c->d_mats, sizeof c->h_mats));
-        HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, sizeof c->h_mats, c->stream));
+        static_assert(sizeof c->h_mats == vrt::kMaterials * sizeof(vrt_material), "the emission table follows the 256 materials");
+        HIP_TRY(c, hipMalloc(&c->d_mats, sizeof c->h_mats + sizeof c->h_emission));   // + the emission table (vrt::emission_table)
+        HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, sizeof c->h_mats + sizeof c->h_emission, c->stream));
         HIP_TRY(c, hipMalloc(&c->d_counters, kCounterBytes));
         HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, kCounterBytes, c->stream));
         int r = alloc_roots(c, cfg->world_size_chunks);

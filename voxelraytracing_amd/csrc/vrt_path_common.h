@@ -89,16 +89,28 @@ struct PathState {
     uint32_t rng;
 };
 
+// The light a hit gives off (path_tracer.wgsl:183-184, vrt_write_emission): (mc * e) * thr per channel, thr the throughput
+// before the hit, e the voxel's entry of the emission table.  false (and `light` untouched) when e is 0: nothing is added.
+__device__ __forceinline__ bool path_emission(const FrameParams &P, const MarchResult &R, const V3 &mc, const V3 &thr, V3 &light) {
+    const float e = emission_table(P.mats)[min(R.voxel, 255u)];
+    if (e == 0.0f) return false;
+    light = V3{(mc.x * e) * thr.x, (mc.y * e) * thr.y, (mc.z * e) * thr.z};
+    return true;
+}
+
 // What follows a segment's march (the rest of the body of ray_color's loop, path_tracer.wgsl:155-192).  Returns true if the
-// path goes on (st updated to the next segment); a miss puts the sky's light, weighted, into `light`.
-__device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState &st, const MarchResult &R, V3 &light, bool &missed) {
-    missed = !R.hit;
+// path goes on (st updated to the next segment); a miss puts the sky's light, weighted, into `light`, and so does — EMIT — a
+// hit on an emissive voxel its own.  lit: `light` holds a term for the sample's texel.
+template <bool EMIT = false>
+__device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
+    lit = !R.hit;
     if (!R.hit) {
         const V3 sky = ray_sky(P, st.origin, st.dir);
         light = V3{sky.x * st.thr.x, sky.y * st.thr.y, sky.z * st.thr.z};
         return false;
     }
     const V3 mc = hit_color(P, R);
+    if (EMIT) lit = path_emission(P, R, mc, st.thr, light);   // (before thr *= mc: :183-186)
     const float d = vdot(R.norm, st.dir);
     const V3 spec{st.dir.x - 2.0f * R.norm.x * d, st.dir.y - 2.0f * R.norm.y * d, st.dir.z - 2.0f * R.norm.z * d};
     const V3 rd = rng_next_dir(st.rng);

@@ -49,11 +49,12 @@ static_assert(kHitSegments == 256, "a launch's first workgroup (256 threads) cle
 
 // Bounce 0: primary rays of sample P.sample. Sample 0 initialises the texel {light, id}; later samples add.
 // MULTI: the samples of a launch chain (P.acc, P.chain) share the primary march; otherwise one sample, straight into `out`
+// EMIT: emissive hits add their light too (vrt_write_emission) — a later sample's texel is then written on those as well
 // GROUPED (the window bounce launch, vrt_path_window.hip): a workgroup's survivors are compacted — by the workgroup, through a
 // counter in LDS — into the workgroup's own region of the path buffer (P.grp_cap records; the count into P.grp_counts), and
 // the workgroups take the tiles in blocks of 4 x 4, so that four consecutive regions hold the paths of 32 x 32 pixels: a
 // bounce workgroup's rays then start within a few voxels of each other.  No cursors, no global atomics.
-template <int MARCH, bool LDS_ROOTS, bool STATS, bool MULTI = false, bool GROUPED = false>
+template <int MARCH, bool LDS_ROOTS, bool STATS, bool MULTI = false, bool GROUPED = false, bool EMIT = false>
 __global__ void __launch_bounds__(256) path_primary_kernel(FrameParams P) {
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem, *s_roots = smem + 24;
@@ -97,8 +98,8 @@ __global__ void __launch_bounds__(256) path_primary_kernel(FrameParams P) {
             // samples continue the accumulation's (P.sample_base: 0 otherwise)
             st.rng = py * P.width + px + (P.sample_base + sample) * (P.width * P.height) + P.seed * 0x9E3779B9u;
             V3 light{0.f, 0.f, 0.f};
-            bool missed;
-            const bool alive = path_after_march(P, st, R, light, missed) && !P.last_bounce;
+            bool lit;
+            const bool alive = path_after_march<EMIT>(P, st, R, light, lit) && !P.last_bounce;
             if (MULTI) {
                 // this sample's own plane: its light so far and, for the frame's first sample, the id word (0 otherwise);
                 // the path's later segments find the plane through the slot
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(256) path_primary_kernel(FrameParams P) {
                 P.acc[st.slot] = make_uint4(__float_as_uint(light.x), __float_as_uint(light.y), __float_as_uint(light.z), sample == 0u ? id0 : 0u);
             } else if (P.sample == 0u) {
                 P.out[st.slot] = make_uint4(__float_as_uint(light.x), __float_as_uint(light.y), __float_as_uint(light.z), id0);
-            } else if (missed) {
+            } else if (lit) {
                 uint4 t = P.out[st.slot];
                 t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
                 t.y = __float_as_uint(__uint_as_float(t.y) + light.y);

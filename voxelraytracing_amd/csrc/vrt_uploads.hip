@@ -1,5 +1,7 @@
 // vrt_uploads.hip — the write half of the C ABI (NodeBuffer::write, ArrayBuffer::write, SimpleBuffer::write_slice:
 // clientdesktop/src/graphics/shader.rs:22-40,101-142) and the derived tables that follow the writes (vrt_accel.hip).
+#include <cfloat>
+
 #include "vrt_ctx.h"
 
 size_t chunk_dir_entries(uint32_t S) { return (size_t)S * (S + 1u) * (S + 1u); }
@@ -739,6 +741,23 @@ int vrt_write_materials(vrt_ctx *c, uint32_t first, const vrt_material *mats, ui
     if (memcmp(old_mask, c->liquid_mask, sizeof old_mask) != 0) mark_all_dirty(c);
     HIP_TRY(c, hipSetDevice(c->device));
     return stage_upload(c, c->d_mats + first, mats, (size_t)n * sizeof(vrt_material));
+}
+
+int vrt_write_emission(vrt_ctx *c, uint32_t first, const float *emission, uint32_t n) {
+    GRP_EACH(c, vrt_write_emission(d, first, emission, n));   // (every device refuses the same arguments: the first one stops it)
+    if (!c || (!emission && n)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_emission: null argument");
+    if ((uint64_t)first + n > 256) return fail(c, VRT_ERR_OUT_OF_RANGE, "vrt_write_emission: %u+%u > 256", first, n);
+    for (uint32_t i = 0; i < n; i++)
+        if (!(emission[i] >= 0.0f && emission[i] <= FLT_MAX))
+            return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_emission: entry %u (%g) is negative, NaN or infinite", first + i, (double)emission[i]);
+    if (n == 0) return VRT_OK;
+    c->accum_restart = true;
+    memcpy(c->h_emission + first, emission, (size_t)n * sizeof(float));
+    uint32_t nz = 0;
+    for (float e : c->h_emission) nz += e != 0.0f ? 1u : 0u;
+    c->n_emissive = nz;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return stage_upload(c, const_cast<float *>(vrt::emission_table(c->d_mats)) + first, emission, (size_t)n * sizeof(float));
 }
 
 int vrt_get_accel_info(vrt_ctx *c, vrt_accel_info *out) {

@@ -121,6 +121,13 @@ class Gpu:
         n = len(mats) if n is None else n
         self._ck(self._lib.vrt_write_materials(self._h, first, C.cast(mats, C.c_void_p), n))
 
+    def write_emission(self, values, first: int = 0):
+        """vrt_write_emission: entries [first, first + len(values)) of the per-material emission table (MODE_PATH only; all 0
+        until written).  values: a sequence of floats or a float32 array; a negative, NaN or infinite entry, or first +
+        len(values) > 256, raises VrtError and writes nothing."""
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        self._ck(self._lib.vrt_write_emission(self._h, first, v.ctypes.data if v.size else None, v.size))
+
     def write_cam_data(self, cam: CamData):
         self._ck(self._lib.vrt_set_camera(self._h, C.byref(cam)))
 
