@@ -177,6 +177,42 @@ pub struct vrt_ray_hit {
 const _: () = assert!(core::mem::size_of::<vrt_ray_query>() == 32);
 const _: () = assert!(core::mem::size_of::<vrt_ray_hit>() == 32);
 
+/// One `clip_aabb_movement(Aabb::new(from, to), mv, |bb| world.get_collisions_w(bb, ..), autojump)` query (vrt_clip_moves).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_box_query {
+    pub from: [f32; 3],
+    pub flags: u32,
+    pub to: [f32; 3],
+    pub _r0: u32,
+    pub mv: [f32; 3],
+    pub _r1: u32,
+}
+
+pub const VRT_BOX_AUTOJUMP: u32 = 1;
+pub const VRT_BOX_MAX_VOXELS: u32 = 4096;
+pub const VRT_BOX_MOVED: u32 = 0;
+pub const VRT_BOX_REJECTED: u32 = 2;
+pub const VRT_BOX_CLIPPED_X: u32 = 1;
+pub const VRT_BOX_CLIPPED_Y: u32 = 2;
+pub const VRT_BOX_CLIPPED_Z: u32 = 4;
+pub const VRT_BOX_STEPPED_UP: u32 = 8;
+
+/// Its answer: `mv` is the reference's `mv_clipped` when `status` is VRT_BOX_MOVED; `flags` says which axes the first pass
+/// clipped and whether the step-up was taken, `boxes[p]` how many solid voxels pass `p` gathered.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_box_move {
+    pub mv: [f32; 3],
+    pub status: u32,
+    pub flags: u32,
+    pub boxes: [u32; 2],
+    pub _reserved: u32,
+}
+
+const _: () = assert!(core::mem::size_of::<vrt_box_query>() == 48);
+const _: () = assert!(core::mem::size_of::<vrt_box_move>() == 32);
+
 /// What issuing a frame costs the host (vrt_get_issue_profile), microseconds per vrt_render call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -241,6 +277,8 @@ extern "C" {
     pub fn vrt_assemble_compact(ctx: *mut vrt_ctx, gathered: *const c_void, rank_stride_bytes: u64, dst: *mut c_void) -> c_int;
     pub fn vrt_cast_rays(ctx: *mut vrt_ctx, queries: *const vrt_ray_query, n: u32, out: *mut vrt_ray_hit) -> c_int;
     pub fn vrt_cast_rays_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
+    pub fn vrt_clip_moves(ctx: *mut vrt_ctx, queries: *const vrt_box_query, n: u32, out: *mut vrt_box_move) -> c_int;
+    pub fn vrt_clip_moves_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
     pub fn vrt_generate_chunks(ctx: *mut vrt_ctx, seed: u32, chunk_pos: *const i32, n: u32, nodes: *mut u16, cap_nodes: u64,
                                offsets: *mut u64) -> c_int;
     pub fn vrt_build_chunks(ctx: *mut vrt_ctx, dense: *const u16, n: u32, nodes: *mut u16, cap_nodes: u64, offsets: *mut u64) -> c_int;

@@ -437,6 +437,57 @@ int vrt_cast_rays(vrt_ctx *ctx, const vrt_ray_query *queries, uint32_t n, vrt_ra
 /* The same with device memory (n vrt_ray_query in, n vrt_ray_hit out, 4-byte aligned), asynchronous on the context's stream. */
 int vrt_cast_rays_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
 
+/* The client's collisions (clientdesktop/src/main.rs:316-319: player.update(&moves, |bb| world.get_collisions_w(bb, &voxels))):
+ * clip_aabb_movement (client/src/player.rs:202-244) over ClientWorld::get_collisions_w (client/src/world.rs:369-391) and
+ * Aabb::expand / translate / clip_{y,x,z}_collide (common/src/math.rs:18-126), batched, one box per lane, in strict binary32,
+ * every component of the answer the reference's bits.
+ * A voxel is a world box [p, p + 1] when it is SOLID: materials[min(v, 255)].is_empty == 0 && .is_liquid == 0 of the context's
+ * material table (Material::construct fills both from the voxel's state, graphics/mod.rs:38-46) — liquids do not collide here,
+ * unlike in vrt_cast_rays.  Outside the world box, or in a chunk whose chunk_roots entry is 0, get_voxel is Err and v is
+ * Voxel::EMPTY (0), looked up in the table like any other voxel.
+ * The boxes of Aabb b are gathered as get_collisions_w does: for x in floor(b.from.x)..ceil(b.to.x) { for y { for z, and the
+ * clipping loop takes them in that order (y, then x, then z against the unmoved box, EPSILON = 0.00001): the answer is the
+ * sequential loop's, quirks included — a box that rests on the floor and moves down is answered with +1e-5, not 0.
+ * flags & VRT_BOX_AUTOJUMP is clip_aabb_movement's autojump (Player::update passes true); other bits are ignored.
+ * A query is REJECTED instead of run in two cases, and only then: one of its nine floats is not finite or has a magnitude of
+ * 2^23 or more (every sum of expand and translate then stays below 2^24, where the casts to i32 and p as f32 + 1.0 are exact);
+ * or the first gather's range, (ceil(to) - floor(from)) multiplied over the axes of from/to expanded by mv, holds more than
+ * VRT_BOX_MAX_VOXELS voxels (the reference would allocate without bound; the second gather's range is the same size within one
+ * layer of y). */
+typedef struct {
+    float from[3];   /* Aabb.from */
+    uint32_t flags;  /* VRT_BOX_AUTOJUMP */
+    float to[3];     /* Aabb.to */
+    uint32_t _r0;
+    float mv[3];     /* the movement asked for (Player::update: frame_vel) */
+    uint32_t _r1;
+} vrt_box_query;  /* 48 B */
+#define VRT_BOX_AUTOJUMP 1u
+#define VRT_BOX_MAX_VOXELS 4096u
+
+#define VRT_BOX_MOVED 0u    /* ran; mv = mv_clipped */
+#define VRT_BOX_REJECTED 2u /* every other field is 0 */
+#define VRT_BOX_CLIPPED_X 1u /* vrt_box_move.flags: mv_clipped != mv on that axis after the first pass (!eq, -0 == 0) */
+#define VRT_BOX_CLIPPED_Y 2u
+#define VRT_BOX_CLIPPED_Z 4u
+#define VRT_BOX_STEPPED_UP 8u /* the autojump was taken: mv.y = clipped y + 1.0, mv.x / mv.z are the second pass's */
+typedef struct {
+    float mv[3];       /* clip_aabb_movement's result */
+    uint32_t status;   /* VRT_BOX_MOVED or VRT_BOX_REJECTED */
+    uint32_t flags;    /* VRT_BOX_CLIPPED_* | VRT_BOX_STEPPED_UP */
+    uint32_t boxes[2]; /* boxes[p]: the solid voxels pass p gathered (boxes[1] = 0 when the second pass did not run) */
+    uint32_t _reserved;
+} vrt_box_move;  /* 32 B */
+
+/* n queries from host memory, n results into host memory; ordering and scope are vrt_cast_rays's: on the context's stream behind
+ * every earlier call — a clip sees every vrt_write_nodes, vrt_write_chunk_roots and vrt_write_materials before it, with no frame
+ * in between — waiting for its own work only, and leaving everything a frame left behind (vrt_read_output, vrt_present*,
+ * vrt_get_stats, the accumulation) as it was.  n = 0 does nothing.  A multi-device context answers on device_ids[0]; a sharded
+ * context holds the whole world and answers alone. */
+int vrt_clip_moves(vrt_ctx *ctx, const vrt_box_query *queries, uint32_t n, vrt_box_move *out);
+/* The same with device memory (n vrt_box_query in, n vrt_box_move out, 4-byte aligned), asynchronous on the context's stream. */
+int vrt_clip_moves_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
+
 /* ---- the chunk source: world generation on the device ---- */
 
 /* What the server answers request_missing_chunks with (client/src/lib.rs:80-118: GiveChunkData -> create_chunk), built on

@@ -6,6 +6,7 @@
  *   Node, Voxel, NodeAlloc, Svo                 common/src/world/mod.rs:137-471
  *   CamData::create, WorldData::from            clientdesktop/src/graphics/mod.rs:92-130
  *   axis_rot_to_ray                             common/src/math.rs:131-146
+ *   Aabb, get_collisions_w, clip_aabb_movement  common/src/math.rs:5-126, client/src/world.rs:369-391, client/src/player.rs:202-244
  * plus the build's deterministic world generator (no reference counterpart can be
  * reproduced: server/src/world/gen.rs uses an unseeded global RNG).
  * No GPU is needed for anything here.  Error codes are SetVoxelErr (common/src/world/mod.rs:129-135):
@@ -90,6 +91,22 @@ const char *vrth_std_voxel_name(uint32_t id);
 int vrth_world_cast_ray(const vrth_world *w, const float start[3], const float dir[3], float max_dist, vrt_ray_hit *out);
 /* n of them; threads <= 0: all cores.  The world must not change meanwhile. */
 void vrth_world_cast_rays(const vrth_world *w, const vrt_ray_query *queries, uint32_t n, vrt_ray_hit *out, int threads);
+
+/* ---- collisions: what Player::update asks the world (clientdesktop/src/main.rs:316-319); csrc/host/collide.hpp ---- */
+/* ClientWorld::get_collisions_w (client/src/world.rs:369-391) for Aabb [from, to]: the voxels v with
+ * mats256[min(v, 255)].is_empty == 0 && .is_liquid == 0 (voxelpack.get(v).is_solid()), Voxel::EMPTY where get_voxel is Err, in
+ * the order of `for x { for y { for z`; each stands for the box [p, p + 1].  Writes min(cap, *n) positions (x, y, z each) and the
+ * whole count to *n.  Returns 0, or -1 with *n = 0 where vrt_clip_moves would reject (a float that is not finite or is 2^23 or
+ * more in magnitude, a range of more than VRT_BOX_MAX_VOXELS voxels) or for a null argument. */
+int vrth_world_get_collisions(const vrth_world *w, const float from[3], const float to[3], const vrt_material *mats256, int32_t *out_xyz,
+                              uint32_t cap, uint32_t *n);
+/* clip_aabb_movement (client/src/player.rs:202-244) over get_collisions_w and Aabb::clip_*_collide (common/src/math.rs:50-115)
+ * in strict binary32: the CPU twin of vrt_clip_moves (include/vrt.h), with the same rejections and the same record.
+ * Returns out->status. */
+int vrth_world_clip_move(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *query, vrt_box_move *out);
+/* n of them; threads <= 0: all cores.  The world must not change meanwhile. */
+void vrth_world_clip_moves(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *queries, uint32_t n, vrt_box_move *out,
+                           int threads);
 
 /* ---- SVO construction ---- */
 /* Svo::set_node driven the way server/src/world/gen.rs:171-286 drives it (x, z, y ascending, air

@@ -93,15 +93,35 @@ class RayHit(C.Structure):
     _fields_ = [("pos", C.c_int32 * 3), ("face", C.c_int32 * 3), ("dist", C.c_float), ("status", C.c_uint32)]
 
 
+class BoxQuery(C.Structure):
+    """include/vrt.h vrt_box_query: clip_aabb_movement's arguments (client/src/player.rs:202-207)"""
+    _fields_ = [("from_", C.c_float * 3), ("flags", C.c_uint32), ("to", C.c_float * 3), ("_r0", C.c_uint32),
+                ("mv", C.c_float * 3), ("_r1", C.c_uint32)]
+
+
+class BoxMove(C.Structure):
+    """include/vrt.h vrt_box_move: mv_clipped plus a status, what was clipped and how many boxes each pass gathered"""
+    _fields_ = [("mv", C.c_float * 3), ("status", C.c_uint32), ("flags", C.c_uint32), ("boxes", C.c_uint32 * 2),
+                ("_reserved", C.c_uint32)]
+
+
 RAY_MISS, RAY_HIT, RAY_REJECTED = 0, 1, 2
+BOX_AUTOJUMP, BOX_MAX_VOXELS = 1, 4096                      # vrt_box_query.flags, the cap on the first gather's range
+BOX_MOVED, BOX_REJECTED = 0, 2                              # vrt_box_move.status
+BOX_CLIPPED_X, BOX_CLIPPED_Y, BOX_CLIPPED_Z, BOX_STEPPED_UP = 1, 2, 4, 8   # vrt_box_move.flags
 # the same records as numpy structured dtypes (32 bytes each)
 RAY_QUERY_DTYPE = np.dtype([("start", "<f4", 3), ("max_dist", "<f4"), ("dir", "<f4", 3), ("_reserved", "<u4")])
 RAY_HIT_DTYPE = np.dtype([("pos", "<i4", 3), ("face", "<i4", 3), ("dist", "<f4"), ("status", "<u4")])
+# ... and the box records (48 and 32 bytes)
+BOX_QUERY_DTYPE = np.dtype([("from", "<f4", 3), ("flags", "<u4"), ("to", "<f4", 3), ("_r0", "<u4"), ("mv", "<f4", 3), ("_r1", "<u4")])
+BOX_MOVE_DTYPE = np.dtype([("mv", "<f4", 3), ("status", "<u4"), ("flags", "<u4"), ("boxes", "<u4", 2), ("_reserved", "<u4")])
 
 
 assert C.sizeof(Material) == 32 and C.sizeof(CamData) == 160
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 32
 assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 32
+assert C.sizeof(BoxQuery) == 48 and C.sizeof(BoxMove) == 32
+assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
@@ -153,6 +173,8 @@ VRT_SYMBOLS = {
     "vrt_assemble_compact": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "vrt_cast_rays": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_cast_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_clip_moves": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_clip_moves_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_generate_chunks": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "vrt_build_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P]),
 }
@@ -279,6 +301,9 @@ VRTH_SYMBOLS = {
     "vrth_world_data_from": (None, [_P, C.POINTER(WorldData)]),
     "vrth_world_cast_ray": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(RayHit)]),
     "vrth_world_cast_rays": (None, [_P, _P, C.c_uint32, _P, C.c_int]),
+    "vrth_world_get_collisions": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, C.c_uint32, _U32P]),
+    "vrth_world_clip_move": (C.c_int, [_P, _P, C.POINTER(BoxQuery), C.POINTER(BoxMove)]),
+    "vrth_world_clip_moves": (None, [_P, _P, _P, C.c_uint32, _P, C.c_int]),
     "vrth_world_create_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _U32P]),
     "vrth_cam_data_create": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(CamData)]),
     "vrth_axis_rot_to_ray": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -89,7 +89,8 @@ struct WorldData : vrt_world_data {
     }
 };
 
-// Player camera fields, client/src/player.rs:31-70 (physics is out of scope)
+// Player camera fields, client/src/player.rs:31-70.  What Player::update asks the world — clip_aabb_movement over
+// get_collisions_w — is collide.hpp (vrth_world_clip_move; on the GPU vrt_clip_moves); process_input and the camera easing are not here
 struct Player {
     float fov = 70.0f;
     Vec3 pos, cam_pos_, rot;  // rot in degrees

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "../../../include/vrt_host.h"
+#include "collide.hpp"
 #include "graphics.hpp"
 #include "materials.hpp"
 #include "netmsg.hpp"
@@ -207,6 +208,53 @@ int vrth_world_chunk_state(const vrth_world *w, const int32_t chunk_pos[3], uint
         spans[2 * i + 1] = fm[i].end;
     }
     return (int)fm.size();
+}
+
+// ---- collisions (collide.hpp) ----
+int vrth_world_get_collisions(const vrth_world *w, const float from[3], const float to[3], const vrt_material *mats256, int32_t *out_xyz,
+                              uint32_t cap, uint32_t *n) {
+    if (n) *n = 0;
+    if (!w || !from || !to || !mats256) return -1;
+    for (int a = 0; a < 3; a++)
+        if (!(std::fabs(from[a]) < 8388608.0f) || !(std::fabs(to[a]) < 8388608.0f)) return -1;
+    const Aabb bb{{from[0], from[1], from[2]}, {to[0], to[1], to[2]}};
+    if (collisions_range(bb) > VRT_BOX_MAX_VOXELS) return -1;
+    const std::vector<VoxelPos> v = get_collisions_w(w->w, bb, mats256);
+    for (size_t i = 0; i < v.size() && i < cap && out_xyz; i++) {
+        out_xyz[3 * i] = v[i].x; out_xyz[3 * i + 1] = v[i].y; out_xyz[3 * i + 2] = v[i].z;
+    }
+    if (n) *n = (uint32_t)v.size();
+    return 0;
+}
+
+int vrth_world_clip_move(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *q, vrt_box_move *out) {
+    vrt_box_move r;
+    clip_aabb_movement(w->w, mats256, *q, r);
+    if (out) *out = r;
+    return (int)r.status;
+}
+
+void vrth_world_clip_moves(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *q, uint32_t n, vrt_box_move *out, int threads) {
+    if (!w || !mats256 || !q || !out || !n) return;
+    unsigned nt = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
+    nt = (unsigned)std::min<uint64_t>(nt, (n + 1023u) / 1024u);
+    std::atomic<uint32_t> next{0};
+    auto work = [&]() {
+        for (;;) {
+            const uint32_t i0 = next.fetch_add(1024u);
+            if (i0 >= n) return;
+            const uint32_t i1 = std::min<uint64_t>((uint64_t)i0 + 1024u, n);
+            for (uint32_t i = i0; i < i1; i++) clip_aabb_movement(w->w, mats256, q[i], out[i]);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
+    } catch (const std::system_error &) {
+        // no more threads to be had: the ones that started (and this one) do the work
+    }
+    work();
+    for (auto &t : pool) t.join();
 }
 
 int vrth_world_highest_vox_at(const vrth_world *w, int32_t x, int32_t z, int32_t *y_out) {

@@ -326,6 +326,9 @@ struct vrt_ctx {
     void *d_cast = nullptr;
     uint32_t cast_cap = 0;
     hipEvent_t ev_cast = nullptr;
+    // vrt_clip_moves (vrt_clip.hip): the same for clip_cap boxes; a host clip waits on ev_cast as a host cast does
+    void *d_clip = nullptr;
+    uint32_t clip_cap = 0;
 
     // vrt_generate_chunks / vrt_build_chunks (vrt_gen.hip): one batch's staging slots, node counts, offsets and inputs (made on
     // first use), and the compacted nodes of a whole call (grown as needed)

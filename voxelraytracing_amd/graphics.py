@@ -283,6 +283,19 @@ class Gpu:
         context's stream (vrt_set_stream) without waiting."""
         self._ck(self._lib.vrt_cast_rays_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
 
+    def clip_moves(self, queries: np.ndarray) -> np.ndarray:
+        """clip_aabb_movement (player.rs:202-244) for every box at once on the GPU, against the world and the material table as of
+        every write so far: _ffi.BOX_QUERY_DTYPE records (world.box_queries) in, _ffi.BOX_MOVE_DTYPE records out."""
+        q = np.ascontiguousarray(queries, _ffi.BOX_QUERY_DTYPE)
+        out = np.zeros(q.size, _ffi.BOX_MOVE_DTYPE)
+        self._ck(self._lib.vrt_clip_moves(self._h, q.ctypes.data, q.size, out.ctypes.data))
+        return out
+
+    def clip_moves_device(self, queries_ptr: int, n: int, out_ptr: int):
+        """vrt_clip_moves_device: n vrt_box_query records at a device address in, n vrt_box_move records out, enqueued on the
+        context's stream (vrt_set_stream) without waiting."""
+        self._ck(self._lib.vrt_clip_moves_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
+
     # --- the chunk source (include/vrt.h vrt_generate_chunks / vrt_build_chunks) ---
     def generate_chunks(self, seed: int, positions, strict: bool = True):
         """The build's world generator on the GPU (csrc/host/worldgen.hpp): (n,3) chunk positions -> (nodes, offsets), chunk i's

@@ -136,6 +136,35 @@ class ClientWorld:
             self._lib.vrth_world_cast_rays(self._h, q.ctypes.data, q.size, out.ctypes.data, threads)
         return out
 
+    # --- collisions (csrc/host/collide.hpp): materials is a (Material * 256) table, e.g. graphics.std_materials() ---
+    def get_collisions(self, from_, to, materials) -> np.ndarray:
+        """ClientWorld::get_collisions_w(&Aabb::new(from, to), voxelpack) — world.rs:369-391: the (n,3) integer positions of
+        the solid voxels (each stands for the box [p, p + 1]) in the reference's order.  ValueError where vrt_clip_moves
+        would reject the box (include/vrt.h)."""
+        f3 = lambda v: (C.c_float * 3)(*[float(c) for c in v])  # noqa: E731
+        n = C.c_uint32()
+        out = np.zeros((_ffi.BOX_MAX_VOXELS, 3), np.int32)
+        if self._lib.vrth_world_get_collisions(self._h, f3(from_), f3(to), C.cast(materials, C.c_void_p), out.ctypes.data, out.shape[0],
+                                               C.byref(n)):
+            raise ValueError(f"get_collisions rejected: {tuple(from_)} .. {tuple(to)} (|v| < 2^23, at most {_ffi.BOX_MAX_VOXELS} voxels)")
+        return out[:n.value].copy()
+
+    def clip_move(self, from_, to, mv, materials, autojump: bool = True) -> _ffi.BoxMove:
+        """clip_aabb_movement(Aabb::new(from, to), mv, |bb| get_collisions_w(bb), autojump) — player.rs:202-244 in strict binary32
+        (vrth_world_clip_move): the whole vrt_box_move record; .mv is the reference's answer when .status is BOX_MOVED."""
+        q = box_queries([from_], [to], [mv], autojump)
+        out = _ffi.BoxMove()
+        self._lib.vrth_world_clip_move(self._h, C.cast(materials, C.c_void_p), C.cast(q.ctypes.data, C.POINTER(_ffi.BoxQuery)), C.byref(out))
+        return out
+
+    def clip_moves(self, queries: np.ndarray, materials, threads: int = 0) -> np.ndarray:
+        """Many of them on the CPU (vrth_world_clip_moves): _ffi.BOX_QUERY_DTYPE records (box_queries) in, _ffi.BOX_MOVE_DTYPE out."""
+        q = np.ascontiguousarray(queries, _ffi.BOX_QUERY_DTYPE)
+        out = np.zeros(q.size, _ffi.BOX_MOVE_DTYPE)
+        if q.size:
+            self._lib.vrth_world_clip_moves(self._h, C.cast(materials, C.c_void_p), q.ctypes.data, q.size, out.ctypes.data, threads)
+        return out
+
     def center_chunks(self, anchor) -> int:
         return self._lib.vrth_world_center_chunks(self._h, _i3(anchor))
 
@@ -329,6 +358,17 @@ def ray_queries(starts, dirs, max_dist) -> np.ndarray:
     q["start"] = starts
     q["dir"] = dirs
     q["max_dist"] = np.broadcast_to(np.asarray(max_dist, np.float32), (starts.shape[0],))
+    return q
+
+
+def box_queries(froms, tos, mvs, autojump=True) -> np.ndarray:
+    """vrt_box_query records (_ffi.BOX_QUERY_DTYPE) from (n,3) box corners and movements, all as float32; autojump: a bool or (n,)."""
+    froms = np.asarray(froms, np.float32).reshape(-1, 3)
+    q = np.zeros(froms.shape[0], _ffi.BOX_QUERY_DTYPE)
+    q["from"] = froms
+    q["to"] = np.asarray(tos, np.float32).reshape(-1, 3)
+    q["mv"] = np.asarray(mvs, np.float32).reshape(-1, 3)
+    q["flags"] = np.where(np.broadcast_to(np.asarray(autojump, bool), q.shape), _ffi.BOX_AUTOJUMP, 0)
     return q
 
 
