@@ -259,6 +259,23 @@ def test_world_generator_is_deterministic_and_consistent():
     assert np.array_equal(w1.nodes(), w.nodes()) and np.array_equal(w1.chunk_roots(), w.chunk_roots())
 
 
+def test_world_generator_known_answers():
+    """The host generator against vectors recorded before its arithmetic moved into the header that the GPU generator compiles
+    too (tests/golden/make_gen_pin.py): heights on both sides of every lattice-cell border, negative and far coordinates, and
+    the CRC-32 of whole chunks with trees, water, sand and snow, and of chunks whose y is within 6 of -2^26."""
+    import os
+    import zlib
+    pin = np.load(os.path.join(os.path.dirname(__file__), "golden", "gen_pin.npz"))
+    pts, want_h = pin["height_points"], pin["heights"]
+    assert len(pts) >= 300 and (pts[:, 1:] < 0).any()
+    got_h = np.array([W.gen_height(int(s), int(x), int(z)) for s, x, z in pts], dtype=np.int32)
+    assert np.array_equal(got_h, want_h), pts[got_h != want_h][:8]
+    chunks, want_crc = pin["chunks"], pin["dense_crc32"]
+    assert len(chunks) >= 36
+    got_crc = np.array([zlib.crc32(W.gen_dense(int(s), (int(x), int(y), int(z))).tobytes()) for s, x, y, z in chunks], dtype=np.uint32)
+    assert np.array_equal(got_crc, want_crc), chunks[got_crc != want_crc][:8]
+
+
 def test_untrusted_chunk_payloads_are_refused():
     """create_chunk walks a payload with its own child indices: a split node pointing outside the payload, or an empty
     payload, is BadChunkData (the reference would panic on the slice bound when the chunk is first walked) — through

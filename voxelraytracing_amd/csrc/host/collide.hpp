@@ -1,71 +1,35 @@
 // collide.hpp — the client's collisions on the host: Aabb (common/src/math.rs:5-126), ClientWorld::get_collisions_w
 // (client/src/world.rs:369-391) and clip_aabb_movement (client/src/player.rs:202-244), restated line for line over
-// ClientWorld::get_voxel.  The CPU twin of vrt_clip_moves (include/vrt.h): same rejections, same record.  Built with
+// ClientWorld::get_voxel.  The CPU twin of vrt_clip_moves (include/vrt.h): same rejections, same record, and the same text for
+// the Aabb arithmetic (../both/aabb_clip.h, which vrt_clip.hip compiles too); the list here and the kernel's fused walk stay apart.  Built with
 // -ffp-contract=off (Makefile): every float operation is one correctly rounded binary32 operation, in the reference's order.
 #pragma once
 #include <cmath>
 #include <vector>
 
+#include "../both/aabb_clip.h"
 #include "graphics.hpp"
 
 namespace vrt {
 
-constexpr float EPSILON = 0.00001f;  // math.rs:3
-
-struct Aabb {  // math.rs:5-126
+struct Aabb {  // math.rs:5-126, over ../both/aabb_clip.h's axes
     Vec3 from, to;
 
     Aabb expand(Vec3 a) const {
-        Vec3 f = from, t = to;
-        if (a.x < 0.0f) f.x += a.x;
-        if (a.x > 0.0f) t.x += a.x;
-        if (a.y < 0.0f) f.y += a.y;
-        if (a.y > 0.0f) t.y += a.y;
-        if (a.z < 0.0f) f.z += a.z;
-        if (a.z > 0.0f) t.z += a.z;
-        return {f, t};
+        Aabb r = *this;
+        aabb_expand(r.from.x, r.to.x, a.x);
+        aabb_expand(r.from.y, r.to.y, a.y);
+        aabb_expand(r.from.z, r.to.z, a.z);
+        return r;
     }
     Aabb translate(Vec3 a) const { return {{from.x + a.x, from.y + a.y, from.z + a.z}, {to.x + a.x, to.y + a.y, to.z + a.z}}; }
 
-    float clip_x_collide(const Aabb &c, float a) const {
-        if (c.to.y <= from.y || c.from.y >= to.y) return a;
-        if (c.to.z <= from.z || c.from.z >= to.z) return a;
-        if (a > 0.0f && c.to.x <= from.x) {
-            const float max = from.x - c.to.x - EPSILON;
-            if (max < a) a = max;
-        }
-        if (a < 0.0f && c.from.x >= to.x) {
-            const float max = to.x - c.from.x + EPSILON;
-            if (max > a) a = max;
-        }
-        return a;
-    }
-    float clip_y_collide(const Aabb &c, float a) const {
-        if (c.to.x <= from.x || c.from.x >= to.x) return a;
-        if (c.to.z <= from.z || c.from.z >= to.z) return a;
-        if (a > 0.0f && c.to.y <= from.y) {
-            const float max = from.y - c.to.y - EPSILON;
-            if (max < a) a = max;
-        }
-        if (a < 0.0f && c.from.y >= to.y) {
-            const float max = to.y - c.from.y + EPSILON;
-            if (max > a) a = max;
-        }
-        return a;
-    }
-    float clip_z_collide(const Aabb &c, float a) const {
-        if (c.to.x <= from.x || c.from.x >= to.x) return a;
-        if (c.to.y <= from.y || c.from.y >= to.y) return a;
-        if (a > 0.0f && c.to.z <= from.z) {
-            const float max = from.z - c.to.z - EPSILON;
-            if (max < a) a = max;
-        }
-        if (a < 0.0f && c.from.z >= to.z) {
-            const float max = to.z - c.from.z + EPSILON;
-            if (max > a) a = max;
-        }
-        return a;
-    }
+    bool overlap_x(const Aabb &c) const { return aabb_overlap(from.x, to.x, c.from.x, c.to.x); }
+    bool overlap_y(const Aabb &c) const { return aabb_overlap(from.y, to.y, c.from.y, c.to.y); }
+    bool overlap_z(const Aabb &c) const { return aabb_overlap(from.z, to.z, c.from.z, c.to.z); }
+    float clip_x_collide(const Aabb &c, float a) const { return overlap_y(c) && overlap_z(c) ? clip_axis(a, from.x, to.x, c.from.x, c.to.x) : a; }
+    float clip_y_collide(const Aabb &c, float a) const { return overlap_x(c) && overlap_z(c) ? clip_axis(a, from.y, to.y, c.from.y, c.to.y) : a; }
+    float clip_z_collide(const Aabb &c, float a) const { return overlap_x(c) && overlap_y(c) ? clip_axis(a, from.z, to.z, c.from.z, c.to.z) : a; }
 };
 
 // voxelpack.get(voxel).is_solid() (common/src/resources/mod.rs:309) as the material table holds it: Material::construct
@@ -90,17 +54,11 @@ inline std::vector<VoxelPos> get_collisions_w(const ClientWorld &w, const Aabb &
     return out;
 }
 
-// The voxels of get_collisions_w's loops for `aabb`, 0 for an empty or inverted range, saturating at 2^32 - 1
-inline uint64_t collisions_range(const Aabb &aabb) {
-    const int64_t nx = (int64_t)std::ceil(aabb.to.x) - (int64_t)std::floor(aabb.from.x);
-    const int64_t ny = (int64_t)std::ceil(aabb.to.y) - (int64_t)std::floor(aabb.from.y);
-    const int64_t nz = (int64_t)std::ceil(aabb.to.z) - (int64_t)std::floor(aabb.from.z);
-    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
-    const int64_t cap = 0xFFFFFFFFll;
-    if (nx > cap || ny > cap || nz > cap) return (uint64_t)cap;
-    const uint64_t xy = (uint64_t)nx * (uint64_t)ny;
-    if (xy > (uint64_t)cap || xy * (uint64_t)nz > (uint64_t)cap) return (uint64_t)cap;
-    return xy * (uint64_t)nz;
+// get_collisions_w's loops for `aabb` would gather more than VRT_BOX_MAX_VOXELS voxels (every coordinate passed clip_in_range)
+inline bool collisions_over_cap(const Aabb &aabb) {
+    const int32_t nx = (int32_t)ceilf(aabb.to.x) - (int32_t)floorf(aabb.from.x), ny = (int32_t)ceilf(aabb.to.y) - (int32_t)floorf(aabb.from.y),
+                  nz = (int32_t)ceilf(aabb.to.z) - (int32_t)floorf(aabb.from.z);
+    return nx > 0 && ny > 0 && nz > 0 && clip_range_over(nx, ny, nz, VRT_BOX_MAX_VOXELS);   // an empty or inverted range: no boxes
 }
 
 // clip_aabb_movement, player.rs:202-244, with world = |bb| get_collisions_w(bb); the record is include/vrt.h's
@@ -108,11 +66,11 @@ inline void clip_aabb_movement(const ClientWorld &w, const Material *mats256, co
     std::memset(&r, 0, sizeof r);
     r.status = VRT_BOX_REJECTED;
     for (int a = 0; a < 3; a++)
-        if (!(std::fabs(q.from[a]) < 8388608.0f) || !(std::fabs(q.to[a]) < 8388608.0f) || !(std::fabs(q.mv[a]) < 8388608.0f)) return;
+        if (!clip_in_range(q.from[a]) || !clip_in_range(q.to[a]) || !clip_in_range(q.mv[a])) return;
     Aabb bbox{{q.from[0], q.from[1], q.from[2]}, {q.to[0], q.to[1], q.to[2]}};
     const Vec3 mv{q.mv[0], q.mv[1], q.mv[2]};
     const bool autojump = (q.flags & VRT_BOX_AUTOJUMP) != 0u;
-    if (collisions_range(bbox.expand(mv)) > VRT_BOX_MAX_VOXELS) return;   // (the reference would allocate without bound)
+    if (collisions_over_cap(bbox.expand(mv))) return;   // (the reference would allocate without bound)
 
     auto to_aabb = [](VoxelPos p) {
         const Vec3 min{(float)p.x, (float)p.y, (float)p.z};

@@ -1,4 +1,5 @@
-// host_capi.cpp — include/vrt_host.h over the C++ host mirror (world.hpp, graphics.hpp, worldgen.hpp).
+// host_capi.cpp — include/vrt_host.h over the C++ host mirror (world.hpp, graphics.hpp, worldgen.hpp, collide.hpp) and the
+// arithmetic it shares with the kernels (../both/).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -7,6 +8,7 @@
 #include <thread>
 
 #include "../../../include/vrt_host.h"
+#include "../both/cast_dda.h"
 #include "collide.hpp"
 #include "graphics.hpp"
 #include "materials.hpp"
@@ -22,6 +24,29 @@ struct vrth_world {
 };
 
 static ChunkPos cp3(const int32_t p[3]) { return {p[0], p[1], p[2]}; }
+
+// fn(i0, i1) over [0, n) in blocks of `block`, handed out to `threads` workers (<= 0: one per hardware thread, at most
+// cap_threads), this thread among them; fn returns false to end its worker.
+template <class Fn>
+static void parallel_blocks(size_t n, size_t block, int threads, unsigned cap_threads, Fn fn) {
+    unsigned nt = threads > 0 ? (unsigned)threads : std::min(cap_threads, std::max(1u, std::thread::hardware_concurrency()));
+    nt = (unsigned)std::min<size_t>(nt, (n + block - 1) / block);
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+        for (;;) {
+            const size_t i0 = next.fetch_add(block);
+            if (i0 >= n || !fn(i0, std::min(i0 + block, n))) return;
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
+    } catch (const std::system_error &) {
+        // no more threads to be had: the ones that started (and this one) do the work
+    }
+    work();
+    for (auto &t : pool) t.join();
+}
 
 extern "C" {
 
@@ -64,73 +89,30 @@ int vrth_world_get_voxel(const vrth_world *w, const int32_t p[3], uint16_t *voxe
     return (int)e;
 }
 
-// common::math::cast_ray, common/src/math.rs:153-226, with the client's collides (clientdesktop/src/main.rs:320-325).  This file is
-// built with -ffp-contract=off (Makefile): every float operation below is one correctly rounded binary32 operation, in the order
-// the reference writes it.
+// common::math::cast_ray from ../both/cast_dda.h's parts (the text the GPU's cast compiles too) with the client's collides
+// (clientdesktop/src/main.rs:320-325).  This file is built with -ffp-contract=off (Makefile).
 int vrth_world_cast_ray(const vrth_world *w, const float start[3], const float dir[3], float max_dist, vrt_ray_hit *out) {
     vrt_ray_hit r;
     memset(&r, 0, sizeof r);
-    // The reference loops forever on max_dist = inf, and start.floor().as_ivec3() / map_check += step leave i32 (or the exact
-    // integers of f32) beyond 2^24: such a query is rejected, not run (include/vrt.h).
-    if (max_dist > 1048576.0f || !(std::fabs(start[0]) < 16777216.0f) || !(std::fabs(start[1]) < 16777216.0f) ||
-        !(std::fabs(start[2]) < 16777216.0f)) {
+    if (cast_rejected(start, max_dist)) {
         r.status = VRT_RAY_REJECTED;
-        if (out) *out = r;
-        return (int)r.status;
-    }
-    const float dx = dir[0], dy = dir[1], dz = dir[2];
-    const float usx = std::sqrt(1.0f + (dy / dx) * (dy / dx) + (dz / dx) * (dz / dx));
-    const float usy = std::sqrt(1.0f + (dx / dy) * (dx / dy) + (dz / dy) * (dz / dy));
-    const float usz = std::sqrt(1.0f + (dx / dz) * (dx / dz) + (dy / dz) * (dy / dz));
-    int32_t m[3] = {(int32_t)std::floor(start[0]), (int32_t)std::floor(start[1]), (int32_t)std::floor(start[2])};
-    int32_t step[3];
-    float len[3];
-    const float us[3] = {usx, usy, usz};
-    for (int a = 0; a < 3; a++) {
-        if (dir[a] < 0.0f) {
-            step[a] = -1;
-            len[a] = (start[a] - (float)m[a]) * us[a];
-        } else {
-            step[a] = 1;
-            len[a] = ((float)(m[a] + 1) - start[a]) * us[a];
+    } else {
+        const VoxelPos lo = w->w.min_voxel();
+        const int32_t lo3[3] = {lo.x, lo.y, lo.z};
+        CastDda d = cast_setup(start, dir);
+        float dist = 0.0f;
+        while (dist < max_dist) {
+            const int32_t px = d.mx, py = d.my, pz = d.mz;
+            dist = cast_step(d);
+            Voxel v;
+            const bool in_world = w->w.get_voxel(VoxelPos{d.mx, d.my, d.mz}, v) == SetVoxelErr::Ok;
+            if (in_world && !v.is_empty()) {
+                cast_hit(r, d, px, py, pz, dist);
+                r.status = VRT_RAY_HIT;
+                break;
+            }
+            if (!in_world && cast_gone(d, lo3, w->w.size_in_voxels())) break;   // (an Err is also a missing chunk: cast_gone says no inside)
         }
-    }
-    const VoxelPos lo = w->w.min_voxel(), hi = w->w.max_voxel();
-    const int32_t lo3[3] = {lo.x, lo.y, lo.z}, hi3[3] = {hi.x, hi.y, hi.z};
-    float dist = 0.0f;
-    while (dist < max_dist) {
-        const int32_t prev[3] = {m[0], m[1], m[2]};
-        if (len[0] < len[1] && len[0] < len[2]) {
-            m[0] += step[0];
-            dist = len[0];
-            len[0] += usx;
-        } else if (len[2] < len[0] && len[2] < len[1]) {
-            m[2] += step[2];
-            dist = len[2];
-            len[2] += usz;
-        } else {
-            m[1] += step[1];
-            dist = len[1];
-            len[1] += usy;
-        }
-        Voxel v;
-        if (w->w.get_voxel(VoxelPos{m[0], m[1], m[2]}, v) == SetVoxelErr::Ok && !v.is_empty()) {
-            r.pos[0] = m[0]; r.pos[1] = m[1]; r.pos[2] = m[2];
-            r.face[0] = prev[0] - m[0]; r.face[1] = prev[1] - m[1]; r.face[2] = prev[2] - m[2];
-            r.dist = dist == dist ? dist : NAN;   // (one NaN for every platform: include/vrt.h)
-            r.status = VRT_RAY_HIT;
-            break;
-        }
-        // Not in the reference, and no change to any result: an axis moves only by its own step, so a voxel outside the world
-        // on an axis whose step leads away from it is followed by voxels outside on that axis, none of which collides.  (The
-        // x and z branches need len < the others: a len that is NaN or inf never takes them, that axis never moves at all.)
-        bool gone = false;
-        for (int a = 0; a < 3; a++) {
-            const bool below = m[a] < lo3[a], above = m[a] >= hi3[a];
-            const bool frozen = a != 1 && !(len[a] < INFINITY);
-            gone = gone || (below && (step[a] < 0 || frozen)) || (above && (step[a] > 0 || frozen));
-        }
-        if (gone) break;
     }
     if (out) *out = r;
     return (int)r.status;
@@ -138,25 +120,10 @@ int vrth_world_cast_ray(const vrth_world *w, const float start[3], const float d
 
 void vrth_world_cast_rays(const vrth_world *w, const vrt_ray_query *q, uint32_t n, vrt_ray_hit *out, int threads) {
     if (!w || !q || !out || !n) return;
-    unsigned nt = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
-    nt = (unsigned)std::min<uint64_t>(nt, (n + 1023u) / 1024u);
-    std::atomic<uint32_t> next{0};
-    auto work = [&]() {
-        for (;;) {
-            const uint32_t i0 = next.fetch_add(1024u);
-            if (i0 >= n) return;
-            const uint32_t i1 = std::min<uint64_t>((uint64_t)i0 + 1024u, n);
-            for (uint32_t i = i0; i < i1; i++) vrth_world_cast_ray(w, q[i].start, q[i].dir, q[i].max_dist, &out[i]);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
-    } catch (const std::system_error &) {
-        // no more threads to be had: the ones that started (and this one) do the work
-    }
-    work();
-    for (auto &t : pool) t.join();
+    parallel_blocks(n, 1024, threads, ~0u, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) vrth_world_cast_ray(w, q[i].start, q[i].dir, q[i].max_dist, &out[i]);
+        return true;
+    });
 }
 
 uint32_t vrth_world_center_chunks(vrth_world *w, const int32_t anchor_chunk[3]) {
@@ -216,9 +183,9 @@ int vrth_world_get_collisions(const vrth_world *w, const float from[3], const fl
     if (n) *n = 0;
     if (!w || !from || !to || !mats256) return -1;
     for (int a = 0; a < 3; a++)
-        if (!(std::fabs(from[a]) < 8388608.0f) || !(std::fabs(to[a]) < 8388608.0f)) return -1;
+        if (!clip_in_range(from[a]) || !clip_in_range(to[a])) return -1;
     const Aabb bb{{from[0], from[1], from[2]}, {to[0], to[1], to[2]}};
-    if (collisions_range(bb) > VRT_BOX_MAX_VOXELS) return -1;
+    if (collisions_over_cap(bb)) return -1;
     const std::vector<VoxelPos> v = get_collisions_w(w->w, bb, mats256);
     for (size_t i = 0; i < v.size() && i < cap && out_xyz; i++) {
         out_xyz[3 * i] = v[i].x; out_xyz[3 * i + 1] = v[i].y; out_xyz[3 * i + 2] = v[i].z;
@@ -236,25 +203,10 @@ int vrth_world_clip_move(const vrth_world *w, const vrt_material *mats256, const
 
 void vrth_world_clip_moves(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *q, uint32_t n, vrt_box_move *out, int threads) {
     if (!w || !mats256 || !q || !out || !n) return;
-    unsigned nt = threads > 0 ? (unsigned)threads : std::max(1u, std::thread::hardware_concurrency());
-    nt = (unsigned)std::min<uint64_t>(nt, (n + 1023u) / 1024u);
-    std::atomic<uint32_t> next{0};
-    auto work = [&]() {
-        for (;;) {
-            const uint32_t i0 = next.fetch_add(1024u);
-            if (i0 >= n) return;
-            const uint32_t i1 = std::min<uint64_t>((uint64_t)i0 + 1024u, n);
-            for (uint32_t i = i0; i < i1; i++) clip_aabb_movement(w->w, mats256, q[i], out[i]);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
-    } catch (const std::system_error &) {
-        // no more threads to be had: the ones that started (and this one) do the work
-    }
-    work();
-    for (auto &t : pool) t.join();
+    parallel_blocks(n, 1024, threads, ~0u, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) clip_aabb_movement(w->w, mats256, q[i], out[i]);
+        return true;
+    });
 }
 
 int vrth_world_highest_vox_at(const vrth_world *w, int32_t x, int32_t z, int32_t *y_out) {
@@ -340,44 +292,30 @@ static int generate_impl(vrth_world *w, uint32_t kind, uint32_t seed, int thread
             skip[i] = w->w.get_chunk(cp) != nullptr;
         }
     }
-    std::atomic<size_t> next{0};
     std::atomic<int> failed{0};
-    // (at most 16 workers unless asked for more: a chunk is ~0.1 ms of work, and a host with hundreds of hardware threads —
-    // or a limit on tasks per process — gains nothing from one thread per core here)
-    unsigned nt = threads > 0 ? (unsigned)threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    nt = (unsigned)std::min<size_t>(nt, total);
     WorldGen g;
     g.seed = seed;
     const ChunkPos mn = w->w.min_chunk();
-    auto work = [&]() {
-        std::vector<uint16_t> dense(32768);
-        std::vector<Node> scratch(NODES_PER_CHUNK + 64);
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= total) return;
-            if (skip[i]) continue;
-            const ChunkPos cp{mn.x + (int32_t)(i % S), mn.y + (int32_t)((i / S) % S), mn.z + (int32_t)(i / ((size_t)S * S))};
-            if (kind == 1) {
-                fill_dense_superflat(cp, dense.data());
-                // C1 is built the reference's way (set_node, x -> z -> y), holes and all
-                const uint32_t used = build_svo_by_set_node(dense.data(), scratch.data(), (uint32_t)scratch.size());
-                if (!used) { failed = (int)SetVoxelErr::OutOfMemory; return; }
-                built[i].assign(scratch.begin(), scratch.begin() + used);
-            } else {
-                const bool uniform = g.fill_dense(cp, dense.data());
-                if (uniform) built[i].assign(1, Node::make(Voxel(dense[0])));
-                else if (!build_svo_bottom_up(dense.data(), built[i])) { failed = (int)SetVoxelErr::OutOfMemory; return; }
-            }
+    // (at most 16 workers unless asked for more: a chunk is ~0.1 ms of work, and a host with hundreds of hardware threads —
+    // or a limit on tasks per process — gains nothing from one thread per core here)
+    parallel_blocks(total, 1, threads, 16u, [&](size_t i, size_t) {
+        thread_local std::vector<uint16_t> dense(32768);   // one pair of buffers per worker, not per chunk
+        thread_local std::vector<Node> scratch(NODES_PER_CHUNK + 64);
+        if (skip[i]) return true;
+        const ChunkPos cp{mn.x + (int32_t)(i % S), mn.y + (int32_t)((i / S) % S), mn.z + (int32_t)(i / ((size_t)S * S))};
+        if (kind == 1) {
+            fill_dense_superflat(cp, dense.data());
+            // C1 is built the reference's way (set_node, x -> z -> y), holes and all
+            const uint32_t used = build_svo_by_set_node(dense.data(), scratch.data(), (uint32_t)scratch.size());
+            if (!used) { failed = (int)SetVoxelErr::OutOfMemory; return false; }
+            built[i].assign(scratch.begin(), scratch.begin() + used);
+        } else {
+            const bool uniform = g.fill_dense(cp, dense.data());
+            if (uniform) built[i].assign(1, Node::make(Voxel(dense[0])));
+            else if (!build_svo_bottom_up(dense.data(), built[i])) { failed = (int)SetVoxelErr::OutOfMemory; return false; }
         }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (unsigned t = 1; t < nt; t++) pool.emplace_back(work);
-    } catch (const std::system_error &) {
-        // no more threads to be had: the ones that started (and this one) do the work
-    }
-    work();
-    for (auto &t : pool) t.join();
+        return true;
+    });
     if (failed) return failed;
     // create_chunk in grid order (x fastest), so pool layout is deterministic regardless of threads
     uint32_t count = 0;

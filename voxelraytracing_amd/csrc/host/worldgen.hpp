@@ -3,7 +3,8 @@
 // Stands where the reference's server-side generator does (server/src/world/gen.rs:171-286: per-column
 // terrain layers, water up to sea level, tree features), but is build-defined: the reference's generator
 // cannot be reproduced even by itself (third-party Perlin + an unseeded global fastrand, gen.rs:11,263,274).
-// Everything here is integer arithmetic on (seed, x, y, z), so every platform produces the same world.
+// Everything here is integer arithmetic on (seed, x, y, z), so every platform produces the same world — the GPU included, whose
+// generator (vrt_gen.hip) compiles the same text: ../both/worldgen_math.h.
 // The SVO is built bottom-up from a dense 32^3 block and laid out breadth-first: the root, its 8
 // children and their 64 children occupy the first 73 node slots (146 B, two cache lines), which is what
 // every ray's descent touches first.
@@ -12,75 +13,20 @@
 #include <cstdint>
 #include <vector>
 
+#include "../both/worldgen_math.h"
 #include "world.hpp"
 
 namespace vrt {
 
-// voxel ids from stdrespack/voxels.ron (index in the list = id)
-namespace vox {
-constexpr uint16_t AIR = 0, LAVA = 2, WATER = 3, LIMESTONE = 4, SLATE = 5, DIRT = 39, GRASS = 40, SNOW = 45,
-                   SAND = 47, OAK_WOOD = 53, OAK_LEAVES = 62;
-}
-
+// The generator over csrc/both/worldgen_math.h, where its arithmetic (mix .. tree_in_cell), its constants and the voxel ids are
+// written once for this file and for vrt_gen.hip's kernel.
 struct WorldGen {
     uint32_t seed = 1;
-    int32_t h_min = 40, h_max = 200, sea_level = 70, snow_line = 172;
+    using Tree = gen::Tree;
 
-    static uint32_t mix(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-        // PCG-style output permutation over a 4-word key
-        uint32_t h = a * 747796405u + 2891336453u;
-        h = (h ^ b) * 277803737u; h ^= h >> 15;
-        h = (h ^ c) * 2246822519u; h ^= h >> 13;
-        h = (h ^ d) * 3266489917u; h ^= h >> 16;
-        return h;
-    }
-    // lattice value in [0, 65535]
-    uint32_t lattice(int32_t ix, int32_t iz, uint32_t octave) const { return mix(seed, (uint32_t)ix, (uint32_t)iz, octave) >> 16; }
-
-    // value noise at (x,z) with cell size `cell` (power of two), 16.16 fixed point result in [0, 65536)
-    uint32_t value_noise(int32_t x, int32_t z, uint32_t cell_log2, uint32_t octave) const {
-        const int32_t ix = x >> cell_log2, iz = z >> cell_log2;  // floor for negatives too
-        const uint32_t m = (1u << cell_log2) - 1u;
-        const uint64_t tx = ((uint64_t)((uint32_t)x & m) << 16) >> cell_log2, tz = ((uint64_t)((uint32_t)z & m) << 16) >> cell_log2;
-        const uint64_t sx = (tx * tx * (3u * 65536u - 2u * tx)) >> 32, sz = (tz * tz * (3u * 65536u - 2u * tz)) >> 32;  // smoothstep, 0..65536
-        const uint64_t v00 = lattice(ix, iz, octave), v10 = lattice(ix + 1, iz, octave), v01 = lattice(ix, iz + 1, octave),
-                       v11 = lattice(ix + 1, iz + 1, octave);
-        const uint64_t a = (v00 * (65536u - sx) + v10 * sx) >> 16, b = (v01 * (65536u - sx) + v11 * sx) >> 16;
-        return (uint32_t)((a * (65536u - sz) + b * sz) >> 16);
-    }
-
-    // terrain surface height at (x,z): y <= height is ground
-    int32_t height(int32_t x, int32_t z) const {
-        const uint64_t f = (8ull * value_noise(x, z, 7, 0) + 4ull * value_noise(x, z, 6, 1) + 2ull * value_noise(x, z, 5, 2) +
-                            1ull * value_noise(x, z, 4, 3)) / 15ull;  // 0..65535
-        // contrast stretch around the middle (x2.25), clamped
-        int64_t g = ((int64_t)f - 32768) * 9 / 4 + 32768;
-        if (g < 0) g = 0;
-        if (g > 65535) g = 65535;
-        return h_min + (int32_t)(((int64_t)(h_max - h_min) * g) >> 16);
-    }
-
-    // terrain + water only (no trees)
-    uint16_t terrain_at(int32_t h, int32_t y) const {
-        if (y > h) return y <= sea_level ? vox::WATER : vox::AIR;
-        const int32_t layer = h - y;
-        if (layer == 0) return h <= sea_level + 1 ? vox::SAND : (h >= snow_line ? vox::SNOW : vox::GRASS);
-        if (layer <= 4) return h <= sea_level + 1 ? vox::SAND : vox::DIRT;
-        return vox::SLATE;
-    }
-
-    struct Tree { bool present; int32_t x, z, base, trunk; };
-    // one candidate tree per 16x16 cell; offsets 3..12 keep the radius-3 crown inside its cell
-    Tree tree_in_cell(int32_t cx16, int32_t cz16) const {
-        const uint32_t h = mix(seed ^ 0x9E3779B9u, (uint32_t)cx16, (uint32_t)cz16, 77u);
-        Tree t;
-        t.x = cx16 * 16 + 3 + (int32_t)((h >> 4) % 10u);
-        t.z = cz16 * 16 + 3 + (int32_t)((h >> 12) % 10u);
-        t.trunk = 5 + (int32_t)((h >> 20) & 3u);
-        t.base = height(t.x, t.z);
-        t.present = (h & 3u) != 0u && t.base > sea_level + 1 && t.base < snow_line - 8;
-        return t;
-    }
+    int32_t height(int32_t x, int32_t z) const { return gen::height(seed, x, z); }
+    uint16_t terrain_at(int32_t h, int32_t y) const { return (uint16_t)gen::terrain_at(h, y); }
+    Tree tree_in_cell(int32_t cx16, int32_t cz16) const { return gen::tree_in_cell(seed, cx16, cz16); }
 
     // dense[x + 32*(y + 32*z)] for chunk cp; returns true if the block is uniform (value in dense[0])
     bool fill_dense(ChunkPos cp, uint16_t *dense) const {
@@ -94,7 +40,7 @@ struct WorldGen {
             for (int32_t cx = 0; cx < 2; cx++) {
                 const Tree t = tree_in_cell((x0 >> 4) + cx, (z0 >> 4) + cz);
                 if (!t.present) continue;
-                const int32_t top = t.base + t.trunk;
+                const int32_t top = t.top;
                 for (int32_t dy = -3; dy <= 3; dy++)
                     for (int32_t dz = -3; dz <= 3; dz++)
                         for (int32_t dx = -3; dx <= 3; dx++) {

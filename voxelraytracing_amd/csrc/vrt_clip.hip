@@ -2,26 +2,28 @@
 // client/src/player.rs:202-244 over ClientWorld::get_collisions_w, client/src/world.rs:369-391, and the Aabb family of
 // common/src/math.rs:18-126) as a batch, one box per lane, bit for bit.
 //
-// Only f32 add, subtract and compare occur, in the reference's order (the translation unit is built with -ffp-contract=off:
-// Makefile).  The loop over the world boxes is sequential by specification (include/vrt.h: its answer depends on the order
-// on arbitrary lists), so a lane walks its own range in gather order — x, then y, then z — and clips as it goes; the list is
+// The Aabb arithmetic (expand, the overlap tests, the clip of one axis, EPSILON, the rejections) is both/aabb_clip.h's, the text
+// the host mirror's Aabb compiles too: only f32 add, subtract and compare occur, in the reference's order (the translation unit
+// is built with -ffp-contract=off: Makefile).
+// The loop over the world boxes is sequential by specification (include/vrt.h: its answer depends on the order on arbitrary
+// lists), so a lane walks its own range in gather order — x, then y, then z — and clips as it goes; the list is
 // never stored.  Voxels are vrt_query.h's cast_voxel.  The last leaf found is kept as an aligned cube in registers together
 // with whether it is solid: the voxels of the range inside it load nothing, and the rest of a leaf that is not solid is
 // stepped over along z (nothing is gathered there, so the order of what is gathered stands).
 #include "vrt_query.h"
+#include "both/aabb_clip.h"
 
 namespace vrt {
 
 namespace {
 
 struct ClipParams {
-    CastParams W;   // the world; W.n = the number of boxes (W.q and W.out are the cast's and stay null)
+    QueryWorld W;
     const vrt_box_query *q;
     vrt_box_move *out;
+    uint32_t n;
     const vrt_material *mats;
 };
-
-constexpr float kEpsilon = 0.00001f;   // math.rs:3
 
 struct ClipBox {
     float fx, fy, fz, tx, ty, tz;   // Aabb.from, Aabb.to
@@ -38,23 +40,17 @@ __device__ __forceinline__ bool clip_solid(const ClipParams &P, uint32_t v) {
 // count = the boxes gathered.  False: the range holds more than VRT_BOX_MAX_VOXELS voxels (asked of the first pass only).
 __device__ __forceinline__ bool clip_pass(const ClipParams &P, const ClipBox &b, float mvx, float mvy, float mvz, bool solid0,
                                           bool capped, float &ax, float &ay, float &az, uint32_t &count) {
-    // Aabb::expand, math.rs:18-44
     float efx = b.fx, efy = b.fy, efz = b.fz, etx = b.tx, ety = b.ty, etz = b.tz;
-    if (mvx < 0.0f) efx += mvx;
-    if (mvx > 0.0f) etx += mvx;
-    if (mvy < 0.0f) efy += mvy;
-    if (mvy > 0.0f) ety += mvy;
-    if (mvz < 0.0f) efz += mvz;
-    if (mvz > 0.0f) etz += mvz;
+    aabb_expand(efx, etx, mvx);
+    aabb_expand(efy, ety, mvy);
+    aabb_expand(efz, etz, mvz);
     // get_collisions_w, world.rs:372-377 (every value is below 2^24 in magnitude: the casts are exact)
     const int32_t x0 = (int32_t)floorf(efx), y0 = (int32_t)floorf(efy), z0 = (int32_t)floorf(efz);
     const int32_t x1 = (int32_t)ceilf(etx), y1 = (int32_t)ceilf(ety), z1 = (int32_t)ceilf(etz);
     count = 0u;
     const int32_t nx = x1 - x0, ny = y1 - y0, nz = z1 - z0;
     if (nx <= 0 || ny <= 0 || nz <= 0) return true;   // an empty or inverted range: no boxes
-    if (capped && (nx > (int32_t)VRT_BOX_MAX_VOXELS || ny > (int32_t)VRT_BOX_MAX_VOXELS || nz > (int32_t)VRT_BOX_MAX_VOXELS ||
-                   (uint64_t)nx * (uint64_t)ny * (uint64_t)nz > (uint64_t)VRT_BOX_MAX_VOXELS))
-        return false;
+    if (capped && clip_range_over(nx, ny, nz, VRT_BOX_MAX_VOXELS)) return false;
     const uint32_t W = P.W.S * 32u;
     // the leaf the last lookup found: voxels v with (v & ~c_lo) == c_base lie in it (no voxel coordinate is 0xFFFFFFFF)
     uint32_t cbx = 0xFFFFFFFFu, cby = 0xFFFFFFFFu, cbz = 0xFFFFFFFFu, c_lo = 0u;
@@ -84,37 +80,10 @@ __device__ __forceinline__ bool clip_pass(const ClipParams &P, const ClipBox &b,
             // of it (self) against the unmoved bbox (c)
             const float wfx = (float)x, wfy = (float)y, wfz = (float)z;
             const float wtx = wfx + 1.0f, wty = wfy + 1.0f, wtz = wfz + 1.0f;
-            const bool ox = !(b.tx <= wfx || b.fx >= wtx), oy = !(b.ty <= wfy || b.fy >= wty), oz = !(b.tz <= wfz || b.fz >= wtz);
-            if (ox && oz) {
-                if (ay > 0.0f && b.ty <= wfy) {
-                    const float m = wfy - b.ty - kEpsilon;
-                    if (m < ay) ay = m;
-                }
-                if (ay < 0.0f && b.fy >= wty) {
-                    const float m = wty - b.fy + kEpsilon;
-                    if (m > ay) ay = m;
-                }
-            }
-            if (oy && oz) {
-                if (ax > 0.0f && b.tx <= wfx) {
-                    const float m = wfx - b.tx - kEpsilon;
-                    if (m < ax) ax = m;
-                }
-                if (ax < 0.0f && b.fx >= wtx) {
-                    const float m = wtx - b.fx + kEpsilon;
-                    if (m > ax) ax = m;
-                }
-            }
-            if (ox && oy) {
-                if (az > 0.0f && b.tz <= wfz) {
-                    const float m = wfz - b.tz - kEpsilon;
-                    if (m < az) az = m;
-                }
-                if (az < 0.0f && b.fz >= wtz) {
-                    const float m = wtz - b.fz + kEpsilon;
-                    if (m > az) az = m;
-                }
-            }
+            const bool ox = aabb_overlap(wfx, wtx, b.fx, b.tx), oy = aabb_overlap(wfy, wty, b.fy, b.ty), oz = aabb_overlap(wfz, wtz, b.fz, b.tz);
+            if (ox && oz) ay = clip_axis(ay, wfy, wty, b.fy, b.ty);
+            if (oy && oz) ax = clip_axis(ax, wfx, wtx, b.fx, b.tx);
+            if (ox && oy) az = clip_axis(az, wfz, wtz, b.fz, b.tz);
         }
         z = z_next;
         if (z >= z1) {
@@ -132,7 +101,7 @@ __device__ __forceinline__ bool clip_pass(const ClipParams &P, const ClipBox &b,
 
 __global__ __launch_bounds__(kCastBlock) void clip_moves_kernel(ClipParams P) {
     const uint32_t i = blockIdx.x * kCastBlock + threadIdx.x;
-    if (i >= P.W.n) return;
+    if (i >= P.n) return;
     const vrt_box_query q = P.q[i];
     vrt_box_move r;
     r.mv[0] = r.mv[1] = r.mv[2] = 0.0f;
@@ -140,9 +109,9 @@ __global__ __launch_bounds__(kCastBlock) void clip_moves_kernel(ClipParams P) {
     r.flags = 0u;
     r.boxes[0] = r.boxes[1] = 0u;
     r._reserved = 0u;
-    // rejected (include/vrt.h): beyond 2^23 the sums of expand and translate could leave the exact integers of f32
+    // rejected (include/vrt.h): clip_in_range
     bool ok = true;
-    for (int a = 0; a < 3; a++) ok = ok && fabsf(q.from[a]) < 8388608.0f && fabsf(q.to[a]) < 8388608.0f && fabsf(q.mv[a]) < 8388608.0f;
+    for (int a = 0; a < 3; a++) ok = ok && clip_in_range(q.from[a]) && clip_in_range(q.to[a]) && clip_in_range(q.mv[a]);
     if (!ok) {
         P.out[i] = r;
         return;
@@ -189,7 +158,7 @@ static int clip_enqueue(vrt_ctx *c, const void *q, uint32_t n, void *out) {
     const int rc = query_world(c, P.W);
     if (rc) return rc;
     hipStream_t st = c->stream;
-    P.W.n = n;
+    P.n = n;
     P.q = static_cast<const vrt_box_query *>(q);
     P.out = static_cast<vrt_box_move *>(out);
     P.mats = c->d_mats;
@@ -217,24 +186,7 @@ int vrt_clip_moves(vrt_ctx *c, const vrt_box_query *q, uint32_t n, vrt_box_move 
     if (!c) return VRT_ERR_INVALID_ARG;
     if (n == 0u) return VRT_OK;
     if (!q || !out) return fail(c, VRT_ERR_INVALID_ARG, "vrt_clip_moves: null argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t q_bytes = (size_t)n * sizeof(vrt_box_query);
-    if (c->clip_cap < n) {   // (the previous host clip has finished: each one waits for its results)
-        (void)hipFree(c->d_clip);
-        c->d_clip = nullptr;
-        c->clip_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_clip, (size_t)n * (sizeof(vrt_box_query) + sizeof(vrt_box_move))));
-        c->clip_cap = n;
-    }
-    if (!c->ev_cast) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_cast, hipEventDisableTiming));
-    uint8_t *dq = static_cast<uint8_t *>(c->d_clip), *dout = dq + (size_t)c->clip_cap * sizeof(vrt_box_query);
-    HIP_TRY(c, hipMemcpyAsync(dq, q, q_bytes, hipMemcpyHostToDevice, c->stream));
-    const int rc = clip_enqueue(c, dq, n, dout);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * sizeof(vrt_box_move), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->ev_cast, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->ev_cast));
-    return VRT_OK;
+    return query_batch_host(c, q, (size_t)n * sizeof(vrt_box_query), out, (size_t)n * sizeof(vrt_box_move), n, clip_enqueue);
 }
 
 }  // extern "C"

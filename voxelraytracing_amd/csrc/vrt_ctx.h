@@ -5,6 +5,10 @@
 //   vrt_uploads.hip  uploads without draining, which chunks a write touched, the derived tables
 //   vrt_present.hip  the presentation blit and the gather root's assembly
 //   vrt_group.hip    one context over several devices
+//   vrt_cast.hip, vrt_clip.hip   the world queries (vrt_cast_rays, vrt_clip_moves) over vrt_query.h: the world as a kernel
+//                    sees it and the host-pointer batch
+//   vrt_gen.hip      the chunk source (vrt_generate_chunks, vrt_build_chunks)
+//   both/            not of this seam: the arithmetic those three kernels share with the host mirror (both/both.h)
 //
 // Replaces the reference's wgpu seam: GpuResources / Buffers / NodeBuffer / SimpleBuffer /
 // ArrayBuffer / PixelShader (clientdesktop/src/graphics/{mod.rs,shader.rs}).  Device memory layout
@@ -322,13 +326,11 @@ struct vrt_ctx {
     uint32_t ndc_w = 0, ndc_h = 0;
     float ndc_proj[2] = {0.f, 0.f};
 
-    // vrt_cast_rays (vrt_cast.hip): the device copy of a host batch, queries then results, for cast_cap rays
-    void *d_cast = nullptr;
-    uint32_t cast_cap = 0;
-    hipEvent_t ev_cast = nullptr;
-    // vrt_clip_moves (vrt_clip.hip): the same for clip_cap boxes; a host clip waits on ev_cast as a host cast does
-    void *d_clip = nullptr;
-    uint32_t clip_cap = 0;
+    // vrt_cast_rays / vrt_clip_moves (vrt_query.h query_batch_host): the device copy of a host batch, queries then results, in
+    // bytes; a host batch waits on ev_query for its own results before it returns, so the two kinds share one buffer
+    void *d_query = nullptr;
+    size_t query_cap = 0;
+    hipEvent_t ev_query = nullptr;
 
     // vrt_generate_chunks / vrt_build_chunks (vrt_gen.hip): one batch's staging slots, node counts, offsets and inputs (made on
     // first use), and the compacted nodes of a whole call (grown as needed)

@@ -663,8 +663,8 @@ void vrt_destroy(vrt_ctx *c) {
     (void)hipFree(c->d_nodes); (void)hipFree(c->d_roots); (void)hipFree(c->d_mats); (void)hipFree(c->own_out);
     (void)hipFree(c->d_hits); (void)hipFree(c->d_counters); (void)hipFree(c->d_steps); (void)hipFree(c->d_rgba8); (void)hipFree(c->d_path);
     (void)hipFree(c->d_blk_counts); (void)hipFree(c->d_clock);
-    (void)hipFree(c->d_cast); (void)hipFree(c->d_clip);
-    if (c->ev_cast) (void)hipEventDestroy(c->ev_cast);
+    (void)hipFree(c->d_query);
+    if (c->ev_query) (void)hipEventDestroy(c->ev_query);
     (void)hipFree(c->d_gen_stage); (void)hipFree(c->d_gen_counts); (void)hipFree(c->d_gen_offs); (void)hipFree(c->d_gen_pos);
     (void)hipFree(c->d_gen_dense); (void)hipFree(c->d_gen_out);
     for (auto &T : c->tabs) {

@@ -1,7 +1,8 @@
 // vrt_gen.hip — vrt_generate_chunks / vrt_build_chunks: the build's world generator (host/worldgen.hpp WorldGen::fill_dense)
 // and its bottom-up SVO builder (build_svo_bottom_up) for a batch of chunks, one workgroup per chunk, word for word.
 //
-// worldgen.hpp is the specification.  What the kernel relies on:
+// worldgen.hpp's fill_dense and build_svo_bottom_up are the specification of what stays apart: the walk over a chunk and the
+// builder.  What the kernel relies on:
 //  - Node order.  build_svo_bottom_up lays nodes out breadth-first, and the children of a cell come in k = x | y<<1 | z<<2
 //    order, so each level is in Morton order.  A mixed level-L cell of global breadth-first rank r (mixed cells of levels
 //    0..L-1, then its rank among the mixed cells of level L in Morton order) has its 8 children at 1 + 8 r.  A mixed cell's
@@ -15,12 +16,13 @@
 //    a crown stays inside its cell, leaves replace only AIR, the trunk overwrites.  So no dense block is kept: the heights of the
 //    32 x 32 columns go to LDS once, and each 2^3 block of voxels is made where it is needed (twice for a mixed level-4 cell: to
 //    reduce it, and to write its 8 leaves).  The build kernel reads the caller's dense block the same way, from device memory.
-//  - The arithmetic is WorldGen's: 64-bit smoothstep products, arithmetic >> for the lattice (floor for negatives), and
-//    terrain_at's layer = h - y in wrapping int32, as the host computes it (chunks within 6 of -2^26 in y see the wrap).
+//  - The arithmetic is WorldGen's because it is the same text: both/worldgen_math.h (heights, terrain_at, tree_in_cell and
+//    their constants), compiled here and into the host mirror.
 //
 // The nodes of chunk b go to staging slot b (kGenSlot u16, node i at slot[7 + i], so every 8-block is 16-byte aligned) and its
 // node count to counts[b]; a scan kernel and a gather kernel then compact the batch.
 #include "vrt_ctx.h"
+#include "both/worldgen_math.h"
 
 #include <vector>
 
@@ -39,44 +41,6 @@ constexpr int32_t kCoordLimit = 1 << 26;         // |chunk coordinate| below thi
 
 __host__ __device__ constexpr uint32_t lv_off(uint32_t L) { return L == 0 ? 0u : L == 1 ? 8u : L == 2 ? 16u : L == 3 ? 80u : 592u; }
 __host__ __device__ constexpr uint32_t word_off(uint32_t L) { return L < 4 ? L : 11u; }
-
-// ---- WorldGen (host/worldgen.hpp), seed-parameterised ----
-__device__ __forceinline__ uint32_t gen_mix(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    uint32_t h = a * 747796405u + 2891336453u;
-    h = (h ^ b) * 277803737u; h ^= h >> 15;
-    h = (h ^ c) * 2246822519u; h ^= h >> 13;
-    h = (h ^ d) * 3266489917u; h ^= h >> 16;
-    return h;
-}
-__device__ __forceinline__ uint64_t gen_lattice(uint32_t seed, int32_t ix, int32_t iz, uint32_t octave) {
-    return gen_mix(seed, (uint32_t)ix, (uint32_t)iz, octave) >> 16;
-}
-__device__ __forceinline__ uint32_t gen_value_noise(uint32_t seed, int32_t x, int32_t z, uint32_t cl, uint32_t octave) {
-    const int32_t ix = x >> cl, iz = z >> cl;   // floor for negatives too
-    const uint32_t m = (1u << cl) - 1u;
-    const uint64_t tx = ((uint64_t)((uint32_t)x & m) << 16) >> cl, tz = ((uint64_t)((uint32_t)z & m) << 16) >> cl;
-    const uint64_t sx = (tx * tx * (3u * 65536u - 2u * tx)) >> 32, sz = (tz * tz * (3u * 65536u - 2u * tz)) >> 32;
-    const uint64_t v00 = gen_lattice(seed, ix, iz, octave), v10 = gen_lattice(seed, ix + 1, iz, octave),
-                   v01 = gen_lattice(seed, ix, iz + 1, octave), v11 = gen_lattice(seed, ix + 1, iz + 1, octave);
-    const uint64_t a = (v00 * (65536u - sx) + v10 * sx) >> 16, b = (v01 * (65536u - sx) + v11 * sx) >> 16;
-    return (uint32_t)((a * (65536u - sz) + b * sz) >> 16);
-}
-__device__ __forceinline__ int32_t gen_height(uint32_t seed, int32_t x, int32_t z) {
-    const uint64_t f = (8ull * gen_value_noise(seed, x, z, 7, 0) + 4ull * gen_value_noise(seed, x, z, 6, 1) +
-                        2ull * gen_value_noise(seed, x, z, 5, 2) + 1ull * gen_value_noise(seed, x, z, 4, 3)) / 15ull;
-    int64_t g = ((int64_t)f - 32768) * 9 / 4 + 32768;
-    if (g < 0) g = 0;
-    if (g > 65535) g = 65535;
-    return 40 + (int32_t)(((int64_t)(200 - 40) * g) >> 16);   // h_min + (h_max - h_min) * g >> 16
-}
-__device__ __forceinline__ uint32_t gen_terrain(int32_t h, int32_t y) {
-    constexpr int32_t sea = 70, snow = 172;
-    if (y > h) return y <= sea ? 3u : 0u;                           // WATER : AIR
-    const int32_t layer = (int32_t)((uint32_t)h - (uint32_t)y);     // wraps as the host's int32 does
-    if (layer == 0) return h <= sea + 1 ? 47u : (h >= snow ? 45u : 40u);   // SAND : SNOW : GRASS
-    if (layer <= 4) return h <= sea + 1 ? 47u : 39u;                // SAND : DIRT
-    return 5u;                                                       // SLATE
-}
 
 struct GenTree {
     int32_t present, lx, lz, base, top;   // lx, lz: chunk-local (a chunk's 2 x 2 cells hold its trees); base, top: world y
@@ -106,12 +70,12 @@ __device__ __forceinline__ void cell_voxels(const uint16_t *dense, const int32_t
             uint32_t v2[2];
             for (uint32_t i = 0; i < 2; i++) {
                 const int32_t lx = (int32_t)(2u * x4 + i);
-                uint32_t v = gen_terrain(hgt[lz * 32 + lx], wy);
+                uint32_t v = gen::terrain_at(hgt[lz * 32 + lx], wy);
                 if (t.present) {
                     const int32_t dx = lx - t.lx, dz = lz - t.lz;
                     const int64_t dy = (int64_t)wy - t.top;
-                    if (dx == 0 && dz == 0 && wy > t.base && wy <= t.top) v = 53u;                       // OAK_WOOD
-                    else if (v == 0u && dy >= -3 && dy <= 3 && dx * dx + (int32_t)(dy * dy) + dz * dz <= 11) v = 62u;   // OAK_LEAVES
+                    if (dx == 0 && dz == 0 && wy > t.base && wy <= t.top) v = vox::OAK_WOOD;
+                    else if (v == 0u && dy >= -3 && dy <= 3 && dx * dx + (int32_t)(dy * dy) + dz * dz <= 11) v = vox::OAK_LEAVES;
                 }
                 v2[i] = v;
             }
@@ -147,17 +111,15 @@ __global__ __launch_bounds__(kGenBlock) void gen_chunks_kernel(GenParams P) {
     if constexpr (kGen) {
         const int32_t x0 = P.pos[3u * b] * 32, z0 = P.pos[3u * b + 2u] * 32;   // |pos| < 2^26 (checked on the host)
         y0 = P.pos[3u * b + 1u] * 32;
-        for (uint32_t i = tid; i < 1024u; i += kGenBlock) hgt[i] = gen_height(P.seed, x0 + (int32_t)(i & 31u), z0 + (int32_t)(i >> 5));
-        if (tid < 4u) {   // WorldGen::tree_in_cell((x0 >> 4) + cx, (z0 >> 4) + cz), cell cx + 2 cz
-            const int32_t cx16 = (x0 >> 4) + (int32_t)(tid & 1u), cz16 = (z0 >> 4) + (int32_t)(tid >> 1);
-            const uint32_t h = gen_mix(P.seed ^ 0x9E3779B9u, (uint32_t)cx16, (uint32_t)cz16, 77u);
-            const int32_t tx = cx16 * 16 + 3 + (int32_t)((h >> 4) % 10u), tz = cz16 * 16 + 3 + (int32_t)((h >> 12) % 10u);
+        for (uint32_t i = tid; i < 1024u; i += kGenBlock) hgt[i] = gen::height(P.seed, x0 + (int32_t)(i & 31u), z0 + (int32_t)(i >> 5));
+        if (tid < 4u) {   // the trees of the chunk's 2 x 2 cells, cell cx + 2 cz (fill_dense's loop)
+            const gen::Tree g = gen::tree_in_cell(P.seed, (x0 >> 4) + (int32_t)(tid & 1u), (z0 >> 4) + (int32_t)(tid >> 1));
             GenTree t;
-            t.base = gen_height(P.seed, tx, tz);
-            t.top = t.base + 5 + (int32_t)((h >> 20) & 3u);
-            t.present = (h & 3u) != 0u && t.base > 70 + 1 && t.base < 172 - 8;
-            t.lx = tx - x0;
-            t.lz = tz - z0;
+            t.base = g.base;
+            t.top = g.top;
+            t.present = g.present;
+            t.lx = g.x - x0;
+            t.lz = g.z - z0;
             trees[tid] = t;
         }
         __syncthreads();

@@ -1,5 +1,5 @@
 // vrt_query.h — what the world queries (vrt_cast.hip: vrt_cast_rays, vrt_clip.hip: vrt_clip_moves) share: the world as a
-// kernel sees it and the voxel at a position.  A voxel is asked of the derived tables the default march keeps (vrt_accel.hip: the
+// kernel sees it, the voxel at a position, and the host-pointer form of a batch.  A voxel is asked of the derived tables the default march keeps (vrt_accel.hip: the
 // cell grid, then the brick of a split cell — at most two loads) after its chunk's chunk_roots entry: the grid takes a root of 0
 // for "walk from node 0", the reference for "no chunk".  A world too large for the tables is walked from chunk_roots through the
 // node pool, as find_node does.
@@ -10,10 +10,7 @@ namespace vrt {
 
 namespace {
 
-struct CastParams {
-    const vrt_ray_query *q;
-    vrt_ray_hit *out;
-    uint32_t n;
+struct QueryWorld {   // what query_world fills; each kernel's parameters add its queries, its results and their number
     const uint16_t *nodes;
     uint32_t n_nodes;
     const uint32_t *roots;
@@ -27,12 +24,12 @@ struct CastParams {
 
 constexpr uint32_t kCastBlock = 256;
 
-__device__ __forceinline__ uint32_t cast_node(const CastParams &P, uint32_t idx) {
+__device__ __forceinline__ uint32_t cast_node(const QueryWorld &P, uint32_t idx) {
     return idx < P.n_nodes ? (uint32_t)P.nodes[idx] : 0u;   // past the end: an air leaf, as in the march
 }
 
 // The voxel at world-local (x, y, z) — every coordinate below 32 S — and lo = the size of the leaf it lies in, minus 1.
-__device__ __forceinline__ uint32_t cast_voxel(const CastParams &P, uint32_t x, uint32_t y, uint32_t z, uint32_t &lo) {
+__device__ __forceinline__ uint32_t cast_voxel(const QueryWorld &P, uint32_t x, uint32_t y, uint32_t z, uint32_t &lo) {
     const uint32_t S = P.S;
     const uint32_t ch = (x >> 5) + S * ((y >> 5) + S * (z >> 5));
     const uint32_t root = ch < P.n_roots ? P.roots[ch] : 0u;
@@ -71,8 +68,8 @@ __device__ __forceinline__ uint32_t cast_voxel(const CastParams &P, uint32_t x, 
 
 // The world the queries see: the tables as of every write enqueued so far (brought up to date on c->stream, as the next frame
 // would — which then finds nothing left to do), or the octree itself.  Orders c->stream behind the uploads so far and fills the
-// world half of P; q, out and n are the caller's, who launches on c->stream and then calls publish_upload.
-static int query_world(vrt_ctx *c, vrt::CastParams &P) {
+// P; the caller launches on c->stream and then calls publish_upload.
+static int query_world(vrt_ctx *c, vrt::QueryWorld &P) {
     int rc = validate_frame(c);
     if (rc) return rc;
     hipStream_t st = c->stream;
@@ -106,5 +103,28 @@ static int query_world(vrt_ctx *c, vrt::CastParams &P) {
             P.brick_entries = T.brick_cap * 64u;
         }
     }
+    return VRT_OK;
+}
+
+// The host-pointer form of a batch of n queries: grows the staging buffer (the previous host batch has finished: each one waits
+// for its results), copies the queries in on c->stream, enqueues, copies the results out and waits for them.
+static int query_batch_host(vrt_ctx *c, const void *q, size_t q_bytes, void *out, size_t out_bytes, uint32_t n,
+                            int (*enqueue)(vrt_ctx *, const void *, uint32_t, void *)) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->query_cap < q_bytes + out_bytes) {
+        (void)hipFree(c->d_query);
+        c->d_query = nullptr;
+        c->query_cap = 0;
+        HIP_TRY(c, hipMalloc(&c->d_query, q_bytes + out_bytes));
+        c->query_cap = q_bytes + out_bytes;
+    }
+    if (!c->ev_query) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    uint8_t *dq = static_cast<uint8_t *>(c->d_query), *dout = dq + q_bytes;   // (both record sizes are multiples of 4)
+    HIP_TRY(c, hipMemcpyAsync(dq, q, q_bytes, hipMemcpyHostToDevice, c->stream));
+    const int rc = enqueue(c, dq, n, dout);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_query, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev_query));
     return VRT_OK;
 }
