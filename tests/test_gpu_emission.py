@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import emission_ref
+from emission_cases import _table
 from voxelraytracing_amd import MODE_PATH, MODE_PRIMARY, MODE_PRIMARY_SHADOW, VrtError, _ffi, scenes
 
 from util import assert_frame_parity, gpu_for_scene
@@ -19,22 +20,6 @@ SEED = 11
 @pytest.fixture(scope="module")
 def eref(tmp_path_factory):
     return emission_ref.load(tmp_path_factory.mktemp("emission_ref"))
-
-
-def _table(gpu):
-    """Two materials that the frame's id words show are hit often, made emissive (and a third entry that no voxel of C4 uses:
-    a table with only some entries in use)."""
-    gpu.render(MODE_PATH, spp=1, seed=SEED)
-    _, ids, _ = gpu.read_output(rgb=False)
-    hit = (ids & (1 << 16)) != 0   # (VRT_ID_HIT)
-    counts = np.bincount((ids[hit] & 0x7FFF).astype(np.int64), minlength=256)[:256]
-    top = np.argsort(counts)[::-1][:2]
-    assert counts[top[1]] > 0
-    t = np.zeros(256, np.float32)
-    t[top[0]] = 1.75
-    t[top[1]] = 0.5
-    t[255] = 3.0
-    return t
 
 
 def _frame(gpu, spp, seed=SEED, **kw):

@@ -19,6 +19,12 @@ def assert_frame_parity(gpu_rgb, gpu_ids, ref_rgb, ref_ids, what=""):
     bad = np.argwhere(gpu_ids != ref_ids)
     assert bad.size == 0, f"{what}: {len(bad)} id words differ, first at (y,x)={tuple(bad[0])}: " \
                           f"gpu={gpu_ids[tuple(bad[0])]:#x} oracle={ref_ids[tuple(bad[0])]:#x}"
-    err = np.abs(gpu_rgb - ref_rgb)
-    assert np.isfinite(gpu_rgb).all() == np.isfinite(ref_rgb).all()
-    assert float(np.nanmax(err)) <= RADIANCE_TOL, f"{what}: max radiance error {np.nanmax(err)}"
+    # the same values are NaN, +inf and -inf on both sides; what is left is finite on both
+    for name, mask in (("NaN", np.isnan), ("+inf", np.isposinf), ("-inf", np.isneginf)):
+        g, r = mask(gpu_rgb), mask(ref_rgb)
+        assert np.array_equal(g, r), f"{what}: {name} in {int(g.sum())} gpu values and {int(r.sum())} oracle values, " \
+                                     f"{int((g != r).sum())} of them not in the same place"
+    fin = np.isfinite(ref_rgb)
+    if fin.any():
+        err = np.abs(gpu_rgb[fin] - ref_rgb[fin])
+        assert float(err.max()) <= RADIANCE_TOL, f"{what}: max radiance error {err.max()}"
