@@ -213,6 +213,16 @@ pub struct vrt_box_move {
 const _: () = assert!(core::mem::size_of::<vrt_box_query>() == 48);
 const _: () = assert!(core::mem::size_of::<vrt_box_move>() == 32);
 
+/// vrt_set_denoise: the path trace's edge-stopped a-trous filter (passes 0 = off, 1..5; sigma_color 0 = no colour stop).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_denoise_opts {
+    pub passes: u32,
+    pub sigma_color: f32,
+    pub flags: u32,
+    pub _reserved: u32,
+}
+
 /// What issuing a frame costs the host (vrt_get_issue_profile), microseconds per vrt_render call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -257,6 +267,8 @@ extern "C" {
     pub fn vrt_set_frames_in_flight(ctx: *mut vrt_ctx, n: u32) -> c_int;
     pub fn vrt_reset_accumulation(ctx: *mut vrt_ctx) -> c_int;
     pub fn vrt_get_accumulation(ctx: *mut vrt_ctx, samples: *mut u32, seed: *mut u32) -> c_int;
+    pub fn vrt_set_denoise(ctx: *mut vrt_ctx, opts: *const vrt_denoise_opts) -> c_int;
+    pub fn vrt_read_guide(ctx: *mut vrt_ctx, guide: *mut u32) -> c_int;
     pub fn vrt_synchronize(ctx: *mut vrt_ctx) -> c_int;
     pub fn vrt_read_output(ctx: *mut vrt_ctx, rgb: *mut f32, ids: *mut u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_present(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8: *mut u8) -> c_int;
@@ -300,5 +312,6 @@ mod layout {
         assert_eq!(size_of::<vrt_stats>(), 112);
         assert_eq!(size_of::<vrt_accel_info>(), 48);
         assert_eq!(size_of::<vrt_issue_profile>(), 72);
+        assert!(size_of::<vrt_denoise_opts>() == 16);
     }
 }

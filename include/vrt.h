@@ -287,6 +287,47 @@ int vrt_reset_accumulation(vrt_ctx *ctx);
  * state: never synchronises.  Either pointer may be NULL. */
 int vrt_get_accumulation(vrt_ctx *ctx, uint32_t *samples, uint32_t *seed);
 
+/* While the view moves every VRT_MODE_PATH frame is a fresh 1-spp image.  vrt_set_denoise filters every later path frame on
+ * the GPU with an edge-stopped a-trous filter (Dammertz et al. 2010), on the frame's own stream behind its last path launch
+ * (the resolve of an accumulating or multi-sample frame included): the filtered colours are what the frame's texels hold, for
+ * vrt_read_output, vrt_present*, vrt_device_output and a bound output alike; id words are never touched.  The primary modes
+ * are the live shader's bytes and are never filtered.  Build-defined, and defined exactly:
+ *   traced area  the 8 (W / 8) x 8 (H / 8) pixels a frame stores to; pixels beyond it keep their zeros
+ *   filterable   a pixel whose id word has VRT_ID_HIT and at least one of VRT_ID_NX / NY / NZ; every other pixel is copied
+ *   key(p)       id(p) & (VRT_ID_VOXEL_MASK | VRT_ID_HIT | VRT_ID_NX | VRT_ID_NY | VRT_ID_NZ | VRT_ID_WATER)
+ *   guide(p)     (uint32_t)(int32_t)floorf(pos[a] + 0.5f) of a filterable pixel: pos the primary march's hit position in
+ *                world-local voxels, a the lowest-numbered axis whose normal bit is set (the integer coordinate of the hit
+ *                face's plane); 0 for every other pixel
+ *   h            {0.0625, 0.25, 0.375, 0.25, 0.0625}
+ * Pass i = 0 .. passes - 1 has tap spacing s = 1 << i and gives a filterable p, of colour c_p,
+ *   sum = {0,0,0}; wsum = 0
+ *   for dy = -2..2, for dx = -2..2 (both ascending):  q = p + s (dx, dy); skipped when outside the traced area or
+ *                                                     key(q) != key(p) or guide(q) != guide(p)
+ *       w = h[dy + 2] * h[dx + 2]
+ *       if sigma_color != 0:  sg = sigma_color / (float)(1u << i);  d = c_q - c_p per channel;
+ *                             d2 = (d.r * d.r + d.g * d.g) + d.b * d.b;  w = w * ((sg * sg) / ((sg * sg) + d2))
+ *       sum.ch = sum.ch + w * c_q.ch;  wsum = wsum + w
+ *   out = sum / wsum per channel
+ * in strict binary32, in this order, nothing contracted; a NaN or infinite colour takes no special path.  Two pixels that
+ * agree on key and guide lie on the same voxel face, whose face-shaded material colour is one value: the filter averages
+ * irradiance, and never across a face's edge.  An accumulation's sum stays unfiltered (the filter works on the frame's mean:
+ * K accumulated frames, denoised, are one denoised frame of K times the samples, bit for bit), and changing the setting does
+ * not restart it.  opts NULL or passes == 0: off, the default — frames are byte for byte what they are without this call and
+ * nothing is launched or allocated.  passes > 5, a negative, NaN or infinite sigma_color, flags or _reserved not 0:
+ * VRT_ERR_INVALID_ARG; passes > 0 on a sharded, tile-major or multi-device context (no neighbouring pixels to read):
+ * VRT_ERR_STATE.  A refused call changes nothing.  A timed frame's GPU time (vrt_get_stats, VRT_RENDER_TIMED) includes the
+ * guide launch and the passes.  Suggested: passes 5, sigma_color 0 (docs/KERNELS.md has the sweep). */
+typedef struct vrt_denoise_opts {
+    uint32_t passes;      /* 0 = off (the default); 1..5 a-trous passes, tap spacing 1, 2, 4, 8, 16 pixels */
+    float    sigma_color; /* colour stop of pass 0, halved every pass; 0 = no colour stop */
+    uint32_t flags;       /* 0 */
+    uint32_t _reserved;   /* 0 */
+} vrt_denoise_opts;   /* 16 B */
+int vrt_set_denoise(vrt_ctx *ctx, const vrt_denoise_opts *opts);
+/* Diagnostic: the guide words of the last denoised frame, width * height of them row-major (0 beyond the traced area).
+ * Synchronises.  VRT_ERR_STATE before the first denoised frame (and after a resize until the next one). */
+int vrt_read_guide(vrt_ctx *ctx, uint32_t *guide);
+
 /* Block until everything enqueued on the context's stream has finished. */
 int vrt_synchronize(vrt_ctx *ctx);
 

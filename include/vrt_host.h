@@ -162,6 +162,13 @@ int vrth_chunk_msg_ingest(vrth_world *w, const uint8_t *bytes, uint64_t n, uint6
  * Returns the byte count (writes if it fits cap), 0 if the world has no such chunk. */
 uint64_t vrth_chunk_msg_encode(const vrth_world *w, const int32_t chunk_pos[3], uint8_t *out, uint64_t cap);
 
+/* ---- the path trace's denoiser (include/vrt.h: vrt_set_denoise) on the host ---- */
+/* The filter a denoised frame goes through on the GPU, in the same text (csrc/both/denoise_math.h): rgb w*h*3 f32, ids and
+ * guide w*h words (row-major; guide as vrt_read_guide gives it) -> out w*h*3 f32 (may not alias rgb).  Pixels beyond the
+ * traced area 8 (w / 8) x 8 (h / 8) and pixels that are not filterable are copied.  opts NULL or passes == 0 copies the frame.
+ * Returns 0, or -1 for a null array or options vrt_set_denoise refuses with VRT_ERR_INVALID_ARG. */
+int vrth_denoise(const float *rgb, const uint32_t *ids, const uint32_t *guide, uint32_t w, uint32_t h, const vrt_denoise_opts *opts, float *out);
+
 #ifdef __cplusplus
 }
 #endif

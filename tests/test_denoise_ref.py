@@ -1,0 +1,208 @@
+"""The path trace's denoiser (vrt_set_denoise, include/vrt.h) without a GPU: libvrt_host.so's vrth_denoise — the text the kernels
+compile, csrc/both/denoise_math.h — against tests/denoise_ref.c, an independent plain-C statement of the filter, bit for bit;
+what the filter promises whatever its input; and, on the oracle's own frames, that it does what it is for.
+
+Bit for bit means the same binary32 bits in every channel of every pixel, except that where one side holds a NaN the other
+must hold a NaN in that same channel of that same pixel, of whatever sign and payload: IEEE 754 leaves those to the
+implementation, and two compilers may order the operands of a commutative operation differently.  A NaN in one place and a
+number in the other is a difference like any other.
+
+    python tests/test_denoise_ref.py        prints the quality sweep docs/KERNELS.md records (the defaults come from it)"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import denoise_ref
+from voxelraytracing_amd import _ffi, scenes
+
+HIT, NX, NY, NZ, WATER = _ffi.ID_HIT, _ffi.ID_NX, _ffi.ID_NY, _ffi.ID_NZ, _ffi.ID_WATER
+SIZES = [(8, 8), (40, 24), (52, 30)]   # (52 x 30: neither a multiple of 8 — the traced area is 48 x 24)
+SIGMAS = [0.0, 0.35, 4.0]
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    return denoise_ref.load(tmp_path_factory.mktemp("denoise_ref"))
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return bool(np.all((denoise_ref.bits(a) == denoise_ref.bits(b)) | (np.isnan(a) & np.isnan(b))))
+
+
+def random_frame(rng, w, h, special=True, n_keys=5, n_guides=3):
+    """A frame of random colours, keys and guides: a few surfaces so that taps agree often, sky and no-normal hits in between,
+    bits outside the key (the shadow bits) set at random, and — special — zeros, denormals, infinities and NaNs among the colours."""
+    vox = rng.integers(1, 200, n_keys).astype(np.uint32)
+    face = rng.choice(np.array([NX, NY, NZ, NX | NY, NY | NZ | WATER], np.uint32), n_keys)
+    k = rng.integers(0, n_keys, (h, w))
+    ids = (vox[k] | HIT | face[k]).astype(np.uint32)
+    kind = rng.random((h, w))
+    ids[kind < 0.12] = 0                                            # sky
+    ids[(kind >= 0.12) & (kind < 0.2)] = HIT | 7                     # a hit without a normal
+    ids |= (rng.integers(0, 4, (h, w)).astype(np.uint32) << 21)      # bits the key leaves out
+    guide = rng.integers(10, 10 + n_guides, (h, w)).astype(np.uint32)
+    guide[(ids & HIT == 0) | (ids & (NX | NY | NZ) == 0)] = 0
+    rgb = (rng.random((h, w, 3), dtype=np.float32) * np.float32(3.0)).astype(np.float32)
+    if special:
+        pick = rng.random((h, w, 3))
+        rgb[pick < 0.03] = 0.0
+        rgb[(pick >= 0.03) & (pick < 0.05)] = np.float32(1e-41)      # a denormal
+        rgb[(pick >= 0.05) & (pick < 0.06)] = np.inf
+        rgb[(pick >= 0.06) & (pick < 0.07)] = np.nan
+        rgb[(pick >= 0.07) & (pick < 0.08)] = np.float32(3e38)
+    return rgb, ids, guide
+
+
+def striped_frame(rng, w, h):
+    """Keys in 1-pixel stripes (columns alternate between two surfaces) with isolated pixels of a third sprinkled in."""
+    rgb, _, _ = random_frame(rng, w, h)
+    ids = np.empty((h, w), np.uint32)
+    ids[:, 0::2] = 3 | HIT | NX
+    ids[:, 1::2] = 4 | HIT | NY
+    lone = rng.random((h, w)) < 0.05
+    ids[lone] = 9 | HIT | NZ
+    guide = np.full((h, w), 20, np.uint32)
+    guide[lone] = (21 + np.arange(int(lone.sum()))).astype(np.uint32)   # no two of them on one plane
+    return rgb, ids, guide
+
+
+@pytest.mark.parametrize("sigma", SIGMAS)
+@pytest.mark.parametrize("passes", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("size", SIZES)
+def test_the_host_entry_point_is_the_reference_bit_for_bit(ref, size, passes, sigma):
+    w, h = size
+    rng = np.random.default_rng(1000 * w + 10 * passes + int(sigma * 7))
+    for name, (rgb, ids, guide) in (("random", random_frame(rng, w, h)), ("stripes", striped_frame(rng, w, h))):
+        got = _ffi.denoise(rgb, ids, guide, passes, sigma)
+        want = ref.denoise(rgb, ids, guide, passes, sigma)
+        assert same_bits(got, want), f"{name} {size} passes {passes} sigma {sigma}: {int((denoise_ref.bits(got) != denoise_ref.bits(want)).sum())} words differ"
+        if passes == 1 and sigma == 0.0:
+            assert not same_bits(got, rgb)   # (it filters)
+
+
+def test_no_passes_is_a_copy_and_bad_options_are_refused(ref):
+    rgb, ids, guide = random_frame(np.random.default_rng(3), 40, 24)
+    assert same_bits(_ffi.denoise(rgb, ids, guide, 0, 0.0), rgb) and same_bits(ref.denoise(rgb, ids, guide, 0, 0.0), rgb)
+    for passes, sigma in ((6, 0.0), (1, -1.0), (1, float("nan")), (1, float("inf"))):
+        with pytest.raises(ValueError):
+            _ffi.denoise(rgb, ids, guide, passes, sigma)
+
+
+@pytest.mark.parametrize("sigma", [0.0, 0.35])
+def test_sky_and_hits_without_a_normal_keep_their_bytes(ref, sigma):
+    rgb, ids, guide = random_frame(np.random.default_rng(5), 52, 30)
+    out = _ffi.denoise(rgb, ids, guide, 5, sigma)
+    copied = ((ids & HIT) == 0) | ((ids & (NX | NY | NZ)) == 0)
+    copied[24:, :] = True    # beyond the traced area (48 x 24)
+    copied[:, 48:] = True
+    assert copied.sum() > 200 and (~copied).sum() > 200
+    assert np.array_equal(denoise_ref.bits(out)[copied], denoise_ref.bits(rgb)[copied])   # (NaN payloads included: a copy)
+
+
+@pytest.mark.parametrize("sigma", [0.0, 0.35])
+def test_a_frame_of_lone_pixels_comes_out_within_an_ulp(sigma):
+    """No two pixels share key and guide: every pixel's only tap is itself, out = (w c) / w."""
+    rng = np.random.default_rng(9)
+    w, h = 40, 24
+    rgb, _, _ = random_frame(rng, w, h, special=False)
+    ids = np.full((h, w), 5 | HIT | NY, np.uint32)
+    guide = np.arange(w * h, dtype=np.uint32).reshape(h, w) + 1
+    out = _ffi.denoise(rgb, ids, guide, 5, sigma)
+    ulps = np.abs(denoise_ref.bits(out).astype(np.int64) - denoise_ref.bits(rgb).astype(np.int64))
+    assert int(ulps.max()) <= 1     # after all five passes: the roundings of w c and of the quotient do not add up pass by pass
+    for passes in (1, 2, 3, 4):
+        one = _ffi.denoise(rgb, ids, guide, passes, sigma)
+        assert int(np.abs(denoise_ref.bits(one).astype(np.int64) - denoise_ref.bits(rgb).astype(np.int64)).max()) <= 1, passes
+
+
+@pytest.mark.parametrize("sigma", [0.0, 0.35])
+def test_the_output_never_depends_on_a_pixel_of_another_surface(ref, sigma):
+    rng = np.random.default_rng(13)
+    rgb, ids, guide = random_frame(rng, 40, 24, special=False)
+    key = ids & np.uint32(0x7FFF | HIT | NX | NY | NZ | WATER)
+    filterable = ((ids & HIT) != 0) & ((ids & (NX | NY | NZ)) != 0)
+    ys, xs = np.nonzero(filterable)
+    k0, g0 = key[ys[0], xs[0]], guide[ys[0], xs[0]]
+    mine = filterable & (key == k0) & (guide == g0)
+    assert mine.sum() > 10 and (filterable & ~mine).sum() > 100
+    other = rgb.copy()
+    other[~mine] = (rng.random((int((~mine).sum()), 3), dtype=np.float32) * np.float32(100.0)).astype(np.float32)
+    for f in (_ffi.denoise, ref.denoise):
+        a, b = f(rgb, ids, guide, 5, sigma), f(other, ids, guide, 5, sigma)
+        assert np.array_equal(denoise_ref.bits(a)[mine], denoise_ref.bits(b)[mine])
+    # ... and the same pixel on another plane, or of another key, is another surface
+    for change in ("guide", "key"):
+        ids2, guide2 = ids.copy(), guide.copy()
+        y, x = ys[0], xs[0]
+        if change == "guide":
+            guide2[y, x] += 1000
+        else:
+            ids2[y, x] ^= np.uint32(WATER)
+        out = _ffi.denoise(rgb, ids2, guide2, 1, sigma)
+        ulp = np.abs(denoise_ref.bits(out[y, x]).astype(np.int64) - denoise_ref.bits(rgb[y, x]).astype(np.int64))
+        assert int(ulp.max()) <= 1, change
+
+
+def test_the_reference_guide_is_the_plane_of_the_hit_face(ref, orc):
+    """On C1's flat world (ground at one height, seen from above): every ground pixel hit a +y face, on one plane."""
+    sc = scenes.c1_flat((48, 48))
+    o = orc.from_package_scene(sc)
+    guide, ids = ref.guide(o, 48, 48)
+    _, want_ids, _, _ = o.render(orc.MODE_PRIMARY, 48, 48)
+    assert np.array_equal(ids, want_ids)
+    top = (ids & (HIT | NX | NY | NZ)) == (HIT | NY)
+    assert top.sum() > 500 and len(np.unique(guide[top])) == 1
+    idw, _, _, out = o.trace_pixel(orc.MODE_PRIMARY, 24, 40)
+    assert idw & NY and guide[40, 24] == int(np.floor(np.float32(out[1]) + np.float32(0.5)))
+    assert np.array_equal(guide != 0, ((ids & HIT) != 0) & ((ids & (NX | NY | NZ)) != 0))
+
+
+# ---- quality: the filter on the oracle's own 1-spp frame against the oracle's 256-spp frame ----
+QUALITY_SIZE, QUALITY_SEED, QUALITY_SPP = (160, 96), 11, 256
+
+
+def quality_frames(orc, ref):
+    sc = scenes.c4(QUALITY_SIZE, bounces=4)
+    o = orc.from_package_scene(sc)
+    w, h = QUALITY_SIZE
+    raw, ids, _, _ = o.render(orc.MODE_PATH, w, h, spp=1, seed=QUALITY_SEED)
+    truth, _, _, _ = o.render(orc.MODE_PATH, w, h, spp=QUALITY_SPP, seed=QUALITY_SEED + 1)
+    guide, g_ids = ref.guide(o, w, h)
+    assert np.array_equal(g_ids, ids)
+    filterable = ((ids & HIT) != 0) & ((ids & (NX | NY | NZ)) != 0)
+    return raw, ids, guide, truth, filterable
+
+
+def mse(a, b, mask):
+    d = a[mask].astype(np.float64) - b[mask].astype(np.float64)
+    return float((d * d).mean())
+
+
+def test_the_defaults_bring_a_one_sample_frame_closer_to_the_converged_one(ref, orc):
+    raw, ids, guide, truth, filterable = quality_frames(orc, ref)
+    assert filterable.mean() > 0.3
+    out = ref.denoise(raw, ids, guide, _ffi.DENOISE_PASSES, _ffi.DENOISE_SIGMA_COLOR)
+    e_raw, e_out = mse(raw, truth, filterable), mse(out, truth, filterable)
+    print(f"mse over filterable pixels: raw {e_raw:.5f}, filtered {e_out:.5f} (ratio {e_out / e_raw:.3f})")
+    assert e_out < e_raw
+
+
+if __name__ == "__main__":
+    import tempfile
+    from oracle import orc as _orc
+    _orc.build()
+    with tempfile.TemporaryDirectory() as d:
+        _ref = denoise_ref.load(d)
+        raw, ids, guide, truth, filterable = quality_frames(_orc, _ref)
+        e_raw = mse(raw, truth, filterable)
+        print(f"C4's scene {QUALITY_SIZE[0]}x{QUALITY_SIZE[1]}, 4 bounces: 1 spp against {QUALITY_SPP} spp, {filterable.mean():.1%} of the pixels filterable; raw mse {e_raw:.5f}")
+        print("passes " + "".join(f"  sigma {s:<5}" for s in (0.0, 0.25, 0.5, 1.0, 2.0, 4.0)))
+        for passes in (1, 2, 3, 4, 5):
+            row = [mse(_ref.denoise(raw, ids, guide, passes, s), truth, filterable) / e_raw for s in (0.0, 0.25, 0.5, 1.0, 2.0, 4.0)]
+            print(f"{passes:6d} " + "".join(f"  {r:11.3f}" for r in row))

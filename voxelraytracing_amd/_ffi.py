@@ -83,6 +83,11 @@ class IssueProfile(C.Structure):
                 ("join_wait_us", C.c_double), ("tail_us", C.c_double), ("message_waits_us", C.c_double)]
 
 
+class DenoiseOpts(C.Structure):
+    """include/vrt.h vrt_denoise_opts: the path trace's a-trous filter (vrt_set_denoise)"""
+    _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
 class RayQuery(C.Structure):
     """include/vrt.h vrt_ray_query: common::math::cast_ray's arguments (common/src/math.rs:153-158)"""
     _fields_ = [("start", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("_reserved", C.c_uint32)]
@@ -123,6 +128,7 @@ assert RAY_QUERY_DTYPE.itemsize == 32 and RAY_HIT_DTYPE.itemsize == 32
 assert C.sizeof(BoxQuery) == 48 and C.sizeof(BoxMove) == 32
 assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
+assert C.sizeof(DenoiseOpts) == 16
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
 RENDER_OWN_STREAMS, RENDER_TIMED, RENDER_ACCUMULATE = 1, 2, 4   # vrt_render_opts.flags (VRT_RENDER_*)
@@ -153,6 +159,8 @@ VRT_SYMBOLS = {
     "vrt_set_frames_in_flight": (C.c_int, [_P, C.c_uint32]),
     "vrt_reset_accumulation": (C.c_int, [_P]),
     "vrt_get_accumulation": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "vrt_set_denoise": (C.c_int, [_P, C.POINTER(DenoiseOpts)]),
+    "vrt_read_guide": (C.c_int, [_P, _P]),
     "vrt_synchronize": (C.c_int, [_P]),
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),
@@ -182,14 +190,20 @@ VRT_SYMBOLS = {
 
 def _load(name: str, symbols: dict) -> C.CDLL:
     path = os.path.join(_HERE, name)
+    absent = ()
     if name == "libvrt.so" and os.environ.get("VRT_LIB"):   # development: A/B another build of the backend (tools/ab/)
         path = os.environ["VRT_LIB"]
+        # ... which may be an older one: VRT_LIB_WITHOUT names (comma-separated) the entry points it is known not to have yet.
+        # Only those may be missing, and only from such a build: the tree's own library answers to the whole header.
+        absent = tuple(s for s in os.environ.get("VRT_LIB_WITHOUT", "").split(",") if s)
     if not os.path.exists(path):
         raise ImportError(
             f"{path} is missing — the native library is the product, there is no fallback. Build it with "
             f"`python -c 'import __graft_entry__ as g; g.build()'` or `make -C voxelraytracing_amd/csrc`.")
     lib = C.CDLL(path)
     for sym, (res, args) in symbols.items():
+        if sym in absent and not hasattr(lib, sym):
+            continue
         fn = getattr(lib, sym)  # AttributeError if the ABI drifted from the header
         fn.restype = res
         fn.argtypes = args
@@ -323,7 +337,11 @@ VRTH_SYMBOLS = {
     "vrth_chunk_msg_encode": (C.c_uint64, [_P, _I32P, _P, C.c_uint64]),
     "vrth_region_of_chunk": (None, [_I32P, _I32P, _U32P]),
     "vrth_region_file_name": (C.c_uint32, [_I32P, C.c_char_p, C.c_uint32]),
+    "vrth_denoise": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseOpts), _P]),
 }
+
+# Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)
+DENOISE_PASSES, DENOISE_SIGMA_COLOR = 5, 0.0
 
 _host = None
 
@@ -334,3 +352,17 @@ def host() -> C.CDLL:
     if _host is None:
         _host = _load("libvrt_host.so", VRTH_SYMBOLS)
     return _host
+
+
+def denoise(rgb, ids, guide, passes: int = DENOISE_PASSES, sigma_color: float = DENOISE_SIGMA_COLOR) -> np.ndarray:
+    """vrth_denoise: the filter a denoised path frame goes through on the GPU (vrt_set_denoise), on the host, in the same text —
+    rgb [h, w, 3] f32, ids and guide [h, w] u32 (Gpu.read_output, Gpu.read_guide) -> the filtered [h, w, 3] f32."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = rgb.shape[:2]
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(h, w)
+    guide = np.ascontiguousarray(guide, dtype=np.uint32).reshape(h, w)
+    out = np.empty_like(rgb)
+    o = DenoiseOpts(passes, sigma_color, 0, 0)
+    if host().vrth_denoise(rgb.ctypes.data, ids.ctypes.data, guide.ctypes.data, w, h, C.byref(o), out.ctypes.data):
+        raise ValueError(f"denoise: passes {passes} (0..5), sigma_color {sigma_color} (finite, >= 0)")
+    return out

@@ -9,6 +9,7 @@
 
 #include "../../../include/vrt_host.h"
 #include "../both/cast_dda.h"
+#include "../both/denoise_math.h"
 #include "collide.hpp"
 #include "graphics.hpp"
 #include "materials.hpp"
@@ -453,6 +454,40 @@ uint64_t vrth_chunk_msg_encode(const vrth_world *w, const int32_t chunk_pos[3], 
     const std::vector<uint8_t> bytes = m.encode();
     if (out && bytes.size() <= cap) std::memcpy(out, bytes.data(), bytes.size());
     return bytes.size();
+}
+
+// vrt_set_denoise's filter over host arrays: csrc/both/denoise_math.h's pixel, pass after pass between two copies of the frame
+int vrth_denoise(const float *rgb, const uint32_t *ids, const uint32_t *guide, uint32_t w, uint32_t h, const vrt_denoise_opts *opts, float *out) {
+    if (!rgb || !ids || !guide || !out) return -1;
+    const uint32_t passes = opts ? opts->passes : 0u;
+    const float sigma = opts ? opts->sigma_color : 0.0f;
+    if (opts && (passes > vrt::kDnMaxPasses || !(sigma >= 0.0f) || std::isinf(sigma) || opts->flags || opts->_reserved)) return -1;
+    const size_t n = (size_t)w * h;
+    std::vector<float> a(rgb, rgb + n * 3), b(a);
+    const int wt = (int)(w & ~7u), ht = (int)(h & ~7u);
+    for (uint32_t i = 0; i < passes; i++) {
+        const int s = 1 << i;
+        const bool stop = sigma != 0.0f;
+        const float sg2 = vrt::denoise_sigma2(sigma, i);
+        for (int y = 0; y < ht; y++)
+            for (int x = 0; x < wt; x++) {
+                const size_t p = (size_t)y * w + x;
+                if (!vrt::denoise_filterable(ids[p])) continue;   // (copied)
+                const uint32_t key = vrt::denoise_key(ids[p]), g = guide[p];
+                auto fetch = [&](int qx, int qy, vrt::DnColor &c) {
+                    if (qx < 0 || qy < 0 || qx >= wt || qy >= ht) return false;
+                    const size_t q = (size_t)qy * w + qx;
+                    if (vrt::denoise_key(ids[q]) != key || guide[q] != g) return false;
+                    c = vrt::DnColor{a[q * 3], a[q * 3 + 1], a[q * 3 + 2]};
+                    return true;
+                };
+                const vrt::DnColor o = vrt::denoise_pixel(fetch, x, y, s, vrt::DnColor{a[p * 3], a[p * 3 + 1], a[p * 3 + 2]}, stop, sg2);
+                b[p * 3] = o.r; b[p * 3 + 1] = o.g; b[p * 3 + 2] = o.b;
+            }
+        a.swap(b);   // (the pixels a pass copies never change: both copies hold them from the start)
+    }
+    std::memcpy(out, a.data(), n * 3 * sizeof(float));
+    return 0;
 }
 
 }  // extern "C"

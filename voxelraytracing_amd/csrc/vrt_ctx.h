@@ -8,6 +8,7 @@
 //   vrt_cast.hip, vrt_clip.hip   the world queries (vrt_cast_rays, vrt_clip_moves) over vrt_query.h: the world as a kernel
 //                    sees it and the host-pointer batch
 //   vrt_gen.hip      the chunk source (vrt_generate_chunks, vrt_build_chunks)
+//   vrt_denoise.hip  the path trace's denoiser (vrt_set_denoise, vrt_read_guide) and its kernels
 //   both/            not of this seam: the arithmetic those three kernels share with the host mirror (both/both.h)
 //
 // Replaces the reference's wgpu seam: GpuResources / Buffers / NodeBuffer / SimpleBuffer /
@@ -365,6 +366,12 @@ struct vrt_ctx {
     bool accum_restart = true;
     hipEvent_t ev_accum = nullptr;
     bool accum_ev_recorded = false;
+    // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); per frame set, made by its first denoised frame and dropped
+    // by a resize, the scratch frame the passes go back and forth over and the guide words; the guide of the last denoised frame
+    vrt_denoise_opts denoise{};
+    vrt::Texel *dn_scratch[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t *dn_guide[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t *dn_last_guide = nullptr;
     bool rendered = false;
     bool last_stats = false;
     uint32_t last_mode = 0;
@@ -438,6 +445,11 @@ struct TileOrderPlan { bool sort = false, dilate = false; };
 VRT_HIDDEN int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, const vrt_render_opts &o, uint32_t variant, bool kstats,
                                        bool edit_in_front, TileOrderPlan &plan);
 VRT_HIDDEN int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st, const TileOrderPlan &plan);
+// vrt_denoise.hip: around a path frame's launches in vrt_render (vrt_set_denoise)
+VRT_HIDDEN void denoise_free(vrt_ctx *c);
+VRT_HIDDEN int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::Texel **trace_into);
+VRT_HIDDEN int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
+                                   hipEvent_t closing);
 // vrt_uploads.hip
 VRT_HIDDEN int alloc_roots(vrt_ctx *c, uint32_t world_size);
 VRT_HIDDEN int flush_staged(vrt_ctx *c);

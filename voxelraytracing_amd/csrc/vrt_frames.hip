@@ -77,6 +77,7 @@ static int alloc_output(vrt_ctx *c) {
     for (auto &n : c->path_buf_records) n = 0;
     (void)hipFree(c->d_accum); c->d_accum = nullptr;
     c->accum_restart = true;
+    denoise_free(c);
     layout_tiles(c);
     const size_t n = c->slots ? c->slots : 1;
     HIP_TRY(c, hipMalloc(&c->own_out, n * sizeof(vrt::Texel)));
@@ -658,6 +659,7 @@ void vrt_destroy(vrt_ctx *c) {
     for (auto p : c->path_acc) (void)hipFree(p);
     for (auto p : c->path_grp_counts) (void)hipFree(p);
     (void)hipFree(c->d_accum);
+    denoise_free(c);
     if (c->ev_accum) (void)hipEventDestroy(c->ev_accum);
     (void)hipFree(c->d_tile_cost); (void)hipFree(c->d_tile_order); (void)hipFree(c->d_tile_scratch);
     (void)hipFree(c->d_nodes); (void)hipFree(c->d_roots); (void)hipFree(c->d_mats); (void)hipFree(c->own_out);
@@ -923,7 +925,16 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (kstats || o.mode == VRT_MODE_PATH) HIP_TRY(c, hipMemsetAsync(f.counters, 0, kCounterBytes, f.st));
     {
         VRT_PROF(13, "  the launch(es)");
-        if (o.mode == VRT_MODE_PATH) rc = launch_path_frame(c, P, f, o, kstats, air_liquid, accum, accum_from, *ev, *ev_kind);
+        if (o.mode == VRT_MODE_PATH) {
+            // vrt_set_denoise: a frame of an odd number of passes is traced into its scratch frame (the last pass lands in f.out)
+            FrameSet ft = f;
+            rc = denoise_before_frame(c, f.slot, f.out, &ft.out);
+            if (rc) return rc;
+            P.out = ft.out;
+            rc = launch_path_frame(c, P, ft, o, kstats, air_liquid, accum, accum_from, *ev, *ev_kind);
+            // (a timed frame's closing event is recorded again behind the filter: vrt_stats and VRT_RENDER_TIMED time it with its passes)
+            if (!rc) rc = denoise_after_frame(c, P, air_liquid, f.slot, f.st, f.out, (*ev)[3]);
+        }
         else rc = launch_march_frame(c, P, f, o.mode == VRT_MODE_PRIMARY_SHADOW, variant, kstats, *ev, *ev_kind);
         if (rc) {
             if (accum) c->accum_restart = true;   // (what the sum holds is not known)

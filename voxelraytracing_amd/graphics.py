@@ -167,6 +167,20 @@ class Gpu:
         self._ck(self._lib.vrt_get_accumulation(self._h, C.byref(n), C.byref(seed)))
         return n.value, seed.value
 
+    def set_denoise(self, passes: int, sigma_color: float = 0.0):
+        """vrt_set_denoise: every later MODE_PATH frame goes through `passes` (1..5; 0 = off) passes of the edge-stopped a-trous
+        filter, tap spacing 1, 2, 4, 8, 16 pixels, sigma_color the colour stop of the first pass (halved every pass; 0 = none).
+        _ffi.DENOISE_PASSES / DENOISE_SIGMA_COLOR are the suggested setting.  Sharded and multi-device contexts refuse it."""
+        o = _ffi.DenoiseOpts(passes, sigma_color, 0, 0)
+        self._ck(self._lib.vrt_set_denoise(self._h, C.byref(o)))
+
+    def read_guide(self) -> np.ndarray:
+        """vrt_read_guide: the guide words [h, w] of the last denoised frame (the plane coordinate of each filterable pixel's face)."""
+        w, h = self.result_size
+        a = np.empty((h, w), dtype=np.uint32)
+        self._ck(self._lib.vrt_read_guide(self._h, a.ctypes.data_as(C.c_void_p)))
+        return a
+
     def synchronize(self):
         self._ck(self._lib.vrt_synchronize(self._h))
 
