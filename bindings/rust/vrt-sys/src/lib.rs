@@ -240,6 +240,22 @@ pub struct vrt_issue_profile {
     pub message_waits_us: f64,
 }
 
+/// One call of the server's BuiltFeature (server/src/world/gen.rs:312-354) for vrt_edit_chunks.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_shape {
+    pub kind: u32,
+    pub voxel: u32,
+    pub a: [i32; 3],
+    pub b: [i32; 3],
+    pub r: f32,
+    pub height: u32,
+}
+pub const VRT_SHAPE_POINT: u32 = 0;
+pub const VRT_SHAPE_LINE: u32 = 1;
+pub const VRT_SHAPE_SPHERE: u32 = 2;
+pub const VRT_SHAPE_DISC: u32 = 3;
+
 pub const VRT_ID_VOXEL_MASK: u32 = 0x7FFF;
 pub const VRT_ID_HIT: u32 = 1 << 16;
 pub const VRT_ID_NX: u32 = 1 << 17;
@@ -294,6 +310,9 @@ extern "C" {
     pub fn vrt_generate_chunks(ctx: *mut vrt_ctx, seed: u32, chunk_pos: *const i32, n: u32, nodes: *mut u16, cap_nodes: u64,
                                offsets: *mut u64) -> c_int;
     pub fn vrt_build_chunks(ctx: *mut vrt_ctx, dense: *const u16, n: u32, nodes: *mut u16, cap_nodes: u64, offsets: *mut u64) -> c_int;
+    pub fn vrt_edit_chunks(ctx: *mut vrt_ctx, chunk_pos: *const i32, n: u32, nodes_in: *const u16, offsets_in: *const u64,
+                           shapes: *const vrt_shape, m: u32, nodes_out: *mut u16, cap_nodes: u64, offsets_out: *mut u64,
+                           changed: *mut u8) -> c_int;
 }
 
 #[cfg(test)]
@@ -313,5 +332,6 @@ mod layout {
         assert_eq!(size_of::<vrt_accel_info>(), 48);
         assert_eq!(size_of::<vrt_issue_profile>(), 72);
         assert!(size_of::<vrt_denoise_opts>() == 16);
+        assert!(size_of::<vrt_shape>() == 40);
     }
 }

@@ -551,6 +551,47 @@ int vrt_generate_chunks(vrt_ctx *ctx, uint32_t seed, const int32_t *chunk_pos, u
  * vrth_svo_build_bottom_up.  Results and errors as vrt_generate_chunks's. */
 int vrt_build_chunks(vrt_ctx *ctx, const uint16_t *dense, uint32_t n, uint16_t *nodes, uint64_t cap_nodes, uint64_t *offsets);
 
+/* Editing chunks that exist: the server's feature placement (server/src/world/mod.rs:28-55 World::place_features pushes every
+ * placement of a BuiltFeature through Svo::set_node, one voxel at a time) and a client's brush, for a batch of chunks at once.
+ * A shape is one call of BuiltFeature (server/src/world/gen.rs): trees, cacti, spikes and lakes (gen.rs:357-485) are built
+ * from nothing else. */
+#define VRT_SHAPE_POINT  0u  /* BuiltFeature::set_voxel(a)                    gen.rs:312-316 */
+#define VRT_SHAPE_LINE   1u  /* place_line(a, b): common::math::walk_line     gen.rs:318-322, math.rs:228-324 */
+#define VRT_SHAPE_SPHERE 2u  /* place_sphere(a, r)                            gen.rs:342-347 */
+#define VRT_SHAPE_DISC   3u  /* place_disc(a, r, height)                      gen.rs:349-354 */
+typedef struct {
+    uint32_t kind;     /* VRT_SHAPE_* */
+    uint32_t voxel;    /* 0 .. 0x7FFF; 0 carves (Voxel::EMPTY, the lake's upper discs) */
+    int32_t  a[3];     /* the point / line start / centre, world voxel coordinates */
+    int32_t  b[3];     /* LINE: the end; otherwise ignored */
+    float    r;        /* SPHERE, DISC */
+    uint32_t height;   /* DISC */
+} vrt_shape;           /* 40 B */
+
+/* n chunks in, the same chunks with m shapes applied out.  Chunk i sits at chunk_pos[3i..]; its tree is
+ * nodes_in[offsets_in[i] .. offsets_in[i+1]) with child addresses relative to its own node 0 — a GiveChunkData payload, a
+ * region-file chunk, or a pool range from vrth_world_chunk_state; an all-air chunk is the one word 0.  The result for chunk i is,
+ * word for word, vrth_svo_build_bottom_up(D_i), D_i being vrth_svo_to_dense of its input tree with the shapes applied in order
+ * 0 .. m-1 (a later shape overwrites an earlier one: BuiltFeature's map in its call order) restricted to the chunk's 32^3 voxels;
+ * placements that fall in none of the n chunks are dropped (the reference logs a warning there).  changed[i] = 1 iff D_i differs
+ * anywhere from the expanded input, compared after all shapes.  nodes_out, cap_nodes, offsets_out, a refused tree and VRT_ERR_OOM
+ * are vrt_build_chunks's (changed is written in those cases too), and so are the batches of 2048 chunks and what the call leaves
+ * alone: everything else of the context.  n = 0: offsets_out[0] = 0.  m = 0 re-canonicalises the trees; every changed is 0.
+ * A shape's voxels are the reference's, in strict binary32:
+ *  - POINT: a.  LINE: a, then LineWalker until the major axis reaches b (an axis where a and b are equal never moves).
+ *  - SPHERE: every p with a - (int32_t)r <= p <= a + (int32_t)r per axis and d2 < r * r, d = ((float)p + 0.5f) - ((float)a + 0.5f)
+ *    per axis, d2 = (d.x*d.x + d.y*d.y) + d.z*d.z: r = 0 places nothing, r = 0.4 the centre only.
+ *  - DISC: the same test (the distance is three-dimensional, as in the reference) over a - ((int32_t)r, 0, (int32_t)r) ..
+ *    a + ((int32_t)r, (int32_t)height - 1, (int32_t)r); height = 0 places nothing.
+ * VRT_ERR_INVALID_ARG before anything is enqueued, with the outputs untouched, for: a null pointer that is needed; an unknown
+ * kind; voxel > 0x7FFF; r negative, NaN or >= 32768; height > 32768; a coordinate of a, of b (LINE) or of 32 * chunk_pos outside
+ * (-2^22, 2^22); a LINE whose largest dist exceeds 4096; offsets_in that decrease, or a range that is empty or longer than 32761;
+ * a tree that is not well-formed (a child block that leaves the chunk's own range, a split node at depth 5).
+ * VRT_ERR_OUT_OF_RANGE before any work for m > 65535, or when the (chunk, shape) pairs whose boxes intersect exceed 2^20. */
+int vrt_edit_chunks(vrt_ctx *ctx, const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes_in, const uint64_t *offsets_in,
+                    const vrt_shape *shapes, uint32_t m, uint16_t *nodes_out, uint64_t cap_nodes, uint64_t *offsets_out,
+                    uint8_t *changed);
+
 /* ---- device-side plumbing for a host that owns streams / device memory (torch, RCCL) ---- */
 
 /* Use the caller's hipStream_t for all subsequent work (NULL = the context's own stream). */

@@ -139,6 +139,16 @@ int vrth_world_generate_missing(vrth_world *w, uint32_t kind, uint32_t seed, int
 int vrth_world_create_chunks(vrth_world *w, const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes, const uint64_t *offsets,
                              uint32_t *ranges, uint32_t cap, uint32_t *n_ranges);
 
+/* ---- feature shapes (include/vrt.h: vrt_shape, vrt_edit_chunks; csrc/both/shape_math.h) ---- */
+/* m shapes, in order, onto one block dense[x + 32*(y + 32*z)] of the chunk at chunk_pos: the voxels of each shape that lie in
+ * the chunk take its voxel id.  Returns VRT_OK, or what vrt_edit_chunks returns for these shapes and this position
+ * (VRT_ERR_INVALID_ARG, VRT_ERR_OUT_OF_RANGE for m > 65535) with dense untouched. */
+int vrth_apply_shapes(uint16_t *dense, const int32_t chunk_pos[3], const vrt_shape *shapes, uint32_t m);
+/* The CPU twin of vrt_edit_chunks and its specification: vrth_svo_to_dense -> vrth_apply_shapes -> vrth_svo_build_bottom_up per
+ * chunk, the same checks, status codes and outputs; threads <= 0: all cores (at most 16). */
+int vrth_edit_chunks(const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes_in, const uint64_t *offsets_in, const vrt_shape *shapes,
+                     uint32_t m, uint16_t *nodes_out, uint64_t cap_nodes, uint64_t *offsets_out, uint8_t *changed, int threads);
+
 /* ---- region files of the reference server (servercli/src/main.rs:25-73; format in csrc/host/regionfile.hpp) ---- */
 /* Parse one `regions/r_X_Y_Z_.data` image and create_chunk every chunk of it that lies inside the world's grid.
  * Returns 0, -1 for a malformed file, or a SetVoxelErr. */

@@ -110,6 +110,16 @@ class BoxMove(C.Structure):
                 ("_reserved", C.c_uint32)]
 
 
+class Shape(C.Structure):
+    """include/vrt.h vrt_shape: one call of the server's BuiltFeature (server/src/world/gen.rs:312-354)"""
+    _fields_ = [("kind", C.c_uint32), ("voxel", C.c_uint32), ("a", C.c_int32 * 3), ("b", C.c_int32 * 3), ("r", C.c_float),
+                ("height", C.c_uint32)]
+
+
+SHAPE_POINT, SHAPE_LINE, SHAPE_SPHERE, SHAPE_DISC = 0, 1, 2, 3   # vrt_shape.kind (VRT_SHAPE_*)
+SHAPE_DTYPE = np.dtype([("kind", "<u4"), ("voxel", "<u4"), ("a", "<i4", 3), ("b", "<i4", 3), ("r", "<f4"), ("height", "<u4")])
+assert C.sizeof(Shape) == 40 and SHAPE_DTYPE.itemsize == 40
+
 RAY_MISS, RAY_HIT, RAY_REJECTED = 0, 1, 2
 BOX_AUTOJUMP, BOX_MAX_VOXELS = 1, 4096                      # vrt_box_query.flags, the cap on the first gather's range
 BOX_MOVED, BOX_REJECTED = 0, 2                              # vrt_box_move.status
@@ -185,6 +195,7 @@ VRT_SYMBOLS = {
     "vrt_clip_moves_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_generate_chunks": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "vrt_build_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P]),
+    "vrt_edit_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P]),
 }
 
 
@@ -331,6 +342,8 @@ VRTH_SYMBOLS = {
     "vrth_gen_dense_superflat": (None, [_I32P, _P]),
     "vrth_world_generate": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int]),
     "vrth_world_generate_missing": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int, _P, C.c_uint32, _U32P]),
+    "vrth_apply_shapes": (C.c_int, [_P, _I32P, _P, C.c_uint32]),
+    "vrth_edit_chunks": (C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, C.c_int]),
     "vrth_region_load_into_world": (C.c_int, [_P, _P, C.c_uint64, _I32P, _U32P]),
     "vrth_region_save_from_world": (C.c_uint64, [_P, _I32P, _P, C.c_uint64]),
     "vrth_chunk_msg_ingest": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64), _I32P, _U32P, _U32P]),

@@ -10,7 +10,9 @@
 #include "../../../include/vrt_host.h"
 #include "../both/cast_dda.h"
 #include "../both/denoise_math.h"
+#include "../both/shape_math.h"
 #include "collide.hpp"
+#include "edit_check.hpp"
 #include "graphics.hpp"
 #include "materials.hpp"
 #include "netmsg.hpp"
@@ -367,6 +369,81 @@ int vrth_world_create_chunks(vrth_world *w, const int32_t *chunk_pos, uint32_t n
     return 0;
 }
 
+
+// ---- feature shapes (include/vrt.h vrt_edit_chunks): the specification of vrt_edit.hip's kernels ----
+
+// One shape onto the block of the chunk whose first voxel is (x0, y0, z0): BuiltFeature's placements (gen.rs:312-354) that lie
+// in the chunk, from ../both/shape_math.h's parts
+static void apply_shape(uint16_t *dense, int32_t x0, int32_t y0, int32_t z0, const vrt_shape &s) {
+    const uint16_t v = (uint16_t)s.voxel;
+    auto put = [&](int32_t x, int32_t y, int32_t z) {
+        const uint32_t lx = (uint32_t)(x - x0), ly = (uint32_t)(y - y0), lz = (uint32_t)(z - z0);
+        if (lx < 32u && ly < 32u && lz < 32u) dense[lx + 32u * (ly + 32u * lz)] = v;
+    };
+    if (s.kind == kShapePoint) {
+        put(s.a[0], s.a[1], s.a[2]);
+    } else if (s.kind == kShapeLine) {
+        LineWalk w = line_begin(s);
+        do put(w.x, w.y, w.z);
+        while (line_next(w));
+    } else {
+        ShapeBox bx = shape_box(s);
+        if (!shape_box_clip(bx, x0, y0, z0)) return;
+        const float r2 = s.r * s.r;
+        for (int32_t z = bx.lo[2]; z <= bx.hi[2]; z++)
+            for (int32_t y = bx.lo[1]; y <= bx.hi[1]; y++)
+                for (int32_t x = bx.lo[0]; x <= bx.hi[0]; x++)
+                    if (shape_within(s.a[0], s.a[1], s.a[2], r2, x, y, z)) put(x, y, z);
+    }
+}
+
+static int edit_status(EditFault f) { return f == EditFault::None ? VRT_OK : edit_fault_is_range(f) ? VRT_ERR_OUT_OF_RANGE : VRT_ERR_INVALID_ARG; }
+
+int vrth_apply_shapes(uint16_t *dense, const int32_t chunk_pos[3], const vrt_shape *shapes, uint32_t m) {
+    if (!dense || !chunk_pos) return VRT_ERR_INVALID_ARG;
+    // (the checks of a call with this one chunk, as an all-air tree)
+    const uint16_t air = 0;
+    const uint64_t offs[2] = {0, 1};
+    uint64_t out_offs[2] = {0, 0}, index;
+    uint8_t changed = 0;
+    EditBins bins;
+    if (const EditFault f = edit_check(chunk_pos, 1, &air, offs, shapes, m, nullptr, 0, out_offs, &changed, bins, &index); f != EditFault::None)
+        return edit_status(f);
+    for (uint16_t j : bins.list) apply_shape(dense, chunk_pos[0] * 32, chunk_pos[1] * 32, chunk_pos[2] * 32, shapes[j]);
+    return VRT_OK;
+}
+
+int vrth_edit_chunks(const int32_t *chunk_pos, uint32_t n, const uint16_t *nodes_in, const uint64_t *offsets_in, const vrt_shape *shapes,
+                     uint32_t m, uint16_t *nodes_out, uint64_t cap_nodes, uint64_t *offsets_out, uint8_t *changed, int threads) {
+    EditBins bins;
+    uint64_t index;
+    if (const EditFault f = edit_check(chunk_pos, n, nodes_in, offsets_in, shapes, m, nodes_out, cap_nodes, offsets_out, changed, bins, &index);
+        f != EditFault::None)
+        return edit_status(f);
+    offsets_out[0] = 0;
+    if (n == 0) return VRT_OK;
+    std::vector<std::vector<Node>> built(n);
+    parallel_blocks(n, 1, threads, 16u, [&](size_t i, size_t) {
+        thread_local std::vector<uint16_t> before(32768), dense(32768);
+        vrth_svo_to_dense(nodes_in + offsets_in[i], before.data());
+        dense = before;
+        const int32_t *p = chunk_pos + 3 * i;
+        for (uint32_t k = bins.start[i]; k < bins.start[i + 1]; k++) apply_shape(dense.data(), p[0] * 32, p[1] * 32, p[2] * 32, shapes[bins.list[k]]);
+        changed[i] = dense != before;
+        if (!build_svo_bottom_up(dense.data(), built[i])) built[i].clear();   // refused: an empty range
+        return true;
+    });
+    // the outputs, as vrt_build_chunks leaves them
+    uint32_t refused = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        offsets_out[i + 1] = offsets_out[i] + built[i].size();
+        refused += built[i].empty();
+    }
+    if (offsets_out[n] > cap_nodes) return VRT_ERR_OOM;
+    for (uint32_t i = 0; i < n; i++)
+        if (!built[i].empty()) std::memcpy(nodes_out + offsets_out[i], built[i].data(), built[i].size() * sizeof(Node));
+    return refused ? VRT_ERR_OUT_OF_RANGE : VRT_OK;
+}
 
 // ---- region files (servercli/src/main.rs:25-73) ----
 

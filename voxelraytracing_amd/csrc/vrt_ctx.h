@@ -8,6 +8,7 @@
 //   vrt_cast.hip, vrt_clip.hip   the world queries (vrt_cast_rays, vrt_clip_moves) over vrt_query.h: the world as a kernel
 //                    sees it and the host-pointer batch
 //   vrt_gen.hip      the chunk source (vrt_generate_chunks, vrt_build_chunks)
+//   vrt_edit.hip     shapes onto chunks that exist (vrt_edit_chunks), in front of vrt_gen.hip's builder
 //   vrt_denoise.hip  the path trace's denoiser (vrt_set_denoise, vrt_read_guide) and its kernels
 //   both/            not of this seam: the arithmetic those three kernels share with the host mirror (both/both.h)
 //
@@ -342,6 +343,15 @@ struct vrt_ctx {
     uint16_t *d_gen_dense = nullptr;
     uint16_t *d_gen_out = nullptr;
     uint64_t gen_out_cap = 0;
+    // vrt_edit_chunks (vrt_edit.hip): one batch's input trees and per-chunk records, the call's shapes and bins (grown as needed)
+    uint16_t *d_edit_nodes = nullptr;
+    uint64_t edit_nodes_cap = 0;
+    void *d_edit_chunks = nullptr;     // kGenBatch records
+    uint8_t *d_edit_changed = nullptr; // kGenBatch
+    void *d_edit_shapes = nullptr;
+    uint32_t edit_shapes_cap = 0;
+    uint16_t *d_edit_bins = nullptr;
+    uint64_t edit_bins_cap = 0;
 
     vrt_material h_mats[256];
     float h_emission[256];    // vrt_write_emission's table (zeros at creation) and how many of its entries are not 0: a frame
@@ -408,6 +418,15 @@ static constexpr uint32_t kMaxDirtyChunks = 256;
 #define VRT_HIDDEN __attribute__((visibility("hidden")))
 extern VRT_HIDDEN thread_local std::string g_create_err;
 VRT_HIDDEN int fail(vrt_ctx *ctx, int code, const char *fmt, ...);
+// vrt_gen.hip's builder over blocks that are on the device already (vrt_edit.hip): n chunks in batches of 2048; for each batch
+// fill(c, arg, b0, nb) enqueues on c->stream whatever leaves chunk b0 + i's block dense[x + 32*(y + 32*z)] in
+// c->d_gen_dense + 32768 i (a non-zero return ends the call with it), then the builder, the scan and the gather run and
+// nodes / offsets come out as vrt_build_chunks's do.  The stream is drained once per batch, after fill's work and the scan.
+namespace vrt {
+typedef int (*GenFillFn)(vrt_ctx *c, void *arg, uint32_t b0, uint32_t nb);
+VRT_HIDDEN int gen_build_device_blocks(vrt_ctx *c, GenFillFn fill, void *fill_arg, uint32_t n, uint16_t *nodes, uint64_t cap_nodes,
+                                       uint64_t *offsets, const char *what);
+}
 #define HIP_TRY(ctx, expr)                                                                          \
     do {                                                                                            \
         hipError_t e_ = (expr);                                                                     \

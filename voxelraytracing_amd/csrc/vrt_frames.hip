@@ -669,6 +669,8 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
     (void)hipFree(c->d_gen_stage); (void)hipFree(c->d_gen_counts); (void)hipFree(c->d_gen_offs); (void)hipFree(c->d_gen_pos);
     (void)hipFree(c->d_gen_dense); (void)hipFree(c->d_gen_out);
+    (void)hipFree(c->d_edit_nodes); (void)hipFree(c->d_edit_chunks); (void)hipFree(c->d_edit_changed); (void)hipFree(c->d_edit_shapes);
+    (void)hipFree(c->d_edit_bins);
     for (auto &T : c->tabs) {
         (void)free_tables(c, T);
         if (T.ev_updated) (void)hipEventDestroy(T.ev_updated);

@@ -241,13 +241,14 @@ __global__ __launch_bounds__(kGenBlock) void gen_gather_kernel(const uint16_t *s
 // One call: the chunks in batches of kGenBatch on c->stream.  Per batch: inputs up, the builder, the scan, the offsets down
 // (the one wait), then — while everything so far fits in cap_nodes — the gather into d_gen_out.  The nodes come down once, at
 // the end, and only if all of them fit: on VRT_ERR_OOM `nodes` is untouched and every offset is written.
+// With `fill` (vrt_ctx.h gen_build_device_blocks) a batch's blocks are not copied up: fill leaves them in d_gen_dense.
 static int gen_run(vrt_ctx *c, bool gen, uint32_t seed, const int32_t *pos, const uint16_t *dense, uint32_t n, uint16_t *nodes,
-                   uint64_t cap_nodes, uint64_t *offsets, const char *what) {
+                   uint64_t cap_nodes, uint64_t *offsets, const char *what, vrt::GenFillFn fill = nullptr, void *fill_arg = nullptr) {
     using namespace vrt;
     if (!offsets) return fail(c, VRT_ERR_INVALID_ARG, "%s: offsets is null", what);
     offsets[0] = 0;
     if (n == 0u) return VRT_OK;
-    if (gen ? !pos : !dense) return fail(c, VRT_ERR_INVALID_ARG, "%s: null input", what);
+    if (gen ? !pos : (!dense && !fill)) return fail(c, VRT_ERR_INVALID_ARG, "%s: null input", what);
     if (gen)
         for (uint64_t i = 0; i < 3ull * n; i++)
             if (pos[i] <= -kCoordLimit || pos[i] >= kCoordLimit)
@@ -278,7 +279,11 @@ static int gen_run(vrt_ctx *c, bool gen, uint32_t seed, const int32_t *pos, cons
             HIP_TRY(c, hipMemcpyAsync(c->d_gen_pos, pos + 3ull * b0, (size_t)nb * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
             gen_chunks_kernel<true><<<dim3(nb), dim3(kGenBlock), 0, st>>>(P);
         } else {
-            HIP_TRY(c, hipMemcpyAsync(c->d_gen_dense, dense + 32768ull * b0, (size_t)nb * 32768u * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+            if (fill) {
+                if (const int rc = fill(c, fill_arg, b0, nb)) return rc;
+            } else {
+                HIP_TRY(c, hipMemcpyAsync(c->d_gen_dense, dense + 32768ull * b0, (size_t)nb * 32768u * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+            }
             gen_chunks_kernel<false><<<dim3(nb), dim3(kGenBlock), 0, st>>>(P);
         }
         HIP_TRY(c, hipGetLastError());
@@ -322,6 +327,13 @@ static int gen_run(vrt_ctx *c, bool gen, uint32_t seed, const int32_t *pos, cons
                     what, refused);
     return VRT_OK;
 }
+
+namespace vrt {
+int gen_build_device_blocks(vrt_ctx *c, GenFillFn fill, void *fill_arg, uint32_t n, uint16_t *nodes, uint64_t cap_nodes, uint64_t *offsets,
+                            const char *what) {
+    return gen_run(c, false, 0u, nullptr, nullptr, n, nodes, cap_nodes, offsets, what, fill, fill_arg);
+}
+}  // namespace vrt
 
 extern "C" {
 

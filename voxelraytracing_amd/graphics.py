@@ -310,7 +310,7 @@ class Gpu:
         context's stream (vrt_set_stream) without waiting."""
         self._ck(self._lib.vrt_clip_moves_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
 
-    # --- the chunk source (include/vrt.h vrt_generate_chunks / vrt_build_chunks) ---
+    # --- the chunk source (include/vrt.h vrt_generate_chunks / vrt_build_chunks / vrt_edit_chunks) ---
     def generate_chunks(self, seed: int, positions, strict: bool = True):
         """The build's world generator on the GPU (csrc/host/worldgen.hpp): (n,3) chunk positions -> (nodes, offsets), chunk i's
         nodes being nodes[offsets[i]:offsets[i+1]], word for word svo_build_bottom_up(gen_dense(seed, pos)).  A chunk whose tree
@@ -325,6 +325,26 @@ class Gpu:
         d = np.ascontiguousarray(np.asarray(dense, np.uint16).reshape(-1, 32768))
         return self._chunks(lambda nodes, cap, offs: self._lib.vrt_build_chunks(self._h, d.ctypes.data, d.shape[0], nodes, cap, offs),
                             d.shape[0], strict)
+
+    def edit_chunks(self, positions, nodes, offsets, shapes, strict: bool = True):
+        """The server's feature placement (World::place_features, server/src/world/mod.rs:28-55) or a brush, on the GPU: chunks
+        at (n,3) positions with trees nodes[offsets[i]:offsets[i+1]] (chunk-relative child addresses: a GiveChunkData payload,
+        a pool range) and vrt_shape records (world.shape_records) applied in order -> (nodes, offsets, changed); chunk i's new
+        tree is word for word svo_build_bottom_up of its edited voxels and changed[i] says whether any voxel differs (the
+        chunks to re-broadcast).  The CPU twin is world.edit_chunks.  strict as generate_chunks's."""
+        from .world import shape_records
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        nin = np.ascontiguousarray(nodes, np.uint16)
+        oin = np.ascontiguousarray(offsets, np.uint64)
+        sh = shape_records(shapes)
+        n = pos.shape[0]
+        if oin.size != n + 1:
+            raise ValueError(f"{n} chunks need {n + 1} offsets, not {oin.size}")
+        changed = np.zeros(n, np.uint8)
+        nodes_out, offs = self._chunks(lambda out, cap, offs: self._lib.vrt_edit_chunks(
+            self._h, pos.ctypes.data, n, nin.ctypes.data, oin.ctypes.data, sh.ctypes.data if sh.size else None, sh.size, out, cap, offs,
+            changed.ctypes.data), n, strict)
+        return nodes_out, offs, changed
 
     def _chunks(self, call, n: int, strict: bool):
         offs = np.zeros(n + 1, np.uint64)

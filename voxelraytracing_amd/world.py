@@ -411,6 +411,79 @@ def gen_dense_superflat(chunk_pos) -> np.ndarray:
     return dense
 
 
+# ---- feature shapes (include/vrt.h vrt_shape; server/src/world/gen.rs:312-354) ----
+
+class ShapeError(ValueError):
+    """A status of vrth_apply_shapes / vrth_edit_chunks (include/vrt.h vrt_status: -1 invalid argument, -2 out of range, -4 the
+    nodes do not fit)."""
+    def __init__(self, code: int, what: str):
+        super().__init__(f"{what}: vrt status {code}")
+        self.code = code
+
+
+def shape_point(a, voxel: int):
+    """BuiltFeature::set_voxel(a, voxel) as a vrt_shape record."""
+    return (_ffi.SHAPE_POINT, voxel, tuple(a), (0, 0, 0), 0.0, 0)
+
+
+def shape_line(a, b, voxel: int):
+    """place_line(a, b, voxel)"""
+    return (_ffi.SHAPE_LINE, voxel, tuple(a), tuple(b), 0.0, 0)
+
+
+def shape_sphere(a, r: float, voxel: int):
+    """place_sphere(a, r, voxel)"""
+    return (_ffi.SHAPE_SPHERE, voxel, tuple(a), (0, 0, 0), r, 0)
+
+
+def shape_disc(a, r: float, height: int, voxel: int):
+    """place_disc(a, r, height, voxel)"""
+    return (_ffi.SHAPE_DISC, voxel, tuple(a), (0, 0, 0), r, height)
+
+
+def shape_records(shapes) -> np.ndarray:
+    """vrt_shape records (_ffi.SHAPE_DTYPE) from such an array or a list of shape_point / _line / _sphere / _disc."""
+    if isinstance(shapes, np.ndarray) and shapes.dtype == _ffi.SHAPE_DTYPE:
+        return np.ascontiguousarray(shapes).reshape(-1)
+    return np.array(list(shapes), _ffi.SHAPE_DTYPE).reshape(-1)
+
+
+def apply_shapes(dense: np.ndarray, chunk_pos, shapes) -> np.ndarray:
+    """The shapes, in order, onto a copy of the block dense[x + 32*(y + 32*z)] of the chunk at chunk_pos (vrth_apply_shapes)."""
+    out = np.array(dense, dtype=np.uint16).reshape(-1)
+    assert out.size == 32768
+    sh = shape_records(shapes)
+    rc = _ffi.host().vrth_apply_shapes(_u16p(out), _i3(chunk_pos), sh.ctypes.data if sh.size else None, sh.size)
+    if rc:
+        raise ShapeError(rc, "apply_shapes")
+    return out
+
+
+def edit_chunks(positions, nodes, offsets, shapes, strict: bool = True, threads: int = 0):
+    """vrth_edit_chunks, the CPU twin of Gpu.edit_chunks: (n,3) chunk positions, their trees nodes[offsets[i]:offsets[i+1]] and
+    the shapes -> (nodes, offsets, changed).  strict=False returns the other chunks when the builder refuses one."""
+    pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+    nin = np.ascontiguousarray(nodes, np.uint16)
+    oin = np.ascontiguousarray(offsets, np.uint64)
+    sh = shape_records(shapes)
+    n = pos.shape[0]
+    assert oin.size == n + 1
+    offs = np.zeros(n + 1, np.uint64)
+    changed = np.zeros(n, np.uint8)
+    out = np.empty(max(1, 2048 * n), np.uint16)
+
+    def call():
+        return _ffi.host().vrth_edit_chunks(pos.ctypes.data, n, nin.ctypes.data, oin.ctypes.data, sh.ctypes.data if sh.size else None,
+                                            sh.size, out.ctypes.data, out.size, offs.ctypes.data, changed.ctypes.data, threads)
+    rc = call()
+    if rc == _ffi.VRT_ERR_OOM and int(offs[n]) > out.size:
+        out = np.empty(int(offs[n]), np.uint16)
+        rc = call()
+    if rc and not (rc == _ffi.VRT_ERR_OUT_OF_RANGE and not strict):
+        raise ShapeError(rc, "edit_chunks")
+    return out[:int(offs[n])].copy(), offs, changed
+
+
 def gen_height(seed: int, x: int, z: int) -> int:
     return _ffi.host().vrth_gen_height(seed, x, z)
 
