@@ -1,0 +1,200 @@
+"""The context's device buffers through their lives (csrc/vrt_devbuf.h): the ones a resize drops made again at a smaller and a
+larger size, the grow-only ones across their floors and back, and whole contexts made and destroyed in a row — at the smallest
+shapes, every answer held to the oracle or to the host mirror (never to an earlier answer of the build under test)."""
+import numpy as np
+import pytest
+
+import cast_ray_cases as cc
+import clip_cases as cl
+import denoise_ref
+from test_edit_chunks_ref import CORNER_CHUNK, STONE, WOOD, _block
+from util import assert_frame_parity, gpu_for_scene
+from voxelraytracing_amd import MODE_PATH, MODE_PRIMARY_SHADOW, scenes
+from voxelraytracing_amd import graphics as g
+from voxelraytracing_amd import world as W
+from voxelraytracing_amd.world import shape_point, shape_sphere
+
+pytestmark = pytest.mark.gpu
+
+SEED = 11
+BATCH = 2048   # chunks per internal batch of the generator (include/vrt.h)
+
+
+def _path_scene(chunks, size):
+    """scenes.c4's settings over a world of chunks^3."""
+    sc = scenes.procedural(chunks, size, MODE_PATH)
+    sc.settings.max_ray_bounces = 4
+    for i in range(256):
+        sc.materials[i].scatter = 1.0
+    return sc
+
+
+def test_output_world_and_frames_in_flight_shrink_and_regrow(orc, tmp_path):
+    """64 x 40 over 2^3 chunks; down to 24 x 16 and back, 2^3 -> 3^3 -> 2^3 chunks, 1 -> 4 -> 2 frames in flight, and behind every
+    step primary + shadow frames, path frames of 1 and 4 spp, a denoised one and accumulated ones, each against the oracle.
+
+    The denoised frame: its guide is the oracle's word for word; its radiance is held to the reference filter
+    (tests/denoise_ref.c) over the ORACLE's frame and guide.  Without a colour stop (sigma_color 0) a pass is a weighted mean
+    whose weights depend on the guide alone, so the passes cannot widen the 1e-4 the raw frames may differ by."""
+    ref = denoise_ref.load(tmp_path)
+    worlds = {2: _path_scene(2, (64, 40)), 3: _path_scene(3, (64, 40))}
+    oracles = {s: orc.from_package_scene(sc) for s, sc in worlds.items()}
+    sc = worlds[2]
+    gpu = gpu_for_scene(sc)          # (both pools have the same number of nodes)
+    assert worlds[3].world.max_nodes() == sc.world.max_nodes()
+    gpu.set_frames_in_flight(1)
+    state = {"s": 2, "size": (64, 40)}
+
+    def frames(what):
+        s, (w, h) = state["s"], state["size"]
+        scn, o = worlds[s], oracles[s]
+        cam = g.cam_data_create(scn.rot, scn.eye, 70.0, (float(w), float(h)))
+        gpu.write_cam_data(cam)
+        o.set_cam(cam)
+        gpu.set_denoise(0)
+        for _ in range(5):           # every frame set in turn, the last one read
+            gpu.render(MODE_PRIMARY_SHADOW)
+        rgb, ids, _ = gpu.read_output()
+        r_rgb, r_ids, _, _ = o.render(orc.MODE_PRIMARY_SHADOW, w, h)
+        assert_frame_parity(rgb, ids, r_rgb, r_ids, f"{what}: primary + shadow")
+        path = {}
+        for spp in (1, 4):
+            for _ in range(2):
+                gpu.render(MODE_PATH, spp=spp, seed=SEED)
+            rgb, ids, _ = gpu.read_output()
+            path[spp] = o.render(orc.MODE_PATH, w, h, spp=spp, seed=SEED)[:2]
+            assert_frame_parity(rgb, ids, path[spp][0], path[spp][1], f"{what}: path, {spp} spp")
+        gpu.set_denoise(3, 0.0)
+        for _ in range(2):
+            gpu.render(MODE_PATH, spp=4, seed=SEED)
+        rgb, ids, _ = gpu.read_output()
+        guide, guide_ids = ref.guide(o, w, h)
+        assert np.array_equal(gpu.read_guide(), guide) and np.array_equal(guide_ids, path[4][1]), f"{what}: guide words"
+        assert_frame_parity(rgb, ids, ref.denoise(path[4][0], path[4][1], guide, 3, 0.0), path[4][1], f"{what}: denoised")
+        gpu.set_denoise(0)
+        gpu.reset_accumulation()
+        for spp in (1, 2, 1):        # the one-sample and the plane path into one sum
+            gpu.render(MODE_PATH, spp=spp, seed=SEED, accumulate=True)
+        rgb, ids, _ = gpu.read_output()
+        assert gpu.accumulation() == (4, SEED)
+        assert_frame_parity(rgb, ids, path[4][0], path[4][1], f"{what}: 1 + 2 + 1 accumulated")
+
+    def resize(size):
+        gpu.resize_result_texture(size)
+        state["size"] = size
+
+    def world(s):
+        gpu.resize_chunk_buffer(s)
+        gpu.upload_world(worlds[s].world, worlds[s].materials)
+        state["s"] = s
+
+    frames("as created")
+    resize((24, 16))
+    frames("24 x 16")
+    resize((64, 40))
+    frames("64 x 40 again")
+    gpu.set_frames_in_flight(4)
+    frames("4 in flight")
+    resize((24, 16))
+    frames("4 in flight, 24 x 16")
+    world(3)
+    frames("3^3 chunks")
+    resize((64, 40))
+    gpu.set_frames_in_flight(2)
+    frames("3^3 chunks, 2 in flight, 64 x 40")
+    world(2)
+    frames("2^3 chunks again")
+    gpu.close()
+
+
+def test_a_tile_order_and_a_step_count_frame_on_either_side_of_a_resize(orc):
+    """One frame in flight and at least 128 tiles (128 x 64): frames of a view at rest come to be launched in an order
+    (ordered_frames rises), and a stats frame counts its steps.  Then down to 64 x 40 (40 tiles: no order; the order's buffers
+    and the step counts go while alive), up to 136 x 64 (another tile count) and back to 128 x 64: an order is made again each
+    time, and every frame and every step count is the oracle's."""
+    sc = scenes.procedural(2, (128, 64))
+    gpu = gpu_for_scene(sc)
+    gpu.set_frames_in_flight(1)
+    o = orc.from_package_scene(sc)
+    for n, (w, h) in enumerate([(128, 64), (64, 40), (136, 64), (128, 64)]):
+        if n:
+            gpu.resize_result_texture((w, h))
+        cam = g.cam_data_create(sc.rot, sc.eye, 70.0, (float(w), float(h)))
+        gpu.write_cam_data(cam)
+        o.set_cam(cam)
+        r_rgb, r_ids, r_steps, _ = o.render(orc.MODE_PRIMARY_SHADOW, w, h, want_steps=True)
+        before = gpu.accel_info().ordered_frames
+        for _ in range(4):           # the second frame of the view notes its trips, the ones behind it use the order
+            gpu.render(MODE_PRIMARY_SHADOW)
+        ordered = gpu.accel_info().ordered_frames - before
+        assert (ordered > 0) == ((w // 8) * (h // 8) >= 128), f"{w} x {h}: {ordered} ordered frames"
+        rgb, ids, _ = gpu.read_output()
+        assert_frame_parity(rgb, ids, r_rgb, r_ids, f"{w} x {h}, step {n}: the last of four frames")
+        gpu.render(MODE_PRIMARY_SHADOW, stats=True)
+        rgb, ids, _ = gpu.read_output()
+        assert_frame_parity(rgb, ids, r_rgb, r_ids, f"{w} x {h}, step {n}: stats frame")
+        assert np.array_equal(gpu.read_steps(), r_steps), f"{w} x {h}, step {n}: step counts"
+    gpu.close()
+
+
+def test_query_batches_grow_and_shrink():
+    """Host batches of 64, 4096 and 64 queries again through the one staging buffer of vrt_cast_rays and vrt_clip_moves."""
+    sc = scenes.procedural(2, (8, 8))
+    gpu = gpu_for_scene(sc)
+    rays = cc.fuzz_queries(sc.world, 4096, seed=21)
+    boxes = cl.fuzz_queries(sc.world, 4096, seed=31)
+    want_rays = sc.world.cast_rays(rays["start"], rays["dir"], rays["max_dist"])
+    want_boxes = sc.world.clip_moves(boxes, sc.materials)
+    assert {0, 1} <= set(np.unique(want_rays["status"]).tolist())
+    for n in (64, 4096, 64):
+        got = gpu.cast_rays(rays["start"][:n], rays["dir"][:n], rays["max_dist"][:n])
+        bad = cc.records_equal(want_rays[:n], got)
+        assert bad.size == 0, f"{n} rays: {bad.size} differ from the host mirror, first {bad[0]}"
+        got = gpu.clip_moves(boxes[:n])
+        bad = cl.records_differ(want_boxes[:n], got)
+        assert bad.size == 0, f"{n} boxes: {bad.size} differ from the host mirror, first {bad[0]}"
+    gpu.close()
+
+
+def test_a_few_generated_chunks_then_one_more_than_a_batch():
+    """3 chunks size the call's node buffer; 2049 grow it in the first batch and again, keeping that batch's nodes, in the second."""
+    gpu = g.Gpu(1 << 16, 2, (8, 8), device=0)
+    # mostly air far above the terrain (one node each), terrain every 64th chunk and in the second batch's only chunk
+    pos = np.array([(i % 47 - 20, 2 if i % 64 == 0 or i == BATCH else 9, i // 47 - 20) for i in range(BATCH + 1)], np.int32)
+    wants = [W.svo_build_bottom_up(W.gen_dense(1, tuple(p))) for p in pos]
+    assert wants[0].size > 1 and wants[BATCH].size > 1 and wants[1].size == 1
+    for n in (3, BATCH + 1):
+        nodes, offs = gpu.generate_chunks(1, pos[:n])
+        assert np.array_equal(offs, np.concatenate([[0], np.cumsum([w.size for w in wants[:n]])]).astype(np.uint64)), f"{n} chunks: offsets"
+        assert np.array_equal(nodes, np.concatenate(wants[:n])), f"{n} chunks: nodes differ from the host generator's"
+    gpu.close()
+
+
+def test_one_shape_then_more_than_the_shape_and_bin_floors():
+    """vrt_edit_chunks with 1 shape, then 1025 (floors: 1024 shapes, 4096 bin entries) on the corner of eight generated chunks."""
+    gpu = g.Gpu(1 << 16, 2, (8, 8), device=0)
+    pos, nodes, offs, _ = _block(CORNER_CHUNK)
+    c = tuple(32 * v for v in CORNER_CHUNK)
+    rng = np.random.default_rng(5)
+    many = [shape_sphere(tuple(int(v) for v in (np.array(c) + rng.integers(-2, 3, 3))), 2.9, int(rng.choice([STONE, WOOD, 0])))
+            for _ in range(1024)] + [shape_point(c, STONE)]
+    for shapes in ([shape_point(c, WOOD)], many, [shape_point(c, WOOD)]):
+        want = W.edit_chunks(pos, nodes, offs, shapes, strict=False, threads=4)
+        got = gpu.edit_chunks(pos, nodes, offs, shapes, strict=False)
+        for name, a, b in zip(("nodes", "offsets", "changed"), got, want):
+            assert np.array_equal(a, b), f"{len(shapes)} shapes: {name} differ from the host mirror's"
+        if len(shapes) > 1:
+            assert want[2].all()     # every one of the eight chunks is in many shapes' bins: 8 x 1024 entries
+    gpu.close()
+
+
+def test_contexts_made_and_destroyed_in_a_row(orc):
+    sc = scenes.c1_flat((64, 40))
+    r_rgb, r_ids, _, _ = orc.from_package_scene(sc).render(orc.MODE_PRIMARY_SHADOW, 64, 40)
+    for k in range(4):
+        gpu = gpu_for_scene(sc)
+        for _ in range(3):
+            gpu.render(MODE_PRIMARY_SHADOW)
+        rgb, ids, _ = gpu.read_output()
+        assert_frame_parity(rgb, ids, r_rgb, r_ids, f"context {k}")
+        gpu.close()

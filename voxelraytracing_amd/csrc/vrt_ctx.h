@@ -17,6 +17,8 @@
 // (DESIGN.md §HBM layout): the node pool is kept byte-identical to the host pool (little-endian u16 =
 // the reference's packed u32 pairs), chunk_roots is a dense u32[S^3], materials 256 x 32 B, output one
 // 16-byte texel {r,g,b f32, id u32} per pixel slot, hit buffer 16 B per local pixel.
+// Ownership: every device allocation of a context is a vrt_ctx::Buf (vrt_devbuf.h), freed with the context; raw pointers are
+// aliases or the caller's memory.  What depends on the output size is vrt_ctx::Sized: a resize assigns it an empty value.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,10 +38,15 @@
 #include <string>
 #include <vector>
 
+#include "vrt_devbuf.h"
 #include "vrt_device.h"
 #include "vrt_exp.h"
 
 namespace vrt {
+struct HipAlloc {   // vrt_devbuf.h's allocator over the HIP runtime
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
 bool variant_supported(uint32_t variant);
 void launch_primary(const FrameParams &P, uint32_t variant, bool stats, bool shadow, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 void launch_shadow(const FrameParams &P, uint32_t variant, bool stats, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
@@ -112,9 +119,16 @@ static_assert(sizeof(vrt_crosshair) == 32, "Crosshair layout (mod.rs:63-70)");
 static_assert(sizeof(vrt::Texel) == 16, "texel");
 
 struct vrt_group;
-struct vrt_group;
+
+static constexpr size_t kSegBytes = (size_t)vrt::kHitSegments * vrt::kSegStride * sizeof(uint32_t);
+// three sets of segment cursors: launch g of a path frame appends to set g % 3, reads set (g - 1) % 3 and clears set
+// (g + 1) % 3 for its successor, so no memset sits between two launches
+static constexpr size_t kCounterBytes = vrt::kCtrCount * sizeof(unsigned long long) + 3 * kSegBytes;   // + the path trace's 3 cursor sets
+static constexpr size_t kCounterWords = kCounterBytes / sizeof(unsigned long long);
+static_assert(kCounterWords * sizeof(unsigned long long) == kCounterBytes, "the counters are allocated as 64-bit words");
 
 struct vrt_ctx {
+    template <typename T> using Buf = vrt::DevBuf<T, vrt::HipAlloc>;
     vrt_group *grp = nullptr;   // a multi-device context (vrt_config.n_devices > 1): everything else below is unused, see vrt_group
     hipStream_t last_stream = nullptr;  // the stream the most recent frame was enqueued on
     hipEvent_t wait_before_frame = nullptr;  // set by a multi-device context: the next frame's stream waits for it first (its message slot is free)
@@ -125,10 +139,7 @@ struct vrt_ctx {
     // instead of the in-order queue's ~5 us hand-over.  Everything else on the context waits for both (quiesce()).
     static constexpr uint32_t kMaxInFlight = 4;
     hipStream_t extra_stream[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};
-    vrt::Texel *extra_out[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};
-    uint32_t *extra_blk[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};
-    uint4 *extra_path[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};                   // path mode: its own path buffers
-    unsigned long long *extra_counters[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};  // ... and segment cursors
+    Buf<unsigned long long> extra_counters[kMaxInFlight - 1];   // path mode: its own segment cursors
     uint32_t in_flight = 2;        // vrt_set_frames_in_flight
     bool alt_pending = false;      // frames may still be running on the extra streams
     bool own_pending = false;      // ... or on own_stream while the caller's stream is the context's stream (VRT_RENDER_OWN_STREAMS)
@@ -155,26 +166,41 @@ struct vrt_ctx {
     uint32_t tiles_x = 0, tiles_total = 0, tiles_local = 0, tiles_padded = 0;
     uint32_t slots = 0;  // pixel slots in the output buffer
 
-    uint16_t *d_nodes = nullptr;
-    uint32_t *d_roots = nullptr;
-    vrt_material *d_mats = nullptr;   // the 256 materials, then the 256 floats of the emission table (vrt::emission_table)
-    vrt::Texel *d_out = nullptr;    // where frames are written: own_out or caller-bound memory
-    vrt::Texel *own_out = nullptr;
+    Buf<uint16_t> d_nodes;
+    Buf<uint32_t> d_roots;
+    Buf<vrt_material> d_mats;       // the 256 materials, then the 256 floats of the emission table (vrt::emission_table): kMatsAlloc
+    vrt::Texel *d_out = nullptr;    // where frames are written: sz.own_out or caller-bound memory
     vrt::Texel *last_out = nullptr;  // the buffer holding the most recent frame
     uint32_t *last_blk = nullptr;
-    uint4 *d_hits = nullptr;
-    uint32_t *d_blk_counts = nullptr;  // hit records per primary workgroup
+    // What a resize drops (alloc_output assigns an empty Sized, then makes own_out, d_hits and d_blk_counts again): every buffer
+    // sized by the output, made on first use, and what is only true of their contents.
+    struct Sized {
+        Buf<vrt::Texel> own_out;
+        Buf<uint4> d_hits;
+        Buf<uint32_t> d_blk_counts;  // hit records per primary workgroup
+        Buf<uint4> d_path;  // path mode: 2 buffers x 3 planes x (kHitSegments * hit_seg_cap) records, lazily allocated, grows only
+        Buf<uint32_t> d_steps;
+        Buf<uint8_t> d_rgba8;
+        // the frame sets beyond the first: output, counts and path buffers
+        Buf<vrt::Texel> extra_out[kMaxInFlight - 1];
+        Buf<uint32_t> extra_blk[kMaxInFlight - 1];
+        Buf<uint4> extra_path[kMaxInFlight - 1];
+        Buf<uint32_t> path_grp_counts[kMaxInFlight];   // VRT_PATH_WINDOW: the regions' counts, per frame set
+        Buf<vrt::Texel> path_acc[kMaxInFlight];        // the samples' accumulation planes of a launch chain, per frame set
+        Buf<uint32_t> d_tile_cost, d_tile_order, d_tile_scratch;   // vrt_order.hip, made together
+        bool tile_order_valid = false;
+        Buf<vrt::Texel> d_accum;     // VRT_RENDER_ACCUMULATE: the running sum
+        Buf<vrt::Texel> dn_scratch[kMaxInFlight];   // vrt_set_denoise: per frame set, made by its first denoised frame
+        Buf<uint32_t> dn_guide[kMaxInFlight];
+        uint32_t *dn_last_guide = nullptr;          // the guide of the last denoised frame (one of dn_guide)
+    } sz;
     uint32_t n_blocks = 0;
     uint32_t n_counts = 0;          // entries of blk_counts the last primary + shadow frame wrote
-    uint4 *d_path = nullptr;  // path mode: 2 buffers x 3 planes x (kHitSegments * hit_seg_cap) records, lazily allocated
-    unsigned long long *d_counters = nullptr;  // [kCtrCount] stats, then the hit-segment counters
-    uint32_t hit_seg_cap = 0;
-    uint32_t *d_steps = nullptr;
-    unsigned long long *d_clock = nullptr;  // clock-probe frames: {s_memtime ticks, s_memrealtime ticks}, summed until vrt_get_stats
-    uint8_t *d_rgba8 = nullptr;
-    // vrt_present's targets: one per frame set, written on the stream of the frame that is presented (vrt_present.hip)
-    uint8_t *d_screen[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t screen_cap[4] = {0, 0, 0, 0};
+    Buf<unsigned long long> d_counters;  // [kCtrCount] stats, then the hit-segment counters
+    uint32_t hit_seg_cap = 0;       // records per hit segment: what the kernels are given (d_hits holds kHitSegments of them)
+    Buf<unsigned long long> d_clock;  // clock-probe frames: {s_memtime ticks, s_memrealtime ticks}, summed until vrt_get_stats
+    // vrt_present's targets: one per frame set, written on the stream of the frame that is presented (vrt_present.hip); bytes
+    Buf<uint8_t> d_screen[4];
     hipStream_t screen_stream[4] = {nullptr, nullptr, nullptr, nullptr};   // the stream of the buffer's last blit
 
     // derived lookup tables of the grid march (vrt_accel.hip), brought up to date lazily when their inputs changed: the whole
@@ -182,19 +208,16 @@ struct vrt_ctx {
     // frame set k has rendered): a frame in flight reads its own set, so bringing the next frame's set up to date does not
     // have to wait for it — each set keeps its own list of the chunks dirtied since *it* was last brought up to date.
     struct Tables {
-        uint32_t *d_grid = nullptr;
-        size_t grid_cap = 0;          // entries allocated ([8S][8S+1][8S+1] with the zero border)
-        uint16_t *d_bricks = nullptr;
-        uint32_t brick_cap = 0;
+        Buf<uint32_t> d_grid;         // [8S][8S+1][8S+1] with the zero border
+        Buf<uint16_t> d_bricks;
+        uint32_t brick_cap() const { return (uint32_t)(d_bricks.cap() / 64u); }   // in 64-word bricks, as the kernels take it
         // the march cells (vrt_accel.hip): a chunk directory [S][S+1][S+1] and 8-KiB blocks of 512 cells (0: outside the world,
         // 1: shared by the chunks that are one air leaf, the rest: one chunk each; the tail takes chunks that stop being air)
-        uint32_t *d_cdir = nullptr;
-        size_t cdir_cap = 0;
-        uint4 *d_mblk = nullptr;
-        uint32_t mblk_cap = 0;        // blocks
-        uint32_t *d_mblk_tail = nullptr;
-        uint32_t *d_chunk_bricks = nullptr, *d_chunk_bases = nullptr, *d_chunk_caps = nullptr, *d_brick_tail = nullptr;
-        uint32_t chunk_cap = 0;
+        Buf<uint32_t> d_cdir;
+        Buf<uint4> d_mblk;
+        uint32_t mblk_cap() const { return (uint32_t)(d_mblk.cap() / 512u); }     // in 512-cell blocks, as the kernels take it
+        Buf<uint32_t> d_mblk_tail;
+        Buf<uint32_t> d_chunk_bricks, d_chunk_bases, d_chunk_caps, d_brick_tail;
         bool live = false;            // a copy of tabs[0] as of the last whole-world build, plus its own chunk updates since
         std::vector<uint32_t> dirty_chunks;     // chunk slots whose nodes or root changed since this set was last brought up to date
         std::vector<uint8_t> chunk_is_dirty;    // ... as flags, [n_roots]
@@ -211,11 +234,10 @@ struct vrt_ctx {
     bool tables_split = false;
     uint32_t quiet_frames = 0;
     bool shared_readers_in_flight = false;   // a frame on another frame set is reading tabs[0] (cleared with the frames in flight)
-    uint32_t *d_brick_total = nullptr;
-    uint32_t *d_chunk_needs = nullptr;   // whole-world build scratch: which chunks need a block of march cells
+    Buf<uint32_t> d_brick_total;
+    Buf<uint32_t> d_chunk_needs;         // whole-world build scratch: which chunks need a block of march cells
     bool march_direct = false;           // the march cells of the whole world, no chunk directory (worlds up to march_direct_max_s)
     uint32_t march_direct_max_s = 0;     // kMarchDirectMaxS, or VRT_MARCH_DIRECT_MAX_S (tests: the directory on a small world)
-    uint32_t chunk_needs_cap = 0;
     uint32_t n_bricks = 0;        // bricks inside the chunks' regions after the last whole-world build
     uint32_t accel_S = 0;         // world size the tables were built for
     bool accel_dirty = true;
@@ -233,11 +255,7 @@ struct vrt_ctx {
     bool path_window = false;
     uint32_t path_window_shape = 2;   // VRT_PATH_WINDOW_SHAPE: 0 = 32^3 voxels, 1 = 48^3, 2 = 64 x 32 x 64, 3 = 64^3, 4 = no window (the rays' state in global memory)
     int32_t path_window_lift = 8;     // VRT_PATH_WINDOW_LIFT: the window's centre above the mean origin, voxels
-    uint32_t *path_grp_counts[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};
-    size_t path_grp_regions[kMaxInFlight] = {0, 0, 0, 0};
     uint32_t path_samples = 8;     // VRT_PATH_SAMPLES_PER_CHAIN: samples a launch chain traces at once when spp > 1 (1: one, as round 1 did)
-    vrt::Texel *path_acc[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};   // ... their accumulation planes, per frame set
-    size_t path_acc_texels[kMaxInFlight] = {0, 0, 0, 0}, path_buf_records[kMaxInFlight] = {0, 0, 0, 0};
     uint32_t path_pool_batches = 0;   // VRT_PATH_POOL_K = 4 | 5: the bounce waves' pools; 0: 5 for small worlds with two frames in flight, else 4
     uint32_t path_refill = 0;      // VRT_PATH_POOL_REFILL: idle lanes that send a bounce wave back to its pool (0: the default, 16)
     uint32_t accel_builds = 0;
@@ -249,9 +267,6 @@ struct vrt_ctx {
     // of a voxel of camera travel; measured): any change of the view goes back to screen order.  With two
     // frames in flight the other frame already fills a launch's tail and the order buys nothing.
     bool tile_lpt = true;               // VRT_TILE_ORDER=0: screen order always
-    uint32_t *d_tile_cost = nullptr, *d_tile_order = nullptr, *d_tile_scratch = nullptr;
-    uint32_t tile_buf_tiles = 0;        // what the buffers are sized for
-    bool tile_order_valid = false;
     uint32_t view_gen = 0;              // counts the changes of anything a tile's trips depend on
     uint32_t frame_view_gen = ~0u;      // ... as of the last frame rendered
     uint32_t order_view_gen = ~0u;      // ... as of the frame the order was made from
@@ -324,36 +339,32 @@ struct vrt_ctx {
     uint64_t upload_gen = 0;          // bumped by every upload; a frame stream waits for ev_upload when it has not seen it
     uint64_t seen_gen[kMaxInFlight] = {0, 0, 0, 0};  // [0] own_stream, [k] extra_stream[k - 1]
 
-    float *d_ndc = nullptr;       // ndc_x[width] then ndc_y[height] (FrameParams), rebuilt when proj_size or the output size change
+    Buf<float> d_ndc;             // ndc_x[width] then ndc_y[height] (FrameParams), rebuilt when proj_size or the output size change
     uint32_t ndc_w = 0, ndc_h = 0;
     float ndc_proj[2] = {0.f, 0.f};
 
     // vrt_cast_rays / vrt_clip_moves (vrt_query.h query_batch_host): the device copy of a host batch, queries then results, in
     // bytes; a host batch waits on ev_query for its own results before it returns, so the two kinds share one buffer
-    void *d_query = nullptr;
-    size_t query_cap = 0;
+    Buf<uint8_t> d_query;
     hipEvent_t ev_query = nullptr;
 
     // vrt_generate_chunks / vrt_build_chunks (vrt_gen.hip): one batch's staging slots, node counts, offsets and inputs (made on
     // first use), and the compacted nodes of a whole call (grown as needed)
-    uint16_t *d_gen_stage = nullptr;
-    uint32_t *d_gen_counts = nullptr;
-    uint64_t *d_gen_offs = nullptr;
-    int32_t *d_gen_pos = nullptr;
-    uint16_t *d_gen_dense = nullptr;
-    uint16_t *d_gen_out = nullptr;
-    uint64_t gen_out_cap = 0;
+    Buf<uint16_t> d_gen_stage;
+    Buf<uint32_t> d_gen_counts;
+    Buf<uint64_t> d_gen_offs;
+    Buf<int32_t> d_gen_pos;
+    Buf<uint16_t> d_gen_dense;
+    Buf<uint16_t> d_gen_out;
     // vrt_edit_chunks (vrt_edit.hip): one batch's input trees and per-chunk records, the call's shapes and bins (grown as needed)
-    uint16_t *d_edit_nodes = nullptr;
-    uint64_t edit_nodes_cap = 0;
-    void *d_edit_chunks = nullptr;     // kGenBatch records
-    uint8_t *d_edit_changed = nullptr; // kGenBatch
-    void *d_edit_shapes = nullptr;
-    uint32_t edit_shapes_cap = 0;
-    uint16_t *d_edit_bins = nullptr;
-    uint64_t edit_bins_cap = 0;
+    Buf<uint16_t> d_edit_nodes;
+    Buf<uint8_t> d_edit_chunks;    // kGenBatch records (vrt_edit.hip's EditChunk), in bytes
+    Buf<uint8_t> d_edit_changed;   // kGenBatch
+    Buf<vrt_shape> d_edit_shapes;
+    Buf<uint16_t> d_edit_bins;
 
     vrt_material h_mats[256];
+    static constexpr size_t kMatsAlloc = 256 + 256 * sizeof(float) / sizeof(vrt_material);   // d_mats, in materials
     float h_emission[256];    // vrt_write_emission's table (zeros at creation) and how many of its entries are not 0: a frame
     uint32_t n_emissive = 0;  // of a context with none runs the kernels without the emission term
     uint32_t liquid_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit v <=> h_mats[v].is_liquid == 1 (kept by vrt_write_materials)
@@ -368,20 +379,16 @@ struct vrt_ctx {
     uint32_t prof_frames = 0;
 
     uint32_t last_spp = 1;
-    // VRT_RENDER_ACCUMULATE: the running sum (one texel per slot, never divided; allocated by the first accumulating frame,
-    // dropped by alloc_output), the samples in it and their seed, whether the next accumulating frame starts again at 0,
+    // VRT_RENDER_ACCUMULATE: the running sum is sz.d_accum (one texel per slot, never divided; allocated by the first accumulating
+    // frame, dropped by alloc_output); the samples in it and their seed, whether the next accumulating frame starts again at 0,
     // and the event behind the last step that wrote the sum (the next frame's first step that touches it waits for it)
-    vrt::Texel *d_accum = nullptr;
     uint32_t accum_n = 0, accum_seed = 0;
     bool accum_restart = true;
     hipEvent_t ev_accum = nullptr;
     bool accum_ev_recorded = false;
-    // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); per frame set, made by its first denoised frame and dropped
-    // by a resize, the scratch frame the passes go back and forth over and the guide words; the guide of the last denoised frame
+    // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); the scratch frames the passes go back and forth over and the
+    // guide words are sz.dn_scratch / sz.dn_guide
     vrt_denoise_opts denoise{};
-    vrt::Texel *dn_scratch[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t *dn_guide[kMaxInFlight] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t *dn_last_guide = nullptr;
     bool rendered = false;
     bool last_stats = false;
     uint32_t last_mode = 0;
@@ -390,11 +397,6 @@ struct vrt_ctx {
 
     std::string err;
 };
-
-static constexpr size_t kSegBytes = (size_t)vrt::kHitSegments * vrt::kSegStride * sizeof(uint32_t);
-// three sets of segment cursors: launch g of a path frame appends to set g % 3, reads set (g - 1) % 3 and clears set
-// (g + 1) % 3 for its successor, so no memset sits between two launches
-static constexpr size_t kCounterBytes = vrt::kCtrCount * sizeof(unsigned long long) + 3 * kSegBytes;   // + the path trace's 3 cursor sets
 
 enum EvKind : uint8_t { kEvNone = 0, kEvOneKernel = 1, kEvTwoKernels = 2, kEvRecorded = 3 };
 
@@ -465,7 +467,6 @@ VRT_HIDDEN int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStrea
                                        bool edit_in_front, TileOrderPlan &plan);
 VRT_HIDDEN int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st, const TileOrderPlan &plan);
 // vrt_denoise.hip: around a path frame's launches in vrt_render (vrt_set_denoise)
-VRT_HIDDEN void denoise_free(vrt_ctx *c);
 VRT_HIDDEN int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::Texel **trace_into);
 VRT_HIDDEN int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
                                    hipEvent_t closing);
@@ -479,7 +480,6 @@ VRT_HIDDEN int wait_for_pool_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot);
 VRT_HIDDEN int frame_waits_for_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot);
 VRT_HIDDEN int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes, bool pool = false);
 VRT_HIDDEN void mark_all_dirty(vrt_ctx *c);
-VRT_HIDDEN int free_tables(vrt_ctx *c, vrt_ctx::Tables &T);
 VRT_HIDDEN int ensure_accel_world(vrt_ctx *c);
 VRT_HIDDEN int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st);
 VRT_HIDDEN size_t chunk_dir_entries(uint32_t S);

@@ -160,27 +160,21 @@ void launch_denoise_pass(const DenoisePass &D, hipStream_t st) {
 
 }  // namespace vrt
 
-void denoise_free(vrt_ctx *c) {
-    for (auto &p : c->dn_scratch) { (void)hipFree(p); p = nullptr; }
-    for (auto &p : c->dn_guide) { (void)hipFree(p); p = nullptr; }
-    c->dn_last_guide = nullptr;
-}
-
 // Before a path frame is enqueued: the frame set's scratch frame and guide words (made by its first denoised frame), and
 // where the frame is traced — into the scratch frame when the number of passes is odd, so that the last pass lands in frame_out.
 int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::Texel **trace_into) {
     *trace_into = frame_out;
     if (!c->denoise.passes || !c->tiles_total) return VRT_OK;
     const size_t n = (size_t)c->width * c->height;
-    if (!c->dn_scratch[slot]) {
-        HIP_TRY(c, hipMalloc(&c->dn_scratch[slot], n * sizeof(vrt::Texel)));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->dn_scratch[slot], n * sizeof(vrt::Texel)));
+    if (!c->sz.dn_scratch[slot]) {
+        HIP_TRY(c, c->sz.dn_scratch[slot].once(n));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.dn_scratch[slot], n * sizeof(vrt::Texel)));
     }
-    if (!c->dn_guide[slot]) {
-        HIP_TRY(c, hipMalloc(&c->dn_guide[slot], n * sizeof(uint32_t)));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->dn_guide[slot], n * sizeof(uint32_t)));   // (beyond the traced area: 0)
+    if (!c->sz.dn_guide[slot]) {
+        HIP_TRY(c, c->sz.dn_guide[slot].once(n));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.dn_guide[slot], n * sizeof(uint32_t)));   // (beyond the traced area: 0)
     }
-    if (c->denoise.passes & 1u) *trace_into = c->dn_scratch[slot];
+    if (c->denoise.passes & 1u) *trace_into = c->sz.dn_scratch[slot];
     return VRT_OK;
 }
 
@@ -190,14 +184,14 @@ int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uin
                         hipEvent_t closing) {
     const uint32_t passes = c->denoise.passes;
     if (!passes || !c->tiles_total) return VRT_OK;
-    vrt::launch_denoise_guide(P, literal, c->dn_guide[slot], st);
+    vrt::launch_denoise_guide(P, literal, c->sz.dn_guide[slot], st);
     HIP_TRY(c, hipGetLastError());
-    vrt::Texel *a = (passes & 1u) ? c->dn_scratch[slot] : frame_out, *b = (passes & 1u) ? frame_out : c->dn_scratch[slot];
+    vrt::Texel *a = (passes & 1u) ? c->sz.dn_scratch[slot] : frame_out, *b = (passes & 1u) ? frame_out : c->sz.dn_scratch[slot];
     for (uint32_t i = 0; i < passes; i++) {
         vrt::DenoisePass D;
         D.in = a;
         D.out = b;
-        D.guide = c->dn_guide[slot];
+        D.guide = c->sz.dn_guide[slot];
         D.stride = c->width;
         D.wt = (int)(c->width & ~7u);
         D.ht = (int)(c->height & ~7u);
@@ -208,7 +202,7 @@ int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uin
         HIP_TRY(c, hipGetLastError());
         std::swap(a, b);
     }
-    c->dn_last_guide = c->dn_guide[slot];
+    c->sz.dn_last_guide = c->sz.dn_guide[slot];
     if (closing) HIP_TRY(c, hipEventRecord(closing, st));
     return VRT_OK;
 }
@@ -238,10 +232,10 @@ int vrt_set_denoise(vrt_ctx *c, const vrt_denoise_opts *opts) {
 int vrt_read_guide(vrt_ctx *c, uint32_t *guide) {
     GRP_REFUSE(c, "vrt_read_guide");
     if (!c || !guide) return fail(c, VRT_ERR_INVALID_ARG, "vrt_read_guide: null argument");
-    if (!c->dn_last_guide) return fail(c, VRT_ERR_STATE, "vrt_read_guide: no frame has been denoised yet (vrt_set_denoise, then a VRT_MODE_PATH frame)");
+    if (!c->sz.dn_last_guide) return fail(c, VRT_ERR_STATE, "vrt_read_guide: no frame has been denoised yet (vrt_set_denoise, then a VRT_MODE_PATH frame)");
     HIP_TRY(c, hipSetDevice(c->device));
     QUIESCE(c);
-    HIP_TRY(c, hipMemcpyAsync(guide, c->dn_last_guide, (size_t)c->width * c->height * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(guide, c->sz.dn_last_guide, (size_t)c->width * c->height * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return VRT_OK;
 }

@@ -165,14 +165,8 @@ int edit_fill(vrt_ctx *c, void *arg, uint32_t b0, uint32_t nb) {
     EditCall &E = *static_cast<EditCall *>(arg);
     hipStream_t st = c->stream;
     const uint64_t first = E.offs_in[b0], words = E.offs_in[b0 + nb] - first;
-    if (words > c->edit_nodes_cap) {   // (the batch before has been waited for: nothing reads the old buffer)
-        (void)hipFree(c->d_edit_nodes);
-        c->d_edit_nodes = nullptr;
-        c->edit_nodes_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(words, 1ull << 20);
-        HIP_TRY(c, hipMalloc(&c->d_edit_nodes, (size_t)cap * sizeof(uint16_t)));
-        c->edit_nodes_cap = cap;
-    }
+    // (the batch before has been waited for: nothing reads the old buffer)
+    if (words > c->d_edit_nodes.cap()) HIP_TRY(c, c->d_edit_nodes.grow(std::max<uint64_t>(words, 1ull << 20)));
     E.recs.resize(nb);
     for (uint32_t i = 0; i < nb; i++) {
         const uint32_t g = b0 + i;
@@ -189,9 +183,9 @@ int edit_fill(vrt_ctx *c, void *arg, uint32_t b0, uint32_t nb) {
     HIP_TRY(c, hipMemcpyAsync(c->d_edit_nodes, E.nodes_in + first, (size_t)words * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->d_edit_chunks, E.recs.data(), (size_t)nb * sizeof(EditChunk), hipMemcpyHostToDevice, st));
     EditParams P;
-    P.chunks = static_cast<const EditChunk *>(c->d_edit_chunks);
+    P.chunks = reinterpret_cast<const EditChunk *>(c->d_edit_chunks.get());
     P.nodes = c->d_edit_nodes;
-    P.shapes = static_cast<const vrt_shape *>(c->d_edit_shapes);
+    P.shapes = c->d_edit_shapes;
     P.bins = c->d_edit_bins;
     P.dense = c->d_gen_dense;
     P.changed = c->d_edit_changed;
@@ -226,26 +220,11 @@ int vrt_edit_chunks(vrt_ctx *c, const int32_t *chunk_pos, uint32_t n, const uint
     }
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (!c->d_edit_chunks) {
-        HIP_TRY(c, hipMalloc(&c->d_edit_chunks, (size_t)kEditBatch * sizeof(EditChunk)));
-        HIP_TRY(c, hipMalloc(&c->d_edit_changed, (size_t)kEditBatch));
-    }
-    if (m > c->edit_shapes_cap) {   // (every earlier call has waited for its work)
-        (void)hipFree(c->d_edit_shapes);
-        c->d_edit_shapes = nullptr;
-        c->edit_shapes_cap = 0;
-        const uint32_t cap = std::max(m, 1024u);
-        HIP_TRY(c, hipMalloc(&c->d_edit_shapes, (size_t)cap * sizeof(vrt_shape)));
-        c->edit_shapes_cap = cap;
-    }
-    if (bins.list.size() > c->edit_bins_cap) {
-        (void)hipFree(c->d_edit_bins);
-        c->d_edit_bins = nullptr;
-        c->edit_bins_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(bins.list.size(), 4096);
-        HIP_TRY(c, hipMalloc(&c->d_edit_bins, (size_t)cap * sizeof(uint16_t)));
-        c->edit_bins_cap = cap;
-    }
+    HIP_TRY(c, c->d_edit_chunks.once((size_t)kEditBatch * sizeof(EditChunk)));
+    HIP_TRY(c, c->d_edit_changed.once(kEditBatch));
+    // (every earlier call has waited for its work)
+    if (m > c->d_edit_shapes.cap()) HIP_TRY(c, c->d_edit_shapes.grow(std::max(m, 1024u)));
+    if (bins.list.size() > c->d_edit_bins.cap()) HIP_TRY(c, c->d_edit_bins.grow(std::max<uint64_t>(bins.list.size(), 4096)));
     if (m) HIP_TRY(c, hipMemcpyAsync(c->d_edit_shapes, shapes, (size_t)m * sizeof(vrt_shape), hipMemcpyHostToDevice, st));
     if (!bins.list.empty())
         HIP_TRY(c, hipMemcpyAsync(c->d_edit_bins, bins.list.data(), bins.list.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));

@@ -59,46 +59,29 @@ static void layout_tiles(vrt_ctx *c) {
 }
 
 static int alloc_output(vrt_ctx *c) {
-    (void)hipFree(c->own_out); (void)hipFree(c->d_hits); (void)hipFree(c->d_steps); (void)hipFree(c->d_rgba8); (void)hipFree(c->d_path);
-    (void)hipFree(c->d_blk_counts);
-    c->own_out = nullptr; c->d_hits = nullptr; c->d_steps = nullptr; c->d_rgba8 = nullptr; c->d_path = nullptr; c->d_blk_counts = nullptr;
-    for (auto &p : c->extra_out) { (void)hipFree(p); p = nullptr; }
-    for (auto &p : c->extra_blk) { (void)hipFree(p); p = nullptr; }
-    for (auto &p : c->extra_path) { (void)hipFree(p); p = nullptr; }
-    for (auto &p : c->path_acc) { (void)hipFree(p); p = nullptr; }
-    for (auto &p : c->path_grp_counts) { (void)hipFree(p); p = nullptr; }
-    for (auto &n : c->path_grp_regions) n = 0;
-    (void)hipFree(c->d_tile_cost); c->d_tile_cost = nullptr;
-    (void)hipFree(c->d_tile_order); c->d_tile_order = nullptr;
-    (void)hipFree(c->d_tile_scratch); c->d_tile_scratch = nullptr;
-    c->tile_buf_tiles = 0;
-    c->tile_order_valid = false;
-    for (auto &n : c->path_acc_texels) n = 0;
-    for (auto &n : c->path_buf_records) n = 0;
-    (void)hipFree(c->d_accum); c->d_accum = nullptr;
+    c->sz = vrt_ctx::Sized{};   // everything of the old size goes (the callers have waited for the frames in flight)
     c->accum_restart = true;
-    denoise_free(c);
     layout_tiles(c);
     const size_t n = c->slots ? c->slots : 1;
-    HIP_TRY(c, hipMalloc(&c->own_out, n * sizeof(vrt::Texel)));
+    HIP_TRY(c, c->sz.own_out.once(n));
     // hit buffer: kHitSegments segments, each able to hold every record its workgroups can produce
     const uint32_t nblocks = (c->tiles_local + 3u) / 4u;
     c->hit_seg_cap = ((nblocks + vrt::kHitSegments - 1u) / vrt::kHitSegments) * 256u;
     if (c->hit_seg_cap == 0) c->hit_seg_cap = 256u;
-    HIP_TRY(c, hipMalloc(&c->d_hits, (size_t)vrt::kHitSegments * c->hit_seg_cap * sizeof(uint4)));  // >= nblocks * 256
+    HIP_TRY(c, c->sz.d_hits.once((size_t)vrt::kHitSegments * c->hit_seg_cap));  // >= nblocks * 256
     c->n_blocks = nblocks;
     // launched-ray counts: one per primary workgroup (two-launch variants) or one per tile (the one-launch kernel)
     const size_t ncnt = c->tiles_local ? c->tiles_local : 1;
-    HIP_TRY(c, hipMalloc(&c->d_blk_counts, ncnt * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_blk_counts, 0, ncnt * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->own_out, 0, n * sizeof(vrt::Texel), c->stream));
+    HIP_TRY(c, c->sz.d_blk_counts.once(ncnt));
+    HIP_TRY(c, hipMemsetAsync(c->sz.d_blk_counts, 0, ncnt * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->sz.own_out, 0, n * sizeof(vrt::Texel), c->stream));
     // (c->stream may be the caller's: a VRT_RENDER_OWN_STREAMS frame on own_stream is not ordered behind these memsets, and
     // result sizes that are not whole tiles rely on the zeros)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // the extra (stream, output, counts) sets of frames in flight are created when first used (vrt_render)
-    c->d_out = c->own_out;  // a resize drops any caller-bound output (its size no longer matches)
-    c->last_out = c->own_out;
-    c->last_blk = c->d_blk_counts;
+    c->d_out = c->sz.own_out;  // a resize drops any caller-bound output (its size no longer matches)
+    c->last_out = c->sz.own_out;
+    c->last_blk = c->sz.d_blk_counts;
     c->rendered = false;
     c->last_fused = false;
     c->last_has_texels = true;
@@ -121,11 +104,10 @@ int ensure_ndc(vrt_ctx *c) {
     if (c->d_ndc && c->ndc_w == c->width && c->ndc_h == c->height &&
         memcmp(c->ndc_proj, c->cam.proj_size, sizeof c->ndc_proj) == 0)
         return VRT_OK;
-    if (!c->d_ndc || c->ndc_w + c->ndc_h < c->width + c->height) {
+    if (!c->d_ndc || c->ndc_w + c->ndc_h < c->width + c->height) {   // (against the size last filled, not the capacity)
         QUIESCE(c);
-        (void)hipFree(c->d_ndc);
-        c->d_ndc = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_ndc, (size_t)(c->width + c->height) * sizeof(float)));
+        c->d_ndc.release();
+        HIP_TRY(c, c->d_ndc.once((size_t)c->width + c->height));
     }
     std::vector<float> t((size_t)c->width + c->height);
     volatile float px = c->cam.proj_size[0], py = c->cam.proj_size[1];
@@ -265,7 +247,7 @@ struct FrameSet {
     hipStream_t st;
     vrt::Texel *out;
     uint32_t *blk;
-    uint4 **path_buf;
+    vrt_ctx::Buf<uint4> *path_buf;
     unsigned long long *counters;
 };
 
@@ -279,9 +261,9 @@ static int pick_frame_set(vrt_ctx *c, const vrt_render_opts &o, uint32_t variant
     // streams (nothing on the caller's stream consumes it before a synchronise; frames in flight are bound to different
     // buffers) — the gather root's own tiles in bench.py
     const bool own_streams = (o.flags & VRT_RENDER_OWN_STREAMS) != 0u;
-    const bool pipelined = c->in_flight > 1u && chain && !kstats && (own_streams || (c->stream == c->own_stream && c->d_out == c->own_out));
-    const bool bound = c->d_out != c->own_out;
-    f = FrameSet{0u, c->stream, c->d_out, c->d_blk_counts, &c->d_path, c->d_counters};
+    const bool pipelined = c->in_flight > 1u && chain && !kstats && (own_streams || (c->stream == c->own_stream && c->d_out == c->sz.own_out));
+    const bool bound = c->d_out != c->sz.own_out;
+    f = FrameSet{0u, c->stream, c->d_out, c->sz.d_blk_counts, &c->sz.d_path, c->d_counters};
     if (!pipelined) {
         QUIESCE(c);
         return VRT_OK;
@@ -290,20 +272,20 @@ static int pick_frame_set(vrt_ctx *c, const vrt_render_opts &o, uint32_t variant
         const uint32_t k = c->flip - 1u;
         f.slot = k + 1u;
         if (o.mode == VRT_MODE_PATH) {
-            if (!c->extra_counters[k]) HIP_TRY(c, hipMalloc(&c->extra_counters[k], kCounterBytes));
+            HIP_TRY(c, c->extra_counters[k].once(kCounterWords));
             f.counters = c->extra_counters[k];
-            f.path_buf = &c->extra_path[k];
+            f.path_buf = &c->sz.extra_path[k];
         }
         if (!c->extra_stream[k]) HIP_TRY(c, hipStreamCreateWithFlags(&c->extra_stream[k], hipStreamNonBlocking));
-        if (!bound && !c->extra_out[k]) {
+        if (!bound && !c->sz.extra_out[k]) {
             const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
-            HIP_TRY(c, hipMalloc(&c->extra_out[k], bytes));
-            if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->extra_out[k], bytes));   // texels no workgroup covers stay zero (main.rs:452)
+            HIP_TRY(c, c->sz.extra_out[k].once(bytes / sizeof(vrt::Texel)));
+            if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.extra_out[k], bytes));   // texels no workgroup covers stay zero (main.rs:452)
         }
-        if (!c->extra_blk[k]) HIP_TRY(c, hipMalloc(&c->extra_blk[k], (size_t)(c->tiles_local ? c->tiles_local : 1) * sizeof(uint32_t)));
+        HIP_TRY(c, c->sz.extra_blk[k].once(c->tiles_local ? c->tiles_local : 1));
         f.st = c->extra_stream[k];
-        f.blk = c->extra_blk[k];
-        if (!bound) f.out = c->extra_out[k];  // a bound output is the caller's buffer for this very frame
+        f.blk = c->sz.extra_blk[k];
+        if (!bound) f.out = c->sz.extra_out[k];  // a bound output is the caller's buffer for this very frame
         c->alt_pending = true;
         const int rc = frame_waits_for_uploads(c, f.st, k + 1u);
         if (rc) return rc;
@@ -372,24 +354,17 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     const bool own_sum = emit && !planes && !accum && spp > 1u && bounces > 0;
     const uint32_t seg_cap = c->hit_seg_cap * samples;
     const size_t cap = (size_t)vrt::kHitSegments * seg_cap;
-    if (c->path_buf_records[f.slot] < cap) {   // (grows only; hipFree waits for whatever still uses the old one)
-        (void)hipFree(*f.path_buf);
-        *f.path_buf = nullptr; c->path_buf_records[f.slot] = 0;
-        // two sets of three record planes (+ two of per-ray state for experiments/vrt_path_window.hip's launch)
-        HIP_TRY(c, hipMalloc(f.path_buf, (2 * 3 + (vrt::g_exp.path_bounce_window ? 2 : 0)) * cap * sizeof(uint4)));
-        c->path_buf_records[f.slot] = cap;
+    // two sets of three record planes (+ two of per-ray state for experiments/vrt_path_window.hip's launch); grows only, and
+    // hipFree waits for whatever still uses the old one
+    HIP_TRY(c, f.path_buf->grow((2 * 3 + (vrt::g_exp.path_bounce_window ? 2 : 0)) * cap));
+    if ((planes || own_sum) && c->sz.path_acc[f.slot].cap() < (size_t)samples * c->slots) {
+        HIP_TRY(c, c->sz.path_acc[f.slot].grow((size_t)samples * c->slots));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
     }
-    if ((planes || own_sum) && c->path_acc_texels[f.slot] < (size_t)samples * c->slots) {
-        (void)hipFree(c->path_acc[f.slot]);
-        c->path_acc[f.slot] = nullptr; c->path_acc_texels[f.slot] = 0;
-        HIP_TRY(c, hipMalloc(&c->path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
-        c->path_acc_texels[f.slot] = (size_t)samples * c->slots;
-    }
-    if (accum && !c->d_accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
+    if (accum && !c->sz.d_accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
         const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
-        HIP_TRY(c, hipMalloc(&c->d_accum, bytes));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->d_accum, bytes));
+        HIP_TRY(c, c->sz.d_accum.once(bytes / sizeof(vrt::Texel)));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.d_accum, bytes));
         if (!c->ev_accum) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
     }
     // Only the steps that read and write the sum are ordered behind the previous accumulating frame's (it may be in flight on
@@ -403,10 +378,10 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     const uint32_t accum_count = accum_from + spp;   // the samples in this frame's mean (<= 2^24: vrt_render)
     vrt::Texel *const frame_out = P.out;
     P.hit_seg_cap = seg_cap;
-    P.acc = planes ? c->path_acc[f.slot] : nullptr;
+    P.acc = planes ? c->sz.path_acc[f.slot] : nullptr;
     P.acc_slots = c->slots;
     P.chain = 1u;
-    if (planes) P.out = c->path_acc[f.slot];   // what the bounce launches accumulate into, through slots that carry the plane
+    if (planes) P.out = c->sz.path_acc[f.slot];   // what the bounce launches accumulate into, through slots that carry the plane
     constexpr uint32_t kSegWords = vrt::kHitSegments * vrt::kSegStride;
     uint32_t *seg[3] = {P.seg_counts, P.seg_counts + kSegWords, P.seg_counts + 2 * kSegWords};
     uint4 *buf[2] = {*f.path_buf, *f.path_buf + 3 * cap};
@@ -426,14 +401,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     const bool window = cells && c->path_window && vrt::g_exp.path_bounce_window && !emit;   // (the window launch: the experiments build; no emission)
     const uint32_t n_regions = (c->tiles_local + 3u) / 4u;
     if (window) {
-        if (c->path_grp_regions[f.slot] < n_regions) {
-            (void)hipFree(c->path_grp_counts[f.slot]);
-            c->path_grp_counts[f.slot] = nullptr; c->path_grp_regions[f.slot] = 0;
-            HIP_TRY(c, hipMalloc(&c->path_grp_counts[f.slot], (size_t)n_regions * sizeof(uint32_t)));
-            c->path_grp_regions[f.slot] = n_regions;
-        }
+        HIP_TRY(c, c->sz.path_grp_counts[f.slot].grow(n_regions));
     }
-    P.grp_counts = window ? c->path_grp_counts[f.slot] : nullptr;
+    P.grp_counts = window ? c->sz.path_grp_counts[f.slot] : nullptr;
     P.grp_cap = 256u * samples;   // (n_regions * grp_cap <= cap: a segment holds what its workgroups can produce)
     P.blk_w = P.blk_h = 4u;
     if (window) {   // a bounce workgroup's regions are one block of tiles: 4 x 4 (4 regions), 8 x 4 (8), 8 x 8 (16)
@@ -480,15 +450,15 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             if (rc) return rc;
         }
         if (planes) {
-            if (accum) vrt::launch_path_chain_finish(c->d_accum, frame_out, c->path_acc[f.slot], c->slots, P.chain, accum_from + smp == 0u,
+            if (accum) vrt::launch_path_chain_finish(c->sz.d_accum, frame_out, c->sz.path_acc[f.slot], c->slots, P.chain, accum_from + smp == 0u,
                                                      smp + P.chain >= spp, accum_count, f.st);
-            else vrt::launch_path_chain_finish(frame_out, frame_out, c->path_acc[f.slot], c->slots, P.chain, smp == 0u, smp + P.chain >= spp, spp, f.st);
+            else vrt::launch_path_chain_finish(frame_out, frame_out, c->sz.path_acc[f.slot], c->slots, P.chain, smp == 0u, smp + P.chain >= spp, spp, f.st);
             HIP_TRY(c, hipGetLastError());
         } else if (accum) {   // one sample per chain: the sample joins the sum (bit-exact only one sample at a time)
-            vrt::launch_path_accum_resolve(frame_out, c->d_accum, c->slots, accum_from + smp == 0u, smp + 1u >= spp, accum_count, f.st);
+            vrt::launch_path_accum_resolve(frame_out, c->sz.d_accum, c->slots, accum_from + smp == 0u, smp + 1u >= spp, accum_count, f.st);
             HIP_TRY(c, hipGetLastError());
         } else if (own_sum) {   // (emission) the same into this frame's own sum
-            vrt::launch_path_accum_resolve(frame_out, c->path_acc[f.slot], c->slots, smp == 0u, smp + 1u >= spp, spp, f.st);
+            vrt::launch_path_accum_resolve(frame_out, c->sz.path_acc[f.slot], c->slots, smp == 0u, smp + 1u >= spp, spp, f.st);
             HIP_TRY(c, hipGetLastError());
         }
     }
@@ -612,7 +582,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         HIP_TRY(c, hipSetDevice(dev));
         HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         c->stream = c->own_stream;
-        HIP_TRY(c, hipMalloc(&c->d_nodes, (size_t)c->max_nodes * sizeof(uint16_t)));
+        HIP_TRY(c, c->d_nodes.once(c->max_nodes));
         // fresh buffer = zeros = every node an air leaf (client/src/world.rs:273-274)
         HIP_TRY(c, hipMemsetAsync(c->d_nodes, 0, (size_t)c->max_nodes * sizeof(uint16_t), c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // (uploads run on their own stream)
@@ -622,9 +592,10 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         HIP_TRY(c, hipHostMalloc((void **)&c->h_ring, vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs, hipHostMallocMapped));
         HIP_TRY(c, hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0));
         static_assert(sizeof c->h_mats == vrt::kMaterials * sizeof(vrt_material), "the emission table follows the 256 materials");
-        HIP_TRY(c, hipMalloc(&c->d_mats, sizeof c->h_mats + sizeof c->h_emission));   // + the emission table (vrt::emission_table)
+        static_assert(vrt_ctx::kMatsAlloc * sizeof(vrt_material) == sizeof c->h_mats + sizeof c->h_emission, "whole materials");
+        HIP_TRY(c, c->d_mats.once(vrt_ctx::kMatsAlloc));   // + the emission table (vrt::emission_table)
         HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, sizeof c->h_mats + sizeof c->h_emission, c->stream));
-        HIP_TRY(c, hipMalloc(&c->d_counters, kCounterBytes));
+        HIP_TRY(c, c->d_counters.once(kCounterWords));
         HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, kCounterBytes, c->stream));
         int r = alloc_roots(c, cfg->world_size_chunks);
         if (r) return r;
@@ -652,30 +623,10 @@ void vrt_destroy(vrt_ctx *c) {
     if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
     for (hipStream_t st : c->extra_stream)
         if (st) (void)hipStreamSynchronize(st);
-    for (auto p : c->extra_out) (void)hipFree(p);
-    for (auto p : c->extra_blk) (void)hipFree(p);
-    for (auto p : c->extra_path) (void)hipFree(p);
-    for (auto p : c->extra_counters) (void)hipFree(p);
-    for (auto p : c->path_acc) (void)hipFree(p);
-    for (auto p : c->path_grp_counts) (void)hipFree(p);
-    (void)hipFree(c->d_accum);
-    denoise_free(c);
     if (c->ev_accum) (void)hipEventDestroy(c->ev_accum);
-    (void)hipFree(c->d_tile_cost); (void)hipFree(c->d_tile_order); (void)hipFree(c->d_tile_scratch);
-    (void)hipFree(c->d_nodes); (void)hipFree(c->d_roots); (void)hipFree(c->d_mats); (void)hipFree(c->own_out);
-    (void)hipFree(c->d_hits); (void)hipFree(c->d_counters); (void)hipFree(c->d_steps); (void)hipFree(c->d_rgba8); (void)hipFree(c->d_path);
-    (void)hipFree(c->d_blk_counts); (void)hipFree(c->d_clock);
-    (void)hipFree(c->d_query);
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
-    (void)hipFree(c->d_gen_stage); (void)hipFree(c->d_gen_counts); (void)hipFree(c->d_gen_offs); (void)hipFree(c->d_gen_pos);
-    (void)hipFree(c->d_gen_dense); (void)hipFree(c->d_gen_out);
-    (void)hipFree(c->d_edit_nodes); (void)hipFree(c->d_edit_chunks); (void)hipFree(c->d_edit_changed); (void)hipFree(c->d_edit_shapes);
-    (void)hipFree(c->d_edit_bins);
-    for (auto &T : c->tabs) {
-        (void)free_tables(c, T);
+    for (auto &T : c->tabs)
         if (T.ev_updated) (void)hipEventDestroy(T.ev_updated);
-    }
-    (void)hipFree(c->d_brick_total); (void)hipFree(c->d_chunk_needs);
     if (c->up_stream) { (void)hipStreamSynchronize(c->up_stream); (void)hipStreamDestroy(c->up_stream); }
     if (c->ev_pool_upload) (void)hipEventDestroy(c->ev_pool_upload);
     if (c->ev_walkers) (void)hipEventDestroy(c->ev_walkers);
@@ -684,14 +635,14 @@ void vrt_destroy(vrt_ctx *c) {
         for (auto ev : evs)
             if (ev) (void)hipEventDestroy(ev);
     if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
-    if (c->ev_upload) (void)hipEventDestroy(c->ev_upload); (void)hipFree(c->d_ndc); for (uint8_t *p : c->d_screen) (void)hipFree(p);
+    if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
     for (auto &t : c->ev_pool)
         for (auto &ev : t)
             if (ev) (void)hipEventDestroy(ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     for (hipStream_t st : c->extra_stream)
         if (st) (void)hipStreamDestroy(st);
-    delete c;
+    delete c;   // the device buffers go with it: behind the waits above, the context's device current
 }
 
 const char *vrt_last_error(const vrt_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
@@ -771,12 +722,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (c->compact && (o.mode == VRT_MODE_PATH || (o.variant != 0u && o.variant != 2u) || c->settings.show_step_count == 1u))
         return fail(c, VRT_ERR_STATE, "vrt_render: a VRT_FLAG_COMPACT context renders primary(+shadow) frames with the default march "
                     "only (no path trace, step-count view, literal or two-launch variants)");
-    if (o.stats == 1u && !c->d_steps) {
-        HIP_TRY(c, hipMalloc(&c->d_steps, (size_t)(c->slots ? c->slots : 1) * sizeof(uint32_t)));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->d_steps, (size_t)(c->slots ? c->slots : 1) * sizeof(uint32_t)));
+    if (o.stats == 1u && !c->sz.d_steps) {
+        HIP_TRY(c, c->sz.d_steps.once(c->slots ? c->slots : 1));
+        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.d_steps, (size_t)(c->slots ? c->slots : 1) * sizeof(uint32_t)));
     }
     if (o.stats == 2u && !c->d_clock) {
-        HIP_TRY(c, hipMalloc(&c->d_clock, 2 * sizeof(unsigned long long)));
+        HIP_TRY(c, c->d_clock.once(2));
         HIP_TRY(c, hipMemsetAsync(c->d_clock, 0, 2 * sizeof(unsigned long long), c->stream));
         const int rc2 = publish_upload(c);
         if (rc2) return rc2;
@@ -859,25 +810,25 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         P.grid_dim = c->accel_S * 8u;
         const size_t G = (size_t)c->accel_S * 8u;
         P.grid_bytes = (uint32_t)(G * (G + 1u) * (G + 1u) * sizeof(uint32_t));  // [8S][8S+1][8S+1]: the zero border
-        P.brick_bytes = (uint32_t)((size_t)T.brick_cap * 64u * sizeof(uint16_t));
+        P.brick_bytes = (uint32_t)((size_t)T.brick_cap() * 64u * sizeof(uint16_t));
         if (T.d_mblk) {
             P.cdir = T.d_cdir;
             P.cdir_bytes = (uint32_t)(chunk_dir_entries(c->accel_S) * sizeof(uint32_t));
             P.mblk = T.d_mblk;
             // (a direct world: exactly its lines — a position beyond the last slab must be out of range, it reads as zeros)
-            P.mblk_bytes = (uint32_t)(c->march_direct ? direct_cell_entries(c->accel_S) * sizeof(uint4) : (size_t)T.mblk_cap * 512u * sizeof(uint4));
+            P.mblk_bytes = (uint32_t)(c->march_direct ? direct_cell_entries(c->accel_S) * sizeof(uint4) : (size_t)T.mblk_cap() * 512u * sizeof(uint4));
             P.march_direct = c->march_direct ? 1u : 0u;
         }
     }
     // a march that walks the octree reads the node pool and chunk_roots: uploads then wait for the frames in flight
     if (!P.grid || variant == 1u || variant == 2u) c->walkers_in_flight = true;
     P.out = f.out;
-    P.hits = c->d_hits;
+    P.hits = c->sz.d_hits;
     P.blk_counts = f.blk;
     P.counters = f.counters;
     P.seg_counts = reinterpret_cast<uint32_t *>(f.counters + vrt::kCtrCount);
     P.hit_seg_cap = c->hit_seg_cap;
-    P.steps = o.stats == 1u ? c->d_steps : nullptr;
+    P.steps = o.stats == 1u ? c->sz.d_steps : nullptr;
     P.clock = o.stats == 2u ? c->d_clock : nullptr;
     fill_uniforms(c, P);
     // vrt_set_presentation: a frame whose kernel finishes its pixels through store_pixel (every primary-only frame; primary + shadow
@@ -887,7 +838,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (fuse_present) {
         rc = screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height);
         if (rc) return rc;
-        P.screen = reinterpret_cast<uint32_t *>(c->d_screen[f.slot]);
+        P.screen = reinterpret_cast<uint32_t *>(c->d_screen[f.slot].get());
         P.screen_only = (c->pres_flags & VRT_PRESENT_SKIP_TEXELS) ? 1u : 0u;
         memcpy(P.present_box, c->pres_box, sizeof P.present_box);
         P.crosshair = c->pres_ch;
@@ -1001,10 +952,10 @@ int vrt_read_output(vrt_ctx *c, float *rgb, uint32_t *ids, uint8_t *rgba8) {
     const size_t npix = (size_t)c->width * c->height;
     if (rgba8) {
         if (c->tile_major) return fail(c, VRT_ERR_STATE, "vrt_read_output: rgba8 readback needs the row-major (unsharded) layout");
-        if (!c->d_rgba8) HIP_TRY(c, hipMalloc(&c->d_rgba8, npix * 4));
-        vrt::launch_quantize(c->last_out, c->d_rgba8, c->width, c->height, c->stream);
+        HIP_TRY(c, c->sz.d_rgba8.once(npix * 4));
+        vrt::launch_quantize(c->last_out, c->sz.d_rgba8, c->width, c->height, c->stream);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(rgba8, c->d_rgba8, npix * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(rgba8, c->sz.d_rgba8, npix * 4, hipMemcpyDeviceToHost, c->stream));
     }
     std::vector<vrt::Texel> t;
     if (rgb || ids) {
@@ -1035,11 +986,11 @@ int vrt_read_output(vrt_ctx *c, float *rgb, uint32_t *ids, uint8_t *rgba8) {
 int vrt_read_steps(vrt_ctx *c, uint32_t *steps) {
     GRP_REFUSE(c, "vrt_read_steps");
     if (!c || !steps) return fail(c, VRT_ERR_INVALID_ARG, "vrt_read_steps: null argument");
-    if (!c->rendered || !c->last_stats || !c->d_steps)
+    if (!c->rendered || !c->last_stats || !c->sz.d_steps)
         return fail(c, VRT_ERR_STATE, "vrt_read_steps: the last frame was not rendered with opts.stats = 1");
     if (c->tile_major) return fail(c, VRT_ERR_STATE, "vrt_read_steps: needs the row-major (unsharded) layout");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(steps, c->d_steps, (size_t)c->width * c->height * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(steps, c->sz.d_steps, (size_t)c->width * c->height * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return VRT_OK;
 }
@@ -1146,7 +1097,7 @@ int vrt_bind_output(vrt_ctx *c, void *texels) {
     if (texels && ((uintptr_t)texels % 16u)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_bind_output: texels must be 16-byte aligned");
     // stream-ordered: launches capture the pointer, so frames already enqueued keep writing where they were
     // told to and the next vrt_render uses the new buffer (lets a host ping-pong two gather messages)
-    c->d_out = texels ? (vrt::Texel *)texels : c->own_out;
+    c->d_out = texels ? (vrt::Texel *)texels : c->sz.own_out;
     c->last_out = c->d_out;
     c->rendered = false;
     return VRT_OK;
@@ -1155,7 +1106,7 @@ int vrt_bind_output(vrt_ctx *c, void *texels) {
 int vrt_device_output(vrt_ctx *c, void **texels, uint64_t *bytes) {
     GRP_ROOT(c, vrt_device_output(d, texels, bytes));
     if (!c) return VRT_ERR_INVALID_ARG;
-    if (texels) *texels = c->d_out == c->own_out ? c->last_out : c->d_out;  // own buffers: the one holding the last frame
+    if (texels) *texels = c->d_out == c->sz.own_out ? c->last_out : c->d_out;  // own buffers: the one holding the last frame
     if (bytes) *bytes = (uint64_t)c->slots * (c->compact ? 8u : sizeof(vrt::Texel));
     return VRT_OK;
 }

@@ -255,13 +255,11 @@ static int gen_run(vrt_ctx *c, bool gen, uint32_t seed, const int32_t *pos, cons
                 return fail(c, VRT_ERR_INVALID_ARG, "%s: chunk %llu has a coordinate %d outside (-2^26, 2^26)", what,
                             (unsigned long long)(i / 3), (int)pos[i]);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_gen_stage) {
-        HIP_TRY(c, hipMalloc(&c->d_gen_stage, (size_t)kGenBatch * kGenSlot * sizeof(uint16_t)));
-        HIP_TRY(c, hipMalloc(&c->d_gen_counts, (size_t)kGenBatch * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_gen_offs, (size_t)(kGenBatch + 1) * sizeof(uint64_t)));
-        HIP_TRY(c, hipMalloc(&c->d_gen_pos, (size_t)kGenBatch * 3 * sizeof(int32_t)));
-    }
-    if (!gen && !c->d_gen_dense) HIP_TRY(c, hipMalloc(&c->d_gen_dense, (size_t)kGenBatch * 32768u * sizeof(uint16_t)));
+    HIP_TRY(c, c->d_gen_stage.once((size_t)kGenBatch * kGenSlot));
+    HIP_TRY(c, c->d_gen_counts.once(kGenBatch));
+    HIP_TRY(c, c->d_gen_offs.once(kGenBatch + 1));
+    HIP_TRY(c, c->d_gen_pos.once((size_t)kGenBatch * 3));
+    if (!gen) HIP_TRY(c, c->d_gen_dense.once((size_t)kGenBatch * 32768u));
     hipStream_t st = c->stream;
     std::vector<uint64_t> h_offs(kGenBatch + 1);
     uint64_t total = 0;
@@ -297,15 +295,12 @@ static int gen_run(vrt_ctx *c, bool gen, uint32_t seed, const int32_t *pos, cons
         }
         const uint64_t bt = h_offs[nb];
         if (fits && total + bt <= cap_nodes) {
-            if (total + bt > c->gen_out_cap) {   // grow, keeping the nodes gathered so far
-                const uint64_t cap = std::max<uint64_t>(total + bt, 2 * c->gen_out_cap);
-                uint16_t *p = nullptr;
-                HIP_TRY(c, hipMalloc(&p, (size_t)cap * sizeof(uint16_t)));
+            if (total + bt > c->d_gen_out.cap()) {   // grow, keeping the nodes gathered so far
+                vrt_ctx::Buf<uint16_t> p;
+                HIP_TRY(c, p.once(std::max<uint64_t>(total + bt, 2 * c->d_gen_out.cap())));
                 if (total) HIP_TRY(c, hipMemcpyAsync(p, c->d_gen_out, (size_t)total * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
                 HIP_TRY(c, hipStreamSynchronize(st));
-                (void)hipFree(c->d_gen_out);
-                c->d_gen_out = p;
-                c->gen_out_cap = cap;
+                c->d_gen_out = std::move(p);
             }
             gen_gather_kernel<<<dim3(nb), dim3(kGenBlock), 0, st>>>(c->d_gen_stage, c->d_gen_counts, c->d_gen_offs, c->d_gen_out + total);
             HIP_TRY(c, hipGetLastError());

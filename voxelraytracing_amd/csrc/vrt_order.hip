@@ -56,25 +56,24 @@ int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, con
     // mode's frame is a stale order, and the frame before a sort must be of the same kind)
     if (c->frame_mode != o.mode) c->view_gen++;
     if (lpt) {
-        if (c->tile_buf_tiles != c->tiles_local) {
+        if (!c->sz.d_tile_scratch) {   // (the last of the three; a resize drops them)
             const uint32_t chunks = (c->tiles_local + 63u) / 64u;
-            HIP_TRY(c, hipMalloc(&c->d_tile_cost, (size_t)c->tiles_local * sizeof(uint32_t)));
-            HIP_TRY(c, hipMalloc(&c->d_tile_order, (size_t)c->tiles_local * sizeof(uint32_t)));
-            HIP_TRY(c, hipMalloc(&c->d_tile_scratch, (size_t)64u * (chunks + 1u) * sizeof(uint32_t)));
-            c->tile_buf_tiles = c->tiles_local;
-            c->tile_order_valid = false;
+            HIP_TRY(c, c->sz.d_tile_cost.once(c->tiles_local));
+            HIP_TRY(c, c->sz.d_tile_order.once(c->tiles_local));
+            HIP_TRY(c, c->sz.d_tile_scratch.once((size_t)64u * (chunks + 1u)));
+            c->sz.tile_order_valid = false;
         }
         // an order is used by the very view it was made from, or — a dilated one — by a view whose camera the dilation still covers
-        const bool exact = c->tile_order_valid && !c->order_dilated && c->order_view_gen == c->view_gen;
+        const bool exact = c->sz.tile_order_valid && !c->order_dilated && c->order_view_gen == c->view_gen;
         // (a 4K frame's order is 8 160 blocks to sort — ~ 50 us —, holds for half as many camera steps, and shortens a 354-us frame
         // by the same ~ 5 us: 364 us per frame against 354 in screen order.  Frames of up to kMovingTilesMax tiles — 1080p: 32 400 — ask.)
         const bool moving_ok = c->tile_lpt_moving && c->tiles_local == P.tiles_total && P.tiles_total % P.tiles_x == 0u &&
                                (P.tiles_total <= kMovingTilesMax || c->mov_any_size);
         const HoldLimits lim = hold_limits(c->cam, c->width, c->height, c->mov_radius);
-        const bool near = c->tile_order_valid && c->order_dilated && moving_ok && c->view_gen - c->order_view_gen == c->cam_gen - c->order_cam_gen &&
+        const bool near = c->sz.tile_order_valid && c->order_dilated && moving_ok && c->view_gen - c->order_view_gen == c->cam_gen - c->order_cam_gen &&
                           cameras_within(c->order_cam, c->cam, lim.voxels, lim.cos_hold);
-        if (!exact && !near) c->tile_order_valid = false;   // the order of another view: worse than none
-        if (c->tile_order_valid) { P.tile_order = c->d_tile_order; c->ordered_frames++; }
+        if (!exact && !near) c->sz.tile_order_valid = false;   // the order of another view: worse than none
+        if (c->sz.tile_order_valid) { P.tile_order = c->sz.d_tile_order; c->ordered_frames++; }
         if (near) c->order_uses++;
         if (!exact) {
             if (c->frame_view_gen == c->view_gen) tile_sort = true;   // the view has come to rest: this frame notes its trips
@@ -90,7 +89,7 @@ int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, con
         // ... and a kept dilated order likewise (the edit may have moved a silhouette further than the dilation covers): this frame's
         // trips whatever the back-off says
         if (near && c->tile_order_stale && !edit_in_front && !tile_sort) tile_sort = dilate = true;
-        if (tile_sort) P.tile_cost = c->d_tile_cost;
+        if (tile_sort) P.tile_cost = c->sz.d_tile_cost;
     }
     c->frame_view_gen = c->view_gen;
     c->frame_mode = o.mode;
@@ -105,18 +104,18 @@ int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st
     if (!plan.sort) return VRT_OK;
     bool made = true;
     if (plan.dilate) {
-        made = vrt::launch_tile_order_blocks(c->d_tile_cost, P.tiles_x, P.tiles_total / P.tiles_x, 1u, c->mov_radius, c->d_tile_order, st, 1024u);
+        made = vrt::launch_tile_order_blocks(c->sz.d_tile_cost, P.tiles_x, P.tiles_total / P.tiles_x, 1u, c->mov_radius, c->sz.d_tile_order, st, 1024u);
         // orders that are not used — the view moves further per frame than they cover — are asked for less and less often
         c->mov_backoff = c->order_dilated && c->order_uses < 2u ? (c->mov_backoff ? (c->mov_backoff < 64u ? c->mov_backoff * 2u : 64u) : 1u) : 0u;
         c->mov_skip = c->mov_backoff;
         c->order_uses = 0;
     } else {
-        vrt::launch_tile_order(c->d_tile_cost, c->tiles_local, 1u, c->d_tile_scratch, c->d_tile_order, st);   // classes of two trips
+        vrt::launch_tile_order(c->sz.d_tile_cost, c->tiles_local, 1u, c->sz.d_tile_scratch, c->sz.d_tile_order, st);   // classes of two trips
     }
     // (a launch that could not be made — more blocks than the one-launch order holds, an LDS size the device refuses — leaves the
     // frames in screen order; it is not the frame's error)
     if (hipGetLastError() != hipSuccess) made = false;
-    c->tile_order_valid = made;
+    c->sz.tile_order_valid = made;
     c->order_view_gen = c->view_gen;
     c->order_dilated = plan.dilate;
     c->order_cam_gen = c->cam_gen;

@@ -95,12 +95,9 @@ int screen_buffer_for_frame(vrt_ctx *c, uint32_t k, hipStream_t st, uint32_t scr
     const size_t bytes = (size_t)screen_w * screen_h * 4u;
     // the buffer's previous blit ran on the frame set's stream of that time: almost always this one
     if (c->screen_stream[k] && c->screen_stream[k] != st) HIP_TRY(c, hipStreamSynchronize(c->screen_stream[k]));
-    if (bytes > c->screen_cap[k]) {
+    if (bytes > c->d_screen[k].cap()) {
         HIP_TRY(c, hipStreamSynchronize(st));   // an earlier present may still be writing the old buffer
-        (void)hipFree(c->d_screen[k]);
-        c->d_screen[k] = nullptr; c->screen_cap[k] = 0;
-        HIP_TRY(c, hipMalloc(&c->d_screen[k], bytes));
-        c->screen_cap[k] = bytes;
+        HIP_TRY(c, c->d_screen[k].grow(bytes));
     }
     c->screen_stream[k] = st;
     return VRT_OK;

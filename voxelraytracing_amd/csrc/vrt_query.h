@@ -100,7 +100,7 @@ static int query_world(vrt_ctx *c, vrt::QueryWorld &P) {
         if (T.dirty_chunks.empty()) {
             P.grid = T.d_grid;
             P.bricks = T.d_bricks;
-            P.brick_entries = T.brick_cap * 64u;
+            P.brick_entries = T.brick_cap() * 64u;
         }
     }
     return VRT_OK;
@@ -111,15 +111,9 @@ static int query_world(vrt_ctx *c, vrt::QueryWorld &P) {
 static int query_batch_host(vrt_ctx *c, const void *q, size_t q_bytes, void *out, size_t out_bytes, uint32_t n,
                             int (*enqueue)(vrt_ctx *, const void *, uint32_t, void *)) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->query_cap < q_bytes + out_bytes) {
-        (void)hipFree(c->d_query);
-        c->d_query = nullptr;
-        c->query_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_query, q_bytes + out_bytes));
-        c->query_cap = q_bytes + out_bytes;
-    }
+    HIP_TRY(c, c->d_query.grow(q_bytes + out_bytes));
     if (!c->ev_query) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
-    uint8_t *dq = static_cast<uint8_t *>(c->d_query), *dout = dq + q_bytes;   // (both record sizes are multiples of 4)
+    uint8_t *dq = c->d_query, *dout = dq + q_bytes;   // (both record sizes are multiples of 4)
     HIP_TRY(c, hipMemcpyAsync(dq, q, q_bytes, hipMemcpyHostToDevice, c->stream));
     const int rc = enqueue(c, dq, n, dout);
     if (rc) return rc;

@@ -16,9 +16,8 @@ int alloc_roots(vrt_ctx *c, uint32_t world_size) {
     }
     if (c->up_stream) HIP_TRY(c, hipStreamSynchronize(c->up_stream));
     c->roots_tag = 0;
-    (void)hipFree(c->d_roots);
-    c->d_roots = nullptr;
-    HIP_TRY(c, hipMalloc(&c->d_roots, n * sizeof(uint32_t)));
+    c->d_roots.release();
+    HIP_TRY(c, c->d_roots.once(n));
     // A fresh wgpu buffer is zero-initialised: every chunk resolves to pool[0], the air leaf.
     HIP_TRY(c, hipMemsetAsync(c->d_roots, 0, n * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (later uploads run on their own stream)
@@ -343,17 +342,6 @@ static void mark_node_range_dirty(vrt_ctx *c, uint32_t start, uint32_t end) {
 //   update_tables       once the frame has its set and stream: the chunks dirtied since *that set* was last brought up to
 //                       date, rebuilt alone on the frame's own stream — nothing waits for the frames in flight, which read
 //                       other sets (or are earlier on this very stream).
-int free_tables(vrt_ctx *c, vrt_ctx::Tables &T) {
-    (void)c;
-    (void)hipFree(T.d_grid); (void)hipFree(T.d_bricks); (void)hipFree(T.d_chunk_bricks); (void)hipFree(T.d_chunk_bases);
-    (void)hipFree(T.d_chunk_caps); (void)hipFree(T.d_brick_tail); (void)hipFree(T.d_cdir); (void)hipFree(T.d_mblk); (void)hipFree(T.d_mblk_tail);
-    T.d_grid = nullptr; T.d_bricks = nullptr; T.d_chunk_bricks = T.d_chunk_bases = T.d_chunk_caps = T.d_brick_tail = nullptr;
-    T.d_cdir = nullptr; T.d_mblk = nullptr; T.d_mblk_tail = nullptr;
-    T.grid_cap = 0; T.brick_cap = 0; T.chunk_cap = 0; T.cdir_cap = 0; T.mblk_cap = 0;
-    T.live = false;
-    return VRT_OK;
-}
-
 // tabs[k] becomes a copy of tabs[0] (device tables and host bookkeeping); everything on c->stream, the caller has waited
 // for the frames in flight.
 static int alloc_tables_like_first(vrt_ctx *c, uint32_t k) {
@@ -361,40 +349,19 @@ static int alloc_tables_like_first(vrt_ctx *c, uint32_t k) {
     auto &T = c->tabs[k];
     const uint32_t S = c->accel_S, n_chunks = S * S * S;
     const size_t G = (size_t)S * 8u, entries = G * (G + 1u) * (G + 1u);
-    if (T.grid_cap < entries) {
-        (void)hipFree(T.d_grid); T.d_grid = nullptr; T.grid_cap = 0;
-        HIP_TRY(c, hipMalloc(&T.d_grid, entries * sizeof(uint32_t)));
-        T.grid_cap = entries;
-    }
+    HIP_TRY(c, T.d_grid.grow(entries));
     if (A.d_mblk) {
-        if (T.cdir_cap < chunk_dir_entries(S)) {
-            (void)hipFree(T.d_cdir); T.d_cdir = nullptr; T.cdir_cap = 0;
-            HIP_TRY(c, hipMalloc(&T.d_cdir, chunk_dir_entries(S) * sizeof(uint32_t)));
-            T.cdir_cap = chunk_dir_entries(S);
-        }
-        if (T.mblk_cap != A.mblk_cap || !T.d_mblk) {
-            (void)hipFree(T.d_mblk); T.d_mblk = nullptr; T.mblk_cap = 0;
-            HIP_TRY(c, hipMalloc(&T.d_mblk, (size_t)A.mblk_cap * 512u * sizeof(uint4)));
-            T.mblk_cap = A.mblk_cap;
-        }
-        if (!T.d_mblk_tail) HIP_TRY(c, hipMalloc(&T.d_mblk_tail, sizeof(uint32_t)));
-    } else if (T.d_mblk) {
-        (void)hipFree(T.d_mblk); T.d_mblk = nullptr; T.mblk_cap = 0;
+        HIP_TRY(c, T.d_cdir.grow(chunk_dir_entries(S)));
+        HIP_TRY(c, T.d_mblk.exactly(A.d_mblk.cap()));
+        HIP_TRY(c, T.d_mblk_tail.once(1));
+    } else {
+        T.d_mblk.release();
     }
-    if (T.chunk_cap < n_chunks) {
-        (void)hipFree(T.d_chunk_bricks); (void)hipFree(T.d_chunk_bases); (void)hipFree(T.d_chunk_caps);
-        T.d_chunk_bricks = T.d_chunk_bases = T.d_chunk_caps = nullptr; T.chunk_cap = 0;
-        HIP_TRY(c, hipMalloc(&T.d_chunk_bricks, (size_t)n_chunks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&T.d_chunk_bases, (size_t)n_chunks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&T.d_chunk_caps, (size_t)n_chunks * sizeof(uint32_t)));
-        T.chunk_cap = n_chunks;
-    }
-    if (T.brick_cap != A.brick_cap || !T.d_bricks) {
-        (void)hipFree(T.d_bricks); T.d_bricks = nullptr; T.brick_cap = 0;
-        HIP_TRY(c, hipMalloc(&T.d_bricks, (size_t)A.brick_cap * 64u * sizeof(uint16_t)));
-        T.brick_cap = A.brick_cap;
-    }
-    if (!T.d_brick_tail) HIP_TRY(c, hipMalloc(&T.d_brick_tail, sizeof(uint32_t)));
+    HIP_TRY(c, T.d_chunk_bricks.grow(n_chunks));
+    HIP_TRY(c, T.d_chunk_bases.grow(n_chunks));
+    HIP_TRY(c, T.d_chunk_caps.grow(n_chunks));
+    HIP_TRY(c, T.d_bricks.exactly(A.d_bricks.cap()));
+    HIP_TRY(c, T.d_brick_tail.once(1));
     return VRT_OK;
 }
 
@@ -410,14 +377,14 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     HIP_TRY(c, hipMemcpyAsync(T.d_grid, A.d_grid, entries * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     if (A.d_mblk) {
         HIP_TRY(c, hipMemcpyAsync(T.d_cdir, A.d_cdir, chunk_dir_entries(S) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(T.d_mblk, A.d_mblk, (size_t)A.mblk_cap * 512u * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(T.d_mblk, A.d_mblk, A.d_mblk.cap() * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(T.d_mblk_tail, A.d_mblk_tail, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(c, hipMemcpyAsync(T.d_chunk_bricks, A.d_chunk_bricks, (size_t)n_chunks * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(T.d_chunk_bases, A.d_chunk_bases, (size_t)n_chunks * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(T.d_chunk_caps, A.d_chunk_caps, (size_t)n_chunks * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(T.d_brick_tail, A.d_brick_tail, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(T.d_bricks, A.d_bricks, (size_t)A.brick_cap * 64u * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(T.d_bricks, A.d_bricks, A.d_bricks.cap() * sizeof(uint16_t), hipMemcpyDeviceToDevice, c->stream));
     T.chunk_may_have_moved = A.chunk_may_have_moved;
     T.chunks_moved = A.chunks_moved;
     T.chunk_builds = A.chunk_builds;
@@ -465,38 +432,18 @@ int ensure_accel_world(vrt_ctx *c) {
     const uint32_t n_chunks = S * S * S;
     const size_t G = (size_t)S * 8u;
     const size_t entries = G * (G + 1u) * (G + 1u);
-    if (entries > A.grid_cap) {
-        (void)hipFree(A.d_grid);
-        A.d_grid = nullptr; A.grid_cap = 0;
-        HIP_TRY(c, hipMalloc(&A.d_grid, entries * sizeof(uint32_t)));
-        A.grid_cap = entries;
-    }
+    HIP_TRY(c, A.d_grid.grow(entries));
     // the border rows / entries are never written by the kernels: zero = "outside the world"
     HIP_TRY(c, hipMemsetAsync(A.d_grid, 0, entries * sizeof(uint32_t), c->stream));
-    if (chunk_dir_entries(S) > A.cdir_cap) {
-        (void)hipFree(A.d_cdir);
-        A.d_cdir = nullptr; A.cdir_cap = 0;
-        HIP_TRY(c, hipMalloc(&A.d_cdir, chunk_dir_entries(S) * sizeof(uint32_t)));
-        A.cdir_cap = chunk_dir_entries(S);
-    }
+    HIP_TRY(c, A.d_cdir.grow(chunk_dir_entries(S)));
     HIP_TRY(c, hipMemsetAsync(A.d_cdir, 0, chunk_dir_entries(S) * sizeof(uint32_t), c->stream));   // the border: outside the world
-    if (!A.d_mblk_tail) HIP_TRY(c, hipMalloc(&A.d_mblk_tail, sizeof(uint32_t)));
-    if (n_chunks > c->chunk_needs_cap) {
-        (void)hipFree(c->d_chunk_needs);
-        c->d_chunk_needs = nullptr; c->chunk_needs_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_chunk_needs, (size_t)n_chunks * sizeof(uint32_t)));
-        c->chunk_needs_cap = n_chunks;
-    }
-    if (n_chunks > A.chunk_cap) {
-        (void)hipFree(A.d_chunk_bricks); (void)hipFree(A.d_chunk_bases); (void)hipFree(A.d_chunk_caps);
-        A.d_chunk_bricks = A.d_chunk_bases = A.d_chunk_caps = nullptr; A.chunk_cap = 0;
-        HIP_TRY(c, hipMalloc(&A.d_chunk_bricks, (size_t)n_chunks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&A.d_chunk_bases, (size_t)n_chunks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&A.d_chunk_caps, (size_t)n_chunks * sizeof(uint32_t)));
-        A.chunk_cap = n_chunks;
-    }
-    if (!c->d_brick_total) HIP_TRY(c, hipMalloc(&c->d_brick_total, 2 * sizeof(uint32_t)));   // [0] bricks, [1] march-cell blocks
-    if (!A.d_brick_tail) HIP_TRY(c, hipMalloc(&A.d_brick_tail, sizeof(uint32_t)));
+    HIP_TRY(c, A.d_mblk_tail.once(1));
+    HIP_TRY(c, c->d_chunk_needs.grow(n_chunks));
+    HIP_TRY(c, A.d_chunk_bricks.grow(n_chunks));
+    HIP_TRY(c, A.d_chunk_bases.grow(n_chunks));
+    HIP_TRY(c, A.d_chunk_caps.grow(n_chunks));
+    HIP_TRY(c, c->d_brick_total.once(2));   // [0] bricks, [1] march-cell blocks
+    HIP_TRY(c, A.d_brick_tail.once(1));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(c, hipEventCreate(&e0));
     HIP_TRY(c, hipEventCreate(&e1));
@@ -505,7 +452,7 @@ int ensure_accel_world(vrt_ctx *c) {
     auto body = [&]() -> int {
         HIP_TRY(c, hipEventRecord(e0, c->stream));
         vrt::launch_accel_cells(c->d_nodes, c->max_nodes, c->d_roots, S, A.d_grid, A.d_chunk_bricks, A.d_chunk_bases, A.d_chunk_caps,
-                                c->d_brick_total, A.d_brick_tail, direct ? nullptr : c->d_chunk_needs, A.d_cdir, A.d_mblk_tail, c->d_brick_total + 1, c->stream);
+                                c->d_brick_total, A.d_brick_tail, direct ? nullptr : c->d_chunk_needs.get(), A.d_cdir, A.d_mblk_tail, c->d_brick_total + 1, c->stream);
         HIP_TRY(c, hipGetLastError());
         uint32_t totals[2] = {0, 0};  // bricks in all chunk regions (counts + slack); chunks that need a block of march cells
         HIP_TRY(c, hipMemcpyAsync(totals, c->d_brick_total, sizeof totals, hipMemcpyDeviceToHost, c->stream));
@@ -515,31 +462,25 @@ int ensure_accel_world(vrt_ctx *c) {
         // before the next whole-world build (every one of them is a chunk rebuilt alone: at most kTailChunks)
         const uint64_t want_blocks = direct ? (direct_cell_entries(S) + 511u) / 512u : 2ull + totals[1] + kTailChunks;
         if (want_blocks > kMarchBlocksMax) {
-            for (auto &T : c->tabs) { (void)hipFree(T.d_mblk); T.d_mblk = nullptr; T.mblk_cap = 0; }
+            for (auto &T : c->tabs) T.d_mblk.release();
         } else {
-            if (want_blocks > A.mblk_cap || !A.d_mblk) {
-                (void)hipFree(A.d_mblk);
-                A.d_mblk = nullptr; A.mblk_cap = 0;
+            if (want_blocks > A.mblk_cap()) {
                 uint64_t cap = want_blocks + (direct ? 0u : totals[1] / 8u);
                 if (cap > kMarchBlocksMax) cap = kMarchBlocksMax;
-                HIP_TRY(c, hipMalloc(&A.d_mblk, (size_t)cap * 512u * sizeof(uint4)));
-                A.mblk_cap = (uint32_t)cap;
+                HIP_TRY(c, A.d_mblk.grow((size_t)cap * 512u));
             }
             // block 0: every cell stops the ray (direct: so do the blocks of the directory's border)
             HIP_TRY(c, hipMemsetAsync(A.d_mblk, 0, (direct ? (size_t)want_blocks : (size_t)1) * 512u * sizeof(uint4), c->stream));
         }
         const uint64_t want = (uint64_t)total + (uint64_t)kTailChunks * 512u;
         if (want > kAccelMaxBricks) return VRT_OK;  // accel_ok stays false
-        if (want > A.brick_cap || !A.d_bricks) {
-            (void)hipFree(A.d_bricks);
-            A.d_bricks = nullptr; A.brick_cap = 0;
+        if (want > A.brick_cap()) {
             uint64_t cap = want + total / 4u;  // room to grow before the next reallocation
             if (cap > kAccelMaxBricks) cap = kAccelMaxBricks;
-            HIP_TRY(c, hipMalloc(&A.d_bricks, (size_t)cap * 64u * sizeof(uint16_t)));
-            A.brick_cap = (uint32_t)cap;
+            HIP_TRY(c, A.d_bricks.grow((size_t)cap * 64u));
         }
-        vrt::launch_accel_bricks(c->d_nodes, c->max_nodes, c->d_roots, S, A.d_grid, A.d_chunk_bases, A.d_bricks, A.brick_cap, direct ? nullptr : A.d_cdir, A.d_mblk,
-                                 A.d_mblk_tail, A.mblk_cap, c->liquid_mask, c->stream);
+        vrt::launch_accel_bricks(c->d_nodes, c->max_nodes, c->d_roots, S, A.d_grid, A.d_chunk_bases, A.d_bricks, A.brick_cap(), direct ? nullptr : A.d_cdir.get(), A.d_mblk,
+                                 A.d_mblk_tail, A.mblk_cap(), c->liquid_mask, c->stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(e1, c->stream));
         HIP_TRY(c, hipEventSynchronize(e1));
@@ -613,7 +554,7 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
     // (the next upload of nodes or roots waits for this reader: ev_updated is the completion signal of the launch itself — a
     // record behind it is one more packet between the rebuild and the frame that waits for it)
     vrt::launch_accel_chunks(c->d_nodes, c->max_nodes, c->d_roots, c->accel_S, T.d_grid, T.d_chunk_bricks, T.d_chunk_bases, T.d_chunk_caps,
-                             T.d_brick_tail, T.d_bricks, T.brick_cap, c->march_direct ? nullptr : T.d_cdir, T.d_mblk, T.d_mblk_tail, T.mblk_cap, c->liquid_mask,
+                             T.d_brick_tail, T.d_bricks, T.brick_cap(), c->march_direct ? nullptr : T.d_cdir.get(), T.d_mblk, T.d_mblk_tail, T.mblk_cap(), c->liquid_mask,
                              T.dirty_chunks.data(), extents.data(), roots_now.data(), (uint32_t)T.dirty_chunks.size(), st, T.ev_updated);
     HIP_TRY(c, hipGetLastError());
     T.update_pending = true;
@@ -647,7 +588,7 @@ static int bricks_in_use(vrt_ctx *c, const vrt_ctx::Tables &T, uint32_t *n) {
     QUIESCE(c);   // (the set's last update may be on another frame stream)
     HIP_TRY(c, hipMemcpyAsync(n, T.d_brick_tail, sizeof *n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (*n > T.brick_cap) *n = T.brick_cap;
+    if (*n > T.brick_cap()) *n = T.brick_cap();
     return VRT_OK;
 }
 
@@ -826,7 +767,7 @@ int vrt_read_march_cells(vrt_ctx *c, uint32_t *cells, uint32_t *direct) {
     const uint32_t S = c->accel_S;
     const size_t G = (size_t)S * 8u;
     if (direct) *direct = c->march_direct ? 1u : 0u;
-    std::vector<uint4> blocks(c->march_direct ? direct_cell_entries(S) : (size_t)T.mblk_cap * 512u);
+    std::vector<uint4> blocks(c->march_direct ? direct_cell_entries(S) : (size_t)T.mblk_cap() * 512u);
     std::vector<uint32_t> dir(chunk_dir_entries(S));
     HIP_TRY(c, hipMemcpyAsync(blocks.data(), T.d_mblk, blocks.size() * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dir.data(), T.d_cdir, dir.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -841,7 +782,7 @@ int vrt_read_march_cells(vrt_ctx *c, uint32_t *cells, uint32_t *direct) {
                     at = (((z >> 1) * B1 + (y >> 1)) * B1 + (x >> 1)) * 8u + sub;
                 } else {
                     const uint32_t blk = dir[((z >> 3) * (S + 1u) + (y >> 3)) * (S + 1u) + (x >> 3)];
-                    if (blk >= T.mblk_cap) return fail(c, VRT_ERR_DEVICE, "vrt_read_march_cells: the directory names block %u of %u", blk, T.mblk_cap);
+                    if (blk >= T.mblk_cap()) return fail(c, VRT_ERR_DEVICE, "vrt_read_march_cells: the directory names block %u of %u", blk, T.mblk_cap());
                     const size_t line = ((((z >> 1) & 3u) << 2 | ((y >> 1) & 3u)) << 2) | ((x >> 1) & 3u);
                     at = (size_t)blk * 512u + line * 8u + sub;
                 }
