@@ -124,6 +124,9 @@ def test_cap_nodes_one_word_short(gpu, block):
 
 
 def test_the_batch_boundary(gpu):
+    """A call of one chunk more than a batch answers, and its last chunk is edited.  This is not the test of the per-batch
+    offsets: the trees are one word each and the call has one (chunk, shape) pair, so the second batch's bin_off is 0.  That is
+    tests/test_gpu_edit_matrix.py's batch cases (hand-made trees of many lengths, shapes on both sides of the boundary)."""
     n = BATCH + 1
     pos = [(i % 64, 0, i // 64) for i in range(n)]
     nodes = np.full(n, 4, np.uint16)
