@@ -1,5 +1,6 @@
 """The context's device buffers through their lives (csrc/vrt_devbuf.h): the ones a resize drops made again at a smaller and a
-larger size, the grow-only ones across their floors and back, and whole contexts made and destroyed in a row — at the smallest
+larger size, the grow-only ones across their floors and back, and whole contexts made and destroyed in a row — the last ones
+with every lazily made stream, event and the pinned ring alive (csrc/vrt_handle.h), and groups of two likewise — at the smallest
 shapes, every answer held to the oracle or to the host mirror (never to an earlier answer of the build under test)."""
 import numpy as np
 import pytest
@@ -198,3 +199,100 @@ def test_contexts_made_and_destroyed_in_a_row(orc):
         rgb, ids, _ = gpu.read_output()
         assert_frame_parity(rgb, ids, r_rgb, r_ids, f"context {k}")
         gpu.close()
+
+
+def test_contexts_with_every_stream_event_and_the_ring_alive_destroyed_in_a_row(orc):
+    """Three contexts over 2^3 chunks at 64 x 40, four frames in flight, each destroyed with every handle it makes on first use
+    alive: the extra frame streams (five primary + shadow frames), the accumulation's event (two path frames, then an accumulating
+    pair), the queries' event (64 rays), a table set's update and a ring event on the upload stream (an edit between two frames),
+    a quadruple of the event pool (a timed frame, folded by stats()).  The steps start at another one for each context, so another
+    handle was the last one used; every frame is the oracle's, every ray the host mirror's."""
+    w, h = 64, 40
+    rays = None
+    for k in range(3):
+        sc = _path_scene(2, (w, h))
+        gpu = gpu_for_scene(sc)
+        gpu.set_frames_in_flight(4)
+        now = {"o": orc.from_package_scene(sc)}   # the oracle of the world as it is now
+        if rays is None:
+            rays = cc.fuzz_queries(sc.world, 64, seed=21)
+
+        def check(what, mode=orc.MODE_PRIMARY_SHADOW, **kw):
+            rgb, ids, _ = gpu.read_output()
+            r_rgb, r_ids = now["o"].render(mode, w, h, **kw)[:2]
+            assert_frame_parity(rgb, ids, r_rgb, r_ids, f"context {k}: {what}")
+
+        def march():
+            for _ in range(5):           # every frame set in turn
+                gpu.render(MODE_PRIMARY_SHADOW)
+            check("the last of five primary + shadow frames")
+
+        def path():
+            for _ in range(2):
+                gpu.render(MODE_PATH, spp=1, seed=SEED)
+            check("path, 1 spp", orc.MODE_PATH, spp=1, seed=SEED)
+            gpu.reset_accumulation()
+            for _ in range(2):
+                gpu.render(MODE_PATH, spp=1, seed=SEED, accumulate=True)
+            assert gpu.accumulation() == (2, SEED)
+            check("1 + 1 accumulated", orc.MODE_PATH, spp=2, seed=SEED)
+
+        def queries():
+            want = sc.world.cast_rays(rays["start"], rays["dir"], rays["max_dist"])
+            bad = cc.records_equal(want, gpu.cast_rays(rays["start"], rays["dir"], rays["max_dist"]))
+            assert bad.size == 0, f"context {k}: {bad.size} rays differ from the host mirror, first {bad[0]}"
+
+        def edit():
+            gpu.render(MODE_PRIMARY_SHADOW)
+            rng = np.random.default_rng(40 + k)
+            ex, ey, ez = (int(v) for v in sc.eye)
+            for _ in range(20):
+                p = (ex + int(rng.integers(-16, 17)), ey + int(rng.integers(-20, 4)), ez + int(rng.integers(-16, 17)))
+                try:
+                    start, n = sc.world.set_voxel(p, int(rng.choice([0, 0, 3, 4])))
+                except Exception as e:
+                    assert getattr(e, "kind", "") in ("NoChange", "NoChunk", "OutOfMemory")
+                    continue
+                break
+            else:
+                raise AssertionError("no voxel could be edited")
+            gpu.write_nodes(sc.world.nodes_ptr(), start, start + n)
+            gpu.write_chunk_roots(sc.world.chunk_roots())
+            now["o"] = orc.from_package_scene(sc)
+            gpu.render(MODE_PRIMARY_SHADOW)
+            check("the frame behind an edit")
+            assert gpu.accel_info().chunk_builds > 0   # (a table set's own update, not a whole-world build)
+
+        def timed():
+            gpu.render(MODE_PRIMARY_SHADOW, timed=True)
+            st = gpu.stats()
+            assert st.frames >= 1 and st.ms_total > 0.0 and st.primary_rays == w * h
+            check("a timed frame")
+
+        steps = [march, path, queries, edit, timed]
+        first = 2 * k % len(steps)       # the last step: timed, path, edit
+        for step in steps[first:] + steps[:first]:
+            step()
+        gpu.close()
+
+
+def test_groups_of_two_made_and_destroyed_in_a_row(orc):
+    """One context over two devices (both device 0) at 64 x 40, with the default messages and with staged ones, each destroyed with
+    its message buffers and events alive: three primary + shadow frames, down to 24 x 16 — the messages are allocated again —
+    and three more, against the oracle."""
+    sc = scenes.procedural(2, (64, 40))
+    o = orc.from_package_scene(sc)
+    for staged in (False, True):
+        grp = gpu_for_scene(sc, devices=[0, 0], staged_messages=staged)
+        for w, h in ((64, 40), (24, 16)):
+            if (w, h) != sc.size:
+                grp.resize_result_texture((w, h))
+            cam = g.cam_data_create(sc.rot, sc.eye, 70.0, (float(w), float(h)))
+            grp.write_cam_data(cam)
+            o.set_cam(cam)
+            r_rgb, r_ids, _, _ = o.render(orc.MODE_PRIMARY_SHADOW, w, h)
+            for _ in range(3):           # both message slots, the first one twice
+                grp.render(MODE_PRIMARY_SHADOW)
+            rgb, ids, _ = grp.read_output()
+            assert_frame_parity(rgb, ids, r_rgb, r_ids, f"staged {staged}, {w} x {h}: the last of three frames")
+        grp.close()

@@ -17,8 +17,10 @@
 // (DESIGN.md §HBM layout): the node pool is kept byte-identical to the host pool (little-endian u16 =
 // the reference's packed u32 pairs), chunk_roots is a dense u32[S^3], materials 256 x 32 B, output one
 // 16-byte texel {r,g,b f32, id u32} per pixel slot, hit buffer 16 B per local pixel.
-// Ownership: every device allocation of a context is a vrt_ctx::Buf (vrt_devbuf.h), freed with the context; raw pointers are
-// aliases or the caller's memory.  What depends on the output size is vrt_ctx::Sized: a resize assigns it an empty value.
+// Ownership: every device allocation of a context is a vrt_ctx::Buf (vrt_devbuf.h), every event, stream and pinned allocation a
+// vrt_ctx::Event / Stream / Pinned (vrt_handle.h, made where first used: ensure()); all go with the context, and so do a group's
+// with the group.  Raw pointers and handles are aliases or the caller's: stream, last_stream, wait_before_frame, screen_stream[],
+// d_ring.  What depends on the output size is vrt_ctx::Sized: a resize assigns it an empty value.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +41,7 @@
 #include <vector>
 
 #include "vrt_devbuf.h"
+#include "vrt_handle.h"
 #include "vrt_device.h"
 #include "vrt_exp.h"
 
@@ -46,6 +49,23 @@ namespace vrt {
 struct HipAlloc {   // vrt_devbuf.h's allocator over the HIP runtime
     static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
     static void free(void *p) { (void)hipFree(p); }
+};
+// vrt_handle.h's policies over the HIP runtime: an event (untimed unless asked: hipEventDefault for the ones that are read as
+// times), a non-blocking stream, mapped pinned host memory
+struct HipEvent {
+    using T = hipEvent_t;
+    static hipError_t create(T *e, unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(e, flags); }
+    static void destroy(T e) { (void)hipEventDestroy(e); }
+};
+struct HipStream {
+    using T = hipStream_t;
+    static hipError_t create(T *s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+    static void destroy(T s) { (void)hipStreamDestroy(s); }
+};
+struct HipPinned {
+    using T = uint8_t *;
+    static hipError_t create(T *p, size_t bytes) { return hipHostMalloc((void **)p, bytes, hipHostMallocMapped); }
+    static void destroy(T p) { (void)hipHostFree(p); }
 };
 bool variant_supported(uint32_t variant);
 void launch_primary(const FrameParams &P, uint32_t variant, bool stats, bool shadow, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
@@ -129,16 +149,19 @@ static_assert(kCounterWords * sizeof(unsigned long long) == kCounterBytes, "the 
 
 struct vrt_ctx {
     template <typename T> using Buf = vrt::DevBuf<T, vrt::HipAlloc>;
+    using Event = vrt::Handle<vrt::HipEvent>;
+    using Stream = vrt::Handle<vrt::HipStream>;
+    using Pinned = vrt::Handle<vrt::HipPinned>;
     vrt_group *grp = nullptr;   // a multi-device context (vrt_config.n_devices > 1): everything else below is unused, see vrt_group
     hipStream_t last_stream = nullptr;  // the stream the most recent frame was enqueued on
     hipEvent_t wait_before_frame = nullptr;  // set by a multi-device context: the next frame's stream waits for it first (its message slot is free)
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    Stream own_stream;
     // Two frames in flight (what a swapchain gives the reference): consecutive plain frames alternate between the
     // context's two streams, each with its own output buffer, so one frame's tail overlaps the next one's ramp-up
     // instead of the in-order queue's ~5 us hand-over.  Everything else on the context waits for both (quiesce()).
     static constexpr uint32_t kMaxInFlight = 4;
-    hipStream_t extra_stream[kMaxInFlight - 1] = {nullptr, nullptr, nullptr};
+    Stream extra_stream[kMaxInFlight - 1];   // each made by the first frame that runs on it
     Buf<unsigned long long> extra_counters[kMaxInFlight - 1];   // path mode: its own segment cursors
     uint32_t in_flight = 2;        // vrt_set_frames_in_flight
     bool alt_pending = false;      // frames may still be running on the extra streams
@@ -148,7 +171,7 @@ struct vrt_ctx {
     // four hipEvents per frame rendered since the last vrt_get_stats.  Primary(+shadow) frames: {begin, end} of the first
     // kernel and {begin, end} of the second, stamped by the dispatches themselves (hipExtLaunchKernel), so the stream
     // carries no marker packets between frames.  Path frames: [0], [1], [3] recorded around the launches.
-    std::vector<std::array<hipEvent_t, 4>> ev_pool;
+    std::vector<std::array<Event, 4>> ev_pool;   // (timing enabled)
     std::vector<uint8_t> ev_kind;  // EvKind
     size_t ev_used = 0;
     double acc_ms[3] = {0, 0, 0};
@@ -224,7 +247,7 @@ struct vrt_ctx {
         std::vector<uint8_t> chunk_may_have_moved;  // rebuilt alone since the last whole-world build: may sit in the pool's tail
         uint32_t chunks_moved = 0;
         uint32_t chunk_builds = 0;              // chunks this set has rebuilt alone (vrt_accel_info reports the most advanced set's)
-        hipEvent_t ev_updated = nullptr;        // behind this set's last chunk update (a reader of the node pool and chunk_roots)
+        Event ev_updated;                       // behind this set's last chunk update (a reader of the node pool and chunk_roots)
         bool update_pending = false;            // ... recorded and not yet known to be over
     };
     Tables tabs[kMaxInFlight];
@@ -310,10 +333,10 @@ struct vrt_ctx {
 
     // uploads are staged through pinned memory (copy-at-call semantics without waiting for the device) and ordered with
     // the frames in flight by events, not by draining them
-    uint8_t *h_ring = nullptr, *d_ring = nullptr;   // the pinned ring, and where the device sees it
+    Pinned h_ring;                // the pinned ring ...
+    uint8_t *d_ring = nullptr;    // ... and where the device sees it
     static constexpr size_t kRingSegBytes = 1u << 20, kRingSegs = 8;
-    hipEvent_t ring_ev[kRingSegs][2] = {};   // behind a segment's last copy on c->stream [0] / the upload stream [1]
-    bool ring_ev_used[kRingSegs][2] = {};
+    Event ring_ev[kRingSegs][2];   // behind a segment's last copy on c->stream [0] / the upload stream [1]; null: none yet
     uint32_t ring_seg = 0;
     size_t ring_off = 0;
     // node-pool / chunk_roots uploads staged since the last flush: copied into the ring at call time, launched together — one
@@ -325,17 +348,16 @@ struct vrt_ctx {
     size_t staged_bytes = 0;
     bool flushed_at_call = false;     // a staged range went out at its vrt_write_* call since the last frame (the device was idle): the next ones wait for the batch
     bool staged_seg[kRingSegs] = {};  // ring segments the staged ranges lie in (their events are recorded at the flush)
-    hipEvent_t ev_frames = nullptr;   // scratch: "everything enqueued on that frame stream so far"
-    hipEvent_t ev_upload = nullptr;   // the last upload / table rebuild on c->stream
+    Event ev_frames;                  // scratch: "everything enqueued on that frame stream so far"
+    Event ev_upload;                  // the last upload / table rebuild on c->stream
     // Node-pool and chunk_roots uploads have a stream of their own: frame set 0 runs on c->stream, and an upload queued
     // behind a frame there would wait for it.  What reads those two buffers — the table updates, and frames that walk the
     // octree itself (variants 1 / 2, worlds beyond the tables) — is what an upload waits for, nothing else.
-    hipStream_t up_stream = nullptr;
-    hipEvent_t ev_pool_upload = nullptr;      // the last upload on up_stream
+    Stream up_stream;
+    Event ev_pool_upload;                     // the last upload on up_stream
     uint64_t pool_gen = 0;                    // bumped by every upload on up_stream
     uint64_t seen_pool_gen[kMaxInFlight + 1] = {0, 0, 0, 0, 0};  // [slot] of the frame streams as seen_gen, [kMaxInFlight] c->stream
     bool walkers_in_flight = false;           // a frame that reads the node pool has been enqueued since the last full synchronise
-    hipEvent_t ev_walkers = nullptr;
     uint64_t upload_gen = 0;          // bumped by every upload; a frame stream waits for ev_upload when it has not seen it
     uint64_t seen_gen[kMaxInFlight] = {0, 0, 0, 0};  // [0] own_stream, [k] extra_stream[k - 1]
 
@@ -346,7 +368,7 @@ struct vrt_ctx {
     // vrt_cast_rays / vrt_clip_moves (vrt_query.h query_batch_host): the device copy of a host batch, queries then results, in
     // bytes; a host batch waits on ev_query for its own results before it returns, so the two kinds share one buffer
     Buf<uint8_t> d_query;
-    hipEvent_t ev_query = nullptr;
+    Event ev_query;
 
     // vrt_generate_chunks / vrt_build_chunks (vrt_gen.hip): one batch's staging slots, node counts, offsets and inputs (made on
     // first use), and the compacted nodes of a whole call (grown as needed)
@@ -384,7 +406,7 @@ struct vrt_ctx {
     // and the event behind the last step that wrote the sum (the next frame's first step that touches it waits for it)
     uint32_t accum_n = 0, accum_seed = 0;
     bool accum_restart = true;
-    hipEvent_t ev_accum = nullptr;
+    Event ev_accum;
     bool accum_ev_recorded = false;
     // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); the scratch frames the passes go back and forth over and the
     // guide words are sz.dn_scratch / sz.dn_guide
@@ -562,13 +584,13 @@ struct vrt_group {
     // [r] device r cannot store into device 0's memory (peer access refused), or VRT_FLAG_STAGED_MESSAGES: it renders into
     // stage[r][slot], a buffer of its own, and copies the message over afterwards (hipMemcpyPeerAsync, its own stream)
     std::vector<uint8_t> staged;
-    std::vector<std::array<void *, 2>> stage;
     static constexpr uint32_t kSlots = 2;
-    void *recv[kSlots] = {nullptr, nullptr};               // on device 0: [n_devices][tiles_padded * 64] records or texels
+    std::vector<std::array<vrt_ctx::Buf<uint8_t>, kSlots>> stage;   // [r][slot], on device r
+    vrt_ctx::Buf<uint8_t> recv[kSlots];                    // on device 0: [n_devices][tiles_padded * 64] records or texels
     size_t rank_stride = 0;                                // bytes between two devices' messages
-    hipEvent_t consumed[kSlots] = {nullptr, nullptr};      // device 0 has assembled the frame of this slot
+    vrt_ctx::Event consumed[kSlots];                       // device 0 has assembled the frame of this slot
     bool consumed_used[kSlots] = {false, false};
-    std::vector<std::array<hipEvent_t, kSlots>> done;      // [r][slot]: device r's message is complete
+    std::vector<std::array<vrt_ctx::Event, kSlots>> done;  // [r][slot]: device r's message is complete
     uint32_t slot = 0, in_flight = 2;
     bool last_was_stats = false;
     // The stream device 0's share of the current frame was enqueued on, published by the calling thread once its own vrt_render has

@@ -276,7 +276,7 @@ static int pick_frame_set(vrt_ctx *c, const vrt_render_opts &o, uint32_t variant
             f.counters = c->extra_counters[k];
             f.path_buf = &c->sz.extra_path[k];
         }
-        if (!c->extra_stream[k]) HIP_TRY(c, hipStreamCreateWithFlags(&c->extra_stream[k], hipStreamNonBlocking));
+        HIP_TRY(c, c->extra_stream[k].ensure());
         if (!bound && !c->sz.extra_out[k]) {
             const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
             HIP_TRY(c, c->sz.extra_out[k].once(bytes / sizeof(vrt::Texel)));
@@ -299,8 +299,8 @@ static int pick_frame_set(vrt_ctx *c, const vrt_render_opts &o, uint32_t variant
     return VRT_OK;
 }
 
-// The next free event quadruple of the pool (folding the pool into the accumulated times when it is full).
-static int next_events(vrt_ctx *c, std::array<hipEvent_t, 4> **ev, uint8_t **kind) {
+// The next free event quadruple of the pool (folding the pool into the accumulated times when it is full), as raw handles.
+static int next_events(vrt_ctx *c, std::array<hipEvent_t, 4> &ev, uint8_t **kind) {
     if (c->ev_used == c->ev_pool.size()) {
         // (512 frames of events: creating one costs the host a few microseconds, so a context is at full speed once it has
         // rendered that many frames between two vrt_get_stats calls; folding costs one drain per 512 frames)
@@ -308,15 +308,16 @@ static int next_events(vrt_ctx *c, std::array<hipEvent_t, 4> **ev, uint8_t **kin
             const int rc = fold_events(c, nullptr);
             if (rc) return rc;
         } else {
-            std::array<hipEvent_t, 4> t{nullptr, nullptr, nullptr, nullptr};
-            for (auto &e : t) HIP_TRY(c, hipEventCreate(&e));
-            c->ev_pool.push_back(t);
+            std::array<vrt_ctx::Event, 4> t;   // (joins the pool whole or not at all)
+            for (auto &e : t) HIP_TRY(c, e.ensure(hipEventDefault));
+            c->ev_pool.push_back(std::move(t));
             c->ev_kind.push_back(kEvNone);
         }
     }
     *kind = &c->ev_kind[c->ev_used];
     **kind = kEvNone;
-    *ev = &c->ev_pool[c->ev_used++];
+    const auto &t = c->ev_pool[c->ev_used++];
+    ev = {t[0], t[1], t[2], t[3]};
     return VRT_OK;
 }
 
@@ -365,7 +366,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
         HIP_TRY(c, c->sz.d_accum.once(bytes / sizeof(vrt::Texel)));
         if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.d_accum, bytes));
-        if (!c->ev_accum) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_accum, hipEventDisableTiming));
+        HIP_TRY(c, c->ev_accum.ensure());
     }
     // Only the steps that read and write the sum are ordered behind the previous accumulating frame's (it may be in flight on
     // another frame set's stream); this frame's launches before them overlap it
@@ -580,16 +581,16 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
 
     auto body = [&]() -> int {
         HIP_TRY(c, hipSetDevice(dev));
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        HIP_TRY(c, c->own_stream.ensure());
         c->stream = c->own_stream;
         HIP_TRY(c, c->d_nodes.once(c->max_nodes));
         // fresh buffer = zeros = every node an air leaf (client/src/world.rs:273-274)
         HIP_TRY(c, hipMemsetAsync(c->d_nodes, 0, (size_t)c->max_nodes * sizeof(uint16_t), c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // (uploads run on their own stream)
         // the upload path's fixtures now, not at the first edit (a mapped pinned allocation is tens of milliseconds)
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pool_upload, hipEventDisableTiming));
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_ring, vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs, hipHostMallocMapped));
+        HIP_TRY(c, c->up_stream.ensure());
+        HIP_TRY(c, c->ev_pool_upload.ensure());
+        HIP_TRY(c, c->h_ring.ensure(vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs));
         HIP_TRY(c, hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0));
         static_assert(sizeof c->h_mats == vrt::kMaterials * sizeof(vrt_material), "the emission table follows the 256 materials");
         static_assert(vrt_ctx::kMatsAlloc * sizeof(vrt_material) == sizeof c->h_mats + sizeof c->h_emission, "whole materials");
@@ -618,31 +619,13 @@ void vrt_destroy(vrt_ctx *c) {
     if (!c) return;
     if (c->grp) { grp_destroy(c); return; }
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    if (c->up_stream) (void)hipStreamSynchronize(c->up_stream);
-    for (hipStream_t st : c->extra_stream)
-        if (st) (void)hipStreamSynchronize(st);
-    if (c->ev_accum) (void)hipEventDestroy(c->ev_accum);
-    if (c->ev_query) (void)hipEventDestroy(c->ev_query);
-    for (auto &T : c->tabs)
-        if (T.ev_updated) (void)hipEventDestroy(T.ev_updated);
-    if (c->up_stream) { (void)hipStreamSynchronize(c->up_stream); (void)hipStreamDestroy(c->up_stream); }
-    if (c->ev_pool_upload) (void)hipEventDestroy(c->ev_pool_upload);
-    if (c->ev_walkers) (void)hipEventDestroy(c->ev_walkers);
-    if (c->h_ring) (void)hipHostFree(c->h_ring);
-    for (auto &evs : c->ring_ev)
-        for (auto ev : evs)
-            if (ev) (void)hipEventDestroy(ev);
-    if (c->ev_frames) (void)hipEventDestroy(c->ev_frames);
-    if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
-    for (auto &t : c->ev_pool)
-        for (auto &ev : t)
-            if (ev) (void)hipEventDestroy(ev);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    for (hipStream_t st : c->extra_stream)
-        if (st) (void)hipStreamDestroy(st);
-    delete c;   // the device buffers go with it: behind the waits above, the context's device current
+    // nothing is destroyed or freed under work that still uses it: every stream the context owns or was given, once
+    auto drain = [](hipStream_t st) { if (st) (void)hipStreamSynchronize(st); };
+    if (c->stream != c->own_stream) drain(c->stream);
+    drain(c->own_stream);
+    drain(c->up_stream);
+    for (hipStream_t st : c->extra_stream) drain(st);
+    delete c;   // the buffers, events, streams and the ring go with it: behind the waits above, the context's device current
 }
 
 const char *vrt_last_error(const vrt_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
@@ -846,7 +829,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     c->last_fused = fuse_present;
     c->last_has_texels = !(fuse_present && P.screen_only);
 
-    std::array<hipEvent_t, 4> *ev = nullptr;
+    std::array<hipEvent_t, 4> *ev = nullptr, pool_events;
     uint8_t *ev_kind = nullptr;
     static std::array<hipEvent_t, 4> no_events{nullptr, nullptr, nullptr, nullptr};
     static uint8_t no_kind = 0;
@@ -855,8 +838,9 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         ev_kind = &no_kind;
     } else {
         VRT_PROF(12, "  next_events");
-        rc = next_events(c, &ev, &ev_kind);
+        rc = next_events(c, pool_events, &ev_kind);
         if (rc) return rc;
+        ev = &pool_events;
     }
     // The frame is about to be enqueued on its stream: say so again.  pick_frame_set announced it, but what ran since may
     // have waited for the frames in flight and cleared the announcement with them — next_events folds the event pool every
@@ -1087,7 +1071,7 @@ int vrt_set_stream(vrt_ctx *c, void *hip_stream) {
     HIP_TRY(c, hipSetDevice(c->device));
     QUIESCE(c);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream.get();
     return VRT_OK;
 }
 

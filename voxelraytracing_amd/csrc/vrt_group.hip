@@ -5,19 +5,19 @@ static int grp_alloc_messages(vrt_ctx *c) {
     vrt_group *g = c->grp;
     vrt_ctx *root = g->dev[0];
     HIP_TRY(c, hipSetDevice(root->device));
-    for (auto &p : g->recv) { (void)hipFree(p); p = nullptr; }
     g->rank_stride = (size_t)root->tiles_padded * 64u * (g->texels ? 16u : 8u);
-    for (auto &p : g->recv) {
-        HIP_TRY(c, hipMalloc(&p, g->rank_stride * g->dev.size()));
-        HIP_TRY(c, hipMemset(p, 0, g->rank_stride * g->dev.size()));
+    for (auto &b : g->recv) {
+        b.release();
+        HIP_TRY(c, b.once(g->rank_stride * g->dev.size()));
+        HIP_TRY(c, hipMemset(b, 0, g->rank_stride * g->dev.size()));
     }
     for (size_t r = 1; r < g->dev.size(); r++) {
         if (!g->staged[r]) continue;
         HIP_TRY(c, hipSetDevice(g->dev[r]->device));
-        for (auto &p : g->stage[r]) {
-            (void)hipFree(p); p = nullptr;
-            HIP_TRY(c, hipMalloc(&p, g->rank_stride));
-            HIP_TRY(c, hipMemset(p, 0, g->rank_stride));
+        for (auto &b : g->stage[r]) {
+            b.release();
+            HIP_TRY(c, b.once(g->rank_stride));
+            HIP_TRY(c, hipMemset(b, 0, g->rank_stride));
         }
     }
     HIP_TRY(c, hipSetDevice(root->device));
@@ -40,7 +40,8 @@ int grp_create(const vrt_config *cfg, vrt_ctx **out) {
     g->texels = (cfg->flags & VRT_FLAG_TEXEL_MESSAGES) != 0u;
     g->poison = (cfg->flags & VRT_FLAG_POISON_MESSAGES) != 0u;
     g->staged.assign(n, (cfg->flags & VRT_FLAG_STAGED_MESSAGES) ? 1 : 0);
-    g->stage.assign(n, {nullptr, nullptr});
+    g->stage.resize(n);
+    g->done.resize(n);
     // the root's own tiles never cross a link, so it takes more of the frame; measured defaults
     const uint32_t w0 = cfg->shard_root_weight ? cfg->shard_root_weight : (n == 2u ? 4u : n <= 4u ? 3u : 2u);
     DeviceRestore restore;
@@ -59,7 +60,6 @@ int grp_create(const vrt_config *cfg, vrt_ctx **out) {
             g->dev.push_back(d);
         }
         g->dev[0]->whole_frame_owner = true;
-        g->done.resize(n);
         for (uint32_t r = 1; r < n; r++) {
             HIP_TRY(c, hipSetDevice(g->dev[r]->device));
             if (g->dev[r]->device != g->dev[0]->device && !g->staged[r]) {
@@ -68,10 +68,10 @@ int grp_create(const vrt_config *cfg, vrt_ctx **out) {
                 if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) g->staged[r] = 1;
                 (void)hipGetLastError();
             }
-            for (auto &ev : g->done[r]) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            for (auto &ev : g->done[r]) HIP_TRY(c, ev.ensure());
         }
         HIP_TRY(c, hipSetDevice(g->dev[0]->device));
-        for (auto &ev : g->consumed) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        for (auto &ev : g->consumed) HIP_TRY(c, ev.ensure());
         // issuing threads pay off when the devices are different ones: launches to one device serialise inside the
         // runtime whichever thread makes them (measured with device_ids = {0, ...}: 168 us of host time per frame for 8
         // contexts with workers, 145 without).  VRT_GROUP_THREADS=1 / 0 forces them on / off.
@@ -106,19 +106,15 @@ void grp_destroy(vrt_ctx *c) {
         (void)hipSetDevice(d->device);
         (void)vrt_synchronize(d);
     }
-    for (size_t r = 1; r < g->dev.size() && r < g->stage.size(); r++) {
+    for (size_t r = 1; r < g->dev.size(); r++) {   // what lives on device r, with device r current
         (void)hipSetDevice(g->dev[r]->device);
-        for (auto p : g->stage[r]) (void)hipFree(p);
+        g->stage[r] = {};
+        g->done[r] = {};
     }
     if (!g->dev.empty()) (void)hipSetDevice(g->dev[0]->device);
-    for (auto p : g->recv) (void)hipFree(p);
-    for (auto ev : g->consumed)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto &evs : g->done)
-        for (auto ev : evs)
-            if (ev) (void)hipEventDestroy(ev);
-    for (vrt_ctx *d : g->dev) vrt_destroy(d);
-    delete g;
+    const std::vector<vrt_ctx *> members = std::move(g->dev);
+    delete g;   // device 0's: the messages and their events, behind the synchronises above
+    for (vrt_ctx *d : members) vrt_destroy(d);
     delete c;
 }
 
@@ -199,8 +195,8 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
         VRT_PROF(1, " issue to a shard device");
         vrt_ctx *d = g->dev[r];
         if (hipSetDevice(d->device) != hipSuccess) return fail(d, VRT_ERR_DEVICE, "hipSetDevice(%d) failed", d->device);
-        void *slot = (uint8_t *)g->recv[k] + (size_t)r * g->rank_stride;
-        int rc = vrt_bind_output(d, g->staged[r] ? g->stage[r][k] : slot);
+        uint8_t *slot = g->recv[k] + (size_t)r * g->rank_stride;
+        int rc = vrt_bind_output(d, g->staged[r] ? g->stage[r][k].get() : slot);
         // the slot's previous message must have been consumed by device 0 before this frame overwrites it
         d->wait_before_frame = g->consumed_used[k] ? g->consumed[k] : nullptr;
         if (!rc) rc = vrt_render(d, &o);
@@ -266,7 +262,7 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
     // shade / scatter the other devices' messages into the frame the root has just rendered its own tiles into
     vrt::Texel *frame = root->last_out;
     if (g->texels) {
-        vrt::launch_assemble((const vrt::Texel *)g->recv[k], frame, root->width, root->tiles_x, root->tiles_total, root->shard_w0,
+        vrt::launch_assemble((const vrt::Texel *)g->recv[k].get(), frame, root->width, root->tiles_x, root->tiles_total, root->shard_w0,
                              root->shard_period, true, g->rank_stride / 16u, X);
     } else {
         vrt::FrameParams P;
@@ -277,7 +273,7 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
     }
     HIP_TRY(c, hipGetLastError());
     // (testing: a consumed slot holds nothing a later frame could pass for its own)
-    if (g->poison) HIP_TRY(c, hipMemsetAsync((uint8_t *)g->recv[k] + g->rank_stride, 0xFF, g->rank_stride * (n - 1u), X));
+    if (g->poison) HIP_TRY(c, hipMemsetAsync(g->recv[k] + g->rank_stride, 0xFF, g->rank_stride * (n - 1u), X));
     HIP_TRY(c, hipEventRecord(g->consumed[k], X));
     g->consumed_used[k] = true;
     g->prof.frames += 1u;

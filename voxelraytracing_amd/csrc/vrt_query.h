@@ -112,7 +112,7 @@ static int query_batch_host(vrt_ctx *c, const void *q, size_t q_bytes, void *out
                             int (*enqueue)(vrt_ctx *, const void *, uint32_t, void *)) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, c->d_query.grow(q_bytes + out_bytes));
-    if (!c->ev_query) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    HIP_TRY(c, c->ev_query.ensure());
     uint8_t *dq = c->d_query, *dout = dq + q_bytes;   // (both record sizes are multiples of 4)
     HIP_TRY(c, hipMemcpyAsync(dq, q, q_bytes, hipMemcpyHostToDevice, c->stream));
     const int rc = enqueue(c, dq, n, dout);

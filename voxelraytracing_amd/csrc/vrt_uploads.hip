@@ -44,7 +44,7 @@ int alloc_roots(vrt_ctx *c, uint32_t world_size) {
 int order_after_frames(vrt_ctx *c, hipStream_t target) {
     auto wait_for = [&](hipStream_t st) -> int {
         if (!st || st == target) return VRT_OK;
-        if (!c->ev_frames) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_frames, hipEventDisableTiming));
+        HIP_TRY(c, c->ev_frames.ensure());
         HIP_TRY(c, hipEventRecord(c->ev_frames, st));
         HIP_TRY(c, hipStreamWaitEvent(target, c->ev_frames, 0));
         return VRT_OK;
@@ -59,7 +59,7 @@ int order_after_frames(vrt_ctx *c) { return order_after_frames(c, c->stream); }
 
 // Everything enqueued on c->stream so far (an upload, a table rebuild) happens before later frames on other streams.
 int publish_upload(vrt_ctx *c) {
-    if (!c->ev_upload) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming));
+    HIP_TRY(c, c->ev_upload.ensure());
     HIP_TRY(c, hipEventRecord(c->ev_upload, c->stream));
     c->upload_gen += 1;
     return VRT_OK;
@@ -95,10 +95,6 @@ int frame_waits_for_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot) {
 // segment (the initial pool upload) take the synchronous route.
 // `bytes` of the pinned ring (64-byte aligned), valid until the segment comes round again (eight segments on)
 static int ring_place(vrt_ctx *c, size_t bytes, size_t *at) {
-    if (!c->h_ring) {
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_ring, vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs, hipHostMallocMapped));
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0));
-    }
     const size_t need = (bytes + 63u) & ~(size_t)63u;
     if (c->ring_off + need > vrt_ctx::kRingSegBytes) {
         const uint32_t next = (c->ring_seg + 1u) % vrt_ctx::kRingSegs;
@@ -111,19 +107,18 @@ static int ring_place(vrt_ctx *c, size_t bytes, size_t *at) {
         c->ring_seg = next;
         c->ring_off = 0;
         // the segment's previous copies must have left it (seven segments ago: practically always long done)
-        for (int k = 0; k < 2; k++)
-            if (c->ring_ev_used[c->ring_seg][k]) HIP_TRY(c, hipEventSynchronize(c->ring_ev[c->ring_seg][k]));
+        for (auto &ev : c->ring_ev[c->ring_seg])
+            if (ev) HIP_TRY(c, hipEventSynchronize(ev));
     }
     *at = (size_t)c->ring_seg * vrt_ctx::kRingSegBytes + c->ring_off;
     c->ring_off += need;
     return VRT_OK;
 }
 
-// The node-pool / chunk_roots uploads staged so far, as one launch on the upload stream: behind the readers of those two
-// buffers (whole-world builds and the other uploads so far, every table set's last update — those that are not over yet: a
-// wait is a barrier packet on the stream, a query is a load; every frame only if one that walks the octree is in flight).
-int flush_staged(vrt_ctx *c) {
-    if (c->staged.empty()) return VRT_OK;
+// The upload stream waits for the readers of the node pool and chunk_roots: whole-world builds and the other uploads so far,
+// every table set's last update — those that are not over yet: a wait is a barrier packet on the stream, a query is a load;
+// every frame only if one that walks the octree is in flight.
+static int upload_waits_for_pool_readers(vrt_ctx *c) {
     hipStream_t st = c->up_stream;
     if (c->ev_upload && hipEventQuery(c->ev_upload) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_upload, 0));
     for (auto &T : c->tabs)
@@ -132,8 +127,15 @@ int flush_staged(vrt_ctx *c) {
             else HIP_TRY(c, hipStreamWaitEvent(st, T.ev_updated, 0));
         }
     (void)hipGetLastError();   // (hipErrorNotReady from the queries is not an error)
-    if (c->walkers_in_flight) {
-        const int rc = order_after_frames(c, st);
+    return c->walkers_in_flight ? order_after_frames(c, st) : VRT_OK;
+}
+
+// The node-pool / chunk_roots uploads staged so far, as one launch on the upload stream, behind the readers of those two buffers.
+int flush_staged(vrt_ctx *c) {
+    if (c->staged.empty()) return VRT_OK;
+    hipStream_t st = c->up_stream;
+    {
+        const int rc = upload_waits_for_pool_readers(c);
         if (rc) return rc;
     }
     vrt::UploadBatch batch;
@@ -153,10 +155,8 @@ int flush_staged(vrt_ctx *c) {
     if (n) { const int rc = launch(); if (rc) return rc; }
     for (uint32_t k = 0; k < vrt_ctx::kRingSegs; k++)
         if (c->staged_seg[k]) {
-            hipEvent_t &rev = c->ring_ev[k][1];
-            if (!rev) HIP_TRY(c, hipEventCreateWithFlags(&rev, hipEventDisableTiming));
-            HIP_TRY(c, hipEventRecord(rev, st));
-            c->ring_ev_used[k][1] = true;
+            HIP_TRY(c, c->ring_ev[k][1].ensure());
+            HIP_TRY(c, hipEventRecord(c->ring_ev[k][1], st));
             c->staged_seg[k] = false;
         }
     c->staged.clear();
@@ -223,30 +223,15 @@ int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes, bool pool
     if (bytes == 0) return VRT_OK;
     hipStream_t st = c->stream;
     if (pool) {
-        if (!c->up_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->up_stream, hipStreamNonBlocking));
-        if (!c->ev_pool_upload) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pool_upload, hipEventDisableTiming));
         st = c->up_stream;
         const bool is_roots = dst >= (void *)c->d_roots && dst < (void *)(c->d_roots + c->n_roots);
         if (bytes <= vrt_ctx::kRingSegBytes && !(bytes & 3u) && !((uintptr_t)dst & 3u))
             return stage_pool_upload(c, is_roots ? 1u : 0u,
                                      (uint32_t)(((uintptr_t)dst - (uintptr_t)(is_roots ? (void *)c->d_roots : (void *)c->d_nodes)) / 4u), src, bytes);
-        {   // (the whole pool at join time: the synchronous route below, behind what is staged)
-            const int rc = flush_staged(c);
-            if (rc) return rc;
-        }
-        // whole-world builds and the other uploads so far, every set's last update — those that are not over yet (a wait is
-        // a barrier packet on the stream, a query is a load)
-        if (c->ev_upload && hipEventQuery(c->ev_upload) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_upload, 0));
-        for (auto &T : c->tabs)
-            if (T.update_pending) {
-                if (hipEventQuery(T.ev_updated) == hipSuccess) T.update_pending = false;
-                else HIP_TRY(c, hipStreamWaitEvent(st, T.ev_updated, 0));
-            }
-        (void)hipGetLastError();   // (hipErrorNotReady from the queries is not an error)
-        if (c->walkers_in_flight) {
-            const int rc = order_after_frames(c, st);
-            if (rc) return rc;
-        }
+        // (the whole pool at join time: the synchronous route below, behind what is staged and the pool's readers)
+        int rc = flush_staged(c);
+        if (!rc) rc = upload_waits_for_pool_readers(c);
+        if (rc) return rc;
     } else {
         const int rc = order_after_frames(c);
         if (rc) return rc;
@@ -270,11 +255,9 @@ int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes, bool pool
     memcpy(c->h_ring + at, src, bytes);
     vrt::launch_upload_words(dst, c->d_ring + at, (uint32_t)(bytes / 4u), st);
     HIP_TRY(c, hipGetLastError());
-    const size_t seg = at / vrt_ctx::kRingSegBytes;
-    hipEvent_t &rev = c->ring_ev[seg][pool ? 1 : 0];
-    if (!rev) HIP_TRY(c, hipEventCreateWithFlags(&rev, hipEventDisableTiming));
+    vrt_ctx::Event &rev = c->ring_ev[at / vrt_ctx::kRingSegBytes][pool ? 1 : 0];
+    HIP_TRY(c, rev.ensure());
     HIP_TRY(c, hipEventRecord(rev, st));
-    c->ring_ev_used[seg][pool ? 1 : 0] = true;
     return publish();
 }
 
@@ -444,9 +427,9 @@ int ensure_accel_world(vrt_ctx *c) {
     HIP_TRY(c, A.d_chunk_caps.grow(n_chunks));
     HIP_TRY(c, c->d_brick_total.once(2));   // [0] bricks, [1] march-cell blocks
     HIP_TRY(c, A.d_brick_tail.once(1));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(c, hipEventCreate(&e0));
-    HIP_TRY(c, hipEventCreate(&e1));
+    vrt_ctx::Event e0, e1;   // (timing enabled: the build's time is vrt_accel_info.last_build_ms)
+    HIP_TRY(c, e0.ensure(hipEventDefault));
+    HIP_TRY(c, e1.ensure(hipEventDefault));
     const bool direct = S <= c->march_direct_max_s;
     c->march_direct = direct;
     auto body = [&]() -> int {
@@ -504,8 +487,6 @@ int ensure_accel_world(vrt_ctx *c) {
         return publish_upload(c);
     };
     const int rc = body();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (rc) c->accel_dirty = true;
     return rc;
 }
@@ -550,7 +531,7 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
         const uint32_t end = nx != c->roots_index.end() ? nx->first : c->max_nodes;
         extents[i] = r ? (end > r ? end - r : 0u) : 1u;   // (a missing chunk is node 0 alone: one air leaf)
     }
-    if (!T.ev_updated) HIP_TRY(c, hipEventCreateWithFlags(&T.ev_updated, hipEventDisableTiming));
+    HIP_TRY(c, T.ev_updated.ensure());
     // (the next upload of nodes or roots waits for this reader: ev_updated is the completion signal of the launch itself — a
     // record behind it is one more packet between the rebuild and the frame that waits for it)
     vrt::launch_accel_chunks(c->d_nodes, c->max_nodes, c->d_roots, c->accel_S, T.d_grid, T.d_chunk_bricks, T.d_chunk_bases, T.d_chunk_caps,
