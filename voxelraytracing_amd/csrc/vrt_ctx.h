@@ -19,7 +19,7 @@
 // 16-byte texel {r,g,b f32, id u32} per pixel slot, hit buffer 16 B per local pixel.
 // Ownership: every device allocation of a context is a vrt_ctx::Buf (vrt_devbuf.h), every event, stream and pinned allocation a
 // vrt_ctx::Event / Stream / Pinned (vrt_handle.h, made where first used: ensure()); all go with the context, and so do a group's
-// with the group.  Raw pointers and handles are aliases or the caller's: stream, last_stream, wait_before_frame, screen_stream[],
+// with the group.  Raw pointers and handles are aliases or the caller's: stream, last.stream, wait_before_frame, screen_stream[],
 // d_ring.  What depends on the output size is vrt_ctx::Sized: a resize assigns it an empty value.
 #include <hip/hip_runtime.h>
 
@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "vrt_devbuf.h"
+#include "vrt_frame_plan.h"
 #include "vrt_handle.h"
 #include "vrt_device.h"
 #include "vrt_exp.h"
@@ -153,7 +154,6 @@ struct vrt_ctx {
     using Stream = vrt::Handle<vrt::HipStream>;
     using Pinned = vrt::Handle<vrt::HipPinned>;
     vrt_group *grp = nullptr;   // a multi-device context (vrt_config.n_devices > 1): everything else below is unused, see vrt_group
-    hipStream_t last_stream = nullptr;  // the stream the most recent frame was enqueued on
     hipEvent_t wait_before_frame = nullptr;  // set by a multi-device context: the next frame's stream waits for it first (its message slot is free)
     int device = 0;
     Stream own_stream;
@@ -193,8 +193,17 @@ struct vrt_ctx {
     Buf<uint32_t> d_roots;
     Buf<vrt_material> d_mats;       // the 256 materials, then the 256 floats of the emission table (vrt::emission_table): kMatsAlloc
     vrt::Texel *d_out = nullptr;    // where frames are written: sz.own_out or caller-bound memory
-    vrt::Texel *last_out = nullptr;  // the buffer holding the most recent frame
-    uint32_t *last_blk = nullptr;
+    // What the last frame was, for the calls that read it back or present it.  vrt_render assigns it whole once the frame is
+    // enqueued: a call that returns an error leaves the record of the frame before it.  alloc_output, vrt_bind_output and the
+    // presentation blit change single fields.
+    struct LastFrame {
+        vrt::Texel *out = nullptr;     // the buffer holding the frame
+        uint32_t *blk = nullptr, n_counts = 0;   // its launched-ray counts, and how many of them a primary + shadow frame wrote
+        hipStream_t stream = nullptr;  // the stream it was enqueued on
+        uint32_t slot = 0, tab = 0, mode = 0, spp = 1;   // its frame set and its table set
+        // it stored the window's image itself (vrt_set_presentation), and texels at all (not with VRT_PRESENT_SKIP_TEXELS); opts.stats == 1
+        bool fused = false, has_texels = true, stats = false;
+    } last;
     // What a resize drops (alloc_output assigns an empty Sized, then makes own_out, d_hits and d_blk_counts again): every buffer
     // sized by the output, made on first use, and what is only true of their contents.
     struct Sized {
@@ -218,7 +227,6 @@ struct vrt_ctx {
         uint32_t *dn_last_guide = nullptr;          // the guide of the last denoised frame (one of dn_guide)
     } sz;
     uint32_t n_blocks = 0;
-    uint32_t n_counts = 0;          // entries of blk_counts the last primary + shadow frame wrote
     Buf<unsigned long long> d_counters;  // [kCtrCount] stats, then the hit-segment counters
     uint32_t hit_seg_cap = 0;       // records per hit segment: what the kernels are given (d_hits holds kHitSegments of them)
     Buf<unsigned long long> d_clock;  // clock-probe frames: {s_memtime ticks, s_memrealtime ticks}, summed until vrt_get_stats
@@ -310,20 +318,18 @@ struct vrt_ctx {
     bool one_to_one = false;
     // vrt_set_presentation: the declared crosshair / window / flags; whether frames of (pres_for_w x pres_for_h) can store their own
     // window pixels (found once per size and declaration) and the crosshair's box; which frame sets' screen buffers hold the
-    // image their last frame stored itself; whether the last frame stored one, and whether it stored texels at all
+    // image their last frame stored itself (whether the last frame stored one, and texels at all: last.fused, last.has_texels)
     bool pres_on = false;
     vrt_crosshair pres_ch{};
     uint32_t pres_w = 0, pres_h = 0, pres_flags = 0;
     uint32_t pres_for_w = 0, pres_for_h = 0, pres_box[4] = {0, 0, 0, 0};
     bool pres_fusable = false;
-    bool last_fused = false, last_has_texels = true;
     uint32_t ordered_frames = 0;        // frames launched in an order (vrt_accel_info.ordered_frames)
     bool order_dilated = false;         // the order in d_tile_order is a dilated one
     uint32_t cam_gen = 0, order_cam_gen = 0;   // counts the changes of the camera (each is a change of the view too)
     vrt_cam_data order_cam{};           // the camera of the frame the order was made from
     bool tile_order_stale = false;      // a chunk was edited since the order was made: still used, made again by the next frame without an edit in front of it
     uint32_t frame_mode = ~0u;          // vrt_mode of the last frame rendered (a change of mode is a change of view)
-    uint32_t last_slot = 0, last_tab = 0;   // the frame set and the table set of the last frame
     float accel_last_ms = 0.f;
     uint64_t roots_tag = 0;         // vrt_write_chunk_roots_tagged: the caller's tag of the table as last written (0: none)
     uint32_t roots_tag_offset = 0, roots_tag_n = 0;
@@ -400,7 +406,6 @@ struct vrt_ctx {
     double prof_render_us = 0.0;
     uint32_t prof_frames = 0;
 
-    uint32_t last_spp = 1;
     // VRT_RENDER_ACCUMULATE: the running sum is sz.d_accum (one texel per slot, never divided; allocated by the first accumulating
     // frame, dropped by alloc_output); the samples in it and their seed, whether the next accumulating frame starts again at 0,
     // and the event behind the last step that wrote the sum (the next frame's first step that touches it waits for it)
@@ -412,8 +417,6 @@ struct vrt_ctx {
     // guide words are sz.dn_scratch / sz.dn_guide
     vrt_denoise_opts denoise{};
     bool rendered = false;
-    bool last_stats = false;
-    uint32_t last_mode = 0;
     bool timing_pending = false;
     vrt_stats stats;
 
@@ -466,16 +469,27 @@ struct DeviceRestore {
     ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
 
-VRT_HIDDEN int quiesce(vrt_ctx *c);   // wait for the frames that may still be running on the context's other streams
-#define QUIESCE(c)                     \
+#define VRT_TRY(call)                  \
     do {                               \
-        const int q_ = quiesce(c);     \
-        if (q_) return q_;             \
+        const int rc_ = (call);        \
+        if (rc_) return rc_;           \
     } while (0)
+VRT_HIDDEN int quiesce(vrt_ctx *c);   // wait for the frames that may still be running on the context's other streams
+#define QUIESCE(c) VRT_TRY(quiesce(c))
 
 // vrt_frames.hip
 VRT_HIDDEN bool ragged_output(const vrt_ctx *c);
 VRT_HIDDEN hipError_t zero_now(vrt_ctx *c, void *p, size_t bytes);
+inline size_t frame_slots(const vrt_ctx *c) { return c->slots ? c->slots : 1; }   // what a buffer of one element per pixel slot holds (an empty shard: one)
+// A buffer that is read as a whole frame, of at least n elements: zero from its allocation on where the output is not whole tiles
+// (ragged_output).  Every caller but the path trace's sample planes asks for the same n until a resize drops the buffer: made once.
+template <typename T>
+inline int frame_buf(vrt_ctx *c, vrt_ctx::Buf<T> &buf, size_t n) {
+    if (n <= buf.cap()) return VRT_OK;
+    HIP_TRY(c, buf.grow(n));
+    if (ragged_output(c)) HIP_TRY(c, zero_now(c, buf.get(), n * sizeof(T)));
+    return VRT_OK;
+}
 VRT_HIDDEN int validate_frame(vrt_ctx *c);
 VRT_HIDDEN int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from);
 VRT_HIDDEN int ensure_ndc(vrt_ctx *c);
@@ -485,12 +499,11 @@ VRT_HIDDEN bool presentation_fusable(vrt_ctx *c);
 VRT_HIDDEN int screen_buffer_for_frame(vrt_ctx *c, uint32_t slot, hipStream_t st, uint32_t screen_w, uint32_t screen_h);
 // vrt_order.hip: the order a one-frame-at-a-time context launches its tiles in, around the frame's launch in vrt_render
 struct TileOrderPlan { bool sort = false, dilate = false; };
-VRT_HIDDEN int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, const vrt_render_opts &o, uint32_t variant, bool kstats,
-                                       bool edit_in_front, TileOrderPlan &plan);
+VRT_HIDDEN int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, const vrt::FramePlan &plan, bool edit_in_front, TileOrderPlan &order);
 VRT_HIDDEN int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st, const TileOrderPlan &plan);
 // vrt_denoise.hip: around a path frame's launches in vrt_render (vrt_set_denoise)
 VRT_HIDDEN int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::Texel **trace_into);
-VRT_HIDDEN int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
+VRT_HIDDEN int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, const vrt::FramePlan &plan, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
                                    hipEvent_t closing);
 // vrt_uploads.hip
 VRT_HIDDEN int alloc_roots(vrt_ctx *c, uint32_t world_size);

@@ -166,25 +166,19 @@ int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::
     *trace_into = frame_out;
     if (!c->denoise.passes || !c->tiles_total) return VRT_OK;
     const size_t n = (size_t)c->width * c->height;
-    if (!c->sz.dn_scratch[slot]) {
-        HIP_TRY(c, c->sz.dn_scratch[slot].once(n));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.dn_scratch[slot], n * sizeof(vrt::Texel)));
-    }
-    if (!c->sz.dn_guide[slot]) {
-        HIP_TRY(c, c->sz.dn_guide[slot].once(n));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.dn_guide[slot], n * sizeof(uint32_t)));   // (beyond the traced area: 0)
-    }
+    VRT_TRY(frame_buf(c, c->sz.dn_scratch[slot], n));
+    VRT_TRY(frame_buf(c, c->sz.dn_guide[slot], n));   // (beyond the traced area: 0)
     if (c->denoise.passes & 1u) *trace_into = c->sz.dn_scratch[slot];
     return VRT_OK;
 }
 
 // Behind the frame's last path launch on its stream: the guide words, then the passes; then, for a timed frame, its closing
 // event once more (launch_path_frame recorded it behind the trace), so that the frame's time holds the filter.
-int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, bool literal, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
+int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, const vrt::FramePlan &plan, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
                         hipEvent_t closing) {
     const uint32_t passes = c->denoise.passes;
     if (!passes || !c->tiles_total) return VRT_OK;
-    vrt::launch_denoise_guide(P, literal, c->sz.dn_guide[slot], st);
+    vrt::launch_denoise_guide(P, plan.literal, c->sz.dn_guide[slot], st);
     HIP_TRY(c, hipGetLastError());
     vrt::Texel *a = (passes & 1u) ? c->sz.dn_scratch[slot] : frame_out, *b = (passes & 1u) ? frame_out : c->sz.dn_scratch[slot];
     for (uint32_t i = 0; i < passes; i++) {

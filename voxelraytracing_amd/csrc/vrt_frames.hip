@@ -62,7 +62,7 @@ static int alloc_output(vrt_ctx *c) {
     c->sz = vrt_ctx::Sized{};   // everything of the old size goes (the callers have waited for the frames in flight)
     c->accum_restart = true;
     layout_tiles(c);
-    const size_t n = c->slots ? c->slots : 1;
+    const size_t n = frame_slots(c);
     HIP_TRY(c, c->sz.own_out.once(n));
     // hit buffer: kHitSegments segments, each able to hold every record its workgroups can produce
     const uint32_t nblocks = (c->tiles_local + 3u) / 4u;
@@ -80,11 +80,9 @@ static int alloc_output(vrt_ctx *c) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // the extra (stream, output, counts) sets of frames in flight are created when first used (vrt_render)
     c->d_out = c->sz.own_out;  // a resize drops any caller-bound output (its size no longer matches)
-    c->last_out = c->sz.own_out;
-    c->last_blk = c->sz.d_blk_counts;
+    c->last.out = c->sz.own_out; c->last.blk = c->sz.d_blk_counts;
+    c->last.fused = false; c->last.has_texels = true;
     c->rendered = false;
-    c->last_fused = false;
-    c->last_has_texels = true;
     return VRT_OK;
 }
 
@@ -113,8 +111,7 @@ int ensure_ndc(vrt_ctx *c) {
     volatile float px = c->cam.proj_size[0], py = c->cam.proj_size[1];
     for (uint32_t i = 0; i < c->width; i++) { volatile float q = ((float)(int)i * 2.0f) / px; t[i] = q - 1.0f; }
     for (uint32_t i = 0; i < c->height; i++) { volatile float q = ((float)(int)i * 2.0f) / py; t[c->width + i] = q - 1.0f; }
-    const int rc = stage_upload(c, c->d_ndc, t.data(), t.size() * sizeof(float));
-    if (rc) return rc;
+    VRT_TRY(stage_upload(c, c->d_ndc, t.data(), t.size() * sizeof(float)));
     c->ndc_w = c->width;
     c->ndc_h = c->height;
     memcpy(c->ndc_proj, c->cam.proj_size, sizeof c->ndc_proj);
@@ -251,49 +248,35 @@ struct FrameSet {
     unsigned long long *counters;
 };
 
-// Two (or more) frames in flight: plain frames — one launch, or the path trace's chain of launches — alternate between
-// the context's sets; anything else (stats, the two-launch variants, a caller's stream or bound buffer without
-// VRT_RENDER_OWN_STREAMS) waits for them and runs alone on c->stream.
-static int pick_frame_set(vrt_ctx *c, const vrt_render_opts &o, uint32_t variant, bool kstats, FrameSet &f) {
-    const bool chain = o.mode == VRT_MODE_PRIMARY || (o.mode == VRT_MODE_PRIMARY_SHADOW && (variant == 0u || (variant == 2u && c->compact))) ||
-                       o.mode == VRT_MODE_PATH;
-    // VRT_RENDER_OWN_STREAMS: the caller set a stream and / or bound an output but lets this frame run on the context's own
-    // streams (nothing on the caller's stream consumes it before a synchronise; frames in flight are bound to different
-    // buffers) — the gather root's own tiles in bench.py
-    const bool own_streams = (o.flags & VRT_RENDER_OWN_STREAMS) != 0u;
-    const bool pipelined = c->in_flight > 1u && chain && !kstats && (own_streams || (c->stream == c->own_stream && c->d_out == c->sz.own_out));
+// A pipelined frame (vrt_frame_plan.h) takes the next of the context's sets in turn; any other waits for the frames in flight
+// and runs alone on c->stream.
+static int pick_frame_set(vrt_ctx *c, const vrt::FramePlan &plan, FrameSet &f) {
     const bool bound = c->d_out != c->sz.own_out;
     f = FrameSet{0u, c->stream, c->d_out, c->sz.d_blk_counts, &c->sz.d_path, c->d_counters};
-    if (!pipelined) {
+    if (!plan.pipelined) {
         QUIESCE(c);
         return VRT_OK;
     }
     if (c->flip) {
         const uint32_t k = c->flip - 1u;
         f.slot = k + 1u;
-        if (o.mode == VRT_MODE_PATH) {
+        if (plan.path) {
             HIP_TRY(c, c->extra_counters[k].once(kCounterWords));
             f.counters = c->extra_counters[k];
             f.path_buf = &c->sz.extra_path[k];
         }
         HIP_TRY(c, c->extra_stream[k].ensure());
-        if (!bound && !c->sz.extra_out[k]) {
-            const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
-            HIP_TRY(c, c->sz.extra_out[k].once(bytes / sizeof(vrt::Texel)));
-            if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.extra_out[k], bytes));   // texels no workgroup covers stay zero (main.rs:452)
-        }
+        if (!bound) VRT_TRY(frame_buf(c, c->sz.extra_out[k], frame_slots(c)));   // texels no workgroup covers stay zero (main.rs:452)
         HIP_TRY(c, c->sz.extra_blk[k].once(c->tiles_local ? c->tiles_local : 1));
         f.st = c->extra_stream[k];
         f.blk = c->sz.extra_blk[k];
         if (!bound) f.out = c->sz.extra_out[k];  // a bound output is the caller's buffer for this very frame
         c->alt_pending = true;
-        const int rc = frame_waits_for_uploads(c, f.st, k + 1u);
-        if (rc) return rc;
+        VRT_TRY(frame_waits_for_uploads(c, f.st, k + 1u));
     } else if (c->stream != c->own_stream) {
         f.st = c->own_stream;
         c->own_pending = true;
-        const int rc = frame_waits_for_uploads(c, f.st, 0u);
-        if (rc) return rc;
+        VRT_TRY(frame_waits_for_uploads(c, f.st, 0u));
     }
     c->flip = (c->flip + 1u) % c->in_flight;
     return VRT_OK;
@@ -305,8 +288,7 @@ static int next_events(vrt_ctx *c, std::array<hipEvent_t, 4> &ev, uint8_t **kind
         // (512 frames of events: creating one costs the host a few microseconds, so a context is at full speed once it has
         // rendered that many frames between two vrt_get_stats calls; folding costs one drain per 512 frames)
         if (c->ev_pool.size() >= 512) {
-            const int rc = fold_events(c, nullptr);
-            if (rc) return rc;
+            VRT_TRY(fold_events(c, nullptr));
         } else {
             std::array<vrt_ctx::Event, 4> t;   // (joins the pool whole or not at all)
             for (auto &e : t) HIP_TRY(c, e.ensure(hipEventDefault));
@@ -337,8 +319,9 @@ int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from) {
 
 // Wavefront path trace: per sample one launch per bounce over the compacted live-path buffer.  accum: an accumulating frame
 // (VRT_RENDER_ACCUMULATE) with accum_from samples in the context's sum before it.
-static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt_render_opts &o, bool kstats, bool literal,
+static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt_render_opts &o, const vrt::FramePlan &plan,
                              bool accum, uint32_t accum_from, std::array<hipEvent_t, 4> &ev, uint8_t &ev_kind) {
+    const bool kstats = plan.kstats, literal = plan.literal;
     const uint32_t spp = o.spp ? o.spp : 1u, bounces = c->settings.max_ray_bounces;
     // Several samples per launch chain (plain frames, spp > 1): every launch of the chain carries `samples` times the rays —
     // 2.7 rays per lane are not enough to cover a bounce launch's tail — and a frame of 16 spp is 4 x 4
@@ -358,14 +341,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     // two sets of three record planes (+ two of per-ray state for experiments/vrt_path_window.hip's launch); grows only, and
     // hipFree waits for whatever still uses the old one
     HIP_TRY(c, f.path_buf->grow((2 * 3 + (vrt::g_exp.path_bounce_window ? 2 : 0)) * cap));
-    if ((planes || own_sum) && c->sz.path_acc[f.slot].cap() < (size_t)samples * c->slots) {
-        HIP_TRY(c, c->sz.path_acc[f.slot].grow((size_t)samples * c->slots));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.path_acc[f.slot], (size_t)samples * c->slots * sizeof(vrt::Texel)));
-    }
-    if (accum && !c->sz.d_accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
-        const size_t bytes = (size_t)(c->slots ? c->slots : 1) * sizeof(vrt::Texel);
-        HIP_TRY(c, c->sz.d_accum.once(bytes / sizeof(vrt::Texel)));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.d_accum, bytes));
+    if (planes || own_sum) VRT_TRY(frame_buf(c, c->sz.path_acc[f.slot], (size_t)samples * c->slots));   // (grows with the samples of a chain)
+    if (accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
+        VRT_TRY(frame_buf(c, c->sz.d_accum, frame_slots(c)));
         HIP_TRY(c, c->ev_accum.ensure());
     }
     // Only the steps that read and write the sum are ordered behind the previous accumulating frame's (it may be in flight on
@@ -446,10 +424,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             HIP_TRY(c, hipGetLastError());
             if (first) { if (timed) HIP_TRY(c, hipEventRecord(ev[1], f.st)); first = false; }
         }
-        if (accum) {
-            const int rc = sum_step();
-            if (rc) return rc;
-        }
+        if (accum) VRT_TRY(sum_step());
         if (planes) {
             if (accum) vrt::launch_path_chain_finish(c->sz.d_accum, frame_out, c->sz.path_acc[f.slot], c->slots, P.chain, accum_from + smp == 0u,
                                                      smp + P.chain >= spp, accum_count, f.st);
@@ -477,26 +452,19 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         HIP_TRY(c, hipEventRecord(ev[3], f.st));
         ev_kind = kEvRecorded;
     }
-    c->last_spp = spp;
     return VRT_OK;
 }
 
-// Primary (+ shadow) rays: one launch (variant 0, 4; primary only) or two (variants 1-3).
-static int launch_march_frame(vrt_ctx *c, const vrt::FrameParams &P, const FrameSet &f, bool shadow, uint32_t variant, bool kstats,
-                              std::array<hipEvent_t, 4> &ev, uint8_t &ev_kind) {
+// Primary (+ shadow) rays: one launch (plan.one_launch) or two.
+static int launch_march_frame(vrt_ctx *c, const vrt::FrameParams &P, const FrameSet &f, const vrt::FramePlan &plan, std::array<hipEvent_t, 4> &ev,
+                              uint8_t &ev_kind) {
     if (!c->tiles_local) return VRT_OK;  // an empty shard
-    const uint32_t march = variant == 3u ? 0u : variant;  // variant 3 = the grid march in two launches
-    // primary + shadow in one launch: the default march, and — on a context whose pixel slots are 8-byte records — the
-    // octree walk it falls back to when the world is too large for the derived tables (the two-launch kernels store and
-    // re-read 16-byte texels, which such a buffer has no room for)
-    const bool fused = shadow && (variant == 0u || (variant == 2u && c->compact));
-    c->n_counts = fused ? c->tiles_local : c->n_blocks;
-    if (fused) vrt::launch_primary_shadow_fused(P, march, kstats, f.st, ev[0], ev[1]);
-    else vrt::launch_primary(P, march, kstats, shadow, f.st, ev[0], ev[1]);
+    if (plan.shadow && plan.one_launch) vrt::launch_primary_shadow_fused(P, plan.march, plan.kstats, f.st, ev[0], ev[1]);
+    else vrt::launch_primary(P, plan.march, plan.kstats, plan.shadow, f.st, ev[0], ev[1]);
     HIP_TRY(c, hipGetLastError());
     if (ev[0]) ev_kind = kEvOneKernel;
-    if (shadow && !fused) {
-        vrt::launch_shadow(P, march, kstats, f.st, ev[2], ev[3]);
+    if (!plan.one_launch) {
+        vrt::launch_shadow(P, plan.march, plan.kstats, f.st, ev[2], ev[3]);
         HIP_TRY(c, hipGetLastError());
         if (ev[0]) ev_kind = kEvTwoKernels;
     }
@@ -598,10 +566,8 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, sizeof c->h_mats + sizeof c->h_emission, c->stream));
         HIP_TRY(c, c->d_counters.once(kCounterWords));
         HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, kCounterBytes, c->stream));
-        int r = alloc_roots(c, cfg->world_size_chunks);
-        if (r) return r;
-        r = alloc_output(c);
-        if (r) return r;
+        VRT_TRY(alloc_roots(c, cfg->world_size_chunks));
+        VRT_TRY(alloc_output(c));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return VRT_OK;
     };
@@ -679,8 +645,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             c->prof_frames += 1u;
         }
     } issue_clock{c};
-    vrt_render_opts o;
-    memset(&o, 0, sizeof o);
+    vrt_render_opts o{};
     if (opts) o = *opts;
     if (o.mode > VRT_MODE_PATH) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: mode %u not supported", o.mode);
     if (o.mode == VRT_MODE_PATH && o.variant != 0) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: the path trace has one kernel variant");
@@ -690,72 +655,53 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (!vrt::variant_supported(o.variant)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_render: unknown kernel variant %u", o.variant);
     const bool accum = (o.flags & VRT_RENDER_ACCUMULATE) != 0u;
     uint32_t accum_from = 0;
-    {
-        const int rc_ = accum_frame_start(c, o, &accum_from);
-        if (rc_) return rc_;
-    }
-    int rc;
+    VRT_TRY(accum_frame_start(c, o, &accum_from));
     {
         VRT_PROF(7, "  validate + hipSetDevice");
-        rc = validate_frame(c);
-        if (rc) return rc;
+        VRT_TRY(validate_frame(c));
         HIP_TRY(c, hipSetDevice(c->device));
     }
-
-    if (c->compact && (o.mode == VRT_MODE_PATH || (o.variant != 0u && o.variant != 2u) || c->settings.show_step_count == 1u))
+    if (c->compact && (o.mode == VRT_MODE_PATH || !vrt::one_launch_march(o.variant, c->compact) || c->settings.show_step_count == 1u))
         return fail(c, VRT_ERR_STATE, "vrt_render: a VRT_FLAG_COMPACT context renders primary(+shadow) frames with the default march "
                     "only (no path trace, step-count view, literal or two-launch variants)");
-    if (o.stats == 1u && !c->sz.d_steps) {
-        HIP_TRY(c, c->sz.d_steps.once(c->slots ? c->slots : 1));
-        if (ragged_output(c)) HIP_TRY(c, zero_now(c, c->sz.d_steps, (size_t)(c->slots ? c->slots : 1) * sizeof(uint32_t)));
-    }
+    if (o.stats == 1u) VRT_TRY(frame_buf(c, c->sz.d_steps, frame_slots(c)));
     if (o.stats == 2u && !c->d_clock) {
         HIP_TRY(c, c->d_clock.once(2));
         HIP_TRY(c, hipMemsetAsync(c->d_clock, 0, 2 * sizeof(unsigned long long), c->stream));
-        const int rc2 = publish_upload(c);
-        if (rc2) return rc2;
+        VRT_TRY(publish_upload(c));
     }
     {
         VRT_PROF(8, "  ensure_ndc");
-        rc = ensure_ndc(c);
-        if (rc) return rc;
+        VRT_TRY(ensure_ndc(c));
     }
-    uint32_t variant = o.variant;
-    // The fast marches never ask whether *air* is liquid (ray_tracer.wgsl:226 asks for every voxel, voxel 0 included): a
-    // material table that flags voxel 0 as liquid — nothing the reference's data packs do — is traced by the literal march.
-    const bool air_liquid = c->h_mats[0].is_liquid == 1u;
-    if (air_liquid) {
-        if (c->compact)
-            return fail(c, VRT_ERR_STATE, "vrt_render: materials[0].is_liquid == 1 (air flagged liquid) is traced by the literal march only");
-        variant = 1u;
-    }
-    if (variant == 0u || variant == 3u || (o.mode == VRT_MODE_PATH && !air_liquid)) {
-        VRT_PROF(9, "  ensure_accel_world");
-        rc = ensure_accel_world(c);
-        if (rc) return rc;
-        if (!c->accel_ok && (variant == 0u || variant == 3u)) variant = 2u;  // world too large for the tables: walk the octree
-    }
-    // per-lane iteration counts exist in the STATS kernels only; the step-count debug view (F2 in the reference,
-    // main.rs:368-370) needs them, so it runs those kernels too
-    const bool kstats = o.stats == 1u || c->settings.show_step_count == 1u;
 
+    // ---- plan: what kind of frame this is (vrt_frame_plan.h), decided before anything of it is enqueued ----
+    vrt::FrameFacts F;
+    F.mode = o.mode; F.variant = o.variant; F.stats = o.stats; F.flags = o.flags;
+    F.compact = c->compact; F.show_step_count = c->settings.show_step_count == 1u; F.air_liquid = c->h_mats[0].is_liquid == 1u;
+    if (F.air_liquid && c->compact)
+        return fail(c, VRT_ERR_STATE, "vrt_render: materials[0].is_liquid == 1 (air flagged liquid) is traced by the literal march only");
+    if (vrt::asks_for_tables(F)) {
+        VRT_PROF(9, "  ensure_accel_world");
+        VRT_TRY(ensure_accel_world(c));
+    }
+    F.accel_ok = c->accel_ok; F.in_flight = c->in_flight; F.tiles_local = c->tiles_local;
+    F.caller_stream = c->stream != c->own_stream; F.output_bound = c->d_out != c->sz.own_out; F.present_fusable = presentation_fusable(c);
+    const vrt::FramePlan plan = vrt::plan_frame(F);
+
+    // ---- enqueue.  What is in flight is announced ahead of the launches it speaks of (own_pending, alt_pending, shared_readers_in_flight,
+    // walkers_in_flight) and stays announced if the call fails further down: that costs a wait, the opposite a race.  No part of the record. ----
     FrameSet f;
     {
         VRT_PROF(10, "  pick_frame_set (+ its upload waits)");
-        rc = pick_frame_set(c, o, variant, kstats, f);
-        if (rc) return rc;
+        VRT_TRY(pick_frame_set(c, plan, f));
     }
-    c->last_out = f.out;
-    c->last_blk = f.blk;
-    c->last_stream = f.st;
-    c->last_slot = f.slot;
     if (c->wait_before_frame) {
         HIP_TRY(c, hipStreamWaitEvent(f.st, c->wait_before_frame, 0));
         c->wait_before_frame = nullptr;
     }
 
     // this frame's table set, brought up to date on its own stream (which waits for the uploads so far first)
-    const bool wants_tables = variant == 0u || variant == 3u || (o.mode == VRT_MODE_PATH && !air_liquid);
     constexpr uint32_t kQuietFrames = 64;
     if (c->tables_split && ++c->quiet_frames > kQuietFrames && c->tabs[0].dirty_chunks.empty()) {
         c->tables_split = false;   // no edit for a while: everybody reads tabs[0] again; the other sets go stale
@@ -764,22 +710,16 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     const uint32_t tab = c->tables_split ? f.slot : 0u;
     const vrt_ctx::Tables &T = c->tabs[tab];
     const bool edit_in_front = !T.dirty_chunks.empty();   // this frame brings an edited chunk's tables up to date first
-    c->last_tab = tab;
     // a frame of another frame set that reads the shared set: an edit's update of tabs[0] must wait for it (update_tables)
-    const bool shares = wants_tables && c->accel_ok && tab == 0u && f.slot != 0u;
-    if (wants_tables && c->accel_ok) {
+    const bool shares = plan.tables && tab == 0u && f.slot != 0u;
+    {
         VRT_PROF(11, "  frame_waits_for_uploads + update_tables");
-        rc = frame_waits_for_uploads(c, f.st, f.slot);
-        if (rc) return rc;
-        rc = update_tables(c, tab, f.st);
-        if (rc) return rc;
-        if (tab == 0u && f.slot != 0u) {   // the shared set from another frame set's stream: behind its last update
-            if (c->tabs[0].update_pending && f.st != c->stream) HIP_TRY(c, hipStreamWaitEvent(f.st, c->tabs[0].ev_updated, 0));
-            c->shared_readers_in_flight = true;
-        }
-    } else {
-        rc = frame_waits_for_uploads(c, f.st, f.slot);   // (a frame on c->stream too: the node pool's uploads have their own stream)
-        if (rc) return rc;
+        VRT_TRY(frame_waits_for_uploads(c, f.st, f.slot));   // (a frame on c->stream too: the node pool's uploads have their own stream)
+        if (plan.tables) VRT_TRY(update_tables(c, tab, f.st));
+    }
+    if (shares) {   // the shared set from another frame set's stream: behind its last update
+        if (c->tabs[0].update_pending && f.st != c->stream) HIP_TRY(c, hipStreamWaitEvent(f.st, c->tabs[0].ev_updated, 0));
+        c->shared_readers_in_flight = true;
     }
 
     vrt::FrameParams P;
@@ -787,7 +727,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     P.nodes = c->d_nodes;
     P.roots = c->d_roots;
     P.mats = c->d_mats;
-    if (wants_tables && c->accel_ok && c->accel_S == c->world.size_in_chunks && !c->accel_dirty && T.live && T.dirty_chunks.empty() && !air_liquid) {
+    if (plan.tables && c->accel_S == c->world.size_in_chunks && !c->accel_dirty && T.live && T.dirty_chunks.empty()) {
         P.grid = T.d_grid;
         P.bricks = T.d_bricks;
         P.grid_dim = c->accel_S * 8u;
@@ -803,8 +743,8 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             P.march_direct = c->march_direct ? 1u : 0u;
         }
     }
-    // a march that walks the octree reads the node pool and chunk_roots: uploads then wait for the frames in flight
-    if (!P.grid || variant == 1u || variant == 2u) c->walkers_in_flight = true;
+    // what reads the node pool and chunk_roots: uploads then wait for the frames in flight
+    if (!P.grid || plan.walks_octree) c->walkers_in_flight = true;
     P.out = f.out;
     P.hits = c->sz.d_hits;
     P.blk_counts = f.blk;
@@ -814,33 +754,20 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     P.steps = o.stats == 1u ? c->sz.d_steps : nullptr;
     P.clock = o.stats == 2u ? c->d_clock : nullptr;
     fill_uniforms(c, P);
-    // vrt_set_presentation: a frame whose kernel finishes its pixels through store_pixel (every primary-only frame; primary + shadow
-    // in one launch) and whose window samples texel for texel also stores the window's image, into its frame set's screen buffer
-    const bool one_launch_shadow = o.mode == VRT_MODE_PRIMARY_SHADOW && (variant == 0u || (variant == 2u && c->compact));
-    const bool fuse_present = (o.mode == VRT_MODE_PRIMARY || one_launch_shadow) && c->tiles_local && presentation_fusable(c);
-    if (fuse_present) {
-        rc = screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height);
-        if (rc) return rc;
+    if (plan.fuse_present) {
+        VRT_TRY(screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height));
         P.screen = reinterpret_cast<uint32_t *>(c->d_screen[f.slot].get());
         P.screen_only = (c->pres_flags & VRT_PRESENT_SKIP_TEXELS) ? 1u : 0u;
         memcpy(P.present_box, c->pres_box, sizeof P.present_box);
         P.crosshair = c->pres_ch;
     }
-    c->last_fused = fuse_present;
-    c->last_has_texels = !(fuse_present && P.screen_only);
 
-    std::array<hipEvent_t, 4> *ev = nullptr, pool_events;
-    uint8_t *ev_kind = nullptr;
-    static std::array<hipEvent_t, 4> no_events{nullptr, nullptr, nullptr, nullptr};
-    static uint8_t no_kind = 0;
-    if (c->timing_every > 1u && (c->frame_no++ % c->timing_every) != 0u && !kstats && !(o.flags & VRT_RENDER_TIMED)) {
-        ev = &no_events;   // an untimed frame: the launches carry no events (vrt_stats' kernel times average the timed ones)
-        ev_kind = &no_kind;
-    } else {
+    // an untimed frame: the launches carry no events (vrt_stats' kernel times average the timed ones)
+    std::array<hipEvent_t, 4> ev{nullptr, nullptr, nullptr, nullptr};
+    uint8_t no_kind = kEvNone, *ev_kind = &no_kind;
+    if (!(c->timing_every > 1u && (c->frame_no++ % c->timing_every) != 0u && !plan.kstats && !(o.flags & VRT_RENDER_TIMED))) {
         VRT_PROF(12, "  next_events");
-        rc = next_events(c, pool_events, &ev_kind);
-        if (rc) return rc;
-        ev = &pool_events;
+        VRT_TRY(next_events(c, ev, &ev_kind));
     }
     // The frame is about to be enqueued on its stream: say so again.  pick_frame_set announced it, but what ran since may
     // have waited for the frames in flight and cleared the announcement with them — next_events folds the event pool every
@@ -856,23 +783,22 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     if (shares) c->shared_readers_in_flight = true;
     // the order this frame's tiles are launched in, and whether it notes its trips for an order to come (vrt_order.hip)
     TileOrderPlan order_plan;
-    rc = tile_order_before_frame(c, P, f.st, o, variant, kstats, edit_in_front, order_plan);
-    if (rc) return rc;
+    VRT_TRY(tile_order_before_frame(c, P, f.st, plan, edit_in_front, order_plan));
     // the counters feed stats frames and the path trace's segment cursors; a plain primary(+shadow) frame reads none
-    if (kstats || o.mode == VRT_MODE_PATH) HIP_TRY(c, hipMemsetAsync(f.counters, 0, kCounterBytes, f.st));
+    if (plan.kstats || plan.path) HIP_TRY(c, hipMemsetAsync(f.counters, 0, kCounterBytes, f.st));
     {
         VRT_PROF(13, "  the launch(es)");
-        if (o.mode == VRT_MODE_PATH) {
+        int rc;
+        if (plan.path) {
             // vrt_set_denoise: a frame of an odd number of passes is traced into its scratch frame (the last pass lands in f.out)
             FrameSet ft = f;
-            rc = denoise_before_frame(c, f.slot, f.out, &ft.out);
-            if (rc) return rc;
+            VRT_TRY(denoise_before_frame(c, f.slot, f.out, &ft.out));
             P.out = ft.out;
-            rc = launch_path_frame(c, P, ft, o, kstats, air_liquid, accum, accum_from, *ev, *ev_kind);
+            rc = launch_path_frame(c, P, ft, o, plan, accum, accum_from, ev, *ev_kind);
             // (a timed frame's closing event is recorded again behind the filter: vrt_stats and VRT_RENDER_TIMED time it with its passes)
-            if (!rc) rc = denoise_after_frame(c, P, air_liquid, f.slot, f.st, f.out, (*ev)[3]);
+            if (!rc) rc = denoise_after_frame(c, P, plan, f.slot, f.st, f.out, ev[3]);
         }
-        else rc = launch_march_frame(c, P, f, o.mode == VRT_MODE_PRIMARY_SHADOW, variant, kstats, *ev, *ev_kind);
+        else rc = launch_march_frame(c, P, f, plan, ev, *ev_kind);
         if (rc) {
             if (accum) c->accum_restart = true;   // (what the sum holds is not known)
             return rc;
@@ -883,12 +809,13 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         c->accum_seed = o.seed;
         c->accum_restart = false;
     }
-    rc = tile_order_after_frame(c, P, f.st, order_plan);   // (the sort behind the frame that noted its trips)
-    if (rc) return rc;
+    VRT_TRY(tile_order_after_frame(c, P, f.st, order_plan));   // (the sort behind the frame that noted its trips)
+
+    // ---- record: the frame is enqueued; from here on the read-backs, the presentation and the statistics speak of it ----
+    c->last = vrt_ctx::LastFrame{f.out, f.blk, plan.counts_per_tile ? c->tiles_local : c->n_blocks, f.st, f.slot, tab, o.mode, o.spp ? o.spp : 1u,
+                                 plan.fuse_present, !(plan.fuse_present && P.screen_only), o.stats == 1u};
     c->rendered = true;
     c->flushed_at_call = false;   // (the next frame's first staged range may go out at its call again: vrt_uploads.hip)
-    c->last_stats = o.stats == 1u;
-    c->last_mode = o.mode;
     c->timing_pending = true;
     return VRT_OK;
 }
@@ -913,10 +840,7 @@ int vrt_synchronize(vrt_ctx *c) {
     if (!c) return VRT_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     QUIESCE(c);
-    {
-        const int rc = flush_staged(c);
-        if (rc) return rc;
-    }
+    VRT_TRY(flush_staged(c));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->up_stream) HIP_TRY(c, hipStreamSynchronize(c->up_stream));
     c->walkers_in_flight = false;   // nothing is in flight any more
@@ -930,21 +854,21 @@ int vrt_read_output(vrt_ctx *c, float *rgb, uint32_t *ids, uint8_t *rgba8) {
     if (!c) return VRT_ERR_INVALID_ARG;
     if (!c->rendered) return fail(c, VRT_ERR_STATE, "vrt_read_output: nothing rendered yet");
     if (c->compact) return fail(c, VRT_ERR_STATE, "vrt_read_output: a VRT_FLAG_COMPACT context holds 8-byte records, not texels (vrt_assemble_compact shades them)");
-    if (!c->last_has_texels) return fail(c, VRT_ERR_STATE, "vrt_read_output: the last frame stored its window pixels only (vrt_set_presentation with VRT_PRESENT_SKIP_TEXELS)");
+    if (!c->last.has_texels) return fail(c, VRT_ERR_STATE, "vrt_read_output: the last frame stored its window pixels only (vrt_set_presentation with VRT_PRESENT_SKIP_TEXELS)");
     HIP_TRY(c, hipSetDevice(c->device));
     QUIESCE(c);
     const size_t npix = (size_t)c->width * c->height;
     if (rgba8) {
         if (c->tile_major) return fail(c, VRT_ERR_STATE, "vrt_read_output: rgba8 readback needs the row-major (unsharded) layout");
         HIP_TRY(c, c->sz.d_rgba8.once(npix * 4));
-        vrt::launch_quantize(c->last_out, c->sz.d_rgba8, c->width, c->height, c->stream);
+        vrt::launch_quantize(c->last.out, c->sz.d_rgba8, c->width, c->height, c->stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(rgba8, c->sz.d_rgba8, npix * 4, hipMemcpyDeviceToHost, c->stream));
     }
     std::vector<vrt::Texel> t;
     if (rgb || ids) {
         t.resize(c->slots);
-        HIP_TRY(c, hipMemcpyAsync(t.data(), c->last_out, t.size() * sizeof(vrt::Texel), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(t.data(), c->last.out, t.size() * sizeof(vrt::Texel), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!rgb && !ids) return VRT_OK;
@@ -970,7 +894,7 @@ int vrt_read_output(vrt_ctx *c, float *rgb, uint32_t *ids, uint8_t *rgba8) {
 int vrt_read_steps(vrt_ctx *c, uint32_t *steps) {
     GRP_REFUSE(c, "vrt_read_steps");
     if (!c || !steps) return fail(c, VRT_ERR_INVALID_ARG, "vrt_read_steps: null argument");
-    if (!c->rendered || !c->last_stats || !c->sz.d_steps)
+    if (!c->rendered || !c->last.stats || !c->sz.d_steps)
         return fail(c, VRT_ERR_STATE, "vrt_read_steps: the last frame was not rendered with opts.stats = 1");
     if (c->tile_major) return fail(c, VRT_ERR_STATE, "vrt_read_steps: needs the row-major (unsharded) layout");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -986,27 +910,24 @@ int vrt_get_stats(vrt_ctx *c, vrt_stats *out) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->timing_pending) {
         float last[3] = {0, 0, 0};
-        int rc = fold_events(c, last);
-        if (rc) return rc;
+        VRT_TRY(fold_events(c, last));
         std::vector<unsigned long long> hbuf(kCounterBytes / sizeof(unsigned long long));
         HIP_TRY(c, hipMemcpyAsync(hbuf.data(), c->d_counters, kCounterBytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         unsigned long long *h = hbuf.data();
-        const uint32_t *seg = reinterpret_cast<const uint32_t *>(h + vrt::kCtrCount);
         unsigned long long launched = 0;
-        if (c->last_mode == VRT_MODE_PRIMARY_SHADOW && c->n_counts) {
-            std::vector<uint32_t> bc(c->n_counts);
-            HIP_TRY(c, hipMemcpyAsync(bc.data(), c->last_blk, bc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (c->last.mode == VRT_MODE_PRIMARY_SHADOW && c->last.n_counts) {
+            std::vector<uint32_t> bc(c->last.n_counts);
+            HIP_TRY(c, hipMemcpyAsync(bc.data(), c->last.blk, bc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             for (uint32_t v : bc) launched += v;
         }
-        (void)seg;
         vrt_stats s;
         memset(&s, 0, sizeof s);
-        s.primary_rays = (uint64_t)c->tiles_local * 64u * (c->last_mode == VRT_MODE_PATH ? c->last_spp : 1u);
-        s.secondary_rays = c->last_mode == VRT_MODE_PRIMARY_SHADOW ? launched : 0;
-        if (c->last_mode == VRT_MODE_PATH && c->last_stats) s.secondary_rays = h[vrt::kCtrSecondary];
-        if (c->last_stats) {
+        s.primary_rays = (uint64_t)c->tiles_local * 64u * (c->last.mode == VRT_MODE_PATH ? c->last.spp : 1u);
+        s.secondary_rays = c->last.mode == VRT_MODE_PRIMARY_SHADOW ? launched : 0;
+        if (c->last.mode == VRT_MODE_PATH && c->last.stats) s.secondary_rays = h[vrt::kCtrSecondary];
+        if (c->last.stats) {
             s.hits = h[vrt::kCtrHits];
             s.steps = h[vrt::kCtrSteps];
             s.node_visits = h[vrt::kCtrVisits];
@@ -1082,7 +1003,7 @@ int vrt_bind_output(vrt_ctx *c, void *texels) {
     // stream-ordered: launches capture the pointer, so frames already enqueued keep writing where they were
     // told to and the next vrt_render uses the new buffer (lets a host ping-pong two gather messages)
     c->d_out = texels ? (vrt::Texel *)texels : c->sz.own_out;
-    c->last_out = c->d_out;
+    c->last.out = c->d_out;
     c->rendered = false;
     return VRT_OK;
 }
@@ -1090,7 +1011,7 @@ int vrt_bind_output(vrt_ctx *c, void *texels) {
 int vrt_device_output(vrt_ctx *c, void **texels, uint64_t *bytes) {
     GRP_ROOT(c, vrt_device_output(d, texels, bytes));
     if (!c) return VRT_ERR_INVALID_ARG;
-    if (texels) *texels = c->d_out == c->sz.own_out ? c->last_out : c->d_out;  // own buffers: the one holding the last frame
+    if (texels) *texels = c->d_out == c->sz.own_out ? c->last.out : c->d_out;  // own buffers: the one holding the last frame
     if (bytes) *bytes = (uint64_t)c->slots * (c->compact ? 8u : sizeof(vrt::Texel));
     return VRT_OK;
 }

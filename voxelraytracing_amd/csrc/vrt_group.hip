@@ -204,10 +204,10 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
         if (rc) return rc;
         // (a staged message: behind the frame on its stream — which waited for the slot to be consumed — over to device 0)
         if (d->tiles_local && g->staged[r] &&
-            hipMemcpyPeerAsync(slot, root->device, g->stage[r][k], d->device, g->rank_stride, d->last_stream) != hipSuccess)
+            hipMemcpyPeerAsync(slot, root->device, g->stage[r][k], d->device, g->rank_stride, d->last.stream) != hipSuccess)
             return fail(d, VRT_ERR_DEVICE, "hipMemcpyPeerAsync from device %d to device %d failed", d->device, root->device);
         VRT_PROF(2, "  record done");
-        if (d->tiles_local && hipEventRecord(g->done[r][k], d->last_stream) != hipSuccess)
+        if (d->tiles_local && hipEventRecord(g->done[r][k], d->last.stream) != hipSuccess)
             return fail(d, VRT_ERR_DEVICE, "hipEventRecord failed on device %d", d->device);
         if (threaded) {
             // this thread, not the caller, tells device 0's frame stream to wait for this message — once the caller has enqueued
@@ -236,7 +236,7 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
     const auto t_root = std::chrono::steady_clock::now();
     int rc = hipSetDevice(root->device) == hipSuccess ? VRT_OK : fail(root, VRT_ERR_DEVICE, "hipSetDevice(%d) failed", root->device);
     if (!rc) rc = vrt_render(root, &o);
-    hipStream_t X = root->last_stream ? root->last_stream : root->stream;
+    hipStream_t X = root->last.stream ? root->last.stream : root->stream;
     g->frame_stream.store(rc ? vrt_group::no_frame_stream() : X, std::memory_order_release);   // (the issuing threads go on from here)
     const double root_us = us_since(t_root);
     const auto t_join = std::chrono::steady_clock::now();
@@ -260,7 +260,7 @@ static int grp_render_frame(vrt_ctx *c, const vrt_render_opts *opts, bool &issue
             if (g->dev[r]->tiles_local) HIP_TRY(c, hipStreamWaitEvent(X, g->done[r][k], 0));
     const double waits_us = threaded ? 0.0 : us_since(t_tail);
     // shade / scatter the other devices' messages into the frame the root has just rendered its own tiles into
-    vrt::Texel *frame = root->last_out;
+    vrt::Texel *frame = root->last.out;
     if (g->texels) {
         vrt::launch_assemble((const vrt::Texel *)g->recv[k].get(), frame, root->width, root->tiles_x, root->tiles_total, root->shard_w0,
                              root->shard_period, true, g->rank_stride / 16u, X);

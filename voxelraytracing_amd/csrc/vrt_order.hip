@@ -45,16 +45,14 @@ static HoldLimits hold_limits(const vrt_cam_data &cam, uint32_t width, uint32_t 
 
 // Ahead of the frame's launch: which order it launches in (P.tile_order), whether it notes its trips (P.tile_cost), and what
 // tile_order_after_frame is to do with them.
-int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, const vrt_render_opts &o, uint32_t variant, bool kstats, bool edit_in_front,
-                            TileOrderPlan &plan) {
-    // longest tiles first: the one-launch primary + shadow kernel over the derived tables, plain frames, one frame at a time
-    // on the context's own stream (a frame, the sort behind it and the next frame are then ordered by the stream alone)
-    const bool lpt = c->tile_lpt && c->in_flight == 1u && st == c->stream && (o.mode == VRT_MODE_PRIMARY_SHADOW || o.mode == VRT_MODE_PRIMARY) && variant == 0u && !kstats &&
-                     o.stats == 0u && P.grid && c->tiles_local >= 128u;
+int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, const vrt::FramePlan &plan, bool edit_in_front, TileOrderPlan &order) {
+    // longest tiles first: the one-launch primary + shadow kernel over the derived tables, plain frames (plan.orderable), one frame
+    // at a time on the context's own stream (a frame, the sort behind it and the next frame are then ordered by the stream alone)
+    const bool lpt = c->tile_lpt && c->in_flight == 1u && st == c->stream && plan.orderable && P.grid && c->tiles_local >= 128u;
     bool tile_sort = false, dilate = false;
     // (a tile's trips depend on the mode too — a primary-only frame has no shadow march: an order made from the other
     // mode's frame is a stale order, and the frame before a sort must be of the same kind)
-    if (c->frame_mode != o.mode) c->view_gen++;
+    if (c->frame_mode != plan.mode) c->view_gen++;
     if (lpt) {
         if (!c->sz.d_tile_scratch) {   // (the last of the three; a resize drops them)
             const uint32_t chunks = (c->tiles_local + 63u) / 64u;
@@ -92,9 +90,9 @@ int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, con
         if (tile_sort) P.tile_cost = c->sz.d_tile_cost;
     }
     c->frame_view_gen = c->view_gen;
-    c->frame_mode = o.mode;
-    plan.sort = tile_sort;
-    plan.dilate = dilate;
+    c->frame_mode = plan.mode;
+    order.sort = tile_sort;
+    order.dilate = dilate;
     return VRT_OK;
 }
 

@@ -111,20 +111,19 @@ static int present_on_device(vrt_ctx *c, const vrt_crosshair *crosshair, uint32_
     if (screen_w == 0u || screen_h == 0u || (uint64_t)screen_w * screen_h > (1ull << 28))
         return fail(c, VRT_ERR_INVALID_ARG, "%s: screen %ux%u out of range", who, screen_w, screen_h);
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t st = c->last_stream ? c->last_stream : c->stream;
-    const uint32_t k = c->last_slot < vrt_ctx::kMaxInFlight ? c->last_slot : 0u;
+    hipStream_t st = c->last.stream ? c->last.stream : c->stream;
+    const uint32_t k = c->last.slot < vrt_ctx::kMaxInFlight ? c->last.slot : 0u;
     // the frame stored the window's image itself (vrt_set_presentation): it is there — or on its way, on the frame's stream
-    if (c->last_fused && screen_w == c->pres_w && screen_h == c->pres_h && memcmp(crosshair, &c->pres_ch, sizeof *crosshair) == 0) {
+    if (c->last.fused && screen_w == c->pres_w && screen_h == c->pres_h && memcmp(crosshair, &c->pres_ch, sizeof *crosshair) == 0) {
         *screen = c->d_screen[k];
         *stream = st;
         return VRT_OK;
     }
-    if (!c->last_has_texels)
+    if (!c->last.has_texels)
         return fail(c, VRT_ERR_STATE, "%s: the last frame stored its window pixels only (VRT_PRESENT_SKIP_TEXELS): it can be presented with the declared "
                     "crosshair and size, nothing else", who);
-    int rc = screen_buffer_for_frame(c, k, st, screen_w, screen_h);
-    if (rc) return rc;
-    c->last_fused = false;   // (the buffer now holds this blit; asked again with the declared crosshair, the frame is blitted again)
+    VRT_TRY(screen_buffer_for_frame(c, k, st, screen_w, screen_h));
+    c->last.fused = false;   // (the buffer now holds this blit; asked again with the declared crosshair, the frame is blitted again)
     // a window of the texture's size: is every pixel's sample its own texel's centre?  (found once per size, below)
     if (screen_w == c->width && screen_h == c->height && (c->one_w != screen_w || c->one_h != screen_h)) {
         c->one_to_one = present_is_one_to_one(screen_w, screen_h);
@@ -133,7 +132,7 @@ static int present_on_device(vrt_ctx *c, const vrt_crosshair *crosshair, uint32_
     const bool one = screen_w == c->width && screen_h == c->height && c->one_to_one;
     uint32_t box[4];
     crosshair_box(crosshair, screen_w, screen_h, box);
-    vrt::launch_present(c->last_out, c->width, c->height, screen_w, screen_h, *crosshair, c->d_screen[k], one, box, st);
+    vrt::launch_present(c->last.out, c->width, c->height, screen_w, screen_h, *crosshair, c->d_screen[k], one, box, st);
     HIP_TRY(c, hipGetLastError());
     *screen = c->d_screen[k];
     *stream = st;
@@ -148,8 +147,7 @@ int vrt_present(vrt_ctx *c, const vrt_crosshair *crosshair, uint32_t screen_w, u
     if (!c || !crosshair || !rgba8) return fail(c, VRT_ERR_INVALID_ARG, "vrt_present: null argument");
     uint8_t *screen = nullptr;
     hipStream_t st = nullptr;
-    const int rc = present_on_device(c, crosshair, screen_w, screen_h, "vrt_present", &screen, &st);
-    if (rc) return rc;
+    VRT_TRY(present_on_device(c, crosshair, screen_w, screen_h, "vrt_present", &screen, &st));
     HIP_TRY(c, hipMemcpyAsync(rgba8, screen, (size_t)screen_w * screen_h * 4u, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return VRT_OK;
@@ -161,8 +159,7 @@ int vrt_present_device(vrt_ctx *c, const vrt_crosshair *crosshair, uint32_t scre
     if (!c || !crosshair || !rgba8_device) return fail(c, VRT_ERR_INVALID_ARG, "vrt_present_device: null argument");
     uint8_t *screen = nullptr;
     hipStream_t st = nullptr;
-    const int rc = present_on_device(c, crosshair, screen_w, screen_h, "vrt_present_device", &screen, &st);
-    if (rc) return rc;
+    VRT_TRY(present_on_device(c, crosshair, screen_w, screen_h, "vrt_present_device", &screen, &st));
     *rgba8_device = screen;
     if (bytes) *bytes = (uint64_t)screen_w * screen_h * 4u;
     return VRT_OK;
@@ -207,11 +204,9 @@ int vrt_assemble_compact(vrt_ctx *c, const void *gathered, uint64_t rank_stride_
     if (!(c->shard_count > 1u && !c->tile_major))
         return fail(c, VRT_ERR_STATE, "vrt_assemble_compact: the gather root must be a VRT_FLAG_ROW_MAJOR shard context (it shades the "
                     "other ranks' records with its own uniforms and has its own tiles in the frame already)");
-    int rc = validate_frame(c);
-    if (rc) return rc;
+    VRT_TRY(validate_frame(c));
     HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_ndc(c);
-    if (rc) return rc;
+    VRT_TRY(ensure_ndc(c));
     vrt::FrameParams P;
     memset(&P, 0, sizeof P);
     P.mats = c->d_mats;

@@ -210,8 +210,8 @@ static int stage_pool_upload(vrt_ctx *c, uint32_t buf, uint32_t dst_word, const 
     // ONE range per frame goes out like that.  A burst — chunks arriving at a join, main.rs:289-295: hundreds of ranges before one
     // frame — outlasts the frames in flight, and from then on every call found the device idle and launched its own copy:
     // 1.5 us per call became 6 (256 uploads per frame: 2.0 ms per frame, tools/stream_burst.py); the rest of a burst is batched.
-    if (c->flushed_at_call || !c->rendered || !c->last_stream) return VRT_OK;
-    if (hipStreamQuery(c->last_stream) == hipSuccess) {
+    if (c->flushed_at_call || !c->rendered || !c->last.stream) return VRT_OK;
+    if (hipStreamQuery(c->last.stream) == hipSuccess) {
         c->flushed_at_call = true;   // (until the next vrt_render)
         return flush_staged(c);
     }
@@ -688,7 +688,7 @@ int vrt_get_accel_info(vrt_ctx *c, vrt_accel_info *out) {
     memset(out, 0, sizeof *out);
     HIP_TRY(c, hipSetDevice(c->device));
     // (as of the table set the last frame used; the other sets catch up when their frame set renders next)
-    const vrt_ctx::Tables &L = c->tabs[c->last_tab];
+    const vrt_ctx::Tables &L = c->tabs[c->last.tab];
     const bool up_to_date = c->accel_ok && !c->accel_dirty && L.live && L.dirty_chunks.empty();
     out->available = up_to_date ? 1u : 0u;
     out->world_size_chunks = c->accel_S;
