@@ -50,7 +50,7 @@ def test_the_emissive_kernels_are_built_apart_from_the_plain_ones():
     regs = _ffi.kernel_registers()
     emissive_cells = {k: v for k, v in regs.items() if "path_emissive_cells_kernel" in k}
     assert len(emissive_cells) == 3 and all(v["vgprs"] <= 64 for v in emissive_cells.values()), emissive_cells
-    # <MARCH, LDS_ROOTS, STATS, (MULTI, GROUPED,) EMIT = true>: the ten march forms each, + the primary's chained one
+    # <MARCH, LDS_ROOTS, STATS, (MULTI,) EMIT = true>: the ten march forms each, + the primary's chained one
     assert sum(1 for k in regs if re.search(r"path_primary_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 11
     assert sum(1 for k in regs if re.search(r"path_bounce_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 10
     bad = {k: v for k, v in regs.items() if "emissive" in k and (v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"])}

@@ -1,5 +1,5 @@
 """The routes a frame can take through vrt_render (csrc/vrt_frame_plan.h: one launch or two, the fallback to the octree walk, frames
-in flight, stats frames, the path trace's chains) on the small C1 world: at 128 x 64 — 128 tiles, the smallest frame at which the
+in flight, stats frames, the path trace's chains and every schedule of its launches) on the small C1 world: at 128 x 64 — 128 tiles, the smallest frame at which the
 tile order engages — and at 44 x 20, which is not whole tiles, so every buffer that is read as a whole frame must start out zero.
 The route is observable through vrt_get_stats: a timed frame planned as one launch has no second kernel time.  Every frame is
 held to the oracle's.  A vrt_render that refuses its arguments leaves the frame before it readable."""
@@ -19,8 +19,8 @@ ROUTES = [(mode, variant) for mode in (MODE_PRIMARY, MODE_PRIMARY_SHADOW) for va
 SEED = 11
 
 
-def _path_settings():
-    return g.make_settings(sun_pos=scenes.SUN_POS, max_ray_bounces=2)
+def _path_settings(bounces=2):
+    return g.make_settings(sun_pos=scenes.SUN_POS, max_ray_bounces=bounces)
 
 
 @pytest.fixture(scope="module")
@@ -146,6 +146,69 @@ def test_path_frames_plain_and_accumulating(refs, size, in_flight):
     check(4, "2 + 2 spp accumulated")
     assert gpu.accumulation() == (4, SEED)
     assert gpu.stats().primary_rays == cw * ch * 2
+    gpu.close()
+
+
+PATH_BOUNCES = (0, 1, 2, 3, 5)   # the memset alone; no bounce launch; a cells launch of one segment; the three cursor sets past one turn
+PATH_SPP = (1, 3, 5)
+# what selects another schedule of a path-traced frame's launches (vrt_frame_plan.h: plan_path): the context's switches (read when
+# the context is made), a stats frame, the same samples accumulated over two frames
+PATH_ROUTES = {"default": {}, "pool off": {"VRT_PATH_POOL": "0"}, "cells off": {"VRT_PATH_CELLS": "0"},
+               "1 sample per chain": {"VRT_PATH_SAMPLES_PER_CHAIN": "1"}, "2 samples per chain": {"VRT_PATH_SAMPLES_PER_CHAIN": "2"},
+               "stats": {}, "accumulated": {}}
+ACCUMULATED_IN = {1: (1,), 3: (1, 2), 5: (2, 3)}   # the frames whose samples make up the oracle's frame of 1, 3 and 5
+
+
+@pytest.fixture(scope="module")
+def path_refs(orc):
+    """The oracle's path-traced frames, once: [size, bounces, spp] = (rgb, ids)."""
+    out = {}
+    for size in SIZES:
+        sc = scenes.c1_flat(size)   # (the oracle reads the scene's own node pool: it stays alive while the oracle renders)
+        o = orc.from_package_scene(sc)
+        for bounces in PATH_BOUNCES:
+            o.set_settings(_path_settings(bounces))
+            for spp in PATH_SPP:
+                out[size, bounces, spp] = o.render(orc.MODE_PATH, *size, spp=spp, seed=SEED)[:2]
+                for a in out[size, bounces, spp]:
+                    a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("bounces", PATH_BOUNCES)
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("route", list(PATH_ROUTES))
+def test_every_schedule_of_a_path_frame_renders_the_oracles_frame(path_refs, monkeypatch, route, size, bounces):
+    """The launches of a path-traced frame — which cursor set and which path buffer each takes, how many segments a bounce launch
+    traces, which pass finishes a chain of samples and with what first / last / count — on every route plan_path can choose, with one
+    and two frames in flight and enough frames to visit both frame sets: every frame is the oracle's."""
+    for k, v in PATH_ROUTES[route].items():
+        monkeypatch.setenv(k, v)
+    w, h = size
+    cw, ch = w & ~7, h & ~7
+    sc = scenes.c1_flat(size)
+    gpu = gpu_for_scene(sc)
+    gpu.write_settings(_path_settings(bounces))
+
+    def check(spp, what):
+        rgb, ids, _ = gpu.read_output()
+        r_rgb, r_ids = path_refs[size, bounces, spp]
+        what = f"{w}x{h} {bounces} bounces {spp} spp, {route}, {what}"
+        assert_frame_parity(rgb, ids, r_rgb, r_ids, what)
+        assert not rgb[:, cw:].any() and not rgb[ch:, :].any() and not ids[:, cw:].any() and not ids[ch:, :].any(), what
+
+    for in_flight in (1, 2):
+        gpu.set_frames_in_flight(in_flight)
+        for spp in PATH_SPP:
+            for frame in range(in_flight + 1):   # (every frame set, and the first one again)
+                if route == "accumulated":
+                    gpu.reset_accumulation()
+                    for n in ACCUMULATED_IN[spp]:
+                        gpu.render(MODE_PATH, spp=n, seed=SEED, accumulate=True)
+                    assert gpu.accumulation() == (spp, SEED)
+                else:
+                    gpu.render(MODE_PATH, spp=spp, seed=SEED, stats=route == "stats")
+                check(spp, f"{in_flight} in flight, frame {frame}")
     gpu.close()
 
 

@@ -14,14 +14,6 @@ from util import assert_frame_parity, gpu_for_scene
 pytestmark = pytest.mark.gpu
 
 
-def needs_experiments():
-    """The structures that were measured and not chosen compile into tools/ab/libvrt_exp.so only (make -C
-    voxelraytracing_amd/csrc experiments; run the tests with VRT_LIB=tools/ab/libvrt_exp.so): their tests skip on the default build."""
-    from voxelraytracing_amd import _ffi
-    if not hasattr(_ffi.vrt(), "vrt_experiments_build"):
-        pytest.skip("the experiments build only (VRT_LIB=tools/ab/libvrt_exp.so)")
-
-
 @pytest.fixture(scope="module")
 def c1():
     return scenes.c1_flat()
@@ -880,17 +872,12 @@ def test_pool_depth_of_the_bounce_waves_does_not_change_the_frame(orc, monkeypat
         gpu.close()
 
 
-@pytest.mark.parametrize("env", [{"VRT_PATH_POOL": "0"}, {"VRT_PATH_CELLS": "0"}] +
-                                [{"VRT_PATH_WINDOW": "1", "VRT_PATH_WINDOW_SHAPE": str(k)} for k in range(5)])
+@pytest.mark.parametrize("env", [{"VRT_PATH_POOL": "0"}, {"VRT_PATH_CELLS": "0"}])
 def test_every_form_of_the_bounce_launch_gives_the_same_frames(orc, monkeypatch, env):
     """The default bounce launch is the pool kernel over the march cells (a wave refills its lanes from its own LDS pool of
     rays; one 16-byte load per step).  VRT_PATH_POOL=0 / VRT_PATH_CELLS=0: lane = path for the whole kernel, one launch per
     bounce, the round-1 structure (what worlds without march cells and stats frames run).
-    VRT_PATH_WINDOW=1 (round 5; built and measured, not the default: profiles/r05_window_ab.txt; the experiments build): the rays
-    grouped by screen block, the march cells around a group staged in LDS (shapes 0-3), or (shape 4) the pool kernel with its rays'
-    state in global memory.  All bit for bit the same frame, with several samples, sharded, and with two frames in flight."""
-    if "VRT_PATH_WINDOW" in env:
-        needs_experiments()
+    All bit for bit the same frame, with several samples, sharded, and with two frames in flight."""
     sc = scenes.c4((320, 184), bounces=4)
     ref = gpu_for_scene(sc)
     ref.render(MODE_PATH, spp=3, seed=11)

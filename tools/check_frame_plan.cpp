@@ -7,12 +7,21 @@
 // equality the two places that asked for the derived tables relied on: asked of the variant before the fallback to the octree
 // walk, and accel_ok, is the same as asked of the variant after it, and accel_ok.
 //
+// The path-traced frame the same way: old_path_frame() restates launch_path_frame's decisions and its double loop word for word,
+// each line beside its line of vrt_frames.hip as of the commit before plan_path (f9d6f41), with the launches replaced by a record
+// of what they were given.  The branches of the window experiment (deleted with that commit's successor: a library without the
+// experiment's hooks never took them) are left out.  new_path_frame() records vrt::plan_path + vrt::for_each_path_step the way
+// the new launch_path_frame enqueues them.  The two must give the same launches in the same order with the same arguments and the
+// same buffers, over the full product of the facts that can reach the function.
+//
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
 //       -static-libasan -static-libubsan -o /tmp/check_frame_plan tools/check_frame_plan.cpp && /tmp/check_frame_plan
 // (the sanitizers' runtimes linked into the program: it then runs the same whatever else the process is made to load first)
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <tuple>
+#include <vector>
 
 #include "../voxelraytracing_amd/csrc/vrt_frame_plan.h"
 
@@ -78,6 +87,159 @@ static Old old_frame(const FrameFacts &F) {
     return o;
 }
 
+// ---- the path-traced frame ----
+using vrt::PathFacts;
+using vrt::PathPlan;
+using vrt::PathStep;
+
+enum Kind : int { kPrimary, kLaneBounce, kCellsBounce, kChainFinish, kResolve, kFinalDivide };
+enum Where : int { kNowhere, kFrame, kContextSum, kPlanes };   // a buffer a finishing pass is given
+// kind, sample, chain, seg_counts / seg_in / seg_clear (which of the three cursor sets), path_out / path_in (which of the two
+// buffers), last_bounce, segments, pool batches, first, last, count, the sum, the mean (resolve: the texels it reads and leaves the mean in)
+using Launch = std::tuple<int, uint32_t, uint32_t, int, int, int, int, int, uint32_t, uint32_t, uint32_t, bool, bool, uint32_t, int, int>;
+struct PathRecord {
+    std::vector<Launch> launches;
+    bool acc_planes = false, accum_sum = false, out_is_planes = false, acc_set = false, zeroed = false;
+    size_t cap = 0, path_buf = 0;
+    uint32_t seg_cap = 0, acc_frames = 0, sample_base = 0, spp = 0, seed = 0, refill = 0;
+    bool kstats = false, literal = false, emit = false;   // what the trace's launchers are given
+    bool operator==(const PathRecord &o) const {
+        return launches == o.launches && acc_planes == o.acc_planes && accum_sum == o.accum_sum && out_is_planes == o.out_is_planes &&
+               acc_set == o.acc_set && zeroed == o.zeroed && cap == o.cap && path_buf == o.path_buf && seg_cap == o.seg_cap &&
+               acc_frames == o.acc_frames && sample_base == o.sample_base && spp == o.spp && seed == o.seed && refill == o.refill &&
+               kstats == o.kstats && literal == o.literal && emit == o.emit;
+    }
+};
+constexpr uint32_t kHitSegments = 256;   // vrt_device.h
+
+static PathRecord old_path_frame(const PathFacts &F) {
+    PathRecord r;
+    const bool accum = F.accum;                                                                       // :323
+    const uint32_t accum_from = F.accum ? F.accum_from : 0u;                                          // :323 (accum_frame_start: 0 unless accumulating, :309-310)
+    const bool kstats = F.kstats, literal = F.literal;                                                // :324
+    const uint32_t spp = F.spp, bounces = F.bounces;                                                  // :325
+    const uint32_t samples = (spp > 1u && !kstats && !literal && F.has_grid && bounces > 0) ? (spp < F.path_samples ? spp : F.path_samples) : 1u;   // :330
+    const bool planes = samples > 1u;                                                                 // :331
+    const bool emit = F.emissive;                                                                     // :337
+    const bool own_sum = emit && !planes && !accum && spp > 1u && bounces > 0;                        // :338
+    const uint32_t seg_cap = F.hit_seg_cap * samples;                                                 // :339
+    const size_t cap = (size_t)kHitSegments * seg_cap;                                                // :340
+    r.path_buf = (2 * 3) * cap;                                                                       // :343
+    if (planes || own_sum) { r.acc_planes = true; r.acc_frames = samples; }                           // :344
+    if (accum) r.accum_sum = true;                                                                    // :345-348
+    const uint32_t accum_count = accum_from + spp;                                                    // :357
+    r.seg_cap = seg_cap;                                                                              // :359, :369
+    r.acc_set = planes;                                                                               // :360
+    if (planes) r.out_is_planes = true;                                                               // :363
+    r.cap = cap;                                                                                      // :367-368
+    r.spp = spp;                                                                                      // :370
+    r.seed = F.seed;                                                                                  // :371
+    r.sample_base = accum ? accum_from : 0u;                                                          // :372
+    const bool pool = !kstats && !literal && F.has_grid && bounces > 1 && F.path_pool;                // :375
+    const bool cells = pool && F.has_cells && F.path_cells;                                           // :376
+    r.kstats = kstats; r.literal = literal; r.emit = emit; r.refill = F.path_refill;                  // :411, :418, :422
+    if (bounces == 0) r.zeroed = true;                                                                // :395
+    uint32_t g = 0;                                                                                   // :397
+    for (uint32_t smp = 0; smp < spp && bounces > 0; smp += samples) {                                // :398
+        const uint32_t chain = spp - smp < samples ? spp - smp : samples;                             // :400
+        for (uint32_t b = 0; b < bounces; b++, g++) {                                                 // :401
+            const int seg_counts = g % 3u, seg_in = (g + 2u) % 3u, seg_clear = (g + 1u) % 3u;         // :402-404
+            const int path_out = g & 1u, path_in = (g + 1u) & 1u;                                     // :405-406
+            uint32_t last_bounce = b + 1 == bounces;                                                  // :407
+            if (b == 0) {                                                                             // :409
+                r.launches.emplace_back(kPrimary, smp, chain, seg_counts, seg_in, seg_clear, path_out, path_in, last_bounce, 1u, 0u, false, false, 0u, kNowhere, kNowhere);   // :411
+            } else if (cells) {                                                                       // :412
+                const uint32_t segments = bounces - b;                                                // :415
+                last_bounce = 1u;                                                                     // :416
+                r.launches.emplace_back(kCellsBounce, smp, chain, seg_counts, seg_in, seg_clear, path_out, path_in, last_bounce, segments,
+                                        F.path_pool_batches ? F.path_pool_batches : (F.in_flight > 1u ? 5u : 4u), false, false, 0u, kNowhere, kNowhere);   // :418
+                b += segments - 1u;                                                                   // :420
+            } else {
+                r.launches.emplace_back(kLaneBounce, smp, chain, seg_counts, seg_in, seg_clear, path_out, path_in, last_bounce, 1u, 0u, false, false, 0u, kNowhere, kNowhere);   // :422
+            }
+        }
+        if (planes) {                                                                                 // :428
+            if (accum) r.launches.emplace_back(kChainFinish, smp, chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, accum_from + smp == 0u, smp + chain >= spp, accum_count, kContextSum, kFrame);   // :429-430
+            else r.launches.emplace_back(kChainFinish, smp, chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, smp == 0u, smp + chain >= spp, spp, kFrame, kFrame);   // :431
+        } else if (accum) {                                                                           // :433
+            r.launches.emplace_back(kResolve, smp, chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, accum_from + smp == 0u, smp + 1u >= spp, accum_count, kContextSum, kFrame);   // :434
+        } else if (own_sum) {                                                                         // :436
+            r.launches.emplace_back(kResolve, smp, chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, smp == 0u, smp + 1u >= spp, spp, kPlanes, kFrame);   // :437
+        }
+    }
+    if (bounces > 0 && spp > 1u && !planes && !accum && !own_sum)                                     // :443
+        r.launches.emplace_back(kFinalDivide, 0u, 0u, -1, -1, -1, -1, -1, 0u, 0u, 0u, false, true, spp, kNowhere, kFrame);   // :444
+    return r;
+}
+
+// plan_path + for_each_path_step, recorded as launch_path_frame (vrt_frames.hip) enqueues them
+static PathRecord new_path_frame(const PathFacts &F) {
+    PathRecord r;
+    const PathPlan p = vrt::plan_path(F);
+    r.path_buf = 6 * p.cap;
+    if (p.needs_acc_planes) { r.acc_planes = true; r.acc_frames = p.samples; }
+    r.accum_sum = p.needs_accum_sum;
+    r.seg_cap = p.seg_cap; r.acc_set = p.planes; r.out_is_planes = p.planes; r.cap = p.cap;
+    r.spp = p.spp; r.seed = p.seed; r.sample_base = p.sample_base;
+    r.kstats = p.kstats; r.literal = p.literal; r.emit = p.emit; r.refill = p.refill;
+    r.zeroed = p.zero_output;
+    const int sum_chain = p.finish_into_accum ? kContextSum : kFrame, sum_resolve = p.finish_into_accum ? kContextSum : kPlanes;
+    vrt::for_each_path_step(p, [&](const PathStep &s) {
+        const uint32_t g = s.launch;
+        switch (s.kind) {
+            case vrt::kStepPrimary: case vrt::kStepLaneBounce: case vrt::kStepCellsBounce:
+                r.launches.emplace_back(s.kind == vrt::kStepPrimary ? kPrimary : s.kind == vrt::kStepLaneBounce ? kLaneBounce : kCellsBounce, s.sample,
+                                        s.chain, g % 3u, (g + 2u) % 3u, (g + 1u) % 3u, g & 1u, (g + 1u) & 1u, s.last_bounce ? 1u : 0u, s.segments,
+                                        s.kind == vrt::kStepCellsBounce ? p.pool_batches : 0u, false, false, 0u, kNowhere, kNowhere);
+                break;
+            case vrt::kStepChainFinish:
+                r.launches.emplace_back(kChainFinish, s.sample, s.chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, s.first, s.last, s.count, sum_chain, kFrame);
+                break;
+            case vrt::kStepResolve:
+                r.launches.emplace_back(kResolve, s.sample, s.chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, s.first, s.last, s.count, sum_resolve, kFrame);
+                break;
+            case vrt::kStepFinalDivide:
+                r.launches.emplace_back(kFinalDivide, 0u, 0u, -1, -1, -1, -1, -1, 0u, 0u, 0u, false, true, s.count, kNowhere, kFrame);
+                break;
+        }
+    });
+    return r;
+}
+
+static void check_path_frames() {
+    long compared = 0, launches = 0, skipped = 0;
+    const uint32_t spps[] = {1, 2, 3, 4, 5, 16, 17}, per_chain[] = {1, 2, 4, 16}, batches[] = {0, 4, 5};
+    const int accums[] = {-1, 0, 7};   // not accumulating; accumulating from 0 and from 7 samples
+    for (uint32_t spp : spps)
+    for (uint32_t bounces = 0; bounces <= 5; bounces++)
+    for (uint32_t bits = 0; bits < 128; bits++)
+    for (int accum : accums)
+    for (uint32_t samples : per_chain)
+    for (uint32_t kb : batches)
+    for (uint32_t in_flight = 1; in_flight <= 2; in_flight++) {
+        PathFacts F;
+        F.spp = spp; F.seed = 11u; F.bounces = bounces;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u;
+        F.march_direct = F.has_cells;   // (no decision reads it)
+        F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
+        F.path_samples = samples; F.path_pool_batches = kb; F.path_refill = 16u; F.in_flight = in_flight; F.hit_seg_cap = 512u;
+        // what cannot reach the function: a literal frame is never handed the tables (vrt_frame_plan.h: asks_for_tables), and the
+        // march cells come with the tables (vrt_render fills P.mblk inside the branch that fills P.grid)
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) { skipped++; continue; }
+        std::snprintf(g_case, sizeof g_case, "path: spp %u bounces %u kstats %d literal %d grid %d cells %d emissive %d pool %d path_cells %d accum %d "
+                      "per chain %u batches %u in_flight %u", spp, bounces, F.kstats, F.literal, F.has_grid, F.has_cells, F.emissive, F.path_pool,
+                      F.path_cells, accum, samples, kb, in_flight);
+        const PathRecord o = old_path_frame(F), n = new_path_frame(F);
+        CHECK(o.launches.size() == n.launches.size());
+        for (size_t i = 0; i < o.launches.size(); i++) CHECK(o.launches[i] == n.launches[i]);
+        CHECK(o == n);
+        compared++;
+        launches += (long)o.launches.size();
+    }
+    std::printf("check_path_plan: ok (%ld frames compared, %ld launches, %ld unreachable)\n", compared, launches, skipped);
+}
+
 int main() {
     long compared[3][4] = {}, skipped = 0;
     const uint32_t flag_sets[4] = {0u, VRT_RENDER_OWN_STREAMS, VRT_RENDER_ACCUMULATE, VRT_RENDER_OWN_STREAMS | VRT_RENDER_ACCUMULATE};
@@ -138,5 +300,6 @@ int main() {
             if (accepted) std::printf("  mode %u variant %u: %ld\n", mode, variant, compared[mode][variant]);
         }
     std::printf("check_frame_plan: ok (%ld frames compared, %ld refused)\n", total, skipped);
+    check_path_frames();
     return 0;
 }

@@ -44,7 +44,6 @@
 #include "vrt_frame_plan.h"
 #include "vrt_handle.h"
 #include "vrt_device.h"
-#include "vrt_exp.h"
 
 namespace vrt {
 struct HipAlloc {   // vrt_devbuf.h's allocator over the HIP runtime
@@ -217,7 +216,6 @@ struct vrt_ctx {
         Buf<vrt::Texel> extra_out[kMaxInFlight - 1];
         Buf<uint32_t> extra_blk[kMaxInFlight - 1];
         Buf<uint4> extra_path[kMaxInFlight - 1];
-        Buf<uint32_t> path_grp_counts[kMaxInFlight];   // VRT_PATH_WINDOW: the regions' counts, per frame set
         Buf<vrt::Texel> path_acc[kMaxInFlight];        // the samples' accumulation planes of a launch chain, per frame set
         Buf<uint32_t> d_tile_cost, d_tile_order, d_tile_scratch;   // vrt_order.hip, made together
         bool tile_order_valid = false;
@@ -280,12 +278,6 @@ struct vrt_ctx {
     uint32_t timing_every = 8, frame_no = 0;
     bool path_pool = true;         // VRT_PATH_POOL=0 / VRT_PATH_CELLS=0: bounce launches with lane = path (the round-1 structure) instead of the
     bool path_cells = true;        // pool kernel over the march cells (tests: the two structures hold each other's frames)
-    // VRT_PATH_WINDOW=1 (experiments build; built and measured in round 5, not chosen: profiles/r05_window_*): the bounce launch over
-    // LDS-staged windows of march cells (experiments/vrt_path_window.hip).  Per frame set: the regions' counts (two 16-byte planes
-    // of per-ray state lie behind the path buffer's six)
-    bool path_window = false;
-    uint32_t path_window_shape = 2;   // VRT_PATH_WINDOW_SHAPE: 0 = 32^3 voxels, 1 = 48^3, 2 = 64 x 32 x 64, 3 = 64^3, 4 = no window (the rays' state in global memory)
-    int32_t path_window_lift = 8;     // VRT_PATH_WINDOW_LIFT: the window's centre above the mean origin, voxels
     uint32_t path_samples = 8;     // VRT_PATH_SAMPLES_PER_CHAIN: samples a launch chain traces at once when spp > 1 (1: one, as round 1 did)
     uint32_t path_pool_batches = 0;   // VRT_PATH_POOL_K = 4 | 5: the bounce waves' pools; 0: 5 for small worlds with two frames in flight, else 4
     uint32_t path_refill = 0;      // VRT_PATH_POOL_REFILL: idle lanes that send a bounce wave back to its pool (0: the default, 16)

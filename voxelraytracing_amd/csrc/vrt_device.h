@@ -7,6 +7,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/vrt.h"
@@ -79,12 +80,11 @@ struct FrameParams {
     uint32_t chain, acc_slots;
     uint32_t last_bounce;    // 1: paths that hit on this segment end (max_ray_bounces reached)
     uint32_t sample_base;    // VRT_RENDER_ACCUMULATE: the samples accumulated before this frame (sample s seeds as sample_base + s;
-                             // in what was padding before grp_counts: the other fields keep their offsets)
-    // the window bounce launch (vrt_path_window.hip): the primary launch's workgroup b compacts its survivors into records
-    // [b * grp_cap, b * grp_cap + grp_counts[b]) of path_out instead of appending to a segment
-    uint32_t *grp_counts;
-    uint32_t grp_cap;
-    uint32_t blk_w, blk_h;   // ... and takes the tiles in blocks of blk_w x blk_h (a bounce workgroup's regions: one block)
+                             // in what was padding: the other fields keep their offsets)
+    // A hole of 20 bytes where the fields of a deleted launch (round 5's window experiment) lay: the kernels read this struct
+    // from the kernarg segment, so with every later offset where it was their code is the same instruction for instruction
+    // (profiles/path_plan_isa_diff.txt).  The next change that alters these kernels' code anyway takes the hole out.
+    uint32_t layout_hole[5];
     uint32_t n_nodes, n_roots;
     uint32_t width, height;
     uint32_t tiles_x, tiles_total;
@@ -124,6 +124,7 @@ struct FrameParams {
     float world_max;         // 0.0 + f32(world.size) (:285)
     uint32_t cam_origin_facts;   // kCamNotFinite | kCamOnPlane (the start nudge :188-190 applies) | kCamOutside (:285, asked of the origin as it is)
 };
+static_assert(offsetof(FrameParams, n_nodes) == 244, "layout_hole keeps the fields behind it where the kernels' code expects them");
 
 // The path-trace buffers are compacted per segment, not globally: one device-scope counter saturates at ~88
 // returning atomics per microsecond (MI355X_MICROARCH.md "dequeue"), which made 32 400 per-wave atomics the

@@ -1,7 +1,10 @@
 #pragma once
 // vrt_frame_plan.h — what kind of frame a vrt_render call asks for, decided once (vrt_frames.hip: vrt_render plans the frame,
-// enqueues it, records it).  Pure functions over plain values, no context pointer, no HIP header: tools/check_frame_plan.cpp holds
-// them to the predicates they replaced over every combination of the facts.  A new kernel route is a line in plan_frame.
+// enqueues it, records it), and — for a path-traced frame — which launches it is made of (plan_path, for_each_path_step:
+// launch_path_frame enqueues them).  Pure functions over plain values, no context pointer, no HIP header:
+// tools/check_frame_plan.cpp holds them to the predicates and the loop they replaced over every combination of the facts.  A new
+// kernel route is a line in plan_frame or plan_path.
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/vrt.h"
@@ -68,6 +71,134 @@ inline FramePlan plan_frame(const FrameFacts &F) {
     // longest tiles first (vrt_order.hip): plain frames of the grid march in one launch, as far as the kind of frame decides it
     p.orderable = !p.path && p.variant == 0u && !p.kstats && F.stats == 0u;
     return p;
+}
+
+// ---- the path-traced frame (plan.path): a wavefront path trace, per chain of samples one launch per bounce over the compacted
+// live-path buffer, then a pass that takes the chain into the frame or a sum ----
+
+constexpr uint32_t kPlanHitSegments = 256;   // vrt::kHitSegments (vrt_device.h; vrt_frames.hip asserts the two equal)
+
+struct PathFacts {   // copied out of the options, the context and the frame's parameters
+    uint32_t spp = 1, seed = 0;     // vrt_render_opts (spp: at least 1)
+    uint32_t bounces = 0;           // settings.max_ray_bounces
+    bool kstats = false, literal = false;   // the FramePlan's
+    bool has_grid = false;          // the frame was handed the derived tables (P.grid)
+    bool has_cells = false;         // ... and the march cells with them (P.mblk)
+    bool march_direct = false;      // the march cells without a chunk directory (what the pool launcher's 320-ray pools ask for)
+    bool accum = false;             // VRT_RENDER_ACCUMULATE ...
+    uint32_t accum_from = 0;        // ... with this many samples in the context's sum before the frame (accum_frame_start)
+    bool emissive = false;          // vrt_write_emission: some material gives off light
+    // the context's switches (vrt_create reads them from the environment)
+    uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
+    bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
+    uint32_t path_pool_batches = 0, path_refill = 0;   // VRT_PATH_POOL_K, VRT_PATH_POOL_REFILL
+    uint32_t in_flight = 1;         // vrt_set_frames_in_flight
+    uint32_t hit_seg_cap = 256;     // records per segment of the hit buffer (a multiple of 256)
+};
+
+enum PathFinish : uint32_t {   // the pass behind each chain of samples
+    kFinishNone,          // one sample per chain adding straight to the frame's texels (divided at the end, if by more than 1)
+    kChainIntoFrame,      // path_chain_finish_kernel: the chain's planes join the frame in sample order; the last chain divides
+    kChainIntoSum,        // ... join the context's sum; the last chain stores the mean into the frame
+    kResolveIntoSum,      // path_accum_resolve_kernel: the texel's one sample joins the context's sum, the last stores the mean
+    kResolveIntoOwnSum,   // ... joins the frame set's own sum (its first plane)
+};
+
+struct PathPlan {   // each field is explained where plan_path sets it
+    uint32_t spp = 1, seed = 0, bounces = 0;
+    bool kstats = false, literal = false, emit = false;
+    uint32_t samples = 1;
+    bool planes = false, own_sum = false, cells = false;
+    uint32_t seg_cap = 0;
+    size_t cap = 0;
+    uint32_t pool_batches = 4, refill = 0;
+    bool zero_output = false;
+    PathFinish finish = kFinishNone;
+    bool finish_into_accum = false, divide_at_end = false;
+    bool needs_acc_planes = false, needs_accum_sum = false;
+    uint32_t sample_base = 0, accum_count = 1;
+};
+
+inline PathPlan plan_path(const PathFacts &F) {
+    PathPlan p;
+    p.spp = F.spp; p.seed = F.seed; p.bounces = F.bounces;
+    p.kstats = F.kstats; p.literal = F.literal;   // which build of the lane = path kernels (the launchers take them)
+    // Plain frames over the derived tables trace their bounces with what was built for speed; a stats frame, the literal march
+    // and a world too large for the tables keep the round-1 structure: one sample per chain, one lane = path launch per bounce
+    const bool fast = !F.kstats && !F.literal && F.has_grid;
+    // Several samples per launch chain (plain frames, spp > 1): every launch of the chain carries `samples` times the rays —
+    // 2.7 rays per lane are not enough to cover a bounce launch's tail — and a frame of 16 spp is 4 x 4
+    // launches instead of 16 x 4.  Each sample accumulates into its own plane; the chain's finishing pass adds the planes
+    // to the frame in sample order, which is the order one sample per chain adds them in.
+    p.samples = (F.spp > 1u && fast && F.bounces > 0u) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
+    p.planes = p.samples > 1u;
+    // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
+    // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
+    // frame's (path_accum_resolve_kernel takes it into the sum behind every sample) and — own_sum — an emissive frame's of
+    // several samples, which takes the same pass into a sum of its own (the frame set's first plane).  Without emission a
+    // sample is one term, added straight to the texel, and a 1-spp frame's texel is its one sample either way.
+    p.emit = F.emissive;
+    p.own_sum = p.emit && !p.planes && !F.accum && F.spp > 1u && F.bounces > 0u;
+    // a segment of the path buffers holds what its workgroups can produce for every sample of a chain; a buffer, every segment
+    p.seg_cap = F.hit_seg_cap * p.samples;
+    p.cap = (size_t)kPlanHitSegments * p.seg_cap;
+    // Bounce launches over the march cells: every later segment of a chain in ONE launch of the pool kernel (vrt_path.hip);
+    // worlds without march cells, or with the pool switched off: one lane = path launch per bounce.
+    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells;
+    // the pool's batches of 64 rays per wave: 5 with two frames in flight (the launcher grants them to direct worlds only), else 4
+    p.pool_batches = F.path_pool_batches ? F.path_pool_batches : (F.in_flight > 1u ? 5u : 4u);
+    p.refill = F.path_refill;
+    p.zero_output = F.bounces == 0u;   // no segment is traced: the frame is zeros, and nothing below is launched
+    // an accumulating frame's samples continue the sum's: they seed as sample_base + s, and the mean is over accum_count
+    p.sample_base = F.accum ? F.accum_from : 0u;
+    p.accum_count = p.sample_base + F.spp;   // (<= 2^24: accum_frame_start)
+    p.finish = p.zero_output ? kFinishNone
+             : p.planes      ? (F.accum ? kChainIntoSum : kChainIntoFrame)
+             : F.accum       ? kResolveIntoSum   // one sample per chain: bit-exact only one sample at a time
+             : p.own_sum     ? kResolveIntoOwnSum
+                             : kFinishNone;
+    p.finish_into_accum = p.finish == kChainIntoSum || p.finish == kResolveIntoSum;   // ordered behind the previous accumulating frame
+    p.divide_at_end = !p.zero_output && p.finish == kFinishNone && F.spp > 1u;   // path_finish_kernel: rgb /= spp behind the last sample
+    p.needs_acc_planes = p.planes || p.own_sum;   // the frame set's planes: `samples` frames of texels
+    p.needs_accum_sum = F.accum;   // the context's sum (and the event behind its last writer), whether or not this frame reaches it
+    return p;
+}
+
+// (the first three trace rays — the launches PathStep::launch counts — and come first: kind <= kStepCellsBounce asks for them)
+enum PathStepKind : uint32_t { kStepPrimary, kStepLaneBounce, kStepCellsBounce, kStepChainFinish, kStepResolve, kStepFinalDivide };
+
+struct PathStep {   // one launch of the frame
+    PathStepKind kind;
+    uint32_t sample, chain;   // the chain traces samples [sample, sample + chain) of every pixel
+    // the launch's number within the frame, counting the trace's launches: it appends to cursor set launch % 3, reads set
+    // (launch + 2) % 3 and clears (launch + 1) % 3 for the next; it writes path buffer launch & 1 and reads the other
+    uint32_t launch;
+    uint32_t segments;        // bounce segments the launch traces (the pool kernel: all that are left of the chain)
+    bool last_bounce;         // paths that hit in this launch end
+    bool first, last;         // a finishing pass: the chain holds the sum's first sample / the frame's last
+    uint32_t count;           // ... and what the last divides by
+};
+
+// The frame's launches in stream order.  All three cursor sets are zero when the frame starts (vrt_render cleared them).
+template <class F>
+void for_each_path_step(const PathPlan &p, F &&f) {
+    uint32_t g = 0;
+    for (uint32_t smp = 0; smp < p.spp && p.bounces > 0u; smp += p.samples) {
+        const uint32_t chain = p.spp - smp < p.samples ? p.spp - smp : p.samples;
+        for (uint32_t b = 0; b < p.bounces; b++, g++) {
+            PathStep s{b == 0u ? kStepPrimary : p.cells ? kStepCellsBounce : kStepLaneBounce, smp, chain, g, 1u, b + 1u == p.bounces, false, false, 0u};
+            if (s.kind == kStepCellsBounce) {   // the waves carry their own survivors from one segment to the next
+                s.segments = p.bounces - b;
+                s.last_bounce = true;
+                b += s.segments - 1u;
+            }
+            f(s);
+        }
+        if (p.finish != kFinishNone)
+            f(PathStep{p.finish == kChainIntoFrame || p.finish == kChainIntoSum ? kStepChainFinish : kStepResolve, smp, chain, g, 0u, false,
+                       p.sample_base + smp == 0u, smp + chain >= p.spp, p.accum_count});
+    }
+    if (p.divide_at_end) f(PathStep{kStepFinalDivide, 0u, 0u, g, 0u, false, false, true, p.spp});
 }
 
 }  // namespace vrt

@@ -18,7 +18,6 @@ int fail(vrt_ctx *ctx, int code, const char *fmt, ...) {
 
 // Wait for the frame that may still be running on the second stream.
 vrt_host_prof g_host_prof;
-namespace vrt { ExpHooks g_exp; }   // all null here: experiments/vrt_exp_register.hip fills them in tools/ab/libvrt_exp.so
 
 int quiesce(vrt_ctx *c) {
     if (c->alt_pending) {
@@ -317,134 +316,76 @@ int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from) {
     return VRT_OK;
 }
 
-// Wavefront path trace: per sample one launch per bounce over the compacted live-path buffer.  accum: an accumulating frame
-// (VRT_RENDER_ACCUMULATE) with accum_from samples in the context's sum before it.
-static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt_render_opts &o, const vrt::FramePlan &plan,
-                             bool accum, uint32_t accum_from, std::array<hipEvent_t, 4> &ev, uint8_t &ev_kind) {
-    const bool kstats = plan.kstats, literal = plan.literal;
-    const uint32_t spp = o.spp ? o.spp : 1u, bounces = c->settings.max_ray_bounces;
-    // Several samples per launch chain (plain frames, spp > 1): every launch of the chain carries `samples` times the rays —
-    // 2.7 rays per lane are not enough to cover a bounce launch's tail — and a frame of 16 spp is 4 x 4
-    // launches instead of 16 x 4.  Each sample accumulates into its own plane; the chain's finishing pass adds the planes
-    // to the frame in sample order, which is the order one sample per chain adds them in.
-    const uint32_t samples = (spp > 1u && !kstats && !literal && P.grid && bounces > 0) ? (spp < c->path_samples ? spp : c->path_samples) : 1u;
-    const bool planes = samples > 1u;
-    // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
-    // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
-    // frame's (path_accum_resolve_kernel takes it into the sum behind every sample) and — own_sum — an emissive frame's of
-    // several samples, which takes the same pass into a sum of its own (the frame set's first plane).  Without emission a
-    // sample is one term, added straight to the texel, and a 1-spp frame's texel is its one sample either way.
-    const bool emit = c->n_emissive != 0u;
-    const bool own_sum = emit && !planes && !accum && spp > 1u && bounces > 0;
-    const uint32_t seg_cap = c->hit_seg_cap * samples;
-    const size_t cap = (size_t)vrt::kHitSegments * seg_cap;
-    // two sets of three record planes (+ two of per-ray state for experiments/vrt_path_window.hip's launch); grows only, and
-    // hipFree waits for whatever still uses the old one
-    HIP_TRY(c, f.path_buf->grow((2 * 3 + (vrt::g_exp.path_bounce_window ? 2 : 0)) * cap));
-    if (planes || own_sum) VRT_TRY(frame_buf(c, c->sz.path_acc[f.slot], (size_t)samples * c->slots));   // (grows with the samples of a chain)
-    if (accum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
+// Wavefront path trace: the launches vrt_frame_plan.h's plan_path decided on, enqueued in for_each_path_step's order.
+static_assert(vrt::kPlanHitSegments == vrt::kHitSegments, "the plan sizes the path buffers");
+static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt::PathPlan &plan, std::array<hipEvent_t, 4> &ev,
+                             uint8_t &ev_kind) {
+    // two sets of three record planes; grows only, and hipFree waits for whatever still uses the old one
+    HIP_TRY(c, f.path_buf->grow(6 * plan.cap));
+    if (plan.needs_acc_planes) VRT_TRY(frame_buf(c, c->sz.path_acc[f.slot], (size_t)plan.samples * c->slots));   // (grows with the samples of a chain)
+    if (plan.needs_accum_sum) {   // (dropped by a resize, with the accumulation: the first frame stores the sum whole)
         VRT_TRY(frame_buf(c, c->sz.d_accum, frame_slots(c)));
         HIP_TRY(c, c->ev_accum.ensure());
     }
-    // Only the steps that read and write the sum are ordered behind the previous accumulating frame's (it may be in flight on
-    // another frame set's stream); this frame's launches before them overlap it
-    bool sum_waited = false;
-    auto sum_step = [&]() -> int {
-        if (!sum_waited && c->accum_ev_recorded) HIP_TRY(c, hipStreamWaitEvent(f.st, c->ev_accum, 0));
-        sum_waited = true;
-        return VRT_OK;
-    };
-    const uint32_t accum_count = accum_from + spp;   // the samples in this frame's mean (<= 2^24: vrt_render)
-    vrt::Texel *const frame_out = P.out;
-    P.hit_seg_cap = seg_cap;
-    P.acc = planes ? c->sz.path_acc[f.slot] : nullptr;
+    vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
+    P.hit_seg_cap = plan.seg_cap;
+    P.acc = plan.planes ? acc : nullptr;
     P.acc_slots = c->slots;
     P.chain = 1u;
-    if (planes) P.out = c->sz.path_acc[f.slot];   // what the bounce launches accumulate into, through slots that carry the plane
+    if (plan.planes) P.out = acc;   // what the bounce launches accumulate into, through slots that carry the plane
     constexpr uint32_t kSegWords = vrt::kHitSegments * vrt::kSegStride;
-    uint32_t *seg[3] = {P.seg_counts, P.seg_counts + kSegWords, P.seg_counts + 2 * kSegWords};
-    uint4 *buf[2] = {*f.path_buf, *f.path_buf + 3 * cap};
-    P.path_cap = (uint32_t)cap;
-    P.in_cap = (uint32_t)cap;
-    P.in_seg_cap = seg_cap;
-    P.spp = spp;
-    P.seed = o.seed;
-    P.sample_base = accum ? accum_from : 0u;
-    // Bounce launches over the derived tables with march cells: every later segment of the frame in ONE launch of the pool
-    // kernel (vrt_path.hip); worlds without march cells, stats frames and the literal march: one lane = path launch per bounce.
-    const bool pool = !kstats && !literal && P.grid && bounces > 1 && c->path_pool;
-    const bool cells = pool && P.mblk && c->path_cells;
-    // ... and among those the window launch (vrt_path_window.hip): the primary launch compacts each workgroup's survivors into
-    // the workgroup's own region (256 records per sample of the chain), the bounce launch stages the march cells around a
-    // group of four regions in LDS
-    const bool window = cells && c->path_window && vrt::g_exp.path_bounce_window && !emit;   // (the window launch: the experiments build; no emission)
-    const uint32_t n_regions = (c->tiles_local + 3u) / 4u;
-    if (window) {
-        HIP_TRY(c, c->sz.path_grp_counts[f.slot].grow(n_regions));
-    }
-    P.grp_counts = window ? c->sz.path_grp_counts[f.slot] : nullptr;
-    P.grp_cap = 256u * samples;   // (n_regions * grp_cap <= cap: a segment holds what its workgroups can produce)
-    P.blk_w = P.blk_h = 4u;
-    if (window) {   // a bounce workgroup's regions are one block of tiles: 4 x 4 (4 regions), 8 x 4 (8), 8 x 8 (16)
-        const uint32_t nw = vrt::g_exp.window_group_regions(c->path_window_shape);
-        P.blk_w = nw == 4u ? 4u : 8u;
-        P.blk_h = nw == 16u ? 8u : 4u;
-    }
+    uint32_t *const seg[3] = {P.seg_counts, P.seg_counts + kSegWords, P.seg_counts + 2 * kSegWords};
+    uint4 *const buf[2] = {*f.path_buf, *f.path_buf + 3 * plan.cap};
+    P.path_cap = (uint32_t)plan.cap;
+    P.in_cap = (uint32_t)plan.cap;
+    P.in_seg_cap = plan.seg_cap;
+    P.spp = plan.spp;
+    P.seed = plan.seed;
+    P.sample_base = plan.sample_base;
     const bool timed = ev[0] != nullptr;
     if (timed) HIP_TRY(c, hipEventRecord(ev[0], f.st));
-    if (bounces == 0) HIP_TRY(c, hipMemsetAsync(f.out, 0, (size_t)c->slots * sizeof(vrt::Texel), f.st));
-    bool first = true;
-    uint32_t g = 0;   // launch number within the frame (all three cursor sets are zero when it starts: vrt_render cleared them)
-    for (uint32_t smp = 0; smp < spp && bounces > 0; smp += samples) {
-        P.sample = smp;
-        P.chain = spp - smp < samples ? spp - smp : samples;
-        for (uint32_t b = 0; b < bounces; b++, g++) {
-            P.seg_counts = seg[g % 3u];
-            P.seg_in = seg[(g + 2u) % 3u];
-            P.seg_clear = seg[(g + 1u) % 3u];
-            P.path_out = buf[g & 1u];
-            P.path_in = buf[(g + 1u) & 1u];
-            P.last_bounce = b + 1 == bounces;
-            // one sample per pixel: the lane that ends a path has the pixel's final value (x / 1 = x) — no finishing pass
-            if (b == 0) {
-                if (window) vrt::g_exp.path_primary_grouped(P, f.st);
-                else vrt::launch_path_primary(P, kstats, literal, emit, f.st);
-            } else if (cells) {
-                // every bounce segment that is left in ONE launch: the waves carry their own survivors from one to the next
-                // (one cursor set, one swap of the path buffers per LAUNCH: g counts launches)
-                const uint32_t segments = bounces - b;
-                P.last_bounce = 1u;
-                if (window) vrt::g_exp.path_bounce_window(P, segments, n_regions, samples, c->path_window_shape, c->path_window_lift, f.st);
-                else vrt::launch_path_bounce_cells(P, c->path_refill, segments, c->path_pool_batches ? c->path_pool_batches : (c->in_flight > 1u ? 5u : 4u), emit,
-                                                   f.st);
-                b += segments - 1u;
-            } else {
-                vrt::launch_path_bounce(P, kstats, literal, emit, f.st);   // (no march cells, a stats frame, the literal march: lane = path)
-            }
-            HIP_TRY(c, hipGetLastError());
-            if (first) { if (timed) HIP_TRY(c, hipEventRecord(ev[1], f.st)); first = false; }
+    if (plan.zero_output) HIP_TRY(c, hipMemsetAsync(f.out, 0, (size_t)c->slots * sizeof(vrt::Texel), f.st));
+    // Only the steps that read and write the context's sum are ordered behind the previous accumulating frame's (it may be in
+    // flight on another frame set's stream); this frame's launches before them overlap it
+    bool sum_waited = false, first_marked = false;
+    auto enqueue = [&](const vrt::PathStep &s) -> int {
+        using namespace vrt;
+        if (s.kind <= kStepCellsBounce) {   // a launch of the trace
+            P.sample = s.sample;
+            P.chain = s.chain;
+            P.seg_counts = seg[s.launch % 3u];
+            P.seg_in = seg[(s.launch + 2u) % 3u];
+            P.seg_clear = seg[(s.launch + 1u) % 3u];
+            P.path_out = buf[s.launch & 1u];
+            P.path_in = buf[(s.launch + 1u) & 1u];
+            P.last_bounce = s.last_bounce;
+        } else if (plan.finish_into_accum && !sum_waited) {
+            if (c->accum_ev_recorded) HIP_TRY(c, hipStreamWaitEvent(f.st, c->ev_accum, 0));
+            sum_waited = true;
         }
-        if (accum) VRT_TRY(sum_step());
-        if (planes) {
-            if (accum) vrt::launch_path_chain_finish(c->sz.d_accum, frame_out, c->sz.path_acc[f.slot], c->slots, P.chain, accum_from + smp == 0u,
-                                                     smp + P.chain >= spp, accum_count, f.st);
-            else vrt::launch_path_chain_finish(frame_out, frame_out, c->sz.path_acc[f.slot], c->slots, P.chain, smp == 0u, smp + P.chain >= spp, spp, f.st);
-            HIP_TRY(c, hipGetLastError());
-        } else if (accum) {   // one sample per chain: the sample joins the sum (bit-exact only one sample at a time)
-            vrt::launch_path_accum_resolve(frame_out, c->sz.d_accum, c->slots, accum_from + smp == 0u, smp + 1u >= spp, accum_count, f.st);
-            HIP_TRY(c, hipGetLastError());
-        } else if (own_sum) {   // (emission) the same into this frame's own sum
-            vrt::launch_path_accum_resolve(frame_out, c->sz.path_acc[f.slot], c->slots, smp == 0u, smp + 1u >= spp, spp, f.st);
-            HIP_TRY(c, hipGetLastError());
+        switch (s.kind) {
+            case kStepPrimary: launch_path_primary(P, plan.kstats, plan.literal, plan.emit, f.st); break;
+            case kStepLaneBounce: launch_path_bounce(P, plan.kstats, plan.literal, plan.emit, f.st); break;
+            case kStepCellsBounce: launch_path_bounce_cells(P, plan.refill, s.segments, plan.pool_batches, plan.emit, f.st); break;
+            case kStepChainFinish:
+                launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
+                break;
+            case kStepResolve:
+                launch_path_accum_resolve(frame_out, plan.finish_into_accum ? c->sz.d_accum.get() : acc, c->slots, s.first, s.last, s.count, f.st);
+                break;
+            case kStepFinalDivide: launch_path_finish(frame_out, c->slots, s.count, f.st); break;
         }
-    }
-    P.out = frame_out;
-    if (first && timed) HIP_TRY(c, hipEventRecord(ev[1], f.st));
-    if (bounces > 0 && spp > 1u && !planes && !accum && !own_sum) {
-        vrt::launch_path_finish(f.out, c->slots, spp, f.st);
         HIP_TRY(c, hipGetLastError());
-    }
-    if (accum && sum_waited) {
+        if (!first_marked && timed) HIP_TRY(c, hipEventRecord(ev[1], f.st));   // (behind the frame's first launch)
+        first_marked = true;
+        return VRT_OK;
+    };
+    int rc = VRT_OK;
+    vrt::for_each_path_step(plan, [&](const vrt::PathStep &s) { if (!rc) rc = enqueue(s); });
+    P.out = frame_out;
+    VRT_TRY(rc);
+    if (!first_marked && timed) HIP_TRY(c, hipEventRecord(ev[1], f.st));   // (a frame without a launch)
+    if (sum_waited) {
         HIP_TRY(c, hipEventRecord(c->ev_accum, f.st));
         c->accum_ev_recorded = true;
     }
@@ -532,10 +473,6 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     if (const char *e = getenv("VRT_TILE_ORDER_RADIUS")) { const int v = atoi(e); if (v >= 1 && v <= 6) c->mov_radius = (uint32_t)v; }
     if (const char *e = getenv("VRT_PATH_POOL")) c->path_pool = e[0] != '0';
     if (const char *e = getenv("VRT_PATH_CELLS")) c->path_cells = e[0] != '0';
-    // (the experiments build, tools/ab/libvrt_exp.so: without its hooks — vrt_exp.h — the next three select nothing)
-    if (const char *e = getenv("VRT_PATH_WINDOW")) c->path_window = e[0] == '1';
-    if (const char *e = getenv("VRT_PATH_WINDOW_SHAPE")) { const int v = atoi(e); if (v >= 0 && v <= 4) c->path_window_shape = (uint32_t)v; }
-    if (const char *e = getenv("VRT_PATH_WINDOW_LIFT")) { const int v = atoi(e); if (v >= -64 && v <= 64) c->path_window_lift = v; }
     if (const char *e = getenv("VRT_PATH_POOL_REFILL")) c->path_refill = (uint32_t)atoi(e);
     if (const char *e = getenv("VRT_PATH_POOL_K")) { const int v = atoi(e); if (v == 4 || v == 5) c->path_pool_batches = (uint32_t)v; }
     if (const char *e = getenv("VRT_PATH_SAMPLES_PER_CHAIN")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->path_samples = (uint32_t)v; }
@@ -794,7 +731,15 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             FrameSet ft = f;
             VRT_TRY(denoise_before_frame(c, f.slot, f.out, &ft.out));
             P.out = ft.out;
-            rc = launch_path_frame(c, P, ft, o, plan, accum, accum_from, ev, *ev_kind);
+            vrt::PathFacts PF;
+            PF.spp = o.spp ? o.spp : 1u; PF.seed = o.seed; PF.bounces = c->settings.max_ray_bounces;
+            PF.kstats = plan.kstats; PF.literal = plan.literal;
+            PF.has_grid = P.grid != nullptr; PF.has_cells = P.mblk != nullptr; PF.march_direct = P.march_direct != 0u;
+            PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u;
+            PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
+            PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
+            PF.in_flight = c->in_flight; PF.hit_seg_cap = c->hit_seg_cap;
+            rc = launch_path_frame(c, P, ft, vrt::plan_path(PF), ev, *ev_kind);
             // (a timed frame's closing event is recorded again behind the filter: vrt_stats and VRT_RENDER_TIMED time it with its passes)
             if (!rc) rc = denoise_after_frame(c, P, plan, f.slot, f.st, f.out, ev[3]);
         }

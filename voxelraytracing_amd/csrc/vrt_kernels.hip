@@ -19,7 +19,6 @@
 
 #include "vrt_tile.h"
 #include "vrt_path_common.h"   // (vrt_selftest_exact_math: the RNG's logarithm and direction, both forms)
-#include "vrt_exp.h"
 
 namespace vrt {
 

@@ -216,14 +216,14 @@ __global__ void path_finish_kernel(Texel *out, uint32_t n, float spp) {
             else hipLaunchKernelGGL((kernel<2, false, false TAIL>), grid, block, sh, st, P);                              \
         }                                                                                                                 \
     } while (0)
-#define VRT_PRIMARY_EMIT , false, false, true   // (MULTI, GROUPED, EMIT)
+#define VRT_PRIMARY_EMIT , false, true   // (MULTI, EMIT)
 #define VRT_BOUNCE_EMIT , true                  // (EMIT)
 
 void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, hipStream_t st) {
     if (P.tiles_local == 0) return;
     const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
     if (P.acc) {   // several samples per launch chain: plain frames over the derived tables only (vrt_frames.hip)
-        if (emit) hipLaunchKernelGGL((path_primary_kernel<0, false, false, true, false, true>), grid, block, lds_bytes_path(P, false), st, P);
+        if (emit) hipLaunchKernelGGL((path_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
         else hipLaunchKernelGGL((path_primary_kernel<0, false, false, true>), grid, block, lds_bytes_path(P, false), st, P);
         return;
     }

@@ -1,6 +1,5 @@
-// vrt_path_common.h — what the path-trace translation units share (vrt_path.hip: the primary launch and the lane = path
-// bounce kernels; vrt_path_window.hip: the fused bounce launch over LDS-staged windows of march cells): the RNG of
-// path_tracer.wgsl:56-72, log and cos spelled out in + - * / (host and device agree to the bit), and what follows a
+// vrt_path_common.h — what the path trace's kernels share (vrt_path.hip: the primary launch, the lane = path bounce kernels
+// and the pool kernel over the march cells; vrt_kernels.hip's self-test of the exact math): the RNG of path_tracer.wgsl:56-72, log and cos spelled out in + - * / (host and device agree to the bit), and what follows a
 // segment's march (path_tracer.wgsl:155-192).  DESIGN.md, path trace.
 #pragma once
 
@@ -158,10 +157,7 @@ __device__ __forceinline__ void append_paths(const FrameParams &P, bool alive, c
 
 // A wave's pool of rays (the bounce launches below): K batches of 64 paths, 4 words each in the wave's own LDS — unit[3]
 // (phase A -> the hand-out), then pos[3] + the packed end state (the march -> phase C): 4 KiB per wave
-#ifndef VRT_POOL_K
-#define VRT_POOL_K 4
-#endif
-constexpr uint32_t kPoolBatches = VRT_POOL_K;            // K
+constexpr uint32_t kPoolBatches = 4;                     // K
 constexpr uint32_t kPoolEntries = kPoolBatches * 64u;
 constexpr uint32_t kPoolWords = 4u * kPoolEntries;
 constexpr uint32_t kPoolRefillAt = 16u;                  // idle lanes (of 64) that send the wave back to the pool
