@@ -28,6 +28,17 @@ pub struct vrt_material {
     pub _padding: [u32; 2],
 }
 
+/// One entry of vrt_write_polish's table: the coat of path_tracer.wgsl's Material (polish_color, polish_bounce_chance,
+/// polish_scatter).  All zero = no coat.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_polish {
+    pub color: [f32; 3],
+    pub chance: f32,
+    pub scatter: f32,
+    pub _reserved: [u32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct vrt_cam_data {
@@ -275,6 +286,7 @@ extern "C" {
     pub fn vrt_resize_world(ctx: *mut vrt_ctx, world_size_chunks: u32) -> c_int;
     pub fn vrt_write_materials(ctx: *mut vrt_ctx, first: u32, mats: *const vrt_material, n: u32) -> c_int;
     pub fn vrt_write_emission(ctx: *mut vrt_ctx, first: u32, emission: *const f32, n: u32) -> c_int;
+    pub fn vrt_write_polish(ctx: *mut vrt_ctx, first: u32, polish: *const vrt_polish, n: u32) -> c_int;
     pub fn vrt_set_camera(ctx: *mut vrt_ctx, cam: *const vrt_cam_data) -> c_int;
     pub fn vrt_set_settings(ctx: *mut vrt_ctx, settings: *const vrt_settings) -> c_int;
     pub fn vrt_set_world(ctx: *mut vrt_ctx, world: *const vrt_world_data) -> c_int;
@@ -333,5 +345,6 @@ mod layout {
         assert_eq!(size_of::<vrt_issue_profile>(), 72);
         assert!(size_of::<vrt_denoise_opts>() == 16);
         assert!(size_of::<vrt_shape>() == 40);
+        assert!(size_of::<vrt_polish>() == 32);
     }
 }

@@ -173,7 +173,7 @@ typedef struct {
  * s spp are, bit for bit, one frame of K * s spp with the same seed.  The sum starts again at n = 0 (without a device
  * step: the first frame stores it) after vrt_reset_accumulation, or when anything the image depends on has changed since
  * the previous accumulating frame: the camera, settings or world (byte-wise), any vrt_write_materials, a non-empty
- * vrt_write_emission that is not refused, a non-empty vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
+ * vrt_write_emission or vrt_write_polish that is not refused, a non-empty vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
  * Non-accumulating frames in between change nothing.  n + spp > 2^24: VRT_ERR_OUT_OF_RANGE, nothing enqueued. */
 #define VRT_RENDER_ACCUMULATE 4u
 
@@ -254,6 +254,45 @@ int vrt_write_materials(vrt_ctx *ctx, uint32_t first, const vrt_material *mats, 
  * VRT_ERR_INVALID_ARG — nothing written either way.  n == 0 is a no-op; any other write restarts the accumulation.  A table
  * that is all zero (never written, or written back to zeros) renders exactly as a context without one. */
 int vrt_write_emission(vrt_ctx *ctx, uint32_t first, const float *emission, uint32_t n);
+
+/* New relative to the live reference: the rest of path_tracer.wgsl's Material — polish_bounce_chance, polish_color and
+ * polish_scatter (:28-31), whose three uses in ray_color are commented out there (:175, :180, :185): a second, specular lobe.
+ * A coin flip per hit chooses between the material's own lobe and a coat with a colour and a roughness of its own.
+ * (translucency, :29 and :167-173, is not part of it.) */
+typedef struct {
+    float    color[3];      /* what the throughput is multiplied by on a polished bounce; NOT face-shaded */
+    float    chance;        /* a hit bounces off the coat when u < chance; 0 = never (the default) */
+    float    scatter;       /* the coat's scatter, used in place of vrt_material.scatter on a polished bounce */
+    uint32_t _reserved[3];  /* not read */
+} vrt_polish;               /* 32 B */
+/* The table: 256 entries per context, indexed like the material and emission tables (voxel ids >= 255 use entry 255), all
+ * bytes 0 until written; entries [first, first + n) are copied at call time.  VRT_MODE_PATH only: the primary (+ shadow)
+ * modes ignore the table, and their frames are byte for byte what they are without it.
+ * A frame is polished when at least one entry's chance != 0.0f.  A table whose chances are all +0 or -0 renders byte for
+ * byte as a context that never called this function — same kernels, nothing launched or allocated — whatever the other
+ * fields hold.
+ * On every hit of a polished frame after which the path goes on, whatever that voxel's own entry says, the body of
+ * ray_color's loop is, in this order:
+ *   1. mc is the hit colour as without the table (face shading, or the step-count grey under show_step_count);
+ *   2. the emission term is unchanged and uses mc: (mc * e) * thr, ahead of everything below;
+ *   3. u = rng_next(rng): one draw, taken before the six draws of rng_next_dir (:175 stands before :178);
+ *   4. polished = u < entry.chance (rng_next can return exactly 1.0: chance = 1 is "nearly always", any chance > 1 "always");
+ *   5. scatter = polished ? entry.scatter : material.scatter;
+ *   6. tint = polished ? entry.color : mc — selects (the reference's mix(a, b, f32(bool)) is one for finite operands);
+ *      entry.color is used as written, also under show_step_count;
+ *   7. the specular and the scattered direction, the mix by scatter and both normalisations are as without the table;
+ *   8. thr *= tint; the next origin is as without the table.
+ * A hit on the path's last allowed segment draws nothing that anything can observe; its emission is still added.
+ * What follows from that: id words and the primary segment are those of the unpolished frame.  Writing the first non-zero
+ * chance shifts the RNG stream of every path by one draw per hit, so the frame changes even where no ray meets a coated
+ * voxel.  At max_ray_bounces <= 1 a polish table changes nothing.  The sums keep the emission contract: a sample's light is
+ * its terms in segment order with the sky last; the frame's light is its samples' lights in sample order, divided by spp.
+ * VRT_RENDER_ACCUMULATE keeps its identity: K frames of s spp equal one frame of K * s spp, bit for bit.
+ * first + n > 256: VRT_ERR_OUT_OF_RANGE; polish NULL with n > 0, a null context, or any of an entry's five floats negative,
+ * NaN or infinite: VRT_ERR_INVALID_ARG — a refused call writes nothing.  n == 0 is a no-op; any other write restarts the
+ * accumulation, as vrt_write_emission does.  A context over several devices replicates the write to every device; a shard's
+ * context keeps its own table. */
+int vrt_write_polish(vrt_ctx *ctx, uint32_t first, const vrt_polish *polish, uint32_t n);
 
 /* SimpleBuffer<T>::write — shader.rs:101-106; callers main.rs:428,439,447-449. */
 int vrt_set_camera(vrt_ctx *ctx, const vrt_cam_data *cam);

@@ -38,6 +38,12 @@ using Texel = uint4;
 // vrt_write_emission's table: 256 floats right behind the 256 materials, in the same allocation (no field of FrameParams of its own)
 constexpr uint32_t kMaterials = 256u;
 __host__ __device__ inline const float *emission_table(const vrt_material *mats) { return reinterpret_cast<const float *>(mats + kMaterials); }
+// vrt_write_polish's table: 256 entries of 32 bytes behind the emission table, in the same allocation again.  Byte 9 216 of it:
+// an entry is 16-byte aligned, so its color + chance are one load
+__host__ __device__ inline const vrt_polish *polish_table(const vrt_material *mats) {
+    return reinterpret_cast<const vrt_polish *>(emission_table(mats) + kMaterials);
+}
+static_assert(sizeof(vrt_polish) == 32 && (kMaterials * (sizeof(vrt_material) + sizeof(float))) % 16 == 0, "the polish table's entries are 16-byte aligned");
 
 // Everything a frame's kernels read, passed by value (kernarg -> SGPRs).
 struct FrameParams {

@@ -7,7 +7,9 @@
 // oracle/vrt_oracle.c:trace_path.  Emission (path_tracer.wgsl:183-184) is a per-material table of the context's own,
 // vrt_write_emission, 0 everywhere until a caller writes it; the kernels that add it are the EMIT instantiations below,
 // chosen by the host only for a context with an entry that is not 0 (a table of zeros runs the kernels that have no
-// emission term).  oracle/ keeps no emission; the tests' reference for it is tests/emission_ref.c.  log and cos are
+// emission term).  The coat of the same Material (:28-31, :175-185) is vrt_write_polish's table behind it, and the kernels
+// that flip its coin are the path_polished_* ones below, chosen only for a context with a chance that is not 0.  oracle/
+// keeps neither; the tests' references are tests/emission_ref.c and tests/polish_ref.c.  log and cos are
 // spelled out in + - * / so that host and device agree to the bit: a one-ulp different bounce direction eventually hits a
 // different voxel.
 //
@@ -17,73 +19,43 @@
 // radiance accumulates into the pixel's texel with plain read-modify-writes.
 #include <cstdlib>
 
-#include "vrt_path_primary.h"
+#include "vrt_path_common.h"
 
 namespace vrt {
 
+static_assert(kHitSegments == 256, "a launch's first workgroup (256 threads) clears the next launch's 256 segment cursors");
+
+static inline size_t lds_bytes_path(const FrameParams &P, bool lds_roots) { return (24u + (lds_roots ? P.n_roots : 0u)) * 4u; }
+
+#define VRT_PRIMARY_KERNEL path_primary_kernel
+#define VRT_PRIMARY_POLISH 0
+#include "vrt_path_primary.h"
+#undef VRT_PRIMARY_KERNEL
+#undef VRT_PRIMARY_POLISH
+#define VRT_PRIMARY_KERNEL path_polished_primary_kernel
+#define VRT_PRIMARY_POLISH 1
+#include "vrt_path_primary.h"
+#undef VRT_PRIMARY_KERNEL
+#undef VRT_PRIMARY_POLISH
+
 // One segment of a path: its march, then path_after_march.
-template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT>
+template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT, bool POLISH>
 __device__ __forceinline__ bool path_segment(const FrameParams &P, const uint32_t *s_roots, const uint32_t *s_liquid,
                                              PathState &st, MarchResult &R, V3 &light, bool &lit) {
     R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, st.origin, st.dir);
-    return path_after_march<EMIT>(P, st, R, light, lit);
+    return path_after_march<EMIT, POLISH>(P, st, R, light, lit);
 }
 
-// Bounce b >= 1: lane = one live path of the in buffer.  EMIT: emissive hits add their light too (vrt_write_emission).
-template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT = false>
-__global__ void __launch_bounds__(256) path_bounce_kernel(FrameParams P) {
-    extern __shared__ uint32_t smem[];
-    uint32_t *s_liquid = smem, *s_roots = smem + 24;
-    unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
-    if (STATS && threadIdx.x < 8) s_acc[threadIdx.x] = 0ull;
-    stage_lds(P, s_roots, s_liquid, LDS_ROOTS);
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t seg = blockIdx.x % kHitSegments, part = blockIdx.x / kHitSegments;
-    if (blockIdx.x == 0 && P.seg_clear) P.seg_clear[threadIdx.x * kSegStride] = 0u;
-    const uint32_t count = P.seg_in[seg * kSegStride];
-    const uint32_t j = part * blockDim.x + threadIdx.x;
-    const bool active = j < count;
-    if (!STATS && part * blockDim.x >= count) return;
-    MarchResult R;
-    R.iters = 0; R.visits = 0; R.hit = false;
-    bool alive = false;
-    PathState st;
-    st.slot = 0; st.rng = 0;
-    st.origin = st.dir = st.thr = V3{0.f, 0.f, 0.f};
-    if (active) {
-        const uint32_t i = seg * P.hit_seg_cap + j;
-        const uint4 a = P.path_in[i], b = P.path_in[P.path_cap + i], c = P.path_in[2u * P.path_cap + i];
-        st.slot = a.x;
-        st.origin = V3{__uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w)};
-        st.dir = V3{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
-        st.rng = b.w;
-        st.thr = V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
-        V3 light{0.f, 0.f, 0.f};
-        bool lit;
-        alive = path_segment<MARCH, LDS_ROOTS, STATS, EMIT>(P, s_roots, s_liquid, st, R, light, lit) && !P.last_bounce;
-        if (lit) {
-            uint4 t = P.out[st.slot];
-            t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
-            t.y = __float_as_uint(__uint_as_float(t.y) + light.y);
-            t.z = __float_as_uint(__uint_as_float(t.z) + light.z);
-            P.out[st.slot] = t;
-        }
-        if (STATS && P.steps && P.sample == 0u) P.steps[st.slot] += R.iters << 16;
-    }
-    append_paths(P, alive, st, lane);
-    if (STATS) {
-        block_add(s_acc, 0, active ? R.iters : 0u);
-        block_add(s_acc, 1, active ? R.visits : 0u);
-        block_add(s_acc, 2, active ? 1ull : 0ull);
-        __syncthreads();
-        if (threadIdx.x == 0 && s_acc[2]) {
-            atomicAdd(&P.counters[kCtrSteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrSecondary], s_acc[2]);
-        }
-    }
-}
+#define VRT_BOUNCE_KERNEL path_bounce_kernel
+#define VRT_BOUNCE_POLISH 0
+#include "vrt_path_bounce.h"
+#undef VRT_BOUNCE_KERNEL
+#undef VRT_BOUNCE_POLISH
+#define VRT_BOUNCE_KERNEL path_polished_bounce_kernel
+#define VRT_BOUNCE_POLISH 1
+#include "vrt_path_bounce.h"
+#undef VRT_BOUNCE_KERNEL
+#undef VRT_BOUNCE_POLISH
 
 
 // ------------------------------------------------------------------------------------------------
@@ -109,14 +81,25 @@ __global__ void __launch_bounds__(256) path_bounce_kernel(FrameParams P) {
 // launch start beside this one: C4 + 2.8 % (one frame at a time - 2.2 %, C5 - 3.8 %: profiles/r05_pool_k5.txt)
 #define VRT_CELLS_KERNEL path_bounce_cells_kernel
 #define VRT_CELLS_EMIT 0
+#define VRT_CELLS_POLISH 0
 #include "vrt_path_cells.h"
 #undef VRT_CELLS_KERNEL
 #undef VRT_CELLS_EMIT
+#undef VRT_CELLS_POLISH
 #define VRT_CELLS_KERNEL path_emissive_cells_kernel
 #define VRT_CELLS_EMIT 1
+#define VRT_CELLS_POLISH 0
 #include "vrt_path_cells.h"
 #undef VRT_CELLS_KERNEL
 #undef VRT_CELLS_EMIT
+#undef VRT_CELLS_POLISH
+#define VRT_CELLS_KERNEL path_polished_cells_kernel
+#define VRT_CELLS_EMIT 1
+#define VRT_CELLS_POLISH 1
+#include "vrt_path_cells.h"
+#undef VRT_CELLS_KERNEL
+#undef VRT_CELLS_EMIT
+#undef VRT_CELLS_POLISH
 
 
 // The end of a launch chain of several samples: the running sum plus the chain's planes, in sample order — the order the
@@ -219,21 +202,24 @@ __global__ void path_finish_kernel(Texel *out, uint32_t n, float spp) {
 #define VRT_PRIMARY_EMIT , false, true   // (MULTI, EMIT)
 #define VRT_BOUNCE_EMIT , true                  // (EMIT)
 
-void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, hipStream_t st) {
+// polish (vrt_write_polish; the frame plan gives it with emit): the kernels of the same three families that flip the coat's coin
+void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st) {
     if (P.tiles_local == 0) return;
     const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
     if (P.acc) {   // several samples per launch chain: plain frames over the derived tables only (vrt_frames.hip)
-        if (emit) hipLaunchKernelGGL((path_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
+        if (polish) hipLaunchKernelGGL((path_polished_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
+        else if (emit) hipLaunchKernelGGL((path_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
         else hipLaunchKernelGGL((path_primary_kernel<0, false, false, true>), grid, block, lds_bytes_path(P, false), st, P);
         return;
     }
-    if (emit) VRT_PATH_LAUNCH(path_primary_kernel, VRT_PRIMARY_EMIT);
+    if (polish) VRT_PATH_LAUNCH(path_polished_primary_kernel, VRT_PRIMARY_EMIT);
+    else if (emit) VRT_PATH_LAUNCH(path_primary_kernel, VRT_PRIMARY_EMIT);
     else VRT_PATH_LAUNCH(path_primary_kernel, );
 }
 
 // the pool kernel over the march cells (P.mblk): `segments` bounce segments in this one launch (every wave carries its own
 // survivors from one to the next; P.path_in / P.path_out are the two buffers it goes back and forth between)
-void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, hipStream_t st) {
+void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, hipStream_t st) {
     if (P.tiles_local == 0 || segments == 0) return;
     const uint32_t refill = refill_at >= 1u && refill_at <= 64u ? refill_at : kPoolRefillAt;
     const uint32_t kb = (pool_batches == 5u && P.march_direct) ? 5u : 4u, entries = kb * 64u;   // (320-ray pools: direct worlds only)
@@ -241,6 +227,12 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
     const dim3 grid(kHitSegments * parts), block(256);
     const size_t sh = 8u * 4u + 4u * (entries * 16u + entries * 2u);   // per wave: the pool + a u16 order per entry
     const CellsLaunch L{P, refill, segments};
+    if (polish) {
+        if (kb == 5u) hipLaunchKernelGGL((path_polished_cells_kernel<true, 5u>), grid, block, sh, st, L);
+        else if (P.march_direct) hipLaunchKernelGGL((path_polished_cells_kernel<true, 4u>), grid, block, sh, st, L);
+        else hipLaunchKernelGGL((path_polished_cells_kernel<false, 4u>), grid, block, sh, st, L);
+        return;
+    }
     if (emit) {
         if (kb == 5u) hipLaunchKernelGGL((path_emissive_cells_kernel<true, 5u>), grid, block, sh, st, L);
         else if (P.march_direct) hipLaunchKernelGGL((path_emissive_cells_kernel<true, 4u>), grid, block, sh, st, L);
@@ -252,10 +244,11 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
     else hipLaunchKernelGGL((path_bounce_cells_kernel<false, 4u>), grid, block, sh, st, L);
 }
 
-void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, hipStream_t st) {
+void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st) {
     if (P.tiles_local == 0) return;
     const dim3 grid(kHitSegments * (P.hit_seg_cap / 256u)), block(256);
-    if (emit) VRT_PATH_LAUNCH(path_bounce_kernel, VRT_BOUNCE_EMIT);
+    if (polish) VRT_PATH_LAUNCH(path_polished_bounce_kernel, VRT_BOUNCE_EMIT);
+    else if (emit) VRT_PATH_LAUNCH(path_bounce_kernel, VRT_BOUNCE_EMIT);
     else VRT_PATH_LAUNCH(path_bounce_kernel, );
 }
 #undef VRT_PATH_LAUNCH

@@ -100,7 +100,9 @@ __device__ __forceinline__ bool path_emission(const FrameParams &P, const MarchR
 // What follows a segment's march (the rest of the body of ray_color's loop, path_tracer.wgsl:155-192).  Returns true if the
 // path goes on (st updated to the next segment); a miss puts the sky's light, weighted, into `light`, and so does — EMIT — a
 // hit on an emissive voxel its own.  lit: `light` holds a term for the sample's texel.
-template <bool EMIT = false>
+// POLISH (vrt_write_polish; :175, :180, :185): every hit draws u ahead of the direction's six draws, and where u is below the
+// chance of the voxel's entry of the polish table, the entry's scatter and colour take the place of the material's scatter and mc.
+template <bool EMIT = false, bool POLISH = false>
 __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
     lit = !R.hit;
     if (!R.hit) {
@@ -112,11 +114,21 @@ __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState
     if (EMIT) lit = path_emission(P, R, mc, st.thr, light);   // (before thr *= mc: :183-186)
     const float d = vdot(R.norm, st.dir);
     const V3 spec{st.dir.x - 2.0f * R.norm.x * d, st.dir.y - 2.0f * R.norm.y * d, st.dir.z - 2.0f * R.norm.z * d};
+    float u = 0.0f;
+    if (POLISH) u = rng_next(st.rng);
     const V3 rd = rng_next_dir(st.rng);
     const V3 sc = normalize_wave(V3{R.norm.x + rd.x, R.norm.y + rd.y, R.norm.z + rd.z});
-    const float scatter = P.mats[min(R.voxel, 255u)].scatter;
+    float scatter = P.mats[min(R.voxel, 255u)].scatter;
+    V3 tint = mc;
+    if (POLISH) {   // (selects, behind the draws: only u is kept across them)
+        const vrt_polish *e = &polish_table(P.mats)[min(R.voxel, 255u)];
+        const float4 cc = *reinterpret_cast<const float4 *>(e);   // color + chance: one load
+        const bool polished = u < cc.w;
+        scatter = polished ? e->scatter : scatter;
+        tint = V3{polished ? cc.x : mc.x, polished ? cc.y : mc.y, polished ? cc.z : mc.z};
+    }
     const V3 nd = normalize_wave(V3{vmix(spec.x, sc.x, scatter), vmix(spec.y, sc.y, scatter), vmix(spec.z, sc.z, scatter)});
-    st.thr = V3{st.thr.x * mc.x, st.thr.y * mc.y, st.thr.z * mc.z};
+    st.thr = V3{st.thr.x * tint.x, st.thr.y * tint.y, st.thr.z * tint.z};
     st.origin = V3{R.pos.x + R.norm.x * kShadowBias, R.pos.y + R.norm.y * kShadowBias, R.pos.z + R.norm.z * kShadowBias};
     st.dir = nd;
     return true;

@@ -682,6 +682,26 @@ int vrt_write_emission(vrt_ctx *c, uint32_t first, const float *emission, uint32
     return stage_upload(c, const_cast<float *>(vrt::emission_table(c->d_mats)) + first, emission, (size_t)n * sizeof(float));
 }
 
+int vrt_write_polish(vrt_ctx *c, uint32_t first, const vrt_polish *polish, uint32_t n) {
+    GRP_EACH(c, vrt_write_polish(d, first, polish, n));   // (every device refuses the same arguments: the first one stops it)
+    if (!c || (!polish && n)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_polish: null argument");
+    if ((uint64_t)first + n > 256) return fail(c, VRT_ERR_OUT_OF_RANGE, "vrt_write_polish: %u+%u > 256", first, n);
+    for (uint32_t i = 0; i < n; i++) {
+        const float v[5] = {polish[i].color[0], polish[i].color[1], polish[i].color[2], polish[i].chance, polish[i].scatter};
+        for (float x : v)
+            if (!(x >= 0.0f && x <= FLT_MAX))
+                return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_polish: entry %u holds %g: negative, NaN or infinite", first + i, (double)x);
+    }
+    if (n == 0) return VRT_OK;
+    c->accum_restart = true;
+    memcpy(c->h_polish + first, polish, (size_t)n * sizeof(vrt_polish));
+    uint32_t nz = 0;
+    for (const vrt_polish &e : c->h_polish) nz += e.chance != 0.0f ? 1u : 0u;
+    c->n_polished = nz;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return stage_upload(c, const_cast<vrt_polish *>(vrt::polish_table(c->d_mats)) + first, polish, (size_t)n * sizeof(vrt_polish));
+}
+
 int vrt_get_accel_info(vrt_ctx *c, vrt_accel_info *out) {
     GRP_ROOT(c, vrt_get_accel_info(d, out));
     if (!c || !out) return fail(c, VRT_ERR_INVALID_ARG, "vrt_get_accel_info: null argument");

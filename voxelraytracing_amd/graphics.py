@@ -128,6 +128,13 @@ class Gpu:
         v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
         self._ck(self._lib.vrt_write_emission(self._h, first, v.ctypes.data if v.size else None, v.size))
 
+    def write_polish(self, entries, first: int = 0):
+        """vrt_write_polish: entries [first, first + len(entries)) of the per-material polish table, the path trace's second,
+        specular lobe (MODE_PATH only; all 0 until written).  entries: an array of _ffi.POLISH_DTYPE (color, chance, scatter);
+        a negative, NaN or infinite float, or first + len(entries) > 256, raises VrtError and writes nothing."""
+        e = np.ascontiguousarray(entries, dtype=_ffi.POLISH_DTYPE).reshape(-1)
+        self._ck(self._lib.vrt_write_polish(self._h, first, e.ctypes.data if e.size else None, e.size))
+
     def write_cam_data(self, cam: CamData):
         self._ck(self._lib.vrt_set_camera(self._h, C.byref(cam)))
 
