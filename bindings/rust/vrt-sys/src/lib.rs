@@ -39,6 +39,15 @@ pub struct vrt_polish {
     pub _reserved: [u32; 3],
 }
 
+/// One entry of vrt_write_translucency's table: the pass-through lobe of path_tracer.wgsl's Material (translucency).
+/// All zero = opaque.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_translucency {
+    pub color: [f32; 3],
+    pub chance: f32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct vrt_cam_data {
@@ -287,6 +296,7 @@ extern "C" {
     pub fn vrt_write_materials(ctx: *mut vrt_ctx, first: u32, mats: *const vrt_material, n: u32) -> c_int;
     pub fn vrt_write_emission(ctx: *mut vrt_ctx, first: u32, emission: *const f32, n: u32) -> c_int;
     pub fn vrt_write_polish(ctx: *mut vrt_ctx, first: u32, polish: *const vrt_polish, n: u32) -> c_int;
+    pub fn vrt_write_translucency(ctx: *mut vrt_ctx, first: u32, entries: *const vrt_translucency, n: u32) -> c_int;
     pub fn vrt_set_camera(ctx: *mut vrt_ctx, cam: *const vrt_cam_data) -> c_int;
     pub fn vrt_set_settings(ctx: *mut vrt_ctx, settings: *const vrt_settings) -> c_int;
     pub fn vrt_set_world(ctx: *mut vrt_ctx, world: *const vrt_world_data) -> c_int;
@@ -346,5 +356,6 @@ mod layout {
         assert!(size_of::<vrt_denoise_opts>() == 16);
         assert!(size_of::<vrt_shape>() == 40);
         assert!(size_of::<vrt_polish>() == 32);
+        assert!(size_of::<vrt_translucency>() == 16);
     }
 }

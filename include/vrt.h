@@ -173,7 +173,7 @@ typedef struct {
  * s spp are, bit for bit, one frame of K * s spp with the same seed.  The sum starts again at n = 0 (without a device
  * step: the first frame stores it) after vrt_reset_accumulation, or when anything the image depends on has changed since
  * the previous accumulating frame: the camera, settings or world (byte-wise), any vrt_write_materials, a non-empty
- * vrt_write_emission or vrt_write_polish that is not refused, a non-empty vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
+ * vrt_write_emission, vrt_write_polish or vrt_write_translucency that is not refused, a non-empty vrt_write_nodes, a chunk_roots write that changes content, vrt_resize_world / vrt_resize_output, or another opts.seed.
  * Non-accumulating frames in between change nothing.  n + spp > 2^24: VRT_ERR_OUT_OF_RANGE, nothing enqueued. */
 #define VRT_RENDER_ACCUMULATE 4u
 
@@ -258,7 +258,7 @@ int vrt_write_emission(vrt_ctx *ctx, uint32_t first, const float *emission, uint
 /* New relative to the live reference: the rest of path_tracer.wgsl's Material — polish_bounce_chance, polish_color and
  * polish_scatter (:28-31), whose three uses in ray_color are commented out there (:175, :180, :185): a second, specular lobe.
  * A coin flip per hit chooses between the material's own lobe and a coat with a colour and a roughness of its own.
- * (translucency, :29 and :167-173, is not part of it.) */
+ * (translucency, :29 and :167-173, the struct's last field, is vrt_translucency below: a table of its own again.) */
 typedef struct {
     float    color[3];      /* what the throughput is multiplied by on a polished bounce; NOT face-shaded */
     float    chance;        /* a hit bounces off the coat when u < chance; 0 = never (the default) */
@@ -293,6 +293,54 @@ typedef struct {
  * accumulation, as vrt_write_emission does.  A context over several devices replicates the write to every device; a shard's
  * context keeps its own table. */
 int vrt_write_polish(vrt_ctx *ctx, uint32_t first, const vrt_polish *polish, uint32_t n);
+
+/* New relative to the live reference: the last field of path_tracer.wgsl's Material, translucency (:29), whose use in
+ * ray_color is commented out there (:167-173): a third lobe, through which a path passes straight on.  The reference's text
+ * cannot be taken literally — it restarts the ray 0.001 along its direction, inside the voxel it has just hit, which the
+ * next ray_world hits again on its first lookup until the bounces run out — so the pass is defined here.  Two things are
+ * the reference's: the draw stands ahead of the coat's draw, and a pass costs one of the path's segments. */
+typedef struct {
+    float color[3];   /* what the throughput is multiplied by when a path passes through; used as written, NOT face-shaded */
+    float chance;     /* a hit passes through when u < chance; 0 = never (the default) */
+} vrt_translucency;   /* 16 B: one load */
+/* The table: 256 entries per context, indexed like the material, emission and polish tables (voxel ids >= 255 use entry
+ * 255), all bytes 0 until written; entries [first, first + n) are copied at call time.  VRT_MODE_PATH only: the primary
+ * (+ shadow) modes ignore the table, and their frames are byte for byte what they are without it.
+ * A frame is translucent when at least one entry's chance != 0.0f.  A table whose chances are all +0 or -0 renders byte for
+ * byte as a context that never called this function — same kernels, nothing launched or allocated — whatever the colours
+ * hold.
+ * On every hit of a translucent frame after which the path may go on, the body of ray_color's loop is, in this order:
+ *   1. mc is the hit colour as without the table (face shading, or the step-count grey under show_step_count);
+ *   2. the emission term is unchanged, (mc * e) * thr, ahead of everything below: a pane that gives off light does so
+ *      whether or not the path passes;
+ *   3. ut = rng_next(rng): one draw on every hit, whatever that voxel's entry says, taken before the coat's draw u (a
+ *      polished frame only) and before the direction's six;
+ *   4. passes = ut < entry.chance (as for the coat: chance = 1 is "nearly always", any chance > 1 "always");
+ *   5. if passes: no further draw is taken (no u, no direction); thr *= entry.color per channel; dir is unchanged; the
+ *      origin moves across the one UNIT voxel that holds the hit position pos, whatever the size of the leaf the tree keeps
+ *      that voxel in (a re-canonicalised tree renders the same), all in strict binary32 with nothing contracted — per axis
+ *        c = floorf(pos); far = dir > 0 ? c + 1 : c; t_a = dir != 0 ? (far - pos) / dir : +inf;
+ *      then t = t_x; if (t_y < t) t = t_y; if (t_z < t) t = t_z (compares and selects, not fminf), and
+ *        origin = pos + dir * (t + 0.001f) per component, a multiply and then an add,
+ *      the form in which the march itself advances across an air node.  The next segment is an ordinary one from that
+ *      origin, with the march's usual start nudge; one that starts inside a solid voxel hits on its first lookup with a
+ *      zero normal, as any such segment does — a hit like any other, which draws ut again and can pass again.  A ray that
+ *      leaves the world misses and takes the sky;
+ *   6. if not: the body is exactly the polished or the unpolished body (vrt_write_polish above), the bounce origin
+ *      pos + norm * bias.
+ * A hit on the path's last allowed segment draws nothing that anything can observe; its emission is still added.
+ * What follows from that: id words and the primary segment are those of the frame without the table.  Writing the first
+ * non-zero chance shifts the RNG stream of every path by one draw per hit, so the frame changes even where no ray meets a
+ * translucent voxel.  At max_ray_bounces <= 1 the table changes nothing.  Liquids do not consult it: the march passes them
+ * itself.  The sums keep the emission contract: a sample's light is its terms in segment order with the sky last; the
+ * frame's light is its samples' lights in sample order, divided by spp.  VRT_RENDER_ACCUMULATE keeps its identity: K frames
+ * of s spp equal one frame of K * s spp, bit for bit.  The denoiser's key and guide come from the primary segment and are
+ * what they were.
+ * first + n > 256: VRT_ERR_OUT_OF_RANGE; entries NULL with n > 0, a null context, or any of an entry's four floats
+ * negative, NaN or infinite: VRT_ERR_INVALID_ARG — a refused call writes nothing.  n == 0 is a no-op; any other write
+ * restarts the accumulation, as vrt_write_emission does.  A context over several devices replicates the write to every
+ * device; a shard's context keeps its own table. */
+int vrt_write_translucency(vrt_ctx *ctx, uint32_t first, const vrt_translucency *entries, uint32_t n);
 
 /* SimpleBuffer<T>::write — shader.rs:101-106; callers main.rs:428,439,447-449. */
 int vrt_set_camera(vrt_ctx *ctx, const vrt_cam_data *cam);

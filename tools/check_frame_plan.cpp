@@ -102,12 +102,12 @@ struct PathRecord {
     bool acc_planes = false, accum_sum = false, out_is_planes = false, acc_set = false, zeroed = false;
     size_t cap = 0, path_buf = 0;
     uint32_t seg_cap = 0, acc_frames = 0, sample_base = 0, spp = 0, seed = 0, refill = 0;
-    bool kstats = false, literal = false, emit = false, polish = false;   // what the trace's launchers are given
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false;   // what the trace's launchers are given
     bool operator==(const PathRecord &o) const {
         return launches == o.launches && acc_planes == o.acc_planes && accum_sum == o.accum_sum && out_is_planes == o.out_is_planes &&
                acc_set == o.acc_set && zeroed == o.zeroed && cap == o.cap && path_buf == o.path_buf && seg_cap == o.seg_cap &&
                acc_frames == o.acc_frames && sample_base == o.sample_base && spp == o.spp && seed == o.seed && refill == o.refill &&
-               kstats == o.kstats && literal == o.literal && emit == o.emit && polish == o.polish;
+               kstats == o.kstats && literal == o.literal && emit == o.emit && polish == o.polish && translucent == o.translucent;
     }
 };
 constexpr uint32_t kHitSegments = 256;   // vrt_device.h
@@ -120,7 +120,7 @@ static PathRecord old_path_frame(const PathFacts &F) {
     const uint32_t spp = F.spp, bounces = F.bounces;                                                  // :325
     const uint32_t samples = (spp > 1u && !kstats && !literal && F.has_grid && bounces > 0) ? (spp < F.path_samples ? spp : F.path_samples) : 1u;   // :330
     const bool planes = samples > 1u;                                                                 // :331
-    const bool emit = F.emissive || F.polished;                                                       // :337 (vrt_write_polish, later: a polished frame is an emissive frame to everything but the launchers)
+    const bool emit = F.emissive || F.polished || F.translucent;                                                       // :337 (vrt_write_polish and vrt_write_translucency, later: such a frame is an emissive frame to everything but the launchers)
     const bool own_sum = emit && !planes && !accum && spp > 1u && bounces > 0;                        // :338
     const uint32_t seg_cap = F.hit_seg_cap * samples;                                                 // :339
     const size_t cap = (size_t)kHitSegments * seg_cap;                                                // :340
@@ -137,7 +137,7 @@ static PathRecord old_path_frame(const PathFacts &F) {
     r.sample_base = accum ? accum_from : 0u;                                                          // :372
     const bool pool = !kstats && !literal && F.has_grid && bounces > 1 && F.path_pool;                // :375
     const bool cells = pool && F.has_cells && F.path_cells;                                           // :376
-    r.kstats = kstats; r.literal = literal; r.emit = emit; r.polish = F.polished; r.refill = F.path_refill;   // :411, :418, :422
+    r.kstats = kstats; r.literal = literal; r.emit = emit; r.polish = F.polished; r.translucent = F.translucent; r.refill = F.path_refill;   // :411, :418, :422
     if (bounces == 0) r.zeroed = true;                                                                // :395
     uint32_t g = 0;                                                                                   // :397
     for (uint32_t smp = 0; smp < spp && bounces > 0; smp += samples) {                                // :398
@@ -181,7 +181,7 @@ static PathRecord new_path_frame(const PathFacts &F) {
     r.accum_sum = p.needs_accum_sum;
     r.seg_cap = p.seg_cap; r.acc_set = p.planes; r.out_is_planes = p.planes; r.cap = p.cap;
     r.spp = p.spp; r.seed = p.seed; r.sample_base = p.sample_base;
-    r.kstats = p.kstats; r.literal = p.literal; r.emit = p.emit; r.polish = p.polish; r.refill = p.refill;
+    r.kstats = p.kstats; r.literal = p.literal; r.emit = p.emit; r.polish = p.polish; r.translucent = p.translucent; r.refill = p.refill;
     r.zeroed = p.zero_output;
     const int sum_chain = p.finish_into_accum ? kContextSum : kFrame, sum_resolve = p.finish_into_accum ? kContextSum : kPlanes;
     vrt::for_each_path_step(p, [&](const PathStep &s) {
@@ -212,7 +212,7 @@ static void check_path_frames() {
     const int accums[] = {-1, 0, 7};   // not accumulating; accumulating from 0 and from 7 samples
     for (uint32_t spp : spps)
     for (uint32_t bounces = 0; bounces <= 5; bounces++)
-    for (uint32_t bits = 0; bits < 256; bits++)
+    for (uint32_t bits = 0; bits < 512; bits++)
     for (int accum : accums)
     for (uint32_t samples : per_chain)
     for (uint32_t kb : batches)
@@ -220,15 +220,15 @@ static void check_path_frames() {
         PathFacts F;
         F.spp = spp; F.seed = 11u; F.bounces = bounces;
         F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
-        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u;
         F.march_direct = F.has_cells;   // (no decision reads it)
         F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
         F.path_samples = samples; F.path_pool_batches = kb; F.path_refill = 16u; F.in_flight = in_flight; F.hit_seg_cap = 512u;
         // what cannot reach the function: a literal frame is never handed the tables (vrt_frame_plan.h: asks_for_tables), and the
         // march cells come with the tables (vrt_render fills P.mblk inside the branch that fills P.grid)
         if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) { skipped++; continue; }
-        std::snprintf(g_case, sizeof g_case, "path: spp %u bounces %u kstats %d literal %d grid %d cells %d emissive %d polished %d pool %d path_cells %d accum %d "
-                      "per chain %u batches %u in_flight %u", spp, bounces, F.kstats, F.literal, F.has_grid, F.has_cells, F.emissive, F.polished, F.path_pool,
+        std::snprintf(g_case, sizeof g_case, "path: spp %u bounces %u kstats %d literal %d grid %d cells %d emissive %d polished %d translucent %d pool %d path_cells %d accum %d "
+                      "per chain %u batches %u in_flight %u", spp, bounces, F.kstats, F.literal, F.has_grid, F.has_cells, F.emissive, F.polished, F.translucent, F.path_pool,
                       F.path_cells, accum, samples, kb, in_flight);
         const PathRecord o = old_path_frame(F), n = new_path_frame(F);
         CHECK(o.launches.size() == n.launches.size());

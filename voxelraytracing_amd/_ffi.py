@@ -132,6 +132,8 @@ BOX_QUERY_DTYPE = np.dtype([("from", "<f4", 3), ("flags", "<u4"), ("to", "<f4", 
 BOX_MOVE_DTYPE = np.dtype([("mv", "<f4", 3), ("status", "<u4"), ("flags", "<u4"), ("boxes", "<u4", 2), ("_reserved", "<u4")])
 # include/vrt.h vrt_polish: one entry of vrt_write_polish's table (32 bytes)
 POLISH_DTYPE = np.dtype([("color", "<f4", 3), ("chance", "<f4"), ("scatter", "<f4"), ("_reserved", "<u4", 3)])
+# include/vrt.h vrt_translucency: one entry of vrt_write_translucency's table (16 bytes)
+TRANSLUCENCY_DTYPE = np.dtype([("color", "<f4", 3), ("chance", "<f4")])
 
 
 assert C.sizeof(Material) == 32 and C.sizeof(CamData) == 160
@@ -142,6 +144,7 @@ assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 assert C.sizeof(DenoiseOpts) == 16
 assert POLISH_DTYPE.itemsize == 32
+assert TRANSLUCENCY_DTYPE.itemsize == 16
 
 MODE_PRIMARY, MODE_PRIMARY_SHADOW, MODE_PATH = 0, 1, 2
 RENDER_OWN_STREAMS, RENDER_TIMED, RENDER_ACCUMULATE = 1, 2, 4   # vrt_render_opts.flags (VRT_RENDER_*)
@@ -165,6 +168,7 @@ VRT_SYMBOLS = {
     "vrt_write_materials": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     "vrt_write_emission": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     "vrt_write_polish": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
+    "vrt_write_translucency": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32]),
     "vrt_set_camera": (C.c_int, [_P, C.POINTER(CamData)]),
     "vrt_set_settings": (C.c_int, [_P, C.POINTER(Settings)]),
     "vrt_set_world": (C.c_int, [_P, C.POINTER(WorldData)]),

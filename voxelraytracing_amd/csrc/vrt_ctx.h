@@ -73,9 +73,12 @@ void launch_shadow(const FrameParams &P, uint32_t variant, bool stats, hipStream
 void launch_primary_shadow_fused(const FrameParams &P, uint32_t march, bool stats, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 // emit: the kernels that add the light of emissive hits (vrt_write_emission; the table is the 256 floats after P.mats)
 // polish: the kernels that also flip the coat's coin on every hit (vrt_write_polish; the table behind the emission table) — given with emit
-void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st);
-void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st);
-void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, hipStream_t st);
+// translucent: the kernels that first draw whether the path passes through (vrt_write_translucency; the table behind the polish
+// table) — given with emit; they take the coat's draw under the word behind the tables, so polish chooses nothing among them
+void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, bool translucent, hipStream_t st);
+void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, bool translucent, hipStream_t st);
+void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, bool translucent,
+                              hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -191,7 +194,7 @@ struct vrt_ctx {
 
     Buf<uint16_t> d_nodes;
     Buf<uint32_t> d_roots;
-    Buf<vrt_material> d_mats;       // the 256 materials, then the 256 floats of the emission table (vrt::emission_table), then the 256 entries of the polish table (vrt::polish_table): kMatsAlloc
+    Buf<vrt_material> d_mats;       // the 256 materials, then the 256 floats of the emission table (vrt::emission_table), then the 256 entries of the polish table (vrt::polish_table), the 256 of the translucency table (vrt::translucency_table) and the coat word (vrt::coat_word): kMatsAlloc
     vrt::Texel *d_out = nullptr;    // where frames are written: sz.own_out or caller-bound memory
     // What the last frame was, for the calls that read it back or present it.  vrt_render assigns it whole once the frame is
     // enqueued: a call that returns an error leaves the record of the frame before it.  alloc_output, vrt_bind_output and the
@@ -385,11 +388,15 @@ struct vrt_ctx {
     Buf<uint16_t> d_edit_bins;
 
     vrt_material h_mats[256];
-    static constexpr size_t kMatsAlloc = 256 + 256 * sizeof(float) / sizeof(vrt_material) + 256 * sizeof(vrt_polish) / sizeof(vrt_material);   // d_mats, in materials
+    static constexpr size_t kMatsAlloc = 256 + 256 * sizeof(float) / sizeof(vrt_material) + 256 * sizeof(vrt_polish) / sizeof(vrt_material) +
+                                         256 * sizeof(vrt_translucency) / sizeof(vrt_material) + 1;   // d_mats, in materials (the last one holds the coat word)
     float h_emission[256];    // vrt_write_emission's table (zeros at creation) and how many of its entries are not 0: a frame
     uint32_t n_emissive = 0;  // of a context with none runs the kernels without the emission term
     vrt_polish h_polish[256]; // vrt_write_polish's table (zero bytes at creation) and how many of its entries have a chance that is
     uint32_t n_polished = 0;  // not 0: a frame of a context with none runs the kernels that do not flip the coat's coin
+    vrt_translucency h_translucency[256];   // vrt_write_translucency's table (zero bytes at creation) and how many of its entries
+    uint32_t n_translucent = 0;             // have a chance that is not 0: a frame of a context with none runs what ran before
+    uint32_t coat_word = 0;   // what the word behind the tables holds on the device: n_polished != 0 (vrt_write_polish keeps it)
     uint32_t liquid_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit v <=> h_mats[v].is_liquid == 1 (kept by vrt_write_materials)
     bool liquid_is_range = true;                          // the liquid ids are one range below 255, or none
     uint32_t liquid_lo = 0x80000000u, liquid_span = 0u;   // (none: no 15-bit voxel id is 0x80000000)

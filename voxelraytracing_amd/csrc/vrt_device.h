@@ -44,6 +44,16 @@ __host__ __device__ inline const vrt_polish *polish_table(const vrt_material *ma
     return reinterpret_cast<const vrt_polish *>(emission_table(mats) + kMaterials);
 }
 static_assert(sizeof(vrt_polish) == 32 && (kMaterials * (sizeof(vrt_material) + sizeof(float))) % 16 == 0, "the polish table's entries are 16-byte aligned");
+// vrt_write_translucency's table: 256 entries of 16 bytes behind the polish table (byte 17 408 of the allocation: an entry is one
+// 16-byte load), and behind it one word, the same for every lane: not 0 while the polish table has a chance that is not 0.  The
+// translucent kernels take the coat's draw under it (the uploads keep it: vrt_uploads.hip), so they exist once, not once per coat
+__host__ __device__ inline const vrt_translucency *translucency_table(const vrt_material *mats) {
+    return reinterpret_cast<const vrt_translucency *>(polish_table(mats) + kMaterials);
+}
+__host__ __device__ inline const uint32_t *coat_word(const vrt_material *mats) {
+    return reinterpret_cast<const uint32_t *>(translucency_table(mats) + kMaterials);
+}
+static_assert(sizeof(vrt_translucency) == 16, "a translucency entry is one 16-byte load");
 
 // Everything a frame's kernels read, passed by value (kernarg -> SGPRs).
 struct FrameParams {

@@ -89,6 +89,7 @@ struct PathFacts {   // copied out of the options, the context and the frame's p
     uint32_t accum_from = 0;        // ... with this many samples in the context's sum before the frame (accum_frame_start)
     bool emissive = false;          // vrt_write_emission: some material gives off light
     bool polished = false;          // vrt_write_polish: some material's coat has a chance that is not 0
+    bool translucent = false;       // vrt_write_translucency: some material lets a path through with a chance that is not 0
     // the context's switches (vrt_create reads them from the environment)
     uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
     bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
@@ -107,7 +108,7 @@ enum PathFinish : uint32_t {   // the pass behind each chain of samples
 
 struct PathPlan {   // each field is explained where plan_path sets it
     uint32_t spp = 1, seed = 0, bounces = 0;
-    bool kstats = false, literal = false, emit = false, polish = false;
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false;
     uint32_t samples = 1;
     bool planes = false, own_sum = false, cells = false;
     uint32_t seg_cap = 0;
@@ -140,8 +141,11 @@ inline PathPlan plan_path(const PathFacts &F) {
     // sample is one term, added straight to the texel, and a 1-spp frame's texel is its one sample either way.
     // vrt_write_polish: a polished frame's kernels carry the emission term (a zero entry adds nothing), so it is planned with
     // everything an emissive frame is planned with; polish is what the launchers switch on
-    p.emit = F.emissive || F.polished;
+    // vrt_write_translucency: the same again.  The translucent kernels are one family, whether the frame is polished or not
+    // (they take the coat's draw under a word the uploads keep on the device), so translucent is what the launchers look at first
+    p.emit = F.emissive || F.polished || F.translucent;
     p.polish = F.polished;
+    p.translucent = F.translucent;
     p.own_sum = p.emit && !p.planes && !F.accum && F.spp > 1u && F.bounces > 0u;
     // a segment of the path buffers holds what its workgroups can produce for every sample of a chain; a buffer, every segment
     p.seg_cap = F.hit_seg_cap * p.samples;

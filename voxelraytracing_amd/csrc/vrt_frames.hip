@@ -364,9 +364,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             sum_waited = true;
         }
         switch (s.kind) {
-            case kStepPrimary: launch_path_primary(P, plan.kstats, plan.literal, plan.emit, plan.polish, f.st); break;
-            case kStepLaneBounce: launch_path_bounce(P, plan.kstats, plan.literal, plan.emit, plan.polish, f.st); break;
-            case kStepCellsBounce: launch_path_bounce_cells(P, plan.refill, s.segments, plan.pool_batches, plan.emit, plan.polish, f.st); break;
+            case kStepPrimary: launch_path_primary(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
+            case kStepLaneBounce: launch_path_bounce(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
+            case kStepCellsBounce: launch_path_bounce_cells(P, plan.refill, s.segments, plan.pool_batches, plan.emit, plan.polish, plan.translucent, f.st); break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -480,6 +480,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     memset(c->h_mats, 0, sizeof c->h_mats);
     memset(c->h_emission, 0, sizeof c->h_emission);
     memset(c->h_polish, 0, sizeof c->h_polish);
+    memset(c->h_translucency, 0, sizeof c->h_translucency);
     memset(&c->cam, 0, sizeof c->cam);
     memset(&c->settings, 0, sizeof c->settings);
     memset(&c->world, 0, sizeof c->world);
@@ -499,9 +500,11 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         HIP_TRY(c, c->h_ring.ensure(vrt_ctx::kRingSegBytes * vrt_ctx::kRingSegs));
         HIP_TRY(c, hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0));
         static_assert(sizeof c->h_mats == vrt::kMaterials * sizeof(vrt_material), "the emission table follows the 256 materials");
-        static_assert(vrt_ctx::kMatsAlloc * sizeof(vrt_material) == sizeof c->h_mats + sizeof c->h_emission + sizeof c->h_polish, "whole materials");
-        HIP_TRY(c, c->d_mats.once(vrt_ctx::kMatsAlloc));   // + the emission table (vrt::emission_table) + the polish table (vrt::polish_table)
-        HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, sizeof c->h_mats + sizeof c->h_emission + sizeof c->h_polish, c->stream));
+        static_assert(vrt_ctx::kMatsAlloc * sizeof(vrt_material) == sizeof c->h_mats + sizeof c->h_emission + sizeof c->h_polish + sizeof c->h_translucency + sizeof(vrt_material),
+                      "whole materials");
+        // + the emission table (vrt::emission_table) + the polish table (vrt::polish_table) + the translucency table and the coat word
+        HIP_TRY(c, c->d_mats.once(vrt_ctx::kMatsAlloc));
+        HIP_TRY(c, hipMemsetAsync(c->d_mats, 0, vrt_ctx::kMatsAlloc * sizeof(vrt_material), c->stream));
         HIP_TRY(c, c->d_counters.once(kCounterWords));
         HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, kCounterBytes, c->stream));
         VRT_TRY(alloc_roots(c, cfg->world_size_chunks));
@@ -736,7 +739,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.spp = o.spp ? o.spp : 1u; PF.seed = o.seed; PF.bounces = c->settings.max_ray_bounces;
             PF.kstats = plan.kstats; PF.literal = plan.literal;
             PF.has_grid = P.grid != nullptr; PF.has_cells = P.mblk != nullptr; PF.march_direct = P.march_direct != 0u;
-            PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u;
+            PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u; PF.translucent = c->n_translucent != 0u;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
             PF.in_flight = c->in_flight; PF.hit_seg_cap = c->hit_seg_cap;

@@ -8,8 +8,10 @@
 // vrt_write_emission, 0 everywhere until a caller writes it; the kernels that add it are the EMIT instantiations below,
 // chosen by the host only for a context with an entry that is not 0 (a table of zeros runs the kernels that have no
 // emission term).  The coat of the same Material (:28-31, :175-185) is vrt_write_polish's table behind it, and the kernels
-// that flip its coin are the path_polished_* ones below, chosen only for a context with a chance that is not 0.  oracle/
-// keeps neither; the tests' references are tests/emission_ref.c and tests/polish_ref.c.  log and cos are
+// that flip its coin are the path_polished_* ones below, chosen only for a context with a chance that is not 0.  The struct's
+// last field, translucency (:29, :167-173), is vrt_write_translucency's table behind that one; the path_translucent_* kernels
+// draw first whether a hit lets the path through, and are chosen only for a context with such a chance.  oracle/
+// keeps none of them; the tests' references are tests/emission_ref.c, tests/polish_ref.c and tests/translucent_ref.c.  log and cos are
 // spelled out in + - * / so that host and device agree to the bit: a one-ulp different bounce direction eventually hits a
 // different voxel.
 //
@@ -29,33 +31,55 @@ static inline size_t lds_bytes_path(const FrameParams &P, bool lds_roots) { retu
 
 #define VRT_PRIMARY_KERNEL path_primary_kernel
 #define VRT_PRIMARY_POLISH 0
+#define VRT_PRIMARY_TRANSLUCENT 0
 #include "vrt_path_primary.h"
 #undef VRT_PRIMARY_KERNEL
 #undef VRT_PRIMARY_POLISH
+#undef VRT_PRIMARY_TRANSLUCENT
 #define VRT_PRIMARY_KERNEL path_polished_primary_kernel
 #define VRT_PRIMARY_POLISH 1
+#define VRT_PRIMARY_TRANSLUCENT 0
 #include "vrt_path_primary.h"
 #undef VRT_PRIMARY_KERNEL
 #undef VRT_PRIMARY_POLISH
+#undef VRT_PRIMARY_TRANSLUCENT
+#define VRT_PRIMARY_KERNEL path_translucent_primary_kernel
+#define VRT_PRIMARY_POLISH 0
+#define VRT_PRIMARY_TRANSLUCENT 1
+#include "vrt_path_primary.h"
+#undef VRT_PRIMARY_KERNEL
+#undef VRT_PRIMARY_POLISH
+#undef VRT_PRIMARY_TRANSLUCENT
 
 // One segment of a path: its march, then path_after_march.
-template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT, bool POLISH>
+template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT, bool POLISH, bool TRANSLUCENT>
 __device__ __forceinline__ bool path_segment(const FrameParams &P, const uint32_t *s_roots, const uint32_t *s_liquid,
                                              PathState &st, MarchResult &R, V3 &light, bool &lit) {
     R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, st.origin, st.dir);
-    return path_after_march<EMIT, POLISH>(P, st, R, light, lit);
+    return path_after_march<EMIT, POLISH, TRANSLUCENT>(P, st, R, light, lit);
 }
 
 #define VRT_BOUNCE_KERNEL path_bounce_kernel
 #define VRT_BOUNCE_POLISH 0
+#define VRT_BOUNCE_TRANSLUCENT 0
 #include "vrt_path_bounce.h"
 #undef VRT_BOUNCE_KERNEL
 #undef VRT_BOUNCE_POLISH
+#undef VRT_BOUNCE_TRANSLUCENT
 #define VRT_BOUNCE_KERNEL path_polished_bounce_kernel
 #define VRT_BOUNCE_POLISH 1
+#define VRT_BOUNCE_TRANSLUCENT 0
 #include "vrt_path_bounce.h"
 #undef VRT_BOUNCE_KERNEL
 #undef VRT_BOUNCE_POLISH
+#undef VRT_BOUNCE_TRANSLUCENT
+#define VRT_BOUNCE_KERNEL path_translucent_bounce_kernel
+#define VRT_BOUNCE_POLISH 0
+#define VRT_BOUNCE_TRANSLUCENT 1
+#include "vrt_path_bounce.h"
+#undef VRT_BOUNCE_KERNEL
+#undef VRT_BOUNCE_POLISH
+#undef VRT_BOUNCE_TRANSLUCENT
 
 
 // ------------------------------------------------------------------------------------------------
@@ -82,24 +106,39 @@ __device__ __forceinline__ bool path_segment(const FrameParams &P, const uint32_
 #define VRT_CELLS_KERNEL path_bounce_cells_kernel
 #define VRT_CELLS_EMIT 0
 #define VRT_CELLS_POLISH 0
+#define VRT_CELLS_TRANSLUCENT 0
 #include "vrt_path_cells.h"
 #undef VRT_CELLS_KERNEL
 #undef VRT_CELLS_EMIT
 #undef VRT_CELLS_POLISH
+#undef VRT_CELLS_TRANSLUCENT
 #define VRT_CELLS_KERNEL path_emissive_cells_kernel
 #define VRT_CELLS_EMIT 1
 #define VRT_CELLS_POLISH 0
+#define VRT_CELLS_TRANSLUCENT 0
 #include "vrt_path_cells.h"
 #undef VRT_CELLS_KERNEL
 #undef VRT_CELLS_EMIT
 #undef VRT_CELLS_POLISH
+#undef VRT_CELLS_TRANSLUCENT
 #define VRT_CELLS_KERNEL path_polished_cells_kernel
 #define VRT_CELLS_EMIT 1
 #define VRT_CELLS_POLISH 1
+#define VRT_CELLS_TRANSLUCENT 0
 #include "vrt_path_cells.h"
 #undef VRT_CELLS_KERNEL
 #undef VRT_CELLS_EMIT
 #undef VRT_CELLS_POLISH
+#undef VRT_CELLS_TRANSLUCENT
+#define VRT_CELLS_KERNEL path_translucent_cells_kernel
+#define VRT_CELLS_EMIT 1
+#define VRT_CELLS_POLISH 0
+#define VRT_CELLS_TRANSLUCENT 1
+#include "vrt_path_cells.h"
+#undef VRT_CELLS_KERNEL
+#undef VRT_CELLS_EMIT
+#undef VRT_CELLS_POLISH
+#undef VRT_CELLS_TRANSLUCENT
 
 
 // The end of a launch chain of several samples: the running sum plus the chain's planes, in sample order — the order the
@@ -203,23 +242,28 @@ __global__ void path_finish_kernel(Texel *out, uint32_t n, float spp) {
 #define VRT_BOUNCE_EMIT , true                  // (EMIT)
 
 // polish (vrt_write_polish; the frame plan gives it with emit): the kernels of the same three families that flip the coat's coin
-void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st) {
+// translucent (vrt_write_translucency; with emit as well): the path_translucent_* kernels, whatever polish says — they read on the
+// device whether there is a coat
+void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, bool translucent, hipStream_t st) {
     if (P.tiles_local == 0) return;
     const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
     if (P.acc) {   // several samples per launch chain: plain frames over the derived tables only (vrt_frames.hip)
-        if (polish) hipLaunchKernelGGL((path_polished_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
+        if (translucent) hipLaunchKernelGGL((path_translucent_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
+        else if (polish) hipLaunchKernelGGL((path_polished_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
         else if (emit) hipLaunchKernelGGL((path_primary_kernel<0, false, false, true, true>), grid, block, lds_bytes_path(P, false), st, P);
         else hipLaunchKernelGGL((path_primary_kernel<0, false, false, true>), grid, block, lds_bytes_path(P, false), st, P);
         return;
     }
-    if (polish) VRT_PATH_LAUNCH(path_polished_primary_kernel, VRT_PRIMARY_EMIT);
+    if (translucent) VRT_PATH_LAUNCH(path_translucent_primary_kernel, VRT_PRIMARY_EMIT);
+    else if (polish) VRT_PATH_LAUNCH(path_polished_primary_kernel, VRT_PRIMARY_EMIT);
     else if (emit) VRT_PATH_LAUNCH(path_primary_kernel, VRT_PRIMARY_EMIT);
     else VRT_PATH_LAUNCH(path_primary_kernel, );
 }
 
 // the pool kernel over the march cells (P.mblk): `segments` bounce segments in this one launch (every wave carries its own
 // survivors from one to the next; P.path_in / P.path_out are the two buffers it goes back and forth between)
-void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, hipStream_t st) {
+void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, bool translucent,
+                              hipStream_t st) {
     if (P.tiles_local == 0 || segments == 0) return;
     const uint32_t refill = refill_at >= 1u && refill_at <= 64u ? refill_at : kPoolRefillAt;
     const uint32_t kb = (pool_batches == 5u && P.march_direct) ? 5u : 4u, entries = kb * 64u;   // (320-ray pools: direct worlds only)
@@ -227,6 +271,12 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
     const dim3 grid(kHitSegments * parts), block(256);
     const size_t sh = 8u * 4u + 4u * (entries * 16u + entries * 2u);   // per wave: the pool + a u16 order per entry
     const CellsLaunch L{P, refill, segments};
+    if (translucent) {
+        if (kb == 5u) hipLaunchKernelGGL((path_translucent_cells_kernel<true, 5u>), grid, block, sh, st, L);
+        else if (P.march_direct) hipLaunchKernelGGL((path_translucent_cells_kernel<true, 4u>), grid, block, sh, st, L);
+        else hipLaunchKernelGGL((path_translucent_cells_kernel<false, 4u>), grid, block, sh, st, L);
+        return;
+    }
     if (polish) {
         if (kb == 5u) hipLaunchKernelGGL((path_polished_cells_kernel<true, 5u>), grid, block, sh, st, L);
         else if (P.march_direct) hipLaunchKernelGGL((path_polished_cells_kernel<true, 4u>), grid, block, sh, st, L);
@@ -244,10 +294,11 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
     else hipLaunchKernelGGL((path_bounce_cells_kernel<false, 4u>), grid, block, sh, st, L);
 }
 
-void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, hipStream_t st) {
+void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, bool translucent, hipStream_t st) {
     if (P.tiles_local == 0) return;
     const dim3 grid(kHitSegments * (P.hit_seg_cap / 256u)), block(256);
-    if (polish) VRT_PATH_LAUNCH(path_polished_bounce_kernel, VRT_BOUNCE_EMIT);
+    if (translucent) VRT_PATH_LAUNCH(path_translucent_bounce_kernel, VRT_BOUNCE_EMIT);
+    else if (polish) VRT_PATH_LAUNCH(path_polished_bounce_kernel, VRT_BOUNCE_EMIT);
     else if (emit) VRT_PATH_LAUNCH(path_bounce_kernel, VRT_BOUNCE_EMIT);
     else VRT_PATH_LAUNCH(path_bounce_kernel, );
 }

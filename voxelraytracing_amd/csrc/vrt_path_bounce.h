@@ -1,12 +1,13 @@
-// vrt_path_bounce.h — the lane = path bounce kernel, for vrt_path.hip, included there twice: as path_bounce_kernel
-// (VRT_BOUNCE_POLISH 0) and as path_polished_bounce_kernel (VRT_BOUNCE_POLISH 1: vrt_write_polish; instantiated with EMIT
-// alone), for the reasons vrt_path_primary.h gives.
-// In: VRT_BOUNCE_KERNEL (the kernel's name), VRT_BOUNCE_POLISH (0 or 1).
+// vrt_path_bounce.h — the lane = path bounce kernel, for vrt_path.hip, included there three times: as path_bounce_kernel
+// (VRT_BOUNCE_POLISH 0), as path_polished_bounce_kernel (VRT_BOUNCE_POLISH 1: vrt_write_polish; instantiated with EMIT
+// alone) and as path_translucent_bounce_kernel (VRT_BOUNCE_TRANSLUCENT 1: vrt_write_translucency; EMIT alone), for the reasons
+// vrt_path_primary.h gives.
+// In: VRT_BOUNCE_KERNEL (the kernel's name), VRT_BOUNCE_POLISH, VRT_BOUNCE_TRANSLUCENT (0 or 1).
 
 // Bounce b >= 1: lane = one live path of the in buffer.  EMIT: emissive hits add their light too (vrt_write_emission).
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT = false>
 __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
-    constexpr bool POLISH = VRT_BOUNCE_POLISH;
+    constexpr bool POLISH = VRT_BOUNCE_POLISH, TRANSLUCENT = VRT_BOUNCE_TRANSLUCENT;
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem, *s_roots = smem + 24;
     unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
@@ -36,7 +37,7 @@ __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
         st.thr = V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
         V3 light{0.f, 0.f, 0.f};
         bool lit;
-        alive = path_segment<MARCH, LDS_ROOTS, STATS, EMIT, POLISH>(P, s_roots, s_liquid, st, R, light, lit) && !P.last_bounce;
+        alive = path_segment<MARCH, LDS_ROOTS, STATS, EMIT, POLISH, TRANSLUCENT>(P, s_roots, s_liquid, st, R, light, lit) && !P.last_bounce;
         if (lit) {
             uint4 t = P.out[st.slot];
             t.x = __float_as_uint(__uint_as_float(t.x) + light.x);

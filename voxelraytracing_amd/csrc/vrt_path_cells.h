@@ -1,15 +1,16 @@
-// vrt_path_cells.h — the body of the pool kernel over the march cells (vrt_path.hip), included there three times: as
+// vrt_path_cells.h — the body of the pool kernel over the march cells (vrt_path.hip), included there four times: as
 // path_bounce_cells_kernel (VRT_CELLS_EMIT 0, the plain frame's), as path_emissive_cells_kernel (VRT_CELLS_EMIT 1: emissive
-// hits add their light too, vrt_write_emission — the hits of the last segment included) and as path_polished_cells_kernel
-// (VRT_CELLS_POLISH 1, with EMIT: phase C also flips the coat's coin, vrt_write_polish).  Kernels of their own rather
+// hits add their light too, vrt_write_emission — the hits of the last segment included), as path_polished_cells_kernel
+// (VRT_CELLS_POLISH 1, with EMIT: phase C also flips the coat's coin, vrt_write_polish) and as path_translucent_cells_kernel
+// (VRT_CELLS_TRANSLUCENT 1, with EMIT: phase C first draws whether the path passes, vrt_write_translucency).  Kernels of their own rather
 // than more template arguments: the plain one keeps its name, its three instantiations and, as the kernel's own body
 // rather than an inlined function, its instruction stream.
-// In: VRT_CELLS_KERNEL (the kernel's name), VRT_CELLS_EMIT, VRT_CELLS_POLISH (0 or 1).
+// In: VRT_CELLS_KERNEL (the kernel's name), VRT_CELLS_EMIT, VRT_CELLS_POLISH, VRT_CELLS_TRANSLUCENT (0 or 1).
 
 template <bool DIRECT, uint32_t KB>
 __attribute__((amdgpu_waves_per_eu(8, 8)))
 __global__ void __launch_bounds__(256) VRT_CELLS_KERNEL(CellsLaunch L) {
-    constexpr bool EMIT = VRT_CELLS_EMIT, POLISH = VRT_CELLS_POLISH;
+    constexpr bool EMIT = VRT_CELLS_EMIT, POLISH = VRT_CELLS_POLISH, TRANSLUCENT = VRT_CELLS_TRANSLUCENT;
     const FrameParams &K = L.P;
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem;
@@ -445,7 +446,7 @@ __global__ void __launch_bounds__(256) VRT_CELLS_KERNEL(CellsLaunch L) {
             V3 light{0.f, 0.f, 0.f};
             bool lit;
             if (EMIT && last_bounce && j < n_hit) lit = path_emission(P, R, hit_color(P, R), st.thr, light);   // (the path ends here)
-            else alive = path_after_march<EMIT, POLISH>(P, st, R, light, lit) && !last_bounce;
+            else alive = path_after_march<EMIT, POLISH, TRANSLUCENT>(P, st, R, light, lit) && !last_bounce;
             if (lit) {
                 uint4 t = P.out[st.slot];
                 t.x = __float_as_uint(__uint_as_float(t.x) + light.x);

@@ -97,12 +97,63 @@ __device__ __forceinline__ bool path_emission(const FrameParams &P, const MarchR
     return true;
 }
 
+// A hit of a translucent frame (vrt_write_translucency, include/vrt.h: steps 3 to 6 there; the family of path_translucent_*
+// kernels).  ut is drawn on every hit, ahead of everything else; a lane whose ut is below its entry's chance passes: it keeps
+// dir, crosses the unit voxel that holds the hit position, multiplies thr by the entry's colour and draws nothing more.  Every
+// other lane runs the body of path_after_march below — the coat's draw under the word behind the tables (the same for every
+// lane: a scalar branch), so that this family exists once, polished or not.  The RNG state, origin, dir and tint are selected per
+// lane; the bounce's draws (three logs, three square roots, three cosines) are branched around only where the whole wave passes.
+__device__ __forceinline__ void path_translucent_hit(const FrameParams &P, PathState &st, const MarchResult &R, const V3 &mc) {
+    const uint32_t entry = min(R.voxel, 255u);
+    const float4 tc = *reinterpret_cast<const float4 *>(&translucency_table(P.mats)[entry]);   // color + chance: one load
+    const float ut = rng_next(st.rng);
+    const bool passes = ut < tc.w;
+    uint32_t rng = st.rng;
+    V3 origin = R.pos, dir = st.dir, tint{tc.x, tc.y, tc.z};
+    if (__ballot(!passes) != 0ull) {
+        const bool coat = __builtin_amdgcn_readfirstlane(*coat_word(P.mats)) != 0u;
+        const float d = vdot(R.norm, st.dir);
+        const V3 spec{st.dir.x - 2.0f * R.norm.x * d, st.dir.y - 2.0f * R.norm.y * d, st.dir.z - 2.0f * R.norm.z * d};
+        float u = 0.0f;
+        if (coat) u = rng_next(rng);
+        const V3 rd = rng_next_dir(rng);
+        const V3 sc = normalize_wave(V3{R.norm.x + rd.x, R.norm.y + rd.y, R.norm.z + rd.z});
+        const vrt_polish *e = &polish_table(P.mats)[entry];
+        const float4 cc = *reinterpret_cast<const float4 *>(e);
+        const bool polished = coat && u < cc.w;
+        const float scatter = polished ? e->scatter : P.mats[entry].scatter;
+        const V3 nd = normalize_wave(V3{vmix(spec.x, sc.x, scatter), vmix(spec.y, sc.y, scatter), vmix(spec.z, sc.z, scatter)});
+        if (!passes) {
+            tint = V3{polished ? cc.x : mc.x, polished ? cc.y : mc.y, polished ? cc.z : mc.z};
+            origin = V3{R.pos.x + R.norm.x * kShadowBias, R.pos.y + R.norm.y * kShadowBias, R.pos.z + R.norm.z * kShadowBias};
+            dir = nd;
+            st.rng = rng;
+        }
+    }
+    // the pass: across the unit voxel of the hit position, in the form the march advances across an air node (compares and selects)
+    const float inf = __builtin_inff();
+    const float cx = floorf(R.pos.x), cy = floorf(R.pos.y), cz = floorf(R.pos.z);
+    const float tx = st.dir.x != 0.0f ? ((st.dir.x > 0.0f ? cx + 1.0f : cx) - R.pos.x) / st.dir.x : inf;
+    const float ty = st.dir.y != 0.0f ? ((st.dir.y > 0.0f ? cy + 1.0f : cy) - R.pos.y) / st.dir.y : inf;
+    const float tz = st.dir.z != 0.0f ? ((st.dir.z > 0.0f ? cz + 1.0f : cz) - R.pos.z) / st.dir.z : inf;
+    float t = tx;
+    if (ty < t) t = ty;
+    if (tz < t) t = tz;
+    const float ts = t + 0.001f;
+    if (passes) origin = V3{R.pos.x + st.dir.x * ts, R.pos.y + st.dir.y * ts, R.pos.z + st.dir.z * ts};
+    st.thr = V3{st.thr.x * tint.x, st.thr.y * tint.y, st.thr.z * tint.z};
+    st.origin = origin;
+    st.dir = dir;
+}
+
 // What follows a segment's march (the rest of the body of ray_color's loop, path_tracer.wgsl:155-192).  Returns true if the
 // path goes on (st updated to the next segment); a miss puts the sky's light, weighted, into `light`, and so does — EMIT — a
 // hit on an emissive voxel its own.  lit: `light` holds a term for the sample's texel.
 // POLISH (vrt_write_polish; :175, :180, :185): every hit draws u ahead of the direction's six draws, and where u is below the
 // chance of the voxel's entry of the polish table, the entry's scatter and colour take the place of the material's scatter and mc.
-template <bool EMIT = false, bool POLISH = false>
+// TRANSLUCENT (vrt_write_translucency; :167-173): path_translucent_hit above in the place of everything behind the emission term;
+// POLISH is then not read (the coat's draw is under the word behind the tables).
+template <bool EMIT = false, bool POLISH = false, bool TRANSLUCENT = false>
 __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
     lit = !R.hit;
     if (!R.hit) {
@@ -112,6 +163,10 @@ __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState
     }
     const V3 mc = hit_color(P, R);
     if (EMIT) lit = path_emission(P, R, mc, st.thr, light);   // (before thr *= mc: :183-186)
+    if (TRANSLUCENT) {
+        path_translucent_hit(P, st, R, mc);
+        return true;
+    }
     const float d = vdot(R.norm, st.dir);
     const V3 spec{st.dir.x - 2.0f * R.norm.x * d, st.dir.y - 2.0f * R.norm.y * d, st.dir.z - 2.0f * R.norm.z * d};
     float u = 0.0f;

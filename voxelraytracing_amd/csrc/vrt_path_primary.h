@@ -1,15 +1,16 @@
-// vrt_path_primary.h — bounce 0 of the path trace, for vrt_path.hip, included there twice: as path_primary_kernel
-// (VRT_PRIMARY_POLISH 0) and as path_polished_primary_kernel (VRT_PRIMARY_POLISH 1: the frames of a context with a coat,
-// vrt_write_polish; instantiated with EMIT alone).  A kernel of its own rather than one more template argument, as the pool
+// vrt_path_primary.h — bounce 0 of the path trace, for vrt_path.hip, included there three times: as path_primary_kernel
+// (VRT_PRIMARY_POLISH 0), as path_polished_primary_kernel (VRT_PRIMARY_POLISH 1: the frames of a context with a coat,
+// vrt_write_polish; instantiated with EMIT alone) and as path_translucent_primary_kernel (VRT_PRIMARY_TRANSLUCENT 1: the frames of
+// a context that lets paths through, vrt_write_translucency; EMIT alone again, the coat's draw under a word on the device).  A kernel of its own rather than one more template argument, as the pool
 // kernel's body has it (vrt_path_cells.h): the plain and the emissive kernels keep their names and their instruction streams.
-// In: VRT_PRIMARY_KERNEL (the kernel's name), VRT_PRIMARY_POLISH (0 or 1).
+// In: VRT_PRIMARY_KERNEL (the kernel's name), VRT_PRIMARY_POLISH, VRT_PRIMARY_TRANSLUCENT (0 or 1).
 
 // Bounce 0: primary rays of sample P.sample. Sample 0 initialises the texel {light, id}; later samples add.
 // MULTI: the samples of a launch chain (P.acc, P.chain) share the primary march; otherwise one sample, straight into `out`
 // EMIT: emissive hits add their light too (vrt_write_emission) — a later sample's texel is then written on those as well
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool MULTI = false, bool EMIT = false>
 __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
-    constexpr bool POLISH = VRT_PRIMARY_POLISH;
+    constexpr bool POLISH = VRT_PRIMARY_POLISH, TRANSLUCENT = VRT_PRIMARY_TRANSLUCENT;
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem, *s_roots = smem + 24;
     unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
@@ -51,7 +52,7 @@ __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
             st.rng = py * P.width + px + (P.sample_base + sample) * (P.width * P.height) + P.seed * 0x9E3779B9u;
             V3 light{0.f, 0.f, 0.f};
             bool lit;
-            const bool alive = path_after_march<EMIT, POLISH>(P, st, R, light, lit) && !P.last_bounce;
+            const bool alive = path_after_march<EMIT, POLISH, TRANSLUCENT>(P, st, R, light, lit) && !P.last_bounce;
             if (MULTI) {
                 // this sample's own plane: its light so far and, for the frame's first sample, the id word (0 otherwise);
                 // the path's later segments find the plane through the slot

@@ -682,6 +682,16 @@ int vrt_write_emission(vrt_ctx *c, uint32_t first, const float *emission, uint32
     return stage_upload(c, const_cast<float *>(vrt::emission_table(c->d_mats)) + first, emission, (size_t)n * sizeof(float));
 }
 
+// The word behind the tables (vrt::coat_word): whether the polish table has a chance that is not 0.  The translucent kernels
+// take the coat's draw under it.  Written behind a write of the polish table, and only when it changes: the word is 0 at creation.
+static int write_coat_word(vrt_ctx *c) {
+    const uint32_t want = c->n_polished != 0u ? 1u : 0u;
+    if (want == c->coat_word) return VRT_OK;
+    const int rc = stage_upload(c, const_cast<uint32_t *>(vrt::coat_word(c->d_mats)), &want, sizeof want);
+    if (!rc) c->coat_word = want;
+    return rc;
+}
+
 int vrt_write_polish(vrt_ctx *c, uint32_t first, const vrt_polish *polish, uint32_t n) {
     GRP_EACH(c, vrt_write_polish(d, first, polish, n));   // (every device refuses the same arguments: the first one stops it)
     if (!c || (!polish && n)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_polish: null argument");
@@ -699,7 +709,28 @@ int vrt_write_polish(vrt_ctx *c, uint32_t first, const vrt_polish *polish, uint3
     for (const vrt_polish &e : c->h_polish) nz += e.chance != 0.0f ? 1u : 0u;
     c->n_polished = nz;
     HIP_TRY(c, hipSetDevice(c->device));
-    return stage_upload(c, const_cast<vrt_polish *>(vrt::polish_table(c->d_mats)) + first, polish, (size_t)n * sizeof(vrt_polish));
+    const int rc = stage_upload(c, const_cast<vrt_polish *>(vrt::polish_table(c->d_mats)) + first, polish, (size_t)n * sizeof(vrt_polish));
+    return rc ? rc : write_coat_word(c);
+}
+
+int vrt_write_translucency(vrt_ctx *c, uint32_t first, const vrt_translucency *entries, uint32_t n) {
+    GRP_EACH(c, vrt_write_translucency(d, first, entries, n));   // (every device refuses the same arguments: the first one stops it)
+    if (!c || (!entries && n)) return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_translucency: null argument");
+    if ((uint64_t)first + n > 256) return fail(c, VRT_ERR_OUT_OF_RANGE, "vrt_write_translucency: %u+%u > 256", first, n);
+    for (uint32_t i = 0; i < n; i++) {
+        const float v[4] = {entries[i].color[0], entries[i].color[1], entries[i].color[2], entries[i].chance};
+        for (float x : v)
+            if (!(x >= 0.0f && x <= FLT_MAX))
+                return fail(c, VRT_ERR_INVALID_ARG, "vrt_write_translucency: entry %u holds %g: negative, NaN or infinite", first + i, (double)x);
+    }
+    if (n == 0) return VRT_OK;
+    c->accum_restart = true;
+    memcpy(c->h_translucency + first, entries, (size_t)n * sizeof(vrt_translucency));
+    uint32_t nz = 0;
+    for (const vrt_translucency &e : c->h_translucency) nz += e.chance != 0.0f ? 1u : 0u;
+    c->n_translucent = nz;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return stage_upload(c, const_cast<vrt_translucency *>(vrt::translucency_table(c->d_mats)) + first, entries, (size_t)n * sizeof(vrt_translucency));
 }
 
 int vrt_get_accel_info(vrt_ctx *c, vrt_accel_info *out) {

@@ -135,6 +135,13 @@ class Gpu:
         e = np.ascontiguousarray(entries, dtype=_ffi.POLISH_DTYPE).reshape(-1)
         self._ck(self._lib.vrt_write_polish(self._h, first, e.ctypes.data if e.size else None, e.size))
 
+    def write_translucency(self, entries, first: int = 0):
+        """vrt_write_translucency: entries [first, first + len(entries)) of the per-material translucency table, the path
+        trace's pass-through lobe (MODE_PATH only; all 0 until written).  entries: an array of _ffi.TRANSLUCENCY_DTYPE (color,
+        chance); a negative, NaN or infinite float, or first + len(entries) > 256, raises VrtError and writes nothing."""
+        e = np.ascontiguousarray(entries, dtype=_ffi.TRANSLUCENCY_DTYPE).reshape(-1)
+        self._ck(self._lib.vrt_write_translucency(self._h, first, e.ctypes.data if e.size else None, e.size))
+
     def write_cam_data(self, cam: CamData):
         self._ck(self._lib.vrt_set_camera(self._h, C.byref(cam)))
 
