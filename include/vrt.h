@@ -415,6 +415,43 @@ int vrt_set_denoise(vrt_ctx *ctx, const vrt_denoise_opts *opts);
  * Synchronises.  VRT_ERR_STATE before the first denoised frame (and after a resize until the next one). */
 int vrt_read_guide(vrt_ctx *ctx, uint32_t *guide);
 
+/* Direct sunlight for VRT_MODE_PATH: next-event estimation towards the scene's one light.  ray_sky's sun is a disc of
+ * dot(dir, sun_dir) > 0.99, which a random bounce rarely leaves the world through; with vrt_set_sun_light every hit of a path
+ * sends a ray to the sun instead.  The primary modes ignore the setting and stay byte for byte what they are.  Build-defined,
+ * and defined exactly — the body of ray_color's loop, in strict binary32, nothing contracted:
+ *   1  mc and the emission term (vrt_write_emission) as without the setting: (mc * e) * thr
+ *   2  the sun term, on every hit — the primary segment's and the last allowed segment's included — whose voxel is not 0 and
+ *      not a liquid:
+ *        so = pos + norm * bias per component (the bounce origin; the shadow ray's origin of VRT_MODE_PRIMARY_SHADOW)
+ *        sd = normalize(sun_pos - f32(world.min) - so)
+ *        c  = dot(norm, sd);  only if c > 0 (a zero normal or a NaN gives no ray): march ray_world(so, sd), start nudge included
+ *        unoccluded = the march does not hit: liquids are passed, running out of steps counts as occluded, a ray that starts
+ *        or ends outside the world is unoccluded
+ *        if unoccluded:  k = settings.sun_intensity * strength;  w = k * c;  light.ch += (mc.ch * w) * thr.ch
+ *      mc is the face-shaded colour (or the step-count grey), never the coat's colour
+ *   3  everything behind it unchanged, in the order it has: the pass-through draw, the coat's draw, the direction, thr *= tint.
+ *      The sun term draws nothing: the RNG stream, every path direction, the id words and vrt_read_steps' counts are those of
+ *      the frame without the setting
+ *   4  a segment other than the primary that misses takes ray_sky with add = +0.0f (the sky of a scene whose sun_intensity
+ *      is 0): its surface received the sun in step 2, and the disc is not counted twice.  The primary segment's miss still
+ *      shows the disc.  Specular glints of the sun are lost
+ *   5  a sample's light is its terms in segment order — within a segment the emission term, then the sun term — the sky last;
+ *      a frame's light is its samples' lights in sample order, divided by spp.  VRT_RENDER_ACCUMULATE keeps its identity (K
+ *      frames of s spp are one frame of K * s spp, bit for bit); the denoiser's key and guide are unchanged
+ *   6  vrt_stats.secondary_rays counts every sun ray marched as well; a stats frame's steps and node_visits include the sun
+ *      marches; a timed frame's ms_secondary includes the sun launches
+ * opts NULL or strength +0 / -0: off, the default — frames are byte for byte those of a context that never called this, the
+ * same kernels run, and nothing is launched or allocated.  strength negative, NaN or infinite, flags or _reserved not 0, a
+ * null context: VRT_ERR_INVALID_ARG; a refused call changes nothing.  A call that changes the setting (off is 16 zero bytes)
+ * restarts the accumulation; one that does not, does not.  A multi-device context replicates the setting; a shard context keeps
+ * its own. */
+typedef struct {
+    float    strength;      /* 0 = off (the default); the sun term's factor on settings.sun_intensity */
+    uint32_t flags;         /* 0 */
+    uint32_t _reserved[2];  /* 0 */
+} vrt_sun_light;            /* 16 B */
+int vrt_set_sun_light(vrt_ctx *ctx, const vrt_sun_light *opts);
+
 /* Block until everything enqueued on the context's stream has finished. */
 int vrt_synchronize(vrt_ctx *ctx);
 

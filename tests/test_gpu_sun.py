@@ -1,0 +1,289 @@
+"""Direct sunlight in the path trace (vrt_set_sun_light, include/vrt.h) on the GPU.
+
+Against tests/sun_ref.c (the oracle's path loop with a sun ray from every hit) on every route through the kernels — the default
+(the occlusion-only march over the march cells in the direct layout), the march cells behind a chunk directory, the literal
+march (air flagged liquid) and the counting kernels of a stats frame — at one wave, two waves, a frame whose size is not whole
+tiles and a frame of several workgroups; 1, 2 and 4 bounces; 1, 3 and 12 samples; one and two frames in flight; the sun alone and
+with the emission, polish and translucency tables set as tests/test_gpu_translucent.py sets them.  Frames against the reference:
+util.assert_frame_parity (id words equal, radiance within RADIANCE_TOL).  A stats frame's secondary rays and steps are the
+reference's counts.  GPU against GPU, bit for bit: strength 0 after strength 1, accumulation, the primary modes, the denoiser's
+guide, two shards.  Every test here calls vrt_set_sun_light."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import emission_cases as E
+import polish_ref
+import sun_ref
+import translucent_ref
+from voxelraytracing_amd import MODE_PATH, MODE_PRIMARY, MODE_PRIMARY_SHADOW, _ffi, scenes
+
+from util import assert_frame_parity, gpu_for_scene
+
+pytestmark = pytest.mark.gpu
+
+SEED = 11
+STRENGTH = 1.0
+SIZES = [(8, 8), (16, 8), (100, 60), (128, 72)]
+BOUNCES = (1, 2, 4)
+SPPS = (1, 3, 12)
+ENV = ["VRT_MARCH_DIRECT_MAX_S", "VRT_PATH_POOL", "VRT_PATH_CELLS", "VRT_PATH_POOL_K", "VRT_PATH_POOL_REFILL", "VRT_PATH_SAMPLES_PER_CHAIN"]
+HALF = (0.5, (0.9, 0.6, 0.3))             # (chance, colour): passes half of the time, with a tint
+ALWAYS = (2.0, (0.25, 0.5, 0.75))         # always passes
+DEAD = (0.5, (0.0, 0.0, 0.0))             # entry 255: no voxel of C4 reads it
+COAT_A = (0.5, 0.0, (1.0, 0.9, 0.8))      # (chance, scatter, colour): a mirror half of the time
+# (environment, stats, literal)
+ROUTES = {"default": ({}, False, False), "directory": ({"VRT_MARCH_DIRECT_MAX_S": "0"}, False, False), "literal": ({}, False, True),
+          "stats": ({}, True, False)}
+
+
+@pytest.fixture(scope="module")
+def sref(tmp_path_factory):
+    return sun_ref.load(tmp_path_factory.mktemp("sun_ref"))
+
+
+def _gpu(monkeypatch, sc, env=None, **kw):
+    """A context for the scene under exactly `env` of the backend's switches (read when the context is created)."""
+    for k in ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    return gpu_for_scene(sc, **kw)
+
+
+def _frame(gpu, spp, seed=SEED, **kw):
+    gpu.render(MODE_PATH, spp=spp, seed=seed, **kw)
+    rgb, ids, _ = gpu.read_output()
+    return rgb, ids
+
+
+def _tables(gpu):
+    """tests/test_gpu_translucent.py's "all": from the context's own 1-spp frame (the setting off), the material its primary rays
+    hit most passes half of the time with a tint, the second always passes, the third has coat A, the fourth gives off light (as
+    many of them as the frame hits); entry 255 has a chance and no voxel to use it."""
+    gpu.render(MODE_PATH, spp=1, seed=SEED)
+    _, ids, _ = gpu.read_output(rgb=False)
+    counts = E.hit_counts(ids)
+    top = [int(t) for t in np.argsort(counts)[::-1][:4] if counts[t] > 0]
+    assert len(top) >= 2
+    tr = translucent_ref.table({top[0]: HALF, top[1]: ALWAYS, 255: DEAD})
+    emission = np.zeros(256, np.float32)
+    polish = polish_ref.table()
+    if len(top) > 2:
+        polish[top[2]]["chance"], polish[top[2]]["scatter"], polish[top[2]]["color"] = COAT_A
+    if len(top) > 3:
+        emission[top[3]] = 1.5
+    return emission, polish, tr
+
+
+def _write(gpu, tables):
+    gpu.write_emission(tables[0])
+    gpu.write_polish(tables[1])
+    gpu.write_translucency(tables[2])
+
+
+_refs = {}
+
+
+def _ref(sref, orc, key, sc, tables, spp, strength=STRENGTH, seed=SEED):
+    """(rgb, ids, counts) of the reference frame, computed once; `key` names the scene (its world, materials, camera, bounces, size)."""
+    tables = tables if tables is not None else (None, None, None)
+    k = (key, tuple(None if t is None else t.tobytes() for t in tables), spp, strength, seed)
+    if k not in _refs:
+        rgb, ids = sref.render(orc.from_package_scene(sc), strength, *sc.size, spp=spp, seed=seed, emission=tables[0], polish=tables[1],
+                               translucency=tables[2])
+        _refs[k] = (rgb, ids, sref.counts)
+    return _refs[k]
+
+
+def _scene(size, bounces=4, literal=False):
+    sc = scenes.c4(size, bounces=bounces)
+    if literal:
+        sc.materials[0].is_liquid = 1
+    return sc
+
+
+# ---- 1. frames against the reference, route by route ----
+
+@pytest.mark.parametrize("bounces", BOUNCES)
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_sun_lit_frames_match_the_reference(sref, orc, monkeypatch, route, size, bounces):
+    env, stats, literal = ROUTES[route]
+    sc = _scene(size, bounces, literal)
+    gpu = _gpu(monkeypatch, sc, env)
+    if route == "directory":
+        gpu.render(MODE_PATH, spp=1, seed=SEED)
+        assert gpu.read_march_cells()[1] == False, "the context's march cells are in the direct layout"   # noqa: E712
+    key = f"c4 {size} b{bounces} literal {literal}"
+    all_tables = _tables(gpu)
+    gpu.set_sun_light(STRENGTH)
+    for kind, tables in (("alone", None), ("all", all_tables)):
+        if tables is not None:
+            _write(gpu, tables)
+        for n in (1, 2):
+            gpu.set_frames_in_flight(n)
+            for spp in SPPS:
+                what = f"{size} b{bounces} {route} {kind}, {n} in flight, spp {spp}"
+                rgb, ids = _frame(gpu, spp, stats=stats)
+                ref_rgb, ref_ids, counts = _ref(sref, orc, key, sc, tables, spp)
+                err = np.abs(rgb - ref_rgb)
+                print(f"{what}: max radiance error {float(err[np.isfinite(err)].max()):.3g}; {counts}")
+                assert_frame_parity(rgb, ids, ref_rgb, ref_ids, what)
+                if stats:
+                    st = gpu.stats()
+                    print(f"    secondary_rays {st.secondary_rays} steps {st.steps}")
+                    assert st.secondary_rays == counts.bounce_segments + counts.sun_rays, what
+                    assert st.steps == counts.steps, what
+    # (the setting is not a no-op here, and at two bounces or more some sun rays are occluded and some are not)
+    _, _, counts = _ref(sref, orc, key, sc, None, 3)
+    assert counts.sun_rays >= 1 and counts.unoccluded >= 1
+    if size[0] >= 100:
+        assert counts.unoccluded < counts.sun_rays
+    gpu.close()
+
+
+# ---- 2. GPU against GPU, bit for bit ----
+
+def _all_modes(gpu):
+    out = {("path", spp): _frame(gpu, spp) for spp in (1, 3)}
+    out[("path stats", 3)] = _frame(gpu, 3, stats=True)
+    for name, mode in (("primary", MODE_PRIMARY), ("primary+shadow", MODE_PRIMARY_SHADOW)):
+        gpu.render(mode)
+        out[(name, 1)] = gpu.read_output()[:2]
+    return out
+
+
+def test_strength_0_after_strength_1_gives_the_frame_from_before(monkeypatch):
+    sc = _scene(SIZES[3])
+    gpu = _gpu(monkeypatch, sc)
+    _write(gpu, _tables(gpu))
+    want = _all_modes(gpu)
+    gpu.set_sun_light(STRENGTH)
+    assert not np.array_equal(_frame(gpu, 3)[0], want[("path", 3)][0])
+    for name, off in (("strength 0", lambda: gpu.set_sun_light(0.0)), ("strength -0", lambda: gpu.set_sun_light(-0.0)),
+                      ("NULL", lambda: gpu._ck(gpu._lib.vrt_set_sun_light(gpu._h, None)))):
+        gpu.set_sun_light(STRENGTH)
+        off()
+        for n in (1, 2):
+            gpu.set_frames_in_flight(n)
+            got = _all_modes(gpu)
+            for k in want:
+                E.assert_bit_identical(got[k], want[k], f"{name}, {n} in flight: {k}")
+    gpu.close()
+
+
+def test_the_primary_modes_ignore_the_setting(monkeypatch):
+    sc = _scene(SIZES[3])
+    gpu = _gpu(monkeypatch, sc)
+    want = {}
+    for mode in (MODE_PRIMARY, MODE_PRIMARY_SHADOW):
+        gpu.render(mode)
+        want[mode] = gpu.read_output()[:2]
+    gpu.set_sun_light(STRENGTH)
+    for n in (1, 2):
+        gpu.set_frames_in_flight(n)
+        for mode in (MODE_PRIMARY, MODE_PRIMARY_SHADOW):
+            gpu.render(mode)
+            E.assert_bit_identical(gpu.read_output()[:2], want[mode], f"mode {mode}, {n} in flight")
+    gpu.close()
+
+
+def _set_raw(gpu, strength, flags=0, r0=0, r1=0):
+    o = _ffi.SunLight(strength, flags, (C.c_uint32 * 2)(r0, r1))
+    return gpu._lib.vrt_set_sun_light(gpu._h, C.byref(o))
+
+
+@pytest.mark.parametrize("in_flight", [1, 2])
+def test_accumulated_sun_lit_frames_are_one_frame_of_all_their_samples(monkeypatch, in_flight):
+    sc = _scene(SIZES[2])
+    gpu = _gpu(monkeypatch, sc)
+    _write(gpu, _tables(gpu))
+    gpu.set_sun_light(STRENGTH)
+    gpu.set_frames_in_flight(in_flight)
+    want = {n: _frame(gpu, n) for n in (3, 6, 12)}
+    for _ in range(4):
+        gpu.render(MODE_PATH, spp=3, seed=SEED, accumulate=True)
+    rgb, ids, _ = gpu.read_output()
+    E.assert_bit_identical((rgb, ids), want[12], f"{in_flight} in flight: 4 x 3 spp")
+    assert gpu.accumulation() == (12, SEED)
+    # an identical call does not restart the sum, nor does a refused one; a call that changes the setting does
+    gpu.set_sun_light(STRENGTH)
+    for bad in ((-0.5, 0, 0, 0), (float("nan"), 0, 0, 0), (float("inf"), 0, 0, 0), (2.0, 1, 0, 0), (2.0, 0, 1, 0), (2.0, 0, 0, 1)):
+        assert _set_raw(gpu, *bad) == _ffi.VRT_ERR_INVALID_ARG, bad
+    assert gpu.accumulation() == (12, SEED)
+    gpu.reset_accumulation()
+    E.assert_bit_identical(_frame(gpu, 3, accumulate=True), want[3], "a refused call changed nothing")
+    gpu.set_sun_light(STRENGTH)
+    E.assert_bit_identical(_frame(gpu, 3, accumulate=True), want[6], "after an identical call: the sum goes on")
+    assert gpu.accumulation() == (6, SEED)
+    gpu.set_sun_light(0.5)
+    gpu.set_sun_light(STRENGTH)
+    E.assert_bit_identical(_frame(gpu, 3, accumulate=True), want[3], "after the setting changed: the sum starts again")
+    assert gpu.accumulation() == (3, SEED)
+    # a refused call leaves the strength as it is: 0.5 stays 0.5, whatever strength the refused struct carried
+    gpu.set_sun_light(0.5)
+    half = _frame(gpu, 3)
+    assert not np.array_equal(half[0], want[3][0])
+    for bad in ((-1.0, 0, 0, 0), (float("nan"), 0, 0, 0), (STRENGTH, 1, 0, 0), (0.0, 0, 0, 7)):
+        assert _set_raw(gpu, *bad) == _ffi.VRT_ERR_INVALID_ARG, bad
+    E.assert_bit_identical(_frame(gpu, 3), half, "after refused calls: strength 0.5 still")
+    # off on a context that is off already — strength 0, -0 or NULL — does not restart the sum; turning it off does
+    gpu.set_sun_light(0.0)
+    off = {n: _frame(gpu, n) for n in (3, 6, 9)}
+    E.assert_bit_identical(_frame(gpu, 3, accumulate=True), off[3], "off: the sum started again")
+    gpu.set_sun_light(0.0)
+    gpu.set_sun_light(-0.0)
+    gpu._ck(gpu._lib.vrt_set_sun_light(gpu._h, None))
+    assert gpu.accumulation() == (3, SEED)
+    E.assert_bit_identical(_frame(gpu, 3, accumulate=True), off[6], "off again, three ways: the sum goes on")
+    assert gpu.accumulation() == (6, SEED)
+    gpu.close()
+
+
+def test_the_denoisers_guide_is_unchanged(monkeypatch):
+    """The guide and the key come from the primary segment's id word and hit position, which the sun term does not touch; the
+    denoised sun-lit frame is the host filter over the raw sun-lit frame, bit for bit."""
+    sc = _scene(SIZES[2])
+    gpu = _gpu(monkeypatch, sc)
+    gpu.set_denoise(3, 0.0)
+    before = _frame(gpu, 1)
+    guide_before = gpu.read_guide()
+    gpu.set_denoise(0)
+    gpu.set_sun_light(STRENGTH)
+    for spp in (1, 3):
+        raw = _frame(gpu, spp)
+        gpu.set_denoise(3, 0.0)
+        got = _frame(gpu, spp)
+        guide = gpu.read_guide()
+        gpu.set_denoise(0)
+        assert np.array_equal(guide, guide_before) and np.array_equal(got[1], raw[1]) and np.array_equal(got[1], before[1])
+        E.assert_bit_identical((got[0], got[1]), (_ffi.denoise(raw[0], raw[1], guide, 3, 0.0), raw[1]), f"spp {spp}: the filter over the raw frame")
+        assert not np.array_equal(got[0], raw[0])
+    gpu.close()
+
+
+def test_the_union_of_two_shards_is_the_whole_frame(monkeypatch):
+    sc = scenes.c4((160, 96))
+    whole = _gpu(monkeypatch, sc)
+    tables = _tables(whole)
+    _write(whole, tables)
+    whole.set_sun_light(STRENGTH)
+    want = _frame(whole, 3)
+    whole.close()
+    sum_rgb, all_ids = np.zeros_like(want[0]), np.zeros_like(want[1])
+    for r in range(2):
+        sh = _gpu(monkeypatch, sc, shard_rank=r, shard_count=2)
+        _write(sh, tables)
+        sh.set_sun_light(STRENGTH)   # (a shard's context keeps its own setting)
+        rgb, ids = _frame(sh, 3)
+        sum_rgb += rgb
+        all_ids |= ids
+        sh.close()
+    E.assert_bit_identical((sum_rgb, all_ids), want, "the union of two shards")
+    grp = _gpu(monkeypatch, sc, devices=[0, 0], texel_messages=True)
+    _write(grp, tables)
+    grp.set_sun_light(STRENGTH)   # (replicated to every device)
+    E.assert_bit_identical(_frame(grp, 3), want, "two devices with texel messages")
+    grp.close()

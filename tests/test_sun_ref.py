@@ -1,0 +1,129 @@
+"""tests/sun_ref.c, the tests' reference for direct sunlight in the path trace (vrt_set_sun_light), without a GPU: with strength 0
+it is tests/translucent_ref.c bit for bit; the sun term draws nothing, so the id words are the sun-off frame's; on C4 at the
+sizes the GPU tests use, sun rays are launched, some are occluded and some are not, and later segments do leave through the
+sun's disc; and the sum order — emission term, then sun term — is followed by hand in numpy binary32 on one-segment paths."""
+import numpy as np
+import pytest
+
+import polish_ref
+import sun_ref
+import translucent_ref
+from emission_cases import common
+from voxelraytracing_amd import scenes
+
+SEED = 11
+F = np.float32
+BIAS = F(0.002)   # oracle/vrt_oracle.c: ORC_SHADOW_BIAS
+
+
+@pytest.fixture(scope="module")
+def sref(tmp_path_factory):
+    return sun_ref.load(tmp_path_factory.mktemp("sun_ref"))
+
+
+@pytest.fixture(scope="module")
+def tref(tmp_path_factory):
+    return translucent_ref.load(tmp_path_factory.mktemp("translucent_ref"))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _tables(ids):
+    e = np.zeros(256, np.float32)
+    top = common(ids, 3)
+    e[top[0]] = 1.5
+    p = polish_ref.table({int(top[1]): (0.5, 0.0, (1.0, 0.9, 0.8))})
+    t = translucent_ref.table({int(top[2]): (0.5, (0.9, 0.6, 0.3))})
+    return e, p, t
+
+
+def test_it_compiles_with_the_oracles_flags(sref):
+    from emission_ref import oracle_cflags
+    flags = oracle_cflags()
+    assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+def test_strength_0_is_the_translucent_reference(sref, tref, orc, spp):
+    W, H = 64, 40
+    sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
+    o = orc.from_package_scene(sc)
+    _, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=1, seed=SEED)
+    e, p, t = _tables(plain_ids)
+    for tables in ((None, None, None), (e, None, None), (e, p, t)):
+        want_rgb, want_ids = tref.render(o, *tables, W, H, spp=spp, seed=SEED)
+        for strength in (0.0, -0.0):
+            rgb, ids = sref.render(o, strength, W, H, spp=spp, seed=SEED, emission=tables[0], polish=tables[1], translucency=tables[2])
+            assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+            assert sref.counts.sun_rays == 0 and sref.counts.unoccluded == 0 and sref.counts.disc_misses == 0
+
+
+@pytest.mark.parametrize("size", [(128, 72), (100, 60)])
+@pytest.mark.parametrize("bounces", [2, 4])
+def test_every_kind_of_sun_ray_occurs_at_the_sizes_the_gpu_tests_use(sref, orc, size, bounces):
+    W, H = size
+    sc = scenes.c4(size, bounces=bounces)   # (kept alive)
+    o = orc.from_package_scene(sc)
+    off_rgb, off_ids = sref.render(o, 0.0, W, H, spp=1, seed=SEED)
+    off = sref.counts
+    rgb, ids = sref.render(o, 1.0, W, H, spp=1, seed=SEED)
+    n = sref.counts
+    print(f"{size} b{bounces}: {n}; mean radiance {off_rgb.mean():.3f} -> {rgb.mean():.3f}")
+    assert np.array_equal(ids, off_ids)                      # the sun term draws nothing and touches no id word
+    assert np.isfinite(rgb).all()
+    assert n.sun_rays >= 1 and n.unoccluded >= 1 and n.disc_misses >= 1
+    assert n.unoccluded < n.sun_rays                         # some are occluded
+    assert n.bounce_segments == off.bounce_segments          # every path direction is the sun-off frame's
+    assert n.steps > off.steps
+    assert rgb.mean() > off_rgb.mean()
+
+
+def _normalize(v):
+    """orc_normalize in numpy binary32: v / sqrt((x x + y y) + z z)"""
+    d = F(F(F(v[0] * v[0]) + F(v[1] * v[1])) + F(v[2] * v[2]))
+    ln = F(np.sqrt(d))
+    return np.array([F(v[0] / ln), F(v[1] / ln), F(v[2] / ln)], F)
+
+
+def test_the_sum_order_by_hand(sref, orc):
+    """One segment, one sample, every material an emitter: a pixel that hits a solid voxel outside water is
+    ((mc * e) * 1) + ((mc * (k * c)) * 1) when its sun ray is free, (mc * e) * 1 when it is not or when the face looks away —
+    each operation rounded to binary32, in this order."""
+    W, H = 64, 40
+    sc = scenes.c4((W, H), bounces=1)   # (kept alive)
+    o = orc.from_package_scene(sc)
+    strength = 0.75
+    e = np.full(256, 1.5, np.float32)
+    rgb, ids = sref.render(o, strength, W, H, spp=1, seed=SEED, emission=e)
+    wmin = o.c.world.min
+    sun_local = np.array([F(F(o.c.settings.sun_pos[a]) - F(float(wmin[a]))) for a in range(3)], F)
+    k = F(F(o.c.settings.sun_intensity) * F(strength))
+    lit = shaded = away = 0
+    hit = ((ids & orc.ID_HIT) != 0) & ((ids & orc.ID_WATER) == 0)
+    for py, px in np.argwhere(hit)[::7]:
+        idw, mc, d, out = o.trace_pixel(orc.MODE_PRIMARY, int(px), int(py))
+        voxel = idw & orc.ID_VOXEL_MASK
+        if voxel == 0 or o.mats[min(voxel, 255)].is_liquid == 1:
+            continue
+        mc, pos, norm = np.array(mc, F), np.array(out[0:3], F), np.array(out[3:6], F)
+        want = np.array([F(F(mc[a] * F(1.5)) * F(1.0)) for a in range(3)], F)   # 0 + the emission term
+        so = np.array([F(pos[a] + F(norm[a] * BIAS)) for a in range(3)], F)
+        sd = _normalize(np.array([F(sun_local[a] - so[a]) for a in range(3)], F))
+        c = F(F(F(norm[0] * sd[0]) + F(norm[1] * sd[1])) + F(norm[2] * sd[2]))
+        if c > 0:
+            shadow_id, _, _ = o.ray_world(so, sd)
+            if not shadow_id & orc.ID_HIT:
+                w = F(k * c)
+                want = np.array([F(want[a] + F(F(mc[a] * w) * F(1.0))) for a in range(3)], F)
+                lit += 1
+            else:
+                shaded += 1
+        else:
+            away += 1
+        assert np.array_equal(_bits(rgb[py, px]), _bits(want)), (px, py, rgb[py, px], want)
+        light, n = sref.trace_pixel(o, strength, W, H, int(px), int(py), seed=SEED, emission=e)
+        assert np.array_equal(_bits(light), _bits(want)) and n.sun_rays == (1 if c > 0 else 0)
+    print(f"by hand: {lit} lit, {shaded} in shadow, {away} facing away")
+    assert lit >= 10 and shaded >= 1 and away >= 1

@@ -192,6 +192,9 @@ static PathRecord new_path_frame(const PathFacts &F) {
                                         s.chain, g % 3u, (g + 2u) % 3u, (g + 1u) % 3u, g & 1u, (g + 1u) & 1u, s.last_bounce ? 1u : 0u, s.segments,
                                         s.kind == vrt::kStepCellsBounce ? p.pool_batches : 0u, false, false, 0u, kNowhere, kNowhere);
                 break;
+            case vrt::kStepSunlitPrimary: case vrt::kStepSunlitBounce: case vrt::kStepSunRays:
+                CHECK(!"a frame without vrt_set_sun_light has no sun-lit step");
+                break;
             case vrt::kStepChainFinish:
                 r.launches.emplace_back(kChainFinish, s.sample, s.chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, s.first, s.last, s.count, sum_chain, kFrame);
                 break;
@@ -238,6 +241,62 @@ static void check_path_frames() {
         launches += (long)o.launches.size();
     }
     std::printf("check_path_plan: ok (%ld frames compared, %ld launches, %ld unreachable)\n", compared, launches, skipped);
+}
+
+// vrt_set_sun_light: a sun-lit frame has no predecessor to be held to; what vrt_frames.hip and the kernels rely on is asked of
+// the plan directly, over the same combinations of the facts.  (F.sun false is every frame above: the plan is what it was.)
+static void check_sun_frames() {
+    long frames = 0, launches = 0;
+    const uint32_t spps[] = {1, 2, 3, 12, 17}, per_chain[] = {1, 4, 16};
+    const int accums[] = {-1, 0, 7};
+    for (uint32_t spp : spps)
+    for (uint32_t bounces = 0; bounces <= 5; bounces++)
+    for (uint32_t bits = 0; bits < 512; bits++)
+    for (int accum : accums)
+    for (uint32_t samples : per_chain) {
+        PathFacts F;
+        F.spp = spp; F.seed = 11u; F.bounces = bounces; F.sun = true;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u;
+        F.march_direct = F.has_cells;
+        F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
+        F.path_samples = samples; F.hit_seg_cap = 512u;
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) continue;
+        std::snprintf(g_case, sizeof g_case, "sun: spp %u bounces %u bits %u accum %d per chain %u", spp, bounces, bits, accum, samples);
+        const PathPlan p = vrt::plan_path(F);
+        PathFacts E = F;   // the same frame of an emissive context without the setting, on the lane route, one sample per chain
+        E.sun = false; E.emissive = true; E.path_pool = false; E.path_samples = 1u;
+        const PathPlan e = vrt::plan_path(E);
+        CHECK(p.sun == (bounces > 0u) && p.emit == (p.sun || F.emissive || F.polished || F.translucent) && !p.cells && (p.samples == 1u || !p.sun) && (!p.planes || !p.sun));
+        CHECK(p.sun_cells == (p.sun && !F.kstats && !F.literal && F.has_cells && F.path_cells));
+        CHECK(p.polish == F.polished && p.translucent == F.translucent);
+        if (!p.sun) continue;
+        CHECK(p.finish == e.finish && p.own_sum == e.own_sum && p.seg_cap == e.seg_cap && p.cap == e.cap && p.divide_at_end == e.divide_at_end &&
+              p.needs_acc_planes == e.needs_acc_planes && p.needs_accum_sum == e.needs_accum_sum && p.sample_base == e.sample_base &&
+              p.accum_count == e.accum_count && p.finish_into_accum == e.finish_into_accum);
+        // the launches: the emissive frame's, each trace launch in its sun-lit kind and followed by the launch over its sun rays
+        std::vector<PathStep> ps, es;
+        vrt::for_each_path_step(p, [&](const PathStep &s) { ps.push_back(s); });
+        vrt::for_each_path_step(e, [&](const PathStep &s) { es.push_back(s); });
+        size_t i = 0;
+        for (const PathStep &s : es) {
+            CHECK(i < ps.size());
+            const PathStep &t = ps[i++];
+            CHECK(t.sample == s.sample && t.chain == s.chain && t.launch == s.launch &&
+                  t.segments == s.segments && t.last_bounce == s.last_bounce && t.first == s.first && t.last == s.last && t.count == s.count);
+            if (s.kind == vrt::kStepPrimary || s.kind == vrt::kStepLaneBounce) {
+                CHECK(t.kind == (s.kind == vrt::kStepPrimary ? vrt::kStepSunlitPrimary : vrt::kStepSunlitBounce) && vrt::traces_paths(t.kind));
+                CHECK(i < ps.size() && ps[i].kind == vrt::kStepSunRays && ps[i].launch == t.launch && !vrt::traces_paths(ps[i].kind));
+                i++;
+            } else {
+                CHECK(s.kind != vrt::kStepCellsBounce && t.kind == s.kind && !vrt::traces_paths(t.kind));
+            }
+        }
+        CHECK(i == ps.size());
+        frames++;
+        launches += (long)ps.size();
+    }
+    std::printf("check_sun_plan: ok (%ld sun-lit frames, %ld launches)\n", frames, launches);
 }
 
 int main() {
@@ -301,5 +360,6 @@ int main() {
         }
     std::printf("check_frame_plan: ok (%ld frames compared, %ld refused)\n", total, skipped);
     check_path_frames();
+    check_sun_frames();
     return 0;
 }

@@ -88,6 +88,11 @@ class DenoiseOpts(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class SunLight(C.Structure):
+    """include/vrt.h vrt_sun_light: the path trace's direct sunlight (vrt_set_sun_light)"""
+    _fields_ = [("strength", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
+
+
 class RayQuery(C.Structure):
     """include/vrt.h vrt_ray_query: common::math::cast_ray's arguments (common/src/math.rs:153-158)"""
     _fields_ = [("start", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("_reserved", C.c_uint32)]
@@ -143,6 +148,7 @@ assert C.sizeof(BoxQuery) == 48 and C.sizeof(BoxMove) == 32
 assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 assert C.sizeof(DenoiseOpts) == 16
+assert C.sizeof(SunLight) == 16
 assert POLISH_DTYPE.itemsize == 32
 assert TRANSLUCENCY_DTYPE.itemsize == 16
 
@@ -179,6 +185,7 @@ VRT_SYMBOLS = {
     "vrt_get_accumulation": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrt_set_denoise": (C.c_int, [_P, C.POINTER(DenoiseOpts)]),
     "vrt_read_guide": (C.c_int, [_P, _P]),
+    "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
     "vrt_synchronize": (C.c_int, [_P]),
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),

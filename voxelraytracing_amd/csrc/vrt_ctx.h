@@ -79,6 +79,11 @@ void launch_path_primary(const FrameParams &P, bool stats, bool literal, bool em
 void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emit, bool polish, bool translucent, hipStream_t st);
 void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t segments, uint32_t pool_batches, bool emit, bool polish, bool translucent,
                               hipStream_t st);
+// vrt_set_sun_light (vrt_path_sun.h): a sun-lit frame's trace launches — they append a sun ray's record for every hit that sees the
+// sun — and the launch behind each that marches the records (cells: with the occlusion-only march over the march cells)
+void launch_path_primary_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
+void launch_path_bounce_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
+void launch_path_sun(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, bool cells, hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -221,6 +226,10 @@ struct vrt_ctx {
         Buf<uint32_t> extra_blk[kMaxInFlight - 1];
         Buf<uint4> extra_path[kMaxInFlight - 1];
         Buf<vrt::Texel> path_acc[kMaxInFlight];        // the samples' accumulation planes of a launch chain, per frame set
+        // vrt_set_sun_light: per frame set, made by its first sun-lit frame — 3 planes x (kHitSegments * hit_seg_cap) sun-ray
+        // records, and two sets of segment cursors (trace launch g appends to set g & 1 and clears the other for its successor)
+        Buf<uint4> sun_recs[kMaxInFlight];
+        Buf<uint32_t> sun_counts[kMaxInFlight];
         Buf<uint32_t> d_tile_cost, d_tile_order, d_tile_scratch;   // vrt_order.hip, made together
         bool tile_order_valid = false;
         Buf<vrt::Texel> d_accum;     // VRT_RENDER_ACCUMULATE: the running sum
@@ -418,6 +427,7 @@ struct vrt_ctx {
     // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); the scratch frames the passes go back and forth over and the
     // guide words are sz.dn_scratch / sz.dn_guide
     vrt_denoise_opts denoise{};
+    vrt_sun_light sun{};      // vrt_set_sun_light: the setting (16 zero bytes: off); the sun-ray buffers are sz.sun_recs / sz.sun_counts
     bool rendered = false;
     bool timing_pending = false;
     vrt_stats stats;

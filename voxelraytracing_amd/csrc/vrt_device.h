@@ -142,6 +142,19 @@ struct FrameParams {
 };
 static_assert(offsetof(FrameParams, n_nodes) == 244, "layout_hole keeps the fields behind it where the kernels' code expects them");
 
+// vrt_set_sun_light (vrt_path_sun.h): what the kernels of a sun-lit path frame are given besides FrameParams — a second kernel
+// argument, so that FrameParams keeps its layout and the kernels that take it alone their code
+struct SunLaunch {
+    uint4 *recs;          // three planes of `cap` records: {slot, so.xyz} {sd.xyz, 0} {term.rgb, 0}, segmented like the path buffers
+    uint32_t *counts;     // records in segment s at counts[s * kSegStride]: what this trace launch appends to and its sun launch reads
+    uint32_t *clear;      // the other cursor set: the next trace launch's.  This launch zeroes it (its last reader ran before it)
+    uint32_t cap;         // records per plane = kHitSegments * seg_cap
+    uint32_t seg_cap;     // records per segment (the path buffers' hit_seg_cap)
+    float k;              // settings.sun_intensity * strength, the host's binary32 product
+    uint32_t lobes;       // bit 0: the frame flips the coat's coin (vrt_write_polish); bit 1: it lets paths through (vrt_write_translucency)
+};
+constexpr uint32_t kSunLobePolish = 1u, kSunLobeTranslucent = 2u;
+
 // The path-trace buffers are compacted per segment, not globally: one device-scope counter saturates at ~88
 // returning atomics per microsecond (MI355X_MICROARCH.md "dequeue"), which made 32 400 per-wave atomics the
 // whole 0.37 ms of the first primary kernel.  Workgroup b appends to segment b % kHitSegments; each counter

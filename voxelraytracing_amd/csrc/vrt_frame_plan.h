@@ -90,6 +90,7 @@ struct PathFacts {   // copied out of the options, the context and the frame's p
     bool emissive = false;          // vrt_write_emission: some material gives off light
     bool polished = false;          // vrt_write_polish: some material's coat has a chance that is not 0
     bool translucent = false;       // vrt_write_translucency: some material lets a path through with a chance that is not 0
+    bool sun = false;               // vrt_set_sun_light: the strength is not 0
     // the context's switches (vrt_create reads them from the environment)
     uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
     bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
@@ -108,7 +109,7 @@ enum PathFinish : uint32_t {   // the pass behind each chain of samples
 
 struct PathPlan {   // each field is explained where plan_path sets it
     uint32_t spp = 1, seed = 0, bounces = 0;
-    bool kstats = false, literal = false, emit = false, polish = false, translucent = false;
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false;
     uint32_t samples = 1;
     bool planes = false, own_sum = false, cells = false;
     uint32_t seg_cap = 0;
@@ -132,7 +133,15 @@ inline PathPlan plan_path(const PathFacts &F) {
     // 2.7 rays per lane are not enough to cover a bounce launch's tail — and a frame of 16 spp is 4 x 4
     // launches instead of 16 x 4.  Each sample accumulates into its own plane; the chain's finishing pass adds the planes
     // to the frame in sample order, which is the order one sample per chain adds them in.
-    p.samples = (F.spp > 1u && fast && F.bounces > 0u) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
+    // vrt_set_sun_light: every trace launch of a sun-lit frame is followed by a launch that marches the sun rays it appended
+    // (vrt_path_sun.h), and stream order is what puts a segment's sun term between its emission term and the next segment's.  The
+    // pool kernel carries all later segments in one launch and cannot be interleaved, and one record per slot per launch is what
+    // keeps the sun launch's read-modify-write plain: such a frame is one sample per chain, one lane = path launch per bounce,
+    // whatever its world.  What the sun launch marches with: the occlusion-only march over the march cells where a plain frame
+    // has them, else the trace's own march
+    p.sun = F.sun && F.bounces > 0u;
+    p.sun_cells = p.sun && fast && F.has_cells && F.path_cells;
+    p.samples = (F.spp > 1u && fast && F.bounces > 0u && !p.sun) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
     p.planes = p.samples > 1u;
     // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
     // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
@@ -143,7 +152,9 @@ inline PathPlan plan_path(const PathFacts &F) {
     // everything an emissive frame is planned with; polish is what the launchers switch on
     // vrt_write_translucency: the same again.  The translucent kernels are one family, whether the frame is polished or not
     // (they take the coat's draw under a word the uploads keep on the device), so translucent is what the launchers look at first
-    p.emit = F.emissive || F.polished || F.translucent;
+    // vrt_set_sun_light: and again — a sample is then several terms (the sun terms, the sky).  Its kernels are one pair, which reads
+    // from its launch whether there is a coat or a pass-through draw
+    p.emit = F.emissive || F.polished || F.translucent || p.sun;
     p.polish = F.polished;
     p.translucent = F.translucent;
     p.own_sum = p.emit && !p.planes && !F.accum && F.spp > 1u && F.bounces > 0u;
@@ -152,7 +163,7 @@ inline PathPlan plan_path(const PathFacts &F) {
     p.cap = (size_t)kPlanHitSegments * p.seg_cap;
     // Bounce launches over the march cells: every later segment of a chain in ONE launch of the pool kernel (vrt_path.hip);
     // worlds without march cells, or with the pool switched off: one lane = path launch per bounce.
-    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells;
+    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells && !p.sun;
     // the pool's batches of 64 rays per wave: 5 with two frames in flight (the launcher grants them to direct worlds only), else 4
     p.pool_batches = F.path_pool_batches ? F.path_pool_batches : (F.in_flight > 1u ? 5u : 4u);
     p.refill = F.path_refill;
@@ -172,8 +183,11 @@ inline PathPlan plan_path(const PathFacts &F) {
     return p;
 }
 
-// (the first three trace rays — the launches PathStep::launch counts — and come first: kind <= kStepCellsBounce asks for them)
-enum PathStepKind : uint32_t { kStepPrimary, kStepLaneBounce, kStepCellsBounce, kStepChainFinish, kStepResolve, kStepFinalDivide };
+// (the first five trace a segment of the paths — the launches PathStep::launch counts — and come first: traces_paths asks for them;
+// kStepSunlitPrimary / kStepSunlitBounce are a sun-lit frame's, each followed by a kStepSunRays with its launch number)
+enum PathStepKind : uint32_t { kStepPrimary, kStepLaneBounce, kStepCellsBounce, kStepSunlitPrimary, kStepSunlitBounce, kStepSunRays,
+                               kStepChainFinish, kStepResolve, kStepFinalDivide };
+inline bool traces_paths(PathStepKind k) { return k <= kStepSunlitBounce; }
 
 struct PathStep {   // one launch of the frame
     PathStepKind kind;
@@ -200,7 +214,12 @@ void for_each_path_step(const PathPlan &p, F &&f) {
                 s.last_bounce = true;
                 b += s.segments - 1u;
             }
+            if (p.sun) s.kind = b == 0u ? kStepSunlitPrimary : kStepSunlitBounce;
             f(s);
+            if (p.sun) {   // the records that launch appended: cursor set launch & 1 of the sun buffer
+                s.kind = kStepSunRays;
+                f(s);
+            }
         }
         if (p.finish != kFinishNone)
             f(PathStep{p.finish == kChainIntoFrame || p.finish == kChainIntoSum ? kStepChainFinish : kStepResolve, smp, chain, g, 0u, false,

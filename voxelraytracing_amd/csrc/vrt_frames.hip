@@ -327,6 +327,21 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         VRT_TRY(frame_buf(c, c->sz.d_accum, frame_slots(c)));
         HIP_TRY(c, c->ev_accum.ensure());
     }
+    vrt::SunLaunch S{};
+    uint32_t *sun_seg[2] = {nullptr, nullptr};
+    if (plan.sun) {   // vrt_set_sun_light: the frame set's sun-ray buffer and its two cursor sets, zero when the frame starts
+        constexpr size_t kSunSegWords = (size_t)vrt::kHitSegments * vrt::kSegStride;
+        HIP_TRY(c, c->sz.sun_recs[f.slot].grow(3 * plan.cap));
+        HIP_TRY(c, c->sz.sun_counts[f.slot].once(2 * kSunSegWords));
+        sun_seg[0] = c->sz.sun_counts[f.slot];
+        sun_seg[1] = sun_seg[0] + kSunSegWords;
+        HIP_TRY(c, hipMemsetAsync(sun_seg[0], 0, 2 * kSunSegWords * sizeof(uint32_t), f.st));
+        S.recs = c->sz.sun_recs[f.slot];
+        S.cap = (uint32_t)plan.cap;
+        S.seg_cap = plan.seg_cap;
+        S.k = c->settings.sun_intensity * c->sun.strength;   // (one binary32 product: the contract's k)
+        S.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
+    }
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
     P.hit_seg_cap = plan.seg_cap;
     P.acc = plan.planes ? acc : nullptr;
@@ -350,7 +365,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     bool sum_waited = false, first_marked = false;
     auto enqueue = [&](const vrt::PathStep &s) -> int {
         using namespace vrt;
-        if (s.kind <= kStepCellsBounce) {   // a launch of the trace
+        if (s.kind == kStepSunRays) {   // (its trace launch's parameters, and the cursor set that launch appended to)
+        } else if (traces_paths(s.kind)) {   // a launch of the trace
             P.sample = s.sample;
             P.chain = s.chain;
             P.seg_counts = seg[s.launch % 3u];
@@ -359,6 +375,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             P.path_out = buf[s.launch & 1u];
             P.path_in = buf[(s.launch + 1u) & 1u];
             P.last_bounce = s.last_bounce;
+            S.counts = sun_seg[s.launch & 1u];
+            S.clear = sun_seg[(s.launch + 1u) & 1u];
         } else if (plan.finish_into_accum && !sum_waited) {
             if (c->accum_ev_recorded) HIP_TRY(c, hipStreamWaitEvent(f.st, c->ev_accum, 0));
             sum_waited = true;
@@ -367,6 +385,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             case kStepPrimary: launch_path_primary(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
             case kStepLaneBounce: launch_path_bounce(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
             case kStepCellsBounce: launch_path_bounce_cells(P, plan.refill, s.segments, plan.pool_batches, plan.emit, plan.polish, plan.translucent, f.st); break;
+            case kStepSunlitPrimary: launch_path_primary_sunlit(P, S, plan.kstats, plan.literal, f.st); break;
+            case kStepSunlitBounce: launch_path_bounce_sunlit(P, S, plan.kstats, plan.literal, f.st); break;
+            case kStepSunRays: launch_path_sun(P, S, plan.kstats, plan.literal, plan.sun_cells, f.st); break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -740,6 +761,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.kstats = plan.kstats; PF.literal = plan.literal;
             PF.has_grid = P.grid != nullptr; PF.has_cells = P.mblk != nullptr; PF.march_direct = P.march_direct != 0u;
             PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u; PF.translucent = c->n_translucent != 0u;
+            PF.sun = c->sun.strength != 0.0f;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
             PF.in_flight = c->in_flight; PF.hit_seg_cap = c->hit_seg_cap;
@@ -766,6 +788,21 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     c->rendered = true;
     c->flushed_at_call = false;   // (the next frame's first staged range may go out at its call again: vrt_uploads.hip)
     c->timing_pending = true;
+    return VRT_OK;
+}
+
+int vrt_set_sun_light(vrt_ctx *c, const vrt_sun_light *opts) {
+    if (!c) return VRT_ERR_INVALID_ARG;
+    vrt_sun_light o;
+    memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if (!(o.strength >= 0.0f) || std::isinf(o.strength))
+        return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_sun_light: strength %g (0 = off, or a finite positive number)", (double)o.strength);
+    if (o.flags || o._reserved[0] || o._reserved[1]) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_sun_light: flags and _reserved must be 0");
+    GRP_EACH(c, vrt_set_sun_light(d, opts));
+    if (o.strength == 0.0f) memset(&o, 0, sizeof o);   // (-0: off is 16 zero bytes)
+    if (memcmp(&c->sun, &o, sizeof o) != 0) c->accum_restart = true;
+    c->sun = o;
     return VRT_OK;
 }
 

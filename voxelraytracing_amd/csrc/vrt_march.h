@@ -853,7 +853,8 @@ __device__ __forceinline__ MarchResult march(const FrameParams &P, const uint32_
 
 // ray_sky, ray_tracer.wgsl:144-157
 // CAM_ORIGIN: `origin` is the camera (a primary ray), whose sun direction the host evaluated once (P.cam_sun_dir).
-template <bool CAM_ORIGIN = false>
+// NO_DISC: the sky of a scene whose sun_intensity is 0 — `add` is +0 (vrt_set_sun_light: a sun-lit path's later misses; vrt_path_sun.h)
+template <bool CAM_ORIGIN = false, bool NO_DISC = false>
 __device__ __forceinline__ V3 ray_sky(const FrameParams &P, V3 origin, V3 dir) {
     const float ground_to_sky_t = vsmoothstep(-0.01f, 0.0f, dir.y);
     // pow(t, 0.35), t in [0, 1], as exp2(0.35 * log2 t) on the hardware transcendentals (what a GPU's WGSL pow is);
@@ -864,7 +865,7 @@ __device__ __forceinline__ V3 ray_sky(const FrameParams &P, V3 origin, V3 dir) {
     const V3 sun_dir = CAM_ORIGIN ? V3{P.cam_sun_dir[0], P.cam_sun_dir[1], P.cam_sun_dir[2]}
                                   : normalize_wave(V3{P.sun_local[0] - origin.x, P.sun_local[1] - origin.y, P.sun_local[2] - origin.z});
     const float sun = (vdot(dir, sun_dir) > (1.0f - 0.01f) && ground_to_sky_t >= 1.0f) ? 1.0f : 0.0f;
-    const float add = sun * P.settings.sun_intensity;
+    const float add = sun * (NO_DISC ? 0.0f : P.settings.sun_intensity);
     return V3{vmix(0.03f, grad.x, ground_to_sky_t) + add, vmix(0.03f, grad.y, ground_to_sky_t) + add,
               vmix(0.03f, grad.z, ground_to_sky_t) + add};
 }

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "vrt_path_common.h"
+#include "vrt_path_sun.h"
 
 namespace vrt {
 
@@ -50,6 +51,15 @@ static inline size_t lds_bytes_path(const FrameParams &P, bool lds_roots) { retu
 #undef VRT_PRIMARY_KERNEL
 #undef VRT_PRIMARY_POLISH
 #undef VRT_PRIMARY_TRANSLUCENT
+#define VRT_PRIMARY_KERNEL path_sunlit_primary_kernel   // (vrt_set_sun_light: coat and pass-through read from the launch)
+#define VRT_PRIMARY_POLISH 0
+#define VRT_PRIMARY_TRANSLUCENT 0
+#define VRT_PRIMARY_SUN
+#include "vrt_path_primary.h"
+#undef VRT_PRIMARY_KERNEL
+#undef VRT_PRIMARY_POLISH
+#undef VRT_PRIMARY_TRANSLUCENT
+#undef VRT_PRIMARY_SUN
 
 // One segment of a path: its march, then path_after_march.
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT, bool POLISH, bool TRANSLUCENT>
@@ -80,6 +90,15 @@ __device__ __forceinline__ bool path_segment(const FrameParams &P, const uint32_
 #undef VRT_BOUNCE_KERNEL
 #undef VRT_BOUNCE_POLISH
 #undef VRT_BOUNCE_TRANSLUCENT
+#define VRT_BOUNCE_KERNEL path_sunlit_bounce_kernel
+#define VRT_BOUNCE_POLISH 0
+#define VRT_BOUNCE_TRANSLUCENT 0
+#define VRT_BOUNCE_SUN
+#include "vrt_path_bounce.h"
+#undef VRT_BOUNCE_KERNEL
+#undef VRT_BOUNCE_POLISH
+#undef VRT_BOUNCE_TRANSLUCENT
+#undef VRT_BOUNCE_SUN
 
 
 // ------------------------------------------------------------------------------------------------
@@ -220,24 +239,26 @@ __global__ void path_finish_kernel(Texel *out, uint32_t n, float spp) {
 // The path trace marches with the grid march when the derived tables exist (P.grid), else with the ancestor-cache walk;
 // `literal` (air flagged liquid, vrt_frames.hip) with the shader's text.  TAIL: the template arguments after the first three
 // (empty: the kernel's defaults, no emission)
+// VRT_PATH_ARGS: the kernel's arguments (P; a sun-lit frame's kernels: P, S)
 #define VRT_PATH_LAUNCH(kernel, TAIL)                                                                                     \
     do {                                                                                                                  \
         const bool lds = (!P.grid || literal) && P.n_roots <= kLdsRootsMax;                                               \
         const size_t sh = lds_bytes_path(P, lds);                                                                         \
         if (literal) {                                                                                                    \
-            if (lds) { if (stats) hipLaunchKernelGGL((kernel<1, true, true TAIL>), grid, block, sh, st, P); else hipLaunchKernelGGL((kernel<1, true, false TAIL>), grid, block, sh, st, P); } \
-            else { if (stats) hipLaunchKernelGGL((kernel<1, false, true TAIL>), grid, block, sh, st, P); else hipLaunchKernelGGL((kernel<1, false, false TAIL>), grid, block, sh, st, P); } \
+            if (lds) { if (stats) hipLaunchKernelGGL((kernel<1, true, true TAIL>), grid, block, sh, st, VRT_PATH_ARGS); else hipLaunchKernelGGL((kernel<1, true, false TAIL>), grid, block, sh, st, VRT_PATH_ARGS); } \
+            else { if (stats) hipLaunchKernelGGL((kernel<1, false, true TAIL>), grid, block, sh, st, VRT_PATH_ARGS); else hipLaunchKernelGGL((kernel<1, false, false TAIL>), grid, block, sh, st, VRT_PATH_ARGS); } \
         } else if (P.grid) {                                                                                              \
-            if (stats) hipLaunchKernelGGL((kernel<0, false, true TAIL>), grid, block, sh, st, P);                         \
-            else hipLaunchKernelGGL((kernel<0, false, false TAIL>), grid, block, sh, st, P);                              \
+            if (stats) hipLaunchKernelGGL((kernel<0, false, true TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                         \
+            else hipLaunchKernelGGL((kernel<0, false, false TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                              \
         } else if (lds) {                                                                                                 \
-            if (stats) hipLaunchKernelGGL((kernel<2, true, true TAIL>), grid, block, sh, st, P);                          \
-            else hipLaunchKernelGGL((kernel<2, true, false TAIL>), grid, block, sh, st, P);                               \
+            if (stats) hipLaunchKernelGGL((kernel<2, true, true TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                          \
+            else hipLaunchKernelGGL((kernel<2, true, false TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                               \
         } else {                                                                                                          \
-            if (stats) hipLaunchKernelGGL((kernel<2, false, true TAIL>), grid, block, sh, st, P);                         \
-            else hipLaunchKernelGGL((kernel<2, false, false TAIL>), grid, block, sh, st, P);                              \
+            if (stats) hipLaunchKernelGGL((kernel<2, false, true TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                         \
+            else hipLaunchKernelGGL((kernel<2, false, false TAIL>), grid, block, sh, st, VRT_PATH_ARGS);                              \
         }                                                                                                                 \
     } while (0)
+#define VRT_PATH_ARGS P
 #define VRT_PRIMARY_EMIT , false, true   // (MULTI, EMIT)
 #define VRT_BOUNCE_EMIT , true                  // (EMIT)
 
@@ -302,6 +323,36 @@ void launch_path_bounce(const FrameParams &P, bool stats, bool literal, bool emi
     else if (emit) VRT_PATH_LAUNCH(path_bounce_kernel, VRT_BOUNCE_EMIT);
     else VRT_PATH_LAUNCH(path_bounce_kernel, );
 }
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, S
+
+// vrt_set_sun_light: a sun-lit frame is one lane = path launch per segment (one sample per chain, the emission term carried), each
+// followed by launch_path_sun over the records it appended
+void launch_path_primary_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
+    VRT_PATH_LAUNCH(path_sunlit_primary_kernel, VRT_PRIMARY_EMIT);
+}
+
+void launch_path_bounce_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid(kHitSegments * (P.hit_seg_cap / 256u)), block(256);
+    VRT_PATH_LAUNCH(path_sunlit_bounce_kernel, VRT_BOUNCE_EMIT);
+}
+
+// cells (the plan's sun_cells: a plain frame that was handed the march cells) — the occlusion-only march (vrt_path_sun.h); else
+// march<>, which also counts.  The plan decides; nothing is asked again here
+void launch_path_sun(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, bool cells, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid(kHitSegments * (S.seg_cap / 256u)), block(256);
+    if (cells) {
+        if (P.march_direct) hipLaunchKernelGGL((path_sun_cells_kernel<true>), grid, block, 0, st, P, S);
+        else hipLaunchKernelGGL((path_sun_cells_kernel<false>), grid, block, 0, st, P, S);
+        return;
+    }
+    VRT_PATH_LAUNCH(path_sun_kernel, );
+}
+#undef VRT_PATH_ARGS
 #undef VRT_PATH_LAUNCH
 #undef VRT_PRIMARY_EMIT
 #undef VRT_BOUNCE_EMIT

@@ -3,11 +3,20 @@
 // alone) and as path_translucent_bounce_kernel (VRT_BOUNCE_TRANSLUCENT 1: vrt_write_translucency; EMIT alone), for the reasons
 // vrt_path_primary.h gives.
 // In: VRT_BOUNCE_KERNEL (the kernel's name), VRT_BOUNCE_POLISH, VRT_BOUNCE_TRANSLUCENT (0 or 1).
+// A fourth time with VRT_BOUNCE_SUN defined, as path_sunlit_bounce_kernel (vrt_set_sun_light), as vrt_path_primary.h says; a miss
+// of these segments takes the sky without the sun's disc.
+#ifdef VRT_BOUNCE_SUN
+#define VRT_BOUNCE_ARGS FrameParams P, SunLaunch S
+#else
+#define VRT_BOUNCE_ARGS FrameParams P
+#endif
 
 // Bounce b >= 1: lane = one live path of the in buffer.  EMIT: emissive hits add their light too (vrt_write_emission).
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT = false>
-__global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
+__global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(VRT_BOUNCE_ARGS) {
+#ifndef VRT_BOUNCE_SUN
     constexpr bool POLISH = VRT_BOUNCE_POLISH, TRANSLUCENT = VRT_BOUNCE_TRANSLUCENT;
+#endif
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem, *s_roots = smem + 24;
     unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
@@ -17,6 +26,11 @@ __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t seg = blockIdx.x % kHitSegments, part = blockIdx.x / kHitSegments;
     if (blockIdx.x == 0 && P.seg_clear) P.seg_clear[threadIdx.x * kSegStride] = 0u;
+#ifdef VRT_BOUNCE_SUN
+    if (blockIdx.x == 0) S.clear[threadIdx.x * kSegStride] = 0u;
+    bool sun = false;
+    V3 so{0.f, 0.f, 0.f}, sd{0.f, 0.f, 0.f}, term{0.f, 0.f, 0.f};
+#endif
     const uint32_t count = P.seg_in[seg * kSegStride];
     const uint32_t j = part * blockDim.x + threadIdx.x;
     const bool active = j < count;
@@ -37,7 +51,13 @@ __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
         st.thr = V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
         V3 light{0.f, 0.f, 0.f};
         bool lit;
+#ifdef VRT_BOUNCE_SUN
+        R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, st.origin, st.dir);
+        sun = sun_ray_of_hit(P, S, s_liquid, R.hit, R, st.thr, so, sd, term);   // (thr: before the hit)
+        alive = path_after_march_sunlit<true>(P, S, st, R, light, lit) && !P.last_bounce;
+#else
         alive = path_segment<MARCH, LDS_ROOTS, STATS, EMIT, POLISH, TRANSLUCENT>(P, s_roots, s_liquid, st, R, light, lit) && !P.last_bounce;
+#endif
         if (lit) {
             uint4 t = P.out[st.slot];
             t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
@@ -48,6 +68,9 @@ __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
         if (STATS && P.steps && P.sample == 0u) P.steps[st.slot] += R.iters << 16;
     }
     append_paths(P, alive, st, lane);
+#ifdef VRT_BOUNCE_SUN
+    append_sun_rays(S, sun, st.slot, so, sd, term, lane);
+#endif
     if (STATS) {
         block_add(s_acc, 0, active ? R.iters : 0u);
         block_add(s_acc, 1, active ? R.visits : 0u);
@@ -60,3 +83,4 @@ __global__ void __launch_bounds__(256) VRT_BOUNCE_KERNEL(FrameParams P) {
         }
     }
 }
+#undef VRT_BOUNCE_ARGS

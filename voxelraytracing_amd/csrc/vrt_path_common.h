@@ -153,11 +153,12 @@ __device__ __forceinline__ void path_translucent_hit(const FrameParams &P, PathS
 // chance of the voxel's entry of the polish table, the entry's scatter and colour take the place of the material's scatter and mc.
 // TRANSLUCENT (vrt_write_translucency; :167-173): path_translucent_hit above in the place of everything behind the emission term;
 // POLISH is then not read (the coat's draw is under the word behind the tables).
-template <bool EMIT = false, bool POLISH = false, bool TRANSLUCENT = false>
+// SKY_NO_DISC (vrt_set_sun_light, vrt_path_sun.h): a miss takes the sky without the sun's disc — a later segment of a sun-lit path.
+template <bool EMIT = false, bool POLISH = false, bool TRANSLUCENT = false, bool SKY_NO_DISC = false>
 __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
     lit = !R.hit;
     if (!R.hit) {
-        const V3 sky = ray_sky(P, st.origin, st.dir);
+        const V3 sky = ray_sky<false, SKY_NO_DISC>(P, st.origin, st.dir);
         light = V3{sky.x * st.thr.x, sky.y * st.thr.y, sky.z * st.thr.z};
         return false;
     }

@@ -4,13 +4,23 @@
 // a context that lets paths through, vrt_write_translucency; EMIT alone again, the coat's draw under a word on the device).  A kernel of its own rather than one more template argument, as the pool
 // kernel's body has it (vrt_path_cells.h): the plain and the emissive kernels keep their names and their instruction streams.
 // In: VRT_PRIMARY_KERNEL (the kernel's name), VRT_PRIMARY_POLISH, VRT_PRIMARY_TRANSLUCENT (0 or 1).
+// A fourth time with VRT_PRIMARY_SUN defined, as path_sunlit_primary_kernel (vrt_set_sun_light, vrt_path_sun.h): the kernel takes a
+// SunLaunch behind FrameParams, every hit that sees the sun appends a sun ray's record, and whether there is a coat or a
+// pass-through draw is read from the launch (the other two macros are then not read).  Instantiated with EMIT alone, never MULTI.
+#ifdef VRT_PRIMARY_SUN
+#define VRT_PRIMARY_ARGS FrameParams P, SunLaunch S
+#else
+#define VRT_PRIMARY_ARGS FrameParams P
+#endif
 
 // Bounce 0: primary rays of sample P.sample. Sample 0 initialises the texel {light, id}; later samples add.
 // MULTI: the samples of a launch chain (P.acc, P.chain) share the primary march; otherwise one sample, straight into `out`
 // EMIT: emissive hits add their light too (vrt_write_emission) — a later sample's texel is then written on those as well
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool MULTI = false, bool EMIT = false>
-__global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
+__global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(VRT_PRIMARY_ARGS) {
+#ifndef VRT_PRIMARY_SUN
     constexpr bool POLISH = VRT_PRIMARY_POLISH, TRANSLUCENT = VRT_PRIMARY_TRANSLUCENT;
+#endif
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem, *s_roots = smem + 24;
     unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
@@ -21,6 +31,9 @@ __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
     const uint32_t t_local = blockIdx.x * 4u + (threadIdx.x >> 6);
     const bool live = t_local < P.tiles_local;
     if (blockIdx.x == 0 && P.seg_clear) P.seg_clear[threadIdx.x * kSegStride] = 0u;   // kHitSegments == blockDim.x cursors
+#ifdef VRT_PRIMARY_SUN
+    if (blockIdx.x == 0) S.clear[threadIdx.x * kSegStride] = 0u;
+#endif
     if (!STATS && !live) return;
     MarchResult R;
     R.iters = 0; R.visits = 0; R.hit = false;
@@ -52,7 +65,13 @@ __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
             st.rng = py * P.width + px + (P.sample_base + sample) * (P.width * P.height) + P.seed * 0x9E3779B9u;
             V3 light{0.f, 0.f, 0.f};
             bool lit;
+#ifdef VRT_PRIMARY_SUN
+            V3 so, sd, term;   // (thr is 1: before the hit)
+            const bool sun = sun_ray_of_hit(P, S, s_liquid, R.hit, R, st.thr, so, sd, term);
+            const bool alive = path_after_march_sunlit<false>(P, S, st, R, light, lit) && !P.last_bounce;
+#else
             const bool alive = path_after_march<EMIT, POLISH, TRANSLUCENT>(P, st, R, light, lit) && !P.last_bounce;
+#endif
             if (MULTI) {
                 // this sample's own plane: its light so far and, for the frame's first sample, the id word (0 otherwise);
                 // the path's later segments find the plane through the slot
@@ -68,6 +87,9 @@ __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
                 P.out[st.slot] = t;
             }
             append_paths(P, alive, st, lane);
+#ifdef VRT_PRIMARY_SUN
+            append_sun_rays(S, sun, st.slot, so, sd, term, lane);
+#endif
         }
         if (STATS && P.steps && P.sample == 0u) P.steps[pixel_slot] = R.iters;
     }
@@ -85,3 +107,4 @@ __global__ void __launch_bounds__(256) VRT_PRIMARY_KERNEL(FrameParams P) {
         }
     }
 }
+#undef VRT_PRIMARY_ARGS

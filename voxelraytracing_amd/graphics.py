@@ -195,6 +195,13 @@ class Gpu:
         self._ck(self._lib.vrt_read_guide(self._h, a.ctypes.data_as(C.c_void_p)))
         return a
 
+    def set_sun_light(self, strength: float):
+        """vrt_set_sun_light: every hit of a later MODE_PATH frame sends a ray to the sun and, where nothing is in the way, adds
+        settings.sun_intensity * strength * dot(normal, sun direction) times its colour (0 = off, the default).  The primary
+        modes ignore it; changing it restarts the accumulation."""
+        o = _ffi.SunLight(strength, 0, (C.c_uint32 * 2)(0, 0))
+        self._ck(self._lib.vrt_set_sun_light(self._h, C.byref(o)))
+
     def synchronize(self):
         self._ck(self._lib.vrt_synchronize(self._h))
 
