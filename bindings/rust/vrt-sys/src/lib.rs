@@ -252,6 +252,16 @@ pub struct vrt_sun_light {
     pub _reserved: [u32; 2],
 }
 
+/// vrt_set_camera_sampling: pixel jitter and a thin lens for the path trace (pixel_spread and aperture both 0 = off).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_camera_sampling {
+    pub pixel_spread: f32,
+    pub aperture: f32,
+    pub focus_distance: f32,
+    pub flags: u32,
+}
+
 /// What issuing a frame costs the host (vrt_get_issue_profile), microseconds per vrt_render call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -317,6 +327,7 @@ extern "C" {
     pub fn vrt_set_denoise(ctx: *mut vrt_ctx, opts: *const vrt_denoise_opts) -> c_int;
     pub fn vrt_read_guide(ctx: *mut vrt_ctx, guide: *mut u32) -> c_int;
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
+    pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
     pub fn vrt_synchronize(ctx: *mut vrt_ctx) -> c_int;
     pub fn vrt_read_output(ctx: *mut vrt_ctx, rgb: *mut f32, ids: *mut u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_present(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8: *mut u8) -> c_int;
@@ -365,6 +376,7 @@ mod layout {
         assert_eq!(size_of::<vrt_issue_profile>(), 72);
         assert!(size_of::<vrt_denoise_opts>() == 16);
         assert!(size_of::<vrt_sun_light>() == 16);
+        assert!(size_of::<vrt_camera_sampling>() == 16);
         assert!(size_of::<vrt_shape>() == 40);
         assert!(size_of::<vrt_polish>() == 32);
         assert!(size_of::<vrt_translucency>() == 16);

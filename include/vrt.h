@@ -452,6 +452,46 @@ typedef struct {
 } vrt_sun_light;            /* 16 B */
 int vrt_set_sun_light(vrt_ctx *ctx, const vrt_sun_light *opts);
 
+/* Camera sampling for VRT_MODE_PATH: a primary ray of its own for every sample — sub-pixel jitter (a box pixel filter, which
+ * is what removes the stair steps of voxel edges as samples accumulate) and a thin lens (depth of field).  Without it every
+ * sample of a pixel starts with the pixel's one ray.  The primary modes ignore the setting and stay byte for byte what they
+ * are.  Build-defined, and defined exactly, in strict binary32, nothing contracted.  The setting is on when pixel_spread or
+ * aperture is not 0:
+ *   1  a sample's RNG is seeded as without the setting; ahead of everything else it takes four draws, u1, u2, u3, u4 = rng_next
+ *      in that order — on every sample of every pixel, whichever of the two floats is 0
+ *   2  fx = f32(px) + (u1 - 0.5) * pixel_spread,  fy = f32(py) + (u2 - 0.5) * pixel_spread;
+ *      x = (fx * 2) / proj_size.x - 1,  y = (fy * 2) / proj_size.y - 1; the products with inv_proj_mat and inv_view_mat follow as
+ *      in create_ray_from_screen;  d = normalize(w)
+ *   3  aperture == 0 (a pinhole):  o' = origin = cam.pos - f32(world.min),  d' = d.  Otherwise
+ *        r = aperture * sqrt(u3);  lx = r * cos2pi(u4);  ly = r * cos2pi(u4 + 0.75)    (cos2pi: the normal deviates' quadrant-and-
+ *        polynomial cosine; its argument may pass 1)
+ *        right.k = inv_view_mat[4k + 0],  up.k = inv_view_mat[4k + 1]  (k = 0, 1, 2: the images of eye-space x and y, as they are)
+ *        F.k = origin.k + d.k * focus_distance;  o'.k = (origin.k + right.k * lx) + up.k * ly;  d' = normalize(F - o')
+ *   4  the sample's primary segment is ray_world(o', d'), an ordinary segment: the start nudge, the test for lying outside the
+ *      world.  A primary miss takes ray_sky(o', d') with the sun's disc (under vrt_set_sun_light too: later misses do not show
+ *      it).  Everything behind the march is unchanged and in its order: emission term, sun term, pass-through draw, coat draw,
+ *      direction, throughput.  A sample's light is its terms in segment order, the sky last; a frame's light is its samples'
+ *      lights in sample order, divided by spp.  VRT_RENDER_ACCUMULATE keeps its identity (K frames of s spp are one frame of
+ *      K * s spp, bit for bit): the four draws hang on the global sample index through the seed
+ *   5  the id word, vrt_read_steps' primary counts, vrt_stats.hits and the denoiser's key and guide are those of the frame with
+ *      the setting off: they come from the pixel's own pinhole ray, which the launch that holds the frame's first sample marches
+ *      once more and shades nothing from.  A stats frame's steps, node_visits, primary_steps and primary_node_visits count that
+ *      march and every sample's own primary march
+ *   6  max_ray_bounces == 0 still gives zeros
+ * opts NULL, or pixel_spread and aperture both +0 / -0: off, the default — frames are byte for byte those of a context that
+ * never called this, the same kernels run, and nothing more is launched or allocated.  A null context, one of the three floats
+ * negative, NaN or infinite, pixel_spread > 8, aperture != 0 with focus_distance == 0, flags != 0: VRT_ERR_INVALID_ARG; a refused
+ * call changes nothing.  A call that changes the setting (off is 16 zero bytes; with aperture == 0 focus_distance is not
+ * compared) restarts the accumulation; one that does not, does not.  A multi-device context replicates the setting; a shard
+ * context keeps its own. */
+typedef struct {
+    float    pixel_spread;    /* width of the box pixel filter in pixels; 0 = every sample through the pixel's own ray */
+    float    aperture;        /* lens radius in voxels; 0 = pinhole */
+    float    focus_distance;  /* distance along each pixel's ray at which the image is sharp; read only when aperture != 0 */
+    uint32_t flags;           /* 0 */
+} vrt_camera_sampling;        /* 16 B */
+int vrt_set_camera_sampling(vrt_ctx *ctx, const vrt_camera_sampling *opts);
+
 /* Block until everything enqueued on the context's stream has finished. */
 int vrt_synchronize(vrt_ctx *ctx);
 

@@ -179,6 +179,14 @@ uint64_t vrth_chunk_msg_encode(const vrth_world *w, const int32_t chunk_pos[3], 
  * Returns 0, or -1 for a null array or options vrt_set_denoise refuses with VRT_ERR_INVALID_ARG. */
 int vrth_denoise(const float *rgb, const uint32_t *ids, const uint32_t *guide, uint32_t w, uint32_t h, const vrt_denoise_opts *opts, float *out);
 
+/* ---- the path trace's camera sampling (include/vrt.h: vrt_set_camera_sampling) on the host ---- */
+/* One sample's own primary ray in the text the kernels compile (csrc/both/lens_math.h), from its four draws u[4]: out[0..2] the
+ * direction of step 2 before it is normalised, out[3..5] the ray's origin o' and out[6..8] the vector that is normalised into
+ * d' (F - o'; with aperture == 0: the origin, and out[0..2] again).  world_min: vrt_world_data.min.  The setting is taken as it
+ * is (not checked).  Returns 0, or -1 for a null argument. */
+int vrth_lens_ray(const vrt_cam_data *cam, const int32_t world_min[3], const vrt_camera_sampling *opts, uint32_t px, uint32_t py, const float u[4],
+                  float out[9]);
+
 #ifdef __cplusplus
 }
 #endif

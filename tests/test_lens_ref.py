@@ -1,0 +1,201 @@
+"""tests/lens_ref.c, the tests' reference for camera sampling in the path trace (vrt_set_camera_sampling), without a GPU: with the
+setting off it is tests/sun_ref.c bit for bit; with it on, the id words are the off frame's (they come from the pixel's own pinhole
+ray) while the four draws shift every sample's stream; on C4 at the sizes the GPU tests use, jittered samples do land on other
+faces than their pixel's centre and every lens sample leaves from another point than the camera; one sample's ray is followed
+by hand in numpy binary32 and held against the reference's and against the text the kernels compile (csrc/both/lens_math.h,
+through libvrt_host.so: vrth_lens_ray), bit for bit; and K frames of s samples are one frame of K * s.
+
+What holds on C4 at 100 x 60 and 128 x 72 (seed 11, 1 spp; printed by the test): pixel_spread 1 alone changes the primary id word of
+1190 and 1792 samples; aperture 0.25 moves all 5376 and 9216 samples; with focus_distance 32 — the distance most of the scene
+lies at — 256 and 515 of them hit another face than the pinhole ray (blurred) and the rest the same one (sharp).  FOCUS = 32 is
+what tests/test_gpu_lens.py takes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import lens_ref
+import sun_ref
+from emission_cases import common
+from test_sun_ref import _tables
+from voxelraytracing_amd import _ffi, scenes
+
+SEED = 11
+F = np.float32
+JITTER, FOCUS = (1.0, 0.0, 0.0), 32.0
+LENS, BOTH = (0.0, 0.25, FOCUS), (1.0, 0.25, FOCUS)
+
+
+@pytest.fixture(scope="module")
+def lref(tmp_path_factory):
+    return lens_ref.load(tmp_path_factory.mktemp("lens_ref"))
+
+
+@pytest.fixture(scope="module")
+def sref(tmp_path_factory):
+    return sun_ref.load(tmp_path_factory.mktemp("sun_ref"))
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+def test_off_is_the_sun_reference(lref, sref, orc, spp):
+    W, H = 64, 40
+    sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
+    o = orc.from_package_scene(sc)
+    _, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=1, seed=SEED)
+    e, p, t = _tables(plain_ids)
+    for tables in ((None, None, None), (e, p, t)):
+        for strength in (0.0, 1.0):
+            want_rgb, want_ids = sref.render(o, strength, W, H, spp=spp, seed=SEED, emission=tables[0], polish=tables[1], translucency=tables[2])
+            for off in (lens_ref.OFF, (-0.0, -0.0, 5.0)):
+                rgb, ids = lref.render(o, off, W, H, spp=spp, seed=SEED, strength=strength, emission=tables[0], polish=tables[1], translucency=tables[2])
+                assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+                n = lref.counts
+                assert (n.steps, n.bounce_segments, n.sun_rays) == (sref.counts.steps, sref.counts.bounce_segments, sref.counts.sun_rays)
+                assert n.jitter_changed == 0 and n.lens_moved == 0
+
+
+@pytest.mark.parametrize("size", [(100, 60), (128, 72)])
+def test_every_kind_of_sample_occurs_at_the_sizes_the_gpu_tests_use(lref, orc, size):
+    W, H = size
+    traced = (W & ~7) * (H & ~7)
+    sc = scenes.c4(size)   # (kept alive)
+    o = orc.from_package_scene(sc)
+    off_rgb, off_ids = lref.render(o, lens_ref.OFF, W, H, spp=1, seed=SEED)
+    off = lref.counts
+    for name, setting in (("jitter", JITTER), ("lens", LENS), ("both", BOTH)):
+        rgb, ids = lref.render(o, setting, W, H, spp=1, seed=SEED)
+        n = lref.counts
+        print(f"{size} {name} {setting}: {n}")
+        assert np.array_equal(ids, off_ids)              # the id words are the centre ray's: those of the frame with the setting off
+        assert np.isfinite(rgb).all() and not np.array_equal(_bits(rgb), _bits(off_rgb))
+        assert n.steps > off.steps                       # (the centre march is counted on top of the samples' own)
+        assert n.jitter_changed >= 1                     # some samples' own primary segment ends on another face ...
+        assert n.jitter_changed < traced                 # ... and some on the centre ray's (with a lens: blurred and sharp)
+        assert n.lens_moved == (traced if setting[1] else 0)
+
+
+def test_the_four_draws_shift_the_stream_where_the_ray_stays(lref, orc):
+    """pixel_spread 1 on a frame small enough that many samples hit the face their pixel's centre hits: their light differs all
+    the same, because the bounce's draws are now the fifth and later of the stream."""
+    W, H = 64, 40
+    sc = scenes.c4((W, H))   # (kept alive)
+    o = orc.from_package_scene(sc)
+    off_rgb, off_ids = lref.render(o, lens_ref.OFF, W, H, spp=1, seed=SEED)
+    rgb, ids = lref.render(o, JITTER, W, H, spp=1, seed=SEED)
+    same_face = changed = 0
+    hit = np.argwhere((off_ids & orc.ID_HIT) != 0)[::5]
+    for py, px in hit:
+        _, sid, _ = lref.trace_pixel(o, JITTER, W, H, int(px), int(py), seed=SEED)
+        if sid == off_ids[py, px]:
+            same_face += 1
+            changed += not np.array_equal(_bits(rgb[py, px]), _bits(off_rgb[py, px]))
+    print(f"{same_face} of {len(hit)} samples on their centre ray's face, {changed} of them with another light")
+    assert same_face >= 100 and changed >= same_face // 2
+    # a setting so small that no ray moves to another voxel face still shifts the stream
+    tiny_rgb, _ = lref.render(o, (1e-6, 0.0, 0.0), W, H, spp=1, seed=SEED)
+    assert lref.counts.jitter_changed == 0 and not np.array_equal(_bits(tiny_rgb), _bits(off_rgb))
+
+
+# ---- one sample's ray by hand ----
+
+def _cos2pi(u):
+    """orc_cos2pi / vcos2pi in numpy binary32"""
+    t = F(u * F(4.0))
+    q = F(np.floor(t))
+    a = F(F(t - q) * F(1.57079637))
+    a2 = F(a * a)
+
+    def horner(cs):
+        acc = F(cs[-1])
+        for c in cs[-2::-1]:
+            acc = F(F(c) + F(a2 * acc))
+        return acc
+    sn = F(a * horner([1.0, -0.166666672, 0.00833333377, -0.000198412701, 2.75573188e-06, -2.50521079e-08]))
+    cs = horner([1.0, -0.5, 0.0416666679, -0.00138888892, 2.48015876e-05, -2.75573199e-07, 2.08767559e-09])
+    return (cs, F(-sn), F(-cs), sn)[int(q) & 3]
+
+
+def _dot4(a, b):
+    return F(F(F(F(a[0] * b[0]) + F(a[1] * b[1])) + F(a[2] * b[2])) + F(a[3] * b[3]))
+
+
+def _by_hand(cam, wmin, setting, px, py, u):
+    """[w, o', F - o' (w for a pinhole)] of steps 2 and 3, each operation rounded to binary32, in the contract's order"""
+    spread, aperture, focus = (F(x) for x in setting)
+    u = [F(x) for x in u]
+    ip, iv, ps = [F(x) for x in cam.inv_proj_mat], [F(x) for x in cam.inv_view_mat], [F(x) for x in cam.proj_size]
+    fx = F(F(px) + F(F(u[0] - F(0.5)) * spread))
+    fy = F(F(py) + F(F(u[1] - F(0.5)) * spread))
+    x = F(F(F(fx * F(2.0)) / ps[0]) - F(1.0))
+    y = F(F(F(fy * F(2.0)) / ps[1]) - F(1.0))
+    clip = [x, F(-y), F(-1.0), F(1.0)]
+    eye = [_dot4(clip, ip[0:4]), _dot4(clip, ip[4:8]), F(-1.0), F(0.0)]
+    w = np.array([_dot4(eye, iv[4 * k:4 * k + 4]) for k in range(3)], F)
+    origin = np.array([F(F(cam.pos[k]) - F(float(wmin[k]))) for k in range(3)], F)
+    if aperture == 0:
+        return np.stack([w, origin, w])
+    ln = F(np.sqrt(F(F(F(w[0] * w[0]) + F(w[1] * w[1])) + F(w[2] * w[2]))))
+    d = [F(w[k] / ln) for k in range(3)]
+    r = F(aperture * F(np.sqrt(u[2])))
+    lx, ly = F(r * _cos2pi(u[3])), F(r * _cos2pi(F(u[3] + F(0.75))))
+    Fp = [F(origin[k] + F(d[k] * focus)) for k in range(3)]
+    o = np.array([F(F(origin[k] + F(iv[4 * k] * lx)) + F(iv[4 * k + 1] * ly)) for k in range(3)], F)
+    return np.stack([w, o, np.array([F(Fp[k] - o[k]) for k in range(3)], F)])
+
+
+def _host_ray(cam, wmin, setting, px, py, u):
+    o = _ffi.CameraSampling(*setting, 0)
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    out = np.zeros((3, 3), np.float32)
+    m = (C.c_int32 * 3)(*wmin)
+    assert _ffi.host().vrth_lens_ray(C.byref(cam), m, C.byref(o), px, py, u.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def test_one_samples_ray_by_hand(lref, orc):
+    W, H = 128, 72
+    sc = scenes.c4((W, H))   # (kept alive)
+    o = orc.from_package_scene(sc)
+    wmin = [int(o.c.world.min[k]) for k in range(3)]
+    rng = np.random.default_rng(5)
+    cases = [(0, 0, (0.0, 0.0, 0.0, 0.0)), (W - 1, H - 1, (1.0, 1.0, 1.0, 1.0)), (5, 7, (0.5, 0.5, 0.0, 0.25)), (64, 36, (0.0, 1.0, 1.0, 0.249999)),
+             (17, 3, (0.3, 0.7, 0.5, 0.25)), (17, 3, (0.3, 0.7, 0.5, 0.75)), (17, 3, (0.3, 0.7, 1e-9, 0.999999))]
+    for _ in range(300):
+        cases.append((int(rng.integers(0, W)), int(rng.integers(0, H)), tuple(rng.random(4, dtype=np.float32))))
+    # draws as the RNG makes them: the first four of real samples' streams
+    for px, py in ((0, 0), (50, 20), (127, 71)):
+        cases.append((px, py, tuple(lref.trace_pixel(o, BOTH, W, H, px, py, seed=SEED)[2])))
+    wrapped = 0
+    for setting in (JITTER, LENS, BOTH, (8.0, 3.0, 0.5)):
+        for px, py, u in cases:
+            want = _by_hand(sc.cam, wmin, setting, px, py, u)
+            ref = lref.ray(o, setting, px, py, u)
+            host = _host_ray(sc.cam, wmin, setting, px, py, u)
+            assert np.array_equal(_bits(ref[:3]), _bits(want)), (setting, px, py, u, ref[:3], want)
+            assert np.array_equal(_bits(host), _bits(want)), (setting, px, py, u, host, want)
+            wrapped += F(u[3]) + F(0.75) >= 1
+    assert wrapped >= 100   # (u4 + 0.75 past 1: the cosine's quadrant wraps)
+
+
+@pytest.mark.parametrize("setting", [JITTER, BOTH])
+def test_frames_of_a_sample_base_add_up_to_one_frame(lref, orc, setting):
+    """K frames of s spp are one frame of K * s spp: the means, recombined in sample order as the accumulation does it."""
+    W, H, K, s = 64, 40, 4, 3
+    sc = scenes.c4((W, H))   # (kept alive)
+    o = orc.from_package_scene(sc)
+    whole, whole_ids = lref.render(o, setting, W, H, spp=K * s, seed=SEED, strength=1.0)
+    # a frame's mean is sum / s with the sum taken in sample order; one-sample frames give the samples themselves
+    total = np.zeros_like(whole)
+    for i in range(K * s):
+        rgb, ids = lref.render(o, setting, W, H, spp=1, seed=SEED, sample_base=i, strength=1.0)
+        assert np.array_equal(ids, whole_ids)
+        total = (total + rgb).astype(F)
+    assert np.array_equal(_bits((total / F(K * s)).astype(F)), _bits(whole))
+    # and sample_base does move the draws
+    a, _ = lref.render(o, setting, W, H, spp=s, seed=SEED, sample_base=0)
+    b, _ = lref.render(o, setting, W, H, spp=s, seed=SEED, sample_base=s)
+    assert not np.array_equal(_bits(a), _bits(b))

@@ -299,6 +299,57 @@ static void check_sun_frames() {
     std::printf("check_sun_plan: ok (%ld sun-lit frames, %ld launches)\n", frames, launches);
 }
 
+// vrt_set_camera_sampling: the setting changes which kernels a frame's bounce-0 launches are (plan.lens) and nothing else — the
+// plan of a frame with it is the plan of the same frame without it, field for field and step for step, over the same
+// combinations of the facts, sun-lit or not.  A frame of no bounces has no primary launch: the flag stays off there.
+static void check_lens_frames() {
+    long frames = 0, launches = 0;
+    const uint32_t spps[] = {1, 2, 3, 12, 17}, per_chain[] = {1, 4, 16};
+    const int accums[] = {-1, 0, 7};
+    for (uint32_t spp : spps)
+    for (uint32_t bounces = 0; bounces <= 5; bounces++)
+    for (uint32_t bits = 0; bits < 1024; bits++)
+    for (int accum : accums)
+    for (uint32_t samples : per_chain) {
+        PathFacts F;
+        F.spp = spp; F.seed = 11u; F.bounces = bounces; F.camera_sampling = true;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u; F.sun = bits & 512u;
+        F.march_direct = F.has_cells;
+        F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
+        F.path_samples = samples; F.hit_seg_cap = 512u;
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) continue;
+        std::snprintf(g_case, sizeof g_case, "lens: spp %u bounces %u bits %u accum %d per chain %u", spp, bounces, bits, accum, samples);
+        const PathPlan p = vrt::plan_path(F);
+        PathFacts E = F;
+        E.camera_sampling = false;
+        const PathPlan e = vrt::plan_path(E);
+        CHECK(p.lens == (bounces > 0u) && !e.lens);
+        CHECK(p.spp == e.spp && p.seed == e.seed && p.bounces == e.bounces && p.kstats == e.kstats && p.literal == e.literal && p.emit == e.emit &&
+              p.polish == e.polish && p.translucent == e.translucent && p.sun == e.sun && p.sun_cells == e.sun_cells && p.samples == e.samples &&
+              p.planes == e.planes && p.own_sum == e.own_sum && p.cells == e.cells && p.seg_cap == e.seg_cap && p.cap == e.cap &&
+              p.pool_batches == e.pool_batches && p.refill == e.refill && p.zero_output == e.zero_output && p.finish == e.finish &&
+              p.finish_into_accum == e.finish_into_accum && p.divide_at_end == e.divide_at_end && p.needs_acc_planes == e.needs_acc_planes &&
+              p.needs_accum_sum == e.needs_accum_sum && p.sample_base == e.sample_base && p.accum_count == e.accum_count);
+        std::vector<PathStep> ps, es;
+        vrt::for_each_path_step(p, [&](const PathStep &s) { ps.push_back(s); });
+        vrt::for_each_path_step(e, [&](const PathStep &s) { es.push_back(s); });
+        CHECK(ps.size() == es.size());
+        uint32_t primaries = 0;
+        for (size_t i = 0; i < ps.size() && i < es.size(); i++) {
+            const PathStep &t = ps[i], &s = es[i];
+            CHECK(t.kind == s.kind && t.sample == s.sample && t.chain == s.chain && t.launch == s.launch && t.segments == s.segments &&
+                  t.last_bounce == s.last_bounce && t.first == s.first && t.last == s.last && t.count == s.count);
+            primaries += t.kind == vrt::kStepPrimary || t.kind == vrt::kStepSunlitPrimary;
+        }
+        // one bounce-0 launch per chain — the launch of the chain that holds sample 0 is the one that marches the centre ray
+        CHECK(primaries == (bounces ? (spp + p.samples - 1u) / p.samples : 0u));
+        frames++;
+        launches += (long)ps.size();
+    }
+    std::printf("check_lens_plan: ok (%ld frames with camera sampling, %ld launches)\n", frames, launches);
+}
+
 int main() {
     long compared[3][4] = {}, skipped = 0;
     const uint32_t flag_sets[4] = {0u, VRT_RENDER_OWN_STREAMS, VRT_RENDER_ACCUMULATE, VRT_RENDER_OWN_STREAMS | VRT_RENDER_ACCUMULATE};
@@ -361,5 +412,6 @@ int main() {
     std::printf("check_frame_plan: ok (%ld frames compared, %ld refused)\n", total, skipped);
     check_path_frames();
     check_sun_frames();
+    check_lens_frames();
     return 0;
 }

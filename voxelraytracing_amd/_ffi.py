@@ -93,6 +93,11 @@ class SunLight(C.Structure):
     _fields_ = [("strength", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
 
 
+class CameraSampling(C.Structure):
+    """include/vrt.h vrt_camera_sampling: the path trace's pixel jitter and thin lens (vrt_set_camera_sampling)"""
+    _fields_ = [("pixel_spread", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32)]
+
+
 class RayQuery(C.Structure):
     """include/vrt.h vrt_ray_query: common::math::cast_ray's arguments (common/src/math.rs:153-158)"""
     _fields_ = [("start", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("_reserved", C.c_uint32)]
@@ -149,6 +154,7 @@ assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 assert C.sizeof(DenoiseOpts) == 16
 assert C.sizeof(SunLight) == 16
+assert C.sizeof(CameraSampling) == 16
 assert POLISH_DTYPE.itemsize == 32
 assert TRANSLUCENCY_DTYPE.itemsize == 16
 
@@ -186,6 +192,7 @@ VRT_SYMBOLS = {
     "vrt_set_denoise": (C.c_int, [_P, C.POINTER(DenoiseOpts)]),
     "vrt_read_guide": (C.c_int, [_P, _P]),
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
+    "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
     "vrt_synchronize": (C.c_int, [_P]),
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),
@@ -366,6 +373,7 @@ VRTH_SYMBOLS = {
     "vrth_region_of_chunk": (None, [_I32P, _I32P, _U32P]),
     "vrth_region_file_name": (C.c_uint32, [_I32P, C.c_char_p, C.c_uint32]),
     "vrth_denoise": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseOpts), _P]),
+    "vrth_lens_ray": (C.c_int, [_P, _I32P, C.POINTER(CameraSampling), C.c_uint32, C.c_uint32, _P, _P]),
 }
 
 # Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)

@@ -10,6 +10,7 @@
 #include "../../../include/vrt_host.h"
 #include "../both/cast_dda.h"
 #include "../both/denoise_math.h"
+#include "../both/lens_math.h"
 #include "../both/shape_math.h"
 #include "collide.hpp"
 #include "edit_check.hpp"
@@ -564,6 +565,26 @@ int vrth_denoise(const float *rgb, const uint32_t *ids, const uint32_t *guide, u
         a.swap(b);   // (the pixels a pass copies never change: both copies hold them from the start)
     }
     std::memcpy(out, a.data(), n * 3 * sizeof(float));
+    return 0;
+}
+
+// vrt_set_camera_sampling's primary ray of one sample: csrc/both/lens_math.h's two halves with the plain operators, and the
+// normalisation between them as orc_normalize / vnormalize write it
+int vrth_lens_ray(const vrt_cam_data *cam, const int32_t world_min[3], const vrt_camera_sampling *opts, uint32_t px, uint32_t py, const float u[4],
+                  float out[9]) {
+    if (!cam || !world_min || !opts || !u || !out) return -1;
+    auto div = [](float n, float d) { return n / d; };
+    auto sqrt_of = [](float x) { return sqrtf(x); };
+    const vrt::LensV3 w = vrt::lens_pixel_dir(px, py, u[0], u[1], opts->pixel_spread, cam->proj_size, cam->inv_proj_mat, cam->inv_view_mat, div);
+    const vrt::LensV3 origin{cam->pos[0] - (float)world_min[0], cam->pos[1] - (float)world_min[1], cam->pos[2] - (float)world_min[2]};
+    vrt::LensV3 o = origin, v = w;
+    if (opts->aperture != 0.0f) {
+        const float len = sqrtf(w.x * w.x + w.y * w.y + w.z * w.z);
+        const vrt::LensV3 d{w.x / len, w.y / len, w.z / len};
+        vrt::lens_thin(origin, d, u[2], u[3], opts->aperture, opts->focus_distance, cam->inv_view_mat, sqrt_of, o, v);
+    }
+    const float r[9] = {w.x, w.y, w.z, o.x, o.y, o.z, v.x, v.y, v.z};
+    std::memcpy(out, r, sizeof r);
     return 0;
 }
 

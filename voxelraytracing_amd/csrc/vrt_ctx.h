@@ -84,6 +84,9 @@ void launch_path_bounce_cells(const FrameParams &P, uint32_t refill_at, uint32_t
 void launch_path_primary_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
 void launch_path_bounce_sunlit(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
 void launch_path_sun(const FrameParams &P, const SunLaunch &S, bool stats, bool literal, bool cells, hipStream_t st);
+// vrt_set_camera_sampling (vrt_path_lens.h): bounce 0 of a frame with the setting on, plain and sun-lit
+void launch_path_primary_lens(const FrameParams &P, const LensLaunch &L, bool stats, bool literal, hipStream_t st);
+void launch_path_primary_lens_sunlit(const FrameParams &P, const LensLaunch &L, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -428,6 +431,7 @@ struct vrt_ctx {
     // guide words are sz.dn_scratch / sz.dn_guide
     vrt_denoise_opts denoise{};
     vrt_sun_light sun{};      // vrt_set_sun_light: the setting (16 zero bytes: off); the sun-ray buffers are sz.sun_recs / sz.sun_counts
+    vrt_camera_sampling lens{};   // vrt_set_camera_sampling: the setting (16 zero bytes: off)
     bool rendered = false;
     bool timing_pending = false;
     vrt_stats stats;

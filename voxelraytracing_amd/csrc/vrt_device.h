@@ -155,6 +155,13 @@ struct SunLaunch {
 };
 constexpr uint32_t kSunLobePolish = 1u, kSunLobeTranslucent = 2u;
 
+// vrt_set_camera_sampling (vrt_path_lens.h): what the primary kernels of a frame with the setting on are given besides
+// FrameParams — again an argument of its own
+struct LensLaunch {
+    float pixel_spread, aperture, focus_distance;   // the setting
+    uint32_t lobes;       // kSunLobePolish | kSunLobeTranslucent, as SunLaunch::lobes
+};
+
 // The path-trace buffers are compacted per segment, not globally: one device-scope counter saturates at ~88
 // returning atomics per microsecond (MI355X_MICROARCH.md "dequeue"), which made 32 400 per-wave atomics the
 // whole 0.37 ms of the first primary kernel.  Workgroup b appends to segment b % kHitSegments; each counter

@@ -91,6 +91,7 @@ struct PathFacts {   // copied out of the options, the context and the frame's p
     bool polished = false;          // vrt_write_polish: some material's coat has a chance that is not 0
     bool translucent = false;       // vrt_write_translucency: some material lets a path through with a chance that is not 0
     bool sun = false;               // vrt_set_sun_light: the strength is not 0
+    bool camera_sampling = false;   // vrt_set_camera_sampling: pixel_spread or aperture is not 0
     // the context's switches (vrt_create reads them from the environment)
     uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
     bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
@@ -109,7 +110,7 @@ enum PathFinish : uint32_t {   // the pass behind each chain of samples
 
 struct PathPlan {   // each field is explained where plan_path sets it
     uint32_t spp = 1, seed = 0, bounces = 0;
-    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false;
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false, lens = false;
     uint32_t samples = 1;
     bool planes = false, own_sum = false, cells = false;
     uint32_t seg_cap = 0;
@@ -157,6 +158,9 @@ inline PathPlan plan_path(const PathFacts &F) {
     p.emit = F.emissive || F.polished || F.translucent || p.sun;
     p.polish = F.polished;
     p.translucent = F.translucent;
+    // vrt_set_camera_sampling: the frame's kStepPrimary / kStepSunlitPrimary launches are the kernels of vrt_path_lens.h, which give
+    // every sample a primary ray of its own; the chains, the launches behind bounce 0 and the finishing passes are what they are
+    p.lens = F.camera_sampling && F.bounces > 0u;
     p.own_sum = p.emit && !p.planes && !F.accum && F.spp > 1u && F.bounces > 0u;
     // a segment of the path buffers holds what its workgroups can produce for every sample of a chain; a buffer, every segment
     p.seg_cap = F.hit_seg_cap * p.samples;

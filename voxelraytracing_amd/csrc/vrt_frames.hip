@@ -342,6 +342,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         S.k = c->settings.sun_intensity * c->sun.strength;   // (one binary32 product: the contract's k)
         S.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
     }
+    // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
+    const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance,
+                            (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u)};
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
     P.hit_seg_cap = plan.seg_cap;
     P.acc = plan.planes ? acc : nullptr;
@@ -382,10 +385,16 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             sum_waited = true;
         }
         switch (s.kind) {
-            case kStepPrimary: launch_path_primary(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
+            case kStepPrimary:
+                if (plan.lens) launch_path_primary_lens(P, L, plan.kstats, plan.literal, f.st);
+                else launch_path_primary(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st);
+                break;
             case kStepLaneBounce: launch_path_bounce(P, plan.kstats, plan.literal, plan.emit, plan.polish, plan.translucent, f.st); break;
             case kStepCellsBounce: launch_path_bounce_cells(P, plan.refill, s.segments, plan.pool_batches, plan.emit, plan.polish, plan.translucent, f.st); break;
-            case kStepSunlitPrimary: launch_path_primary_sunlit(P, S, plan.kstats, plan.literal, f.st); break;
+            case kStepSunlitPrimary:
+                if (plan.lens) launch_path_primary_lens_sunlit(P, L, S, plan.kstats, plan.literal, f.st);
+                else launch_path_primary_sunlit(P, S, plan.kstats, plan.literal, f.st);
+                break;
             case kStepSunlitBounce: launch_path_bounce_sunlit(P, S, plan.kstats, plan.literal, f.st); break;
             case kStepSunRays: launch_path_sun(P, S, plan.kstats, plan.literal, plan.sun_cells, f.st); break;
             case kStepChainFinish:
@@ -762,6 +771,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.has_grid = P.grid != nullptr; PF.has_cells = P.mblk != nullptr; PF.march_direct = P.march_direct != 0u;
             PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u; PF.translucent = c->n_translucent != 0u;
             PF.sun = c->sun.strength != 0.0f;
+            PF.camera_sampling = c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
             PF.in_flight = c->in_flight; PF.hit_seg_cap = c->hit_seg_cap;
@@ -803,6 +813,28 @@ int vrt_set_sun_light(vrt_ctx *c, const vrt_sun_light *opts) {
     if (o.strength == 0.0f) memset(&o, 0, sizeof o);   // (-0: off is 16 zero bytes)
     if (memcmp(&c->sun, &o, sizeof o) != 0) c->accum_restart = true;
     c->sun = o;
+    return VRT_OK;
+}
+
+int vrt_set_camera_sampling(vrt_ctx *c, const vrt_camera_sampling *opts) {
+    if (!c) return VRT_ERR_INVALID_ARG;
+    vrt_camera_sampling o;
+    memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    const float f[3] = {o.pixel_spread, o.aperture, o.focus_distance};
+    for (float x : f)
+        if (!(x >= 0.0f) || std::isinf(x))
+            return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_camera_sampling: pixel_spread %g, aperture %g, focus_distance %g (each 0 or a finite positive number)",
+                        (double)o.pixel_spread, (double)o.aperture, (double)o.focus_distance);
+    if (o.pixel_spread > 8.0f) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_camera_sampling: pixel_spread %g (at most 8 pixels)", (double)o.pixel_spread);
+    if (o.aperture != 0.0f && o.focus_distance == 0.0f) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_camera_sampling: an aperture needs a focus_distance");
+    if (o.flags) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_camera_sampling: flags must be 0");
+    GRP_EACH(c, vrt_set_camera_sampling(d, opts));
+    // what is kept: -0 as +0, and no focus distance without a lens (it is not read, so it is not compared; off is 16 zero bytes)
+    if (o.pixel_spread == 0.0f) o.pixel_spread = 0.0f;
+    if (o.aperture == 0.0f) o.aperture = o.focus_distance = 0.0f;
+    if (memcmp(&c->lens, &o, sizeof o) != 0) c->accum_restart = true;
+    c->lens = o;
     return VRT_OK;
 }
 

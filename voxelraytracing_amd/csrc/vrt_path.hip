@@ -23,6 +23,7 @@
 
 #include "vrt_path_common.h"
 #include "vrt_path_sun.h"
+#include "both/lens_math.h"
 
 namespace vrt {
 
@@ -60,6 +61,14 @@ static inline size_t lds_bytes_path(const FrameParams &P, bool lds_roots) { retu
 #undef VRT_PRIMARY_POLISH
 #undef VRT_PRIMARY_TRANSLUCENT
 #undef VRT_PRIMARY_SUN
+#define VRT_LENS_KERNEL path_lens_primary_kernel   // (vrt_set_camera_sampling: a primary ray of its own for every sample)
+#include "vrt_path_lens.h"
+#undef VRT_LENS_KERNEL
+#define VRT_LENS_KERNEL path_lens_sun_primary_kernel
+#define VRT_LENS_SUN
+#include "vrt_path_lens.h"
+#undef VRT_LENS_KERNEL
+#undef VRT_LENS_SUN
 
 // One segment of a path: its march, then path_after_march.
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool EMIT, bool POLISH, bool TRANSLUCENT>
@@ -351,6 +360,27 @@ void launch_path_sun(const FrameParams &P, const SunLaunch &S, bool stats, bool 
         return;
     }
     VRT_PATH_LAUNCH(path_sun_kernel, );
+}
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, L
+
+// vrt_set_camera_sampling: bounce 0 of a frame with the setting on (vrt_path_lens.h); the launches behind it are the frame's own
+void launch_path_primary_lens(const FrameParams &P, const LensLaunch &L, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
+    if (P.acc) {   // several samples per launch chain: plain frames over the derived tables only
+        hipLaunchKernelGGL((path_lens_primary_kernel<0, false, false, true>), grid, block, lds_bytes_path(P, false), st, P, L);
+        return;
+    }
+    VRT_PATH_LAUNCH(path_lens_primary_kernel, );
+}
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, L, S
+
+void launch_path_primary_lens_sunlit(const FrameParams &P, const LensLaunch &L, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
+    VRT_PATH_LAUNCH(path_lens_sun_primary_kernel, );
 }
 #undef VRT_PATH_ARGS
 #undef VRT_PATH_LAUNCH

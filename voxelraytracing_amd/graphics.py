@@ -202,6 +202,14 @@ class Gpu:
         o = _ffi.SunLight(strength, 0, (C.c_uint32 * 2)(0, 0))
         self._ck(self._lib.vrt_set_sun_light(self._h, C.byref(o)))
 
+    def set_camera_sampling(self, pixel_spread: float, aperture: float = 0.0, focus_distance: float = 0.0):
+        """vrt_set_camera_sampling: every sample of a later MODE_PATH frame gets a primary ray of its own — through a point of
+        the pixel_spread-wide box around the pixel's centre (1: the pixel itself; 0: no jitter) and, with aperture != 0, from
+        a point of a lens of that radius (in voxels) towards the point of the pixel's ray focus_distance away.  Both 0 = off,
+        the default.  The primary modes ignore it; changing it restarts the accumulation."""
+        o = _ffi.CameraSampling(pixel_spread, aperture, focus_distance, 0)
+        self._ck(self._lib.vrt_set_camera_sampling(self._h, C.byref(o)))
+
     def synchronize(self):
         self._ck(self._lib.vrt_synchronize(self._h))
 
