@@ -262,6 +262,38 @@ pub struct vrt_camera_sampling {
     pub flags: u32,
 }
 
+/// vrt_set_lamp_light: next-event estimation towards the world's emissive voxels for the path trace (strength 0 = off;
+/// max_geometry 0 = the geometry factor is not clamped).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_lamp_light {
+    pub strength: f32,
+    pub max_geometry: f32,
+    pub flags: u32,
+    pub _reserved: u32,
+}
+
+/// An entry of the lamp list (vrt_read_lamps): a face of an emissive voxel, world-local voxel coordinates; face = 2 * axis + side.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_lamp {
+    pub pos: [u16; 3],
+    pub voxel: u16,
+    pub face: u32,
+    pub _reserved: u32,
+}
+
+/// The lamp list the last lamp-lit frame used (vrt_get_lamp_info).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_lamp_info {
+    pub listed: u32,
+    pub cap: u32,
+    pub faces: u64,
+    pub builds: u32,
+    pub last_build_ms: f32,
+}
+
 /// What issuing a frame costs the host (vrt_get_issue_profile), microseconds per vrt_render call.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -328,6 +360,9 @@ extern "C" {
     pub fn vrt_read_guide(ctx: *mut vrt_ctx, guide: *mut u32) -> c_int;
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
     pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
+    pub fn vrt_set_lamp_light(ctx: *mut vrt_ctx, opts: *const vrt_lamp_light) -> c_int;
+    pub fn vrt_get_lamp_info(ctx: *mut vrt_ctx, out: *mut vrt_lamp_info) -> c_int;
+    pub fn vrt_read_lamps(ctx: *mut vrt_ctx, out: *mut vrt_lamp, cap: u32, n: *mut u32) -> c_int;
     pub fn vrt_synchronize(ctx: *mut vrt_ctx) -> c_int;
     pub fn vrt_read_output(ctx: *mut vrt_ctx, rgb: *mut f32, ids: *mut u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_present(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8: *mut u8) -> c_int;
@@ -377,6 +412,9 @@ mod layout {
         assert!(size_of::<vrt_denoise_opts>() == 16);
         assert!(size_of::<vrt_sun_light>() == 16);
         assert!(size_of::<vrt_camera_sampling>() == 16);
+        assert!(size_of::<vrt_lamp_light>() == 16);
+        assert!(size_of::<vrt_lamp>() == 16);
+        assert!(size_of::<vrt_lamp_info>() == 24);
         assert!(size_of::<vrt_shape>() == 40);
         assert!(size_of::<vrt_polish>() == 32);
         assert!(size_of::<vrt_translucency>() == 16);

@@ -492,6 +492,74 @@ typedef struct {
 } vrt_camera_sampling;        /* 16 B */
 int vrt_set_camera_sampling(vrt_ctx *ctx, const vrt_camera_sampling *opts);
 
+/* Lamp light for VRT_MODE_PATH: next-event estimation towards the world's emissive voxels (vrt_write_emission).  A lamp of a
+ * few voxels is found by a random bounce a handful of times in a thousand; with vrt_set_lamp_light every hit of a path sends a
+ * ray to a point of a lamp face instead.  The primary modes ignore the setting and stay byte for byte what they are.
+ *
+ * The lamp list.  A lamp face is face f of a unit voxel p of the world with voxel id v for which emission[min(v,255)] != 0, v is
+ * not 0 and not a liquid of the material table, and the unit voxel across the face is passable: air, a liquid, outside the
+ * world box, or in a chunk whose chunk_roots entry is 0.  f = 2 * axis + side: 0 = -x, 1 = +x, 2 = -y, 3 = +y, 4 = -z, 5 = +z.
+ * The list holds the lamp faces of the whole world by ascending depth-3 cell index (x fastest, as vrt_read_accel's grid), then
+ * ascending u = (x&3) | (y&3)<<2 | (z&3)<<4 inside the cell, then ascending f; every unit voxel of a large leaf is looked at on
+ * its own.  It is derived on the GPU from the derived tables, the liquid set and the emission table, on the stream of the frame
+ * that needs it and without a host round trip, whenever one of the three changed since its last build; each frame set in
+ * flight has a list of its own.  It is capped at 2^20 entries (VRT_LAMP_CAP, read by vrt_create, overrides the cap): a world
+ * with more faces lists the first `cap` in order, and vrt_lamp_info.faces still counts them all.  N is the list's length.
+ *
+ * Build-defined, and defined exactly — the body of ray_color's loop on a hit, in a lamp-lit frame (strength != 0,
+ * max_ray_bounces > 0), in strict binary32, nothing contracted:
+ *   1  mc as without the setting
+ *   2  the emission term (mc * e) * thr is added only while the path is direct: a path starts direct, stays direct through
+ *      pass-throughs (vrt_write_translucency) and stops being direct at its first bounce; after that the lamps are counted by
+ *      step 5 and not twice.  A lamp seen through a pane still shines
+ *   3  the sun term (vrt_set_sun_light) unchanged, if the sun is on
+ *   4  three draws u1, u2, u3 = rng_next, in that order, on every hit of every segment — the last allowed segment's included —
+ *      whatever the voxel and whatever N is, ahead of the pass-through draw, the coat's draw and the direction's six draws
+ *      (camera sampling's four draws stay first)
+ *   5  the lamp term, only if the hit voxel is not 0 and not a liquid, and N > 0:
+ *        so = pos + norm * bias                                  (the bounce origin, as the sun term's)
+ *        j = min((uint32_t)(u1 * (float)N), N - 1);  L = list[j];  a = L.face >> 1;  s = L.face & 1
+ *        q[a] = (float)L.pos[a] + (float)s;  the other two axes b < c:  q[b] = (float)L.pos[b] + u2;  q[c] = (float)L.pos[c] + u3
+ *        v = q - so;  d2 = (v.x*v.x + v.y*v.y) + v.z*v.z;  ld = normalize(v)
+ *        c = dot(norm, ld);  cl = s ? -ld[a] : ld[a]
+ *        only if c > 0 && cl > 0 (a NaN gives no ray): march ray_world(so, ld), start nudge included
+ *        unoccluded = the march hits AND (int)floor(hit pos) == L.pos on all three axes (liquids are passed; running out of
+ *        steps counts as occluded)
+ *        g = (c * cl) / d2;  if (max_geometry != 0 && g > max_geometry) g = max_geometry
+ *        k = ((strength * emission[min(L.voxel,255)]) * 0.318309886f) * (float)N;  w = k * g
+ *        lc = materials[min(L.voxel,255)].color with hit_color's face factors for face L.face in hit_color's order (x faces
+ *        * 0.5, z faces * 0.7, face 2 * 0.2); show_step_count's grey is not applied to lc
+ *        if unoccluded:  light.ch += ((mc.ch * lc.ch) * w) * thr.ch
+ *   6  everything behind it unchanged and in its order
+ *   7  within a segment: emission, sun, lamp.  A sample's terms go in segment order, the sky last; samples in sample order;
+ *      / spp.  VRT_RENDER_ACCUMULATE keeps its identity.  The id words, vrt_read_steps' primary counts and the denoiser's key
+ *      and guide are those of the frame with the setting off.  Mirror glints of lamps are lost, as the sun's are
+ *   8  vrt_stats.secondary_rays counts the lamp rays marched; a stats frame's steps and node_visits include their marches; a
+ *      timed frame's ms_secondary includes their launches
+ * With scatter = 1 the bounce normalize(norm + rng_next_dir) is cosine-weighted, a face has area 1 and is picked with
+ * probability 1 / N: at strength 1 the term is the expectation of the emission term the next segment would have added.
+ * opts NULL or strength +0 / -0: off, the default — frames are byte for byte those of a context that never called this, the
+ * same kernels run, and nothing is launched, built or allocated.  A null context, strength or max_geometry negative, NaN or
+ * infinite, flags or _reserved not 0: VRT_ERR_INVALID_ARG; a refused call changes nothing.  A lamp-lit path frame of a world
+ * that keeps no derived tables: VRT_ERR_STATE, nothing enqueued.  A call that changes the setting restarts the accumulation.
+ * A multi-device context replicates the setting and every device builds its own identical list; a shard context keeps its own. */
+typedef struct {
+    float    strength;      /* 0 = off (the default); 1 = matched to what a diffuse path finds by chance */
+    float    max_geometry;  /* 0 = no clamp; otherwise the geometry factor g is clamped to it (fireflies in corners) */
+    uint32_t flags;         /* 0 */
+    uint32_t _reserved;     /* 0 */
+} vrt_lamp_light;           /* 16 B */
+int vrt_set_lamp_light(vrt_ctx *ctx, const vrt_lamp_light *opts);
+
+typedef struct { uint16_t pos[3]; uint16_t voxel; uint32_t face; uint32_t _reserved; } vrt_lamp;   /* 16 B, world-local voxel coordinates */
+typedef struct { uint32_t listed; uint32_t cap; uint64_t faces; uint32_t builds; float last_build_ms; } vrt_lamp_info;   /* 24 B */
+/* The list the last lamp-lit frame used: its length, the cap, the world's lamp faces (saturating at 2^64 - 1), the whole builds
+ * of that frame set's list so far and what the last one took on the GPU.  Synchronises.  VRT_ERR_STATE before the first
+ * lamp-lit frame. */
+int vrt_get_lamp_info(vrt_ctx *ctx, vrt_lamp_info *out);
+/* ... and its first min(cap, listed) entries into out (out may be NULL with cap 0); *n = listed.  Synchronises. */
+int vrt_read_lamps(vrt_ctx *ctx, vrt_lamp *out, uint32_t cap, uint32_t *n);
+
 /* Block until everything enqueued on the context's stream has finished. */
 int vrt_synchronize(vrt_ctx *ctx);
 

@@ -98,6 +98,24 @@ class CameraSampling(C.Structure):
     _fields_ = [("pixel_spread", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32)]
 
 
+class LampLight(C.Structure):
+    """include/vrt.h vrt_lamp_light: the path trace's lamp light (vrt_set_lamp_light)"""
+    _fields_ = [("strength", C.c_float), ("max_geometry", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class Lamp(C.Structure):
+    """include/vrt.h vrt_lamp: an entry of the lamp list (vrt_read_lamps)"""
+    _fields_ = [("pos", C.c_uint16 * 3), ("voxel", C.c_uint16), ("face", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class LampInfo(C.Structure):
+    """include/vrt.h vrt_lamp_info (vrt_get_lamp_info)"""
+    _fields_ = [("listed", C.c_uint32), ("cap", C.c_uint32), ("faces", C.c_uint64), ("builds", C.c_uint32), ("last_build_ms", C.c_float)]
+
+
+LAMP_DTYPE = np.dtype([("pos", "<u2", (3,)), ("voxel", "<u2"), ("face", "<u4"), ("_reserved", "<u4")])
+
+
 class RayQuery(C.Structure):
     """include/vrt.h vrt_ray_query: common::math::cast_ray's arguments (common/src/math.rs:153-158)"""
     _fields_ = [("start", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("_reserved", C.c_uint32)]
@@ -154,6 +172,7 @@ assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 assert C.sizeof(DenoiseOpts) == 16
 assert C.sizeof(SunLight) == 16
+assert C.sizeof(LampLight) == 16 and C.sizeof(Lamp) == 16 and LAMP_DTYPE.itemsize == 16 and C.sizeof(LampInfo) == 24
 assert C.sizeof(CameraSampling) == 16
 assert POLISH_DTYPE.itemsize == 32
 assert TRANSLUCENCY_DTYPE.itemsize == 16
@@ -193,6 +212,9 @@ VRT_SYMBOLS = {
     "vrt_read_guide": (C.c_int, [_P, _P]),
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
     "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
+    "vrt_set_lamp_light": (C.c_int, [_P, C.POINTER(LampLight)]),
+    "vrt_get_lamp_info": (C.c_int, [_P, C.POINTER(LampInfo)]),
+    "vrt_read_lamps": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     "vrt_synchronize": (C.c_int, [_P]),
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),

@@ -87,6 +87,12 @@ void launch_path_sun(const FrameParams &P, const SunLaunch &S, bool stats, bool 
 // vrt_set_camera_sampling (vrt_path_lens.h): bounce 0 of a frame with the setting on, plain and sun-lit
 void launch_path_primary_lens(const FrameParams &P, const LensLaunch &L, bool stats, bool literal, hipStream_t st);
 void launch_path_primary_lens_sunlit(const FrameParams &P, const LensLaunch &L, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
+// vrt_set_lamp_light (vrt_path_lamp.h): a lamp-lit frame's trace launches — one pair that carries the sun term too (M.sun) and, the
+// primary one, camera sampling (sampled: L is read) — and the launch behind each that marches the lamp rays it appended
+void launch_path_primary_lamp(const FrameParams &P, const LensLaunch &L, const SunLaunch &S, const LampLaunch &M, bool sampled, bool stats, bool literal,
+                              hipStream_t st);
+void launch_path_bounce_lamp(const FrameParams &P, const SunLaunch &S, const LampLaunch &M, bool stats, bool literal, hipStream_t st);
+void launch_path_lamp_rays(const FrameParams &P, const LampLaunch &M, bool stats, bool literal, hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -233,6 +239,9 @@ struct vrt_ctx {
         // records, and two sets of segment cursors (trace launch g appends to set g & 1 and clears the other for its successor)
         Buf<uint4> sun_recs[kMaxInFlight];
         Buf<uint32_t> sun_counts[kMaxInFlight];
+        // vrt_set_lamp_light: the same again for the lamp rays, made by the frame set's first lamp-lit frame
+        Buf<uint4> lamp_recs[kMaxInFlight];
+        Buf<uint32_t> lamp_counts[kMaxInFlight];
         Buf<uint32_t> d_tile_cost, d_tile_order, d_tile_scratch;   // vrt_order.hip, made together
         bool tile_order_valid = false;
         Buf<vrt::Texel> d_accum;     // VRT_RENDER_ACCUMULATE: the running sum
@@ -269,10 +278,12 @@ struct vrt_ctx {
         std::vector<uint8_t> chunk_may_have_moved;  // rebuilt alone since the last whole-world build: may sit in the pool's tail
         uint32_t chunks_moved = 0;
         uint32_t chunk_builds = 0;              // chunks this set has rebuilt alone (vrt_accel_info reports the most advanced set's)
+        uint64_t gen = 0;                       // what the set's device tables hold: a new value of c->tables_gen with every build, copy and chunk update (the lamp lists' key)
         Event ev_updated;                       // behind this set's last chunk update (a reader of the node pool and chunk_roots)
         bool update_pending = false;            // ... recorded and not yet known to be over
     };
     Tables tabs[kMaxInFlight];
+    uint64_t tables_gen = 0;
     // The sets are split — every frame set its own — only while edits arrive: two copies of the tables are twice the lines
     // in every XCD's 4 MB L2 (measured: + 1.0 % on the C2 frame period).  After kQuietFrames frames without a dirtied chunk
     // every frame set reads tabs[0] again; the next edit splits them (one wait for the frames in flight, then copies).
@@ -432,6 +443,25 @@ struct vrt_ctx {
     vrt_denoise_opts denoise{};
     vrt_sun_light sun{};      // vrt_set_sun_light: the setting (16 zero bytes: off); the sun-ray buffers are sz.sun_recs / sz.sun_counts
     vrt_camera_sampling lens{};   // vrt_set_camera_sampling: the setting (16 zero bytes: off)
+    // vrt_set_lamp_light (vrt_lamp.hip): the setting (16 zero bytes: off), the cap (VRT_LAMP_CAP) and one lamp list per frame set,
+    // built on that set's stream by the lamp-lit frame that finds it out of date: what it was built from is kept beside it
+    vrt_lamp_light lamp{};
+    uint32_t lamp_cap = 1u << 20;
+    struct LampList {
+        Buf<uint4> d_list;                 // lamp_cap entries (include/vrt.h: vrt_lamp)
+        Buf<uint32_t> d_sums, d_bases;     // faces per block of 256 cells, and their exclusive scan (saturating)
+        Buf<uint32_t> d_info;              // [0] listed = N, [1] 0, [2..3] the world's faces in 64 bits
+        bool valid = false;
+        uint32_t tab = 0, S = 0;           // the table set and world size ...
+        uint64_t tab_gen = 0;              // ... its contents ...
+        float emission[256];               // ... the emission table and the liquid set of the last build
+        uint32_t liquid[8];
+        uint32_t builds = 0;
+        Event e0, e1;                      // around the last build (read by vrt_get_lamp_info, never by a frame)
+        float last_ms = 0.f;
+        bool timed = false;                // last_ms is the last build's
+    } lamps[kMaxInFlight];
+    int lamp_last = -1;                    // the frame set whose list the last lamp-lit frame used
     bool rendered = false;
     bool timing_pending = false;
     vrt_stats stats;
@@ -535,6 +565,9 @@ VRT_HIDDEN int ensure_accel_world(vrt_ctx *c);
 VRT_HIDDEN int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st);
 VRT_HIDDEN size_t chunk_dir_entries(uint32_t S);
 VRT_HIDDEN size_t direct_cell_entries(uint32_t S);
+// vrt_lamp.hip: the frame set's lamp list, rebuilt on `st` if what it was built from has changed (the frame's tables are up to date
+// on `st` and it waits for the uploads so far); fills M.list and M.n
+VRT_HIDDEN int lamp_list_for_frame(vrt_ctx *c, uint32_t slot, uint32_t tab, hipStream_t st, vrt::LampLaunch &M);
 
 // ---- one context over several devices (vrt_config.n_devices > 1): vrt_group.hip ----
 // ---------------------------------------------------------------------------------------------------------------------

@@ -162,6 +162,20 @@ struct LensLaunch {
     uint32_t lobes;       // kSunLobePolish | kSunLobeTranslucent, as SunLaunch::lobes
 };
 
+// vrt_set_lamp_light (vrt_path_lamp.h): what the kernels of a lamp-lit path frame are given besides FrameParams and a SunLaunch
+// (whose buffers are null and whose k is 0 when the sun is off)
+struct LampLaunch {
+    const uint4 *list;    // the lamp list (vrt_lamp.hip), an entry as include/vrt.h's vrt_lamp: {pos.x | pos.y << 16, pos.z | voxel << 16, face, 0}
+    const uint32_t *n;    // its length N, on the device: the build is stream-ordered, nothing comes back to the host
+    uint4 *recs;          // three planes of `cap` records: {slot, so.xyz} {ld.xyz, pos.x | pos.y << 16} {term.rgb, pos.z}, segmented like the sun's
+    uint32_t *counts;     // the cursor set this trace launch appends to and its lamp launch reads
+    uint32_t *clear;      // the other set: the next trace launch's, zeroed by this one
+    uint32_t cap, seg_cap;
+    float strength, max_geometry;   // the setting
+    uint32_t lobes;       // kSunLobePolish | kSunLobeTranslucent, as SunLaunch::lobes
+    uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun term, and the later misses' sky without the disc
+};
+
 // The path-trace buffers are compacted per segment, not globally: one device-scope counter saturates at ~88
 // returning atomics per microsecond (MI355X_MICROARCH.md "dequeue"), which made 32 400 per-wave atomics the
 // whole 0.37 ms of the first primary kernel.  Workgroup b appends to segment b % kHitSegments; each counter

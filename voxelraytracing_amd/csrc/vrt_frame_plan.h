@@ -92,6 +92,7 @@ struct PathFacts {   // copied out of the options, the context and the frame's p
     bool translucent = false;       // vrt_write_translucency: some material lets a path through with a chance that is not 0
     bool sun = false;               // vrt_set_sun_light: the strength is not 0
     bool camera_sampling = false;   // vrt_set_camera_sampling: pixel_spread or aperture is not 0
+    bool lamp = false;              // vrt_set_lamp_light: the strength is not 0
     // the context's switches (vrt_create reads them from the environment)
     uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
     bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
@@ -110,7 +111,7 @@ enum PathFinish : uint32_t {   // the pass behind each chain of samples
 
 struct PathPlan {   // each field is explained where plan_path sets it
     uint32_t spp = 1, seed = 0, bounces = 0;
-    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false, lens = false;
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false, lens = false, lamp = false;
     uint32_t samples = 1;
     bool planes = false, own_sum = false, cells = false;
     uint32_t seg_cap = 0;
@@ -142,7 +143,10 @@ inline PathPlan plan_path(const PathFacts &F) {
     // has them, else the trace's own march
     p.sun = F.sun && F.bounces > 0u;
     p.sun_cells = p.sun && fast && F.has_cells && F.path_cells;
-    p.samples = (F.spp > 1u && fast && F.bounces > 0u && !p.sun) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
+    // vrt_set_lamp_light: the same structure for the same reasons — each trace launch is followed by the launch over the lamp rays it
+    // appended (vrt_path_lamp.h), behind the sun launch when the frame is sun-lit too.  Its kernels are one pair that carries both terms
+    p.lamp = F.lamp && F.bounces > 0u;
+    p.samples = (F.spp > 1u && fast && F.bounces > 0u && !p.sun && !p.lamp) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
     p.planes = p.samples > 1u;
     // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
     // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
@@ -155,7 +159,7 @@ inline PathPlan plan_path(const PathFacts &F) {
     // (they take the coat's draw under a word the uploads keep on the device), so translucent is what the launchers look at first
     // vrt_set_sun_light: and again — a sample is then several terms (the sun terms, the sky).  Its kernels are one pair, which reads
     // from its launch whether there is a coat or a pass-through draw
-    p.emit = F.emissive || F.polished || F.translucent || p.sun;
+    p.emit = F.emissive || F.polished || F.translucent || p.sun || p.lamp;
     p.polish = F.polished;
     p.translucent = F.translucent;
     // vrt_set_camera_sampling: the frame's kStepPrimary / kStepSunlitPrimary launches are the kernels of vrt_path_lens.h, which give
@@ -167,7 +171,7 @@ inline PathPlan plan_path(const PathFacts &F) {
     p.cap = (size_t)kPlanHitSegments * p.seg_cap;
     // Bounce launches over the march cells: every later segment of a chain in ONE launch of the pool kernel (vrt_path.hip);
     // worlds without march cells, or with the pool switched off: one lane = path launch per bounce.
-    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells && !p.sun;
+    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells && !p.sun && !p.lamp;
     // the pool's batches of 64 rays per wave: 5 with two frames in flight (the launcher grants them to direct worlds only), else 4
     p.pool_batches = F.path_pool_batches ? F.path_pool_batches : (F.in_flight > 1u ? 5u : 4u);
     p.refill = F.path_refill;
@@ -188,10 +192,12 @@ inline PathPlan plan_path(const PathFacts &F) {
 }
 
 // (the first five trace a segment of the paths — the launches PathStep::launch counts — and come first: traces_paths asks for them;
-// kStepSunlitPrimary / kStepSunlitBounce are a sun-lit frame's, each followed by a kStepSunRays with its launch number)
+// kStepSunlitPrimary / kStepSunlitBounce are a sun-lit frame's, each followed by a kStepSunRays with its launch number;
+// kStepLampPrimary / kStepLampBounce, appended behind the others, are a lamp-lit frame's, sun-lit or not: each is followed by a
+// kStepSunRays, if the frame is sun-lit too, and then by a kStepLampRays)
 enum PathStepKind : uint32_t { kStepPrimary, kStepLaneBounce, kStepCellsBounce, kStepSunlitPrimary, kStepSunlitBounce, kStepSunRays,
-                               kStepChainFinish, kStepResolve, kStepFinalDivide };
-inline bool traces_paths(PathStepKind k) { return k <= kStepSunlitBounce; }
+                               kStepChainFinish, kStepResolve, kStepFinalDivide, kStepLampPrimary, kStepLampBounce, kStepLampRays };
+inline bool traces_paths(PathStepKind k) { return k <= kStepSunlitBounce || k == kStepLampPrimary || k == kStepLampBounce; }
 
 struct PathStep {   // one launch of the frame
     PathStepKind kind;
@@ -219,9 +225,14 @@ void for_each_path_step(const PathPlan &p, F &&f) {
                 b += s.segments - 1u;
             }
             if (p.sun) s.kind = b == 0u ? kStepSunlitPrimary : kStepSunlitBounce;
+            if (p.lamp) s.kind = b == 0u ? kStepLampPrimary : kStepLampBounce;
             f(s);
             if (p.sun) {   // the records that launch appended: cursor set launch & 1 of the sun buffer
                 s.kind = kStepSunRays;
+                f(s);
+            }
+            if (p.lamp) {   // ... and of the lamp buffer
+                s.kind = kStepLampRays;
                 f(s);
             }
         }

@@ -318,7 +318,7 @@ int accum_frame_start(vrt_ctx *c, const vrt_render_opts &o, uint32_t *from) {
 
 // Wavefront path trace: the launches vrt_frame_plan.h's plan_path decided on, enqueued in for_each_path_step's order.
 static_assert(vrt::kPlanHitSegments == vrt::kHitSegments, "the plan sizes the path buffers");
-static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, const vrt::PathPlan &plan, std::array<hipEvent_t, 4> &ev,
+static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f, uint32_t tab, const vrt::PathPlan &plan, std::array<hipEvent_t, 4> &ev,
                              uint8_t &ev_kind) {
     // two sets of three record planes; grows only, and hipFree waits for whatever still uses the old one
     HIP_TRY(c, f.path_buf->grow(6 * plan.cap));
@@ -341,6 +341,24 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         S.seg_cap = plan.seg_cap;
         S.k = c->settings.sun_intensity * c->sun.strength;   // (one binary32 product: the contract's k)
         S.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
+    }
+    vrt::LampLaunch M{};
+    uint32_t *lamp_seg[2] = {nullptr, nullptr};
+    if (plan.lamp) {   // vrt_set_lamp_light: the frame set's lamp list, brought up to date on its stream, and its lamp-ray buffer
+        constexpr size_t kLampSegWords = (size_t)vrt::kHitSegments * vrt::kSegStride;
+        VRT_TRY(lamp_list_for_frame(c, f.slot, tab, f.st, M));
+        HIP_TRY(c, c->sz.lamp_recs[f.slot].grow(3 * plan.cap));
+        HIP_TRY(c, c->sz.lamp_counts[f.slot].once(2 * kLampSegWords));
+        lamp_seg[0] = c->sz.lamp_counts[f.slot];
+        lamp_seg[1] = lamp_seg[0] + kLampSegWords;
+        HIP_TRY(c, hipMemsetAsync(lamp_seg[0], 0, 2 * kLampSegWords * sizeof(uint32_t), f.st));
+        M.recs = c->sz.lamp_recs[f.slot];
+        M.cap = (uint32_t)plan.cap;
+        M.seg_cap = plan.seg_cap;
+        M.strength = c->lamp.strength;
+        M.max_geometry = c->lamp.max_geometry;
+        M.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
+        M.sun = plan.sun ? 1u : 0u;
     }
     // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
     const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance,
@@ -368,7 +386,7 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     bool sum_waited = false, first_marked = false;
     auto enqueue = [&](const vrt::PathStep &s) -> int {
         using namespace vrt;
-        if (s.kind == kStepSunRays) {   // (its trace launch's parameters, and the cursor set that launch appended to)
+        if (s.kind == kStepSunRays || s.kind == kStepLampRays) {   // (its trace launch's parameters, and the cursor set that launch appended to)
         } else if (traces_paths(s.kind)) {   // a launch of the trace
             P.sample = s.sample;
             P.chain = s.chain;
@@ -380,6 +398,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             P.last_bounce = s.last_bounce;
             S.counts = sun_seg[s.launch & 1u];
             S.clear = sun_seg[(s.launch + 1u) & 1u];
+            M.counts = lamp_seg[s.launch & 1u];
+            M.clear = lamp_seg[(s.launch + 1u) & 1u];
         } else if (plan.finish_into_accum && !sum_waited) {
             if (c->accum_ev_recorded) HIP_TRY(c, hipStreamWaitEvent(f.st, c->ev_accum, 0));
             sum_waited = true;
@@ -397,6 +417,9 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
                 break;
             case kStepSunlitBounce: launch_path_bounce_sunlit(P, S, plan.kstats, plan.literal, f.st); break;
             case kStepSunRays: launch_path_sun(P, S, plan.kstats, plan.literal, plan.sun_cells, f.st); break;
+            case kStepLampPrimary: launch_path_primary_lamp(P, L, S, M, plan.lens, plan.kstats, plan.literal, f.st); break;
+            case kStepLampBounce: launch_path_bounce_lamp(P, S, M, plan.kstats, plan.literal, f.st); break;
+            case kStepLampRays: launch_path_lamp_rays(P, M, plan.kstats, plan.literal, f.st); break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -502,6 +525,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     c->mov_any_size = getenv("VRT_TILE_ORDER_MOVING") != nullptr;   // (asked for by name: also for frames larger than kMovingTilesMax)
     if (const char *e = getenv("VRT_TILE_ORDER_RADIUS")) { const int v = atoi(e); if (v >= 1 && v <= 6) c->mov_radius = (uint32_t)v; }
     if (const char *e = getenv("VRT_PATH_POOL")) c->path_pool = e[0] != '0';
+    if (const char *e = getenv("VRT_LAMP_CAP")) { const long v = atol(e); if (v >= 1 && v <= (1l << 24)) c->lamp_cap = (uint32_t)v; }   // (tests: a list that is cut off)
     if (const char *e = getenv("VRT_PATH_CELLS")) c->path_cells = e[0] != '0';
     if (const char *e = getenv("VRT_PATH_POOL_REFILL")) c->path_refill = (uint32_t)atoi(e);
     if (const char *e = getenv("VRT_PATH_POOL_K")) { const int v = atoi(e); if (v == 4 || v == 5) c->path_pool_batches = (uint32_t)v; }
@@ -652,10 +676,14 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     F.compact = c->compact; F.show_step_count = c->settings.show_step_count == 1u; F.air_liquid = c->h_mats[0].is_liquid == 1u;
     if (F.air_liquid && c->compact)
         return fail(c, VRT_ERR_STATE, "vrt_render: materials[0].is_liquid == 1 (air flagged liquid) is traced by the literal march only");
-    if (vrt::asks_for_tables(F)) {
+    // vrt_set_lamp_light: a lamp-lit path frame reads the derived tables for its lamp list, whatever it marches with
+    const bool lamp_lit = o.mode == VRT_MODE_PATH && c->lamp.strength != 0.0f && c->settings.max_ray_bounces > 0u;
+    if (vrt::asks_for_tables(F) || lamp_lit) {
         VRT_PROF(9, "  ensure_accel_world");
         VRT_TRY(ensure_accel_world(c));
     }
+    if (lamp_lit && (!c->accel_ok || c->accel_dirty || c->accel_S != c->world.size_in_chunks))   // (before anything of the frame is enqueued)
+        return fail(c, VRT_ERR_STATE, "vrt_render: a lamp-lit frame (vrt_set_lamp_light) needs the derived tables, which this world does not keep");
     F.accel_ok = c->accel_ok; F.in_flight = c->in_flight; F.tiles_local = c->tiles_local;
     F.caller_stream = c->stream != c->own_stream; F.output_bound = c->d_out != c->sz.own_out; F.present_fusable = presentation_fusable(c);
     const vrt::FramePlan plan = vrt::plan_frame(F);
@@ -682,11 +710,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     const vrt_ctx::Tables &T = c->tabs[tab];
     const bool edit_in_front = !T.dirty_chunks.empty();   // this frame brings an edited chunk's tables up to date first
     // a frame of another frame set that reads the shared set: an edit's update of tabs[0] must wait for it (update_tables)
-    const bool shares = plan.tables && tab == 0u && f.slot != 0u;
+    const bool reads_tables = plan.tables || lamp_lit;
+    const bool shares = reads_tables && tab == 0u && f.slot != 0u;
     {
         VRT_PROF(11, "  frame_waits_for_uploads + update_tables");
         VRT_TRY(frame_waits_for_uploads(c, f.st, f.slot));   // (a frame on c->stream too: the node pool's uploads have their own stream)
-        if (plan.tables) VRT_TRY(update_tables(c, tab, f.st));
+        if (reads_tables) VRT_TRY(update_tables(c, tab, f.st));
     }
     if (shares) {   // the shared set from another frame set's stream: behind its last update
         if (c->tabs[0].update_pending && f.st != c->stream) HIP_TRY(c, hipStreamWaitEvent(f.st, c->tabs[0].ev_updated, 0));
@@ -771,11 +800,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.has_grid = P.grid != nullptr; PF.has_cells = P.mblk != nullptr; PF.march_direct = P.march_direct != 0u;
             PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u; PF.translucent = c->n_translucent != 0u;
             PF.sun = c->sun.strength != 0.0f;
+            PF.lamp = c->lamp.strength != 0.0f;
             PF.camera_sampling = c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
             PF.in_flight = c->in_flight; PF.hit_seg_cap = c->hit_seg_cap;
-            rc = launch_path_frame(c, P, ft, vrt::plan_path(PF), ev, *ev_kind);
+            rc = launch_path_frame(c, P, ft, tab, vrt::plan_path(PF), ev, *ev_kind);
             // (a timed frame's closing event is recorded again behind the filter: vrt_stats and VRT_RENDER_TIMED time it with its passes)
             if (!rc) rc = denoise_after_frame(c, P, plan, f.slot, f.st, f.out, ev[3]);
         }

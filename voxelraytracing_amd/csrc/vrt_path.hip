@@ -109,6 +109,9 @@ __device__ __forceinline__ bool path_segment(const FrameParams &P, const uint32_
 #undef VRT_BOUNCE_TRANSLUCENT
 #undef VRT_BOUNCE_SUN
 
+}  // namespace vrt
+#include "vrt_path_lamp.h"   // (vrt_set_lamp_light: kernels of their own, behind everything they share with the others)
+namespace vrt {
 
 // ------------------------------------------------------------------------------------------------
 // Bounce b >= 1 over the MARCH CELLS (vrt_accel.hip; the default for plain frames of worlds that have them): the pool
@@ -382,6 +385,39 @@ void launch_path_primary_lens_sunlit(const FrameParams &P, const LensLaunch &L, 
     const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
     VRT_PATH_LAUNCH(path_lens_sun_primary_kernel, );
 }
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, L, S, M
+#define VRT_LAMP_PINHOLE , false
+#define VRT_LAMP_SAMPLED , true
+
+// vrt_set_lamp_light (vrt_path_lamp.h): a lamp-lit frame is one lane = path launch per segment, as a sun-lit one; each is followed by
+// the sun launch, if the sun is on as well, and by launch_path_lamp_rays over the lamp records it appended.  sampled: the frame has
+// vrt_set_camera_sampling on (L is read then)
+void launch_path_primary_lamp(const FrameParams &P, const LensLaunch &L, const SunLaunch &S, const LampLaunch &M, bool sampled, bool stats, bool literal,
+                              hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid((P.tiles_local + 3u) / 4u), block(256);
+    if (sampled) VRT_PATH_LAUNCH(path_lamp_primary_kernel, VRT_LAMP_SAMPLED);
+    else VRT_PATH_LAUNCH(path_lamp_primary_kernel, VRT_LAMP_PINHOLE);
+}
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, S, M
+
+void launch_path_bounce_lamp(const FrameParams &P, const SunLaunch &S, const LampLaunch &M, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid(kHitSegments * (P.hit_seg_cap / 256u)), block(256);
+    VRT_PATH_LAUNCH(path_lamp_bounce_kernel, );
+}
+#undef VRT_PATH_ARGS
+#define VRT_PATH_ARGS P, M
+
+void launch_path_lamp_rays(const FrameParams &P, const LampLaunch &M, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid(kHitSegments * (M.seg_cap / 256u)), block(256);
+    VRT_PATH_LAUNCH(path_lamp_rays_kernel, );
+}
+#undef VRT_LAMP_PINHOLE
+#undef VRT_LAMP_SAMPLED
 #undef VRT_PATH_ARGS
 #undef VRT_PATH_LAUNCH
 #undef VRT_PRIMARY_EMIT

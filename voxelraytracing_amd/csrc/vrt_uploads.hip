@@ -375,6 +375,7 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     T.chunk_is_dirty = A.chunk_is_dirty;
     T.update_pending = false;
     T.live = true;
+    T.gen = ++c->tables_gen;
     return VRT_OK;
 }
 
@@ -475,6 +476,7 @@ int ensure_accel_world(vrt_ctx *c) {
         A.chunks_moved = 0;
         A.update_pending = false;
         A.live = true;
+        A.gen = ++c->tables_gen;
         for (uint32_t k = 1; k < vrt_ctx::kMaxInFlight; k++) {   // the other sets in use start over as copies
             if (c->tabs[k].live) {
                 const int rc = copy_tables_from_first(c, k);
@@ -539,6 +541,7 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
                              T.dirty_chunks.data(), extents.data(), roots_now.data(), (uint32_t)T.dirty_chunks.size(), st, T.ev_updated);
     HIP_TRY(c, hipGetLastError());
     T.update_pending = true;
+    T.gen = ++c->tables_gen;
     for (uint32_t ch : T.dirty_chunks) {
         if (!T.chunk_may_have_moved[ch]) { T.chunk_may_have_moved[ch] = 1; T.chunks_moved += 1; }
         T.chunk_is_dirty[ch] = 0;

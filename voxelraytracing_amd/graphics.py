@@ -210,6 +210,29 @@ class Gpu:
         o = _ffi.CameraSampling(pixel_spread, aperture, focus_distance, 0)
         self._ck(self._lib.vrt_set_camera_sampling(self._h, C.byref(o)))
 
+    def set_lamp_light(self, strength: float, max_geometry: float = 0.0):
+        """vrt_set_lamp_light: every hit of a later MODE_PATH frame sends a ray to a point of a face of the world's lamp list —
+        the emissive voxels' faces that look at air or a liquid, derived on the GPU — and, where it arrives, adds that lamp's
+        light (0 = off, the default; 1 = what a diffuse bounce would have found by chance).  max_geometry clamps the geometry
+        factor (0 = no clamp).  The primary modes ignore it; changing it restarts the accumulation."""
+        o = _ffi.LampLight(strength, max_geometry, 0, 0)
+        self._ck(self._lib.vrt_set_lamp_light(self._h, C.byref(o)))
+
+    def lamp_info(self) -> dict:
+        """vrt_get_lamp_info: of the list the last lamp-lit frame used — listed, cap, faces, builds, last_build_ms."""
+        o = _ffi.LampInfo()
+        self._ck(self._lib.vrt_get_lamp_info(self._h, C.byref(o)))
+        return {"listed": o.listed, "cap": o.cap, "faces": o.faces, "builds": o.builds, "last_build_ms": o.last_build_ms}
+
+    def read_lamps(self) -> np.ndarray:
+        """vrt_read_lamps: the lamp list the last lamp-lit frame used, as records of _ffi.LAMP_DTYPE in list order."""
+        n = C.c_uint32(0)
+        self._ck(self._lib.vrt_read_lamps(self._h, None, 0, C.byref(n)))
+        a = np.zeros(n.value, dtype=_ffi.LAMP_DTYPE)
+        if n.value:
+            self._ck(self._lib.vrt_read_lamps(self._h, a.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return a
+
     def synchronize(self):
         self._ck(self._lib.vrt_synchronize(self._h))
 
