@@ -24,7 +24,8 @@ typedef struct {   /* include/vrt.h: vrt_lamp */
 } ref_lamp;
 
 /* steps: the lookups of every march; bounce segments: the segments behind the primary ones; sun rays and lamp rays marched; the
- * lamp rays that arrived; hits whose emission term was dropped because the path was no longer direct */
+ * lamp rays that arrived; hits whose emission term was dropped because the path was no longer direct.  Beside them, where the
+ * caller asks: per list entry, the lamp rays that arrived at it */
 enum { LAMP_STEPS, LAMP_BOUNCE_SEGMENTS, LAMP_SUN_RAYS, LAMP_RAYS, LAMP_UNOCCLUDED, LAMP_EMISSION_DROPPED, LAMP_COUNTS };
 
 /* the voxel id of every unit voxel of the world, dense[z][y][x], by the oracle's own walk */
@@ -44,7 +45,8 @@ static float comp(v3 v, uint32_t a) { return a == 0u ? v.x : (a == 1u ? v.y : v.
 /* one sample: its light; *id: the id word of ITS primary segment */
 static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const float *emission, const ref_polish *polish,
                           const ref_translucency *tr, int polished_frame, int translucent_frame, float sun_strength, const ref_camera_sampling *cs,
-                          const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n) {
+                          const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n,
+                          uint32_t *arrived) {
     v3 light = V3(0.0f, 0.0f, 0.0f);
     v3 origin, dir;
     if (cs->pixel_spread != 0.0f || cs->aperture != 0.0f) {
@@ -137,6 +139,10 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
                     if (L->face == 2u) { lc.x *= 0.2f; lc.y *= 0.2f; lc.z *= 0.2f; }
                     if (unoccluded) {
                         n[LAMP_UNOCCLUDED] += 1u;
+                        if (arrived) {
+#pragma omp atomic
+                            arrived[j] += 1u;
+                        }
                         light.x += ((rs.color.x * lc.x) * w) * thr.x;
                         light.y += ((rs.color.y * lc.y) * w) * thr.y;
                         light.z += ((rs.color.z * lc.z) * w) * thr.z;
@@ -172,10 +178,12 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
     return light;
 }
 
-/* lens_ref.c's ref_render_path_lens with the lamp setting and the lamp list; counts[LAMP_COUNTS] as the enum says */
-void ref_render_path_lamp(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
-                          const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t w, uint32_t h, uint32_t spp,
-                          uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids, uint64_t *counts) {
+/* lens_ref.c's ref_render_path_lens with the lamp setting and the lamp list; counts[LAMP_COUNTS] as the enum says.  arrived: NULL, or
+ * N words that the frame adds to: per list entry, the lamp rays that arrived at it unoccluded (their sum grows by counts[LAMP_UNOCCLUDED]) */
+void ref_render_path_lamp_arrivals(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr,
+                                   float sun_strength, const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N,
+                                   uint32_t w, uint32_t h, uint32_t spp, uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids,
+                                   uint64_t *counts, uint32_t *arrived) {
     const uint32_t x1 = w & ~7u, y1 = h & ~7u, nspp = spp ? spp : 1u;
     const int on = cs->pixel_spread != 0.0f || cs->aperture != 0.0f;
     int polished_frame, translucent_frame;
@@ -200,7 +208,7 @@ void ref_render_path_lamp(const orc_scene *scene, const float *emission, const r
                 uint32_t sid = 0;
                 uint64_t n[LAMP_COUNTS] = {0, 0, 0, 0, 0, 0};
                 v3 l = trace_path_lamp(scene, &no_disc, emission, polish, tr, polished_frame, translucent_frame, sun_strength, cs, ll, list, N, px,
-                                       (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n);
+                                       (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, arrived);
                 sum.x += l.x; sum.y += l.y; sum.z += l.z;
                 n0 += n[0]; n1 += n[1]; n2 += n[2]; n3 += n[3]; n4 += n[4]; n5 += n[5];
                 if (!on && sm == 0) id = sid;
@@ -214,6 +222,12 @@ void ref_render_path_lamp(const orc_scene *scene, const float *emission, const r
     counts[0] = n0; counts[1] = n1; counts[2] = n2; counts[3] = n3; counts[4] = n4; counts[5] = n5;
 }
 
+void ref_render_path_lamp(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
+                          const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t w, uint32_t h, uint32_t spp,
+                          uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids, uint64_t *counts) {
+    ref_render_path_lamp_arrivals(scene, emission, polish, tr, sun_strength, cs, ll, list, N, w, h, spp, seed, sample_base, rgb, ids, counts, NULL);
+}
+
 /* one pixel's one sample: its light and its counts */
 void ref_trace_pixel_lamp(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
                           const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t w, uint32_t h, uint32_t px,
@@ -225,6 +239,6 @@ void ref_trace_pixel_lamp(const orc_scene *scene, const float *emission, const r
     uint32_t id = 0;
     for (int i = 0; i < LAMP_COUNTS; i++) counts[i] = 0;
     const v3 l = trace_path_lamp(scene, &no_disc, emission, polish, tr, polished_frame, translucent_frame, sun_strength, cs, ll, list, N, px, py,
-                                 path_seed(px, py, w, h, sample, seed), &id, counts);
+                                 path_seed(px, py, w, h, sample, seed), &id, counts, NULL);
     light[0] = l.x; light[1] = l.y; light[2] = l.z;
 }

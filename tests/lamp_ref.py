@@ -81,6 +81,8 @@ class LampRef:
         L.ref_render_path_lamp.restype = None
         L.ref_render_path_lamp.argtypes = [C.POINTER(orc.Scene), C.POINTER(f32), C.c_void_p, C.c_void_p, f32, C.POINTER(CameraSampling),
                                            C.POINTER(LampLight), C.c_void_p, u32, u32, u32, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ref_render_path_lamp_arrivals.restype = None
+        L.ref_render_path_lamp_arrivals.argtypes = L.ref_render_path_lamp.argtypes + [C.c_void_p]
         L.ref_trace_pixel_lamp.restype = None
         L.ref_trace_pixel_lamp.argtypes = [C.POINTER(orc.Scene), C.POINTER(f32), C.c_void_p, C.c_void_p, f32, C.POINTER(CameraSampling),
                                            C.POINTER(LampLight), C.c_void_p, u32, u32, u32, u32, u32, u32, u32, C.c_void_p, C.c_void_p]
@@ -102,10 +104,11 @@ class LampRef:
         return lamp_list(self.dense_world(scene), scene.roots, _tables(emission, None, None)[0], liquid_set(scene.mats))
 
     def render(self, scene: "orc.OracleScene", lamp, lamps, w: int, h: int, spp: int = 1, seed: int = 0, sample_base: int = 0, sun: float = 0.0,
-               setting=OFF, emission=None, polish=None, translucency=None):
+               setting=OFF, emission=None, polish=None, translucency=None, arrived=None):
         """(rgb [h, w, 3] f32, ids [h, w] u32) of samples sample_base .. sample_base + spp - 1.  lamp = (strength, max_geometry);
         lamps: the list (LAMP_DTYPE records, already cut to the cap); sun: vrt_set_sun_light's strength; setting: the camera
-        sampling; the three 256-entry tables (None = zeros)."""
+        sampling; the three 256-entry tables (None = zeros).  arrived: None, or a contiguous uint32 array of len(lamps) that
+        the frame adds to: per list entry, the lamp rays that arrived at it unoccluded."""
         e, p, t = _tables(emission, polish, translucency)
         rgb = np.zeros((h, w, 3), dtype=np.float32)
         ids = np.zeros((h, w), dtype=np.uint32)
@@ -113,9 +116,12 @@ class LampRef:
         cs = CameraSampling(float(setting[0]), float(setting[1]), float(setting[2]), 0)
         ll = LampLight(float(lamp[0]), float(lamp[1]), 0, 0)
         lamps = np.ascontiguousarray(lamps, LAMP_DTYPE)
-        self._lib.ref_render_path_lamp(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, sun, C.byref(cs),
-                                       C.byref(ll), lamps.ctypes.data, lamps.size, w, h, spp, seed, sample_base, rgb.ctypes.data, ids.ctypes.data,
-                                       n.ctypes.data)
+        if arrived is not None:
+            assert arrived.dtype == np.uint32 and arrived.shape == (lamps.size,) and arrived.flags.c_contiguous and arrived.flags.writeable
+        self._lib.ref_render_path_lamp_arrivals(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, sun,
+                                                C.byref(cs), C.byref(ll), lamps.ctypes.data, lamps.size, w, h, spp, seed, sample_base,
+                                                rgb.ctypes.data, ids.ctypes.data, n.ctypes.data,
+                                                arrived.ctypes.data if arrived is not None and arrived.size else None)
         self.counts = Counts(*(int(x) for x in n))
         return rgb, ids
 

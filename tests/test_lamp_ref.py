@@ -1,7 +1,11 @@
 """tests/lamp_ref.c and tests/lamp_ref.py, the tests' reference for lamp light in the path trace (vrt_set_lamp_light), without a
 GPU: with strength 0 it is tests/lens_ref.c bit for bit; a frame's pixel is its samples' lights in sample order; the lamp list
 of hand-made worlds is what the contract says, face by face; and the definition is an estimator of what it replaces — in a
-sealed, diffuse room the lamp-lit frame at B bounces agrees with the plain frame at B + 1, and does not at strength pi."""
+sealed, diffuse room the lamp-lit frame at B bounces agrees with the plain frame at B + 1, and does not at strength pi.
+
+And the preconditions of tests/test_gpu_lamp_list.py, from the reference alone: lamp_cases' scan worlds put faces into the
+workgroups of the list build that its scan has a path for, the random worlds hold what they are meant to, and lamp rays arrive
+at every kind of lamp of the hand-made world in the frames that test holds to the reference."""
 import numpy as np
 import pytest
 
@@ -166,3 +170,104 @@ def test_the_lamp_term_estimates_what_the_next_segment_would_have_found(lref, or
           f"strength pi {too_bright.mean():.6f} +- {se(too_bright):.2g}: {apart_pi:.1f}")
     assert apart <= 4.0
     assert apart_pi > 4.0
+
+
+# ---- the preconditions of tests/test_gpu_lamp_list.py ----
+
+@pytest.mark.parametrize("S", [9, 11])
+def test_the_scan_worlds_put_faces_where_the_scan_has_a_path(lref, orc, S):
+    """The list build's scan (lamp_scan_kernel) gives each of 1024 threads per = ceil(n_blocks / 1024) workgroup sums."""
+    world = LC.scan_world(S)
+    assert world.min_voxel() == (0, 0, 0) and world.size_in_chunks() == S
+    roots = world.chunk_roots()
+    assert int((np.asarray(roots) != 0).sum()) == len(LC.scan_blocks(S)) == 7
+    lamps = lref.lamps(orc.from_package_scene(LC.scan_scene(world, S)), LC.emission(lamp=2.0, ore=1.0))
+    n_blocks = (8 * S) ** 3 // 256
+    per = (n_blocks + 1023) // 1024
+    assert (n_blocks, per) == {9: (1458, 2), 11: (2662, 3)}[S]
+    b, base, count = LC.workgroups(lamps, S)
+    print(f"S = {S}: {len(lamps)} faces in {len(b)} workgroups of {n_blocks}, per = {per}: {b.tolist()}")
+    have = set(b.tolist())
+    assert 0 in have
+    # the last workgroup, from a lamp in the world's last cell whose +x, +y and +z faces look out of the world box
+    assert n_blocks - 1 in have
+    last = lamps[-1]
+    assert tuple(int(v) for v in last["pos"]) == (32 * S - 1,) * 3 and int(last["face"]) == 5
+    assert sorted(int(f) for f in lamps[lamps["pos"].astype(np.int64).min(1) == 32 * S - 1]["face"]) == [0, 1, 2, 3, 4, 5]
+    # a scan thread's serial running base: two workgroups of one thread, the second with a non-zero sum in front of it
+    assert any(x != y and x // per == y // per for x in have for y in have)
+    # neighbours that belong to different threads
+    assert any(x + 1 in have and x // per != (x + 1) // per for x in have)
+    # long runs of empty workgroups
+    assert np.diff(b).max() >= 256
+    if S == 11:   # thread 887 owns workgroup 2661 alone (its range is clipped), the 136 threads behind it nothing
+        assert (n_blocks - 1) // per == 887 and 888 * per >= n_blocks and 887 * per == n_blocks - 1
+    if S == 9:    # 729 threads exactly full
+        assert n_blocks == 729 * per
+    assert 0 < len(lamps) < 1 << 20
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_the_random_worlds_hold_what_they_are_meant_to(lref, orc, seed):
+    S = 3
+    world = LC.random_world(seed, S)
+    assert world.min_voxel() == (0, 0, 0)
+    o = orc.from_package_scene(LC.random_scene(world, S))
+    assert int((np.asarray(o.roots) == 0).sum()) == 3
+    dense = lref.dense_world(o)
+    lamps = lref.lamps(o, LC.emission_big(lamp=2.0, ore=1.0))
+    assert 0 < len(lamps) < 1 << 20
+    p = lamps["pos"].astype(np.int64)
+    G = 8 * S
+    cell = ((p[:, 2] >> 2) * G + (p[:, 1] >> 2)) * G + (p[:, 0] >> 2)
+    # an id above 255 is listed as it is — from a cell that is one leaf of it (the entry's e >> 16) and from a split cell (a brick's u16 >> 1)
+    big = lamps["voxel"] == LC.BIG
+    assert big.any() and set(np.unique(lamps["voxel"]).tolist()) == {LC.LAMP, LC.ORE, LC.BIG}
+    cells = dense.reshape(G, 4, G, 4, G, 4).transpose(0, 2, 4, 1, 3, 5).reshape(G ** 3, 64)
+    whole = (cells == LC.BIG).all(1)
+    assert whole[cell[big]].any() and (~whole[cell[big]]).any()
+    # a checkerboard cell: 32 lamps with every face listed
+    per_cell = np.bincount(cell)
+    assert per_cell.max() >= 150
+    # lamps next to lamps: a lamp voxel with fewer than six faces, one of them because its neighbour is a lamp
+    voxel = (p[:, 2] * (32 * S) + p[:, 1]) * (32 * S) + p[:, 0]
+    lamp_voxels, faces = np.unique(voxel[lamps["voxel"] == LC.LAMP], return_counts=True)
+    assert (faces < 6).any()
+    few = lamp_voxels[faces < 6]
+    z, y, x = few // (32 * S) ** 2, (few // (32 * S)) % (32 * S), few % (32 * S)
+    n = 32 * S
+    assert any(bool((dense[np.clip(z + dz, 0, n - 1), np.clip(y + dy, 0, n - 1), np.clip(x + dx, 0, n - 1)] == LC.LAMP).any())
+               for dz, dy, dx in ((0, 0, 1), (0, 0, -1), (0, 1, 0), (0, -1, 0), (1, 0, 0), (-1, 0, 0)))
+    print(f"seed {seed}: {len(lamps)} faces, {int(big.sum())} of id {LC.BIG}, at most {int(per_cell.max())} in a cell, "
+          f"{int((faces < 6).sum())} of {len(lamp_voxels)} lamp voxels with fewer than six")
+
+
+def test_lamp_rays_arrive_at_every_kind_of_lamp_of_the_hand_made_world(lref, orc):
+    """Over the frames tests/test_gpu_lamp_list.py holds to the reference — lamp_cases.EDGE_CAMERAS, EDGE_SIZES, EDGE_SPPS, 2
+    bounces — at least one lamp ray arrives unoccluded at an entry of each kind (the reference's per-entry count).  The lamp under
+    water is enclosed by water on all six sides: a ray that arrives there went through a liquid."""
+    world = LC.hand_made_world()
+    e = LC.emission(lamp=2.0, ore=1.0)
+    kinds = LC.hand_made_kinds()
+    total = {k: 0 for k in kinds}
+    for eye, rot in LC.EDGE_CAMERAS:
+        for size in LC.EDGE_SIZES:
+            sc = LC.hand_made_scene(world, size=size, eye=eye, rot=rot)
+            o = orc.from_package_scene(sc)
+            lamps = lref.lamps(o, e)
+            pos = lamps["pos"].astype(np.int64)
+            for spp in LC.EDGE_SPPS:
+                arrived = np.zeros(len(lamps), np.uint32)
+                plain = lref.render(o, (1.0, 0.01), lamps, *size, spp=spp, seed=SEED, emission=e)
+                plain_counts = lref.counts
+                got = lref.render(o, (1.0, 0.01), lamps, *size, spp=spp, seed=SEED, emission=e, arrived=arrived)
+                assert np.array_equal(_bits(got[0]), _bits(plain[0])) and np.array_equal(got[1], plain[1]) and lref.counts == plain_counts
+                assert int(arrived.sum()) == lref.counts.unoccluded
+                for k, test in kinds.items():
+                    total[k] += int(arrived[test(pos)].sum())
+    print(total)
+    for k, n in total.items():
+        assert n >= 1, k
+    dense = lref.dense_world(orc.from_package_scene(LC.hand_made_scene(world)))
+    assert dense[12, 20, 12] == LC.LAMP   # [z, y, x]
+    assert all(dense[12 + dz, 20 + dy, 12 + dx] == LC.WATER for dz, dy, dx in ((0, 0, 1), (0, 0, -1), (0, 1, 0), (0, -1, 0), (1, 0, 0), (-1, 0, 0)))

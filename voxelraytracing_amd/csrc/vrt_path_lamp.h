@@ -44,7 +44,7 @@ __device__ __forceinline__ LampRay lamp_ray_of_hit(const FrameParams &P, const L
     r.so = V3{R.pos.x + R.norm.x * kShadowBias, R.pos.y + R.norm.y * kShadowBias, R.pos.z + R.norm.z * kShadowBias};
     uint4 L = make_uint4(0u, 0u, 0u, 0u);
     if (solid) {
-        const uint32_t j = min((uint32_t)(u1 * (float)n), n - 1u);   // (u1 <= 1, n <= 2^20: in range)
+        const uint32_t j = min((uint32_t)(u1 * (float)n), n - 1u);   // (u1 <= 1, n <= 2^24, VRT_LAMP_CAP's most: in range)
         L = M.list[j];
     }
     const uint32_t px = L.x & 0xFFFFu, py = L.x >> 16, pz = L.y & 0xFFFFu, voxel = L.y >> 16, face = L.z;
