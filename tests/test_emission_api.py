@@ -6,6 +6,7 @@ import os
 import re
 
 from voxelraytracing_amd import _ffi, graphics
+from kernel_families import in_family, path_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -48,10 +49,12 @@ def test_the_emissive_kernels_are_built_apart_from_the_plain_ones():
     """The emission term lives in instantiations of their own: the plain frame's kernels keep their code (tools/isa_diff.py
     compares two builds), and none of the new ones spills."""
     regs = _ffi.kernel_registers()
-    emissive_cells = {k: v for k, v in regs.items() if "path_emissive_cells_kernel" in k}
+    emissive_cells = {k: v for k, v in regs.items() if in_family(k, "emissive")}
     assert len(emissive_cells) == 3 and all(v["vgprs"] <= 64 for v in emissive_cells.values()), emissive_cells
     # <MARCH, LDS_ROOTS, STATS, (MULTI,) EMIT = true>: the ten march forms each, + the primary's chained one
-    assert sum(1 for k in regs if re.search(r"path_primary_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 11
-    assert sum(1 for k in regs if re.search(r"path_bounce_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 10
-    bad = {k: v for k, v in regs.items() if "emissive" in k and (v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"])}
+    kernels = {k: path_kernel(k) for k in regs}
+    emit_alone = {k: p for k, p in kernels.items() if p and p["emit"] and not (p["polish"] or p["translucent"] or p["sun"])}
+    assert sum(1 for k, p in emit_alone.items() if p["template"] == "primary" and k.endswith("EvNS_11FrameParamsEDpT6_")) == 11
+    assert sum(1 for k, p in emit_alone.items() if p["template"] == "bounce" and k.endswith("EvNS_11FrameParamsEDpT5_")) == 10
+    bad = {k: v for k, v in regs.items() if in_family(k, "emissive") and (v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"])}
     assert not bad

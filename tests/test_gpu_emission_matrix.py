@@ -2,7 +2,7 @@
 count, every route and switch of the bounce launch, mirrors and mixed scatter, rays that run out of lookups, lone waves and the
 edges of the table.  The cases are tests/emission_cases.py's; tests/test_emission_cases.py counts on the CPU what each holds.
 
-Which instantiation a test runs (the host's choice, vrt_path.hip launch_path_bounce_cells): path_emissive_cells_kernel<true, 4>
+Which instantiation a test runs (the host's choice, vrt_path.hip launch_path_bounce_cells): path_bounce_cells_kernel<true, 4, EMIT>
 with one frame in flight on a direct world, <true, 5> with two (or VRT_PATH_POOL_K=5), <false, 4> on a world with a chunk directory
 (VRT_MARCH_DIRECT_MAX_S=0, C5's 32^3 chunks); path_bounce_kernel<EMIT> for VRT_PATH_POOL=0 / VRT_PATH_CELLS=0, stats frames and
 the literal march; path_primary_kernel<EMIT> always.  Every context that has march cells asserts

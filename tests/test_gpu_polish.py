@@ -6,9 +6,9 @@ a table without a chance renders exactly as no table; accumulated polished frame
 bit; what restarts the sum and what is refused; the primary modes; shards and devices.  Frames against the reference:
 util.assert_frame_parity (id words equal, radiance within RADIANCE_TOL); GPU against GPU: bit for bit.
 
-Which instantiation a test runs (the host's choice, vrt_path.hip): path_polished_cells_kernel<true, 4> with one frame in flight
+Which instantiation a test runs (the host's choice, vrt_path.hip): path_bounce_cells_kernel<true, 4, EMIT, POLISH> with one frame in flight
 on a direct world, <true, 5> with two, <false, 4> on a world with a chunk directory (VRT_MARCH_DIRECT_MAX_S=0);
-path_polished_bounce_kernel for VRT_PATH_POOL=0, stats frames and the literal march; path_polished_primary_kernel always (its
+path_bounce_kernel<.., EMIT, POLISH> for VRT_PATH_POOL=0, stats frames and the literal march; path_primary_kernel<.., EMIT, POLISH> always (its
 chained form where a frame of several samples has more than one per chain)."""
 import numpy as np
 import pytest

@@ -10,9 +10,9 @@ GPU: bit for bit.
 Two sets of tables, both chosen from the context's own 1-spp frame: "alone" is the translucency table with nothing else (the
 translucent kernels with the coat word 0: no coat's draw), "all" adds a coat and an emitter (the coat word 1).
 
-Which instantiation a test runs (the host's choice, vrt_path.hip): path_translucent_cells_kernel<true, 4> with one frame in
+Which instantiation a test runs (the host's choice, vrt_path.hip): path_bounce_cells_kernel<true, 4, EMIT, false, TRANSLUCENT> with one frame in
 flight on a direct world, <true, 5> with two, <false, 4> on a world with a chunk directory (VRT_MARCH_DIRECT_MAX_S=0);
-path_translucent_bounce_kernel for VRT_PATH_POOL=0, stats frames and the literal march; path_translucent_primary_kernel always
+path_bounce_kernel<.., EMIT, false, TRANSLUCENT> for VRT_PATH_POOL=0, stats frames and the literal march; path_primary_kernel<.., EMIT, false, TRANSLUCENT> always
 (its chained form where a frame of several samples has more than one per chain).
 
 That a table without a chance runs the kernels that ran before is the plan's doing (PathFacts::translucent is false while no

@@ -10,6 +10,7 @@ import re
 import subprocess
 
 from voxelraytracing_amd import _ffi, graphics
+from kernel_families import in_family, path_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -69,20 +70,22 @@ def test_rust_binding():
 
 
 def test_the_lens_kernels_are_built_apart_from_the_others():
-    """Camera sampling lives in primary kernels with names of their own, which take a LensLaunch behind FrameParams (and a
-    SunLaunch behind that in their sun-lit form): every other kernel keeps its name and its code (profiles/lens_isa_diff.txt).
+    """Camera sampling lives in a primary kernel template of its own, path_lens_primary_kernel, which takes a LensLaunch behind
+    FrameParams (and a SunLaunch behind that in its sun-lit form): every other kernel keeps its code (profiles/lens_isa_diff.txt).
     The ten march forms each and the one form of several samples per chain; whether there is a coat or a pass-through draw is
     read from the launch, not a family per combination.  Nothing spills: their sample loop reads its arguments anew per trip
     (vrt_path_lens.h) — read once in front of the loop they cost up to 43 spilled scalar registers."""
     regs = _ffi.kernel_registers()
-    lens = {k: v for k, v in regs.items() if "lens" in k}
-    plain = [k for k in lens if re.search(r"path_lens_primary_kernelI.*FrameParamsENS_10LensLaunchE$", k)]
-    sunlit = [k for k in lens if re.search(r"path_lens_sun_primary_kernelI.*FrameParamsENS_10LensLaunchENS_9SunLaunchE$", k)]
-    assert len(plain) == 11 and sum(1 for k in plain if "ILi0ELb0ELb0ELb1EE" in k) == 1   # (+ several samples per chain)
+    lens = {k: v for k, v in regs.items() if in_family(k, "lens")}
+    plain = [k for k in lens if not path_kernel(k)["sun"] and re.search(r"FrameParamsENS_10LensLaunchEDpT", k)]
+    sunlit = [k for k in lens if path_kernel(k)["sun"] and re.search(r"FrameParamsENS_10LensLaunchEDpT", k)]
+    chained = [k for k in plain if path_kernel(k)["multi"] and path_kernel(k)["build"] == "Li0ELb0ELb0E"]
+    assert len(plain) == 11 and len(chained) == 1 and sum(1 for k in plain if path_kernel(k)["multi"]) == 1   # (+ several samples per chain)
+    assert not [k for k in sunlit if path_kernel(k)["multi"]]
     assert len(sunlit) == 10
     assert len(lens) == 21
     bad = {k: v for k, v in lens.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
     assert not bad, bad
     # the other families are what tests/test_sun_api.py records
-    assert sum(1 for k in regs if "sunlit" in k or "path_sun_" in k) == 32
-    assert sum(1 for k in regs if "translucent" in k) == 24 and sum(1 for k in regs if "polished" in k) == 24
+    assert sum(1 for k in regs if in_family(k, "sunlit") or "path_sun_" in k) == 32
+    assert sum(1 for k in regs if in_family(k, "translucent")) == 24 and sum(1 for k in regs if in_family(k, "polished")) == 24

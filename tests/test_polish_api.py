@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 
 from voxelraytracing_amd import _ffi, graphics
+from kernel_families import in_family, path_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -69,17 +70,17 @@ def test_rust_binding():
 
 
 def test_the_polished_kernels_are_built_apart_from_the_others():
-    """The coat's coin lives in kernels with names of their own: the plain and the emissive kernels keep their names and their
-    code (tools/isa_diff.py compares two builds).  The pool kernel's polished form has the emissive one's three instantiations
+    """The coat's coin lives in instantiations of their own (POLISH of the three templates, tests/kernel_families.py): the plain
+    and the emissive kernels keep their code (tools/isa_diff.py compares two builds).  The pool kernel's polished form has the emissive one's three instantiations
     and no more registers than it (64: eight waves a SIMD), and none of the new kernels spills."""
     regs = _ffi.kernel_registers()
-    cells = {k: v for k, v in regs.items() if "path_polished_cells_kernel" in k}
+    polished = {k: v for k, v in regs.items() if in_family(k, "polished")}
+    cells = {k: v for k, v in polished.items() if path_kernel(k)["template"] == "bounce_cells"}
     assert len(cells) == 3 and all(v["vgprs"] <= 64 for v in cells.values()), cells
-    assert sorted(re.search(r"kernelI(Lb\dELj\dE)E", k).group(1) for k in cells) == ["Lb0ELj4E", "Lb1ELj4E", "Lb1ELj5E"]
+    assert sorted(path_kernel(k)["build"] for k in cells) == ["Lb0ELj4E", "Lb1ELj4E", "Lb1ELj5E"]
     # <MARCH, LDS_ROOTS, STATS, (MULTI,) EMIT = true>: the ten march forms each, + the primary's chained one
-    assert sum(1 for k in regs if re.search(r"path_polished_primary_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 11
-    assert sum(1 for k in regs if re.search(r"path_polished_bounce_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 10
-    polished = {k: v for k, v in regs.items() if "polished" in k}
+    assert sum(1 for k in polished if path_kernel(k)["template"] == "primary" and path_kernel(k)["emit"] and k.endswith("EvNS_11FrameParamsEDpT6_")) == 11
+    assert sum(1 for k in polished if path_kernel(k)["template"] == "bounce" and path_kernel(k)["emit"] and k.endswith("EvNS_11FrameParamsEDpT5_")) == 10
     assert len(polished) == 24
     bad = {k: v for k, v in polished.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
     assert not bad

@@ -9,6 +9,7 @@ import re
 import subprocess
 
 from voxelraytracing_amd import _ffi, graphics
+from kernel_families import in_family, path_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,18 +62,18 @@ def test_rust_binding():
 
 
 def test_the_sun_lit_kernels_are_built_apart_from_the_others():
-    """The sun term lives in kernels with names of their own, which take a SunLaunch behind FrameParams: every other kernel keeps
-    its name and its code (profiles/sun_isa_diff.txt).  One pair of trace kernels — the ten march forms each, whether there is a
+    """The sun term lives in instantiations of their own (SUN = SunLaunch of the two trace templates, tests/kernel_families.py),
+    which take a SunLaunch behind FrameParams: every other kernel keeps its code (profiles/sun_isa_diff.txt).  One pair of trace kernels — the ten march forms each, whether there is a
     coat or a pass-through draw read from the launch, not a family per combination — the sun launch over the march cells in
     both layouts, and the ten march forms of the sun launch that counts; nothing spills."""
     regs = _ffi.kernel_registers()
-    sun = {k: v for k, v in regs.items() if "sunlit" in k or "path_sun_" in k}
-    assert sum(1 for k in sun if re.search(r"path_sunlit_primary_kernelI.*FrameParamsENS_9SunLaunchE$", k)) == 10
-    assert sum(1 for k in sun if re.search(r"path_sunlit_bounce_kernelI.*FrameParamsENS_9SunLaunchE$", k)) == 10
+    sun = {k: v for k, v in regs.items() if in_family(k, "sunlit") or "path_sun_" in k}
+    assert sum(1 for k in sun if in_family(k, "sunlit") and path_kernel(k)["template"] == "primary" and k.endswith("EvNS_11FrameParamsEDpT6_")) == 10
+    assert sum(1 for k in sun if in_family(k, "sunlit") and path_kernel(k)["template"] == "bounce" and k.endswith("EvNS_11FrameParamsEDpT5_")) == 10
     assert sorted(re.search(r"path_sun_cells_kernelI(Lb\d)E", k).group(1) for k in sun if "path_sun_cells_kernel" in k) == ["Lb0", "Lb1"]
     assert sum(1 for k in sun if "path_sun_kernel" in k) == 10
     assert len(sun) == 32
     bad = {k: v for k, v in sun.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
     assert not bad, bad
     # the other families are what they were
-    assert sum(1 for k in regs if "translucent" in k) == 24 and sum(1 for k in regs if "polished" in k) == 24
+    assert sum(1 for k in regs if in_family(k, "translucent")) == 24 and sum(1 for k in regs if in_family(k, "polished")) == 24

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 
 from voxelraytracing_amd import _ffi, graphics
+from kernel_families import in_family, path_kernel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -68,19 +69,19 @@ def test_rust_binding():
 
 
 def test_the_translucent_kernels_are_built_apart_from_the_others():
-    """The draw lives in kernels with names of their own: every other kernel keeps its name and its code (tools/isa_diff.py
-    compares two builds).  The family has the polished one's instantiations and no others — the coat's draw is under a word on
+    """The draw lives in instantiations of their own (TRANSLUCENT of the three templates, tests/kernel_families.py): every other
+    kernel keeps its code (tools/isa_diff.py compares two builds).  The family has the polished one's instantiations and no others — the coat's draw is under a word on
     the device, not a template argument; its pool kernel stays at 64 VGPRs (eight waves a SIMD), and nothing spills."""
     regs = _ffi.kernel_registers()
-    cells = {k: v for k, v in regs.items() if "path_translucent_cells_kernel" in k}
+    translucent = {k: v for k, v in regs.items() if in_family(k, "translucent")}
+    cells = {k: v for k, v in translucent.items() if path_kernel(k)["template"] == "bounce_cells"}
     assert len(cells) == 3 and all(v["vgprs"] <= 64 for v in cells.values()), cells
-    assert sorted(re.search(r"kernelI(Lb\dELj\dE)E", k).group(1) for k in cells) == ["Lb0ELj4E", "Lb1ELj4E", "Lb1ELj5E"]
+    assert sorted(path_kernel(k)["build"] for k in cells) == ["Lb0ELj4E", "Lb1ELj4E", "Lb1ELj5E"]
     # <MARCH, LDS_ROOTS, STATS, (MULTI,) EMIT = true>: the ten march forms each, + the primary's chained one
-    assert sum(1 for k in regs if re.search(r"path_translucent_primary_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 11
-    assert sum(1 for k in regs if re.search(r"path_translucent_bounce_kernelI.*Lb1EEEvNS_11FrameParamsE$", k)) == 10
-    translucent = {k: v for k, v in regs.items() if "translucent" in k}
+    assert sum(1 for k in translucent if path_kernel(k)["template"] == "primary" and path_kernel(k)["emit"] and k.endswith("EvNS_11FrameParamsEDpT6_")) == 11
+    assert sum(1 for k in translucent if path_kernel(k)["template"] == "bounce" and path_kernel(k)["emit"] and k.endswith("EvNS_11FrameParamsEDpT5_")) == 10
     assert len(translucent) == 24
     bad = {k: v for k, v in translucent.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
     assert not bad
     # the polished family is what it was
-    assert sum(1 for k in regs if "polished" in k) == 24
+    assert sum(1 for k in regs if in_family(k, "polished")) == 24

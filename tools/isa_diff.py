@@ -1,9 +1,9 @@
 """tools/isa_diff.py — the gfx950 instruction streams of two builds of libvrt.so, kernel by kernel (no GPU).
 
-    python tools/isa_diff.py OLD.so NEW.so [--rename NEW_REGEX=OLD_REPL ...]
+    python tools/isa_diff.py OLD.so NEW.so [--rename NEW_REGEX=OLD_REPL ...] [--rename-file FILE]
 
 Every kernel of OLD is looked up in NEW (after the --rename substitutions, applied to NEW's symbol names: a template argument
-that a later build added with its old value as the default) and their bodies are compared instruction for instruction, with
+that a later build added with its old value as the default; --rename-file: one REGEX=REPL per line, # comments) and their bodies are compared instruction for instruction, with
 what legitimately differs between two links left out: addresses, raw encodings, comments, symbolic branch labels.  Prints
 one line per kernel that differs or is missing and a summary; exit status 1 if any kernel of OLD differs or is missing."""
 import argparse
@@ -71,9 +71,13 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--rename", action="append", default=[], help="REGEX=REPL applied to NEW's symbols before the lookup")
+    ap.add_argument("--rename-file", help="a file of REGEX=REPL lines, applied after the --rename ones (blank lines and # comments skipped)")
     a = ap.parse_args()
     old, new = kernels(a.old), kernels(a.new)
-    subs = [r.split("=", 1) for r in a.rename]
+    renames = list(a.rename)
+    if a.rename_file:
+        renames += [ln.strip() for ln in open(a.rename_file) if ln.strip() and not ln.lstrip().startswith("#")]
+    subs = [r.split("=", 1) for r in renames]
     renamed = {}
     for sym, body in new.items():
         k = sym

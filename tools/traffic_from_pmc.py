@@ -54,8 +54,10 @@ n_v = sum(fp.get(k, 0) for k in ("valu_simple", "valu_half", "valu_pk", "valu_tr
 pick = {"primary_shadow_march": (["primary_shadow_wave_kernel<0, false, false, 1, false>"], True),
         "primary_march": (["primary_tile_kernel<0, false, false, true>", "primary_tile_kernel<0, false, false, false>"], True),
         "shadow_march": (["shadow_kernel<0, false, false>"], True),
-        "path_primary_march": (["path_primary_kernel<0, false, false, false, false, false>", "path_primary_kernel<0, false, false, true, false, false>"], False),
-        "path_bounce_marches": (["path_bounce_cells_kernel<true, 5u>(vrt::CellsLaunch)", "path_bounce_cells_kernel<true, 4u>(vrt::CellsLaunch)", "path_bounce_cells_kernel<false, 4u>(vrt::CellsLaunch)"], False)}
+        # <MARCH, LDS_ROOTS, STATS, MULTI, EMIT, POLISH, TRANSLUCENT> and <DIRECT, KB, EMIT, POLISH, TRANSLUCENT>: the plain frame's
+        "path_primary_march": (["path_primary_kernel<0, false, false, false, false, false, false>", "path_primary_kernel<0, false, false, true, false, false, false>"], False),
+        "path_bounce_marches": (["path_bounce_cells_kernel<true, 5u, false, false, false>(vrt::CellsLaunch)", "path_bounce_cells_kernel<true, 4u, false, false, false>(vrt::CellsLaunch)",
+                                 "path_bounce_cells_kernel<false, 4u, false, false, false>(vrt::CellsLaunch)"], False)}
 frames = 8.0   # tools/pmc.sh: bench.py --steps 6 --warmup 2, standing camera, no extra legs
 kernels = {}
 for k, (names, use_mix) in pick.items():

@@ -27,7 +27,7 @@ namespace {
 static_assert(kDnMaxPasses == 5u, "a kernel per tap spacing: 1, 2 (LDS), 4, 8, 16");
 static_assert(kDnKeyMask == (VRT_ID_VOXEL_MASK | VRT_ID_HIT | VRT_ID_NX | VRT_ID_NY | VRT_ID_NZ | VRT_ID_WATER), "both/denoise_math.h restates the id bits");
 
-// One wave = one 8 x 8 tile, as in the frame's own primary launch; the id word composed as path_primary_kernel composes it.
+// One wave = one 8 x 8 tile, as in the frame's own primary launch; the id word composed as path_primary_kernel composes it (id_word, vrt_path_common.h).
 template <int MARCH>
 __global__ void __launch_bounds__(256) denoise_guide_kernel(FrameParams P, uint32_t *guide) {
     __shared__ uint32_t smem[24];

@@ -327,42 +327,40 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         VRT_TRY(frame_buf(c, c->sz.d_accum, frame_slots(c)));
         HIP_TRY(c, c->ev_accum.ensure());
     }
+    // what a frame's kernels read from the launch instead of being built per combination: the coat's coin, the pass-through draw
+    const uint32_t lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
+    // The record buffer of a light's rays (the sun's, the lamps'), the frame set's own: three planes of plan.cap records and two
+    // cursor sets, zero when the frame starts; the fields every such launch struct has
+    auto light_rays = [&](vrt_ctx::Buf<uint4> &recs, vrt_ctx::Buf<uint32_t> &counts, auto &launch, uint32_t *(&seg)[2]) -> int {
+        constexpr size_t kSegWords = (size_t)vrt::kHitSegments * vrt::kSegStride;
+        HIP_TRY(c, recs.grow(3 * plan.cap));
+        HIP_TRY(c, counts.once(2 * kSegWords));
+        seg[0] = counts;
+        seg[1] = seg[0] + kSegWords;
+        HIP_TRY(c, hipMemsetAsync(seg[0], 0, 2 * kSegWords * sizeof(uint32_t), f.st));
+        launch.recs = recs;
+        launch.cap = (uint32_t)plan.cap;
+        launch.seg_cap = plan.seg_cap;
+        launch.lobes = lobes;
+        return VRT_OK;
+    };
     vrt::SunLaunch S{};
     uint32_t *sun_seg[2] = {nullptr, nullptr};
-    if (plan.sun) {   // vrt_set_sun_light: the frame set's sun-ray buffer and its two cursor sets, zero when the frame starts
-        constexpr size_t kSunSegWords = (size_t)vrt::kHitSegments * vrt::kSegStride;
-        HIP_TRY(c, c->sz.sun_recs[f.slot].grow(3 * plan.cap));
-        HIP_TRY(c, c->sz.sun_counts[f.slot].once(2 * kSunSegWords));
-        sun_seg[0] = c->sz.sun_counts[f.slot];
-        sun_seg[1] = sun_seg[0] + kSunSegWords;
-        HIP_TRY(c, hipMemsetAsync(sun_seg[0], 0, 2 * kSunSegWords * sizeof(uint32_t), f.st));
-        S.recs = c->sz.sun_recs[f.slot];
-        S.cap = (uint32_t)plan.cap;
-        S.seg_cap = plan.seg_cap;
+    if (plan.sun) {   // vrt_set_sun_light
+        VRT_TRY(light_rays(c->sz.sun_recs[f.slot], c->sz.sun_counts[f.slot], S, sun_seg));
         S.k = c->settings.sun_intensity * c->sun.strength;   // (one binary32 product: the contract's k)
-        S.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
     }
     vrt::LampLaunch M{};
     uint32_t *lamp_seg[2] = {nullptr, nullptr};
     if (plan.lamp) {   // vrt_set_lamp_light: the frame set's lamp list, brought up to date on its stream, and its lamp-ray buffer
-        constexpr size_t kLampSegWords = (size_t)vrt::kHitSegments * vrt::kSegStride;
         VRT_TRY(lamp_list_for_frame(c, f.slot, tab, f.st, M));
-        HIP_TRY(c, c->sz.lamp_recs[f.slot].grow(3 * plan.cap));
-        HIP_TRY(c, c->sz.lamp_counts[f.slot].once(2 * kLampSegWords));
-        lamp_seg[0] = c->sz.lamp_counts[f.slot];
-        lamp_seg[1] = lamp_seg[0] + kLampSegWords;
-        HIP_TRY(c, hipMemsetAsync(lamp_seg[0], 0, 2 * kLampSegWords * sizeof(uint32_t), f.st));
-        M.recs = c->sz.lamp_recs[f.slot];
-        M.cap = (uint32_t)plan.cap;
-        M.seg_cap = plan.seg_cap;
+        VRT_TRY(light_rays(c->sz.lamp_recs[f.slot], c->sz.lamp_counts[f.slot], M, lamp_seg));
         M.strength = c->lamp.strength;
         M.max_geometry = c->lamp.max_geometry;
-        M.lobes = (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u);
         M.sun = plan.sun ? 1u : 0u;
     }
     // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
-    const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance,
-                            (plan.polish ? vrt::kSunLobePolish : 0u) | (plan.translucent ? vrt::kSunLobeTranslucent : 0u)};
+    const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance, lobes};
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
     P.hit_seg_cap = plan.seg_cap;
     P.acc = plan.planes ? acc : nullptr;

@@ -1,16 +1,33 @@
-// vrt_path_cells.h — the body of the pool kernel over the march cells (vrt_path.hip), included there four times: as
-// path_bounce_cells_kernel (VRT_CELLS_EMIT 0, the plain frame's), as path_emissive_cells_kernel (VRT_CELLS_EMIT 1: emissive
-// hits add their light too, vrt_write_emission — the hits of the last segment included), as path_polished_cells_kernel
-// (VRT_CELLS_POLISH 1, with EMIT: phase C also flips the coat's coin, vrt_write_polish) and as path_translucent_cells_kernel
-// (VRT_CELLS_TRANSLUCENT 1, with EMIT: phase C first draws whether the path passes, vrt_write_translucency).  Kernels of their own rather
-// than more template arguments: the plain one keeps its name, its three instantiations and, as the kernel's own body
-// rather than an inlined function, its instruction stream.
-// In: VRT_CELLS_KERNEL (the kernel's name), VRT_CELLS_EMIT, VRT_CELLS_POLISH, VRT_CELLS_TRANSLUCENT (0 or 1).
+// vrt_path_cells.h — the pool kernel over the march cells, for vrt_path.hip: path_bounce_cells_kernel, one template for the plain
+// frame's kernel, the emissive one (EMIT: emissive hits add their light too, vrt_write_emission — the hits of the last segment
+// included), the one whose phase C also flips the coat's coin (POLISH, with EMIT: vrt_write_polish) and the one whose phase C first
+// draws whether the path passes (TRANSLUCENT, with EMIT: vrt_write_translucency).
+//
+// Bounce b >= 1 over the MARCH CELLS (vrt_accel.hip; the default for plain frames of worlds that have them): the lane = path
+// kernel of vrt_path_bounce.h with a march loop that has ONE load per step and no dependent load at all.
+//
+// What held the lane = path kernel at a quarter of its issue rate was the pair of dependent loads of a step in a split cell —
+// cell entry, then the voxel's brick entry: 290 + 515 cycles of a 2 200-cycle wave-step, half of them L1 misses
+// (profiles/r02_path_pmc_summary.txt) — on the critical path of every ray, and a launch lasts as long as its longest
+// chain of steps.  A march cell answers both questions of a step from one 16-byte entry: the leaf's size (a leaf
+// cell's lo, or the split cell's size-2 mask) and whether the voxel stops the ray (64 bits; liquids are transparent to
+// a path segment, so they count as air — the tables are built with the material table's liquid set).  Which voxel it
+// stopped on is only asked after the march, at full width, from the brick (phase C).
+// Also here: phase C takes the rays that hit and the rays that missed in separate batches (a wave executes both sides of that
+// branch otherwise: ~510 + ~130 vector instructions per ray), and on the last bounce the rays that hit are not shaded at all
+// (their bounce would be dropped).  Every ray executes the arithmetic the other kernels execute for it: bit-identical frames (tests).
+#pragma once
 
-template <bool DIRECT, uint32_t KB>
+#include "vrt_path_common.h"
+
+namespace vrt {
+
+// KB: batches of 64 rays in a wave's pool.  4 (256 rays, 32 waves per CU) everywhere but for small worlds with two frames in flight:
+// there 5 (320 rays, 28 waves per CU) — fewer dry tails per ray, and the four wave slots a CU keeps free let the next frame's primary
+// launch start beside this one: C4 + 2.8 % (one frame at a time - 2.2 %, C5 - 3.8 %: profiles/r05_pool_k5.txt)
+template <bool DIRECT, uint32_t KB, bool EMIT = false, bool POLISH = false, bool TRANSLUCENT = false>
 __attribute__((amdgpu_waves_per_eu(8, 8)))
-__global__ void __launch_bounds__(256) VRT_CELLS_KERNEL(CellsLaunch L) {
-    constexpr bool EMIT = VRT_CELLS_EMIT, POLISH = VRT_CELLS_POLISH, TRANSLUCENT = VRT_CELLS_TRANSLUCENT;
+__global__ void __launch_bounds__(256) path_bounce_cells_kernel(CellsLaunch L) {
     const FrameParams &K = L.P;
     extern __shared__ uint32_t smem[];
     uint32_t *s_liquid = smem;
@@ -447,13 +464,7 @@ __global__ void __launch_bounds__(256) VRT_CELLS_KERNEL(CellsLaunch L) {
             bool lit;
             if (EMIT && last_bounce && j < n_hit) lit = path_emission(P, R, hit_color(P, R), st.thr, light);   // (the path ends here)
             else alive = path_after_march<EMIT, POLISH, TRANSLUCENT>(P, st, R, light, lit) && !last_bounce;
-            if (lit) {
-                uint4 t = P.out[st.slot];
-                t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
-                t.y = __float_as_uint(__uint_as_float(t.y) + light.y);
-                t.z = __float_as_uint(__uint_as_float(t.z) + light.z);
-                P.out[st.slot] = t;
-            }
+            if (lit) add_light(P.out, st.slot, light);
         }
         if (left != 1u) {   // the survivors, compacted into this wave's own range of the other buffer
             const unsigned long long m = __ballot(alive);
@@ -479,3 +490,4 @@ __global__ void __launch_bounds__(256) VRT_CELLS_KERNEL(CellsLaunch L) {
     }
 }
 
+}  // namespace vrt

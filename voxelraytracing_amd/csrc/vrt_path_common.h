@@ -97,8 +97,8 @@ __device__ __forceinline__ bool path_emission(const FrameParams &P, const MarchR
     return true;
 }
 
-// A hit of a translucent frame (vrt_write_translucency, include/vrt.h: steps 3 to 6 there; the family of path_translucent_*
-// kernels).  ut is drawn on every hit, ahead of everything else; a lane whose ut is below its entry's chance passes: it keeps
+// A hit of a translucent frame (vrt_write_translucency, include/vrt.h: steps 3 to 6 there; the TRANSLUCENT builds of the
+// path kernels).  ut is drawn on every hit, ahead of everything else; a lane whose ut is below its entry's chance passes: it keeps
 // dir, crosses the unit voxel that holds the hit position, multiplies thr by the entry's colour and draws nothing more.  Every
 // other lane runs the body of path_after_march below — the coat's draw under the word behind the tables (the same for every
 // lane: a scalar branch), so that this family exists once, polished or not.  The RNG state, origin, dir and tint are selected per
@@ -190,6 +190,16 @@ __device__ __forceinline__ bool path_after_march(const FrameParams &P, PathState
     return true;
 }
 
+// path_after_march of a frame whose kernels read coat and pass-through from the launch (`lobes`: kSunLobePolish | kSunLobeTranslucent,
+// the same for every lane — a scalar branch; one kernel, not one per combination), the emission term always carried: a table of
+// zeros adds nothing and marks nothing lit
+template <bool SKY_NO_DISC = false>
+__device__ __forceinline__ bool path_after_march_lobes(const FrameParams &P, uint32_t lobes, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
+    if (lobes & kSunLobeTranslucent) return path_after_march<true, false, true, SKY_NO_DISC>(P, st, R, light, lit);
+    if (lobes & kSunLobePolish) return path_after_march<true, true, false, SKY_NO_DISC>(P, st, R, light, lit);
+    return path_after_march<true, false, false, SKY_NO_DISC>(P, st, R, light, lit);
+}
+
 // the nudge off a voxel face at the start of a march (ray_tracer.wgsl:204-207)
 __device__ __forceinline__ V3 nudged(V3 pos, V3 dir) {
     if (pos.x - floorf(pos.x) < 0.001f || pos.y - floorf(pos.y) < 0.001f || pos.z - floorf(pos.z) < 0.001f) {
@@ -205,8 +215,9 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
-// Append the wave's surviving paths to this workgroup's segment of the out buffer (one atomic per wave).
-__device__ __forceinline__ void append_paths(const FrameParams &P, bool alive, const PathState &st, uint32_t lane) {
+// Append the wave's surviving paths to this workgroup's segment of the out buffer (one atomic per wave).  direct: what the
+// record's spare word — the third plane's .w — carries, 1 or 0 (a lamp-lit frame: whether the path is still direct, vrt_path_lamp.h).
+__device__ __forceinline__ void append_paths(const FrameParams &P, bool alive, const PathState &st, uint32_t lane, bool direct = false) {
     const unsigned long long ballot = __ballot(alive);
     const uint32_t n = (uint32_t)__popcll(ballot);
     if (!n) return;
@@ -219,7 +230,102 @@ __device__ __forceinline__ void append_paths(const FrameParams &P, bool alive, c
         const uint32_t i = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
         P.path_out[i] = make_uint4(st.slot, __float_as_uint(st.origin.x), __float_as_uint(st.origin.y), __float_as_uint(st.origin.z));
         P.path_out[P.path_cap + i] = make_uint4(__float_as_uint(st.dir.x), __float_as_uint(st.dir.y), __float_as_uint(st.dir.z), st.rng);
-        P.path_out[2u * P.path_cap + i] = make_uint4(__float_as_uint(st.thr.x), __float_as_uint(st.thr.y), __float_as_uint(st.thr.z), 0u);
+        P.path_out[2u * P.path_cap + i] = make_uint4(__float_as_uint(st.thr.x), __float_as_uint(st.thr.y), __float_as_uint(st.thr.z), direct ? 1u : 0u);
+    }
+}
+
+// A path record of the in buffer (append_paths wrote it), read back by the lane that marches it; its spare word, for the kernels
+// that read it (the third plane is loaded once: the compiler merges the two reads)
+__device__ __forceinline__ PathState load_path(const FrameParams &P, uint32_t i) {
+    const uint4 a = P.path_in[i], b = P.path_in[P.path_cap + i], c = P.path_in[2u * P.path_cap + i];
+    PathState st;
+    st.slot = a.x;
+    st.origin = V3{__uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w)};
+    st.dir = V3{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
+    st.rng = b.w;
+    st.thr = V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
+    return st;
+}
+__device__ __forceinline__ uint32_t path_spare_word(const FrameParams &P, uint32_t i) { return P.path_in[2u * P.path_cap + i].w; }
+
+// Append the wave's rays towards a light to this workgroup's segment of that light's buffer (append_paths' ballot compaction; B: the
+// SunLaunch or the LampLaunch, whose recs / counts / cap / seg_cap it is).  w1, w2: the spare words of the direction's and the term's plane.
+template <class B>
+__device__ __forceinline__ void append_light_rays(const B &buf, bool wants, uint32_t slot, const V3 &so, const V3 &dir, const V3 &term, uint32_t w1,
+                                                  uint32_t w2, uint32_t lane) {
+    const unsigned long long ballot = __ballot(wants);
+    const uint32_t n = (uint32_t)__popcll(ballot);
+    if (!n) return;
+    const uint32_t seg = blockIdx.x % kHitSegments;
+    const int leader = __ffsll((long long)ballot) - 1;
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(&buf.counts[seg * kSegStride], n);
+    base = __shfl(base, leader, 64);
+    if (wants) {
+        const uint32_t j = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+        if (j < buf.seg_cap) {   // (a segment holds what its workgroups can produce; never taken)
+            const uint32_t i = seg * buf.seg_cap + j;
+            buf.recs[i] = make_uint4(slot, __float_as_uint(so.x), __float_as_uint(so.y), __float_as_uint(so.z));
+            buf.recs[buf.cap + i] = make_uint4(__float_as_uint(dir.x), __float_as_uint(dir.y), __float_as_uint(dir.z), w1);
+            buf.recs[2u * buf.cap + i] = make_uint4(__float_as_uint(term.x), __float_as_uint(term.y), __float_as_uint(term.z), w2);
+        }
+    }
+}
+
+// ---- what the kernels of the lane = path families open and close with ----
+
+// The LDS of a launch (lds_bytes_path, vrt_path.hip): the liquid set, the stats frame's block sums (zeroed here), the root table
+// where it fits.  The tables are staged by the kernel itself, behind this: stage_lds(P, s.roots, s.liquid, LDS_ROOTS)
+struct PathLds {
+    uint32_t *liquid, *roots;
+    unsigned long long *acc;
+};
+template <bool STATS>
+__device__ __forceinline__ PathLds path_lds() {
+    extern __shared__ uint32_t smem[];
+    const PathLds s{smem, smem + 24, reinterpret_cast<unsigned long long *>(smem + 8)};
+    if (STATS && threadIdx.x < 8) s.acc[threadIdx.x] = 0ull;
+    return s;
+}
+
+// the id word of a march result, composed as shade() does
+__device__ __forceinline__ uint32_t id_word(const MarchResult R) {
+    uint32_t id = R.voxel & VRT_ID_VOXEL_MASK;
+    if (R.hit) id |= VRT_ID_HIT;
+    if (R.norm.x != 0.0f) id |= VRT_ID_NX;
+    if (R.norm.y != 0.0f) id |= VRT_ID_NY;
+    if (R.norm.z != 0.0f) id |= VRT_ID_NZ;
+    if (R.water_dist != 0.0f) id |= VRT_ID_WATER;
+    return id;
+}
+
+// A sample's seed: path_tracer.wgsl:328 (y*W + x) + the per-sample stride and frame seed of SURVEY §8d; an accumulating frame's
+// samples continue the accumulation's (P.sample_base: 0 otherwise)
+__device__ __forceinline__ uint32_t sample_seed(const FrameParams &P, uint32_t px, uint32_t py, uint32_t sample) {
+    return py * P.width + px + (P.sample_base + sample) * (P.width * P.height) + P.seed * 0x9E3779B9u;
+}
+
+// a light term into its texel: a plain read-modify-write (one owner lane per slot and launch)
+__device__ __forceinline__ void add_light(Texel *out, uint32_t slot, const V3 light) {
+    uint4 t = out[slot];
+    t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
+    t.y = __float_as_uint(__uint_as_float(t.y) + light.y);
+    t.z = __float_as_uint(__uint_as_float(t.z) + light.z);
+    out[slot] = t;
+}
+
+// What a stats frame's bounce kernels close with: the block's steps, node visits and marched paths into the frame's counters (the
+// secondary rays).  The two light-ray kernels (path_sun_kernel, path_lamp_rays_kernel) keep this text written out: called from
+// them, the load of P.counters moves in their compiled code (profiles/path_templates_isa_diff.txt).
+__device__ __forceinline__ void secondary_stats(const FrameParams &P, unsigned long long *acc, bool active, const MarchResult &R) {
+    block_add(acc, 0, active ? R.iters : 0u);
+    block_add(acc, 1, active ? R.visits : 0u);
+    block_add(acc, 2, active ? 1ull : 0ull);
+    __syncthreads();
+    if (threadIdx.x == 0 && acc[2]) {
+        atomicAdd(&P.counters[kCtrSteps], acc[0]);
+        atomicAdd(&P.counters[kCtrVisits], acc[1]);
+        atomicAdd(&P.counters[kCtrSecondary], acc[2]);
     }
 }
 

@@ -8,13 +8,14 @@
 // One pair of trace kernels carries the sun term too (vrt_path_sun.h's, under M.sun: the same for every lane) and reads coat and
 // pass-through from the launch, as the sun-lit pair does; the primary kernel is built with and without camera sampling
 // (vrt_path_lens.h's sample loop: the pixel's own pinhole ray is trip -1).  Kernels of their own: every kernel from before keeps
-// its name and its instruction stream (profiles/lamp_isa_diff.txt).  The path record's spare word — the third plane's .w —
+// its instruction stream (profiles/lamp_isa_diff.txt).  The path record's spare word — the third plane's .w —
 // carries whether the path is still direct: its emissive hits count only until its first bounce, behind which the lamp term
 // has them.
 #pragma once
 
 #include "vrt_path_common.h"
 #include "vrt_path_sun.h"
+#include "vrt_path_lens.h"
 
 namespace vrt {
 
@@ -69,45 +70,6 @@ __device__ __forceinline__ LampRay lamp_ray_of_hit(const FrameParams &P, const L
     return r;
 }
 
-// Append the wave's lamp rays to this workgroup's segment of the lamp buffer (append_sun_rays with the lamp voxel in the spare words).
-__device__ __forceinline__ void append_lamp_rays(const LampLaunch &M, const LampRay &r, uint32_t slot, uint32_t lane) {
-    const unsigned long long ballot = __ballot(r.wants);
-    const uint32_t n = (uint32_t)__popcll(ballot);
-    if (!n) return;
-    const uint32_t seg = blockIdx.x % kHitSegments;
-    const int leader = __ffsll((long long)ballot) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(&M.counts[seg * kSegStride], n);
-    base = __shfl(base, leader, 64);
-    if (r.wants) {
-        const uint32_t j = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-        if (j < M.seg_cap) {   // (a segment holds what its workgroups can produce; never taken)
-            const uint32_t i = seg * M.seg_cap + j;
-            M.recs[i] = make_uint4(slot, __float_as_uint(r.so.x), __float_as_uint(r.so.y), __float_as_uint(r.so.z));
-            M.recs[M.cap + i] = make_uint4(__float_as_uint(r.ld.x), __float_as_uint(r.ld.y), __float_as_uint(r.ld.z), r.pxy);
-            M.recs[2u * M.cap + i] = make_uint4(__float_as_uint(r.term.x), __float_as_uint(r.term.y), __float_as_uint(r.term.z), r.pz);
-        }
-    }
-}
-
-// append_paths with the path's direct bit in the record's spare word
-__device__ __forceinline__ void append_paths_lamp(const FrameParams &P, bool alive, const PathState &st, bool direct, uint32_t lane) {
-    const unsigned long long ballot = __ballot(alive);
-    const uint32_t n = (uint32_t)__popcll(ballot);
-    if (!n) return;
-    const uint32_t seg = blockIdx.x % kHitSegments;
-    const int leader = __ffsll((long long)ballot) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(&P.seg_counts[seg * kSegStride], n);
-    base = __shfl(base, leader, 64) + seg * P.hit_seg_cap;
-    if (alive) {
-        const uint32_t i = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-        P.path_out[i] = make_uint4(st.slot, __float_as_uint(st.origin.x), __float_as_uint(st.origin.y), __float_as_uint(st.origin.z));
-        P.path_out[P.path_cap + i] = make_uint4(__float_as_uint(st.dir.x), __float_as_uint(st.dir.y), __float_as_uint(st.dir.z), st.rng);
-        P.path_out[2u * P.path_cap + i] = make_uint4(__float_as_uint(st.thr.x), __float_as_uint(st.thr.y), __float_as_uint(st.thr.z), direct ? 1u : 0u);
-    }
-}
-
 // What follows a segment's march in a lamp-lit frame (the hit's three draws are taken by the caller, ahead of this): the sky of a
 // miss — without the disc for a later segment of a frame that is sun-lit too — or path_after_march with the emission term, kept
 // only while the path is direct, and the coat's coin or the pass-through draw as the frame has them.  direct: in, the path
@@ -126,10 +88,7 @@ __device__ __forceinline__ bool path_after_march_lamp(const FrameParams &P, cons
         uint32_t peek = st.rng;
         passes = rng_next(peek) < translucency_table(P.mats)[min(R.voxel, 255u)].chance;
     }
-    bool alive;
-    if (M.lobes & kSunLobeTranslucent) alive = path_after_march<true, false, true>(P, st, R, light, lit);
-    else if (M.lobes & kSunLobePolish) alive = path_after_march<true, true, false>(P, st, R, light, lit);
-    else alive = path_after_march<true, false, false>(P, st, R, light, lit);
+    const bool alive = path_after_march_lobes(P, M.lobes, st, R, light, lit);
     if (!direct) lit = false;   // (behind the first bounce the lamp term has the lamps)
     if (!passes) direct = false;
     return alive;
@@ -144,11 +103,8 @@ constexpr size_t kLampAt = kernarg_after(kLampSunAt + sizeof(SunLaunch), alignof
 // primary ray from four draws, the pixel's pinhole ray marched once more for the id word by the launch of the frame's first sample.
 template <int MARCH, bool LDS_ROOTS, bool STATS, bool LENS>
 __global__ void __launch_bounds__(256) path_lamp_primary_kernel(FrameParams P, LensLaunch L, SunLaunch S, LampLaunch M) {
-    extern __shared__ uint32_t smem[];
-    uint32_t *s_liquid = smem, *s_roots = smem + 24;
-    unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
-    if (STATS && threadIdx.x < 8) s_acc[threadIdx.x] = 0ull;
-    stage_lds(P, s_roots, s_liquid, LDS_ROOTS);
+    const PathLds s = path_lds<STATS>();
+    stage_lds(P, s.roots, s.liquid, LDS_ROOTS);
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t t_local = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -176,27 +132,22 @@ __global__ void __launch_bounds__(256) path_lamp_primary_kernel(FrameParams P, L
             PathState st;
             st.slot = pixel_slot;
             st.thr = V3{1.0f, 1.0f, 1.0f};
-            st.rng = py * Q.width + px + (Q.sample_base + Q.sample) * (Q.width * Q.height) + Q.seed * 0x9E3779B9u;   // vrt_path_primary.h's seed
+            st.rng = py * Q.width + px + (Q.sample_base + Q.sample) * (Q.width * Q.height) + Q.seed * 0x9E3779B9u;   // (sample_seed's text, vrt_path_common.h)
             MarchResult R;
             if (LENS) {
                 if (s_local < 0) create_ray(Q, (int)px, (int)py, st.origin, st.dir);
                 else lens_ray(Q, LQ, px, py, st.rng, st.origin, st.dir);
-                R = march<MARCH, LDS_ROOTS, STATS>(Q, s_roots, s_liquid, st.origin, st.dir);
+                R = march<MARCH, LDS_ROOTS, STATS>(Q, s.roots, s.liquid, st.origin, st.dir);
             } else {
                 create_ray(Q, (int)px, (int)py, st.origin, st.dir);
-                R = march<MARCH, LDS_ROOTS, STATS, true>(Q, s_roots, s_liquid, st.origin, st.dir);
+                R = march<MARCH, LDS_ROOTS, STATS, true>(Q, s.roots, s.liquid, st.origin, st.dir);
             }
             if (STATS) {
                 iters += R.iters;
                 visits += R.visits;
             }
-            if (!LENS || s_local < 0) {   // the id word of the pixel's own ray, composed as shade() does
-                id0 = R.voxel & VRT_ID_VOXEL_MASK;
-                if (R.hit) id0 |= VRT_ID_HIT;
-                if (R.norm.x != 0.0f) id0 |= VRT_ID_NX;
-                if (R.norm.y != 0.0f) id0 |= VRT_ID_NY;
-                if (R.norm.z != 0.0f) id0 |= VRT_ID_NZ;
-                if (R.water_dist != 0.0f) id0 |= VRT_ID_WATER;
+            if (!LENS || s_local < 0) {   // the id word of the pixel's own ray
+                id0 = id_word(R);
                 centre_hit = R.hit && Q.sample == 0u;
                 if (STATS && Q.steps && Q.sample == 0u) Q.steps[pixel_slot] = R.iters;
             }
@@ -206,36 +157,32 @@ __global__ void __launch_bounds__(256) path_lamp_primary_kernel(FrameParams P, L
             if (R.hit) { u1 = rng_next(st.rng); u2 = rng_next(st.rng); u3 = rng_next(st.rng); }
             V3 so{0.f, 0.f, 0.f}, sd{0.f, 0.f, 0.f}, sterm{0.f, 0.f, 0.f};   // (thr is 1: before the hit)
             bool sun = false;
-            if (MQ.sun) sun = sun_ray_of_hit(Q, SQ, s_liquid, R.hit, R, st.thr, so, sd, sterm);
-            const LampRay lr = lamp_ray_of_hit(Q, MQ, n_lamps, s_liquid, R, st.thr, u1, u2, u3);
+            if (MQ.sun) sun = sun_ray_of_hit(Q, SQ, s.liquid, R.hit, R, st.thr, so, sd, sterm);
+            const LampRay lr = lamp_ray_of_hit(Q, MQ, n_lamps, s.liquid, R, st.thr, u1, u2, u3);
             V3 light{0.f, 0.f, 0.f};
             bool lit, direct = true;
             const bool alive = path_after_march_lamp<false>(Q, MQ, st, R, light, lit, direct) && !Q.last_bounce;
             if (Q.sample == 0u) {
                 Q.out[st.slot] = make_uint4(__float_as_uint(light.x), __float_as_uint(light.y), __float_as_uint(light.z), id0);
             } else if (lit) {
-                uint4 t = Q.out[st.slot];
-                t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
-                t.y = __float_as_uint(__uint_as_float(t.y) + light.y);
-                t.z = __float_as_uint(__uint_as_float(t.z) + light.z);
-                Q.out[st.slot] = t;
+                add_light(Q.out, st.slot, light);
             }
-            append_paths_lamp(Q, alive, st, direct, lane);
-            if (MQ.sun) append_sun_rays(SQ, sun, st.slot, so, sd, sterm, lane);
-            append_lamp_rays(MQ, lr, st.slot, lane);
+            append_paths(Q, alive, st, lane, direct);
+            if (MQ.sun) append_light_rays(SQ, sun, st.slot, so, sd, sterm, 0u, 0u, lane);
+            append_light_rays(MQ, lr.wants, st.slot, lr.so, lr.ld, lr.term, lr.pxy, lr.pz, lane);
         }
     }
     if (STATS) {
-        block_add(s_acc, 0, iters);
-        block_add(s_acc, 1, visits);
-        block_add(s_acc, 2, centre_hit ? 1ull : 0ull);
+        block_add(s.acc, 0, iters);
+        block_add(s.acc, 1, visits);
+        block_add(s.acc, 2, centre_hit ? 1ull : 0ull);
         __syncthreads();
         if (threadIdx.x == 0) {
-            atomicAdd(&P.counters[kCtrSteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrPrimarySteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrPrimaryVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrHits], s_acc[2]);
+            atomicAdd(&P.counters[kCtrSteps], s.acc[0]);
+            atomicAdd(&P.counters[kCtrVisits], s.acc[1]);
+            atomicAdd(&P.counters[kCtrPrimarySteps], s.acc[0]);
+            atomicAdd(&P.counters[kCtrPrimaryVisits], s.acc[1]);
+            atomicAdd(&P.counters[kCtrHits], s.acc[2]);
         }
     }
 }
@@ -243,11 +190,8 @@ __global__ void __launch_bounds__(256) path_lamp_primary_kernel(FrameParams P, L
 // Bounce b >= 1 of a lamp-lit frame: lane = one live path of the in buffer.
 template <int MARCH, bool LDS_ROOTS, bool STATS>
 __global__ void __launch_bounds__(256) path_lamp_bounce_kernel(FrameParams P, SunLaunch S, LampLaunch M) {
-    extern __shared__ uint32_t smem[];
-    uint32_t *s_liquid = smem, *s_roots = smem + 24;
-    unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
-    if (STATS && threadIdx.x < 8) s_acc[threadIdx.x] = 0ull;
-    stage_lds(P, s_roots, s_liquid, LDS_ROOTS);
+    const PathLds s = path_lds<STATS>();
+    stage_lds(P, s.roots, s.liquid, LDS_ROOTS);
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t seg = blockIdx.x % kHitSegments, part = blockIdx.x / kHitSegments;
@@ -273,45 +217,23 @@ __global__ void __launch_bounds__(256) path_lamp_bounce_kernel(FrameParams P, Su
     st.slot = 0; st.rng = 0;
     st.origin = st.dir = st.thr = V3{0.f, 0.f, 0.f};
     if (active) {
-        const uint32_t i = seg * P.hit_seg_cap + j;
-        const uint4 a = P.path_in[i], b = P.path_in[P.path_cap + i], c = P.path_in[2u * P.path_cap + i];
-        st.slot = a.x;
-        st.origin = V3{__uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w)};
-        st.dir = V3{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
-        st.rng = b.w;
-        st.thr = V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)};
-        direct = c.w != 0u;
+        st = load_path(P, seg * P.hit_seg_cap + j);
+        direct = path_spare_word(P, seg * P.hit_seg_cap + j) != 0u;
         V3 light{0.f, 0.f, 0.f};
         bool lit;
-        R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, st.origin, st.dir);
+        R = march<MARCH, LDS_ROOTS, STATS>(P, s.roots, s.liquid, st.origin, st.dir);
         float u1 = 0.0f, u2 = 0.0f, u3 = 0.0f;
         if (R.hit) { u1 = rng_next(st.rng); u2 = rng_next(st.rng); u3 = rng_next(st.rng); }
-        if (M.sun) sun = sun_ray_of_hit(P, S, s_liquid, R.hit, R, st.thr, so, sd, sterm);   // (thr: before the hit)
-        lr = lamp_ray_of_hit(P, M, n_lamps, s_liquid, R, st.thr, u1, u2, u3);
+        if (M.sun) sun = sun_ray_of_hit(P, S, s.liquid, R.hit, R, st.thr, so, sd, sterm);   // (thr: before the hit)
+        lr = lamp_ray_of_hit(P, M, n_lamps, s.liquid, R, st.thr, u1, u2, u3);
         alive = path_after_march_lamp<true>(P, M, st, R, light, lit, direct) && !P.last_bounce;
-        if (lit) {
-            uint4 t = P.out[st.slot];
-            t.x = __float_as_uint(__uint_as_float(t.x) + light.x);
-            t.y = __float_as_uint(__uint_as_float(t.y) + light.y);
-            t.z = __float_as_uint(__uint_as_float(t.z) + light.z);
-            P.out[st.slot] = t;
-        }
+        if (lit) add_light(P.out, st.slot, light);
         if (STATS && P.steps && P.sample == 0u) P.steps[st.slot] += R.iters << 16;
     }
-    append_paths_lamp(P, alive, st, direct, lane);
-    if (M.sun) append_sun_rays(S, sun, st.slot, so, sd, sterm, lane);
-    append_lamp_rays(M, lr, st.slot, lane);
-    if (STATS) {
-        block_add(s_acc, 0, active ? R.iters : 0u);
-        block_add(s_acc, 1, active ? R.visits : 0u);
-        block_add(s_acc, 2, active ? 1ull : 0ull);
-        __syncthreads();
-        if (threadIdx.x == 0 && s_acc[2]) {
-            atomicAdd(&P.counters[kCtrSteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrSecondary], s_acc[2]);
-        }
-    }
+    append_paths(P, alive, st, lane, direct);
+    if (M.sun) append_light_rays(S, sun, st.slot, so, sd, sterm, 0u, 0u, lane);
+    append_light_rays(M, lr.wants, st.slot, lr.so, lr.ld, lr.term, lr.pxy, lr.pz, lane);
+    if (STATS) secondary_stats(P, s.acc, active, R);
 }
 
 // The lamp launch: lane = one record of the trace launch in front of it, marched by march<> — which also counts: a stats frame's
@@ -319,11 +241,8 @@ __global__ void __launch_bounds__(256) path_lamp_bounce_kernel(FrameParams P, Su
 // the record's lamp voxel.
 template <int MARCH, bool LDS_ROOTS, bool STATS>
 __global__ void __launch_bounds__(256) path_lamp_rays_kernel(FrameParams P, LampLaunch M) {
-    extern __shared__ uint32_t smem[];
-    uint32_t *s_liquid = smem, *s_roots = smem + 24;
-    unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
-    if (STATS && threadIdx.x < 8) s_acc[threadIdx.x] = 0ull;
-    stage_lds(P, s_roots, s_liquid, LDS_ROOTS);
+    const PathLds s = path_lds<STATS>();
+    stage_lds(P, s.roots, s.liquid, LDS_ROOTS);
     const uint32_t seg = blockIdx.x % kHitSegments, part = blockIdx.x / kHitSegments;
     const uint32_t count = min(M.counts[seg * kSegStride], M.seg_cap);
     const uint32_t j = part * blockDim.x + threadIdx.x;
@@ -336,27 +255,21 @@ __global__ void __launch_bounds__(256) path_lamp_rays_kernel(FrameParams P, Lamp
         const uint4 a = M.recs[i], b = M.recs[M.cap + i], c = M.recs[2u * M.cap + i];
         const V3 so{__uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w)};
         const V3 ld{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)};
-        R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, so, ld);
+        R = march<MARCH, LDS_ROOTS, STATS>(P, s.roots, s.liquid, so, ld);
         // (a hit position is inside the world: its floor is a small non-negative integer)
         const bool on_lamp = R.hit && (int)floorf(R.pos.x) == (int)(b.w & 0xFFFFu) && (int)floorf(R.pos.y) == (int)(b.w >> 16) &&
                              (int)floorf(R.pos.z) == (int)c.w;
-        if (on_lamp) {
-            uint4 t = P.out[a.x];
-            t.x = __float_as_uint(__uint_as_float(t.x) + __uint_as_float(c.x));
-            t.y = __float_as_uint(__uint_as_float(t.y) + __uint_as_float(c.y));
-            t.z = __float_as_uint(__uint_as_float(t.z) + __uint_as_float(c.z));
-            P.out[a.x] = t;
-        }
+        if (on_lamp) add_light(P.out, a.x, V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)});
     }
     if (STATS) {
-        block_add(s_acc, 0, active ? R.iters : 0u);
-        block_add(s_acc, 1, active ? R.visits : 0u);
-        block_add(s_acc, 2, active ? 1ull : 0ull);
+        block_add(s.acc, 0, active ? R.iters : 0u);
+        block_add(s.acc, 1, active ? R.visits : 0u);
+        block_add(s.acc, 2, active ? 1ull : 0ull);
         __syncthreads();
-        if (threadIdx.x == 0 && s_acc[2]) {
-            atomicAdd(&P.counters[kCtrSteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrSecondary], s_acc[2]);
+        if (threadIdx.x == 0 && s.acc[2]) {
+            atomicAdd(&P.counters[kCtrSteps], s.acc[0]);
+            atomicAdd(&P.counters[kCtrVisits], s.acc[1]);
+            atomicAdd(&P.counters[kCtrSecondary], s.acc[2]);
         }
     }
 }

@@ -1,7 +1,7 @@
 // vrt_path_sun.h — direct sunlight for the path trace (vrt_set_sun_light, include/vrt.h), for vrt_path.hip: what the kernels
 // of a sun-lit frame share.  Every hit on a solid voxel whose face looks at the sun appends a record — its texel's slot, the
 // shadow ray's origin and direction (shadow_kernel's: the bounce origin, towards P.sun_local) and the term (mc * (k * c)) * thr —
-// to a compacted buffer of the frame set's own, segmented and appended to as the path buffers are (append_paths); a launch of
+// to a compacted buffer of the frame set's own, segmented and appended to as the path buffers are (append_light_rays); a launch of
 // its own right behind each trace launch marches the records and adds the term of the unoccluded ones to the slot's texel.
 // Stream order puts the term behind the segment's emission term and ahead of the next segment's; one record per slot per launch
 // keeps the plain read-modify-write free of races.
@@ -31,36 +31,8 @@ __device__ __forceinline__ bool sun_ray_of_hit(const FrameParams &P, const SunLa
     return solid && c > 0.0f;   // (a zero normal or a NaN: no ray)
 }
 
-// Append the wave's sun rays to this workgroup's segment of the sun buffer (append_paths' ballot compaction, the sun buffer's cursors).
-__device__ __forceinline__ void append_sun_rays(const SunLaunch &S, bool wants, uint32_t slot, const V3 &so, const V3 &sd, const V3 &term, uint32_t lane) {
-    const unsigned long long ballot = __ballot(wants);
-    const uint32_t n = (uint32_t)__popcll(ballot);
-    if (!n) return;
-    const uint32_t seg = blockIdx.x % kHitSegments;
-    const int leader = __ffsll((long long)ballot) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(&S.counts[seg * kSegStride], n);
-    base = __shfl(base, leader, 64);
-    if (wants) {
-        const uint32_t j = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-        if (j < S.seg_cap) {   // (a segment holds what its workgroups can produce; never taken)
-            const uint32_t i = seg * S.seg_cap + j;
-            S.recs[i] = make_uint4(slot, __float_as_uint(so.x), __float_as_uint(so.y), __float_as_uint(so.z));
-            S.recs[S.cap + i] = make_uint4(__float_as_uint(sd.x), __float_as_uint(sd.y), __float_as_uint(sd.z), 0u);
-            S.recs[2u * S.cap + i] = make_uint4(__float_as_uint(term.x), __float_as_uint(term.y), __float_as_uint(term.z), 0u);
-        }
-    }
-}
-
-// What follows a segment's march in a sun-lit frame: path_after_march with the emission term, and the coat's coin or the
-// pass-through draw as the frame has them (S.lobes: the same for every lane — a scalar branch; one pair of kernels, not one per
-// combination).  LATER: a segment other than the primary — its miss takes the sky without the disc (step 4).
-template <bool LATER>
-__device__ __forceinline__ bool path_after_march_sunlit(const FrameParams &P, const SunLaunch &S, PathState &st, const MarchResult &R, V3 &light, bool &lit) {
-    if (S.lobes & kSunLobeTranslucent) return path_after_march<true, false, true, LATER>(P, st, R, light, lit);
-    if (S.lobes & kSunLobePolish) return path_after_march<true, true, false, LATER>(P, st, R, light, lit);
-    return path_after_march<true, false, false, LATER>(P, st, R, light, lit);
-}
+// the SunLaunch of a kernel built with one: the trailing argument pack (nothing, or SunLaunch) of the templates that have a sun-lit form
+__device__ __forceinline__ const SunLaunch &sun_launch(const SunLaunch &S) { return S; }
 
 // Is the ray from `origin` along `dir` (finite both) stopped before it leaves the world?  ray_world's answer — its hit flag — over the
 // march cells: liquids are passed (the cells' "passes" bits are built with the material table's liquid set), running out of the
@@ -128,13 +100,6 @@ __device__ __forceinline__ SunRecord load_sun_record(const SunLaunch &S, uint32_
                      V3{__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z)},
                      V3{__uint_as_float(c.x), __uint_as_float(c.y), __uint_as_float(c.z)}};
 }
-__device__ __forceinline__ void add_sun_term(const FrameParams &P, const SunRecord &r) {
-    uint4 t = P.out[r.slot];
-    t.x = __float_as_uint(__uint_as_float(t.x) + r.term.x);
-    t.y = __float_as_uint(__uint_as_float(t.y) + r.term.y);
-    t.z = __float_as_uint(__uint_as_float(t.z) + r.term.z);
-    P.out[r.slot] = t;
-}
 
 // The sun launch of a plain frame over the march cells: lane = one record of the trace launch in front of it.
 template <bool DIRECT>
@@ -144,7 +109,7 @@ __global__ void __launch_bounds__(256) path_sun_cells_kernel(FrameParams P, SunL
     const uint32_t j = part * blockDim.x + threadIdx.x;
     if (j >= count) return;
     const SunRecord r = load_sun_record(S, seg * S.seg_cap + j);
-    if (!sun_occluded_cells<DIRECT>(P, r.so, r.sd)) add_sun_term(P, r);
+    if (!sun_occluded_cells<DIRECT>(P, r.so, r.sd)) add_light(P.out, r.slot, r.term);
 }
 
 // ... of every other frame (stats, the literal march, worlds without march cells): the records marched by march<> — which also
@@ -152,11 +117,8 @@ __global__ void __launch_bounds__(256) path_sun_cells_kernel(FrameParams P, SunL
 // per-pixel counts stay the path segments'.
 template <int MARCH, bool LDS_ROOTS, bool STATS>
 __global__ void __launch_bounds__(256) path_sun_kernel(FrameParams P, SunLaunch S) {
-    extern __shared__ uint32_t smem[];
-    uint32_t *s_liquid = smem, *s_roots = smem + 24;
-    unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(smem + 8);
-    if (STATS && threadIdx.x < 8) s_acc[threadIdx.x] = 0ull;
-    stage_lds(P, s_roots, s_liquid, LDS_ROOTS);
+    const PathLds s = path_lds<STATS>();
+    stage_lds(P, s.roots, s.liquid, LDS_ROOTS);
     const uint32_t seg = blockIdx.x % kHitSegments, part = blockIdx.x / kHitSegments;
     const uint32_t count = min(S.counts[seg * kSegStride], S.seg_cap);
     const uint32_t j = part * blockDim.x + threadIdx.x;
@@ -166,18 +128,18 @@ __global__ void __launch_bounds__(256) path_sun_kernel(FrameParams P, SunLaunch 
     R.iters = 0; R.visits = 0; R.hit = false;
     if (active) {
         const SunRecord r = load_sun_record(S, seg * S.seg_cap + j);
-        R = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, r.so, r.sd);
-        if (!R.hit) add_sun_term(P, r);
+        R = march<MARCH, LDS_ROOTS, STATS>(P, s.roots, s.liquid, r.so, r.sd);
+        if (!R.hit) add_light(P.out, r.slot, r.term);
     }
     if (STATS) {
-        block_add(s_acc, 0, active ? R.iters : 0u);
-        block_add(s_acc, 1, active ? R.visits : 0u);
-        block_add(s_acc, 2, active ? 1ull : 0ull);
+        block_add(s.acc, 0, active ? R.iters : 0u);
+        block_add(s.acc, 1, active ? R.visits : 0u);
+        block_add(s.acc, 2, active ? 1ull : 0ull);
         __syncthreads();
-        if (threadIdx.x == 0 && s_acc[2]) {
-            atomicAdd(&P.counters[kCtrSteps], s_acc[0]);
-            atomicAdd(&P.counters[kCtrVisits], s_acc[1]);
-            atomicAdd(&P.counters[kCtrSecondary], s_acc[2]);
+        if (threadIdx.x == 0 && s.acc[2]) {
+            atomicAdd(&P.counters[kCtrSteps], s.acc[0]);
+            atomicAdd(&P.counters[kCtrVisits], s.acc[1]);
+            atomicAdd(&P.counters[kCtrSecondary], s.acc[2]);
         }
     }
 }
