@@ -28,6 +28,10 @@ typedef struct {   /* include/vrt.h: vrt_lamp */
  * caller asks: per list entry, the lamp rays that arrived at it */
 enum { LAMP_STEPS, LAMP_BOUNCE_SEGMENTS, LAMP_SUN_RAYS, LAMP_RAYS, LAMP_UNOCCLUDED, LAMP_EMISSION_DROPPED, LAMP_COUNTS };
 
+/* what a segment of a sample hands to the launches behind it, where the caller asks (ref_render_path_lamp_load): the path goes on
+ * into the next segment (it hit, and this was not its last allowed segment); a sun ray was marched from the hit; a lamp ray was */
+enum { LOAD_PATH = 1, LOAD_SUN = 2, LOAD_LAMP = 4 };
+
 /* the voxel id of every unit voxel of the world, dense[z][y][x], by the oracle's own walk */
 void ref_dense_world(const orc_scene *scene, uint16_t *dense) {
     const int32_t n = (int32_t)scene->world.size_in_chunks * 32;
@@ -46,7 +50,7 @@ static float comp(v3 v, uint32_t a) { return a == 0u ? v.x : (a == 1u ? v.y : v.
 static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const float *emission, const ref_polish *polish,
                           const ref_translucency *tr, int polished_frame, int translucent_frame, float sun_strength, const ref_camera_sampling *cs,
                           const ref_lamp_light *ll, const ref_lamp *list, uint32_t N, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n,
-                          uint32_t *arrived) {
+                          uint32_t *arrived, uint8_t *load, size_t load_stride) {
     v3 light = V3(0.0f, 0.0f, 0.0f);
     v3 origin, dir;
     if (cs->pixel_spread != 0.0f || cs->aperture != 0.0f) {
@@ -93,6 +97,7 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
             if (c > 0.0f) {
                 const hit_result sh = ray_world(s, so, sd);
                 n[LAMP_SUN_RAYS] += 1u;
+                if (load) load[bounce * load_stride] |= LOAD_SUN;
                 n[LAMP_STEPS] += sh.iter_count;
                 if (!sh.hit) {
                     const float k = s->settings.sun_intensity * sun_strength;
@@ -124,6 +129,7 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
                 if (c > 0.0f && cl > 0.0f) {
                     const hit_result lh = ray_world(s, so, ld);
                     n[LAMP_RAYS] += 1u;
+                    if (load) load[bounce * load_stride] |= LOAD_LAMP;
                     n[LAMP_STEPS] += lh.iter_count;
                     const int unoccluded = lh.hit && (int)floorf(lh.pos.x) == (int)L->pos[0] && (int)floorf(lh.pos.y) == (int)L->pos[1] &&
                                            (int)floorf(lh.pos.z) == (int)L->pos[2];
@@ -151,6 +157,7 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
             }
         }
         if (bounce + 1 == s->settings.max_ray_bounces) break;   /* the last allowed segment: what follows is observed by nothing */
+        if (load) load[bounce * load_stride] |= LOAD_PATH;
         if (translucent_frame && orc_rng_next(&rng) < tr[entry].chance) {   /* ut: ahead of u and of the direction; the path stays direct */
             const float tx = exit_t(rs.pos.x, dir.x), ty = exit_t(rs.pos.y, dir.y), tz = exit_t(rs.pos.z, dir.z);
             float t = tx;
@@ -179,11 +186,13 @@ static v3 trace_path_lamp(const orc_scene *s, const orc_scene *s_no_disc, const 
 }
 
 /* lens_ref.c's ref_render_path_lens with the lamp setting and the lamp list; counts[LAMP_COUNTS] as the enum says.  arrived: NULL, or
- * N words that the frame adds to: per list entry, the lamp rays that arrived at it unoccluded (their sum grows by counts[LAMP_UNOCCLUDED]) */
-void ref_render_path_lamp_arrivals(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr,
-                                   float sun_strength, const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N,
-                                   uint32_t w, uint32_t h, uint32_t spp, uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids,
-                                   uint64_t *counts, uint32_t *arrived) {
+ * N words that the frame adds to: per list entry, the lamp rays that arrived at it unoccluded (their sum grows by counts[LAMP_UNOCCLUDED]).
+ * load: NULL, or load[spp][max_ray_bounces][h][w] bytes, zero on entry: the LOAD_ bits of segment b of sample s of pixel (x, y) */
+void ref_render_path_lamp_load(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr,
+                               float sun_strength, const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N,
+                               uint32_t w, uint32_t h, uint32_t spp, uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids,
+                               uint64_t *counts, uint32_t *arrived, uint8_t *load) {
+    const size_t plane = (size_t)w * h;
     const uint32_t x1 = w & ~7u, y1 = h & ~7u, nspp = spp ? spp : 1u;
     const int on = cs->pixel_spread != 0.0f || cs->aperture != 0.0f;
     int polished_frame, translucent_frame;
@@ -208,7 +217,8 @@ void ref_render_path_lamp_arrivals(const orc_scene *scene, const float *emission
                 uint32_t sid = 0;
                 uint64_t n[LAMP_COUNTS] = {0, 0, 0, 0, 0, 0};
                 v3 l = trace_path_lamp(scene, &no_disc, emission, polish, tr, polished_frame, translucent_frame, sun_strength, cs, ll, list, N, px,
-                                       (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, arrived);
+                                       (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, arrived,
+                                       load ? load + ((size_t)sm * scene->settings.max_ray_bounces) * plane + o : NULL, plane);
                 sum.x += l.x; sum.y += l.y; sum.z += l.z;
                 n0 += n[0]; n1 += n[1]; n2 += n[2]; n3 += n[3]; n4 += n[4]; n5 += n[5];
                 if (!on && sm == 0) id = sid;
@@ -220,6 +230,13 @@ void ref_render_path_lamp_arrivals(const orc_scene *scene, const float *emission
         }
     }
     counts[0] = n0; counts[1] = n1; counts[2] = n2; counts[3] = n3; counts[4] = n4; counts[5] = n5;
+}
+
+void ref_render_path_lamp_arrivals(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr,
+                                   float sun_strength, const ref_camera_sampling *cs, const ref_lamp_light *ll, const ref_lamp *list, uint32_t N,
+                                   uint32_t w, uint32_t h, uint32_t spp, uint32_t seed, uint32_t sample_base, float *rgb, uint32_t *ids,
+                                   uint64_t *counts, uint32_t *arrived) {
+    ref_render_path_lamp_load(scene, emission, polish, tr, sun_strength, cs, ll, list, N, w, h, spp, seed, sample_base, rgb, ids, counts, arrived, NULL);
 }
 
 void ref_render_path_lamp(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
@@ -239,6 +256,6 @@ void ref_trace_pixel_lamp(const orc_scene *scene, const float *emission, const r
     uint32_t id = 0;
     for (int i = 0; i < LAMP_COUNTS; i++) counts[i] = 0;
     const v3 l = trace_path_lamp(scene, &no_disc, emission, polish, tr, polished_frame, translucent_frame, sun_strength, cs, ll, list, N, px, py,
-                                 path_seed(px, py, w, h, sample, seed), &id, counts, NULL);
+                                 path_seed(px, py, w, h, sample, seed), &id, counts, NULL, NULL, 0);
     light[0] = l.x; light[1] = l.y; light[2] = l.z;
 }

@@ -29,6 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 Counts = namedtuple("Counts", "steps bounce_segments sun_rays lamp_rays unoccluded emission_dropped")
 
 OFF = (0.0, 0.0, 0.0)
+LOAD_PATH, LOAD_SUN, LOAD_LAMP = 1, 2, 4   # tests/lamp_ref.c's bits of a load plane
 
 
 def liquid_set(materials) -> np.ndarray:
@@ -83,6 +84,8 @@ class LampRef:
                                            C.POINTER(LampLight), C.c_void_p, u32, u32, u32, u32, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ref_render_path_lamp_arrivals.restype = None
         L.ref_render_path_lamp_arrivals.argtypes = L.ref_render_path_lamp.argtypes + [C.c_void_p]
+        L.ref_render_path_lamp_load.restype = None
+        L.ref_render_path_lamp_load.argtypes = L.ref_render_path_lamp_arrivals.argtypes + [C.c_void_p]
         L.ref_trace_pixel_lamp.restype = None
         L.ref_trace_pixel_lamp.argtypes = [C.POINTER(orc.Scene), C.POINTER(f32), C.c_void_p, C.c_void_p, f32, C.POINTER(CameraSampling),
                                            C.POINTER(LampLight), C.c_void_p, u32, u32, u32, u32, u32, u32, u32, C.c_void_p, C.c_void_p]
@@ -104,11 +107,13 @@ class LampRef:
         return lamp_list(self.dense_world(scene), scene.roots, _tables(emission, None, None)[0], liquid_set(scene.mats))
 
     def render(self, scene: "orc.OracleScene", lamp, lamps, w: int, h: int, spp: int = 1, seed: int = 0, sample_base: int = 0, sun: float = 0.0,
-               setting=OFF, emission=None, polish=None, translucency=None, arrived=None):
+               setting=OFF, emission=None, polish=None, translucency=None, arrived=None, load=None):
         """(rgb [h, w, 3] f32, ids [h, w] u32) of samples sample_base .. sample_base + spp - 1.  lamp = (strength, max_geometry);
         lamps: the list (LAMP_DTYPE records, already cut to the cap); sun: vrt_set_sun_light's strength; setting: the camera
         sampling; the three 256-entry tables (None = zeros).  arrived: None, or a contiguous uint32 array of len(lamps) that
-        the frame adds to: per list entry, the lamp rays that arrived at it unoccluded."""
+        the frame adds to: per list entry, the lamp rays that arrived at it unoccluded.  load: None, or a contiguous uint8 array
+        [spp, max_ray_bounces, h, w] of zeros that the frame fills: what segment b of sample s of pixel (x, y) hands on —
+        LOAD_PATH: the path was appended for segment b + 1; LOAD_SUN: a sun ray was recorded; LOAD_LAMP: a lamp ray was."""
         e, p, t = _tables(emission, polish, translucency)
         rgb = np.zeros((h, w, 3), dtype=np.float32)
         ids = np.zeros((h, w), dtype=np.uint32)
@@ -118,10 +123,14 @@ class LampRef:
         lamps = np.ascontiguousarray(lamps, LAMP_DTYPE)
         if arrived is not None:
             assert arrived.dtype == np.uint32 and arrived.shape == (lamps.size,) and arrived.flags.c_contiguous and arrived.flags.writeable
-        self._lib.ref_render_path_lamp_arrivals(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, sun,
-                                                C.byref(cs), C.byref(ll), lamps.ctypes.data, lamps.size, w, h, spp, seed, sample_base,
-                                                rgb.ctypes.data, ids.ctypes.data, n.ctypes.data,
-                                                arrived.ctypes.data if arrived is not None and arrived.size else None)
+        if load is not None:
+            assert load.dtype == np.uint8 and load.shape == (max(spp, 1), int(scene.c.settings.max_ray_bounces), h, w)
+            assert load.flags.c_contiguous and load.flags.writeable and not load.any()
+        self._lib.ref_render_path_lamp_load(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, sun,
+                                            C.byref(cs), C.byref(ll), lamps.ctypes.data, lamps.size, w, h, spp, seed, sample_base,
+                                            rgb.ctypes.data, ids.ctypes.data, n.ctypes.data,
+                                            arrived.ctypes.data if arrived is not None and arrived.size else None,
+                                            load.ctypes.data if load is not None and load.size else None)
         self.counts = Counts(*(int(x) for x in n))
         return rgb, ids
 

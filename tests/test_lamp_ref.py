@@ -83,6 +83,40 @@ def test_a_pixel_is_its_samples_lights_in_sample_order_and_the_ids_are_the_off_f
         assert np.array_equal(_bits((total / F(spp)).astype(F)), _bits(rgb[py, px]))
 
 
+@pytest.mark.parametrize("bounces", [1, 4])
+def test_the_load_planes_sum_to_the_counts_and_change_no_output(lref, orc, bounces):
+    """render(load=...): per sample, segment and pixel, whether the path went on, a sun ray was recorded, a lamp ray was.  Their
+    sums are the frame's counts; a path that goes on into segment b + 1 went on into segment b; the last allowed segment hands no
+    path on; a frame that is not whole tiles leaves its border zero; and the frame itself is what it is without the planes."""
+    W, H, spp = 44, 28, 3
+    sc = scenes.c4((W, H), bounces=bounces)
+    o = orc.from_package_scene(sc)
+    _, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=1, seed=SEED)
+    e, p, t = _tables(plain_ids)
+    lamps = lref.lamps(o, e)
+    kw = dict(spp=spp, seed=SEED, sun=1.0, setting=(1.0, 0.05, 20.0), emission=e, polish=p, translucency=t)
+    want = lref.render(o, (1.0, 0.01), lamps, W, H, **kw)
+    want_counts = lref.counts
+    load = np.zeros((spp, bounces, H, W), np.uint8)
+    got = lref.render(o, (1.0, 0.01), lamps, W, H, load=load, **kw)
+    assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(got[1], want[1]) and lref.counts == want_counts
+    path, sun, lamp = ((load & bit) != 0 for bit in (lamp_ref.LOAD_PATH, lamp_ref.LOAD_SUN, lamp_ref.LOAD_LAMP))
+    assert int(path.sum()) == want_counts.bounce_segments
+    assert int(sun.sum()) == want_counts.sun_rays > 0
+    assert int(lamp.sum()) == want_counts.lamp_rays > 0
+    assert not (load & ~np.uint8(7)).any()
+    assert not path[:, -1].any()
+    assert not (path[:, 1:] & ~path[:, :-1]).any()
+    assert not ((sun | lamp)[:, 1:] & ~path[:, :-1]).any()   # (a light's ray leaves a hit of a segment that was traced)
+    assert not load[:, :, H & ~7:].any() and not load[:, :, :, W & ~7:].any()
+    if bounces > 1:
+        assert path[:, 0].any() and path[:, 1].any()
+    # with every setting off there is nothing but paths
+    load = np.zeros((1, bounces, H, W), np.uint8)
+    lref.render(o, (0.0, 0.0), lamps, W, H, spp=1, seed=SEED, load=load)
+    assert not (load & ~np.uint8(lamp_ref.LOAD_PATH)).any() and int(load.sum()) == lref.counts.bounce_segments
+
+
 def test_one_segment_paths_add_the_lamp_term_to_the_emission_term(lref, orc):
     """max_ray_bounces = 1 in the sealed room: a sample is its primary hit's emission term and, behind it, its lamp term.  Where
     no lamp ray arrives the light is the off frame's, bit for bit; where one does, the light is larger in every channel (the

@@ -263,7 +263,8 @@ __device__ __forceinline__ void append_light_rays(const B &buf, bool wants, uint
     base = __shfl(base, leader, 64);
     if (wants) {
         const uint32_t j = base + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-        if (j < buf.seg_cap) {   // (a segment holds what its workgroups can produce; never taken)
+        // (never false: a workgroup appends at most 256 records in a launch, and a segment has seg_cap / 256 producers)
+        if (j < buf.seg_cap) {
             const uint32_t i = seg * buf.seg_cap + j;
             buf.recs[i] = make_uint4(slot, __float_as_uint(so.x), __float_as_uint(so.y), __float_as_uint(so.z));
             buf.recs[buf.cap + i] = make_uint4(__float_as_uint(dir.x), __float_as_uint(dir.y), __float_as_uint(dir.z), w1);
