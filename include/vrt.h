@@ -669,6 +669,22 @@ int vrt_read_accel(vrt_ctx *ctx, uint32_t *grid, uint16_t *bricks);
  * enough to be kept without a directory.  VRT_ERR_STATE when the tables are not up to date or this world keeps none. */
 int vrt_read_march_cells(vrt_ctx *ctx, uint32_t *cells, uint32_t *direct);
 
+/* The sun marks (docs/NUMERICS.md "Lit stops"): a primary + shadow frame of the default march stops a shadow ray at a cell from
+ * which every ray towards the sun leaves the world through air; the marks live in the cell grid's air-leaf entries (which
+ * vrt_read_accel returns without them) and are made again, lazily, when the tables or the sun's position changed and have then stood
+ * still for four frames (frames in between trace their shadow rays to the end, as a context without marks does) — not when equal
+ * settings are rewritten.  *passes: lit passes launched so far; *min_leaf: the smallest leaf (in voxels) the last such frame's marks
+ * cover, 0 when it had none (sun inside the world or too low beside it, world too large for the step budget, VRT_SUN_MARKS=0);
+ * *lit_trips: the wave trip count up to which a mark stops a ray; lit[(8S)^3], x-major over the whole world: 1 for a lit cell of the
+ * table set the last frame used (synchronises).  Every pointer may be NULL. */
+int vrt_get_sun_marks(vrt_ctx *ctx, uint32_t *passes, uint32_t *min_leaf, uint32_t *lit_trips, uint8_t *lit);
+
+/* The trips the last frame that noted them took per tile (longest tiles first, above: a context that renders one frame at a time
+ * notes them on the second plain frame of a view at rest): cost[tiles], the wave's trips through its primary and its shadow march
+ * loop; cost[t] is tile t of this context's tiles, counted row by row over the screen's 8 x 8 tiles (a sharded context: its own tiles in that
+ * order), whatever order the frame launched them in (synchronises).  VRT_ERR_STATE when no frame has noted any. */
+int vrt_read_tile_cost(vrt_ctx *ctx, uint32_t *cost);
+
 /* Per-pixel march-loop iteration counts of the last frame (primary | shadow << 16); the frame must
  * have been rendered with opts.stats = 1.  Numeric twin of the reference's F2 step-count heat-map
  * (main.rs:368-370, ray_tracer.wgsl:311-314). */

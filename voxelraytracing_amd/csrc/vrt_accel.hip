@@ -11,7 +11,9 @@
 //               next decision (lo = leaf size - 1):
 //               air leaf at depth d <= 3     ->  0xFF800000 | lo          (lo 3, 7, 15 or 31: "step through, nothing to do"; the
 //                                                                          set bits make the entry the march's bit selector as
-//                                                                          it is, vrt_device.h kAirLeaf)
+//                                                                          it is, vrt_device.h kAirLeaf).  Bit 22 is the sun
+//                                                                          mark: written set, cleared by the lit pass below for a
+//                                                                          cell with a clear path to the sun (kAirUnlit)
 //               other leaf at depth d <= 3   ->  voxel << 16 | lo
 //               cell split at depth 3        ->  0x80000000 | brick * 64
 //               border / beyond the grid     ->  0                        (a raw buffer load past the end returns 0 too:
@@ -538,7 +540,80 @@ __global__ void __launch_bounds__(256) upload_batch_kernel(uint32_t *dst0, uint3
     if (tail < n) dst[tail] = last;
 }
 
+// The lit pass: the sun marks of the cell grid's air leaves (vrt_device.h kAirUnlit; docs/NUMERICS.md "Lit stops").
+//
+// A cell is LIT when a shadow ray whose position is anywhere in it meets nothing from there to the world's face.  The host has
+// picked the axis `a` on which the sun lies beyond the world (on the side `up`), and made sure that on the two other axes no ray
+// towards the sun moves more than 0.99 voxels per voxel of `a` (LitPass, vrt_uploads.hip: lit_plan).  A ray inside one layer of cells
+// (4 voxels of `a`) therefore moves less than one cell sideways — 0.99 * 4.001 voxels, the steps' 0.001 nudges and their roundings: 3.976, 0.024 voxels short
+// of 4 (docs/NUMERICS.md) — and only towards the sun's side of where it is: towards lower coordinates only if the sun is below some point of the cell
+// (widened by one voxel: a ray's positions stray from its line by the nudges, less than 500 * 0.001), towards higher ones only if
+// above.  So, for the cell's FOOTPRINT — itself and the up to three neighbours of its layer on the sun's side(s), nine where the sun
+// stands over the cell:
+//     lit(cell)  <=>  every footprint cell is an air leaf of at least `min_lo + 1` voxels (or outside the world), and
+//                     the cells behind the footprint in the next layer towards the sun are lit (or outside the world).
+// The layers are swept from the sun's side, so the next layer's marks are final when a layer reads them.  Every air leaf of the
+// grid gets its bit written, set or clear: nothing of an earlier sun or an earlier world survives a pass.
+struct LitPass {
+    uint32_t G;          // cells per axis
+    uint32_t axis;       // 0, 1, 2: x, y, z
+    uint32_t up;         // 1: the sun is beyond the world's high face of `axis`
+    uint32_t min_lo;     // leaves below min_lo + 1 voxels are never lit (the step budget: docs/NUMERICS.md)
+    float sun[3];        // settings.sun_pos - f32(world.min), as the shadow ray subtracts from it
+};
+
+// Layers first .. first + count - 1, counted from the sun's side.  count > 1: ONE workgroup walks them (a barrier between layers);
+// count == 1: any number of workgroups.
+__global__ void __launch_bounds__(1024) accel_lit_kernel(uint32_t *grid, LitPass lp, uint32_t first, uint32_t count) {
+    const uint32_t G = lp.G, G1 = G + 1u;
+    const uint32_t a = lp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // the two other axes, the lower one fastest
+    const size_t row = G1, slab = (size_t)G1 * G1;
+    const size_t sa = a == 0u ? 1u : a == 1u ? row : slab, su = u == 0u ? 1u : row, sv = v == 1u ? row : slab;   // strides of [z][y][x]
+    const float sun_u = u == 0u ? lp.sun[0] : lp.sun[1], sun_v = v == 1u ? lp.sun[1] : lp.sun[2];
+    for (uint32_t k = first; k < first + count; k++) {
+        const uint32_t ca = lp.up ? G - 1u - k : k;
+        const bool next_inside = lp.up ? ca + 1u < G : ca > 0u;
+        const size_t next_off = lp.up ? sa : (size_t)0 - sa;
+        for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < G * G; t += gridDim.x * blockDim.x) {
+            const uint32_t cu = t % G, cv = t / G;
+            const size_t at = ca * sa + cu * su + cv * sv;
+            const uint32_t e = grid[at];
+            if (e < kAirLeaf) continue;   // not an air leaf: no mark
+            // which way a ray in this cell can move on u and v
+            const float u0 = (float)(cu * 4u), v0 = (float)(cv * 4u);
+            const int ulo = sun_u <= u0 + 5.0f ? -1 : 0, uhi = sun_u >= u0 - 1.0f ? 1 : 0;
+            const int vlo = sun_v <= v0 + 5.0f ? -1 : 0, vhi = sun_v >= v0 - 1.0f ? 1 : 0;
+            bool lit = true;
+            for (int dv = vlo; dv <= vhi; dv++)
+                for (int du = ulo; du <= uhi; du++) {
+                    const uint32_t nu = cu + (uint32_t)du, nv = cv + (uint32_t)dv;
+                    if (nu >= G || nv >= G) continue;   // (also -1: unsigned) outside the world
+                    const size_t n = ca * sa + nu * su + nv * sv;
+                    const uint32_t own = grid[n];
+                    lit = lit && own >= kAirLeaf && (own & 31u) >= lp.min_lo;
+                    if (next_inside) {
+                        const uint32_t nx = grid[n + next_off];
+                        lit = lit && nx >= kAirLeaf && !(nx & kAirUnlit);
+                    }
+                }
+            grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
+        }
+        if (count > 1u) __syncthreads();   // (one workgroup: the layer's marks are written before the next layer reads them)
+    }
+}
+
 }  // namespace
+
+// The lit pass over the whole grid, on `st`.  Small grids: one launch of one workgroup that walks the layers; large ones: a launch per layer.
+void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], hipStream_t st) {
+    const LitPass lp{G, axis, up ? 1u : 0u, min_lo, {sun[0], sun[1], sun[2]}};
+    if (G <= 64u) {
+        hipLaunchKernelGGL(accel_lit_kernel, dim3(1), dim3(1024), 0, st, grid, lp, 0u, G);
+        return;
+    }
+    const uint32_t blocks = (G * G + 1023u) / 1024u;
+    for (uint32_t k = 0; k < G; k++) hipLaunchKernelGGL(accel_lit_kernel, dim3(blocks), dim3(1024), 0, st, grid, lp, k, 1u);
+}
 
 void launch_upload_batch(void *dst0, void *dst1, const void *pinned_ring, const UploadBatch &batch, uint32_t n_pieces, hipStream_t st) {
     if (!n_pieces) return;

@@ -118,6 +118,7 @@ void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t
                          uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *tail, uint16_t *bricks,
                          uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail, uint32_t block_cap, const uint32_t liquid[8],
                          const uint32_t *chunks, const uint32_t *extents, const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done);
+void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], hipStream_t st);
 }  // namespace vrt
 
 // Host-time profile of the frame path (VRT_HOST_PROF=1: printed at process exit): where the calling thread's microseconds per
@@ -279,6 +280,20 @@ struct vrt_ctx {
         uint32_t chunks_moved = 0;
         uint32_t chunk_builds = 0;              // chunks this set has rebuilt alone (vrt_accel_info reports the most advanced set's)
         uint64_t gen = 0;                       // what the set's device tables hold: a new value of c->tables_gen with every build, copy and chunk update (the lamp lists' key)
+        // the sun marks in d_grid's air leaves (vrt_accel.hip: the lit pass): what they were made for.  They hold while the set's
+        // tables are the ones they were made from (gen), the sun stands where it stood and the smallest marked leaf is the same
+        bool lit_valid = false;
+        uint64_t lit_gen = 0;
+        float lit_sun[3] = {0.f, 0.f, 0.f};
+        uint32_t lit_min_lo = 0;
+        // ... and what the frames ask for: the pass runs once kLitSettleFrames frames in a row have asked for the same marks
+        uint64_t want_gen = 0;
+        float want_sun[3] = {0.f, 0.f, 0.f};
+        uint32_t want_min_lo = 0, want_frames = 0;
+        Event ev_lit;                           // behind the set's last lit pass: a frame on another stream that reads the marks waits for it
+        bool lit_pending = false;               // ... recorded and not yet known to be over
+        hipStream_t lit_stream = nullptr;       // the stream the pass ran on (frames on it are ordered behind it as they are)
+        Event ev_lit_guard;                     // what the context's stream held when a pass on another stream was enqueued
         Event ev_updated;                       // behind this set's last chunk update (a reader of the node pool and chunk_roots)
         bool update_pending = false;            // ... recorded and not yet known to be over
     };
@@ -309,6 +324,9 @@ struct vrt_ctx {
     uint32_t path_pool_batches = 0;   // VRT_PATH_POOL_K = 4 | 5: the bounce waves' pools; 0: 5 for small worlds with two frames in flight, else 4
     uint32_t path_refill = 0;      // VRT_PATH_POOL_REFILL: idle lanes that send a bounce wave back to its pool (0: the default, 16)
     uint32_t accel_builds = 0;
+    bool sun_marks = true;         // VRT_SUN_MARKS=0: shadow rays never stop at lit cells (the A/B of profiles/DECISIONS.md)
+    uint32_t lit_passes = 0;       // lit passes launched (vrt_get_sun_marks)
+    uint32_t lit_last_min_leaf = 0, lit_last_trips = 0;   // of the last one-launch shadow frame: 0 = its marks were off
     // longest tiles first (vrt_kernels.hip: tile_order_*), for a context that renders one frame at a time
     // (vrt_set_frames_in_flight(1)) and whose view is at rest: the second plain frame of an unchanged view (camera, settings,
     // world, materials) notes its tiles' march-loop trips, right behind it on the stream four small launches turn them into the
@@ -563,6 +581,10 @@ VRT_HIDDEN int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes
 VRT_HIDDEN void mark_all_dirty(vrt_ctx *c);
 VRT_HIDDEN int ensure_accel_world(vrt_ctx *c);
 VRT_HIDDEN int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st);
+// The sun marks of table set k for the sun at `sun_local`, made on `st` if the set does not hold them; *below / *trips: what the
+// frame's shadow rays are given (FrameParams.shadow_below / lit_trips) — vrt::kAirLeaf / 0 when this world and sun get no marks
+// `shares`: the frame is of another frame set than the table set's own (tabs[0] read from a second stream)
+VRT_HIDDEN int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips);
 VRT_HIDDEN size_t chunk_dir_entries(uint32_t S);
 VRT_HIDDEN size_t direct_cell_entries(uint32_t S);
 // vrt_lamp.hip: the frame set's lamp list, rebuilt on `st` if what it was built from has changed (the frame's tables are up to date

@@ -29,8 +29,15 @@ constexpr uint32_t kCamNotFinite = 1u, kCamOnPlane = 2u, kCamOutside = 4u;   // 
 constexpr uint32_t kAirLeaf = 0xFF800000u;
 // ... of a cell split at depth 3: 0x80000000 | brick * 64 — below the air leaves: the pool holds fewer than 0x1FE0000 bricks
 __host__ __device__ inline bool is_split_entry(uint32_t e) { return (int32_t)e < 0 && e < kAirLeaf; }
+// Bit 22 of an air leaf's entry is the sun mark (vrt_accel.hip: the lit pass): SET = not known to be lit, CLEAR = every ray from
+// this cell towards the sun meets nothing.  The builds write air leaves with the bit set; the lit pass clears it.  Nothing else reads
+// it: a voxel coordinate never reaches bit 12 (grid_dim <= 800), the direction masks of the exit-plane insert carry a zero there,
+// and everyone who asks `e >= kAirLeaf` or `e & 31` gets the answer they got.  A shadow ray asks `e < kLitBelow` instead of
+// `e < kAirLeaf` (FrameParams.shadow_below), which a lit air leaf answers like a split cell: the lane leaves the fast path, and stops.
+constexpr uint32_t kAirUnlit = 1u << 22;
+constexpr uint32_t kLitBelow = kAirLeaf | kAirUnlit;
 // a march cell's first word (lo of an air leaf, voxel << 16 | lo, 0x80000000 | brick * 64) as the cell grid holds it
-__host__ __device__ inline uint32_t grid_entry(uint32_t x) { return x - 1u < 31u ? (kAirLeaf | x) : x; }
+__host__ __device__ inline uint32_t grid_entry(uint32_t x) { return x - 1u < 31u ? (kAirLeaf | kAirUnlit | x) : x; }
 
 // One output texel: {r, g, b as f32 bits, id word}. 16 B so that a wave stores 1 KiB contiguously.
 using Texel = uint4;
@@ -99,8 +106,12 @@ struct FrameParams {
                              // in what was padding: the other fields keep their offsets)
     // A hole of 20 bytes where the fields of a deleted launch (round 5's window experiment) lay: the kernels read this struct
     // from the kernarg segment, so with every later offset where it was their code is the same instruction for instruction
-    // (profiles/path_plan_isa_diff.txt).  The next change that alters these kernels' code anyway takes the hole out.
-    uint32_t layout_hole[5];
+    // (profiles/path_plan_isa_diff.txt).  (The sun marks' two words went into the hole for the same reason: the one-launch kernel's code
+    // changed with them, the path trace's kernels kept theirs.)  A change that alters all of these kernels' code takes the rest out.
+    // (two of its words are taken: what a shadow ray of the one-launch frame compares an entry against — kLitBelow while this table
+    // set's sun marks hold for this sun, else kAirLeaf — and the wave trip count up to which a lit entry may stop it, vrt_march.h (t))
+    uint32_t shadow_below, lit_trips;
+    uint32_t layout_hole[3];
     uint32_t n_nodes, n_roots;
     uint32_t width, height;
     uint32_t tiles_x, tiles_total;

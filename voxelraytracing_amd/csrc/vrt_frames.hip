@@ -220,6 +220,9 @@ void fill_uniforms(const vrt_ctx *c, vrt::FrameParams &P) {
     P.liquid_lo = c->liquid_lo;
     P.liquid_span = c->liquid_span;
 
+    P.shadow_below = vrt::kAirLeaf;   // (no sun marks: vrt_render hands them to the frames that take them)
+    P.lit_trips = 0u;
+
     P.ndc_x = c->d_ndc;
     P.ndc_y = c->d_ndc + c->width;
     cam_sun_dir(c, P.cam_sun_dir);
@@ -518,6 +521,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
         if (v >= 0 && v <= (long)kMarchDirectMaxS) c->march_direct_max_s = (uint32_t)v;
     }
     if (const char *e = getenv("VRT_TILE_ORDER")) c->tile_lpt = e[0] != '0';
+    if (const char *e = getenv("VRT_SUN_MARKS")) c->sun_marks = e[0] != '0';
     // (0: screen order while the view moves — profiles/r05_tile_order_moving.txt)
     if (const char *e = getenv("VRT_TILE_ORDER_MOVING")) c->tile_lpt_moving = e[0] != '0' ? 1u : 0u;
     c->mov_any_size = getenv("VRT_TILE_ORDER_MOVING") != nullptr;   // (asked for by name: also for frames larger than kMovingTilesMax)
@@ -752,6 +756,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     P.steps = o.stats == 1u ? c->sz.d_steps : nullptr;
     P.clock = o.stats == 2u ? c->d_clock : nullptr;
     fill_uniforms(c, P);
+    // the shadow rays of the one-launch frame stop at lit cells: this set's sun marks, made now if the tables or the sun changed
+    if (P.grid && plan.shadow && plan.variant == 0u && !plan.kstats) {
+        c->lit_last_min_leaf = 0u;
+        if (c->sun_marks) VRT_TRY(ensure_sun_marks(c, tab, f.st, shares, P.sun_local, &P.shadow_below, &P.lit_trips));
+        c->lit_last_trips = P.lit_trips;
+    }
     if (plan.fuse_present) {
         VRT_TRY(screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height));
         P.screen = reinterpret_cast<uint32_t *>(c->d_screen[f.slot].get());

@@ -504,8 +504,158 @@ __device__ __forceinline__ bool finite3(V3 v) {
            ((__float_as_uint(v.z) & 0x7F800000u) != 0x7F800000u);
 }
 
+// The grid march's inner loop (march_grid below, (r)): the text of its asm statement, as a macro because the loop exists twice — a
+// primary ray's, and a shadow ray's with two more pieces on its split path ((t): LIT_TEST where the deciding lanes are known, LIT_PARK
+// out of line) — and an asm statement takes nothing but a string literal.  What the loop does and why is told where it is used.
+#define VRT_MARCH_LOOP(LIT_TEST, LIT_PARK) \
+                "s_mov_b64 %[sd], 0\n\t" \
+                "s_setprio 1\n\t"                                           /* (the waves in the loop before the ones that set up or shade: + 1 %) */ \
+                "v_cmp_ne_u32_e64 %[sw], %[plain], %[below]\n"               /* lanes in water, a careful wave: the general step's */ \
+                ".Lvrt_step_%=:\n\t" \
+                "v_ashrrev_i32_e32 %[t1], 2, %[vy]\n\t" \
+                "v_and_b32_e32 %[t2], -4, %[vx]\n\t" \
+                "v_mad_i32_i24 %[t1], %[t1], %[row], %[t2]\n\t" \
+                "v_ashrrev_i32_e32 %[t0], 2, %[vz]\n\t" \
+                "v_mad_i32_i24 %[t0], %[t0], %[slab], %[t1]\n\t" \
+                "buffer_load_dword %[e], %[t0], %[desc], 0 offen\n\t" \
+                "s_waitcnt vmcnt(0)\n\t" \
+                "v_cmp_lt_u32_e32 vcc, %[e], %[below]\n\t" \
+                "s_cbranch_vccnz .Lvrt_split_%=\n"                         /* some lane is not in a plain air leaf */ \
+                ".Lvrt_planes_%=:\n\t" \
+                "v_bitop3_b32 %[ax], %[e], %[mx], %[vx] bitop3:0xca\n\t"     /* (h), (q): the exit planes under the bits of 2^23 */ \
+                "v_bitop3_b32 %[ay], %[e], %[my], %[vy] bitop3:0xca\n\t" \
+                "v_bitop3_b32 %[az], %[e], %[mz], %[vz] bitop3:0xca\n\t" \
+                "v_add_f32_e32 %[ax], %[cx], %[ax]\n\t" \
+                "v_add_f32_e32 %[ay], %[cy], %[ay]\n\t" \
+                "v_add_f32_e32 %[az], %[cz], %[az]\n\t" \
+                "v_sub_f32_e32 %[ax], %[ax], %[px]\n\t" \
+                "v_sub_f32_e32 %[ay], %[ay], %[py]\n\t" \
+                "v_sub_f32_e32 %[az], %[az], %[pz]\n\t" \
+                "v_mul_f32_e64 %[ax], |%[ax]|, %[ux]\n\t"                    /* (b'') */ \
+                "v_mul_f32_e64 %[ay], |%[ay]|, %[uy]\n\t" \
+                "v_mul_f32_e64 %[az], |%[az]|, %[uz]\n\t" \
+                "v_min3_f32 %[st], %[ax], %[ay], %[az]\n\t"                  /* (p) */ \
+                "v_cmp_nlt_f32_e32 vcc, 0, %[st]\n\t" \
+                "s_cbranch_vccnz .Lvrt_zero_%=\n"                            /* some lane's smallest distance is zero or NaN: (c') */ \
+                ".Lvrt_move_%=:\n\t" \
+                /* (the half-rate instructions — compares, selects, conversions — each between two plain ones: next to a plain instruction */ \
+                /* a half-rate one issues in a plain one's time, next to another half-rate one it takes its own: tools/valu_rates.hip k_mix_*) */ \
+                /* (a VALU's write of vcc or of an SGPR pair is read by a VALU two wait states later at the earliest — nothing pads */ \
+                /* inside this string: each compare has its own flags, three instructions or more ahead of its select) */ \
+                "v_cmp_eq_f32_e32 vcc, %[st], %[ax]\n\t" \
+                "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t"                /* step + 0.001 */ \
+                "v_cmp_eq_f32_e64 %[fy], %[st], %[ay]\n\t" \
+                "v_add_f32_e32 %[tl], %[tl], %[st]\n\t" \
+                "v_cndmask_b32_e32 %[t1], %[st], %[t0], vcc\n\t" \
+                "v_mul_f32_e32 %[t1], %[dx], %[t1]\n\t" \
+                "v_cmp_eq_f32_e64 %[fz], %[st], %[az]\n\t" \
+                "v_add_f32_e32 %[px], %[px], %[t1]\n\t" \
+                "v_cndmask_b32_e64 %[t2], %[st], %[t0], %[fy]\n\t" \
+                "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t" \
+                "v_cndmask_b32_e64 %[t0], %[st], %[t0], %[fz]\n\t" \
+                "v_add_f32_e32 %[py], %[py], %[t2]\n\t" \
+                "v_cvt_flr_i32_f32_e32 %[vx], %[px]\n\t" \
+                "v_mul_f32_e32 %[t0], %[dz], %[t0]\n\t" \
+                "v_cvt_flr_i32_f32_e32 %[vy], %[py]\n\t" \
+                "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t" \
+                "v_cvt_flr_i32_f32_e32 %[vz], %[pz]\n\t" \
+                "s_add_u32 %[it], %[it], 1\n\t"                              /* (carries when the count reaches kMaxSteps, :220) */ \
+                "s_cbranch_scc0 .Lvrt_step_%=\n\t" \
+                "s_branch .Lvrt_out_%=\n" \
+                ".Lvrt_zero_%=:\n\t" \
+                "v_add_u32_e32 %[t0], -1, %[ax]\n\t" \
+                "v_add_u32_e32 %[t1], -1, %[ay]\n\t" \
+                "v_add_u32_e32 %[t2], -1, %[az]\n\t" \
+                "v_min3_u32 %[t0], %[t0], %[t1], %[t2]\n\t" \
+                "v_add_u32_e32 %[st], 1, %[t0]\n\t" \
+                "s_branch .Lvrt_move_%=\n" \
+                /* (s) Some lane is not in a plain air leaf (vcc).  Two steps in five of C2's are that for one reason only: plain lanes in */ \
+                /* split cells, on voxels of their bricks that are air (a ray close to a surface walks leaves of one and two voxels) — */ \
+                /* and for those the step is the one above with the brick's entry as the selector.  One step in eleven has a lane that */ \
+                /* STOPS — at the border (entry 0), on a leaf or a brick's voxel that is solid: such a lane is parked (off the exec */ \
+                /* mask, its registers as they are, the voxel it stopped on recorded) and the others march on; `parked` tells the */ \
+                /* caller, which breaks out of its loop for it.  What is left for the general step: a lane in water or a careful wave */ \
+                /* (the threshold is not kAirLeaf) and a voxel that is a liquid — the loop leaves with `e` as it was loaded. */ \
+                ".Lvrt_split_%=:\n\t" \
+                "s_cmp_lg_u64 %[sw], 0\n\t"                                 /* (a lane in water, a careful wave: asked once, at the loop's entry) */ \
+                "s_cbranch_scc1 .Lvrt_out_%=\n\t" \
+                "s_and_saveexec_b64 %[sx], vcc\n\t"                         /* the lanes with something to decide: border, leaf, split cell */ \
+                LIT_TEST                                                    /* (t) a shadow ray's loop: ... or a lit air leaf */ \
+                "v_cmp_gt_i32_e32 vcc, 0, %[e]\n\t" \
+                "s_and_saveexec_b64 %[sa], vcc\n\t"                         /* the lanes in split cells */ \
+                "s_andn2_b64 %[sn], %[sa], exec\n\t"                        /* the others: at the border, in a leaf that is not air */ \
+                "s_cbranch_execz .Lvrt_decide_%=\n\t" \
+                "v_lshlrev_b32_e32 %[t0], 2, %[vy]\n\t"                     /* u = (x&3) | (y&3) << 2 | (z&3) << 4 */ \
+                "v_lshlrev_b32_e32 %[t1], 4, %[vz]\n\t" \
+                "v_bitop3_b32 %[t0], 3, %[vx], %[t0] bitop3:0xca\n\t" \
+                "v_bitop3_b32 %[t0], 15, %[t0], %[t1] bitop3:0xca\n\t"      /* (z's upper bits on top) */ \
+                "v_bitop3_b32 %[t0], %[kbrick], %[e], %[t0] bitop3:0xca\n\t"  /* brick * 64 from the entry (bits 6..30), u below: the 16-bit entry's index */ \
+                "buffer_load_ushort %[t1], %[t0], %[bdesc], 0 idxen\n\t" \
+                "s_waitcnt vmcnt(0)\n\t" \
+                "v_cmp_lt_u32_e32 vcc, 1, %[t1]\n\t"                        /* voxel << 1 | lo: a voxel that is not air */ \
+                "s_or_b64 %[sb], %[sn], vcc\n\t" \
+                "s_cbranch_scc1 .Lvrt_decide_%=\n\t"                        /* someone stops, or meets a liquid */ \
+                "v_and_or_b32 %[e], %[t1], 1, %[kair]\n\t"                  /* all air: the selector of the voxel's leaf (one voxel or two) */ \
+                "s_mov_b64 exec, %[sx]\n\t" \
+                "s_branch .Lvrt_planes_%=\n" \
+                ".Lvrt_decide_%=:\n\t" \
+                "v_lshrrev_b32_e32 %[t2], 1, %[t1]\n\t"                     /* the voxel of a brick's entry ... */ \
+                "s_mov_b64 exec, %[sn]\n\t" \
+                "v_lshrrev_b32_e32 %[t2], 16, %[e]\n\t"                     /* ... of a leaf (the border: 0) */ \
+                "s_mov_b64 exec, %[sa]\n\t" \
+                "v_subrev_u32_e32 %[t0], %[liqlo], %[t2]\n\t" \
+                "v_cmp_ge_u32_e32 vcc, %[liqspan], %[t0]\n\t"               /* a liquid (air is none: liqlo >= 1): the general step's */ \
+                "s_cbranch_vccnz .Lvrt_leave_%=\n\t" \
+                "v_cmp_ne_u32_e32 vcc, 0, %[t2]\n\t"                        /* solid */ \
+                "v_cmp_eq_u32_e64 %[sb], 0, %[e]\n\t"                       /* the border */ \
+                "s_or_b64 %[sb], %[sb], vcc\n\t"                            /* the lanes that stop here */ \
+                "s_or_b64 %[sd], %[sd], %[sb]\n\t" \
+                "s_andn2_b64 exec, %[sa], %[sb]\n\t"                        /* split cells, air voxels: */ \
+                "v_and_or_b32 %[e], %[t1], 1, %[kair]\n\t"                  /* the selector of the voxel's leaf */ \
+                "s_mov_b64 exec, %[sb]\n\t" \
+                "v_mov_b32_e32 %[vox], %[t2]\n\t"                           /* what a parked lane stopped on */ \
+                "s_andn2_b64 exec, %[sx], %[sb]\n\t"                        /* the lanes that march on */ \
+                "s_cbranch_scc1 .Lvrt_planes_%=\n\t" \
+                "s_branch .Lvrt_out_%=\n"                                   /* none: every lane is parked */ \
+                LIT_PARK \
+                ".Lvrt_leave_%=:\n\t" \
+                "s_mov_b64 exec, %[sx]\n" \
+                ".Lvrt_out_%=:\n\t" \
+                "s_setprio 0\n\t" \
+                "s_or_b64 exec, exec, %[sd]\n\t" \
+                "v_cndmask_b32_e64 %[parked], 0, 1, %[sd]"
+#define VRT_MARCH_LOOP_OPERANDS \
+                : [px] "+v"(pos.x), [py] "+v"(pos.y), [pz] "+v"(pos.z), [tl] "+v"(total_len), [vx] "+v"(vx), [vy] "+v"(vy), [vz] "+v"(vz), \
+                  [st] "+v"(step), [ax] "+v"(adx), [ay] "+v"(ady), [az] "+v"(adz), [e] "=&v"(e), [it] "+s"(trips), \
+                  [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [sa] "=&s"(sa), [sb] "=&s"(sb), [sx] "=&s"(sx), [sd] "=&s"(sd), [sn] "=&s"(sn), [sw] "=&s"(sw), \
+                  [fy] "=&s"(fy), [fz] "=&s"(fz), \
+                  [vox] "+v"(voxel), [parked] "=&v"(parked) \
+                : [mx] "v"(mxm), [my] "v"(mym), [mz] "v"(mzm), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [ux] "v"(ux), [uy] "v"(uy), [uz] "v"(uz), \
+                  [dx] "v"(dir.x), [dy] "v"(dir.y), [dz] "v"(dir.z), [below] "v"(slow_below), [desc] "s"(gb), [row] "s"(row_bytes), [slab] "s"(slab_bytes), \
+                  [bdesc] "s"(bb16), [kair] "s"(kAirLeaf), [plain] "s"(plain_s), [kbrick] "s"(0x7FFFFFC0u), [liqlo] "s"(liq_lo), [liqspan] "s"(liq_span) \
+                : "vcc", "scc", "memory"
+// (t) What a shadow ray's instance of the loop adds (march_grid<.., SHADOW>; the primary ray's has neither piece).  A shadow lane's
+// threshold is kLitBelow while the table set's sun marks hold, so a LIT air leaf — bit 22 clear — arrives on the split path with the
+// lanes that have something to decide.  One compare finds those lanes; they are parked like lanes at the border (off the exec mask
+// and off the marchers' mask, on the parked mask), with `e` kept and `voxel` left 0: that is how the code behind the loop tells them
+// from a lane that stopped on something.  The fast path above is the same 37 vector instructions.
+#define VRT_LIT_TEST \
+                "v_cmp_le_u32_e32 vcc, %[kair], %[e]\n\t"                   /* the deciding lanes whose entry is an air leaf: lit */ \
+                "s_cbranch_vccnz .Lvrt_lit_%=\n"                            /* (out of line: a lane meets this once) */ \
+                ".Lvrt_cells_%=:\n\t"
+#define VRT_LIT_PARK \
+                ".Lvrt_lit_%=:\n\t" \
+                "s_or_b64 %[sd], %[sd], vcc\n\t"                            /* parked */ \
+                "s_andn2_b64 %[sx], %[sx], vcc\n\t"                         /* ... and no marchers any more */ \
+                "s_andn2_b64 exec, exec, vcc\n\t"                           /* the rest decide as ever (none: every mask below comes out empty) */ \
+                "s_branch .Lvrt_cells_%=\n"
+
 // CAMERA: `origin` is the camera's (a primary ray): what the march asks of the origin alone is FrameParams.cam_origin_facts, the host's.
-template <bool STATS, bool CAMERA = false>
+// SHADOW: the ray is the one-launch frame's shadow ray, of which the frame reads `hit` and nothing else (vrt_tile.h: trace_tile).  Such a
+// ray may stop at a lit air leaf (t): every ray from that cell towards the sun leaves the world through air (vrt_accel.hip: the lit
+// pass), so the reference's ray misses — provided it does not run out of its kMaxSteps lookups on the way, which P.lit_trips sees
+// to (docs/NUMERICS.md, "Lit stops").  The counting kernels (STATS) never stop early: their counts are the reference's.
+template <bool STATS, bool CAMERA = false, bool SHADOW = false>
 __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const uint32_t *s_liquid, V3 origin, V3 dir) {
     MarchResult R;
     R.hit = false;
@@ -546,7 +696,9 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // is exact (integers below 2^24).  Two full-rate instructions for v_cvt_f32_i32's half-rate one and the integer increment.
     // (Until round 6 the "+ 1" and the exponent were an integer subtraction of their own: three instructions per step.)
     constexpr uint32_t kTwo23 = 0x4B000000u;
-    uint32_t mxm = kTwo23 | (mx ? 0x007FFFFFu : 0u), mym = kTwo23 | (my ? 0x007FFFFFu : 0u), mzm = kTwo23 | (mz ? 0x007FFFFFu : 0u);
+    // (bit 22 of the masks is zero: an air leaf's entry may carry the sun mark there — vrt_device.h kAirUnlit — and the insert must
+    // not take it for a bit of the plane; only the selector's low five bits and its top nine ever select anything)
+    uint32_t mxm = kTwo23 | (mx ? 0x003FFFFFu : 0u), mym = kTwo23 | (my ? 0x003FFFFFu : 0u), mzm = kTwo23 | (mz ? 0x003FFFFFu : 0u);
     float cx = mx ? -8388607.0f : -8388608.0f, cy = my ? -8388607.0f : -8388608.0f, cz = mz ? -8388607.0f : -8388608.0f;
     asm("" : "+v"(mxm), "+v"(mym), "+v"(mzm));   // (held in registers)
 
@@ -575,8 +727,16 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // lane of a `careful` wave (the shader's own bounds test, the lookup repeated at its i32(f32) coordinates)
     // (as a threshold: the air leaves are the highest entries there are — kAirLeaf | lo — so "not an air leaf" is e < kAirLeaf,
     // and a lane that has more to do compares against a number above every entry: one compare asks the question)
-    constexpr uint32_t kPlain = kAirLeaf, kSlow = 0xFFFFFFFFu;
-    uint32_t slow_below = careful ? kSlow : kPlain;
+    constexpr uint32_t kSlow = 0xFFFFFFFFu;
+    // (t) a shadow ray's plain threshold is the frame's: kLitBelow while the sun marks hold — a lit air leaf is then below it, and
+    // stops the lane — else kAirLeaf, as for every other ray.  Wave-uniform.  The marks stop a lane only while the wave has made
+    // fewer than `limit` trips (P.lit_trips: what is left of kMaxSteps then covers the way out of the world); past that a lit
+    // leaf is air like any other
+    constexpr bool kLitStops = SHADOW && !STATS;
+    uint32_t plain_below = kLitStops ? P.shadow_below : kAirLeaf;
+    uint32_t limit = (kLitStops && plain_below != kAirLeaf) ? P.lit_trips : kMaxSteps;
+    bool lit_stop = false;
+    uint32_t slow_below = careful ? kSlow : plain_below;
     float total_len = 0.0f;
     uint32_t iter = 0u;      // wave-uniform trip count (loop control)
     uint32_t looked_up = 0u; // STATS: node lookups of this lane (:221) — one less than its trips if it left through the border
@@ -623,6 +783,11 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // returns.  Same steps in the same order for every lane; `iter` counts them for the whole wave.
     for (;;) {
         uint32_t e;
+        if (kLitStops && iter >= limit && limit != kMaxSteps) {   // (wave-uniform) the lit stops' budget is spent: (t)
+            limit = kMaxSteps;
+            plain_below = kAirLeaf;
+            if (slow_below != kSlow) slow_below = kAirLeaf;
+        }
         if constexpr (!STATS) {
             // (r) The inner loop as the instructions themselves.  What the compiler makes of the C++ below is the same vector
             // instructions, but it wraps every step in seven scalar instructions, four branches (three taken) and six s_nop /
@@ -639,134 +804,19 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             uint32_t t0, t1, t2;
             unsigned long long sa, sb, sx, sd, sn, sw, fy, fz;
             uint32_t parked;
-            uint32_t trips = __builtin_amdgcn_readfirstlane(iter) - kMaxSteps;   // (wave-uniform already: tells the compiler)
-            asm volatile(
-                "s_mov_b64 %[sd], 0\n\t"
-                "s_setprio 1\n\t"                                           // (the waves in the loop before the ones that set up or shade: + 1 %)
-                "v_cmp_ne_u32_e64 %[sw], %[kair], %[below]\n"                // lanes in water, a careful wave: the general step's
-                ".Lvrt_step_%=:\n\t"
-                "v_ashrrev_i32_e32 %[t1], 2, %[vy]\n\t"
-                "v_and_b32_e32 %[t2], -4, %[vx]\n\t"
-                "v_mad_i32_i24 %[t1], %[t1], %[row], %[t2]\n\t"
-                "v_ashrrev_i32_e32 %[t0], 2, %[vz]\n\t"
-                "v_mad_i32_i24 %[t0], %[t0], %[slab], %[t1]\n\t"
-                "buffer_load_dword %[e], %[t0], %[desc], 0 offen\n\t"
-                "s_waitcnt vmcnt(0)\n\t"
-                "v_cmp_lt_u32_e32 vcc, %[e], %[below]\n\t"
-                "s_cbranch_vccnz .Lvrt_split_%=\n"                         // some lane is not in a plain air leaf
-                ".Lvrt_planes_%=:\n\t"
-                "v_bitop3_b32 %[ax], %[e], %[mx], %[vx] bitop3:0xca\n\t"     // (h), (q): the exit planes under the bits of 2^23
-                "v_bitop3_b32 %[ay], %[e], %[my], %[vy] bitop3:0xca\n\t"
-                "v_bitop3_b32 %[az], %[e], %[mz], %[vz] bitop3:0xca\n\t"
-                "v_add_f32_e32 %[ax], %[cx], %[ax]\n\t"
-                "v_add_f32_e32 %[ay], %[cy], %[ay]\n\t"
-                "v_add_f32_e32 %[az], %[cz], %[az]\n\t"
-                "v_sub_f32_e32 %[ax], %[ax], %[px]\n\t"
-                "v_sub_f32_e32 %[ay], %[ay], %[py]\n\t"
-                "v_sub_f32_e32 %[az], %[az], %[pz]\n\t"
-                "v_mul_f32_e64 %[ax], |%[ax]|, %[ux]\n\t"                    // (b'')
-                "v_mul_f32_e64 %[ay], |%[ay]|, %[uy]\n\t"
-                "v_mul_f32_e64 %[az], |%[az]|, %[uz]\n\t"
-                "v_min3_f32 %[st], %[ax], %[ay], %[az]\n\t"                  // (p)
-                "v_cmp_nlt_f32_e32 vcc, 0, %[st]\n\t"
-                "s_cbranch_vccnz .Lvrt_zero_%=\n"                            // some lane's smallest distance is zero or NaN: (c')
-                ".Lvrt_move_%=:\n\t"
-                // (the half-rate instructions — compares, selects, conversions — each between two plain ones: next to a plain instruction
-                // a half-rate one issues in a plain one's time, next to another half-rate one it takes its own: tools/valu_rates.hip k_mix_*)
-                // (a VALU's write of vcc or of an SGPR pair is read by a VALU two wait states later at the earliest — nothing pads
-                // inside this string: each compare has its own flags, three instructions or more ahead of its select)
-                "v_cmp_eq_f32_e32 vcc, %[st], %[ax]\n\t"
-                "v_add_f32_e32 %[t0], 0x3a83126f, %[st]\n\t"                // step + 0.001
-                "v_cmp_eq_f32_e64 %[fy], %[st], %[ay]\n\t"
-                "v_add_f32_e32 %[tl], %[tl], %[st]\n\t"
-                "v_cndmask_b32_e32 %[t1], %[st], %[t0], vcc\n\t"
-                "v_mul_f32_e32 %[t1], %[dx], %[t1]\n\t"
-                "v_cmp_eq_f32_e64 %[fz], %[st], %[az]\n\t"
-                "v_add_f32_e32 %[px], %[px], %[t1]\n\t"
-                "v_cndmask_b32_e64 %[t2], %[st], %[t0], %[fy]\n\t"
-                "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t"
-                "v_cndmask_b32_e64 %[t0], %[st], %[t0], %[fz]\n\t"
-                "v_add_f32_e32 %[py], %[py], %[t2]\n\t"
-                "v_cvt_flr_i32_f32_e32 %[vx], %[px]\n\t"
-                "v_mul_f32_e32 %[t0], %[dz], %[t0]\n\t"
-                "v_cvt_flr_i32_f32_e32 %[vy], %[py]\n\t"
-                "v_add_f32_e32 %[pz], %[pz], %[t0]\n\t"
-                "v_cvt_flr_i32_f32_e32 %[vz], %[pz]\n\t"
-                "s_add_u32 %[it], %[it], 1\n\t"                              // (carries when the count reaches kMaxSteps, :220)
-                "s_cbranch_scc0 .Lvrt_step_%=\n\t"
-                "s_branch .Lvrt_out_%=\n"
-                ".Lvrt_zero_%=:\n\t"
-                "v_add_u32_e32 %[t0], -1, %[ax]\n\t"
-                "v_add_u32_e32 %[t1], -1, %[ay]\n\t"
-                "v_add_u32_e32 %[t2], -1, %[az]\n\t"
-                "v_min3_u32 %[t0], %[t0], %[t1], %[t2]\n\t"
-                "v_add_u32_e32 %[st], 1, %[t0]\n\t"
-                "s_branch .Lvrt_move_%=\n"
-                // (s) Some lane is not in a plain air leaf (vcc).  Two steps in five of C2's are that for one reason only: plain lanes in
-                // split cells, on voxels of their bricks that are air (a ray close to a surface walks leaves of one and two voxels) —
-                // and for those the step is the one above with the brick's entry as the selector.  One step in eleven has a lane that
-                // STOPS — at the border (entry 0), on a leaf or a brick's voxel that is solid: such a lane is parked (off the exec
-                // mask, its registers as they are, the voxel it stopped on recorded) and the others march on; `parked` tells the
-                // caller, which breaks out of its loop for it.  What is left for the general step: a lane in water or a careful wave
-                // (the threshold is not kAirLeaf) and a voxel that is a liquid — the loop leaves with `e` as it was loaded.
-                ".Lvrt_split_%=:\n\t"
-                "s_cmp_lg_u64 %[sw], 0\n\t"                                 // (a lane in water, a careful wave: asked once, at the loop's entry)
-                "s_cbranch_scc1 .Lvrt_out_%=\n\t"
-                "s_and_saveexec_b64 %[sx], vcc\n\t"                         // the lanes with something to decide: border, leaf, split cell
-                "v_cmp_gt_i32_e32 vcc, 0, %[e]\n\t"
-                "s_and_saveexec_b64 %[sa], vcc\n\t"                         // the lanes in split cells
-                "s_andn2_b64 %[sn], %[sa], exec\n\t"                        // the others: at the border, in a leaf that is not air
-                "s_cbranch_execz .Lvrt_decide_%=\n\t"
-                "v_lshlrev_b32_e32 %[t0], 2, %[vy]\n\t"                     // u = (x&3) | (y&3) << 2 | (z&3) << 4
-                "v_lshlrev_b32_e32 %[t1], 4, %[vz]\n\t"
-                "v_bitop3_b32 %[t0], 3, %[vx], %[t0] bitop3:0xca\n\t"
-                "v_bitop3_b32 %[t0], 15, %[t0], %[t1] bitop3:0xca\n\t"      // (z's upper bits on top)
-                "v_bitop3_b32 %[t0], %[kbrick], %[e], %[t0] bitop3:0xca\n\t"  // brick * 64 from the entry (bits 6..30), u below: the 16-bit entry's index
-                "buffer_load_ushort %[t1], %[t0], %[bdesc], 0 idxen\n\t"
-                "s_waitcnt vmcnt(0)\n\t"
-                "v_cmp_lt_u32_e32 vcc, 1, %[t1]\n\t"                        // voxel << 1 | lo: a voxel that is not air
-                "s_or_b64 %[sb], %[sn], vcc\n\t"
-                "s_cbranch_scc1 .Lvrt_decide_%=\n\t"                        // someone stops, or meets a liquid
-                "v_and_or_b32 %[e], %[t1], 1, %[kair]\n\t"                  // all air: the selector of the voxel's leaf (one voxel or two)
-                "s_mov_b64 exec, %[sx]\n\t"
-                "s_branch .Lvrt_planes_%=\n"
-                ".Lvrt_decide_%=:\n\t"
-                "v_lshrrev_b32_e32 %[t2], 1, %[t1]\n\t"                     // the voxel of a brick's entry ...
-                "s_mov_b64 exec, %[sn]\n\t"
-                "v_lshrrev_b32_e32 %[t2], 16, %[e]\n\t"                     // ... of a leaf (the border: 0)
-                "s_mov_b64 exec, %[sa]\n\t"
-                "v_subrev_u32_e32 %[t0], %[liqlo], %[t2]\n\t"
-                "v_cmp_ge_u32_e32 vcc, %[liqspan], %[t0]\n\t"               // a liquid (air is none: liqlo >= 1): the general step's
-                "s_cbranch_vccnz .Lvrt_leave_%=\n\t"
-                "v_cmp_ne_u32_e32 vcc, 0, %[t2]\n\t"                        // solid
-                "v_cmp_eq_u32_e64 %[sb], 0, %[e]\n\t"                       // the border
-                "s_or_b64 %[sb], %[sb], vcc\n\t"                            // the lanes that stop here
-                "s_or_b64 %[sd], %[sd], %[sb]\n\t"
-                "s_andn2_b64 exec, %[sa], %[sb]\n\t"                        // split cells, air voxels:
-                "v_and_or_b32 %[e], %[t1], 1, %[kair]\n\t"                  // the selector of the voxel's leaf
-                "s_mov_b64 exec, %[sb]\n\t"
-                "v_mov_b32_e32 %[vox], %[t2]\n\t"                           // what a parked lane stopped on
-                "s_andn2_b64 exec, %[sx], %[sb]\n\t"                        // the lanes that march on
-                "s_cbranch_scc1 .Lvrt_planes_%=\n\t"
-                "s_branch .Lvrt_out_%=\n"                                   // none: every lane is parked
-                ".Lvrt_leave_%=:\n\t"
-                "s_mov_b64 exec, %[sx]\n"
-                ".Lvrt_out_%=:\n\t"
-                "s_setprio 0\n\t"
-                "s_or_b64 exec, exec, %[sd]\n\t"
-                "v_cndmask_b32_e64 %[parked], 0, 1, %[sd]"
-                : [px] "+v"(pos.x), [py] "+v"(pos.y), [pz] "+v"(pos.z), [tl] "+v"(total_len), [vx] "+v"(vx), [vy] "+v"(vy), [vz] "+v"(vz),
-                  [st] "+v"(step), [ax] "+v"(adx), [ay] "+v"(ady), [az] "+v"(adz), [e] "=&v"(e), [it] "+s"(trips),
-                  [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [sa] "=&s"(sa), [sb] "=&s"(sb), [sx] "=&s"(sx), [sd] "=&s"(sd), [sn] "=&s"(sn), [sw] "=&s"(sw),
-                  [fy] "=&s"(fy), [fz] "=&s"(fz),
-                  [vox] "+v"(voxel), [parked] "=&v"(parked)
-                : [mx] "v"(mxm), [my] "v"(mym), [mz] "v"(mzm), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [ux] "v"(ux), [uy] "v"(uy), [uz] "v"(uz),
-                  [dx] "v"(dir.x), [dy] "v"(dir.y), [dz] "v"(dir.z), [below] "v"(slow_below), [desc] "s"(gb), [row] "s"(row_bytes), [slab] "s"(slab_bytes),
-                  [bdesc] "s"(bb16), [kair] "s"(kAirLeaf), [kbrick] "s"(0x7FFFFFC0u), [liqlo] "s"(liq_lo), [liqspan] "s"(liq_span)
-                : "vcc", "scc", "memory");
-            iter = trips + kMaxSteps;
-            if (parked) break;              // stopped in the loop: border, or the solid voxel now in `voxel`
+            // (wave-uniform already: tells the compiler)
+            const uint32_t plain_s = kLitStops ? __builtin_amdgcn_readfirstlane(plain_below) : kAirLeaf;
+            const uint32_t limit_s = kLitStops ? __builtin_amdgcn_readfirstlane(limit) : kMaxSteps;
+            uint32_t trips = __builtin_amdgcn_readfirstlane(iter) - limit_s;
+            if constexpr (kLitStops) asm volatile(VRT_MARCH_LOOP(VRT_LIT_TEST, VRT_LIT_PARK) VRT_MARCH_LOOP_OPERANDS);
+            else asm volatile(VRT_MARCH_LOOP("", "") VRT_MARCH_LOOP_OPERANDS);
+            iter = trips + limit_s;
+            if (parked) {                   // stopped in the loop: border, the solid voxel now in `voxel`, or (t) a lit air leaf, still in `e`
+                if (kLitStops) lit_stop = e >= kAirLeaf;
+                break;
+            }
             if (iter >= kMaxSteps) break;   // (wave-uniform) at most kMaxSteps lookups (:220)
+            if (kLitStops && iter >= limit) continue;   // (wave-uniform) the loop left at the lit stops' limit, nothing to decide: on, without them
         } else {   // (the kernels that count: the same loop as the compiler lays it out, with the per-lane counters)
             bool exhausted = false;
             for (;;) {
@@ -794,6 +844,8 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
                 lo = e;
             }
             stop = e == 0u;  // border, or past either end of the grid: the position is outside the world
+            // (t) a lit air leaf under a plain shadow lane (a lane in water, a careful wave: kSlow — they march on)
+            if (kLitStops && e >= kAirLeaf && slow_below != kSlow) { lit_stop = true; stop = true; }
             if (!stop) {
                 voxel = 0u;
                 if (is_split_entry(e)) {
@@ -812,7 +864,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
                 } else if (dew != -1.0f) {
                     R.water_dist += total_len - dew;
                     dew = -1.0f;
-                    if (!careful) slow_below = kPlain;
+                    if (!careful) slow_below = plain_below;
                 }
             }
         } else if (STATS) {
@@ -826,6 +878,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // per-lane lookup counts are kept by the STATS kernels only (counters, step-count debug view)
     R.iters = STATS ? looked_up : 0u;
     R.trips = iter;
+    if (kLitStops && lit_stop) return R;   // (t) from here the reference's ray leaves the world through air: a miss, whatever the position says
     if (dew != -1.0f) R.water_dist += total_len - dew;
     // (i): "left the world" (:285-290) from the position itself; a lane that left through a solid leaf or by exhaustion
     // holds a position that passes this test
@@ -843,12 +896,17 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     return R;
 }
 
-template <int MARCH, bool LDS_ROOTS, bool STATS = false, bool CAMERA = false>
+#undef VRT_MARCH_LOOP
+#undef VRT_MARCH_LOOP_OPERANDS
+#undef VRT_LIT_TEST
+#undef VRT_LIT_PARK
+
+template <int MARCH, bool LDS_ROOTS, bool STATS = false, bool CAMERA = false, bool SHADOW = false>
 __device__ __forceinline__ MarchResult march(const FrameParams &P, const uint32_t *s_roots, const uint32_t *s_liquid,
                                              V3 origin, V3 dir) {
     if (MARCH == 1) return march_literal<LDS_ROOTS>(P, s_roots, s_liquid, origin, dir);
     if (MARCH == 2) return march_fast<LDS_ROOTS>(P, s_roots, s_liquid, origin, dir);
-    return march_grid<STATS, CAMERA>(P, s_liquid, origin, dir);
+    return march_grid<STATS, CAMERA, SHADOW>(P, s_liquid, origin, dir);
 }
 
 // ray_sky, ray_tracer.wgsl:144-157

@@ -96,6 +96,16 @@ int tile_order_before_frame(vrt_ctx *c, vrt::FrameParams &P, hipStream_t st, con
     return VRT_OK;
 }
 
+extern "C" int vrt_read_tile_cost(vrt_ctx *c, uint32_t *cost) {
+    GRP_ROOT(c, vrt_read_tile_cost(d, cost));
+    if (!c || !cost) return fail(c, VRT_ERR_INVALID_ARG, "vrt_read_tile_cost: null argument");
+    if (!c->sz.d_tile_cost || !c->sz.tile_order_valid) return fail(c, VRT_ERR_STATE, "vrt_read_tile_cost: no frame has noted its trips");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(cost, c->sz.d_tile_cost, (size_t)c->tiles_local * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
 // Behind the frame's launch: the sort of the trips it noted, on the frame's stream (the frame read the old order and is over when
 // the sort runs; the next frame starts after it).
 int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st, const TileOrderPlan &plan) {

@@ -138,7 +138,7 @@ __device__ __forceinline__ void trace_tile(const FrameParams &P, const uint32_t 
         id |= VRT_ID_SHADOW_RAY;
         const V3 so{R.pos.x + R.norm.x * kShadowBias, R.pos.y + R.norm.y * kShadowBias, R.pos.z + R.norm.z * kShadowBias};
         const V3 sd = normalize_wave(V3{P.sun_local[0] - so.x, P.sun_local[1] - so.y, P.sun_local[2] - so.z});   // (sun_pos - f32(world.min), the host's)
-        S = march<MARCH, LDS_ROOTS, STATS>(P, s_roots, s_liquid, so, sd);
+        S = march<MARCH, LDS_ROOTS, STATS, false, true>(P, s_roots, s_liquid, so, sd);   // (SHADOW: only S.hit is read below, and S.trips / S.iters for the counts)
         if (S.hit) {
             color.x *= kShadowFactor;
             color.y *= kShadowFactor;

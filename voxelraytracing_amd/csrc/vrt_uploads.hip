@@ -357,6 +357,7 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
         const int rc = alloc_tables_like_first(c, k);
         if (rc) return rc;
     }
+    if (A.lit_pending && A.lit_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, A.ev_lit, 0));   // (the marks travel with the grid)
     HIP_TRY(c, hipMemcpyAsync(T.d_grid, A.d_grid, entries * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     if (A.d_mblk) {
         HIP_TRY(c, hipMemcpyAsync(T.d_cdir, A.d_cdir, chunk_dir_entries(S) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
@@ -376,6 +377,12 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     T.update_pending = false;
     T.live = true;
     T.gen = ++c->tables_gen;
+    // (the grid's copy carries tabs[0]'s sun marks: they hold for the copy if they held for the original)
+    T.lit_valid = A.lit_valid && A.lit_gen == A.gen;
+    T.lit_gen = T.gen;
+    memcpy(T.lit_sun, A.lit_sun, sizeof T.lit_sun);
+    T.lit_min_lo = A.lit_min_lo;
+    T.lit_pending = false;   // (whoever reads the copy is ordered behind the copy)
     return VRT_OK;
 }
 
@@ -548,6 +555,102 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
     }
     T.chunk_builds += (uint32_t)T.dirty_chunks.size();
     T.dirty_chunks.clear();
+    return VRT_OK;
+}
+
+// ---- the sun marks (vrt_accel.hip: the lit pass; docs/NUMERICS.md "Lit stops") ----
+// Whether this world and this sun get marks, and which: the axis on which the sun lies beyond the world, the smallest leaf that is
+// marked, and the wave trip count up to which a mark may stop a shadow ray.
+struct LitPlan { uint32_t axis; bool up; uint32_t min_lo, trips; };
+static constexpr uint32_t kLitSettleFrames = 4;
+static bool lit_plan(uint32_t world_size, const float sun[3], LitPlan *lp) {
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(sun[k])) return false;
+    // every ray's line passes within one voxel of the cells it is in: the directions are those from the box widened by a voxel
+    const float lo = -1.0f, hi = (float)world_size + 1.0f;
+    float best = 0.0f;
+    for (uint32_t a = 0; a < 3; a++)
+        for (int up = 0; up < 2; up++) {
+            const float clear = up ? sun[a] - hi : lo - sun[a];   // the sun's distance beyond the face, along the axis
+            if (clear > best) { best = clear; lp->axis = a; lp->up = up != 0; }
+        }
+    if (!(best > 0.0f)) return false;   // the sun is inside the world (or within a voxel of it on every axis)
+    for (uint32_t b = 0; b < 3; b++) {
+        if (b == lp->axis) continue;
+        const float lateral = std::max(std::fabs(sun[b] - lo), std::fabs(sun[b] - hi));
+        if (!(lateral <= 0.99f * best)) return false;   // some ray could cross more than a cell sideways per layer
+    }
+    // The step budget: through air leaves of at least L voxels a ray takes at most B = 6 (W / L + 1) + 2 steps to the world's face
+    // (docs/NUMERICS.md); a lit entry stops a lane only while the wave's trip count leaves the reference's ray B + 1 of its 500
+    for (uint32_t L = 4u; L <= 32u; L *= 2u) {
+        const uint32_t B = 6u * (world_size / L + 1u) + 2u;
+        if (B + 2u <= vrt::kMaxSteps) { lp->min_lo = L - 1u; lp->trips = vrt::kMaxSteps - B - 1u; return true; }
+    }
+    return false;
+}
+
+// Ordered like the chunk updates of update_tables, which it follows on the frame's stream `st`: the pass is a launch (or G launches)
+// on `st`, behind the set's chunk update and before the frame; nothing waits for it on the host.  Whoever else reads the set:
+//   - frames of the set's own frame set run on `st` too: stream order;
+//   - a split set (edits arriving: every frame set its own tables) has no other readers;
+//   - the shared set tabs[0], read from several streams: frames of OTHER frame sets still in flight are waited for as update_tables
+//     waits for them before it rewrites a shared set (quiesce: the one host wait, of at most the frames in flight, and only when the
+//     sun moved or the world was built — an edit splits the sets first); what the context's own stream holds is waited for by an event;
+//     and every later frame on another stream waits for the pass by the event behind it (ev_lit), as it waits for ev_updated.
+int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips) {
+    *below = vrt::kAirLeaf;
+    *trips = 0u;
+    auto &T = c->tabs[k];
+    LitPlan lp{};
+    if (!c->accel_ok || !T.live || !T.d_grid || !lit_plan(c->world.size, sun_local, &lp)) return VRT_OK;
+    const bool held = T.lit_valid && T.lit_gen == T.gen && memcmp(T.lit_sun, sun_local, sizeof T.lit_sun) == 0 && T.lit_min_lo == lp.min_lo;
+    if (held) T.want_frames = 0u;   // (a sun that swings between two places must not collect its four frames one at a time)
+    if (!held) {
+        // Marks are worth a pass (0.4 ms for 64^3 cells, 0.9 ms for the client's 240^3: profiles/sun_marks_edit_cost.txt) once what
+        // they are made from stands still: while edits arrive or the sun moves from frame to frame, the frames run without marks,
+        // as they always did, and the pass follows kLitSettleFrames frames after the last change
+        if (T.want_frames && T.want_gen == T.gen && memcmp(T.want_sun, sun_local, sizeof T.want_sun) == 0 && T.want_min_lo == lp.min_lo) {
+            T.want_frames += 1u;
+        } else {
+            T.want_gen = T.gen;
+            memcpy(T.want_sun, sun_local, sizeof T.want_sun);
+            T.want_min_lo = lp.min_lo;
+            T.want_frames = 1u;
+        }
+        if (T.want_frames < kLitSettleFrames) return VRT_OK;
+        T.want_frames = 0u;
+        if (k == 0u && (shares || c->shared_readers_in_flight)) {   // (the frame about to be enqueued has been announced on its stream already)
+            const bool alt = c->alt_pending, own = c->own_pending;
+            QUIESCE(c);
+            c->alt_pending = alt;
+            c->own_pending = own;
+            if (st != c->stream) {
+                HIP_TRY(c, T.ev_lit_guard.ensure());
+                HIP_TRY(c, hipEventRecord(T.ev_lit_guard, c->stream));
+                HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit_guard, 0));
+            }
+        }
+        if (T.lit_pending && T.lit_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));   // (a pass behind a pass)
+        T.lit_valid = false;
+        vrt::launch_accel_lit(T.d_grid, c->accel_S * 8u, lp.axis, lp.up, lp.min_lo, sun_local, st);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, T.ev_lit.ensure());
+        HIP_TRY(c, hipEventRecord(T.ev_lit, st));
+        T.lit_pending = true;
+        T.lit_stream = st;
+        T.lit_valid = true;
+        T.lit_gen = T.gen;
+        memcpy(T.lit_sun, sun_local, sizeof T.lit_sun);
+        T.lit_min_lo = lp.min_lo;
+        c->lit_passes += 1u;
+    }
+    if (T.lit_pending && T.lit_stream != st) {   // the marks this frame reads were made on another stream
+        if (hipEventQuery(T.ev_lit) == hipSuccess) T.lit_pending = false;
+        else HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));
+    }
+    *below = vrt::kLitBelow;
+    *trips = lp.trips;
+    c->lit_last_min_leaf = lp.min_lo + 1u;
     return VRT_OK;
 }
 
@@ -778,6 +881,9 @@ int vrt_read_accel(vrt_ctx *c, uint32_t *grid, uint16_t *bricks) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (size_t z = 0; z < G; z++)
             for (size_t y = 0; y < G; y++) memcpy(grid + (z * G + y) * G, t.data() + (z * G1 + y) * G1, G * sizeof(uint32_t));
+        // the caller gets canonical entries: an air leaf without its sun mark (vrt_device.h kAirUnlit; vrt_get_sun_marks reads the marks)
+        for (size_t i = 0; i < G * G * G; i++)
+            if (grid[i] >= vrt::kAirLeaf) grid[i] &= ~vrt::kAirUnlit;
     }
     uint32_t used = 0;
     const int rc = bricks_in_use(c, c->tabs[0], &used);
@@ -785,6 +891,33 @@ int vrt_read_accel(vrt_ctx *c, uint32_t *grid, uint16_t *bricks) {
     if (bricks && used)
         HIP_TRY(c, hipMemcpyAsync(bricks, c->tabs[0].d_bricks, (size_t)used * 64u * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+int vrt_get_sun_marks(vrt_ctx *c, uint32_t *passes, uint32_t *min_leaf, uint32_t *lit_trips, uint8_t *lit) {
+    GRP_ROOT(c, vrt_get_sun_marks(d, passes, min_leaf, lit_trips, lit));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    if (passes) *passes = c->lit_passes;
+    if (min_leaf) *min_leaf = c->lit_last_min_leaf;
+    if (lit_trips) *lit_trips = c->lit_last_trips;
+    if (!lit) return VRT_OK;
+    if (!c->accel_ok || c->accel_dirty || !c->tabs[c->last.tab].live)
+        return fail(c, VRT_ERR_STATE, "vrt_get_sun_marks: the tables are not up to date (render a frame first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    QUIESCE(c);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    vrt_ctx::Tables &T = c->tabs[c->last.tab];   // the table set the last frame used
+    if (T.lit_pending) { HIP_TRY(c, hipEventSynchronize(T.ev_lit)); T.lit_pending = false; }
+    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u;
+    std::vector<uint32_t> t(G * G1 * G1);
+    HIP_TRY(c, hipMemcpy(t.data(), T.d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const bool held = T.lit_valid && T.lit_gen == T.gen;
+    for (size_t z = 0; z < G; z++)
+        for (size_t y = 0; y < G; y++)
+            for (size_t x = 0; x < G; x++) {
+                const uint32_t e = t[(z * G1 + y) * G1 + x];
+                lit[(z * G + y) * G + x] = (held && e >= vrt::kAirLeaf && !(e & vrt::kAirUnlit)) ? 1u : 0u;
+            }
     return VRT_OK;
 }
 

@@ -311,6 +311,25 @@ class Gpu:
         self._ck(self._lib.vrt_read_march_cells(self._h, cells.ctypes.data_as(C.c_void_p), C.byref(direct)))
         return cells, bool(direct.value)
 
+    def read_tile_cost(self, tiles: int) -> np.ndarray:
+        """The trips per tile the last frame that noted them took — see vrt_read_tile_cost in include/vrt.h."""
+        cost = np.empty(tiles, dtype=np.uint32)
+        self._ck(self._lib.vrt_read_tile_cost(self._h, cost.ctypes.data_as(C.c_void_p)))
+        return cost
+
+    def sun_marks(self, cells: bool = False):
+        """{passes, min_leaf, lit_trips[, lit[G,G,G] indexed [z,y,x]]} — see vrt_get_sun_marks in include/vrt.h."""
+        p, m, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        lit = None
+        if cells:
+            g = self.accel_info().world_size_chunks * 8
+            lit = np.empty((g, g, g), dtype=np.uint8)
+        self._ck(self._lib.vrt_get_sun_marks(self._h, C.byref(p), C.byref(m), C.byref(t), lit.ctypes.data_as(C.c_void_p) if cells else None))
+        out = dict(passes=p.value, min_leaf=m.value, lit_trips=t.value)
+        if cells:
+            out["lit"] = lit
+        return out
+
     # --- device plumbing for torch / RCCL ---
     def set_stream(self, hip_stream: int):
         self._ck(self._lib.vrt_set_stream(self._h, C.c_void_p(hip_stream)))
