@@ -243,6 +243,43 @@ pub struct vrt_denoise_opts {
     pub _reserved: u32,
 }
 
+/// vrt_set_tone_map: exposure and tone curve of presented path frames (curve VRT_TONE_OFF = off; include/vrt.h has the contract).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_tone_map {
+    pub curve: u32,
+    pub flags: u32,
+    pub exposure: f32,
+    pub white: f32,
+    pub key: f32,
+    pub adapt: f32,
+    pub min_auto: f32,
+    pub max_auto: f32,
+    pub percentile: u32,
+    pub _reserved: [u32; 3],
+}
+
+/// vrt_get_tone_info: the last mapped frame's exposure and, with VRT_TONE_AUTO, what it metered.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_tone_info {
+    pub exposure: f32,
+    pub target: f32,
+    pub luminance: f32,
+    pub bin: u32,
+    pub counted: u64,
+    pub skipped: u64,
+    pub frames: u32,
+    pub _reserved: u32,
+}
+
+pub const VRT_TONE_OFF: u32 = 0;
+pub const VRT_TONE_LINEAR: u32 = 1;
+pub const VRT_TONE_REINHARD: u32 = 2;
+pub const VRT_TONE_FILMIC: u32 = 3;
+pub const VRT_TONE_AUTO: u32 = 1;
+pub const VRT_TONE_GAMMA2: u32 = 2;
+
 /// vrt_set_sun_light: direct sunlight for the path trace (strength 0 = off; the sun term's factor on settings.sun_intensity).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -358,6 +395,9 @@ extern "C" {
     pub fn vrt_get_accumulation(ctx: *mut vrt_ctx, samples: *mut u32, seed: *mut u32) -> c_int;
     pub fn vrt_set_denoise(ctx: *mut vrt_ctx, opts: *const vrt_denoise_opts) -> c_int;
     pub fn vrt_read_guide(ctx: *mut vrt_ctx, guide: *mut u32) -> c_int;
+    pub fn vrt_set_tone_map(ctx: *mut vrt_ctx, opts: *const vrt_tone_map) -> c_int;
+    pub fn vrt_get_tone_info(ctx: *mut vrt_ctx, out: *mut vrt_tone_info) -> c_int;
+    pub fn vrt_read_tone_histogram(ctx: *mut vrt_ctx, bins: *mut u32) -> c_int;
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
     pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
     pub fn vrt_set_lamp_light(ctx: *mut vrt_ctx, opts: *const vrt_lamp_light) -> c_int;
@@ -412,6 +452,8 @@ mod layout {
         assert_eq!(size_of::<vrt_accel_info>(), 48);
         assert_eq!(size_of::<vrt_issue_profile>(), 72);
         assert!(size_of::<vrt_denoise_opts>() == 16);
+        assert!(size_of::<vrt_tone_map>() == 48);
+        assert!(size_of::<vrt_tone_info>() == 40);
         assert!(size_of::<vrt_sun_light>() == 16);
         assert!(size_of::<vrt_camera_sampling>() == 16);
         assert!(size_of::<vrt_lamp_light>() == 16);

@@ -415,6 +415,82 @@ int vrt_set_denoise(vrt_ctx *ctx, const vrt_denoise_opts *opts);
  * Synchronises.  VRT_ERR_STATE before the first denoised frame (and after a resize until the next one). */
 int vrt_read_guide(vrt_ctx *ctx, uint32_t *guide);
 
+/* Exposure and tone mapping of presented path frames.  A path frame's radiance lies well outside [0, 1] (emission, the sun
+ * term, the lamps); vrt_present / vrt_present_device quantise unorm8(clamp(c, 0, 1)), the live shader's textureStore, which is
+ * right for the primary modes and clips a path frame.  vrt_set_tone_map puts an exposure E — the host's, or metered from every
+ * frame — and a tone curve between the texel and that quantisation.  Build-defined, and defined exactly, in strict binary32,
+ * nothing contracted:
+ *   mapped frame  a VRT_MODE_PATH frame rendered while curve != VRT_TONE_OFF.  The whole setting is the frame's from vrt_render
+ *                 on: a vrt_set_tone_map between render and present does not change what the frame presents as.  Primary and
+ *                 primary + shadow frames are never mapped, and the fused presentation (vrt_set_presentation) is theirs alone.
+ *   scope         vrt_present and vrt_present_device only.  vrt_read_output (all three outputs), vrt_device_output, a bound
+ *                 output, the accumulation's sum, the denoiser's input and the id words are what they are without the setting,
+ *                 and changing it does not restart the accumulation.
+ *   the map       the blit quantises every texel it taps with unorm8(encode(curve(c * E))) per colour channel in place of
+ *                 unorm8(c); alpha, the bilinear sample, the crosshair's blend and the final quantisation are unchanged.
+ *                   x = c * E
+ *                   LINEAR    y = x
+ *                   REINHARD  w2 = white * white (once, on the host);
+ *                             y = white != 0 ? (x * (1.0f + x / w2)) / (1.0f + x) : x / (1.0f + x)
+ *                   FILMIC    y = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)      (Narkowicz's ACES fit)
+ *                   GAMMA2    y = sqrtf(clamp(y, 0, 1)), the clamp the quantisation's own: (y > 0 ? y : 0), then the smaller of it and 1
+ *                 A NaN or an infinity takes no special path (a NaN quantises to 0).  Every curve maps 0 to 0.
+ *   metering      VRT_TONE_AUTO: behind the frame's last launch on its own stream (the resolve of a multi-sample or accumulating
+ *                 frame and the denoiser's passes included: the colours the frame's texels hold).  For every pixel of the traced
+ *                 area 8 (W / 8) x 8 (H / 8):  lum = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  skipped when !(lum > 0) or lum
+ *                 is infinite;  otherwise counted in bin clamp((int)(bits(lum) >> 20) - 888, 0, 255): eight bins an octave from
+ *                 2^-16 to 2^16, denormals and larger values in the end bins.  Then, once:
+ *                   N = the bins' sum.  N == 0: target = the previous adapted exposure, or `exposure` if there is none
+ *                   otherwise, in 64 bits, rank = min(N * percentile / 1000, N - 1); b = the lowest bin whose inclusive prefix
+ *                   sum exceeds rank; before = the prefix sum below b; lo = as_float((b + 888) << 20), hi = as_float((b + 889) << 20);
+ *                   frac = ((float)(uint32_t)(rank - before) + 0.5f) / (float)bins[b];  L = lo + (hi - lo) * frac;
+ *                   target = (key / L) * exposure;  if (min_auto != 0 && target < min_auto) target = min_auto;  likewise max_auto
+ *   adaptation    metered frames are ordered by their vrt_render calls, whatever stream or frame set each ran on.  The first one
+ *                 since the adaptation started takes E = target; later ones E = target when adapt == 1, else
+ *                 E = E_prev + (target - E_prev) * adapt.  The adaptation starts at vrt_create, at a vrt_set_tone_map that
+ *                 changes any byte of the setting, and at vrt_resize_output — not at a change of camera, world or settings.
+ *                 Without VRT_TONE_AUTO, E = exposure.
+ * E stays on the device: the blit reads it from the frame set's word, and nothing on the render or present path waits for it.
+ * opts NULL or curve == VRT_TONE_OFF: off, the default — every frame, launch and allocation is what it is without this call.
+ * VRT_ERR_INVALID_ARG: an unknown curve or flag, _reserved not 0, any float negative, NaN or infinite, percentile > 1000,
+ * min_auto > max_auto when both are set, VRT_TONE_AUTO with VRT_TONE_OFF; with a curve, exposure == 0; with VRT_TONE_AUTO, key == 0
+ * or adapt outside (0, 1].  VRT_ERR_STATE: a curve on a sharded, tile-major or multi-device context (they cannot present, or
+ * assemble their frame elsewhere).  A refused call changes nothing.  A timed frame's GPU time includes the metering. */
+#define VRT_TONE_OFF      0u   /* default: present as without the setting */
+#define VRT_TONE_LINEAR   1u   /* exposure only, then the existing clamp */
+#define VRT_TONE_REINHARD 2u   /* extended Reinhard, per channel */
+#define VRT_TONE_FILMIC   3u   /* Narkowicz's ACES fit, per channel */
+#define VRT_TONE_AUTO     1u   /* flags: exposure metered from every path frame */
+#define VRT_TONE_GAMMA2   2u   /* flags: square-root encode behind the curve */
+typedef struct vrt_tone_map {
+    uint32_t curve;       /* VRT_TONE_* */
+    uint32_t flags;       /* VRT_TONE_AUTO | VRT_TONE_GAMMA2 */
+    float    exposure;    /* manual: the factor E.  AUTO: a compensation multiplied onto the metered value.  finite, > 0 */
+    float    white;       /* REINHARD: the value mapped to 1; 0 = plain x / (1 + x).  finite, >= 0 */
+    float    key;         /* AUTO: the value the metered luminance is brought to (suggested 0.18).  finite, > 0 */
+    float    adapt;       /* AUTO: 1 = follow at once; (0, 1): share of the way taken per metered frame */
+    float    min_auto, max_auto;   /* AUTO: bounds of the adapted exposure's target; 0 = none.  finite, >= 0, min <= max when both set */
+    uint32_t percentile;  /* AUTO: 0..1000, the rank metered, in thousandths (suggested 500) */
+    uint32_t _reserved[3];/* 0 */
+} vrt_tone_map;           /* 48 B */
+int vrt_set_tone_map(vrt_ctx *ctx, const vrt_tone_map *opts);
+
+typedef struct vrt_tone_info {
+    float    exposure;    /* E of the last mapped frame */
+    float    target;      /* AUTO: what that frame metered, before adaptation */
+    float    luminance;   /* AUTO: L (0 when nothing was counted) */
+    uint32_t bin;         /* AUTO: the bin that holds the rank (0 when nothing was counted) */
+    uint64_t counted, skipped;   /* AUTO: pixels in the histogram / left out of it */
+    uint32_t frames;      /* metered frames since the adaptation last started, that frame included */
+    uint32_t _reserved;
+} vrt_tone_info;          /* 40 B */
+/* The last mapped frame's exposure and, with VRT_TONE_AUTO, what it metered (without: the other fields are 0).  Synchronises.
+ * VRT_ERR_STATE before the first mapped frame (and after a resize until the next one). */
+int vrt_get_tone_info(vrt_ctx *ctx, vrt_tone_info *out);
+/* The 256 bins of the last metered frame.  Synchronises.  VRT_ERR_STATE before the first metered frame (and after a resize
+ * until the next one). */
+int vrt_read_tone_histogram(vrt_ctx *ctx, uint32_t bins[256]);
+
 /* Direct sunlight for VRT_MODE_PATH: next-event estimation towards the scene's one light.  ray_sky's sun is a disc of
  * dot(dir, sun_dir) > 0.99, which a random bounce rarely leaves the world through; with vrt_set_sun_light every hit of a path
  * sends a ray to the sun instead.  The primary modes ignore the setting and stay byte for byte what they are.  Build-defined,

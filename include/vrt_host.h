@@ -187,6 +187,19 @@ int vrth_denoise(const float *rgb, const uint32_t *ids, const uint32_t *guide, u
 int vrth_lens_ray(const vrt_cam_data *cam, const int32_t world_min[3], const vrt_camera_sampling *opts, uint32_t px, uint32_t py, const float u[4],
                   float out[9]);
 
+/* ---- exposure and tone mapping (include/vrt.h: vrt_set_tone_map) on the host ---- */
+/* What a metered frame's kernels compute, in the same text (csrc/both/tone_math.h): the luminance histogram of the traced area
+ * 8 (w / 8) x 8 (h / 8) of rgb (w*h*3 f32, row-major) into bins[256], and the one-thread step into *info — has_prev /
+ * prev_exposure: whether a metered frame came before this one since the adaptation started, and its adapted exposure.
+ * info->frames is left 0 (the count is the context's).  opts are taken with or without VRT_TONE_AUTO.  Either output may be
+ * NULL.  Returns 0, or -1 for a null rgb or opts, or a setting vrt_set_tone_map refuses with VRT_ERR_INVALID_ARG (key and adapt
+ * are held to VRT_TONE_AUTO's ranges). */
+int vrth_tone_meter(const float *rgb, uint32_t w, uint32_t h, const vrt_tone_map *opts, int has_prev, float prev_exposure, vrt_tone_info *info,
+                    uint32_t bins[256]);
+/* encode(curve(c * E)) of n floats, each a colour channel: what the blit of a mapped frame quantises in place of c.  rgb_out
+ * may alias rgb_in.  Returns 0, or -1 as vrth_tone_meter does (VRT_TONE_OFF copies). */
+int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, float exposure, float *rgb_out);
+
 #ifdef __cplusplus
 }
 #endif

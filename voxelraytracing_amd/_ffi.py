@@ -88,6 +88,24 @@ class DenoiseOpts(C.Structure):
     _fields_ = [("passes", C.c_uint32), ("sigma_color", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class ToneMap(C.Structure):
+    """include/vrt.h vrt_tone_map: exposure and tone curve of presented path frames (vrt_set_tone_map)"""
+    _fields_ = [("curve", C.c_uint32), ("flags", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),
+                ("adapt", C.c_float), ("min_auto", C.c_float), ("max_auto", C.c_float), ("percentile", C.c_uint32),
+                ("_reserved", C.c_uint32 * 3)]
+
+
+class ToneInfo(C.Structure):
+    """include/vrt.h vrt_tone_info (vrt_get_tone_info)"""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("luminance", C.c_float), ("bin", C.c_uint32),
+                ("counted", C.c_uint64), ("skipped", C.c_uint64), ("frames", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+TONE_OFF, TONE_LINEAR, TONE_REINHARD, TONE_FILMIC = 0, 1, 2, 3   # vrt_tone_map.curve (VRT_TONE_*)
+TONE_AUTO, TONE_GAMMA2 = 1, 2                                    # vrt_tone_map.flags
+TONE_KEY, TONE_PERCENTILE = 0.18, 500                            # the suggested metering
+
+
 class SunLight(C.Structure):
     """include/vrt.h vrt_sun_light: the path trace's direct sunlight (vrt_set_sun_light)"""
     _fields_ = [("strength", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
@@ -171,6 +189,7 @@ assert C.sizeof(BoxQuery) == 48 and C.sizeof(BoxMove) == 32
 assert BOX_QUERY_DTYPE.itemsize == 48 and BOX_MOVE_DTYPE.itemsize == 32
 assert C.sizeof(WorldData) == 32 and C.sizeof(Settings) == 48
 assert C.sizeof(DenoiseOpts) == 16
+assert C.sizeof(ToneMap) == 48 and C.sizeof(ToneInfo) == 40
 assert C.sizeof(SunLight) == 16
 assert C.sizeof(LampLight) == 16 and C.sizeof(Lamp) == 16 and LAMP_DTYPE.itemsize == 16 and C.sizeof(LampInfo) == 24
 assert C.sizeof(CameraSampling) == 16
@@ -210,6 +229,9 @@ VRT_SYMBOLS = {
     "vrt_get_accumulation": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrt_set_denoise": (C.c_int, [_P, C.POINTER(DenoiseOpts)]),
     "vrt_read_guide": (C.c_int, [_P, _P]),
+    "vrt_set_tone_map": (C.c_int, [_P, C.POINTER(ToneMap)]),
+    "vrt_get_tone_info": (C.c_int, [_P, C.POINTER(ToneInfo)]),
+    "vrt_read_tone_histogram": (C.c_int, [_P, _P]),
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
     "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
     "vrt_set_lamp_light": (C.c_int, [_P, C.POINTER(LampLight)]),
@@ -398,6 +420,8 @@ VRTH_SYMBOLS = {
     "vrth_region_file_name": (C.c_uint32, [_I32P, C.c_char_p, C.c_uint32]),
     "vrth_denoise": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseOpts), _P]),
     "vrth_lens_ray": (C.c_int, [_P, _I32P, C.POINTER(CameraSampling), C.c_uint32, C.c_uint32, _P, _P]),
+    "vrth_tone_meter": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(ToneMap), C.c_int, C.c_float, C.POINTER(ToneInfo), _P]),
+    "vrth_tone_map": (C.c_int, [_P, C.c_uint64, C.POINTER(ToneMap), C.c_float, _P]),
 }
 
 # Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)
@@ -425,4 +449,34 @@ def denoise(rgb, ids, guide, passes: int = DENOISE_PASSES, sigma_color: float = 
     o = DenoiseOpts(passes, sigma_color, 0, 0)
     if host().vrth_denoise(rgb.ctypes.data, ids.ctypes.data, guide.ctypes.data, w, h, C.byref(o), out.ctypes.data):
         raise ValueError(f"denoise: passes {passes} (0..5), sigma_color {sigma_color} (finite, >= 0)")
+    return out
+
+
+def tone_setting(curve: int = TONE_FILMIC, exposure: float = 1.0, auto: bool = False, gamma2: bool = False, white: float = 0.0,
+                 key: float = TONE_KEY, adapt: float = 1.0, min_auto: float = 0.0, max_auto: float = 0.0,
+                 percentile: int = TONE_PERCENTILE) -> ToneMap:
+    """A vrt_tone_map from keywords (Gpu.set_tone_map takes the same ones)."""
+    return ToneMap(curve, (TONE_AUTO if auto else 0) | (TONE_GAMMA2 if gamma2 else 0), exposure, white, key, adapt, min_auto, max_auto,
+                   percentile, (C.c_uint32 * 3)(0, 0, 0))
+
+
+def tone_meter(rgb, opts: ToneMap, prev_exposure=None):
+    """vrth_tone_meter: what a metered frame's kernels compute (vrt_set_tone_map with VRT_TONE_AUTO), on the host, in the same
+    text — rgb [h, w, 3] f32 -> (ToneInfo, bins [256] u32); prev_exposure: the adapted exposure of the metered frame before
+    (None: the adaptation starts here)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = rgb.shape[:2]
+    info, bins = ToneInfo(), np.zeros(256, dtype=np.uint32)
+    if host().vrth_tone_meter(rgb.ctypes.data, w, h, C.byref(opts), 0 if prev_exposure is None else 1,
+                              0.0 if prev_exposure is None else float(prev_exposure), C.byref(info), bins.ctypes.data):
+        raise ValueError("tone_meter: a setting vrt_set_tone_map refuses")
+    return info, bins
+
+
+def tone_map(rgb, opts: ToneMap, exposure: float) -> np.ndarray:
+    """vrth_tone_map: encode(curve(c * E)) of every value of rgb (f32, any shape), in the text the mapped blit compiles."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    out = np.empty_like(rgb)
+    if host().vrth_tone_map(rgb.ctypes.data, rgb.size, C.byref(opts), float(exposure), out.ctypes.data):
+        raise ValueError("tone_map: a setting vrt_set_tone_map refuses")
     return out

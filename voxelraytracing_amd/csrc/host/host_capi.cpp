@@ -12,6 +12,7 @@
 #include "../both/denoise_math.h"
 #include "../both/lens_math.h"
 #include "../both/shape_math.h"
+#include "../both/tone_math.h"
 #include "collide.hpp"
 #include "edit_check.hpp"
 #include "graphics.hpp"
@@ -585,6 +586,58 @@ int vrth_lens_ray(const vrt_cam_data *cam, const int32_t world_min[3], const vrt
     }
     const float r[9] = {w.x, w.y, w.z, o.x, o.y, o.z, v.x, v.y, v.z};
     std::memcpy(out, r, sizeof r);
+    return 0;
+}
+
+// vrt_set_tone_map's metering over a host frame: csrc/both/tone_math.h's bin per pixel of the traced area, then its one-thread
+// step over the bins' prefix sums, found here in a plain loop
+int vrth_tone_meter(const float *rgb, uint32_t w, uint32_t h, const vrt_tone_map *opts, int has_prev, float prev_exposure, vrt_tone_info *info,
+                    uint32_t bins[256]) {
+    if (!rgb || !opts) return -1;
+    vrt_tone_map o = *opts;
+    if (!vrt::tone_setting_ok(o)) return -1;
+    o.flags |= vrt::kToneAuto;   // (what is metered is held to the metering's ranges)
+    if (o.curve == vrt::kToneOff) o.curve = vrt::kToneLinear;
+    if (!vrt::tone_setting_ok(o)) return -1;
+    uint32_t count[vrt::kToneBins] = {};
+    const uint32_t wt = w & ~7u, ht = h & ~7u;
+    for (uint32_t y = 0; y < ht; y++)
+        for (uint32_t x = 0; x < wt; x++) {
+            const float *p = rgb + ((size_t)y * w + x) * 3;
+            const int b = vrt::tone_bin(vrt::tone_luminance(p[0], p[1], p[2]));
+            if (b >= 0) count[b] += 1u;
+        }
+    uint64_t n = 0;
+    for (uint32_t v : count) n += v;
+    uint64_t rank = 0, before = 0;
+    uint32_t b = 0;
+    if (n) {
+        rank = vrt::tone_rank(n, o.percentile);
+        while (before + count[b] <= rank) before += count[b++];
+    }
+    const vrt::ToneMeter m{o.exposure, o.key, o.adapt, o.min_auto, o.max_auto, o.percentile};
+    const vrt::ToneMetered r = vrt::tone_finish(m, n, rank, b, before, count[b], has_prev != 0, prev_exposure);
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->exposure = r.exposure;
+        info->target = r.target;
+        info->luminance = r.luminance;
+        info->bin = r.bin;
+        info->counted = n;
+        info->skipped = (uint64_t)wt * ht - n;
+    }
+    if (bins) std::memcpy(bins, count, sizeof count);
+    return 0;
+}
+
+int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, float exposure, float *rgb_out) {
+    if (!rgb_in || !rgb_out || !opts || !vrt::tone_setting_ok(*opts)) return -1;
+    if (opts->curve == vrt::kToneOff) {
+        if (rgb_out != rgb_in) std::memmove(rgb_out, rgb_in, n * sizeof(float));
+        return 0;
+    }
+    const vrt::ToneCurve t = vrt::tone_curve_of(opts->curve, opts->flags, opts->white);
+    for (uint64_t i = 0; i < n; i++) rgb_out[i] = vrt::tone_map_channel(t, exposure, rgb_in[i]);
     return 0;
 }
 

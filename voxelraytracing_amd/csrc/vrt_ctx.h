@@ -10,6 +10,7 @@
 //   vrt_gen.hip      the chunk source (vrt_generate_chunks, vrt_build_chunks)
 //   vrt_edit.hip     shapes onto chunks that exist (vrt_edit_chunks), in front of vrt_gen.hip's builder
 //   vrt_denoise.hip  the path trace's denoiser (vrt_set_denoise, vrt_read_guide) and its kernels
+//   vrt_tone.hip     exposure and tone mapping of presented path frames (vrt_set_tone_map): the metering kernels and the read-backs
 //   both/            not of this seam: the arithmetic those three kernels share with the host mirror (both/both.h)
 //
 // Replaces the reference's wgpu seam: GpuResources / Buffers / NodeBuffer / SimpleBuffer /
@@ -102,8 +103,10 @@ void launch_path_accum_resolve(Texel *out, Texel *sum, uint32_t n, bool first, b
 void launch_quantize(const Texel *out, uint8_t *rgba8, uint32_t w, uint32_t h, hipStream_t st);
 void launch_assemble(const Texel *gathered, Texel *dst, uint32_t width, uint32_t tiles_x, uint32_t tiles_total,
                      uint32_t root_weight, uint32_t period, bool skip_root, uint64_t rank_stride, hipStream_t st);
+// tone: a mapped frame's blit (vrt_set_tone_map) — the kernels that put the exposure and the curve in front of every texel's
+// quantisation; null: the blit as it is without the setting
 void launch_present(const Texel *out, uint32_t w, uint32_t h, uint32_t screen_w, uint32_t screen_h, const vrt_crosshair &ch,
-                    uint8_t *rgba8, bool one_to_one, const uint32_t box[4], hipStream_t st);
+                    uint8_t *rgba8, bool one_to_one, const uint32_t box[4], hipStream_t st, const ToneBlit *tone = nullptr);
 void launch_assemble_shade(const FrameParams &P, const void *gathered, Texel *dst, uint32_t root_weight, uint32_t period,
                            uint64_t rank_stride, hipStream_t st);
 void launch_accel_cells(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
@@ -221,6 +224,10 @@ struct vrt_ctx {
         uint32_t slot = 0, tab = 0, mode = 0, spp = 1;   // its frame set and its table set
         // it stored the window's image itself (vrt_set_presentation), and texels at all (not with VRT_PRESENT_SKIP_TEXELS); opts.stats == 1
         bool fused = false, has_texels = true, stats = false;
+        // vrt_set_tone_map as it stood at the frame's vrt_render (curve 0: not a mapped frame), and where the blit reads the
+        // frame's E: the frame set's word on the device (a metered frame) or, null, tone.exposure
+        vrt_tone_map tone{};
+        const float *tone_E = nullptr;
     } last;
     // What a resize drops (alloc_output assigns an empty Sized, then makes own_out, d_hits and d_blk_counts again): every buffer
     // sized by the output, made on first use, and what is only true of their contents.
@@ -459,6 +466,21 @@ struct vrt_ctx {
     // vrt_set_denoise (vrt_denoise.hip): the setting (passes 0: off); the scratch frames the passes go back and forth over and the
     // guide words are sz.dn_scratch / sz.dn_guide
     vrt_denoise_opts denoise{};
+    // vrt_set_tone_map (vrt_tone.hip): the setting (48 zero bytes: off).  One word block per frame set, made by its first metered
+    // frame (vrt::kTone*: the histogram being counted, the last metered frame's, its E and its vrt_tone_info); the frame set whose
+    // block holds the adapted exposure of the metered frame before the next one (-1: the adaptation starts), the metered frames
+    // since it started, and the event behind the last one-thread step: the next one, on whatever stream, waits for it
+    vrt_tone_map tone{};
+    Buf<uint32_t> d_tone[kMaxInFlight];
+    int tone_prev = -1;
+    uint32_t tone_frames = 0;
+    Event ev_tone;
+    uint32_t tone_blocks = 512;              // VRT_TONE_BLOCKS: about how many workgroups count a frame's histogram
+    hipStream_t tone_ev_stream = nullptr;    // the stream ev_tone was last recorded on (null: never)
+    // the last mapped frame (vrt_get_tone_info) and the last metered one (vrt_read_tone_histogram): -1 none yet
+    int tone_info_slot = -1, tone_hist_slot = -1;
+    bool tone_info_metered = false;          // the last mapped frame was metered: its record is in its set's block
+    float tone_info_exposure = 0.0f;         // ... it was not: its E
     vrt_sun_light sun{};      // vrt_set_sun_light: the setting (16 zero bytes: off); the sun-ray buffers are sz.sun_recs / sz.sun_counts
     vrt_camera_sampling lens{};   // vrt_set_camera_sampling: the setting (16 zero bytes: off)
     // vrt_set_lamp_light (vrt_lamp.hip): the setting (16 zero bytes: off), the cap (VRT_LAMP_CAP) and one lamp list per frame set,
@@ -569,6 +591,11 @@ VRT_HIDDEN int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hip
 VRT_HIDDEN int denoise_before_frame(vrt_ctx *c, uint32_t slot, vrt::Texel *frame_out, vrt::Texel **trace_into);
 VRT_HIDDEN int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, const vrt::FramePlan &plan, uint32_t slot, hipStream_t st, vrt::Texel *frame_out,
                                    hipEvent_t closing);
+// vrt_tone.hip: behind a path frame's last launch (the denoiser's passes included) in vrt_render (vrt_set_tone_map with
+// VRT_TONE_AUTO): the histogram and the one-thread step; *E: where the frame's blit reads its exposure (null: the setting's own).
+// tone_restart: the adaptation starts again and the last mapped / metered frame is forgotten (a resize)
+VRT_HIDDEN int tone_after_frame(vrt_ctx *c, uint32_t slot, hipStream_t st, const vrt::Texel *frame_out, hipEvent_t closing, const float **E);
+VRT_HIDDEN void tone_restart(vrt_ctx *c);
 // vrt_uploads.hip
 VRT_HIDDEN int alloc_roots(vrt_ctx *c, uint32_t world_size);
 VRT_HIDDEN int flush_staged(vrt_ctx *c);

@@ -187,6 +187,19 @@ struct LampLaunch {
     uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun term, and the later misses' sky without the disc
 };
 
+// vrt_set_tone_map: what the blit of a mapped frame is given besides the unmapped blit's arguments (both/tone_math.h's
+// ToneCurve, flat).  E_dev: the frame set's exposure word on the device (a metered frame: nothing of it comes back to the host);
+// null: E, the setting's own
+struct ToneBlit {
+    const float *E_dev;
+    float E;
+    uint32_t curve, gamma2;
+    float white, w2;
+};
+// A frame set's tone block (vrt_tone.hip), in words: the bins being counted (zero between two frames), the last metered
+// frame's bins, its E, and its vrt_tone_info (8-byte aligned)
+constexpr uint32_t kToneCounting = 0u, kToneHistogram = 256u, kToneExposure = 512u, kToneInfo = 514u, kToneWords = 524u;
+
 // The path-trace buffers are compacted per segment, not globally: one device-scope counter saturates at ~88
 // returning atomics per microsecond (MI355X_MICROARCH.md "dequeue"), which made 32 400 per-wave atomics the
 // whole 0.37 ms of the first primary kernel.  Workgroup b appends to segment b % kHitSegments; each counter

@@ -60,6 +60,7 @@ static void layout_tiles(vrt_ctx *c) {
 static int alloc_output(vrt_ctx *c) {
     c->sz = vrt_ctx::Sized{};   // everything of the old size goes (the callers have waited for the frames in flight)
     c->accum_restart = true;
+    tone_restart(c);
     layout_tiles(c);
     const size_t n = frame_slots(c);
     HIP_TRY(c, c->sz.own_out.once(n));
@@ -528,6 +529,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     if (const char *e = getenv("VRT_TILE_ORDER_RADIUS")) { const int v = atoi(e); if (v >= 1 && v <= 6) c->mov_radius = (uint32_t)v; }
     if (const char *e = getenv("VRT_PATH_POOL")) c->path_pool = e[0] != '0';
     if (const char *e = getenv("VRT_LAMP_CAP")) { const long v = atol(e); if (v >= 1 && v <= (1l << 24)) c->lamp_cap = (uint32_t)v; }   // (tests: a list that is cut off)
+    if (const char *e = getenv("VRT_TONE_BLOCKS")) { const long v = atol(e); if (v >= 1 && v <= 65536) c->tone_blocks = (uint32_t)v; }   // (docs/KERNELS.md: the sweep)
     if (const char *e = getenv("VRT_PATH_CELLS")) c->path_cells = e[0] != '0';
     if (const char *e = getenv("VRT_PATH_POOL_REFILL")) c->path_refill = (uint32_t)atoi(e);
     if (const char *e = getenv("VRT_PATH_POOL_K")) { const int v = atoi(e); if (v == 4 || v == 5) c->path_pool_batches = (uint32_t)v; }
@@ -794,6 +796,8 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     VRT_TRY(tile_order_before_frame(c, P, f.st, plan, edit_in_front, order_plan));
     // the counters feed stats frames and the path trace's segment cursors; a plain primary(+shadow) frame reads none
     if (plan.kstats || plan.path) HIP_TRY(c, hipMemsetAsync(f.counters, 0, kCounterBytes, f.st));
+    vrt_tone_map frame_tone{};          // (a primary frame is never mapped)
+    const float *tone_E = nullptr;
     {
         VRT_PROF(13, "  the launch(es)");
         int rc;
@@ -816,6 +820,9 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             rc = launch_path_frame(c, P, ft, tab, vrt::plan_path(PF), ev, *ev_kind);
             // (a timed frame's closing event is recorded again behind the filter: vrt_stats and VRT_RENDER_TIMED time it with its passes)
             if (!rc) rc = denoise_after_frame(c, P, plan, f.slot, f.st, f.out, ev[3]);
+            // vrt_set_tone_map: the colours the frame's texels now hold are metered (VRT_TONE_AUTO), and the setting is the frame's
+            if (!rc) rc = tone_after_frame(c, f.slot, f.st, f.out, ev[3], &tone_E);
+            frame_tone = c->tone;
         }
         else rc = launch_march_frame(c, P, f, plan, ev, *ev_kind);
         if (rc) {
@@ -832,7 +839,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
 
     // ---- record: the frame is enqueued; from here on the read-backs, the presentation and the statistics speak of it ----
     c->last = vrt_ctx::LastFrame{f.out, f.blk, plan.counts_per_tile ? c->tiles_local : c->n_blocks, f.st, f.slot, tab, o.mode, o.spp ? o.spp : 1u,
-                                 plan.fuse_present, !(plan.fuse_present && P.screen_only), o.stats == 1u};
+                                 plan.fuse_present, !(plan.fuse_present && P.screen_only), o.stats == 1u, frame_tone, tone_E};
     c->rendered = true;
     c->flushed_at_call = false;   // (the next frame's first staged range may go out at its call again: vrt_uploads.hip)
     c->timing_pending = true;

@@ -18,6 +18,7 @@
 #include <atomic>
 
 #include "vrt_tile.h"
+#include "both/tone_math.h"   // (the mapped blits: vrt_set_tone_map)
 #include "vrt_path_common.h"   // (vrt_selftest_exact_math: the RNG's logarithm and direction, both forms)
 
 namespace vrt {
@@ -516,39 +517,62 @@ __global__ void quantize_rgba8_kernel(const Texel *out, uint8_t *rgba8, uint32_t
 // 0 beyond its workgroups — all of it when w and h are multiples of 8).  (Sampling a texture quantised once by its own launch
 // instead — 4 bytes a tap, no quantisation per tap — was measured for windows larger than the texture: no faster, the blit is
 // bound by its ~ 170 vector instructions per pixel, not by its loads: profiles/r04_present_cost.txt.)
-__device__ __forceinline__ void present_tap(const Texel *tex, size_t i, bool covered, const float *decoded, float v[4]) {
+// (quant: a colour channel of a texel as the rgba8unorm texture holds it — QuantPlain, or a mapped frame's QuantTone)
+struct QuantPlain {
+    __device__ __forceinline__ uint32_t operator()(float c) const { return unorm8(c); }
+};
+// vrt_set_tone_map: unorm8(encode(curve(c * E))), both/tone_math.h's text
+struct QuantTone {
+    ToneCurve t;
+    float E;
+    __device__ __forceinline__ QuantTone(const ToneBlit &b) : t{b.curve, b.gamma2, b.white, b.w2}, E(b.E_dev ? *b.E_dev : b.E) {}
+    __device__ __forceinline__ uint32_t operator()(float c) const { return unorm8(tone_map_channel(t, E, c)); }
+};
+template <class Quant>
+__device__ __forceinline__ void present_tap(const Texel *tex, size_t i, bool covered, const float *decoded, float v[4], const Quant &quant) {
     const Texel t = tex[i];
-    v[0] = decoded[unorm8(__uint_as_float(t.x))]; v[1] = decoded[unorm8(__uint_as_float(t.y))]; v[2] = decoded[unorm8(__uint_as_float(t.z))];
+    v[0] = decoded[quant(__uint_as_float(t.x))]; v[1] = decoded[quant(__uint_as_float(t.y))]; v[2] = decoded[quant(__uint_as_float(t.z))];
     v[3] = covered ? 1.0f : 0.0f;
 }
 
+template <class Quant>
 __device__ __forceinline__ uint32_t present_pixel(const Texel *tex, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, uint32_t screen_w, uint32_t screen_h,
-                                                   const vrt_crosshair &ch, uint32_t sx, uint32_t sy, const float *decoded, bool in_box) {
+                                                   const vrt_crosshair &ch, uint32_t sx, uint32_t sy, const float *decoded, bool in_box, const Quant &quant) {
     // (the sample's taps and weights, the crosshair's mask and the blend: vrt_tile.h, shared with the march kernels' own store)
     const PresentSample S = present_sample(w, h, screen_w, screen_h, ch, sx, sy, in_box);
     // alpha: 1 where the compute pass stored a texel, 0 beyond its workgroups (all of it when w and h are multiples of 8)
     float v00[4], v10[4] = {0.f, 0.f, 0.f, 0.f}, v01[4] = {0.f, 0.f, 0.f, 0.f}, v11[4] = {0.f, 0.f, 0.f, 0.f};
-    present_tap(tex, (size_t)S.y0 * w + S.x0, (uint32_t)S.x0 < cov_w && (uint32_t)S.y0 < cov_h, decoded, v00);
+    present_tap(tex, (size_t)S.y0 * w + S.x0, (uint32_t)S.x0 < cov_w && (uint32_t)S.y0 < cov_h, decoded, v00, quant);
     if (!(S.a == 0.0f && S.b == 0.0f)) {
         // (a sample at a texel's centre looks at one tap instead of four: every pixel of a window of the texture's size that
         // present_plain_kernel does not take)
-        present_tap(tex, (size_t)S.y0 * w + S.x1, (uint32_t)S.x1 < cov_w && (uint32_t)S.y0 < cov_h, decoded, v10);
-        present_tap(tex, (size_t)S.y1 * w + S.x0, (uint32_t)S.x0 < cov_w && (uint32_t)S.y1 < cov_h, decoded, v01);
-        present_tap(tex, (size_t)S.y1 * w + S.x1, (uint32_t)S.x1 < cov_w && (uint32_t)S.y1 < cov_h, decoded, v11);
+        present_tap(tex, (size_t)S.y0 * w + S.x1, (uint32_t)S.x1 < cov_w && (uint32_t)S.y0 < cov_h, decoded, v10, quant);
+        present_tap(tex, (size_t)S.y1 * w + S.x0, (uint32_t)S.x0 < cov_w && (uint32_t)S.y1 < cov_h, decoded, v01, quant);
+        present_tap(tex, (size_t)S.y1 * w + S.x1, (uint32_t)S.x1 < cov_w && (uint32_t)S.y1 < cov_h, decoded, v11, quant);
     }
     return present_blend(S, ch, v00, v10, v01, v11);
 }
 
 
-__global__ void present_kernel(const Texel *tex, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, uint32_t screen_w, uint32_t screen_h,
-                               vrt_crosshair ch, uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8) {
+// (the kernel's body: present_kernel with QuantPlain, present_tone_kernel with a mapped frame's QuantTone)
+template <class Quant>
+__device__ __forceinline__ void present_body(const Texel *tex, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, uint32_t screen_w, uint32_t screen_h,
+                                             const vrt_crosshair &ch, uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8, const Quant &quant) {
     __shared__ float s_decoded[256];
     s_decoded[threadIdx.x] = (float)threadIdx.x / 255.0f;   // (256 threads: the launcher's)
     __syncthreads();
     const uint32_t sx = blockIdx.x * blockDim.x + threadIdx.x, sy = blockIdx.y;
     if (sx >= screen_w) return;
     const bool in_box = sx >= box_x0 && sx < box_x1 && sy >= box_y0 && sy < box_y1;
-    reinterpret_cast<uint32_t *>(rgba8)[(size_t)sy * screen_w + sx] = present_pixel(tex, w, h, cov_w, cov_h, screen_w, screen_h, ch, sx, sy, s_decoded, in_box);
+    reinterpret_cast<uint32_t *>(rgba8)[(size_t)sy * screen_w + sx] = present_pixel(tex, w, h, cov_w, cov_h, screen_w, screen_h, ch, sx, sy, s_decoded, in_box, quant);
+}
+__global__ void present_kernel(const Texel *tex, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, uint32_t screen_w, uint32_t screen_h,
+                               vrt_crosshair ch, uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8) {
+    present_body(tex, w, h, cov_w, cov_h, screen_w, screen_h, ch, box_x0, box_x1, box_y0, box_y1, rgba8, QuantPlain{});
+}
+__global__ void present_tone_kernel(const Texel *tex, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, uint32_t screen_w, uint32_t screen_h,
+                                    vrt_crosshair ch, uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8, ToneBlit tone) {
+    present_body(tex, w, h, cov_w, cov_h, screen_w, screen_h, ch, box_x0, box_x1, box_y0, box_y1, rgba8, QuantTone(tone));
 }
 
 // The blit of a window of the texture's size (the reference keeps its texture at 1080 rows and the window's aspect, main.rs:255-262:
@@ -558,8 +582,9 @@ __global__ void present_kernel(const Texel *tex, uint32_t w, uint32_t h, uint32_
 // the floors and the clamps that only find that out again per pixel (~ 110 instructions, two thirds of the blit's issue slots
 // beside a frame that is bound by exactly those) are not executed.  Four pixels per thread: 64 bytes of texels in, 16 bytes out.
 // Inside the box around the crosshair (the host's, a pixel wider than the mask can reach) every pixel takes present_pixel.
-__global__ void __launch_bounds__(256) present_plain_kernel(const Texel *out, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, vrt_crosshair ch,
-                                                            uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8) {
+template <class Quant>
+__device__ __forceinline__ void present_plain_body(const Texel *out, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, vrt_crosshair ch,
+                                                   uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8, Quant quant) {
     __shared__ float s_decoded[256];
     const bool box_row = ch.style != 0u && blockIdx.y >= box_y0 && blockIdx.y < box_y1;   // (uniform)
     if (box_row) {
@@ -571,17 +596,25 @@ __global__ void __launch_bounds__(256) present_plain_kernel(const Texel *out, ui
     uint32_t q[4];
     if (box_row && x4 + 4u > box_x0 && x4 < box_x1) {
 #pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) q[k] = present_pixel(out, w, h, cov_w, cov_h, w, h, ch, x4 + k, sy, s_decoded, true);
+        for (uint32_t k = 0; k < 4u; k++) q[k] = present_pixel(out, w, h, cov_w, cov_h, w, h, ch, x4 + k, sy, s_decoded, true, quant);
     } else {
         Texel t[4];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++) t[k] = out[(size_t)sy * w + x4 + k];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++)
-            q[k] = (x4 + k < cov_w && sy < cov_h ? 0xFF000000u : 0u) | unorm8(__uint_as_float(t[k].x)) | (unorm8(__uint_as_float(t[k].y)) << 8) |
-                   (unorm8(__uint_as_float(t[k].z)) << 16);
+            q[k] = (x4 + k < cov_w && sy < cov_h ? 0xFF000000u : 0u) | quant(__uint_as_float(t[k].x)) | (quant(__uint_as_float(t[k].y)) << 8) |
+                   (quant(__uint_as_float(t[k].z)) << 16);
     }
     reinterpret_cast<uint4 *>(rgba8)[((size_t)sy * w + x4) / 4u] = make_uint4(q[0], q[1], q[2], q[3]);
+}
+__global__ void __launch_bounds__(256) present_plain_kernel(const Texel *out, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, vrt_crosshair ch,
+                                                            uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8) {
+    present_plain_body(out, w, h, cov_w, cov_h, ch, box_x0, box_x1, box_y0, box_y1, rgba8, QuantPlain{});
+}
+__global__ void __launch_bounds__(256) present_plain_tone_kernel(const Texel *out, uint32_t w, uint32_t h, uint32_t cov_w, uint32_t cov_h, vrt_crosshair ch,
+                                                                 uint32_t box_x0, uint32_t box_x1, uint32_t box_y0, uint32_t box_y1, uint8_t *rgba8, ToneBlit tone) {
+    present_plain_body(out, w, h, cov_w, cov_h, ch, box_x0, box_x1, box_y0, box_y1, rgba8, QuantTone(tone));
 }
 
 // Gather root: tile-major [rank][slots_per_rank] texels -> row-major frame of texels.  Tiles are dealt out in periods
@@ -758,13 +791,16 @@ void launch_assemble_shade(const FrameParams &P, const void *gathered, Texel *ds
 // one_to_one: the host's finding for this pair of sizes (screen == texture, every sample at its own texel's centre); box: the
 // pixels the crosshair's mask can reach, [x0, x1) x [y0, y1)
 void launch_present(const Texel *out, uint32_t w, uint32_t h, uint32_t screen_w, uint32_t screen_h, const vrt_crosshair &ch,
-                    uint8_t *rgba8, bool one_to_one, const uint32_t box[4], hipStream_t st) {
+                    uint8_t *rgba8, bool one_to_one, const uint32_t box[4], hipStream_t st, const ToneBlit *tone) {
     if (one_to_one && screen_w == w && screen_h == h && w % 4u == 0u) {
-        hipLaunchKernelGGL(present_plain_kernel, dim3((w / 4u + 255u) / 256u, h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, ch, box[0], box[1], box[2], box[3], rgba8);
+        if (tone) hipLaunchKernelGGL(present_plain_tone_kernel, dim3((w / 4u + 255u) / 256u, h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, ch, box[0], box[1], box[2], box[3], rgba8, *tone);
+        else hipLaunchKernelGGL(present_plain_kernel, dim3((w / 4u + 255u) / 256u, h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, ch, box[0], box[1], box[2], box[3], rgba8);
         return;
     }
-    hipLaunchKernelGGL(present_kernel, dim3((screen_w + 255u) / 256u, screen_h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, screen_w,
-                       screen_h, ch, box[0], box[1], box[2], box[3], rgba8);
+    if (tone) hipLaunchKernelGGL(present_tone_kernel, dim3((screen_w + 255u) / 256u, screen_h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, screen_w,
+                                 screen_h, ch, box[0], box[1], box[2], box[3], rgba8, *tone);
+    else hipLaunchKernelGGL(present_kernel, dim3((screen_w + 255u) / 256u, screen_h), dim3(256), 0, st, out, w, h, w & ~7u, h & ~7u, screen_w,
+                            screen_h, ch, box[0], box[1], box[2], box[3], rgba8);
 }
 
 void launch_assemble(const Texel *gathered, Texel *dst, uint32_t width, uint32_t tiles_x, uint32_t tiles_total,

@@ -132,7 +132,11 @@ static int present_on_device(vrt_ctx *c, const vrt_crosshair *crosshair, uint32_
     const bool one = screen_w == c->width && screen_h == c->height && c->one_to_one;
     uint32_t box[4];
     crosshair_box(crosshair, screen_w, screen_h, box);
-    vrt::launch_present(c->last.out, c->width, c->height, screen_w, screen_h, *crosshair, c->d_screen[k], one, box, st);
+    // a mapped frame (vrt_set_tone_map): the setting as it stood at its vrt_render, its E from the frame set's word on the device
+    const vrt_tone_map &tm = c->last.tone;
+    const vrt::ToneBlit tone{c->last.tone_E, tm.exposure, tm.curve, (tm.flags & VRT_TONE_GAMMA2) ? 1u : 0u, tm.white, tm.white * tm.white};
+    vrt::launch_present(c->last.out, c->width, c->height, screen_w, screen_h, *crosshair, c->d_screen[k], one, box, st,
+                        tm.curve != VRT_TONE_OFF ? &tone : nullptr);
     HIP_TRY(c, hipGetLastError());
     *screen = c->d_screen[k];
     *stream = st;

@@ -195,6 +195,30 @@ class Gpu:
         self._ck(self._lib.vrt_read_guide(self._h, a.ctypes.data_as(C.c_void_p)))
         return a
 
+    def set_tone_map(self, curve: int = _ffi.TONE_FILMIC, exposure: float = 1.0, auto: bool = False, gamma2: bool = False, white: float = 0.0,
+                     key: float = _ffi.TONE_KEY, adapt: float = 1.0, min_auto: float = 0.0, max_auto: float = 0.0,
+                     percentile: int = _ffi.TONE_PERCENTILE, opts=None):
+        """vrt_set_tone_map: every later MODE_PATH frame is presented (present / present_device only) through an exposure and a
+        tone curve — _ffi.TONE_LINEAR / TONE_REINHARD (white: the value mapped to 1) / TONE_FILMIC, gamma2: a square-root encode
+        behind it; curve _ffi.TONE_OFF = off, the default.  auto: the exposure is metered from every frame on the GPU (the
+        percentile-th thousandth of the luminance histogram is brought to key, times `exposure`, within min_auto / max_auto)
+        and adapts by `adapt` of the way per frame.  opts: a ready _ffi.ToneMap instead of the keywords.  Sharded and multi-device
+        contexts refuse a curve."""
+        o = opts if opts is not None else _ffi.tone_setting(curve, exposure, auto, gamma2, white, key, adapt, min_auto, max_auto, percentile)
+        self._ck(self._lib.vrt_set_tone_map(self._h, C.byref(o)))
+
+    def tone_info(self) -> _ffi.ToneInfo:
+        """vrt_get_tone_info: the exposure of the last mapped frame and what it metered (synchronises)."""
+        info = _ffi.ToneInfo()
+        self._ck(self._lib.vrt_get_tone_info(self._h, C.byref(info)))
+        return info
+
+    def tone_histogram(self) -> np.ndarray:
+        """vrt_read_tone_histogram: the 256 luminance bins of the last metered frame (synchronises)."""
+        bins = np.empty(256, dtype=np.uint32)
+        self._ck(self._lib.vrt_read_tone_histogram(self._h, bins.ctypes.data_as(C.c_void_p)))
+        return bins
+
     def set_sun_light(self, strength: float):
         """vrt_set_sun_light: every hit of a later MODE_PATH frame sends a ray to the sun and, where nothing is in the way, adds
         settings.sun_intensity * strength * dot(normal, sun direction) times its colour (0 = off, the default).  The primary
