@@ -233,6 +233,57 @@ pub struct vrt_box_move {
 const _: () = assert!(core::mem::size_of::<vrt_box_query>() == 48);
 const _: () = assert!(core::mem::size_of::<vrt_box_move>() == 32);
 
+pub const VRT_VOXEL_OK: u16 = 0;
+pub const VRT_VOXEL_OUT_OF_BOUNDS: u16 = 1;
+pub const VRT_VOXEL_NO_CHUNK: u16 = 3;
+
+/// `ClientWorld::get_voxel(pos)` (vrt_get_voxels): the voxel when `status` is VRT_VOXEL_OK, else 0 and the SetVoxelErr's number.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_voxel_at {
+    pub voxel: u16,
+    pub status: u16,
+}
+
+pub const VRT_COLUMN_FROM_Y: u32 = 1;
+pub const VRT_COLUMN_SOLID: u32 = 2;
+pub const VRT_COLUMN_NONE: u32 = 0;
+pub const VRT_COLUMN_FOUND: u32 = 1;
+pub const VRT_COLUMN_OUTSIDE: u32 = 2;
+
+/// One `ClientWorld::highest_vox_at` query (vrt_column_tops): the column, and with VRT_COLUMN_FROM_Y where the scan starts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_column_query {
+    pub x: i32,
+    pub z: i32,
+    pub from_y: i32,
+    pub flags: u32,
+}
+
+/// Its answer: the highest voxel that counts when `status` is VRT_COLUMN_FOUND.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_column_top {
+    pub y: i32,
+    pub voxel: u32,
+    pub status: u32,
+    pub _reserved: u32,
+}
+
+/// One column of vrt_read_top_map: `y` is `world.min[1] - 1` and `voxel` 0 where nothing counts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_top_entry {
+    pub y: i32,
+    pub voxel: u32,
+}
+
+const _: () = assert!(core::mem::size_of::<vrt_voxel_at>() == 4);
+const _: () = assert!(core::mem::size_of::<vrt_column_query>() == 16);
+const _: () = assert!(core::mem::size_of::<vrt_column_top>() == 16);
+const _: () = assert!(core::mem::size_of::<vrt_top_entry>() == 8);
+
 /// vrt_set_denoise: the path trace's edge-stopped a-trous filter (passes 0 = off, 1..5; sigma_color 0 = no colour stop).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -427,6 +478,12 @@ extern "C" {
     pub fn vrt_cast_rays_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
     pub fn vrt_clip_moves(ctx: *mut vrt_ctx, queries: *const vrt_box_query, n: u32, out: *mut vrt_box_move) -> c_int;
     pub fn vrt_clip_moves_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
+    pub fn vrt_get_voxels(ctx: *mut vrt_ctx, pos: *const i32, n: u32, out: *mut vrt_voxel_at) -> c_int;
+    pub fn vrt_get_voxels_device(ctx: *mut vrt_ctx, pos_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
+    pub fn vrt_column_tops(ctx: *mut vrt_ctx, queries: *const vrt_column_query, n: u32, out: *mut vrt_column_top) -> c_int;
+    pub fn vrt_column_tops_device(ctx: *mut vrt_ctx, queries_device: *const c_void, n: u32, out_device: *mut c_void) -> c_int;
+    pub fn vrt_read_top_map(ctx: *mut vrt_ctx, flags: u32, map: *mut vrt_top_entry) -> c_int;
+    pub fn vrt_top_map_device(ctx: *mut vrt_ctx, flags: u32, map_device: *mut c_void) -> c_int;
     pub fn vrt_generate_chunks(ctx: *mut vrt_ctx, seed: u32, chunk_pos: *const i32, n: u32, nodes: *mut u16, cap_nodes: u64,
                                offsets: *mut u64) -> c_int;
     pub fn vrt_build_chunks(ctx: *mut vrt_ctx, dense: *const u16, n: u32, nodes: *mut u16, cap_nodes: u64, offsets: *mut u64) -> c_int;

@@ -853,6 +853,76 @@ int vrt_clip_moves(vrt_ctx *ctx, const vrt_box_query *queries, uint32_t n, vrt_b
 /* The same with device memory (n vrt_box_query in, n vrt_box_move out, 4-byte aligned), asynchronous on the context's stream. */
 int vrt_clip_moves_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
 
+/* ClientWorld::get_voxel (client/src/world.rs:352-357), batched, one position per lane: check_bounds — the position lies inside
+ * [min, min + 32 * size_in_chunks) of the context's vrt_world_data on every axis, else VRT_VOXEL_OUT_OF_BOUNDS — then the chunk —
+ * a chunk_roots entry of 0 is "no chunk", VRT_VOXEL_NO_CHUNK, as in vrt_cast_rays — then the voxel of the leaf find_node reaches.
+ * Any int32 coordinate is legal: the box test is made on unsigned differences and nothing overflows.  (The reference's own
+ * check_bounds lets the 31 voxels past each far face through — max_voxel is the last voxel of the chunk after the grid — and
+ * then finds no chunk there: vrth_world_get_voxel answers NoChunk where this call answers OUT_OF_BOUNDS.  Either way no voxel.) */
+#define VRT_VOXEL_OK 0u
+#define VRT_VOXEL_OUT_OF_BOUNDS 1u /* SetVoxelErr::PosOutOfBounds, the number vrth_world_get_voxel returns */
+#define VRT_VOXEL_NO_CHUNK 3u      /* SetVoxelErr::NoChunk */
+typedef struct {
+    uint16_t voxel;  /* 0 unless status == VRT_VOXEL_OK */
+    uint16_t status; /* VRT_VOXEL_* */
+} vrt_voxel_at;  /* 4 B */
+
+/* n positions (n x 3 int32: x, y, z in world voxel coordinates) from host memory, n results into host memory.  Ordering and
+ * scope are vrt_cast_rays's: on the context's stream behind every earlier call — a look-up sees every vrt_write_nodes and
+ * vrt_write_chunk_roots before it, with no frame in between — waiting for its own work only, and leaving everything a frame left
+ * behind (vrt_read_output, vrt_present*, vrt_get_stats, the accumulation) as it was.  n = 0 does nothing.  A multi-device context
+ * answers on device_ids[0]; a sharded context holds the whole world and answers alone. */
+int vrt_get_voxels(vrt_ctx *ctx, const int32_t *pos, uint32_t n, vrt_voxel_at *out);
+/* The same with device memory (n x 3 int32 in, n vrt_voxel_at out, 4-byte aligned), asynchronous on the context's stream. */
+int vrt_get_voxels_device(vrt_ctx *ctx, const void *pos_device, uint32_t n, void *out_device);
+
+/* ClientWorld::highest_vox_at (client/src/world.rs:359-366), batched, one column per lane: the largest y in
+ * [min.y, min.y + 32 * size_in_chunks) at which the voxel of column (x, z) counts.
+ * A voxel counts when its id is not 0 (Voxel::is_empty: liquids count) — or, with VRT_COLUMN_SOLID, when it is SOLID as in
+ * vrt_clip_moves: materials[min(v, 255)].is_empty == 0 && .is_liquid == 0 of the context's material table, so water over sand
+ * answers the sand.  A position in a chunk whose chunk_roots entry is 0 holds Voxel::EMPTY.  Voxel 0 never counts, whatever
+ * entry 0 of the table says: highest_vox_at never reports air.
+ * Without VRT_COLUMN_FROM_Y the scan starts at the top of the world, min.y + 32 * size_in_chunks - 1: highest_vox_at itself.
+ * With it the scan starts at min(from_y, top of the world): a from_y that lies on a counting voxel answers that voxel, and a
+ * from_y below min.y is NONE.  x or z outside the world box is OUTSIDE.  Other bits of flags have no meaning and are ignored.
+ * No query is rejected: every int32 is legal in every field, and a scan ends after the 32 * size_in_chunks voxels of a column
+ * at the latest (the kernel steps over whole leaves that do not count: docs/KERNELS.md). */
+#define VRT_COLUMN_FROM_Y 1u /* start at min(from_y, top of the world) instead of at the top */
+#define VRT_COLUMN_SOLID 2u  /* a voxel counts when it is solid, not merely non-empty */
+typedef struct {
+    int32_t x, z;
+    int32_t from_y;  /* read with VRT_COLUMN_FROM_Y only */
+    uint32_t flags;  /* VRT_COLUMN_FROM_Y | VRT_COLUMN_SOLID */
+} vrt_column_query;  /* 16 B */
+
+#define VRT_COLUMN_NONE 0u    /* nothing counts in the range; y = world.min[1] - 1, voxel = 0 */
+#define VRT_COLUMN_FOUND 1u
+#define VRT_COLUMN_OUTSIDE 2u /* x or z outside the world box; y = 0, voxel = 0 */
+typedef struct {
+    int32_t y;       /* the highest counting voxel's y */
+    uint32_t voxel;  /* its id */
+    uint32_t status; /* VRT_COLUMN_* */
+    uint32_t _reserved; /* 0 */
+} vrt_column_top;  /* 16 B */
+
+/* n queries from host memory, n results into host memory; ordering and scope are vrt_get_voxels's, and with VRT_COLUMN_SOLID
+ * the call sees every vrt_write_materials before it as well. */
+int vrt_column_tops(vrt_ctx *ctx, const vrt_column_query *queries, uint32_t n, vrt_column_top *out);
+/* The same with device memory (n vrt_column_query in, n vrt_column_top out, 4-byte aligned), asynchronous on the context's stream. */
+int vrt_column_tops_device(vrt_ctx *ctx, const void *queries_device, uint32_t n, void *out_device);
+
+/* The whole world from above: the column top of every (x, z) of the world box, (32 * size_in_chunks)^2 entries,
+ * map[(z - min.z) * 32 * size_in_chunks + (x - min.x)] (x fastest).  flags: 0 or VRT_COLUMN_SOLID, anything else is
+ * VRT_ERR_INVALID_ARG; with VRT_COLUMN_SOLID the material table is read in enqueue order, as vrt_column_tops reads it. */
+typedef struct {
+    int32_t y;       /* no voxel of the column counts: world.min[1] - 1 */
+    uint32_t voxel;  /* ... and 0 */
+} vrt_top_entry;  /* 8 B */
+/* Into host memory; ordered as vrt_column_tops, waits for its own work only. */
+int vrt_read_top_map(vrt_ctx *ctx, uint32_t flags, vrt_top_entry *map);
+/* Into device memory (8-byte aligned), asynchronous on the context's stream. */
+int vrt_top_map_device(vrt_ctx *ctx, uint32_t flags, void *map_device);
+
 /* ---- the chunk source: world generation on the device ---- */
 
 /* What the server answers request_missing_chunks with (client/src/lib.rs:80-118: GiveChunkData -> create_chunk), built on

@@ -108,6 +108,24 @@ int vrth_world_clip_move(const vrth_world *w, const vrt_material *mats256, const
 void vrth_world_clip_moves(const vrth_world *w, const vrt_material *mats256, const vrt_box_query *queries, uint32_t n, vrt_box_move *out,
                            int threads);
 
+/* ---- column tops: highest_vox_at with include/vrt.h's flags; csrc/both/column_top.h ---- */
+/* The CPU twin of vrt_get_voxels (include/vrt.h): n x 3 int32 positions in, n vrt_voxel_at records out — vrth_world_get_voxel's
+ * answer inside [min, min + 32 S), VRT_VOXEL_OUT_OF_BOUNDS outside it (the band of 31 voxels past the far faces included, where
+ * vrth_world_get_voxel itself says NoChunk).  threads <= 0: all cores.  The world must not change meanwhile. */
+void vrth_world_get_voxels(const vrth_world *w, const int32_t *pos, uint32_t n, vrt_voxel_at *out, int threads);
+/* The CPU twin of vrt_column_tops (include/vrt.h) and its specification: ClientWorld::highest_vox_at's loop (world.rs:359-366),
+ * every y of the column from the start downwards through get_voxel (an Err is Voxel::EMPTY), with the same start, the same
+ * "counts" and the same record as the GPU's.  mats256 is the material table VRT_COLUMN_SOLID asks; it may be NULL when no
+ * query sets that flag (a NULL table has no solid voxel).  With flags 0 the answer is vrth_world_highest_vox_at's on every column
+ * of the world.  Returns out->status, or -1 for a null argument. */
+int vrth_world_column_top(const vrth_world *w, const vrt_material *mats256, const vrt_column_query *query, vrt_column_top *out);
+/* n of them; threads <= 0: all cores.  The world must not change meanwhile. */
+void vrth_world_column_tops(const vrth_world *w, const vrt_material *mats256, const vrt_column_query *queries, uint32_t n, vrt_column_top *out,
+                            int threads);
+/* The CPU twin of vrt_read_top_map: (32 S)^2 entries, map[(z - min.z) * 32 S + (x - min.x)]; flags 0 or VRT_COLUMN_SOLID.
+ * threads as above.  Returns 0, or -1 for a null world or map or another flag. */
+int vrth_world_top_map(const vrth_world *w, const vrt_material *mats256, uint32_t flags, vrt_top_entry *map, int threads);
+
 /* ---- SVO construction ---- */
 /* Svo::set_node driven the way server/src/world/gen.rs:171-286 drives it (x, z, y ascending, air
  * skipped) from dense[x + 32*(y + 32*z)]. Returns nodes in use (last_used_addr + 1), 0 on OOM. */

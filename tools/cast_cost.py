@@ -13,7 +13,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from voxelraytracing_amd import Gpu, _ffi, scenes  # noqa: E402
-from voxelraytracing_amd.world import ray_queries  # noqa: E402
+from voxelraytracing_amd.world import column_queries, ray_queries  # noqa: E402
 
 
 def camera_rays(sc, n_side):
@@ -60,7 +60,7 @@ def main():
     # the pick: a player's eye 2.5 voxels above the terrain at the world's centre (from C2's own eye, 24 voxels up, nothing is
     # within 10)
     c = sc.world.size_in_chunks() * 16
-    player = np.asarray((c + 0.5, sc.world.highest_vox_at(c, c) + 2.5, c + 0.5), np.float32)
+    player = np.asarray((c + 0.5, int(gpu.column_tops(column_queries([c], [c]))["y"][0]) + 2.5, c + 0.5), np.float32)
     res = {"world": "C2 8^3 procedural", "rays": int(starts.shape[0]), "pick_eye": player.tolist(), "eye": list(sc.eye)}
     for name, md, eye in (("pick_max_dist_10", 10.0, player), ("max_dist_300", 300.0, None)):
         q = ray_queries(starts if eye is None else np.broadcast_to(eye, dirs.shape), dirs, md)

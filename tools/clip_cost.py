@@ -19,15 +19,10 @@ from voxelraytracing_amd.world import box_queries  # noqa: E402
 PLAYER = np.array((0.9, 4.0, 0.9))
 
 
-def player_boxes(world, n, walking, seed=1):
+def player_boxes(world, top, n, walking, seed=1):
+    """top: highest_vox_at per column, [z][x], min.y - 1 where there is none (Gpu.top_map()["y"])."""
     W = world.size_in_voxels()
     lo = np.array(world.min_voxel(), np.float64)
-    top = np.full((W, W), int(lo[1]) - 1, np.int64)   # highest_vox_at per column, [z][x]
-    for z in range(W):
-        for x in range(W):
-            y = world.highest_vox_at(int(lo[0]) + x, int(lo[2]) + z)
-            if y is not None:
-                top[z, x] = y
     rng = np.random.default_rng(seed)
     cxz = lo[[0, 2]] + rng.uniform(1.0, W - 1.0, (n, 2))
     col = np.floor(cxz - lo[[0, 2]]).astype(np.int64)
@@ -71,8 +66,9 @@ def main():
     side = torch.cuda.Stream()   # (not torch's default stream: vrt_set_stream(NULL) would mean the context's own)
     gpu.set_stream(side.cuda_stream)
     res = {"world": "C2 8^3 procedural", "boxes": 1 << 20, "box": PLAYER.tolist(), "warmup_launches": 30, "timed_launches": 50}
+    top = gpu.top_map()["y"].astype(np.int64)   # the ground under every column: one vrt_read_top_map
     for name, walking in (("standing", False), ("walking", True)):
-        q = player_boxes(sc.world, 1 << 20, walking)
+        q = player_boxes(sc.world, top, 1 << 20, walking)
         with torch.cuda.stream(side):
             ms, out = gpu_rate(gpu, q)
         host = sc.world.clip_moves(q, sc.materials)

@@ -156,6 +156,38 @@ class BoxMove(C.Structure):
                 ("_reserved", C.c_uint32)]
 
 
+class VoxelAt(C.Structure):
+    """include/vrt.h vrt_voxel_at: ClientWorld::get_voxel's Result (world.rs:352-357), the voxel or the SetVoxelErr's number"""
+    _fields_ = [("voxel", C.c_uint16), ("status", C.c_uint16)]
+
+
+class ColumnQuery(C.Structure):
+    """include/vrt.h vrt_column_query: highest_vox_at's column (world.rs:359-366), where to start and what counts"""
+    _fields_ = [("x", C.c_int32), ("z", C.c_int32), ("from_y", C.c_int32), ("flags", C.c_uint32)]
+
+
+class ColumnTop(C.Structure):
+    """include/vrt.h vrt_column_top: the highest voxel of a column that counts"""
+    _fields_ = [("y", C.c_int32), ("voxel", C.c_uint32), ("status", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class TopEntry(C.Structure):
+    """include/vrt.h vrt_top_entry: one column of vrt_read_top_map"""
+    _fields_ = [("y", C.c_int32), ("voxel", C.c_uint32)]
+
+
+VOXEL_OK, VOXEL_OUT_OF_BOUNDS, VOXEL_NO_CHUNK = 0, 1, 3    # vrt_voxel_at.status (SetVoxelErr's numbers)
+COLUMN_FROM_Y, COLUMN_SOLID = 1, 2                          # vrt_column_query.flags
+COLUMN_NONE, COLUMN_FOUND, COLUMN_OUTSIDE = 0, 1, 2         # vrt_column_top.status
+# the same records as numpy structured dtypes (4, 16, 16 and 8 bytes)
+VOXEL_AT_DTYPE = np.dtype([("voxel", "<u2"), ("status", "<u2")])
+COLUMN_QUERY_DTYPE = np.dtype([("x", "<i4"), ("z", "<i4"), ("from_y", "<i4"), ("flags", "<u4")])
+COLUMN_TOP_DTYPE = np.dtype([("y", "<i4"), ("voxel", "<u4"), ("status", "<u4"), ("_reserved", "<u4")])
+TOP_ENTRY_DTYPE = np.dtype([("y", "<i4"), ("voxel", "<u4")])
+assert C.sizeof(VoxelAt) == 4 and C.sizeof(ColumnQuery) == 16 and C.sizeof(ColumnTop) == 16 and C.sizeof(TopEntry) == 8
+assert (VOXEL_AT_DTYPE.itemsize, COLUMN_QUERY_DTYPE.itemsize, COLUMN_TOP_DTYPE.itemsize, TOP_ENTRY_DTYPE.itemsize) == (4, 16, 16, 8)
+
+
 class Shape(C.Structure):
     """include/vrt.h vrt_shape: one call of the server's BuiltFeature (server/src/world/gen.rs:312-354)"""
     _fields_ = [("kind", C.c_uint32), ("voxel", C.c_uint32), ("a", C.c_int32 * 3), ("b", C.c_int32 * 3), ("r", C.c_float),
@@ -261,6 +293,12 @@ VRT_SYMBOLS = {
     "vrt_cast_rays_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_clip_moves": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "vrt_clip_moves_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_get_voxels": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_get_voxels_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_column_tops": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_column_tops_device": (C.c_int, [_P, _P, C.c_uint32, _P]),
+    "vrt_read_top_map": (C.c_int, [_P, C.c_uint32, _P]),
+    "vrt_top_map_device": (C.c_int, [_P, C.c_uint32, _P]),
     "vrt_generate_chunks": (C.c_int, [_P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "vrt_build_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P]),
     "vrt_edit_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_uint64, _P, _P]),
@@ -397,6 +435,10 @@ VRTH_SYMBOLS = {
     "vrth_world_get_collisions": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, C.c_uint32, _U32P]),
     "vrth_world_clip_move": (C.c_int, [_P, _P, C.POINTER(BoxQuery), C.POINTER(BoxMove)]),
     "vrth_world_clip_moves": (None, [_P, _P, _P, C.c_uint32, _P, C.c_int]),
+    "vrth_world_get_voxels": (None, [_P, _P, C.c_uint32, _P, C.c_int]),
+    "vrth_world_column_top": (C.c_int, [_P, _P, C.POINTER(ColumnQuery), C.POINTER(ColumnTop)]),
+    "vrth_world_column_tops": (None, [_P, _P, _P, C.c_uint32, _P, C.c_int]),
+    "vrth_world_top_map": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_int]),
     "vrth_world_create_chunks": (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _U32P]),
     "vrth_cam_data_create": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(CamData)]),
     "vrth_axis_rot_to_ray": (None, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -9,6 +9,7 @@
 
 #include "../both/aabb_clip.h"
 #include "graphics.hpp"
+#include "../both/material.h"
 
 namespace vrt {
 
@@ -32,12 +33,9 @@ struct Aabb {  // math.rs:5-126, over ../both/aabb_clip.h's axes
     float clip_z_collide(const Aabb &c, float a) const { return overlap_x(c) && overlap_y(c) ? clip_axis(a, from.z, to.z, c.from.z, c.to.z) : a; }
 };
 
-// voxelpack.get(voxel).is_solid() (common/src/resources/mod.rs:309) as the material table holds it: Material::construct
-// (graphics/mod.rs:38-46) sets is_empty for Gas and is_liquid for Liquid; ids >= 255 share entry 255 as on the GPU
-inline bool is_solid(const Material *mats256, Voxel v) {
-    const Material &m = mats256[v.as_data() < 255 ? v.as_data() : 255];
-    return m.is_empty == 0u && m.is_liquid == 0u;
-}
+// voxelpack.get(voxel).is_solid() (common/src/resources/mod.rs:309) as the material table holds it: ../both/material.h's,
+// the text the GPU's queries compile too
+inline bool is_solid(const Material *mats256, Voxel v) { return material_solid(mats256, v.as_data()); }
 
 // get_collisions_w, world.rs:369-391: the solid voxels' positions in gather order (each stands for Aabb [p, p + 1])
 inline std::vector<VoxelPos> get_collisions_w(const ClientWorld &w, const Aabb &aabb, const Material *mats256) {

@@ -9,6 +9,7 @@
 
 #include "../../../include/vrt_host.h"
 #include "../both/cast_dda.h"
+#include "../both/column_top.h"
 #include "../both/denoise_math.h"
 #include "../both/lens_math.h"
 #include "../both/shape_math.h"
@@ -219,6 +220,90 @@ int vrth_world_highest_vox_at(const vrth_world *w, int32_t x, int32_t z, int32_t
     if (!y) return 0;
     if (y_out) *y_out = *y;
     return 1;
+}
+
+// ---- column tops (../both/column_top.h): highest_vox_at's loop, every voxel of the column through get_voxel ----
+// One column against a solid set made once (solid_set); the x / z test is include/vrt.h's box, not check_bounds' (whose far
+// faces lie 31 voxels further out, where get_voxel then finds no chunk)
+static void column_top(const ClientWorld &w, const uint32_t solid[8], const vrt_column_query &q, vrt_column_top &r) {
+    const VoxelPos lo = w.min_voxel();
+    const uint32_t W = w.size_in_voxels();
+    const uint32_t ux = (uint32_t)q.x - (uint32_t)lo.x, uz = (uint32_t)q.z - (uint32_t)lo.z;
+    if (!(ux < W && uz < W)) {
+        column_outside(r);
+        return;
+    }
+    uint32_t uy;
+    if (column_start(q.flags, q.from_y, lo.y, W, uy)) {
+        for (;; uy--) {
+            Voxel v;   // get_voxel(pos) or Voxel::EMPTY
+            if (w.get_voxel(VoxelPos{q.x, (int32_t)((uint32_t)lo.y + uy), q.z}, v) != SetVoxelErr::Ok) v = Voxel();
+            if (column_counts(v.as_data(), q.flags, solid)) {
+                column_found(r, lo.y, uy, v.as_data());
+                return;
+            }
+            if (uy == 0u) break;
+        }
+    }
+    column_none(r, lo.y);
+}
+
+// get_voxel as vrt_get_voxels records it: include/vrt.h's box first (see above), then ClientWorld::get_voxel's own answer
+void vrth_world_get_voxels(const vrth_world *w, const int32_t *pos, uint32_t n, vrt_voxel_at *out, int threads) {
+    if (!w || !pos || !out || !n) return;
+    const VoxelPos lo = w->w.min_voxel();
+    const uint32_t W = w->w.size_in_voxels();
+    parallel_blocks(n, 4096, threads, ~0u, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) {
+            const int32_t *p = pos + 3 * i;
+            vrt_voxel_at r{0, (uint16_t)VRT_VOXEL_OUT_OF_BOUNDS};
+            if ((uint32_t)p[0] - (uint32_t)lo.x < W && (uint32_t)p[1] - (uint32_t)lo.y < W && (uint32_t)p[2] - (uint32_t)lo.z < W) {
+                Voxel v;
+                r.status = (uint16_t)w->w.get_voxel(VoxelPos{p[0], p[1], p[2]}, v);
+                r.voxel = r.status == VRT_VOXEL_OK ? v.as_data() : (uint16_t)0;
+            }
+            out[i] = r;
+        }
+        return true;
+    });
+}
+
+int vrth_world_column_top(const vrth_world *w, const vrt_material *mats256, const vrt_column_query *q, vrt_column_top *out) {
+    if (!w || !q || !out) return -1;
+    uint32_t solid[8];
+    solid_set(mats256, solid);
+    column_top(w->w, solid, *q, *out);
+    return (int)out->status;
+}
+
+void vrth_world_column_tops(const vrth_world *w, const vrt_material *mats256, const vrt_column_query *q, uint32_t n, vrt_column_top *out,
+                            int threads) {
+    if (!w || !q || !out || !n) return;
+    uint32_t solid[8];
+    solid_set(mats256, solid);
+    parallel_blocks(n, 1024, threads, ~0u, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) column_top(w->w, solid, q[i], out[i]);
+        return true;
+    });
+}
+
+int vrth_world_top_map(const vrth_world *w, const vrt_material *mats256, uint32_t flags, vrt_top_entry *map, int threads) {
+    if (!w || !map || (flags & ~VRT_COLUMN_SOLID)) return -1;
+    uint32_t solid[8];
+    solid_set(mats256, solid);
+    const VoxelPos lo = w->w.min_voxel();
+    const size_t W = w->w.size_in_voxels();
+    parallel_blocks(W * W, 256, threads, ~0u, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; i++) {
+            const vrt_column_query q{(int32_t)((uint32_t)lo.x + (uint32_t)(i % W)), (int32_t)((uint32_t)lo.z + (uint32_t)(i / W)), 0, flags};
+            vrt_column_top r;
+            column_top(w->w, solid, q, r);
+            map[i].y = r.y;
+            map[i].voxel = r.voxel;
+        }
+        return true;
+    });
+    return 0;
 }
 
 void vrth_world_data_from(const vrth_world *w, vrt_world_data *out) { *out = WorldData::from(w->w); }

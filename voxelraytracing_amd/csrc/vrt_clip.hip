@@ -12,6 +12,7 @@
 // stepped over along z (nothing is gathered there, so the order of what is gathered stands).
 #include "vrt_query.h"
 #include "both/aabb_clip.h"
+#include "both/material.h"
 
 namespace vrt {
 
@@ -29,12 +30,8 @@ struct ClipBox {
     float fx, fy, fz, tx, ty, tz;   // Aabb.from, Aabb.to
 };
 
-// voxelpack.get(v).is_solid() as the material table holds it (Material::construct, graphics/mod.rs:38-46); ids >= 255 share
-// entry 255 as everywhere else
-__device__ __forceinline__ bool clip_solid(const ClipParams &P, uint32_t v) {
-    const vrt_material *m = &P.mats[min(v, 255u)];
-    return m->is_empty == 0u && m->is_liquid == 0u;
-}
+// voxelpack.get(v).is_solid() as the material table holds it: both/material.h's, which the column queries ask too
+__device__ __forceinline__ bool clip_solid(const ClipParams &P, uint32_t v) { return material_solid(P.mats, v); }
 
 // world(&bbox.expand(mv)) and the loop over it (player.rs:208-215 / :226-233): (ax, ay, az) enter as mv and leave clipped,
 // count = the boxes gathered.  False: the range holds more than VRT_BOX_MAX_VOXELS voxels (asked of the first pass only).

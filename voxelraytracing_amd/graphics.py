@@ -91,6 +91,8 @@ class Gpu:
         self._h = h
         self.result_size = (result_size[0], result_size[1])
         self.shard_rank, self.shard_count = shard_rank, shard_count
+        self._roots_size = int(world_size)   # the chunk_roots buffer holds _roots_size^3 entries: no world is larger (validate_frame)
+        self._world_size = 0                 # vrt_world_data.size_in_chunks as last written
 
     def close(self):
         if getattr(self, "_h", None):
@@ -116,6 +118,7 @@ class Gpu:
 
     def resize_chunk_buffer(self, world_size: int):
         self._ck(self._lib.vrt_resize_world(self._h, world_size))
+        self._roots_size = int(world_size)
 
     def write_materials(self, mats, first: int = 0, n: Optional[int] = None):
         n = len(mats) if n is None else n
@@ -150,6 +153,7 @@ class Gpu:
 
     def write_world_data(self, w: WorldData):
         self._ck(self._lib.vrt_set_world(self._h, C.byref(w)))
+        self._world_size = int(w.size_in_chunks)   # (top_map sizes its array by it)
 
     def resize_result_texture(self, new_size):
         self._ck(self._lib.vrt_resize_output(self._h, new_size[0], new_size[1]))
@@ -404,6 +408,48 @@ class Gpu:
         """vrt_clip_moves_device: n vrt_box_query records at a device address in, n vrt_box_move records out, enqueued on the
         context's stream (vrt_set_stream) without waiting."""
         self._ck(self._lib.vrt_clip_moves_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
+
+    def get_voxels(self, positions) -> np.ndarray:
+        """ClientWorld::get_voxel (world.rs:352-357) for every (n,3) integer position at once on the GPU, against the world as of
+        every write so far: _ffi.VOXEL_AT_DTYPE records (voxel, status = VOXEL_OK / VOXEL_OUT_OF_BOUNDS / VOXEL_NO_CHUNK)."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        out = np.zeros(pos.shape[0], _ffi.VOXEL_AT_DTYPE)
+        self._ck(self._lib.vrt_get_voxels(self._h, pos.ctypes.data, pos.shape[0], out.ctypes.data))
+        return out
+
+    def get_voxels_device(self, pos_ptr: int, n: int, out_ptr: int):
+        """vrt_get_voxels_device: n x 3 int32 at a device address in, n vrt_voxel_at records out, enqueued on the context's stream
+        (vrt_set_stream) without waiting."""
+        self._ck(self._lib.vrt_get_voxels_device(self._h, C.c_void_p(pos_ptr or None), n, C.c_void_p(out_ptr or None)))
+
+    def column_tops(self, queries: np.ndarray) -> np.ndarray:
+        """ClientWorld::highest_vox_at (world.rs:359-366) with include/vrt.h's flags for every column at once on the GPU, against
+        the world and the material table as of every write so far: _ffi.COLUMN_QUERY_DTYPE records (world.column_queries) in,
+        _ffi.COLUMN_TOP_DTYPE records out."""
+        q = np.ascontiguousarray(queries, _ffi.COLUMN_QUERY_DTYPE)
+        out = np.zeros(q.size, _ffi.COLUMN_TOP_DTYPE)
+        self._ck(self._lib.vrt_column_tops(self._h, q.ctypes.data, q.size, out.ctypes.data))
+        return out
+
+    def column_tops_device(self, queries_ptr: int, n: int, out_ptr: int):
+        """vrt_column_tops_device: n vrt_column_query records at a device address in, n vrt_column_top records out, enqueued on
+        the context's stream (vrt_set_stream) without waiting."""
+        self._ck(self._lib.vrt_column_tops_device(self._h, C.c_void_p(queries_ptr or None), n, C.c_void_p(out_ptr or None)))
+
+    def top_map(self, solid: bool = False) -> np.ndarray:
+        """vrt_read_top_map: the whole world from above, _ffi.TOP_ENTRY_DTYPE records [z - min.z][x - min.x]; a column where
+        nothing counts holds y = min.y - 1, voxel 0.  solid: VRT_COLUMN_SOLID."""
+        W = 32 * self._world_size   # (0: no world set yet, and the library says so)
+        # room for the largest world the context can hold, whatever it was last told: the library writes (32 S)^2 entries
+        cap = 32 * max(self._roots_size, self._world_size, 1)
+        buf = np.zeros(cap * cap, _ffi.TOP_ENTRY_DTYPE)
+        self._ck(self._lib.vrt_read_top_map(self._h, _ffi.COLUMN_SOLID if solid else 0, buf.ctypes.data))
+        return buf[:W * W].reshape(W, W).copy()
+
+    def top_map_device(self, map_ptr: int, flags: int = 0):
+        """vrt_top_map_device: (32 S)^2 vrt_top_entry records to a device address (8-byte aligned), enqueued on the context's
+        stream (vrt_set_stream) without waiting."""
+        self._ck(self._lib.vrt_top_map_device(self._h, flags, C.c_void_p(map_ptr or None)))
 
     # --- the chunk source (include/vrt.h vrt_generate_chunks / vrt_build_chunks / vrt_edit_chunks) ---
     def generate_chunks(self, seed: int, positions, strict: bool = True):

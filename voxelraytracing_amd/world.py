@@ -293,6 +293,43 @@ class ClientWorld:
         y = C.c_int32()
         return y.value if self._lib.vrth_world_highest_vox_at(self._h, x, z, C.byref(y)) else None
 
+    def get_voxels(self, positions, threads: int = 0) -> np.ndarray:
+        """get_voxel for every (n,3) integer position on the CPU (vrth_world_get_voxels), as vrt_get_voxels records it:
+        _ffi.VOXEL_AT_DTYPE records (voxel, status = VOXEL_OK / VOXEL_OUT_OF_BOUNDS / VOXEL_NO_CHUNK)."""
+        pos = np.ascontiguousarray(np.asarray(positions, np.int32).reshape(-1, 3))
+        out = np.zeros(pos.shape[0], _ffi.VOXEL_AT_DTYPE)
+        if pos.shape[0]:
+            self._lib.vrth_world_get_voxels(self._h, pos.ctypes.data, pos.shape[0], out.ctypes.data, threads)
+        return out
+
+    # --- column tops (csrc/both/column_top.h): materials is a (Material * 256) table or None when no query sets COLUMN_SOLID ---
+    def column_top(self, x: int, z: int, from_y=None, solid: bool = False, materials=None) -> _ffi.ColumnTop:
+        """highest_vox_at with include/vrt.h's flags (vrth_world_column_top): the whole vrt_column_top record.  from_y: start at
+        min(from_y, top of the world); solid: a voxel counts when the material table says it is solid."""
+        q = _ffi.ColumnQuery(x, z, 0 if from_y is None else from_y,
+                             (0 if from_y is None else _ffi.COLUMN_FROM_Y) | (_ffi.COLUMN_SOLID if solid else 0))
+        out = _ffi.ColumnTop()
+        self._lib.vrth_world_column_top(self._h, C.cast(materials, C.c_void_p), C.byref(q), C.byref(out))
+        return out
+
+    def column_tops(self, queries: np.ndarray, materials=None, threads: int = 0) -> np.ndarray:
+        """Many of them on the CPU (vrth_world_column_tops): _ffi.COLUMN_QUERY_DTYPE records (column_queries) in,
+        _ffi.COLUMN_TOP_DTYPE records out."""
+        q = np.ascontiguousarray(queries, _ffi.COLUMN_QUERY_DTYPE)
+        out = np.zeros(q.size, _ffi.COLUMN_TOP_DTYPE)
+        if q.size:
+            self._lib.vrth_world_column_tops(self._h, C.cast(materials, C.c_void_p), q.ctypes.data, q.size, out.ctypes.data, threads)
+        return out
+
+    def top_map(self, solid: bool = False, materials=None, threads: int = 0) -> np.ndarray:
+        """The whole world from above on the CPU (vrth_world_top_map): _ffi.TOP_ENTRY_DTYPE records [z - min.z][x - min.x]; a
+        column where nothing counts holds y = min.y - 1, voxel 0."""
+        W = self.size_in_voxels()
+        out = np.zeros((W, W), _ffi.TOP_ENTRY_DTYPE)
+        if self._lib.vrth_world_top_map(self._h, C.cast(materials, C.c_void_p), _ffi.COLUMN_SOLID if solid else 0, out.ctypes.data, threads):
+            raise ValueError("top_map: a null world")
+        return out
+
     # --- region files (servercli/src/main.rs:25-73) ---
     def load_region(self, data: bytes, region_pos) -> int:
         """create_chunk every chunk of a reference region file that lies inside the grid; returns how many."""
@@ -369,6 +406,20 @@ def box_queries(froms, tos, mvs, autojump=True) -> np.ndarray:
     q["to"] = np.asarray(tos, np.float32).reshape(-1, 3)
     q["mv"] = np.asarray(mvs, np.float32).reshape(-1, 3)
     q["flags"] = np.where(np.broadcast_to(np.asarray(autojump, bool), q.shape), _ffi.BOX_AUTOJUMP, 0)
+    return q
+
+
+def column_queries(xs, zs, from_y=None, solid=False) -> np.ndarray:
+    """vrt_column_query records (_ffi.COLUMN_QUERY_DTYPE) from (n,) xs and zs; from_y: None (the top of the world), a scalar or
+    (n,); solid: a bool or (n,)."""
+    xs = np.asarray(xs, np.int32).reshape(-1)
+    q = np.zeros(xs.size, _ffi.COLUMN_QUERY_DTYPE)
+    q["x"] = xs
+    q["z"] = np.asarray(zs, np.int32).reshape(-1)
+    if from_y is not None:
+        q["from_y"] = np.broadcast_to(np.asarray(from_y, np.int32), q.shape)
+        q["flags"] |= _ffi.COLUMN_FROM_Y
+    q["flags"] |= np.where(np.broadcast_to(np.asarray(solid, bool), q.shape), _ffi.COLUMN_SOLID, 0).astype(np.uint32)
     return q
 
 
