@@ -1,6 +1,6 @@
 """Case builders for the emission tests (vrt_write_emission): tables, scenes and the comparison.  TEST INFRASTRUCTURE ONLY.
 
-tests/test_emission_cases.py counts on the reference alone (tests/emission_ref.c) that each case holds what it claims;
+tests/test_emission_cases.py counts on the reference alone (tests/emission_ref.py) that each case holds what it claims;
 tests/test_gpu_emission_matrix.py renders the same cases on the GPU.  The tables are float32[256]; the scenes are
 voxelraytracing_amd.scenes.Scene objects, each with a world of its own."""
 import numpy as np

@@ -9,7 +9,7 @@ tiles, 65 536 traced pixels — a segment has one producer, part is 0 everywhere
 are past that.
 
 Every case is scenes.c4's world seen from its own eye; the cases marked with a rotation look down (every primary ray hits).
-`segment_loads` is what a launch puts into each segment, from a plane of tests/lamp_ref.c's `load` output."""
+`segment_loads` is what a launch puts into each segment, from a plane of tests/lamp_ref.py's `load` output."""
 from __future__ import annotations
 
 from collections import namedtuple

@@ -1,87 +1,42 @@
-"""ctypes wrapper of tests/sun_ref.c: the path trace with direct sunlight (vrt_set_sun_light) on top of the emission, polish and
-translucency tables — tests/translucent_ref.c's loop with a sun ray from every hit, as include/vrt.h defines it.  TEST
-INFRASTRUCTURE ONLY.
-
-``load(directory)`` compiles it with oracle/Makefile's own CFLAGS (strict IEEE: no contraction, no fast-math) into
-`directory` — a pytest temporary directory, never the source tree — and loads it; the scene struct is oracle/orc.py's."""
+"""The tests' reference for direct sunlight (vrt_set_sun_light) on top of the emission, polish and translucency tables:
+tests/path_ref.c's loop with camera sampling and lamp light off — a sun ray from every hit, as include/vrt.h defines it.  TEST
+INFRASTRUCTURE ONLY."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
 from collections import namedtuple
 
-import numpy as np
-
-import polish_ref
-import translucent_ref
-from emission_ref import oracle_cflags
-from oracle import orc
-from voxelraytracing_amd._ffi import POLISH_DTYPE, TRANSLUCENCY_DTYPE
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
+import path_ref
+from path_ref import _tables  # noqa: F401
 
 # of one render: the sun rays marched, the unoccluded ones, the later segments' misses through the sun's disc, the lookups of
 # every march (path segments and sun rays), the path segments behind the primary ones
 Counts = namedtuple("Counts", "sun_rays unoccluded disc_misses steps bounce_segments")
 
 
-def _tables(emission, polish, translucency):
-    e = np.zeros(256, dtype=np.float32)
-    if emission is not None:
-        em = np.asarray(emission, dtype=np.float32).reshape(-1)
-        e[:em.size] = em
-    p = polish_ref.table()
-    if polish is not None:
-        po = np.asarray(polish, dtype=POLISH_DTYPE).reshape(-1)
-        p[:po.size] = po
-    t = translucent_ref.table()
-    if translucency is not None:
-        tr = np.asarray(translucency, dtype=TRANSLUCENCY_DTYPE).reshape(-1)
-        t[:tr.size] = tr
-    return e, p, t
+def _counts(n: path_ref.Counts) -> Counts:
+    return Counts(n.sun_rays, n.sun_unoccluded, n.disc_misses, n.steps, n.bounce_segments)
 
 
 class SunRef:
-    def __init__(self, so: str):
-        L = C.CDLL(so)
-        u32, f32 = C.c_uint32, C.c_float
-        L.ref_render_path_sun.restype = None
-        L.ref_render_path_sun.argtypes = [C.POINTER(orc.Scene), C.POINTER(f32), C.c_void_p, C.c_void_p, f32, u32, u32, u32, u32, u32,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ref_trace_pixel_sun.restype = None
-        L.ref_trace_pixel_sun.argtypes = [C.POINTER(orc.Scene), C.POINTER(f32), C.c_void_p, C.c_void_p, f32, u32, u32, u32, u32, u32, u32,
-                                          C.c_void_p, C.c_void_p]
-        self._lib = L
+    def __init__(self, ref: path_ref.PathRef):
+        self._ref = ref
         self.counts = Counts(0, 0, 0, 0, 0)   # of the last render
 
-    def render(self, scene: "orc.OracleScene", strength: float, w: int, h: int, spp: int = 1, seed: int = 0, sample_base: int = 0,
-               emission=None, polish=None, translucency=None):
+    def render(self, scene, strength: float, w: int, h: int, spp: int = 1, seed: int = 0, sample_base: int = 0, emission=None, polish=None,
+               translucency=None):
         """(rgb [h, w, 3] f32, ids [h, w] u32) of samples sample_base .. sample_base + spp - 1 with the sun term's factor
         `strength` (0: off) under the three 256-entry tables (None = zeros)."""
-        e, p, t = _tables(emission, polish, translucency)
-        rgb = np.zeros((h, w, 3), dtype=np.float32)
-        ids = np.zeros((h, w), dtype=np.uint32)
-        n = np.zeros(5, dtype=np.uint64)
-        self._lib.ref_render_path_sun(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, strength,
-                                      w, h, spp, seed, sample_base, rgb.ctypes.data, ids.ctypes.data, n.ctypes.data)
-        self.counts = Counts(*(int(x) for x in n))
+        rgb, ids, n = self._ref.render(scene, w, h, spp, seed, sample_base, sun=strength, emission=emission, polish=polish, translucency=translucency)
+        self.counts = _counts(n)
         return rgb, ids
 
-    def trace_pixel(self, scene: "orc.OracleScene", strength: float, w: int, h: int, px: int, py: int, sample: int = 0, seed: int = 0,
-                    emission=None, polish=None, translucency=None):
+    def trace_pixel(self, scene, strength: float, w: int, h: int, px: int, py: int, sample: int = 0, seed: int = 0, emission=None, polish=None,
+                    translucency=None):
         """(light [3] f32, Counts) of one sample of one pixel of a w x h frame."""
-        e, p, t = _tables(emission, polish, translucency)
-        light = np.zeros(3, dtype=np.float32)
-        n = np.zeros(5, dtype=np.uint64)
-        self._lib.ref_trace_pixel_sun(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data, t.ctypes.data, strength,
-                                      w, h, px, py, sample, seed, light.ctypes.data, n.ctypes.data)
-        return light, Counts(*(int(x) for x in n))
+        light, _, _, n = self._ref.trace_pixel(scene, w, h, px, py, sample, seed, sun=strength, emission=emission, polish=polish,
+                                               translucency=translucency)
+        return light, _counts(n)
 
 
 def load(directory) -> SunRef:
-    """Compile tests/sun_ref.c into `directory` and load it."""
-    so = os.path.join(str(directory), "libsun_ref.so")
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc, *oracle_cflags(), "-shared", "-o", so, os.path.join(_HERE, "sun_ref.c"), "-lm"])
-    return SunRef(so)
+    return SunRef(path_ref.load(directory))

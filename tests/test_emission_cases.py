@@ -1,4 +1,4 @@
-"""The cases of tests/emission_cases.py hold what they claim: counted on the reference alone (tests/emission_ref.c and the plain
+"""The cases of tests/emission_cases.py hold what they claim: counted on the reference alone (tests/emission_ref.py and the plain
 oracle), without a GPU.  Each claim has a floor of 50 pixels, as tests/test_emission_ref.py uses, and prints its count.
 
 Also here: what the reference says about tables that should change nothing (liquids, air, -0.0)."""

@@ -1,5 +1,6 @@
-"""tests/emission_ref.c, the tests' reference for the emission table (vrt_write_emission), without a GPU: with a table of
-zeros it is the oracle's path trace bit for bit, and on a case small enough to check by hand it adds what the contract says."""
+"""tests/emission_ref.py, the tests' reference for the emission table (vrt_write_emission: tests/path_ref.c with every later term
+off), without a GPU: with a table of zeros it is the oracle's path trace bit for bit, and on a case small enough to check by
+hand it adds what the contract says."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 """Emissive materials in the path trace (vrt_write_emission, include/vrt.h) on the GPU.
 
-Against tests/emission_ref.c (the oracle's path loop with path_tracer.wgsl's emission term) for every variant, sample count and
+Against tests/emission_ref.py (the oracle's path loop with path_tracer.wgsl's emission term) for every variant, sample count and
 frames in flight; a table of zeros renders exactly as no table; emission only adds light; accumulated emissive frames are one
 frame of all their samples, bit for bit; what restarts the sum and what is refused; shards and devices."""
 import numpy as np

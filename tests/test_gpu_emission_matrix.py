@@ -1,4 +1,4 @@
-"""The emissive path kernels beyond C4's defaults, against tests/emission_ref.c: both layouts of the march cells, every bounce
+"""The emissive path kernels beyond C4's defaults, against tests/emission_ref.py: both layouts of the march cells, every bounce
 count, every route and switch of the bounce launch, mirrors and mixed scatter, rays that run out of lookups, lone waves and the
 edges of the table.  The cases are tests/emission_cases.py's; tests/test_emission_cases.py counts on the CPU what each holds.
 

@@ -5,7 +5,7 @@ split cell, in a size-2 leaf, an 8^3 block, lamps across a chunk border, on the 
 water; a world that gives off nothing; a cut-off list; and after a node edit, an emission write and a change of the liquid
 set, with one and two frames in flight.
 
-Frames against tests/lamp_ref.c on every route through the kernels — the default, the march cells behind a chunk directory, the
+Frames against tests/lamp_ref.py on every route through the kernels — the default, the march cells behind a chunk directory, the
 literal march (air flagged liquid) and the counting kernels of a stats frame — at one wave, two waves and a frame that is not
 whole tiles; 1, 2 and 4 bounces; 1 and 3 samples; the lamps alone and together with the sun, a second emissive material, a coat,
 two pass-through materials and camera sampling: util.assert_frame_parity.  A stats frame's secondary rays and steps are the

@@ -1,5 +1,5 @@
 """The lamp list of vrt_set_lamp_light (vrt_lamp.hip: a count per workgroup, a one-workgroup scan, an ordered write under a cap) held
-to tests/lamp_ref.py's list where test_gpu_lamp.py does not reach, and the frames that index it to tests/lamp_ref.c.
+to tests/lamp_ref.py's list where test_gpu_lamp.py does not reach, and the frames that index it to its frames (tests/path_ref.c).
 
 A. Worlds of 9^3 and 11^3 chunks (lamp_cases.scan_world): 1458 and 2662 workgroups, so a scan thread owns 2 or 3 sums, one thread
    a clipped range and the ones behind it nothing; faces in workgroup 0, in the last one, in workgroups of one thread and in

@@ -1,6 +1,6 @@
 """Camera sampling in the path trace (vrt_set_camera_sampling, include/vrt.h) on the GPU.
 
-Against tests/lens_ref.c (tests/sun_ref.c's loop with a primary ray of its own for every sample) on every route through the
+Against tests/lens_ref.py (tests/sun_ref.py's loop with a primary ray of its own for every sample) on every route through the
 kernels — the default (several samples per launch chain, the pool kernel behind bounce 0), the march cells behind a chunk
 directory, the literal march (air flagged liquid) and the counting kernels of a stats frame — at one wave, two waves, a frame
 whose size is not whole tiles and a frame of several workgroups; 1, 2 and 4 bounces; 1, 3 and 12 samples (12: more than one

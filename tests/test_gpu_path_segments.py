@@ -1,4 +1,4 @@
-"""The path-trace kernel families past 256 primary workgroups, against tests/lamp_ref.c.
+"""The path-trace kernel families past 256 primary workgroups, against tests/lamp_ref.py.
 
 Every launch of the wavefront path trace hands its records — paths, sun rays, lamp rays — to the next through 256 segments
 (vrt_device.h: kHitSegments): workgroup k appends to segment k % 256, and the consuming launch's workgroup `part` = k / 256 of a

@@ -1,6 +1,6 @@
 """Polished materials in the path trace (vrt_write_polish, include/vrt.h) on the GPU.
 
-Against tests/polish_ref.c (the oracle's path loop with path_tracer.wgsl's emission term and its coat) on every route through
+Against tests/polish_ref.py (the oracle's path loop with path_tracer.wgsl's emission term and its coat) on every route through
 the kernels, both layouts of the march cells, every bounce count, one sample per chain, lone waves and the edges of the table;
 a table without a chance renders exactly as no table; accumulated polished frames are one frame of all their samples, bit for
 bit; what restarts the sum and what is refused; the primary modes; shards and devices.  Frames against the reference:

@@ -1,6 +1,6 @@
 """Direct sunlight in the path trace (vrt_set_sun_light, include/vrt.h) on the GPU.
 
-Against tests/sun_ref.c (the oracle's path loop with a sun ray from every hit) on every route through the kernels — the default
+Against tests/sun_ref.py (the oracle's path loop with a sun ray from every hit) on every route through the kernels — the default
 (the occlusion-only march over the march cells in the direct layout), the march cells behind a chunk directory, the literal
 march (air flagged liquid) and the counting kernels of a stats frame — at one wave, two waves, a frame whose size is not whole
 tiles and a frame of several workgroups; 1, 2 and 4 bounces; 1, 3 and 12 samples; one and two frames in flight; the sun alone and

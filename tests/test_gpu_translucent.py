@@ -1,6 +1,6 @@
 """Translucent materials in the path trace (vrt_write_translucency, include/vrt.h) on the GPU.
 
-Against tests/translucent_ref.c (the oracle's path loop with path_tracer.wgsl's emission term, its coat and the pass-through
+Against tests/translucent_ref.py (the oracle's path loop with path_tracer.wgsl's emission term, its coat and the pass-through
 lobe) on every route through the kernels, both layouts of the march cells, every bounce count, one sample per chain, lone waves
 and the edges of the table; a table without a chance renders exactly as no table; accumulated translucent frames are one frame
 of all their samples, bit for bit; what restarts the sum and what is refused; the primary modes; the denoiser; shards and

@@ -1,5 +1,7 @@
-"""tests/lens_ref.c, the tests' reference for camera sampling in the path trace (vrt_set_camera_sampling), without a GPU: with the
-setting off it is tests/sun_ref.c bit for bit; with it on, the id words are the off frame's (they come from the pixel's own pinhole
+"""tests/lens_ref.py, the tests' reference for camera sampling in the path trace (vrt_set_camera_sampling: tests/path_ref.c with lamp
+light off), without a GPU: with the setting off it is the sun reference bit for bit — its frames and counts as
+tests/golden/path_ref_pins.json recorded them — and with the sun off too and no table the oracle's path trace; with it on, the id
+words are the off frame's (they come from the pixel's own pinhole
 ray) while the four draws shift every sample's stream; on C4 at the sizes the GPU tests use, jittered samples do land on other
 faces than their pixel's centre and every lens sample leaves from another point than the camera; one sample's ray is followed
 by hand in numpy binary32 and held against the reference's and against the text the kernels compile (csrc/both/lens_math.h,
@@ -15,8 +17,7 @@ import numpy as np
 import pytest
 
 import lens_ref
-import sun_ref
-from emission_cases import common
+from golden.make_path_ref_pins import is_frame, load_pins
 from test_sun_ref import _tables
 from voxelraytracing_amd import _ffi, scenes
 
@@ -24,6 +25,7 @@ SEED = 11
 F = np.float32
 JITTER, FOCUS = (1.0, 0.0, 0.0), 32.0
 LENS, BOTH = (0.0, 0.25, FOCUS), (1.0, 0.25, FOCUS)
+PINS = load_pins()
 
 
 @pytest.fixture(scope="module")
@@ -31,31 +33,37 @@ def lref(tmp_path_factory):
     return lens_ref.load(tmp_path_factory.mktemp("lens_ref"))
 
 
-@pytest.fixture(scope="module")
-def sref(tmp_path_factory):
-    return sun_ref.load(tmp_path_factory.mktemp("sun_ref"))
-
-
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.parametrize("spp", [1, 3])
-def test_off_is_the_sun_reference(lref, sref, orc, spp):
+def test_off_is_the_sun_reference(lref, orc, spp):
     W, H = 64, 40
     sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
     o = orc.from_package_scene(sc)
     _, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=1, seed=SEED)
     e, p, t = _tables(plain_ids)
-    for tables in ((None, None, None), (e, p, t)):
+    for name, tables in (("T0", (None, None, None)), ("T2", (e, p, t))):
         for strength in (0.0, 1.0):
-            want_rgb, want_ids = sref.render(o, strength, W, H, spp=spp, seed=SEED, emission=tables[0], polish=tables[1], translucency=tables[2])
+            want = PINS[f"sun/{name}/strength{strength!r}/spp{spp}"]   # (the sun reference's frame, from before the two were one loop)
+            sun_rays, _, _, steps, bounce_segments = want["counts"]     # (tests/sun_ref.py: Counts)
             for off in (lens_ref.OFF, (-0.0, -0.0, 5.0)):
                 rgb, ids = lref.render(o, off, W, H, spp=spp, seed=SEED, strength=strength, emission=tables[0], polish=tables[1], translucency=tables[2])
-                assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+                assert is_frame((rgb, ids), want)
                 n = lref.counts
-                assert (n.steps, n.bounce_segments, n.sun_rays) == (sref.counts.steps, sref.counts.bounce_segments, sref.counts.sun_rays)
+                assert (n.steps, n.bounce_segments, n.sun_rays) == (steps, bounce_segments, sun_rays)
                 assert n.jitter_changed == 0 and n.lens_moved == 0
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+def test_everything_off_is_the_oracles_path_trace(lref, orc, spp):
+    W, H = 64, 40
+    sc = scenes.c4((W, H))   # (kept alive)
+    o = orc.from_package_scene(sc)
+    want_rgb, want_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=spp, seed=SEED)
+    rgb, ids = lref.render(o, lens_ref.OFF, W, H, spp=spp, seed=SEED)
+    assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
 
 
 @pytest.mark.parametrize("size", [(100, 60), (128, 72)])

@@ -1,27 +1,25 @@
-"""tests/polish_ref.c, the tests' reference for the polish table (vrt_write_polish), without a GPU: with a table of zeros it
-is tests/emission_ref.c and the oracle's path trace bit for bit, one bounce sees no table, the coat's draw is taken on every
-hit of a polished frame, and on a case small enough to check by hand it does what the contract says."""
+"""tests/polish_ref.py, the tests' reference for the polish table (vrt_write_polish: tests/path_ref.c with every later term off),
+without a GPU: with a table of zeros it is the emission reference — its frames as tests/golden/path_ref_pins.json recorded them —
+and the oracle's path trace bit for bit, one bounce sees no table, the coat's draw is taken on every hit of a polished frame, and
+on a case small enough to check by hand it does what the contract says."""
 import numpy as np
 import pytest
 
 import emission_ref
 import polish_ref
 from emission_cases import common
+from golden.make_path_ref_pins import is_frame, load_pins, sha
 from voxelraytracing_amd import scenes
 
 SEED = 11
 W, H = 64, 40
 F = np.float32
+PINS = load_pins()
 
 
 @pytest.fixture(scope="module")
 def pref(tmp_path_factory):
     return polish_ref.load(tmp_path_factory.mktemp("polish_ref"))
-
-
-@pytest.fixture(scope="module")
-def eref(tmp_path_factory):
-    return emission_ref.load(tmp_path_factory.mktemp("emission_ref"))
 
 
 def _bits(a):
@@ -39,7 +37,7 @@ def test_it_compiles_with_the_oracles_flags(pref):
 
 
 @pytest.mark.parametrize("spp", [1, 3, 8])
-def test_a_table_of_zeros_is_the_emission_reference_and_the_oracle(pref, eref, orc, spp):
+def test_a_table_of_zeros_is_the_emission_reference_and_the_oracle(pref, orc, spp):
     sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
     o = orc.from_package_scene(sc)
     plain_rgb, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=spp, seed=SEED)
@@ -48,11 +46,10 @@ def test_a_table_of_zeros_is_the_emission_reference_and_the_oracle(pref, eref, o
     zeros = polish_ref.table()
     zeros["color"], zeros["scatter"] = (0.25, 0.5, 0.75), 0.5   # (a chance of 0, whatever the other fields hold)
     zeros["chance"][1::2] = -0.0
-    want_rgb, want_ids = eref.render(o, e, W, H, spp=spp, seed=SEED)
-    rgb, ids = pref.render(o, e, zeros, W, H, spp=spp, seed=SEED)
-    assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+    want = PINS[f"emission/E2/spp{spp}"]   # (the emission reference's frame under this table, from before the two were one loop)
+    assert is_frame(pref.render(o, e, zeros, W, H, spp=spp, seed=SEED), want)
     assert pref.polished_bounces == 0
-    assert not np.array_equal(_bits(want_rgb), _bits(plain_rgb))   # (the emission table is not a no-op here)
+    assert want["rgb"] != sha(plain_rgb)   # (the emission table is not a no-op here)
     rgb, ids = pref.render(o, None, zeros, W, H, spp=spp, seed=SEED)
     assert np.array_equal(ids, plain_ids) and np.array_equal(_bits(rgb), _bits(plain_rgb))
 

@@ -1,7 +1,9 @@
-"""tests/sun_ref.c, the tests' reference for direct sunlight in the path trace (vrt_set_sun_light), without a GPU: with strength 0
-it is tests/translucent_ref.c bit for bit; the sun term draws nothing, so the id words are the sun-off frame's; on C4 at the
-sizes the GPU tests use, sun rays are launched, some are occluded and some are not, and later segments do leave through the
-sun's disc; and the sum order — emission term, then sun term — is followed by hand in numpy binary32 on one-segment paths."""
+"""tests/sun_ref.py, the tests' reference for direct sunlight in the path trace (vrt_set_sun_light: tests/path_ref.c with camera
+sampling and lamp light off), without a GPU: with strength 0 it is the translucent reference bit for bit — its frames as
+tests/golden/path_ref_pins.json recorded them — and with no table the oracle's path trace; the sun term draws nothing, so the id
+words are the sun-off frame's; on C4 at the sizes the GPU tests use, sun rays are launched, some are occluded and some are not,
+and later segments do leave through the sun's disc; and the sum order — emission term, then sun term — is followed by hand in
+numpy binary32 on one-segment paths."""
 import numpy as np
 import pytest
 
@@ -9,21 +11,18 @@ import polish_ref
 import sun_ref
 import translucent_ref
 from emission_cases import common
+from golden.make_path_ref_pins import is_frame, load_pins
 from voxelraytracing_amd import scenes
 
 SEED = 11
 F = np.float32
 BIAS = F(0.002)   # oracle/vrt_oracle.c: ORC_SHADOW_BIAS
+PINS = load_pins()
 
 
 @pytest.fixture(scope="module")
 def sref(tmp_path_factory):
     return sun_ref.load(tmp_path_factory.mktemp("sun_ref"))
-
-
-@pytest.fixture(scope="module")
-def tref(tmp_path_factory):
-    return translucent_ref.load(tmp_path_factory.mktemp("translucent_ref"))
 
 
 def _bits(a):
@@ -46,18 +45,28 @@ def test_it_compiles_with_the_oracles_flags(sref):
 
 
 @pytest.mark.parametrize("spp", [1, 3])
-def test_strength_0_is_the_translucent_reference(sref, tref, orc, spp):
+def test_strength_0_is_the_translucent_reference(sref, orc, spp):
     W, H = 64, 40
     sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
     o = orc.from_package_scene(sc)
     _, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=1, seed=SEED)
     e, p, t = _tables(plain_ids)
-    for tables in ((None, None, None), (e, None, None), (e, p, t)):
-        want_rgb, want_ids = tref.render(o, *tables, W, H, spp=spp, seed=SEED)
+    for name, tables in (("T0", (None, None, None)), ("T1", (e, None, None)), ("T2", (e, p, t))):
+        want = PINS[f"translucent/{name}/spp{spp}"]   # (the translucent reference's frame, from before the two were one loop)
         for strength in (0.0, -0.0):
             rgb, ids = sref.render(o, strength, W, H, spp=spp, seed=SEED, emission=tables[0], polish=tables[1], translucency=tables[2])
-            assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+            assert is_frame((rgb, ids), want)
             assert sref.counts.sun_rays == 0 and sref.counts.unoccluded == 0 and sref.counts.disc_misses == 0
+
+
+@pytest.mark.parametrize("spp", [1, 3])
+def test_everything_off_is_the_oracles_path_trace(sref, orc, spp):
+    W, H = 64, 40
+    sc = scenes.c4((W, H))   # (kept alive)
+    o = orc.from_package_scene(sc)
+    want_rgb, want_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=spp, seed=SEED)
+    rgb, ids = sref.render(o, 0.0, W, H, spp=spp, seed=SEED)
+    assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
 
 
 @pytest.mark.parametrize("size", [(128, 72), (100, 60)])

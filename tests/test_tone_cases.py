@@ -1,4 +1,4 @@
-"""What keeps tests/test_gpu_tone.py from being vacuous, held to the CPU path reference (tests/sun_ref.c: the oracle's path loop
+"""What keeps tests/test_gpu_tone.py from being vacuous, held to the CPU path reference (tests/sun_ref.py: the oracle's path loop
 with the sun term and the emission table): the main scene's luminance histogram is spread out and counts most of the frame, and
 the two views the adaptation test alternates between meter exposures far apart."""
 import numpy as np

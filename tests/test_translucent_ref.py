@@ -1,27 +1,25 @@
-"""tests/translucent_ref.c, the tests' reference for the translucency table (vrt_write_translucency), without a GPU: with a
-table of zero chances it is tests/polish_ref.c bit for bit, one bounce sees no table, the draw is taken on every hit of a
-translucent frame, and where every hit passes a path is one straight line that numpy can follow by hand."""
+"""tests/translucent_ref.py, the tests' reference for the translucency table (vrt_write_translucency: tests/path_ref.c with every
+later term off), without a GPU: with a table of zero chances it is the polish reference bit for bit — its frames as
+tests/golden/path_ref_pins.json recorded them — one bounce sees no table, the draw is taken on every hit of a translucent frame,
+and where every hit passes a path is one straight line that numpy can follow by hand."""
 import numpy as np
 import pytest
 
 import polish_ref
 import translucent_ref
 from emission_cases import common
+from golden.make_path_ref_pins import is_frame, load_pins
 from voxelraytracing_amd import scenes
 
 SEED = 11
 W, H = 64, 40
 F = np.float32
+PINS = load_pins()
 
 
 @pytest.fixture(scope="module")
 def tref(tmp_path_factory):
     return translucent_ref.load(tmp_path_factory.mktemp("translucent_ref"))
-
-
-@pytest.fixture(scope="module")
-def pref(tmp_path_factory):
-    return polish_ref.load(tmp_path_factory.mktemp("polish_ref"))
 
 
 def _bits(a):
@@ -44,7 +42,7 @@ def test_it_compiles_with_the_oracles_flags(tref):
 
 
 @pytest.mark.parametrize("spp", [1, 3])
-def test_a_table_of_zero_chances_is_the_polish_reference(tref, pref, orc, spp):
+def test_a_table_of_zero_chances_is_the_polish_reference(tref, orc, spp):
     sc = scenes.c4((W, H))   # (kept alive: the oracle's scene points into it)
     o = orc.from_package_scene(sc)
     plain_rgb, plain_ids, _, _ = o.render(orc.MODE_PATH, W, H, spp=spp, seed=SEED)
@@ -54,9 +52,10 @@ def test_a_table_of_zero_chances_is_the_polish_reference(tref, pref, orc, spp):
     zeros["color"] = (0.25, 7.5, 0.75)   # (a chance of 0, whatever the colours hold)
     zeros["chance"][1::2] = -0.0
     for emission, polish in ((None, None), (e, None), (None, _some_polish()), (e, _some_polish())):
-        want_rgb, want_ids = pref.render(o, emission, polish, W, H, spp=spp, seed=SEED)
+        # the polish reference's frame under these tables, from before the two were one loop
+        want = PINS[f"polish/{'none' if emission is None else 'E2'}+{'none' if polish is None else 'some'}/spp{spp}"]
         rgb, ids = tref.render(o, emission, polish, zeros, W, H, spp=spp, seed=SEED)
-        assert np.array_equal(ids, want_ids) and np.array_equal(_bits(rgb), _bits(want_rgb))
+        assert is_frame((rgb, ids), want)
         assert tref.passes == 0
         if emission is None and polish is None:
             assert np.array_equal(ids, plain_ids) and np.array_equal(_bits(rgb), _bits(plain_rgb))

@@ -1,6 +1,6 @@
 """The scene tests/test_gpu_tone.py meters and maps, and the views its adaptation test alternates between: C4's world under
 vrt_set_sun_light with one emissive material, so that a frame's radiance spans many octaves.  tests/test_tone_cases.py holds the
-conditions that keep those tests from being vacuous to the CPU path reference (tests/sun_ref.c); the GPU tests check them again
+conditions that keep those tests from being vacuous to the CPU path reference (tests/sun_ref.py); the GPU tests check them again
 on the frames they read back."""
 import functools
 

@@ -1,69 +1,24 @@
-"""ctypes wrapper of tests/translucent_ref.c: the path trace with the per-material emission, polish and translucency tables
-(vrt_write_emission, vrt_write_polish, vrt_write_translucency), the oracle's loop with path_tracer.wgsl's emission term, its
-coat and the pass-through lobe as include/vrt.h defines it.  TEST INFRASTRUCTURE ONLY.
-
-``load(directory)`` compiles it with oracle/Makefile's own CFLAGS (strict IEEE: no contraction, no fast-math) into
-`directory` — a pytest temporary directory, never the source tree — and loads it; the scene struct is oracle/orc.py's."""
+"""The tests' reference for the emission, polish and translucency tables (vrt_write_emission, vrt_write_polish,
+vrt_write_translucency): tests/path_ref.c's loop with every later term off — the oracle's loop with path_tracer.wgsl's emission
+term, its coat and the pass-through lobe as include/vrt.h defines it.  TEST INFRASTRUCTURE ONLY."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
-import numpy as np
-
-import polish_ref
-from emission_ref import oracle_cflags
-from oracle import orc
-from voxelraytracing_amd._ffi import POLISH_DTYPE, TRANSLUCENCY_DTYPE
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def table(entries=None):
-    """A 256-entry translucency table of zeros with `entries` ({index: (chance, (r, g, b))}) filled in."""
-    t = np.zeros(256, dtype=TRANSLUCENCY_DTYPE)
-    for i, (chance, color) in (entries or {}).items():
-        t[i]["chance"], t[i]["color"] = chance, color
-    return t
+import path_ref
+from path_ref import translucency_table as table  # noqa: F401
 
 
 class TranslucentRef:
-    def __init__(self, so: str):
-        L = C.CDLL(so)
-        u32 = C.c_uint32
-        L.ref_render_path_translucent.restype = C.c_uint64
-        L.ref_render_path_translucent.argtypes = [C.POINTER(orc.Scene), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, u32, u32, u32, u32, u32,
-                                                  C.c_void_p, C.c_void_p]
-        self._lib = L
+    def __init__(self, ref: path_ref.PathRef):
+        self._ref = ref
         self.passes = 0   # of the last render: how many times a path passed through a voxel
 
-    def render(self, scene: "orc.OracleScene", emission, polish, translucency, w: int, h: int, spp: int = 1, seed: int = 0,
-               sample_base: int = 0):
+    def render(self, scene, emission, polish, translucency, w: int, h: int, spp: int = 1, seed: int = 0, sample_base: int = 0):
         """(rgb [h, w, 3] f32, ids [h, w] u32) of samples sample_base .. sample_base + spp - 1 under the three 256-entry tables
         (emission: float32; polish: POLISH_DTYPE; translucency: TRANSLUCENCY_DTYPE; None = zeros)."""
-        e = np.zeros(256, dtype=np.float32)
-        if emission is not None:
-            em = np.asarray(emission, dtype=np.float32).reshape(-1)
-            e[:em.size] = em
-        p = polish_ref.table()
-        if polish is not None:
-            po = np.asarray(polish, dtype=POLISH_DTYPE).reshape(-1)
-            p[:po.size] = po
-        t = table()
-        if translucency is not None:
-            tr = np.asarray(translucency, dtype=TRANSLUCENCY_DTYPE).reshape(-1)
-            t[:tr.size] = tr
-        rgb = np.zeros((h, w, 3), dtype=np.float32)
-        ids = np.zeros((h, w), dtype=np.uint32)
-        self.passes = int(self._lib.ref_render_path_translucent(C.byref(scene.c), e.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data,
-                                                                t.ctypes.data, w, h, spp, seed, sample_base, rgb.ctypes.data, ids.ctypes.data))
+        rgb, ids, n = self._ref.render(scene, w, h, spp, seed, sample_base, emission=emission, polish=polish, translucency=translucency)
+        self.passes = n.passes
         return rgb, ids
 
 
 def load(directory) -> TranslucentRef:
-    """Compile tests/translucent_ref.c into `directory` and load it."""
-    so = os.path.join(str(directory), "libtranslucent_ref.so")
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc, *oracle_cflags(), "-shared", "-o", so, os.path.join(_HERE, "translucent_ref.c"), "-lm"])
-    return TranslucentRef(so)
+    return TranslucentRef(path_ref.load(directory))
