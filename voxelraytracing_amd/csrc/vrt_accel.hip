@@ -544,16 +544,24 @@ __global__ void __launch_bounds__(256) upload_batch_kernel(uint32_t *dst0, uint3
 //
 // A cell is LIT when a shadow ray whose position is anywhere in it meets nothing from there to the world's face.  The host has
 // picked the axis `a` on which the sun lies beyond the world (on the side `up`), and made sure that on the two other axes no ray
-// towards the sun moves more than 0.99 voxels per voxel of `a` (LitPass, vrt_uploads.hip: lit_plan).  A ray inside one layer of cells
-// (4 voxels of `a`) therefore moves less than one cell sideways — 0.99 * 4.001 voxels, the steps' 0.001 nudges and their roundings: 3.976, 0.024 voxels short
-// of 4 (docs/NUMERICS.md) — and only towards the sun's side of where it is: towards lower coordinates only if the sun is below some point of the cell
-// (widened by one voxel: a ray's positions stray from its line by the nudges, less than 500 * 0.001), towards higher ones only if
-// above.  So, for the cell's FOOTPRINT — itself and the up to three neighbours of its layer on the sun's side(s), nine where the sun
-// stands over the cell:
-//     lit(cell)  <=>  every footprint cell is an air leaf of at least `min_lo + 1` voxels (or outside the world), and
-//                     the cells behind the footprint in the next layer towards the sun are lit (or outside the world).
-// The layers are swept from the sun's side, so the next layer's marks are final when a layer reads them.  Every air leaf of the
-// grid gets its bit written, set or clear: nothing of an earlier sun or an earlier world survives a pass.
+// towards the sun moves more than 0.99 voxels per voxel of `a` (LitPass, vrt_uploads.hip: lit_plan).  A ray with a position in
+// cell C has the direction of a line to the sun through a point of C widened by one voxel (its positions stray from its line by
+// the nudges, less than 500 * 0.001, and their roundings), so on each other axis `b` its slope (sun_b - q_b) / (sun_a - q_a) lies
+// between the smallest and the largest one over the widened cell.  Layers are counted from C towards the sun; while the ray is in
+// layer c_a + k it has risen between max(0, 4k - 5) and 4k + 5 voxels on `a` since it was in C, so its `b` lies in
+//     [4 c_b + rise * slope_min - allow_k,  4 c_b + 4 + rise * slope_max + allow_k]      (each end with the rise that widens it)
+// (and never beyond C's own cell on a side no ray of C points to: a ray's coordinates are monotone)
+// where allow_k covers the nudges and roundings of the steps in between (0.015 per layer, never more than a ray's 500 steps can
+// add up to: 1) and this kernel's own binary32 arithmetic (0.01).  The cells overlapping that interval on both axes are
+// REACH_k(C): what a ray of C can be in while in layer c_a + k — a corridor along the rays, not a pyramid that widens by a cell
+// per layer.  For a slab of `depth` layers whose sun-side end is m layers from C's layer (m = 1 .. depth):
+//     lit(C)  <=>  for k = 0 .. m - 1 every cell of REACH_k(C) inside the world is an air leaf of at least `min_lo + 1` voxels, and
+//                  every cell a ray of C can be in when it enters layer c_a + m is lit (or outside the world).
+// The slabs are swept from the sun's side, so the marks behind a slab are final when it reads them, and all cells of a slab are
+// independent: G / depth dependent launches.  depth = G is the whole corridor in one launch; depth = 1 has the reach of a sweep
+// layer by layer.  Every air leaf of the grid gets its bit written, set or clear: nothing of an earlier sun or an earlier world
+// survives a pass.  (A cell's bit is written while neighbours test its entry: they ask `>= kAirLeaf` and `& 31`, which the bit
+// leaves alone.)
 struct LitPass {
     uint32_t G;          // cells per axis
     uint32_t axis;       // 0, 1, 2: x, y, z
@@ -562,57 +570,90 @@ struct LitPass {
     float sun[3];        // settings.sun_pos - f32(world.min), as the shadow ray subtracts from it
 };
 
-// Layers first .. first + count - 1, counted from the sun's side.  count > 1: ONE workgroup walks them (a barrier between layers);
-// count == 1: any number of workgroups.
-__global__ void __launch_bounds__(1024) accel_lit_kernel(uint32_t *grid, LitPass lp, uint32_t first, uint32_t count) {
+// The cells of axis `b` a ray of cell c_b can be in after a rise of r_lo .. r_hi voxels, as [lo, hi] clamped to the world;
+// false: all of them lie outside it.  s_min / s_max: the slopes over the widened cell.
+__device__ inline bool lit_reach(float c4, float s_min, float s_max, float r_lo, float r_hi, float allow, uint32_t G, uint32_t *lo, uint32_t *hi) {
+    const float b_lo = c4 + (s_min < 0.0f ? r_hi : r_lo) * s_min - allow;
+    const float b_hi = c4 + 4.0f + (s_max > 0.0f ? r_hi : r_lo) * s_max + allow;
+    int l = (int)floorf(b_lo * 0.25f), h = (int)floorf(b_hi * 0.25f);
+    // a coordinate is monotone along a ray (a step adds a rounded product of the direction's sign): where no ray of the cell points
+    // to lower `b` none gets below the cell it is in, whatever the allowance says, and likewise above
+    const int own = (int)(c4 * 0.25f);
+    if (!(s_min < 0.0f)) l = max(l, own);
+    if (!(s_max > 0.0f)) h = min(h, own);
+    if (h < 0 || l >= (int)G) return false;
+    *lo = (uint32_t)max(l, 0);
+    *hi = (uint32_t)min(h, (int)G - 1);
+    return true;
+}
+
+// Smallest and largest slope on `b` of a line to the sun through the widened cell: sun_b - q_b in [n_lo, n_hi], sun_a - q_a in
+// [d_lo, d_hi] (d_lo > 0: the sun lies beyond the widened world).
+__device__ inline void lit_slopes(float n_lo, float n_hi, float d_lo, float d_hi, float *s_min, float *s_max) {
+    *s_min = n_lo / (n_lo < 0.0f ? d_lo : d_hi);
+    *s_max = n_hi / (n_hi > 0.0f ? d_lo : d_hi);
+}
+
+// One slab: layers first .. first + count - 1, counted from the sun's side; a thread per cell.
+__global__ void __launch_bounds__(256) accel_lit_kernel(uint32_t *grid, LitPass lp, uint32_t first, uint32_t count) {
     const uint32_t G = lp.G, G1 = G + 1u;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count * G * G) return;
     const uint32_t a = lp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // the two other axes, the lower one fastest
     const size_t row = G1, slab = (size_t)G1 * G1;
     const size_t sa = a == 0u ? 1u : a == 1u ? row : slab, su = u == 0u ? 1u : row, sv = v == 1u ? row : slab;   // strides of [z][y][x]
-    const float sun_u = u == 0u ? lp.sun[0] : lp.sun[1], sun_v = v == 1u ? lp.sun[1] : lp.sun[2];
-    for (uint32_t k = first; k < first + count; k++) {
-        const uint32_t ca = lp.up ? G - 1u - k : k;
-        const bool next_inside = lp.up ? ca + 1u < G : ca > 0u;
-        const size_t next_off = lp.up ? sa : (size_t)0 - sa;
-        for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < G * G; t += gridDim.x * blockDim.x) {
-            const uint32_t cu = t % G, cv = t / G;
-            const size_t at = ca * sa + cu * su + cv * sv;
-            const uint32_t e = grid[at];
-            if (e < kAirLeaf) continue;   // not an air leaf: no mark
-            // which way a ray in this cell can move on u and v
-            const float u0 = (float)(cu * 4u), v0 = (float)(cv * 4u);
-            const int ulo = sun_u <= u0 + 5.0f ? -1 : 0, uhi = sun_u >= u0 - 1.0f ? 1 : 0;
-            const int vlo = sun_v <= v0 + 5.0f ? -1 : 0, vhi = sun_v >= v0 - 1.0f ? 1 : 0;
-            bool lit = true;
-            for (int dv = vlo; dv <= vhi; dv++)
-                for (int du = ulo; du <= uhi; du++) {
-                    const uint32_t nu = cu + (uint32_t)du, nv = cv + (uint32_t)dv;
-                    if (nu >= G || nv >= G) continue;   // (also -1: unsigned) outside the world
-                    const size_t n = ca * sa + nu * su + nv * sv;
-                    const uint32_t own = grid[n];
-                    lit = lit && own >= kAirLeaf && (own & 31u) >= lp.min_lo;
-                    if (next_inside) {
-                        const uint32_t nx = grid[n + next_off];
-                        lit = lit && nx >= kAirLeaf && !(nx & kAirUnlit);
-                    }
-                }
-            grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
-        }
-        if (count > 1u) __syncthreads();   // (one workgroup: the layer's marks are written before the next layer reads them)
+    const uint32_t cu = t % G, cv = (t / G) % G, j = t / (G * G);
+    const uint32_t ca = lp.up ? G - 1u - (first + j) : first + j;
+    const size_t at = ca * sa + cu * su + cv * sv;
+    const uint32_t e = grid[at];
+    if (e < kAirLeaf) return;   // not an air leaf: no mark
+    // the sweep's own frame: `a` mirrored when the sun is below, so that it grows towards the sun; i: the cell's layer there
+    const float W = (float)(G * 4u);
+    const float sun_a = lp.up ? lp.sun[a] : W - lp.sun[a], sun_u = lp.sun[u], sun_v = lp.sun[v];
+    const float a4 = (float)((G - 1u - (first + j)) * 4u), u4 = (float)(cu * 4u), v4 = (float)(cv * 4u);
+    const float d_lo = sun_a - (a4 + 5.0f), d_hi = sun_a - (a4 - 1.0f);
+    float us_min, us_max, vs_min, vs_max;
+    lit_slopes(sun_u - (u4 + 5.0f), sun_u - (u4 - 1.0f), d_lo, d_hi, &us_min, &us_max);
+    lit_slopes(sun_v - (v4 + 5.0f), sun_v - (v4 - 1.0f), d_lo, d_hi, &vs_min, &vs_max);
+    const size_t step = lp.up ? sa : (size_t)0 - sa;   // one layer towards the sun
+    bool lit = true;
+    size_t layer = ca * sa;
+    for (uint32_t k = 0; k <= j && lit; k++, layer += step) {
+        const float r_lo = k >= 2u ? (float)(4u * k - 5u) : 0.0f, r_hi = (float)(4u * k + 5u);
+        const float allow = fminf(0.015f * (float)(k + 1u), 1.0f) + 0.01f;
+        uint32_t ul, uh, vl, vh;
+        if (!lit_reach(u4, us_min, us_max, r_lo, r_hi, allow, G, &ul, &uh) || !lit_reach(v4, vs_min, vs_max, r_lo, r_hi, allow, G, &vl, &vh)) continue;
+        for (uint32_t nv = vl; nv <= vh; nv++)
+            for (uint32_t nu = ul; nu <= uh; nu++) {
+                const uint32_t own = grid[layer + nu * su + nv * sv];
+                lit = lit && own >= kAirLeaf && (own & 31u) >= lp.min_lo;
+            }
     }
+    if (lit && first > 0u) {   // the layer behind the slab: its marks are final
+        const uint32_t m = j + 1u;
+        const float r_lo = m >= 2u ? (float)(4u * m - 5u) : 0.0f, r_hi = (float)(4u * m + 1u) + 0.01f;
+        const float allow = fminf(0.015f * (float)(m + 1u), 1.0f) + 0.01f;
+        uint32_t ul, uh, vl, vh;
+        if (lit_reach(u4, us_min, us_max, r_lo, r_hi, allow, G, &ul, &uh) && lit_reach(v4, vs_min, vs_max, r_lo, r_hi, allow, G, &vl, &vh))
+            for (uint32_t nv = vl; nv <= vh; nv++)
+                for (uint32_t nu = ul; nu <= uh; nu++) {
+                    const uint32_t nx = grid[layer + nu * su + nv * sv];
+                    lit = lit && nx >= kAirLeaf && !(nx & kAirUnlit);
+                }
+    }
+    grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
 }
 
 }  // namespace
 
-// The lit pass over the whole grid, on `st`.  Small grids: one launch of one workgroup that walks the layers; large ones: a launch per layer.
-void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], hipStream_t st) {
+// The lit pass over the whole grid, on `st`: a launch per slab of `depth` layers, from the sun's side (the last one may be short).
+void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st) {
     const LitPass lp{G, axis, up ? 1u : 0u, min_lo, {sun[0], sun[1], sun[2]}};
-    if (G <= 64u) {
-        hipLaunchKernelGGL(accel_lit_kernel, dim3(1), dim3(1024), 0, st, grid, lp, 0u, G);
-        return;
+    if (depth < 1u) depth = 1u;
+    for (uint32_t first = 0; first < G; first += depth) {
+        const uint32_t count = G - first < depth ? G - first : depth;
+        hipLaunchKernelGGL(accel_lit_kernel, dim3((count * G * G + 255u) / 256u), dim3(256), 0, st, grid, lp, first, count);
     }
-    const uint32_t blocks = (G * G + 1023u) / 1024u;
-    for (uint32_t k = 0; k < G; k++) hipLaunchKernelGGL(accel_lit_kernel, dim3(blocks), dim3(1024), 0, st, grid, lp, k, 1u);
 }
 
 void launch_upload_batch(void *dst0, void *dst1, const void *pinned_ring, const UploadBatch &batch, uint32_t n_pieces, hipStream_t st) {

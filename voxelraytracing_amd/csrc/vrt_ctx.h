@@ -121,7 +121,7 @@ void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t
                          uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *tail, uint16_t *bricks,
                          uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail, uint32_t block_cap, const uint32_t liquid[8],
                          const uint32_t *chunks, const uint32_t *extents, const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done);
-void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], hipStream_t st);
+void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st);
 }  // namespace vrt
 
 // Host-time profile of the frame path (VRT_HOST_PROF=1: printed at process exit): where the calling thread's microseconds per
@@ -332,6 +332,7 @@ struct vrt_ctx {
     uint32_t path_refill = 0;      // VRT_PATH_POOL_REFILL: idle lanes that send a bounce wave back to its pool (0: the default, 16)
     uint32_t accel_builds = 0;
     bool sun_marks = true;         // VRT_SUN_MARKS=0: shadow rays never stop at lit cells (the A/B of profiles/DECISIONS.md)
+    uint32_t lit_slab = 0;         // VRT_LIT_SLAB: layers a launch of the lit pass tests a cell's corridor over (1: layer by layer; 0: by grid size, vrt_uploads.hip)
     uint32_t lit_passes = 0;       // lit passes launched (vrt_get_sun_marks)
     uint32_t lit_last_min_leaf = 0, lit_last_trips = 0;   // of the last one-launch shadow frame: 0 = its marks were off
     // longest tiles first (vrt_kernels.hip: tile_order_*), for a context that renders one frame at a time

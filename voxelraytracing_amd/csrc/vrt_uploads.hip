@@ -589,7 +589,20 @@ static bool lit_plan(uint32_t world_size, const float sun[3], LitPlan *lp) {
     return false;
 }
 
-// Ordered like the chunk updates of update_tables, which it follows on the frame's stream `st`: the pass is a launch (or G launches)
+// How many layers a launch of the lit pass tests a cell's corridor over before it relies on the marks behind (vrt_accel.hip): the
+// largest depth whose pass pays for itself within 100 frames of the world it is built for, measured per grid size
+// (profiles/lit_corridor_ab.txt).  Up to 64 cells a side the whole corridor: one launch, 97 us where the sweep layer by layer took
+// 305, and 5.7 us off every frame.  Larger grids gain no frame time at any depth (their marks sit on leaves of 8 or 16 voxels, high
+// over the terrain), so a depth qualifies while its pass is no dearer than the layer-by-layer sweep's, for a sun on any axis:
+// 32 up to 128 cells a side (312 us against 494; the whole corridor: 769), 8 above (313 us against 696 for 240 cells; 16 is dearer
+// than the sweep for a sun on x).  VRT_LIT_SLAB overrides: the A/B, and the tests' comparison of the rules inside one build
+// (1: the reach of a sweep layer by layer).
+static uint32_t lit_slab_depth(const vrt_ctx *c, uint32_t G) {
+    const uint32_t depth = c->lit_slab ? c->lit_slab : G <= 64u ? G : G <= 128u ? 32u : 8u;
+    return depth < G ? depth : G;
+}
+
+// Ordered like the chunk updates of update_tables, which it follows on the frame's stream `st`: the pass is one launch per slab (ceil(G / depth): 1, 4 or 30 for the bench's worlds)
 // on `st`, behind the set's chunk update and before the frame; nothing waits for it on the host.  Whoever else reads the set:
 //   - frames of the set's own frame set run on `st` too: stream order;
 //   - a split set (edits arriving: every frame set its own tables) has no other readers;
@@ -632,7 +645,7 @@ int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const 
         }
         if (T.lit_pending && T.lit_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));   // (a pass behind a pass)
         T.lit_valid = false;
-        vrt::launch_accel_lit(T.d_grid, c->accel_S * 8u, lp.axis, lp.up, lp.min_lo, sun_local, st);
+        vrt::launch_accel_lit(T.d_grid, c->accel_S * 8u, lp.axis, lp.up, lp.min_lo, sun_local, lit_slab_depth(c, c->accel_S * 8u), st);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, T.ev_lit.ensure());
         HIP_TRY(c, hipEventRecord(T.ev_lit, st));
