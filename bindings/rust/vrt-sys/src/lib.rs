@@ -467,6 +467,7 @@ extern "C" {
     pub fn vrt_read_march_cells(ctx: *mut vrt_ctx, cells: *mut u32, direct: *mut u32) -> c_int;
     pub fn vrt_read_tile_cost(ctx: *mut vrt_ctx, cost: *mut u32) -> c_int;
     pub fn vrt_get_sun_marks(ctx: *mut vrt_ctx, passes: *mut u32, min_leaf: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
+    pub fn vrt_read_lit_voxels(ctx: *mut vrt_ctx, passes: *mut u32, layers: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
     pub fn vrt_read_steps(ctx: *mut vrt_ctx, steps: *mut u32) -> c_int;
     pub fn vrt_set_stream(ctx: *mut vrt_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn vrt_bind_output(ctx: *mut vrt_ctx, texels: *mut c_void) -> c_int;

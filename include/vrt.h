@@ -755,6 +755,18 @@ int vrt_read_march_cells(vrt_ctx *ctx, uint32_t *cells, uint32_t *direct);
  * table set the last frame used (synchronises).  Every pointer may be NULL. */
 int vrt_get_sun_marks(vrt_ctx *ctx, uint32_t *passes, uint32_t *min_leaf, uint32_t *lit_trips, uint8_t *lit);
 
+/* The voxel marks, for inspection (docs/NUMERICS.md "Lit stops", the voxels of split cells): with every lit pass a table set also
+ * gets a copy of its brick pool in which the air voxels of split cells that see lit cells through air carry a mark, and the shadow
+ * rays of such a frame read that copy (VRT_LIT_VOXELS=0: they never do; vrt_read_accel returns the bricks themselves as ever).
+ * *passes: such passes launched so far; *layers: the voxel layers a voxel's walk may take, of the last such frame, 0 when it read
+ * the plain bricks; *lit_trips: the wave trip count up to which a voxel's mark stopped a ray of that frame (vrt_get_sun_marks'
+ * less the voxel marks' step budget; a cell's mark goes on stopping it up to vrt_get_sun_marks' own); lit[(32S)^3], x-major over
+ * the whole world's voxels: 1 for a voxel that holds the mark in the copy the table set of the last frame was last given, read from
+ * the copy itself (synchronises).  A world that holds the mark's voxel id in a brick gets a copy without marks, and its frames go
+ * back to the plain bricks — from the first frame that finds that pass over, which differs from run to run: the frames are the same
+ * bytes either way, *layers of the frames in between is K or 0.  Every pointer may be NULL. */
+int vrt_read_lit_voxels(vrt_ctx *ctx, uint32_t *passes, uint32_t *layers, uint32_t *lit_trips, uint8_t *lit);
+
 /* The trips the last frame that noted them took per tile (longest tiles first, above: a context that renders one frame at a time
  * notes them on the second plain frame of a view at rest): cost[tiles], the wave's trips through its primary and its shadow march
  * loop; cost[t] is tile t of this context's tiles, counted row by row over the screen's 8 x 8 tiles (a sharded context: its own tiles in that

@@ -5,7 +5,10 @@
 Every kernel of OLD is looked up in NEW (after the --rename substitutions, applied to NEW's symbol names: a template argument
 that a later build added with its old value as the default; --rename-file: one REGEX=REPL per line, # comments) and their bodies are compared instruction for instruction, with
 what legitimately differs between two links left out: addresses, raw encodings, comments, symbolic branch labels.  Prints
-one line per kernel that differs or is missing and a summary; exit status 1 if any kernel of OLD differs or is missing."""
+one line per kernel that differs or is missing and a summary; exit status 1 if any kernel of OLD differs or is missing.
+Under a kernel that differs, its hand-written march loops (vrt_march.h VRT_MARCH_LOOP: from `s_setprio 1` to `s_setprio 0`) are
+compared on their own with the register numbers left out — the compiler allocates an asm statement's operands anew when the code
+around it changes.  The disassembler's "..." for zero padding behind a function is not an instruction."""
 import argparse
 import os
 import re
@@ -61,8 +64,22 @@ def kernels(path):
                 continue
             ins = re.sub(r"//.*$", "", line)
             ins = re.sub(r"<[^>]*>", "", ins).strip()
-            if ins:
+            if ins and ins != "...":   # ("...": the disassembler's word for zero padding behind a function, not an instruction)
                 cur.append(" ".join(ins.split()))
+    return out
+
+
+def asm_loops(body):
+    """The instruction sequences between `s_setprio 1` and `s_setprio 0`, register numbers left out."""
+    out, cur = [], None
+    for ins in body:
+        if ins.startswith("s_setprio 1"):
+            cur = []
+        if cur is not None:
+            cur.append(re.sub(r"\b[vs]\[?\d+(:\d+)?\]?", "R", ins))
+        if ins.startswith("s_setprio 0") and cur is not None:
+            out.append(cur)
+            cur = None
     return out
 
 
@@ -97,6 +114,10 @@ def main():
         differ += 1
         n = sum(1 for x, y in zip(body, nbody) if x != y) + abs(len(body) - len(nbody))
         print(f"DIFFERS  {sym} -> {nsym}: {len(body)} vs {len(nbody)} instructions, {n} lines differ")
+        lo, ln = asm_loops(body), asm_loops(nbody)
+        if lo or ln:
+            print(f"         march loops (s_setprio 1 .. s_setprio 0), instructions: {[len(x) for x in lo]} vs {[len(x) for x in ln]}; "
+                  f"{'the same sequences, register numbers left out' if lo == ln else 'THEY DIFFER'}")
     extra = sorted(s for s in new if s not in {renamed[k][0] for k in old if k in renamed})
     for s in extra:
         print(f"NEW      {s} ({len(new[s])} instructions)")

@@ -281,6 +281,7 @@ VRT_SYMBOLS = {
     "vrt_read_accel": (C.c_int, [_P, _P, _P]),
     "vrt_read_march_cells": (C.c_int, [_P, _P, _P]),
     "vrt_get_sun_marks": (C.c_int, [_P, _P, _P, _P, _P]),
+    "vrt_read_lit_voxels": (C.c_int, [_P, _P, _P, _P, _P]),
     "vrt_read_tile_cost": (C.c_int, [_P, _P]),
     "vrt_read_steps": (C.c_int, [_P, _P]),
     "vrt_set_stream": (C.c_int, [_P, _P]),

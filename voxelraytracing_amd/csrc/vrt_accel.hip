@@ -644,7 +644,143 @@ __global__ void __launch_bounds__(256) accel_lit_kernel(uint32_t *grid, LitPass 
     grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
 }
 
+// The voxel marks: the lit rule carried down to the air voxels of SPLIT cells (docs/NUMERICS.md "Lit stops", the voxels of split
+// cells; tests/lit_voxel_ref.py states it in numpy).  A shadow ray starts a hair above a surface voxel, so inside a split cell, where
+// the cell marks say nothing; it walks that cell's and its neighbours' bricks voxel by voxel until it reaches an air leaf.  This
+// pass writes the table set's SHADOW POOL: the brick pool entry for entry, except that an air voxel from which every shadow ray
+// reaches lit cells through air holds kLitVoxel (its lo kept) — which the march loop of a shadow ray takes for a solid voxel, at no
+// instruction of its own (vrt_march.h (u)).  The rule is the cell rule with a cell of one voxel: slopes over the voxel widened by a
+// voxel, a rise of max(0, k - 2) .. k + 2 voxels to voxel layer k, the cell rule's allowance, one-sided intervals; layer 0 is the
+// voxel's own.  Layer by layer towards the sun every voxel of the reach must be air (an air-leaf cell is air throughout); the walk
+// ends LIT at the first layer whose whole reach lies in cells with the cell mark — a ray with a point of its path in a lit cell is a
+// ray of that cell, and the cell's proof takes over — and UNLIT at a voxel that is not air, at the world's border, or after
+// `layers` layers.  Runs behind accel_lit_kernel on its stream: the cell marks it reads are final.
+// A wave takes 16 cells of the grid — cell w, w + waves, w + 2 waves ... of the G^3 numbered with y slowest: at 16 heights, because
+// the split cells of a terrain lie together in a few layers, and a wave that met a whole row of them walked them one after the
+// other while the others had left (64 cells in a row: 640 us more than the cell marks' pass for 64^3 cells; 16 cells a slab apart: 204;
+// this: profiles/lit_voxels_ab.txt) — finds the split ones among them
+// with one ballot, and gives each a trip with a lane per voxel.  Only bricks a cell of the grid points to are written; nothing else of the pool is ever read.
+// A brick entry that holds kLitVoxel as the world's own voxel sets *clash: accel_lit_voxels_undo_kernel then makes the pool a plain copy.
+constexpr uint32_t kLitVoxelCellsPerWave = 16u;
+struct LitVoxelPass {
+    uint32_t G;          // cells per axis
+    uint32_t axis, up;   // as LitPass
+    uint32_t layers;     // K: voxel layers beyond the voxel's own
+    uint32_t entries;    // 16-bit entries of either pool
+    float sun_a, sun_u, sun_v;   // the sun on the pass's axes: on `a` mirrored with the world when the sun is below
+};
+
+// The voxels of axis `b` a ray of voxel i can be in after a rise of r_lo .. r_hi voxels, as [lo, hi]; false: some lie beyond the world.
+__device__ inline bool lit_voxel_reach(float i, float s_min, float s_max, float r_lo, float r_hi, float allow, int W, int *lo, int *hi) {
+    const float b_lo = i + (s_min < 0.0f ? r_hi : r_lo) * s_min - allow;
+    const float b_hi = i + 1.0f + (s_max > 0.0f ? r_hi : r_lo) * s_max + allow;
+    int l = (int)floorf(b_lo), h = (int)floorf(b_hi);
+    const int own = (int)i;
+    if (!(s_min < 0.0f)) l = max(l, own);   // (monotone coordinates, as lit_reach)
+    if (!(s_max > 0.0f)) h = min(h, own);
+    *lo = l;
+    *hi = h;
+    return l >= 0 && h < W;
+}
+
+// The walk of one air voxel, in the pass's own frame: `a` the sun's axis (mirrored when the sun is below, so that it grows towards
+// the sun), u and v the two others; ca / cu / cv: the strides of a cell in the bordered grid, ha / hu / hv: the shifts of a voxel's
+// two low bits in a brick's index.  One exit: the loops carry flags, not returns.
+__device__ inline bool lit_voxel_walk(const uint32_t *grid, const uint16_t *bricks, const LitVoxelPass &lp, int ia, int iu, int iv, uint32_t ca,
+                                      uint32_t cu, uint32_t cv, uint32_t ha, uint32_t hu, uint32_t hv) {
+    const int W = (int)(lp.G * 4u);
+    const float fa = (float)ia, fu = (float)iu, fv = (float)iv;
+    const float d_lo = lp.sun_a - (fa + 2.0f), d_hi = lp.sun_a - (fa - 1.0f);
+    float us_min, us_max, vs_min, vs_max;
+    lit_slopes(lp.sun_u - (fu + 2.0f), lp.sun_u - (fu - 1.0f), d_lo, d_hi, &us_min, &us_max);
+    lit_slopes(lp.sun_v - (fv + 2.0f), lp.sun_v - (fv - 1.0f), d_lo, d_hi, &vs_min, &vs_max);
+    bool open = true, lit = false;
+    for (uint32_t k = 0; k <= lp.layers && open; k++) {
+        const int la = ia + (int)k;
+        const float r_lo = k >= 2u ? (float)(k - 2u) : 0.0f, r_hi = (float)(k + 2u);
+        const float allow = fminf(0.015f * (float)(k + 1u), 1.0f) + 0.01f;
+        int ul, uh, vl, vh;
+        const bool in_u = lit_voxel_reach(fu, us_min, us_max, r_lo, r_hi, allow, W, &ul, &uh);
+        const bool in_v = lit_voxel_reach(fv, vs_min, vs_max, r_lo, r_hi, allow, W, &vl, &vh);
+        if (!in_u || !in_v || la >= W) break;   // the world's border: unlit
+        const uint32_t qa = (uint32_t)(lp.up ? la : W - 1 - la);
+        const uint32_t cell_a = (qa >> 2) * ca, bit_a = (qa & 3u) << ha;
+        bool all_air = true, all_lit = true;
+        for (int nv = vl; nv <= vh; nv++)
+            for (int nu = ul; nu <= uh; nu++) {
+                // (every coordinate is inside the world here: the cell is one of the grid's G^3)
+                const uint32_t e = grid[cell_a + ((uint32_t)nu >> 2) * cu + ((uint32_t)nv >> 2) * cv];
+                const bool split = is_split_entry(e);
+                const uint32_t at = (e & 0x7FFFFFC0u) + (bit_a | (((uint32_t)nu & 3u) << hu) | (((uint32_t)nv & 3u) << hv));
+                uint32_t voxel = 1u;   // (a brick beyond the pool: not air)
+                if (split && at < lp.entries) voxel = (uint32_t)bricks[at] >> 1;
+                all_air = all_air && (e >= kAirLeaf || (split && voxel == 0u));   // (an air-leaf cell is air throughout)
+                all_lit = all_lit && e >= kAirLeaf && !(e & kAirUnlit);
+            }
+        open = all_air && !all_lit;
+        lit = all_air && all_lit;
+    }
+    return lit;
+}
+
+__global__ void __launch_bounds__(256) accel_lit_voxels_kernel(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, LitVoxelPass lp,
+                                                               uint32_t *clash) {
+    const uint32_t G = lp.G, G1 = G + 1u, lane = threadIdx.x & 63u;
+    const uint32_t cells = G * G * G, waves = (cells + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave >= waves) return;   // (wave-uniform)
+    const uint32_t mine = wave + lane * waves;   // (below 2^32: lane < kLitVoxelCellsPerWave where it is used)
+    uint32_t e_mine = 0u;
+    // (the cells are numbered with y slowest — x = n % G, z = n / G % G, y = n / G^2 — so that a wave's cells lie at 16 heights)
+    if (lane < kLitVoxelCellsPerWave && mine < cells) e_mine = grid[(((mine / G) % G) * G1 + mine / (G * G)) * G1 + mine % G];   // (below 2^32: grid_dim <= 800)
+    const uint32_t a = lp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // the two other axes, as accel_lit_kernel
+    const uint32_t cs[3] = {1u, G1, G1 * G1};
+    const uint32_t ca = cs[a], cu = cs[u], cv = cs[v], ha = 2u * a, hu = 2u * u, hv = 2u * v;
+    const int W = (int)(G * 4u);
+    unsigned long long todo = __ballot(is_split_entry(e_mine));
+    while (todo) {
+        const uint32_t i = (uint32_t)__ffsll((long long)todo) - 1u;
+        todo &= todo - 1ull;
+        const uint32_t e = (uint32_t)__shfl((int)e_mine, (int)i, 64), cell = wave + i * waves;
+        if ((e & 0x7FFFFFC0u) + 64u > lp.entries) continue;   // (wave-uniform: a brick beyond the pool is never read by the march either)
+        const uint32_t at = (e & 0x7FFFFFC0u) + lane;
+        const int px = (int)((cell % G) * 4u + (lane & 3u)), py = (int)((cell / (G * G)) * 4u + ((lane >> 2) & 3u)), pz = (int)(((cell / G) % G) * 4u + (lane >> 4));
+        const int pa = a == 0u ? px : a == 1u ? py : pz, pu = u == 0u ? px : py, pv = v == 1u ? py : pz;
+        uint32_t b = bricks[at];
+        if ((b >> 1) == kLitVoxel) atomicOr(clash, 1u);
+        if ((b >> 1) == 0u && lit_voxel_walk(grid, bricks, lp, lp.up ? pa : W - 1 - pa, pu, pv, ca, cu, cv, ha, hu, hv)) b |= kLitVoxel << 1;
+        lit_bricks[at] = (uint16_t)b;
+    }
+}
+
+// ... and where the world itself holds kLitVoxel in a brick: the shadow pool becomes the plain one without any mark — entry for
+// entry, but for the world's own voxels of that id, which are written as the id below it: as solid and as little a liquid to a
+// shadow ray, of which the frame reads `hit` alone (the host builds no marks where the liquid table could tell the two apart)
+__global__ void __launch_bounds__(256) accel_lit_voxels_undo_kernel(const uint32_t *clash, const uint32_t *bricks, uint32_t *lit_bricks, uint32_t words) {
+    if (*clash == 0u) return;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) {
+        uint32_t w = bricks[i];
+        if (((w >> 1) & 0x7FFFu) == kLitVoxel) w &= ~2u;          // (0x7FFF -> 0x7FFE: the voxel's lowest bit is the entry's bit 1)
+        if ((w >> 17) == kLitVoxel) w &= ~(2u << 16);
+        lit_bricks[i] = w;
+    }
+}
+
 }  // namespace
+
+// The voxel marks of a table set, on `st` behind launch_accel_lit: `lit_bricks` becomes the shadow pool of `bricks` (both of
+// `entries` 16-bit entries, a multiple of 64); *clash (device) is cleared, and set if the world holds kLitVoxel in a brick.
+void launch_accel_lit_voxels(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, uint32_t entries, uint32_t G, uint32_t axis, bool up,
+                             const float sun[3], uint32_t layers, uint32_t *clash, hipStream_t st) {
+    const uint32_t u = axis == 0u ? 1u : 0u, v = axis == 2u ? 1u : 2u;
+    const LitVoxelPass lp{G, axis, up ? 1u : 0u, layers, entries, up ? sun[axis] : (float)(G * 4u) - sun[axis], sun[u], sun[v]};
+    if (hipMemsetAsync(clash, 0, sizeof(uint32_t), st) != hipSuccess) return;   // (the caller asks hipGetLastError)
+    const uint32_t waves = (G * G * G + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
+    hipLaunchKernelGGL(accel_lit_voxels_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, st, grid, bricks, lit_bricks, lp, clash);
+    const uint32_t words = entries / 2u, blocks = (words + 255u) / 256u;
+    hipLaunchKernelGGL(accel_lit_voxels_undo_kernel, dim3(blocks < 1024u ? (blocks ? blocks : 1u) : 1024u), dim3(256), 0, st, clash,
+                       reinterpret_cast<const uint32_t *>(bricks), reinterpret_cast<uint32_t *>(lit_bricks), words);
+}
 
 // The lit pass over the whole grid, on `st`: a launch per slab of `depth` layers, from the sun's side (the last one may be short).
 void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st) {

@@ -122,6 +122,8 @@ void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t
                          uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail, uint32_t block_cap, const uint32_t liquid[8],
                          const uint32_t *chunks, const uint32_t *extents, const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done);
 void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st);
+void launch_accel_lit_voxels(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, uint32_t entries, uint32_t G, uint32_t axis, bool up,
+                             const float sun[3], uint32_t layers, uint32_t *clash, hipStream_t st);
 }  // namespace vrt
 
 // Host-time profile of the frame path (VRT_HOST_PROF=1: printed at process exit): where the calling thread's microseconds per
@@ -293,6 +295,19 @@ struct vrt_ctx {
         uint64_t lit_gen = 0;
         float lit_sun[3] = {0.f, 0.f, 0.f};
         uint32_t lit_min_lo = 0;
+        // the voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): the shadow pool — d_bricks entry for entry, a lit air voxel of a
+        // split cell holding vrt::kLitVoxel — made behind the lit pass that made the cell marks and held exactly as long as they
+        // are; a copy of the set does not take it along.  Allocated by the set's first pass that builds voxel marks
+        Buf<uint16_t> d_lit_bricks;
+        Buf<uint32_t> d_lit_clash;              // one word: the world holds kLitVoxel in a brick (the pool is then a plain copy)
+        bool lit_voxels_valid = false;
+        uint64_t lit_pool_gen = ~0ull;          // the tables the pool was last written from (vrt_read_lit_voxels reads it back, marks or none)
+        // the flag comes back to the host behind the pass, without a wait: a frame that finds the pass over reads it, and where it is set
+        // goes back to the plain bricks; the tables it was set for get no voxel pass again (a moved sun: the world still holds the id)
+        Pinned h_lit_clash;
+        bool lit_clash_pending = false;
+        uint64_t lit_clash_gen = ~0ull;
+        uint32_t lit_voxel_layers = 0;          // K the pool was made with
         // ... and what the frames ask for: the pass runs once kLitSettleFrames frames in a row have asked for the same marks
         uint64_t want_gen = 0;
         float want_sun[3] = {0.f, 0.f, 0.f};
@@ -334,6 +349,10 @@ struct vrt_ctx {
     bool sun_marks = true;         // VRT_SUN_MARKS=0: shadow rays never stop at lit cells (the A/B of profiles/DECISIONS.md)
     uint32_t lit_slab = 0;         // VRT_LIT_SLAB: layers a launch of the lit pass tests a cell's corridor over (1: layer by layer; 0: by grid size, vrt_uploads.hip)
     uint32_t lit_passes = 0;       // lit passes launched (vrt_get_sun_marks)
+    bool lit_voxels = true;        // VRT_LIT_VOXELS=0: the cell marks alone (the A/B of profiles/lit_voxels_ab.txt); VRT_SUN_MARKS=0 switches both off
+    int lit_voxel_layers = -1;     // VRT_LIT_VOXEL_LAYERS: voxel layers a voxel's walk may take (0: no voxel marks; -1: by grid size, vrt_uploads.hip)
+    uint32_t lit_voxel_passes = 0; // voxel-mark passes launched (vrt_read_lit_voxels)
+    uint32_t lit_last_voxel_layers = 0, lit_last_voxel_trips = 0;   // of the last one-launch shadow frame: 0 = it read the plain bricks
     uint32_t lit_last_min_leaf = 0, lit_last_trips = 0;   // of the last one-launch shadow frame: 0 = its marks were off
     // longest tiles first (vrt_kernels.hip: tile_order_*), for a context that renders one frame at a time
     // (vrt_set_frames_in_flight(1)) and whose view is at rest: the second plain frame of an unchanged view (camera, settings,
@@ -612,7 +631,8 @@ VRT_HIDDEN int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st);
 // The sun marks of table set k for the sun at `sun_local`, made on `st` if the set does not hold them; *below / *trips: what the
 // frame's shadow rays are given (FrameParams.shadow_below / lit_trips) — vrt::kAirLeaf / 0 when this world and sun get no marks
 // `shares`: the frame is of another frame set than the table set's own (tabs[0] read from a second stream)
-VRT_HIDDEN int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips);
+VRT_HIDDEN int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips,
+                                const uint16_t **shadow_bricks, uint32_t *voxel_trips);
 VRT_HIDDEN size_t chunk_dir_entries(uint32_t S);
 VRT_HIDDEN size_t direct_cell_entries(uint32_t S);
 // vrt_lamp.hip: the frame set's lamp list, rebuilt on `st` if what it was built from has changed (the frame's tables are up to date

@@ -36,6 +36,11 @@ __host__ __device__ inline bool is_split_entry(uint32_t e) { return (int32_t)e <
 // `e < kAirLeaf` (FrameParams.shadow_below), which a lit air leaf answers like a split cell: the lane leaves the fast path, and stops.
 constexpr uint32_t kAirUnlit = 1u << 22;
 constexpr uint32_t kLitBelow = kAirLeaf | kAirUnlit;
+// The voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): a table set's SHADOW POOL is a copy of its brick pool in which a lit air
+// voxel of a split cell holds this voxel id — the highest a brick's 16-bit entry (voxel << 1 | lo) can carry.  Not air and, by the
+// host's check of the liquid table, not a liquid: the march loop's "solid: stop" parks a shadow lane on it as on any solid voxel, and
+// the code behind the loop tells it by the id (vrt_march.h (u)).  A world one of whose bricks holds the id gets a shadow pool without marks.
+constexpr uint32_t kLitVoxel = 0x7FFFu;
 // a march cell's first word (lo of an air leaf, voxel << 16 | lo, 0x80000000 | brick * 64) as the cell grid holds it
 __host__ __device__ inline uint32_t grid_entry(uint32_t x) { return x - 1u < 31u ? (kAirLeaf | kAirUnlit | x) : x; }
 
@@ -111,7 +116,11 @@ struct FrameParams {
     // (two of its words are taken: what a shadow ray of the one-launch frame compares an entry against — kLitBelow while this table
     // set's sun marks hold for this sun, else kAirLeaf — and the wave trip count up to which a lit entry may stop it, vrt_march.h (t))
     uint32_t shadow_below, lit_trips;
-    uint32_t layout_hole[3];
+    // (the rest: the bricks a shadow ray of the one-launch frame reads — the table set's shadow pool while its voxel marks hold, null:
+    // `bricks`; same size and indexing as `bricks` — and the wave trip count up to which it reads them: lit_trips less the voxel
+    // marks' step budget, vrt_march.h (u))
+    const uint16_t *shadow_bricks;
+    uint32_t lit_voxel_trips;
     uint32_t n_nodes, n_roots;
     uint32_t width, height;
     uint32_t tiles_x, tiles_total;
@@ -151,7 +160,8 @@ struct FrameParams {
     float world_max;         // 0.0 + f32(world.size) (:285)
     uint32_t cam_origin_facts;   // kCamNotFinite | kCamOnPlane (the start nudge :188-190 applies) | kCamOutside (:285, asked of the origin as it is)
 };
-static_assert(offsetof(FrameParams, n_nodes) == 244, "layout_hole keeps the fields behind it where the kernels' code expects them");
+static_assert(offsetof(FrameParams, n_nodes) == 244, "what fills the hole keeps the fields behind it where the kernels' code expects them");
+static_assert(offsetof(FrameParams, shadow_bricks) == 232, "the shadow pool's pointer lies in the hole, aligned as it is");
 
 // vrt_set_sun_light (vrt_path_sun.h): what the kernels of a sun-lit path frame are given besides FrameParams — a second kernel
 // argument, so that FrameParams keeps its layout and the kernels that take it alone their code

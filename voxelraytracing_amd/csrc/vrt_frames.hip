@@ -523,6 +523,8 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     }
     if (const char *e = getenv("VRT_TILE_ORDER")) c->tile_lpt = e[0] != '0';
     if (const char *e = getenv("VRT_SUN_MARKS")) c->sun_marks = e[0] != '0';
+    if (const char *e = getenv("VRT_LIT_VOXELS")) c->lit_voxels = e[0] != '0';
+    if (const char *e = getenv("VRT_LIT_VOXEL_LAYERS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c->lit_voxel_layers = (int)v; }
     if (const char *e = getenv("VRT_LIT_SLAB")) { const long v = atol(e); if (v >= 1 && v <= 4096) c->lit_slab = (uint32_t)v; }
     // (0: screen order while the view moves — profiles/r05_tile_order_moving.txt)
     if (const char *e = getenv("VRT_TILE_ORDER_MOVING")) c->tile_lpt_moving = e[0] != '0' ? 1u : 0u;
@@ -761,9 +763,10 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     fill_uniforms(c, P);
     // the shadow rays of the one-launch frame stop at lit cells: this set's sun marks, made now if the tables or the sun changed
     if (P.grid && plan.shadow && plan.variant == 0u && !plan.kstats) {
-        c->lit_last_min_leaf = 0u;
-        if (c->sun_marks) VRT_TRY(ensure_sun_marks(c, tab, f.st, shares, P.sun_local, &P.shadow_below, &P.lit_trips));
-        c->lit_last_trips = P.lit_trips;
+        c->lit_last_min_leaf = c->lit_last_trips = 0u;
+        if (c->sun_marks) VRT_TRY(ensure_sun_marks(c, tab, f.st, shares, P.sun_local, &P.shadow_below, &P.lit_trips, &P.shadow_bricks, &P.lit_voxel_trips));
+        c->lit_last_voxel_layers = P.shadow_bricks ? c->tabs[tab].lit_voxel_layers : 0u;   // (vrt_read_lit_voxels)
+        c->lit_last_voxel_trips = P.lit_voxel_trips;
     }
     if (plan.fuse_present) {
         VRT_TRY(screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height));

@@ -743,6 +743,11 @@ void launch_primary_shadow_fused(const FrameParams &P, uint32_t march, bool stat
     if (march == 2u) {
         if (P.n_roots <= kLdsRootsMax) launch_fused_t<2, true>(P, stats, st, e0, e1);
         else launch_fused_t<2, false>(P, stats, st, e0, e1);
+    } else if (P.shadow_bricks && !stats && !P.clock) {
+        // the frame was given a shadow pool (the voxel marks, vrt_march.h (u)): the grid march's kernel whose shadow rays read it — an
+        // instantiation of its own, so that every other frame runs the one it always ran.  (The counting and the probe kernels read the plain bricks.)
+        const dim3 grid(P.tiles_local), block(64);
+        hipExtLaunchKernelGGL((primary_shadow_wave_kernel<kMarchLitVoxels, false, false, 1>), grid, block, (uint32_t)lds_bytes(P, false), st, e0, e1, 0, P);
     } else {
         launch_fused_t<0, false>(P, stats, st, e0, e1);
     }

@@ -655,7 +655,9 @@ __device__ __forceinline__ bool finite3(V3 v) {
 // ray may stop at a lit air leaf (t): every ray from that cell towards the sun leaves the world through air (vrt_accel.hip: the lit
 // pass), so the reference's ray misses — provided it does not run out of its kMaxSteps lookups on the way, which P.lit_trips sees
 // to (docs/NUMERICS.md, "Lit stops").  The counting kernels (STATS) never stop early: their counts are the reference's.
-template <bool STATS, bool CAMERA = false, bool SHADOW = false>
+// LITVOX: ... and reads its bricks from the frame's shadow pool, where a lit air voxel of a split cell stops it (u): the kernel of the
+// frames that were given one (MARCH = kMarchLitVoxels).  Every other frame runs the code it ran before there were voxel marks.
+template <bool STATS, bool CAMERA = false, bool SHADOW = false, bool LITVOX = false>
 __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const uint32_t *s_liquid, V3 origin, V3 dir) {
     MarchResult R;
     R.hit = false;
@@ -703,9 +705,14 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     asm("" : "+v"(mxm), "+v"(mym), "+v"(mzm));   // (held in registers)
 
     const uint32_t wsize = P.world.size;
-    const TableBuf gb = table_buffer(P.grid, P.grid_bytes), bb = table_buffer(P.bricks, P.brick_bytes);
+    // (u) a shadow ray reads its bricks from the table set's shadow pool while the frame was given one (wave-uniform): a lit air voxel
+    // of a split cell holds kLitVoxel there, which the loop takes for a solid voxel — the lane parks, and the id says why
+    constexpr bool kLitStops = SHADOW && !STATS;
+    const TableBuf gb = table_buffer(P.grid, P.grid_bytes), bb_plain = table_buffer(P.bricks, P.brick_bytes);
     // (the bricks as an array of 16-bit entries — stride 2, indexed — for (s): the index is a merge, not an addition and a shift)
-    const TableBuf bb16 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(P.bricks), 2, P.brick_bytes / 2u, 0x00020000);
+    const TableBuf bb16_plain = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(P.bricks), 2, P.brick_bytes / 2u, 0x00020000);
+    const TableBuf bb_lit = table_buffer(P.shadow_bricks, P.brick_bytes);
+    const TableBuf bb16_lit = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(P.shadow_bricks), 2, P.brick_bytes / 2u, 0x00020000);
     // (s): the liquids as the loop asks for them — voxel - liq_lo <= liq_span, never true of air (id 0).  A material table whose liquids
     // are not one range makes every voxel a candidate: the general step asks the table
     uint32_t liq_lo = P.liquid_lo, liq_span = P.liquid_span;
@@ -732,9 +739,12 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // stops the lane — else kAirLeaf, as for every other ray.  Wave-uniform.  The marks stop a lane only while the wave has made
     // fewer than `limit` trips (P.lit_trips: what is left of kMaxSteps then covers the way out of the world); past that a lit
     // leaf is air like any other
-    constexpr bool kLitStops = SHADOW && !STATS;
     uint32_t plain_below = kLitStops ? P.shadow_below : kAirLeaf;
-    uint32_t limit = (kLitStops && plain_below != kAirLeaf) ? P.lit_trips : kMaxSteps;
+    const uint32_t cells_limit = (kLitStops && plain_below != kAirLeaf) ? P.lit_trips : kMaxSteps;
+    // (u) ... and the voxel marks only while it has made fewer than P.lit_voxel_trips, below the cell marks' count by their own step
+    // budget: `limit` is the trip count at which the next of the two ends
+    bool lit_voxels = kLitStops && LITVOX && P.shadow_bricks != nullptr && P.lit_voxel_trips < cells_limit;
+    uint32_t limit = lit_voxels ? P.lit_voxel_trips : cells_limit;
     bool lit_stop = false;
     uint32_t slow_below = careful ? kSlow : plain_below;
     float total_len = 0.0f;
@@ -783,11 +793,20 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // returns.  Same steps in the same order for every lane; `iter` counts them for the whole wave.
     for (;;) {
         uint32_t e;
-        if (kLitStops && iter >= limit && limit != kMaxSteps) {   // (wave-uniform) the lit stops' budget is spent: (t)
-            limit = kMaxSteps;
-            plain_below = kAirLeaf;
-            if (slow_below != kSlow) slow_below = kAirLeaf;
+        if (kLitStops && iter >= limit && limit != kMaxSteps) {   // (wave-uniform) a budget of the lit stops is spent
+            if (lit_voxels && iter < cells_limit) {   // (u) the voxel marks': a lit voxel is air like any other, the plain bricks from here on
+                limit = cells_limit;
+            } else {                                  // (t) the cell marks'
+                limit = kMaxSteps;
+                plain_below = kAirLeaf;
+                if (slow_below != kSlow) slow_below = kAirLeaf;
+            }
+            lit_voxels = false;
         }
+        // (u) the bricks of this trip through the loop and the general step behind it (wave-uniform already: tells the compiler, which
+        // then selects between the two descriptors on the scalar unit)
+        const bool lit_pool = kLitStops && LITVOX && __builtin_amdgcn_readfirstlane((uint32_t)lit_voxels) != 0u;
+        const TableBuf bb = lit_pool ? bb_lit : bb_plain, bb16 = lit_pool ? bb16_lit : bb16_plain;
         if constexpr (!STATS) {
             // (r) The inner loop as the instructions themselves.  What the compiler makes of the C++ below is the same vector
             // instructions, but it wraps every step in seven scalar instructions, four branches (three taken) and six s_nop /
@@ -812,7 +831,8 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             else asm volatile(VRT_MARCH_LOOP("", "") VRT_MARCH_LOOP_OPERANDS);
             iter = trips + limit_s;
             if (parked) {                   // stopped in the loop: border, the solid voxel now in `voxel`, or (t) a lit air leaf, still in `e`
-                if (kLitStops) lit_stop = e >= kAirLeaf;
+                // (u) ... or a lit voxel of a split cell's brick (a leaf of that id in the cell grid is a solid leaf: the pass does not see those)
+                if (kLitStops) lit_stop = e >= kAirLeaf || (lit_pool && voxel == kLitVoxel && is_split_entry(e));
                 break;
             }
             if (iter >= kMaxSteps) break;   // (wave-uniform) at most kMaxSteps lookups (:220)
@@ -853,6 +873,10 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
                     const uint32_t b = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(bb, (e + u) << 1, 0, 0);  // the shift drops bit 31
                     lo = kAirLeaf | (b & 1u);
                     voxel = b >> 1;
+                    if (kLitStops && lit_pool && voxel == kLitVoxel) {   // (u) a lit air voxel: stops a plain lane; air to a lane in water, a careful wave
+                        voxel = 0u;
+                        if (slow_below != kSlow) { lit_stop = true; stop = true; }
+                    }
                 } else if (e < kAirLeaf) {   // a leaf that is not air (an air leaf is its own selector)
                     lo = kAirLeaf | (e & 31u);
                     voxel = e >> 16;
@@ -901,12 +925,14 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
 #undef VRT_LIT_TEST
 #undef VRT_LIT_PARK
 
+// MARCH = kMarchLitVoxels: the grid march (as 0) of a frame whose shadow rays read the table set's shadow pool
+constexpr int kMarchLitVoxels = 4;
 template <int MARCH, bool LDS_ROOTS, bool STATS = false, bool CAMERA = false, bool SHADOW = false>
 __device__ __forceinline__ MarchResult march(const FrameParams &P, const uint32_t *s_roots, const uint32_t *s_liquid,
                                              V3 origin, V3 dir) {
     if (MARCH == 1) return march_literal<LDS_ROOTS>(P, s_roots, s_liquid, origin, dir);
     if (MARCH == 2) return march_fast<LDS_ROOTS>(P, s_roots, s_liquid, origin, dir);
-    return march_grid<STATS, CAMERA, SHADOW>(P, s_liquid, origin, dir);
+    return march_grid<STATS, CAMERA, SHADOW, MARCH == kMarchLitVoxels>(P, s_liquid, origin, dir);
 }
 
 // ray_sky, ray_tracer.wgsl:144-157

@@ -383,6 +383,7 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     memcpy(T.lit_sun, A.lit_sun, sizeof T.lit_sun);
     T.lit_min_lo = A.lit_min_lo;
     T.lit_pending = false;   // (whoever reads the copy is ordered behind the copy)
+    T.lit_voxels_valid = false;   // (the shadow pool stays behind: a copy is made for edits, whose chunk updates drop every mark)
     return VRT_OK;
 }
 
@@ -602,6 +603,21 @@ static uint32_t lit_slab_depth(const vrt_ctx *c, uint32_t G) {
     return depth < G ? depth : G;
 }
 
+// The voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): how many voxel layers K a voxel's walk may take before it gives up, per
+// grid size, by the slab depth's rule — the largest K whose pass pays for itself within 100 frames (profiles/lit_voxels_ab.txt);
+// 0: no voxel marks at that size.  Up to 64 cells a side 8 layers: 99 us on the pass for 2.1 us off every frame (4: 59 us for 1.2; 12: 134
+// us for the same 2.1).  128 cells a side: the frames gain 2.0 us at 8 layers, but the pass costs 376 us more: 185 frames, so none; 240: the
+// frames get slower with the second pool, none.  VRT_LIT_VOXEL_LAYERS overrides.  And what K costs the step budget (docs/NUMERICS.md "Lit
+// stops"): from a lit voxel to the first lit cell a ray crosses at most K + 1 voxel planes of the sun's axis and, its slopes below
+// one over a rise of at most K + 2, K + 3 of each other axis with the widened voxel's — 3 K + 6 in all, allowed for in full —
+// and one re-step per plane.
+static uint32_t lit_voxel_layers(const vrt_ctx *c, uint32_t G) {
+    if (!c->lit_voxels) return 0u;
+    if (c->lit_voxel_layers >= 0) return (uint32_t)c->lit_voxel_layers;
+    return G <= 64u ? 8u : 0u;
+}
+static uint32_t lit_voxel_budget(uint32_t layers) { return 2u * (3u * layers + 6u); }
+
 // Ordered like the chunk updates of update_tables, which it follows on the frame's stream `st`: the pass is one launch per slab (ceil(G / depth): 1, 4 or 30 for the bench's worlds)
 // on `st`, behind the set's chunk update and before the frame; nothing waits for it on the host.  Whoever else reads the set:
 //   - frames of the set's own frame set run on `st` too: stream order;
@@ -610,9 +626,12 @@ static uint32_t lit_slab_depth(const vrt_ctx *c, uint32_t G) {
 //     waits for them before it rewrites a shared set (quiesce: the one host wait, of at most the frames in flight, and only when the
 //     sun moved or the world was built — an edit splits the sets first); what the context's own stream holds is waited for by an event;
 //     and every later frame on another stream waits for the pass by the event behind it (ev_lit), as it waits for ev_updated.
-int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips) {
+int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips,
+                     const uint16_t **shadow_bricks, uint32_t *voxel_trips) {
     *below = vrt::kAirLeaf;
     *trips = 0u;
+    *shadow_bricks = nullptr;
+    *voxel_trips = 0u;
     auto &T = c->tabs[k];
     LitPlan lp{};
     if (!c->accel_ok || !T.live || !T.d_grid || !lit_plan(c->world.size, sun_local, &lp)) return VRT_OK;
@@ -645,8 +664,27 @@ int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const 
         }
         if (T.lit_pending && T.lit_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));   // (a pass behind a pass)
         T.lit_valid = false;
+        T.lit_voxels_valid = false;
         vrt::launch_accel_lit(T.d_grid, c->accel_S * 8u, lp.axis, lp.up, lp.min_lo, sun_local, lit_slab_depth(c, c->accel_S * 8u), st);
         HIP_TRY(c, hipGetLastError());
+        // the voxel marks, behind the cell marks they hand over to: not where the reserved id could be a liquid (a liquid table that is
+        // not a range below 255 covers it: ids above 255 are material 255), and not where their step budget leaves the marks no trips
+        const uint32_t layers = lit_voxel_layers(c, c->accel_S * 8u);
+        T.lit_clash_pending = false;
+        if (layers && c->liquid_is_range && lit_voxel_budget(layers) < lp.trips && T.d_bricks.cap() >= 64u && T.lit_clash_gen != T.gen) {
+            HIP_TRY(c, T.d_lit_bricks.exactly(T.d_bricks.cap()));
+            HIP_TRY(c, T.d_lit_clash.once(1));
+            HIP_TRY(c, T.h_lit_clash.ensure((size_t)64));
+            vrt::launch_accel_lit_voxels(T.d_grid, T.d_bricks, T.d_lit_bricks, (uint32_t)T.d_bricks.cap(), c->accel_S * 8u, lp.axis, lp.up, sun_local, layers,
+                                         T.d_lit_clash, st);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(T.h_lit_clash, T.d_lit_clash, sizeof(uint32_t), hipMemcpyDeviceToHost, st));   // (pinned: nothing waits; ev_lit is behind it)
+            T.lit_clash_pending = true;
+            T.lit_pool_gen = T.gen;
+            T.lit_voxels_valid = true;
+            T.lit_voxel_layers = layers;
+            c->lit_voxel_passes += 1u;
+        }
         HIP_TRY(c, T.ev_lit.ensure());
         HIP_TRY(c, hipEventRecord(T.ev_lit, st));
         T.lit_pending = true;
@@ -664,6 +702,15 @@ int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const 
     *below = vrt::kLitBelow;
     *trips = lp.trips;
     c->lit_last_min_leaf = lp.min_lo + 1u;
+    c->lit_last_trips = lp.trips;
+    if (T.lit_clash_pending && hipEventQuery(T.ev_lit) == hipSuccess) {   // the pass is over: did it meet the reserved id in a brick of the world?
+        T.lit_clash_pending = false;
+        if (*reinterpret_cast<volatile uint32_t *>(T.h_lit_clash.get())) { T.lit_voxels_valid = false; T.lit_clash_gen = T.gen; }   // the plain bricks from here on
+    }
+    if (T.lit_voxels_valid && T.d_lit_bricks && T.d_lit_bricks.cap() == T.d_bricks.cap() && lit_voxel_budget(T.lit_voxel_layers) < lp.trips) {
+        *shadow_bricks = T.d_lit_bricks;
+        *voxel_trips = lp.trips - lit_voxel_budget(T.lit_voxel_layers);
+    }
     return VRT_OK;
 }
 
@@ -930,6 +977,41 @@ int vrt_get_sun_marks(vrt_ctx *c, uint32_t *passes, uint32_t *min_leaf, uint32_t
             for (size_t x = 0; x < G; x++) {
                 const uint32_t e = t[(z * G1 + y) * G1 + x];
                 lit[(z * G + y) * G + x] = (held && e >= vrt::kAirLeaf && !(e & vrt::kAirUnlit)) ? 1u : 0u;
+            }
+    return VRT_OK;
+}
+
+int vrt_read_lit_voxels(vrt_ctx *c, uint32_t *passes, uint32_t *layers, uint32_t *lit_trips, uint8_t *lit) {
+    GRP_ROOT(c, vrt_read_lit_voxels(d, passes, layers, lit_trips, lit));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    if (passes) *passes = c->lit_voxel_passes;
+    if (layers) *layers = c->lit_last_voxel_layers;
+    if (lit_trips) *lit_trips = c->lit_last_voxel_trips;
+    if (!lit) return VRT_OK;
+    if (!c->accel_ok || c->accel_dirty || !c->tabs[c->last.tab].live)
+        return fail(c, VRT_ERR_STATE, "vrt_read_lit_voxels: the tables are not up to date (render a frame first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    QUIESCE(c);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    vrt_ctx::Tables &T = c->tabs[c->last.tab];   // the table set the last frame used
+    if (T.lit_pending) { HIP_TRY(c, hipEventSynchronize(T.ev_lit)); T.lit_pending = false; }
+    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u, W = G * 4u;
+    memset(lit, 0, W * W * W);
+    // (the pool as the last pass left it, in use or not: where the world holds the reserved id in a brick it is a copy without a mark)
+    if (!(T.lit_pool_gen == T.gen && T.lit_valid && T.lit_gen == T.gen && T.d_lit_bricks && T.d_lit_bricks.cap() == T.d_bricks.cap())) return VRT_OK;
+    std::vector<uint32_t> t(G * G1 * G1);
+    std::vector<uint16_t> pool(T.d_lit_bricks.cap());
+    HIP_TRY(c, hipMemcpy(t.data(), T.d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(pool.data(), T.d_lit_bricks, pool.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (size_t z = 0; z < G; z++)
+        for (size_t y = 0; y < G; y++)
+            for (size_t x = 0; x < G; x++) {
+                const uint32_t e = t[(z * G1 + y) * G1 + x];
+                const size_t at = e & 0x7FFFFFC0u;
+                if (!vrt::is_split_entry(e) || at + 64u > pool.size()) continue;
+                for (size_t u = 0; u < 64u; u++)
+                    if ((uint32_t)(pool[at + u] >> 1) == vrt::kLitVoxel)
+                        lit[((z * 4u + (u >> 4)) * W + (y * 4u + ((u >> 2) & 3u))) * W + (x * 4u + (u & 3u))] = 1u;
             }
     return VRT_OK;
 }

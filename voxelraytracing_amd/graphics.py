@@ -345,6 +345,19 @@ class Gpu:
         self._ck(self._lib.vrt_read_tile_cost(self._h, cost.ctypes.data_as(C.c_void_p)))
         return cost
 
+    def lit_voxels(self, voxels: bool = False):
+        """{passes, layers, lit_trips[, lit[n,n,n] indexed [z,y,x], n = 32 S]} — see vrt_read_lit_voxels in include/vrt.h."""
+        p, k, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        lit = None
+        if voxels:
+            n = self.accel_info().world_size_chunks * 32
+            lit = np.empty((n, n, n), dtype=np.uint8)
+        self._ck(self._lib.vrt_read_lit_voxels(self._h, C.byref(p), C.byref(k), C.byref(t), lit.ctypes.data_as(C.c_void_p) if voxels else None))
+        out = dict(passes=p.value, layers=k.value, lit_trips=t.value)
+        if voxels:
+            out["lit"] = lit
+        return out
+
     def sun_marks(self, cells: bool = False):
         """{passes, min_leaf, lit_trips[, lit[G,G,G] indexed [z,y,x]]} — see vrt_get_sun_marks in include/vrt.h."""
         p, m, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
