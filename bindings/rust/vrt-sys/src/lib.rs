@@ -466,6 +466,8 @@ extern "C" {
     pub fn vrt_read_accel(ctx: *mut vrt_ctx, grid: *mut u32, bricks: *mut u16) -> c_int;
     pub fn vrt_read_march_cells(ctx: *mut vrt_ctx, cells: *mut u32, direct: *mut u32) -> c_int;
     pub fn vrt_read_tile_cost(ctx: *mut vrt_ctx, cost: *mut u32) -> c_int;
+    pub fn vrt_read_tile_order(ctx: *mut vrt_ctx, order: *mut u32, dilated: *mut u32) -> c_int;
+    pub fn vrt_selftest_tile_order(device: i32, cost: *const u32, tiles_x: u32, tiles_y: u32, radius: i32, order: *mut u32) -> c_int;
     pub fn vrt_get_sun_marks(ctx: *mut vrt_ctx, passes: *mut u32, min_leaf: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
     pub fn vrt_read_lit_voxels(ctx: *mut vrt_ctx, passes: *mut u32, layers: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
     pub fn vrt_read_steps(ctx: *mut vrt_ctx, steps: *mut u32) -> c_int;

@@ -773,6 +773,21 @@ int vrt_read_lit_voxels(vrt_ctx *ctx, uint32_t *passes, uint32_t *layers, uint32
  * order), whatever order the frame launched them in (synchronises).  VRT_ERR_STATE when no frame has noted any. */
 int vrt_read_tile_cost(vrt_ctx *ctx, uint32_t *cost);
 
+/* The order the next frame of this view launches its tiles in: order[tiles], the t-th wave of the launch takes tile order[t] (numbered
+ * as vrt_read_tile_cost numbers them).  *dilated = 0 for the exact order of a view at rest — tiles by descending class
+ * min(cost >> 1, 63), screen order within a class —, 1 for a moving view's order of 4 x 4-tile blocks by the largest cost within
+ * VRT_TILE_ORDER_RADIUS blocks (may be NULL).  Synchronises.  VRT_ERR_STATE while the context holds no order: before a frame has made
+ * one, with more than one frame in flight, after a resize, under VRT_TILE_ORDER=0.  Diagnostic only. */
+int vrt_read_tile_order(vrt_ctx *ctx, uint32_t *order, uint32_t *dilated);
+
+/* Self-test of the kernels that make those orders, on costs of the caller's choosing: cost[tiles_x * tiles_y] goes to `device`,
+ * order[tiles_x * tiles_y] comes back (0xFFFFFFFF where the kernels wrote nothing).  radius < 0: the exact order, as a view at rest
+ * gets it (tiles_x * tiles_y tiles in a row); radius 1..6: the block order dilated over that many blocks.  The launchers, class
+ * width and thread count are the ones a frame uses.  VRT_ERR_OUT_OF_RANGE, nothing written, for a frame the block order refuses (more
+ * than 8 192 blocks, more than 255 blocks a side, radius above 6) and for more than 2^28 tiles; a null pointer, a zero size or radius 0: VRT_ERR_INVALID_ARG.
+ * Diagnostic only; no context needed. */
+int vrt_selftest_tile_order(int32_t device, const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, int32_t radius, uint32_t *order);
+
 /* Per-pixel march-loop iteration counts of the last frame (primary | shadow << 16); the frame must
  * have been rendered with opts.stats = 1.  Numeric twin of the reference's F2 step-count heat-map
  * (main.rs:368-370, ray_tracer.wgsl:311-314). */

@@ -106,6 +106,47 @@ extern "C" int vrt_read_tile_cost(vrt_ctx *c, uint32_t *cost) {
     return VRT_OK;
 }
 
+extern "C" int vrt_read_tile_order(vrt_ctx *c, uint32_t *order, uint32_t *dilated) {
+    GRP_ROOT(c, vrt_read_tile_order(d, order, dilated));
+    if (!c || !order) return fail(c, VRT_ERR_INVALID_ARG, "vrt_read_tile_order: null argument");
+    if (!c->sz.d_tile_order || !c->sz.tile_order_valid) return fail(c, VRT_ERR_STATE, "vrt_read_tile_order: the context holds no order");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(order, c->sz.d_tile_order, (size_t)c->tiles_local * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (dilated) *dilated = c->order_dilated ? 1u : 0u;
+    return VRT_OK;
+}
+
+// The two launchers above on costs of the caller's choosing, with the constants tile_order_after_frame gives them (classes of two
+// trips, 1024 threads) and the scratch tile_order_before_frame sizes: buffers and a stream of its own, no context.
+extern "C" int vrt_selftest_tile_order(int32_t device, const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, int32_t radius, uint32_t *order) {
+    if (!cost || !order || !tiles_x || !tiles_y || radius == 0) return VRT_ERR_INVALID_ARG;
+    const uint64_t n64 = (uint64_t)tiles_x * tiles_y;
+    if (n64 > 0x10000000ull) return VRT_ERR_OUT_OF_RANGE;
+    const uint32_t n = (uint32_t)n64, chunks = (n + 63u) / 64u;
+    if (hipSetDevice(device) != hipSuccess) return VRT_ERR_DEVICE;
+    uint32_t *d_cost = nullptr, *d_order = nullptr, *d_scratch = nullptr;
+    hipStream_t st = nullptr;
+    int rc = VRT_OK;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { st = nullptr; rc = VRT_ERR_DEVICE; }
+    if (rc == VRT_OK && (hipMalloc(&d_cost, (size_t)n * sizeof(uint32_t)) != hipSuccess || hipMalloc(&d_order, (size_t)n * sizeof(uint32_t)) != hipSuccess ||
+                         (radius < 0 && hipMalloc(&d_scratch, (size_t)64u * (chunks + 1u) * sizeof(uint32_t)) != hipSuccess))) rc = VRT_ERR_OOM;
+    if (rc == VRT_OK && (hipMemcpyAsync(d_cost, cost, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+                         hipMemsetAsync(d_order, 0xFF, (size_t)n * sizeof(uint32_t), st) != hipSuccess)) rc = VRT_ERR_DEVICE;
+    if (rc == VRT_OK) {
+        if (radius < 0) vrt::launch_tile_order(d_cost, n, 1u, d_scratch, d_order, st);
+        else if (!vrt::launch_tile_order_blocks(d_cost, tiles_x, tiles_y, 1u, (uint32_t)radius, d_order, st, 1024u)) rc = VRT_ERR_OUT_OF_RANGE;
+        if (hipGetLastError() != hipSuccess && rc == VRT_OK) rc = VRT_ERR_DEVICE;
+    }
+    if (rc == VRT_OK && hipMemcpyAsync(order, d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ERR_DEVICE;
+    if (st && hipStreamSynchronize(st) != hipSuccess && rc == VRT_OK) rc = VRT_ERR_DEVICE;
+    (void)hipFree(d_scratch);
+    (void)hipFree(d_order);
+    (void)hipFree(d_cost);
+    if (st) (void)hipStreamDestroy(st);
+    return rc;
+}
+
 // Behind the frame's launch: the sort of the trips it noted, on the frame's stream (the frame read the old order and is over when
 // the sort runs; the next frame starts after it).
 int tile_order_after_frame(vrt_ctx *c, const vrt::FrameParams &P, hipStream_t st, const TileOrderPlan &plan) {

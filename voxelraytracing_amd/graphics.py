@@ -65,6 +65,20 @@ def std_materials():
     return arr
 
 
+def selftest_tile_order(cost, tiles_x: int, tiles_y: int, radius: int, device: int = 0) -> np.ndarray:
+    """order[tiles_x * tiles_y] the tile-order kernels make of cost (radius < 0: the exact order, 1..6: the dilated block order) —
+    see vrt_selftest_tile_order in include/vrt.h.  Entries nothing wrote are 0xFFFFFFFF; a refused call raises and writes nothing."""
+    cost = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+    if cost.size != tiles_x * tiles_y:
+        raise ValueError(f"{cost.size} costs for {tiles_x} x {tiles_y} tiles")
+    order = np.full(cost.size, 0xFFFFFFFF, dtype=np.uint32)
+    lib = _ffi.vrt()
+    rc = lib.vrt_selftest_tile_order(device, cost.ctypes.data_as(C.c_void_p), tiles_x, tiles_y, radius, order.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise VrtError(rc, "vrt_selftest_tile_order refused the call")
+    return order
+
+
 class Gpu:
     """Owns one backend context; stands where the reference passes `&Gpu` (mod.rs:227-304).
 
@@ -344,6 +358,13 @@ class Gpu:
         cost = np.empty(tiles, dtype=np.uint32)
         self._ck(self._lib.vrt_read_tile_cost(self._h, cost.ctypes.data_as(C.c_void_p)))
         return cost
+
+    def read_tile_order(self, tiles: int):
+        """(order[tiles], dilated): the order the next frame of this view launches in — see vrt_read_tile_order in include/vrt.h."""
+        order = np.empty(tiles, dtype=np.uint32)
+        dilated = C.c_uint32()
+        self._ck(self._lib.vrt_read_tile_order(self._h, order.ctypes.data_as(C.c_void_p), C.byref(dilated)))
+        return order, bool(dilated.value)
 
     def lit_voxels(self, voxels: bool = False):
         """{passes, layers, lit_trips[, lit[n,n,n] indexed [z,y,x], n = 32 S]} — see vrt_read_lit_voxels in include/vrt.h."""
