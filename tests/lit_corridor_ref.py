@@ -1,4 +1,4 @@
-"""The lit rule of the sun marks (docs/NUMERICS.md "Lit stops"; vrt_accel.hip: accel_lit_kernel), stated in numpy.
+"""The lit rule of the sun marks (docs/NUMERICS.md "Lit stops"; vrt_lit.hip: accel_lit_kernel), stated in numpy.
 
 A cell of the grid (4^3 voxels) is LIT when every shadow ray with a position in it leaves the world through air.  The rule tests,
 layer by layer towards the sun, the cells such a ray can be in — REACH_k(C), from the smallest and largest slope of a line to the
@@ -6,7 +6,7 @@ sun through the cell widened by a voxel, times the rise to layer c_a + k — ove
 marks of the cells the ray can enter the next layer in.  This file is written from the text, not from the kernel: it mirrors the
 world so that the sun is always "above", works on whole layers with summed-area tables, and computes in float64.
 
-    plan(world_size, sun)                 (axis, up, min_lo) or None — vrt_uploads.hip: lit_plan
+    plan(world_size, sun)                 (axis, up, min_lo) or None — vrt_lit.hip: lit_plan
     leaf_lo(dense)                        [G, G, G] int: leaf size - 1 of every all-air cell, -1 for any other (canonical octrees)
     lit(lo, sun, depth, margins=True)     [G, G, G] uint8, indexed [z, y, x] like vrt_get_sun_marks' `lit`
 

@@ -1,4 +1,4 @@
-"""The lit rule of the voxel marks (docs/NUMERICS.md "Lit stops", the voxels of split cells; vrt_accel.hip:
+"""The lit rule of the voxel marks (docs/NUMERICS.md "Lit stops", the voxels of split cells; vrt_lit.hip:
 accel_lit_voxels_kernel), stated in numpy over a dense copy of the world.
 
 An AIR voxel (id 0) of a SPLIT cell is lit when every shadow ray with a point of its path in the voxel meets only air voxels

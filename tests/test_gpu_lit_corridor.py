@@ -1,4 +1,4 @@
-"""The lit pass that tests whole ray corridors (vrt_accel.hip: accel_lit_kernel; docs/NUMERICS.md "Lit stops") on the GPU.
+"""The lit pass that tests whole ray corridors (vrt_lit.hip: accel_lit_kernel; docs/NUMERICS.md "Lit stops") on the GPU.
 
 The marks of vrt_get_sun_marks against the rule as tests/lit_corridor_ref.py states it, over the grid the device built
 (vrt_read_accel): whatever the kernel lights, the rule evaluated in float64 without any margin must light too, and whatever the

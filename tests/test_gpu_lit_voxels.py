@@ -1,4 +1,4 @@
-"""The voxel marks (vrt_accel.hip: accel_lit_voxels_kernel; vrt_march.h (u); docs/NUMERICS.md "Lit stops") on the GPU.
+"""The voxel marks (vrt_lit.hip: accel_lit_voxels_kernel; vrt_march.h (u); docs/NUMERICS.md "Lit stops") on the GPU.
 
 Marks: the shadow pool as vrt_read_lit_voxels reads it back, against the rule as tests/lit_voxel_ref.py states it over the world
 the device built (vrt_read_accel) and the cell marks the device made (vrt_get_sun_marks).  The kernel computes in binary32 and
@@ -20,7 +20,7 @@ from voxelraytracing_amd.world import ClientWorld, gen_height, svo_build_by_set_
 pytestmark = pytest.mark.gpu
 
 AIR_LEAF = 0xFF800000
-K = 8   # the default up to 64^3 cells (vrt_uploads.hip: lit_voxel_layers)
+K = 8   # the default up to 64^3 cells (vrt_lit.hip: lit_voxel_layers)
 _scenes = {}
 
 

@@ -1,6 +1,6 @@
 """Shadow rays that stop at cells with a clear path to the sun (docs/NUMERICS.md "Lit stops"), against the oracle.
 
-The one-launch primary + shadow kernel stops a shadow ray at a LIT air leaf of the cell grid — the lit pass of vrt_accel.hip has
+The one-launch primary + shadow kernel stops a shadow ray at a LIT air leaf of the cell grid — the lit pass of vrt_lit.hip has
 proven that every ray from that cell towards the sun leaves the world through air — and the frame must stay what the oracle
 renders: ids bit for bit (VRT_ID_SHADOWED among them), radiance within the suite's 1e-4.  Every frame here is traced by the TIMED
 kernel (the counting kernels never stop early: their step counts are the oracle's, which is checked too).  Suns on every side of
@@ -161,6 +161,55 @@ def test_moved_sun_and_edits_rebuild_the_marks(orc, in_flight):
         o = orc.OracleScene(sc.world.nodes(), roots, sc.materials, sc.cam, sc.settings, sc.world.world_data())
         ids3, _ = render_and_check(orc, gpu, sc, "chunk dropped", oracle=o)
         assert not np.array_equal(ids3, ids2) and gpu.sun_marks()["passes"] > passes
+    finally:
+        gpu.close()
+
+
+@pytest.mark.parametrize("in_flight", [1, 2])
+def test_a_sun_that_swings_between_two_places_collects_no_pass(orc, in_flight):
+    """The settle count is of frames IN A ROW that ask for the same marks.  A sun that is written before every frame, at B and at A
+    in turn, never gets a pass: a frame at A finds the held marks and starts B's count over, a frame at B runs without marks.  A
+    count that B's frames collected one at a time would launch a pass on B's fourth visit."""
+    world = scenes.procedural(4, (64, 40)).world
+    ground = gen_height(1, GX, GZ)
+    sc = scenes._scene("looking down", world, (64, 40), (GX + 0.5, ground + 24.5, GZ + 0.5), (89.0, 0.0, 0.0), MODE_PRIMARY_SHADOW)
+    sun_a, sun_b = tuple(scenes.SUN_POS), (9000.0, 20000.0, -6000.0)
+    w, h = sc.size
+    ref = {}
+    for name, sun in (("A", sun_a), ("B", sun_b)):   # two oracle frames, each for its sun
+        sc.settings.sun_pos[:] = sun
+        r_rgb, r_ids, _, _ = orc.from_package_scene(sc).render(MODE_PRIMARY_SHADOW, w, h, want_steps=True)
+        ref[name] = (r_rgb, r_ids)
+    gpu = gpu_for_scene(sc)
+    gpu.set_frames_in_flight(in_flight)
+
+    def frame(name, sun):
+        sc.settings.sun_pos[:] = sun
+        gpu.write_settings(sc.settings)
+        gpu.render(MODE_PRIMARY_SHADOW, timed=True)
+        return gpu.sun_marks(), gpu.lit_voxels()
+
+    try:
+        for _ in range(SETTLE):
+            held, held_voxels = frame("A", sun_a)
+        print("after A settled:", held, held_voxels)
+        assert held["passes"] == 1 and held["lit_trips"] > 0, held
+        for k in range(12):
+            name, sun = (("B", sun_b), ("A", sun_a))[k % 2]
+            m, v = frame(name, sun)
+            print(f"frame {k} at {name}:", m, v)
+            assert m["passes"] == 1, (k, name, m)
+            if name == "B":   # the frame ran without marks
+                assert m["lit_trips"] == 0 and v["lit_trips"] == 0, (k, m, v)
+            else:             # the held marks are handed out again
+                assert m["lit_trips"] == held["lit_trips"] and v["lit_trips"] == held_voxels["lit_trips"], (k, m, v)
+            if k >= 10:       # the last frame at B and the last at A
+                rgb, ids, _ = gpu.read_output()
+                assert_frame_parity(rgb, ids, *ref[name], f"swinging sun, last frame at {name}, {in_flight} in flight")
+        for _ in range(SETTLE):
+            m, _ = frame("B", sun_b)
+        print("after B settled:", m)
+        assert m["passes"] == 2, m
     finally:
         gpu.close()
 

@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "voxelraytracing_amd", "csrc")
-PRODUCT_UNITS = ("vrt_kernels", "vrt_path", "vrt_accel", "vrt_denoise") # the translation units with kernels that ship in libvrt.so
+PRODUCT_UNITS = ("vrt_kernels", "vrt_path", "vrt_accel", "vrt_lit", "vrt_denoise") # the translation units with kernels that ship in libvrt.so
 EXPERIMENT_UNITS = ()   # none is left (csrc/experiments/ is deleted); the name stays for code written against this module that adds the two
 
 _REG = re.compile(r"(?<![\w.])(v|s|a)(\d+)\b|(?<![\w.])(v|s|a)\[(\d+):(\d+)\]|\b(vcc|exec|vcc_lo|vcc_hi|exec_lo|exec_hi|m0|scc)\b")

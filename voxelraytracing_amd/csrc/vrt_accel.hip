@@ -12,7 +12,7 @@
 //               air leaf at depth d <= 3     ->  0xFF800000 | lo          (lo 3, 7, 15 or 31: "step through, nothing to do"; the
 //                                                                          set bits make the entry the march's bit selector as
 //                                                                          it is, vrt_device.h kAirLeaf).  Bit 22 is the sun
-//                                                                          mark: written set, cleared by the lit pass below for a
+//                                                                          mark: written set, cleared by the lit pass (vrt_lit.hip) for a
 //                                                                          cell with a clear path to the sun (kAirUnlit)
 //               other leaf at depth d <= 3   ->  voxel << 16 | lo
 //               cell split at depth 3        ->  0x80000000 | brick * 64
@@ -304,21 +304,6 @@ struct ChunkList { uint32_t chunk[64]; uint32_t extent[64]; uint32_t root[64]; }
 
 constexpr uint32_t kChunkNodesMax = 0x7FFFu + 8u;  // child_idx <= 0x7FFF, + 8 children
 
-// Node `idx` of the chunk rooted at `root`: from LDS if it was staged, else from the pool (a pool whose child indices reach
-// past the chunk's own extent — no world the host mirror builds; garbage pools in the tests — is still read as the march
-// reads it); an index the 15-bit child field cannot form, or one past the end of the pool, is an air leaf.
-struct ChunkNodes {
-    const uint16_t *lds;     // staged words, relative to the root
-    const uint16_t *pool;
-    uint32_t staged, root, n_nodes;
-    __device__ __forceinline__ uint32_t operator()(uint32_t idx) const {
-        if (idx < staged) return (uint32_t)lds[idx];
-        if (idx >= kChunkNodesMax) return 0u;
-        const uint64_t g = (uint64_t)root + idx;
-        return g < n_nodes ? (uint32_t)pool[g] : 0u;
-    }
-};
-
 __global__ void __launch_bounds__(512) accel_chunks_kernel(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S,
                                                            uint32_t *grid, uint32_t *chunk_bricks, uint32_t *chunk_bases,
                                                            uint32_t *chunk_caps, uint32_t *tail, uint16_t *bricks, uint32_t brick_cap,
@@ -373,7 +358,9 @@ __global__ void __launch_bounds__(512) accel_chunks_kernel(const uint16_t *nodes
     __syncthreads();
     if (t == 0 && (n_nodes & 1u) && n_nodes - 1u >= first && n_nodes - 1u - first < vecs * 8u) s_raw[n_nodes - 1u - first] = nodes[n_nodes - 1u];
     if (n_nodes & 1u) __syncthreads();   // (uniform)
-    // node `idx` of the chunk, relative to its root: the one place that reads one (ChunkNodes above, spelled out once)
+    // node `idx` of the chunk, relative to its root — the one place that reads one: from LDS if it was staged, else from the pool (a
+    // pool whose child indices reach past the chunk's own extent — no world the host mirror builds; garbage pools in the tests — is
+    // still read as the march reads it); an index the 15-bit child field cannot form, or one past the end of the pool, is an air leaf
     const uint16_t *lds = s_raw + head;
     auto node_at = [&](uint32_t idx) __attribute__((always_inline)) -> uint32_t {
         if (idx < staged) return (uint32_t)lds[idx];
@@ -540,257 +527,7 @@ __global__ void __launch_bounds__(256) upload_batch_kernel(uint32_t *dst0, uint3
     if (tail < n) dst[tail] = last;
 }
 
-// The lit pass: the sun marks of the cell grid's air leaves (vrt_device.h kAirUnlit; docs/NUMERICS.md "Lit stops").
-//
-// A cell is LIT when a shadow ray whose position is anywhere in it meets nothing from there to the world's face.  The host has
-// picked the axis `a` on which the sun lies beyond the world (on the side `up`), and made sure that on the two other axes no ray
-// towards the sun moves more than 0.99 voxels per voxel of `a` (LitPass, vrt_uploads.hip: lit_plan).  A ray with a position in
-// cell C has the direction of a line to the sun through a point of C widened by one voxel (its positions stray from its line by
-// the nudges, less than 500 * 0.001, and their roundings), so on each other axis `b` its slope (sun_b - q_b) / (sun_a - q_a) lies
-// between the smallest and the largest one over the widened cell.  Layers are counted from C towards the sun; while the ray is in
-// layer c_a + k it has risen between max(0, 4k - 5) and 4k + 5 voxels on `a` since it was in C, so its `b` lies in
-//     [4 c_b + rise * slope_min - allow_k,  4 c_b + 4 + rise * slope_max + allow_k]      (each end with the rise that widens it)
-// (and never beyond C's own cell on a side no ray of C points to: a ray's coordinates are monotone)
-// where allow_k covers the nudges and roundings of the steps in between (0.015 per layer, never more than a ray's 500 steps can
-// add up to: 1) and this kernel's own binary32 arithmetic (0.01).  The cells overlapping that interval on both axes are
-// REACH_k(C): what a ray of C can be in while in layer c_a + k — a corridor along the rays, not a pyramid that widens by a cell
-// per layer.  For a slab of `depth` layers whose sun-side end is m layers from C's layer (m = 1 .. depth):
-//     lit(C)  <=>  for k = 0 .. m - 1 every cell of REACH_k(C) inside the world is an air leaf of at least `min_lo + 1` voxels, and
-//                  every cell a ray of C can be in when it enters layer c_a + m is lit (or outside the world).
-// The slabs are swept from the sun's side, so the marks behind a slab are final when it reads them, and all cells of a slab are
-// independent: G / depth dependent launches.  depth = G is the whole corridor in one launch; depth = 1 has the reach of a sweep
-// layer by layer.  Every air leaf of the grid gets its bit written, set or clear: nothing of an earlier sun or an earlier world
-// survives a pass.  (A cell's bit is written while neighbours test its entry: they ask `>= kAirLeaf` and `& 31`, which the bit
-// leaves alone.)
-struct LitPass {
-    uint32_t G;          // cells per axis
-    uint32_t axis;       // 0, 1, 2: x, y, z
-    uint32_t up;         // 1: the sun is beyond the world's high face of `axis`
-    uint32_t min_lo;     // leaves below min_lo + 1 voxels are never lit (the step budget: docs/NUMERICS.md)
-    float sun[3];        // settings.sun_pos - f32(world.min), as the shadow ray subtracts from it
-};
-
-// The cells of axis `b` a ray of cell c_b can be in after a rise of r_lo .. r_hi voxels, as [lo, hi] clamped to the world;
-// false: all of them lie outside it.  s_min / s_max: the slopes over the widened cell.
-__device__ inline bool lit_reach(float c4, float s_min, float s_max, float r_lo, float r_hi, float allow, uint32_t G, uint32_t *lo, uint32_t *hi) {
-    const float b_lo = c4 + (s_min < 0.0f ? r_hi : r_lo) * s_min - allow;
-    const float b_hi = c4 + 4.0f + (s_max > 0.0f ? r_hi : r_lo) * s_max + allow;
-    int l = (int)floorf(b_lo * 0.25f), h = (int)floorf(b_hi * 0.25f);
-    // a coordinate is monotone along a ray (a step adds a rounded product of the direction's sign): where no ray of the cell points
-    // to lower `b` none gets below the cell it is in, whatever the allowance says, and likewise above
-    const int own = (int)(c4 * 0.25f);
-    if (!(s_min < 0.0f)) l = max(l, own);
-    if (!(s_max > 0.0f)) h = min(h, own);
-    if (h < 0 || l >= (int)G) return false;
-    *lo = (uint32_t)max(l, 0);
-    *hi = (uint32_t)min(h, (int)G - 1);
-    return true;
-}
-
-// Smallest and largest slope on `b` of a line to the sun through the widened cell: sun_b - q_b in [n_lo, n_hi], sun_a - q_a in
-// [d_lo, d_hi] (d_lo > 0: the sun lies beyond the widened world).
-__device__ inline void lit_slopes(float n_lo, float n_hi, float d_lo, float d_hi, float *s_min, float *s_max) {
-    *s_min = n_lo / (n_lo < 0.0f ? d_lo : d_hi);
-    *s_max = n_hi / (n_hi > 0.0f ? d_lo : d_hi);
-}
-
-// One slab: layers first .. first + count - 1, counted from the sun's side; a thread per cell.
-__global__ void __launch_bounds__(256) accel_lit_kernel(uint32_t *grid, LitPass lp, uint32_t first, uint32_t count) {
-    const uint32_t G = lp.G, G1 = G + 1u;
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count * G * G) return;
-    const uint32_t a = lp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // the two other axes, the lower one fastest
-    const size_t row = G1, slab = (size_t)G1 * G1;
-    const size_t sa = a == 0u ? 1u : a == 1u ? row : slab, su = u == 0u ? 1u : row, sv = v == 1u ? row : slab;   // strides of [z][y][x]
-    const uint32_t cu = t % G, cv = (t / G) % G, j = t / (G * G);
-    const uint32_t ca = lp.up ? G - 1u - (first + j) : first + j;
-    const size_t at = ca * sa + cu * su + cv * sv;
-    const uint32_t e = grid[at];
-    if (e < kAirLeaf) return;   // not an air leaf: no mark
-    // the sweep's own frame: `a` mirrored when the sun is below, so that it grows towards the sun; i: the cell's layer there
-    const float W = (float)(G * 4u);
-    const float sun_a = lp.up ? lp.sun[a] : W - lp.sun[a], sun_u = lp.sun[u], sun_v = lp.sun[v];
-    const float a4 = (float)((G - 1u - (first + j)) * 4u), u4 = (float)(cu * 4u), v4 = (float)(cv * 4u);
-    const float d_lo = sun_a - (a4 + 5.0f), d_hi = sun_a - (a4 - 1.0f);
-    float us_min, us_max, vs_min, vs_max;
-    lit_slopes(sun_u - (u4 + 5.0f), sun_u - (u4 - 1.0f), d_lo, d_hi, &us_min, &us_max);
-    lit_slopes(sun_v - (v4 + 5.0f), sun_v - (v4 - 1.0f), d_lo, d_hi, &vs_min, &vs_max);
-    const size_t step = lp.up ? sa : (size_t)0 - sa;   // one layer towards the sun
-    bool lit = true;
-    size_t layer = ca * sa;
-    for (uint32_t k = 0; k <= j && lit; k++, layer += step) {
-        const float r_lo = k >= 2u ? (float)(4u * k - 5u) : 0.0f, r_hi = (float)(4u * k + 5u);
-        const float allow = fminf(0.015f * (float)(k + 1u), 1.0f) + 0.01f;
-        uint32_t ul, uh, vl, vh;
-        if (!lit_reach(u4, us_min, us_max, r_lo, r_hi, allow, G, &ul, &uh) || !lit_reach(v4, vs_min, vs_max, r_lo, r_hi, allow, G, &vl, &vh)) continue;
-        for (uint32_t nv = vl; nv <= vh; nv++)
-            for (uint32_t nu = ul; nu <= uh; nu++) {
-                const uint32_t own = grid[layer + nu * su + nv * sv];
-                lit = lit && own >= kAirLeaf && (own & 31u) >= lp.min_lo;
-            }
-    }
-    if (lit && first > 0u) {   // the layer behind the slab: its marks are final
-        const uint32_t m = j + 1u;
-        const float r_lo = m >= 2u ? (float)(4u * m - 5u) : 0.0f, r_hi = (float)(4u * m + 1u) + 0.01f;
-        const float allow = fminf(0.015f * (float)(m + 1u), 1.0f) + 0.01f;
-        uint32_t ul, uh, vl, vh;
-        if (lit_reach(u4, us_min, us_max, r_lo, r_hi, allow, G, &ul, &uh) && lit_reach(v4, vs_min, vs_max, r_lo, r_hi, allow, G, &vl, &vh))
-            for (uint32_t nv = vl; nv <= vh; nv++)
-                for (uint32_t nu = ul; nu <= uh; nu++) {
-                    const uint32_t nx = grid[layer + nu * su + nv * sv];
-                    lit = lit && nx >= kAirLeaf && !(nx & kAirUnlit);
-                }
-    }
-    grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
-}
-
-// The voxel marks: the lit rule carried down to the air voxels of SPLIT cells (docs/NUMERICS.md "Lit stops", the voxels of split
-// cells; tests/lit_voxel_ref.py states it in numpy).  A shadow ray starts a hair above a surface voxel, so inside a split cell, where
-// the cell marks say nothing; it walks that cell's and its neighbours' bricks voxel by voxel until it reaches an air leaf.  This
-// pass writes the table set's SHADOW POOL: the brick pool entry for entry, except that an air voxel from which every shadow ray
-// reaches lit cells through air holds kLitVoxel (its lo kept) — which the march loop of a shadow ray takes for a solid voxel, at no
-// instruction of its own (vrt_march.h (u)).  The rule is the cell rule with a cell of one voxel: slopes over the voxel widened by a
-// voxel, a rise of max(0, k - 2) .. k + 2 voxels to voxel layer k, the cell rule's allowance, one-sided intervals; layer 0 is the
-// voxel's own.  Layer by layer towards the sun every voxel of the reach must be air (an air-leaf cell is air throughout); the walk
-// ends LIT at the first layer whose whole reach lies in cells with the cell mark — a ray with a point of its path in a lit cell is a
-// ray of that cell, and the cell's proof takes over — and UNLIT at a voxel that is not air, at the world's border, or after
-// `layers` layers.  Runs behind accel_lit_kernel on its stream: the cell marks it reads are final.
-// A wave takes 16 cells of the grid — cell w, w + waves, w + 2 waves ... of the G^3 numbered with y slowest: at 16 heights, because
-// the split cells of a terrain lie together in a few layers, and a wave that met a whole row of them walked them one after the
-// other while the others had left (64 cells in a row: 640 us more than the cell marks' pass for 64^3 cells; 16 cells a slab apart: 204;
-// this: profiles/lit_voxels_ab.txt) — finds the split ones among them
-// with one ballot, and gives each a trip with a lane per voxel.  Only bricks a cell of the grid points to are written; nothing else of the pool is ever read.
-// A brick entry that holds kLitVoxel as the world's own voxel sets *clash: accel_lit_voxels_undo_kernel then makes the pool a plain copy.
-constexpr uint32_t kLitVoxelCellsPerWave = 16u;
-struct LitVoxelPass {
-    uint32_t G;          // cells per axis
-    uint32_t axis, up;   // as LitPass
-    uint32_t layers;     // K: voxel layers beyond the voxel's own
-    uint32_t entries;    // 16-bit entries of either pool
-    float sun_a, sun_u, sun_v;   // the sun on the pass's axes: on `a` mirrored with the world when the sun is below
-};
-
-// The voxels of axis `b` a ray of voxel i can be in after a rise of r_lo .. r_hi voxels, as [lo, hi]; false: some lie beyond the world.
-__device__ inline bool lit_voxel_reach(float i, float s_min, float s_max, float r_lo, float r_hi, float allow, int W, int *lo, int *hi) {
-    const float b_lo = i + (s_min < 0.0f ? r_hi : r_lo) * s_min - allow;
-    const float b_hi = i + 1.0f + (s_max > 0.0f ? r_hi : r_lo) * s_max + allow;
-    int l = (int)floorf(b_lo), h = (int)floorf(b_hi);
-    const int own = (int)i;
-    if (!(s_min < 0.0f)) l = max(l, own);   // (monotone coordinates, as lit_reach)
-    if (!(s_max > 0.0f)) h = min(h, own);
-    *lo = l;
-    *hi = h;
-    return l >= 0 && h < W;
-}
-
-// The walk of one air voxel, in the pass's own frame: `a` the sun's axis (mirrored when the sun is below, so that it grows towards
-// the sun), u and v the two others; ca / cu / cv: the strides of a cell in the bordered grid, ha / hu / hv: the shifts of a voxel's
-// two low bits in a brick's index.  One exit: the loops carry flags, not returns.
-__device__ inline bool lit_voxel_walk(const uint32_t *grid, const uint16_t *bricks, const LitVoxelPass &lp, int ia, int iu, int iv, uint32_t ca,
-                                      uint32_t cu, uint32_t cv, uint32_t ha, uint32_t hu, uint32_t hv) {
-    const int W = (int)(lp.G * 4u);
-    const float fa = (float)ia, fu = (float)iu, fv = (float)iv;
-    const float d_lo = lp.sun_a - (fa + 2.0f), d_hi = lp.sun_a - (fa - 1.0f);
-    float us_min, us_max, vs_min, vs_max;
-    lit_slopes(lp.sun_u - (fu + 2.0f), lp.sun_u - (fu - 1.0f), d_lo, d_hi, &us_min, &us_max);
-    lit_slopes(lp.sun_v - (fv + 2.0f), lp.sun_v - (fv - 1.0f), d_lo, d_hi, &vs_min, &vs_max);
-    bool open = true, lit = false;
-    for (uint32_t k = 0; k <= lp.layers && open; k++) {
-        const int la = ia + (int)k;
-        const float r_lo = k >= 2u ? (float)(k - 2u) : 0.0f, r_hi = (float)(k + 2u);
-        const float allow = fminf(0.015f * (float)(k + 1u), 1.0f) + 0.01f;
-        int ul, uh, vl, vh;
-        const bool in_u = lit_voxel_reach(fu, us_min, us_max, r_lo, r_hi, allow, W, &ul, &uh);
-        const bool in_v = lit_voxel_reach(fv, vs_min, vs_max, r_lo, r_hi, allow, W, &vl, &vh);
-        if (!in_u || !in_v || la >= W) break;   // the world's border: unlit
-        const uint32_t qa = (uint32_t)(lp.up ? la : W - 1 - la);
-        const uint32_t cell_a = (qa >> 2) * ca, bit_a = (qa & 3u) << ha;
-        bool all_air = true, all_lit = true;
-        for (int nv = vl; nv <= vh; nv++)
-            for (int nu = ul; nu <= uh; nu++) {
-                // (every coordinate is inside the world here: the cell is one of the grid's G^3)
-                const uint32_t e = grid[cell_a + ((uint32_t)nu >> 2) * cu + ((uint32_t)nv >> 2) * cv];
-                const bool split = is_split_entry(e);
-                const uint32_t at = (e & 0x7FFFFFC0u) + (bit_a | (((uint32_t)nu & 3u) << hu) | (((uint32_t)nv & 3u) << hv));
-                uint32_t voxel = 1u;   // (a brick beyond the pool: not air)
-                if (split && at < lp.entries) voxel = (uint32_t)bricks[at] >> 1;
-                all_air = all_air && (e >= kAirLeaf || (split && voxel == 0u));   // (an air-leaf cell is air throughout)
-                all_lit = all_lit && e >= kAirLeaf && !(e & kAirUnlit);
-            }
-        open = all_air && !all_lit;
-        lit = all_air && all_lit;
-    }
-    return lit;
-}
-
-__global__ void __launch_bounds__(256) accel_lit_voxels_kernel(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, LitVoxelPass lp,
-                                                               uint32_t *clash) {
-    const uint32_t G = lp.G, G1 = G + 1u, lane = threadIdx.x & 63u;
-    const uint32_t cells = G * G * G, waves = (cells + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (wave >= waves) return;   // (wave-uniform)
-    const uint32_t mine = wave + lane * waves;   // (below 2^32: lane < kLitVoxelCellsPerWave where it is used)
-    uint32_t e_mine = 0u;
-    // (the cells are numbered with y slowest — x = n % G, z = n / G % G, y = n / G^2 — so that a wave's cells lie at 16 heights)
-    if (lane < kLitVoxelCellsPerWave && mine < cells) e_mine = grid[(((mine / G) % G) * G1 + mine / (G * G)) * G1 + mine % G];   // (below 2^32: grid_dim <= 800)
-    const uint32_t a = lp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // the two other axes, as accel_lit_kernel
-    const uint32_t cs[3] = {1u, G1, G1 * G1};
-    const uint32_t ca = cs[a], cu = cs[u], cv = cs[v], ha = 2u * a, hu = 2u * u, hv = 2u * v;
-    const int W = (int)(G * 4u);
-    unsigned long long todo = __ballot(is_split_entry(e_mine));
-    while (todo) {
-        const uint32_t i = (uint32_t)__ffsll((long long)todo) - 1u;
-        todo &= todo - 1ull;
-        const uint32_t e = (uint32_t)__shfl((int)e_mine, (int)i, 64), cell = wave + i * waves;
-        if ((e & 0x7FFFFFC0u) + 64u > lp.entries) continue;   // (wave-uniform: a brick beyond the pool is never read by the march either)
-        const uint32_t at = (e & 0x7FFFFFC0u) + lane;
-        const int px = (int)((cell % G) * 4u + (lane & 3u)), py = (int)((cell / (G * G)) * 4u + ((lane >> 2) & 3u)), pz = (int)(((cell / G) % G) * 4u + (lane >> 4));
-        const int pa = a == 0u ? px : a == 1u ? py : pz, pu = u == 0u ? px : py, pv = v == 1u ? py : pz;
-        uint32_t b = bricks[at];
-        if ((b >> 1) == kLitVoxel) atomicOr(clash, 1u);
-        if ((b >> 1) == 0u && lit_voxel_walk(grid, bricks, lp, lp.up ? pa : W - 1 - pa, pu, pv, ca, cu, cv, ha, hu, hv)) b |= kLitVoxel << 1;
-        lit_bricks[at] = (uint16_t)b;
-    }
-}
-
-// ... and where the world itself holds kLitVoxel in a brick: the shadow pool becomes the plain one without any mark — entry for
-// entry, but for the world's own voxels of that id, which are written as the id below it: as solid and as little a liquid to a
-// shadow ray, of which the frame reads `hit` alone (the host builds no marks where the liquid table could tell the two apart)
-__global__ void __launch_bounds__(256) accel_lit_voxels_undo_kernel(const uint32_t *clash, const uint32_t *bricks, uint32_t *lit_bricks, uint32_t words) {
-    if (*clash == 0u) return;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < words; i += gridDim.x * blockDim.x) {
-        uint32_t w = bricks[i];
-        if (((w >> 1) & 0x7FFFu) == kLitVoxel) w &= ~2u;          // (0x7FFF -> 0x7FFE: the voxel's lowest bit is the entry's bit 1)
-        if ((w >> 17) == kLitVoxel) w &= ~(2u << 16);
-        lit_bricks[i] = w;
-    }
-}
-
 }  // namespace
-
-// The voxel marks of a table set, on `st` behind launch_accel_lit: `lit_bricks` becomes the shadow pool of `bricks` (both of
-// `entries` 16-bit entries, a multiple of 64); *clash (device) is cleared, and set if the world holds kLitVoxel in a brick.
-void launch_accel_lit_voxels(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, uint32_t entries, uint32_t G, uint32_t axis, bool up,
-                             const float sun[3], uint32_t layers, uint32_t *clash, hipStream_t st) {
-    const uint32_t u = axis == 0u ? 1u : 0u, v = axis == 2u ? 1u : 2u;
-    const LitVoxelPass lp{G, axis, up ? 1u : 0u, layers, entries, up ? sun[axis] : (float)(G * 4u) - sun[axis], sun[u], sun[v]};
-    if (hipMemsetAsync(clash, 0, sizeof(uint32_t), st) != hipSuccess) return;   // (the caller asks hipGetLastError)
-    const uint32_t waves = (G * G * G + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
-    hipLaunchKernelGGL(accel_lit_voxels_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, st, grid, bricks, lit_bricks, lp, clash);
-    const uint32_t words = entries / 2u, blocks = (words + 255u) / 256u;
-    hipLaunchKernelGGL(accel_lit_voxels_undo_kernel, dim3(blocks < 1024u ? (blocks ? blocks : 1u) : 1024u), dim3(256), 0, st, clash,
-                       reinterpret_cast<const uint32_t *>(bricks), reinterpret_cast<uint32_t *>(lit_bricks), words);
-}
-
-// The lit pass over the whole grid, on `st`: a launch per slab of `depth` layers, from the sun's side (the last one may be short).
-void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st) {
-    const LitPass lp{G, axis, up ? 1u : 0u, min_lo, {sun[0], sun[1], sun[2]}};
-    if (depth < 1u) depth = 1u;
-    for (uint32_t first = 0; first < G; first += depth) {
-        const uint32_t count = G - first < depth ? G - first : depth;
-        hipLaunchKernelGGL(accel_lit_kernel, dim3((count * G * G + 255u) / 256u), dim3(256), 0, st, grid, lp, first, count);
-    }
-}
 
 void launch_upload_batch(void *dst0, void *dst1, const void *pinned_ring, const UploadBatch &batch, uint32_t n_pieces, hipStream_t st) {
     if (!n_pieces) return;
@@ -810,37 +547,32 @@ static LiquidMask liquid_mask(const uint32_t liquid[8]) {
     return lq;
 }
 
-// march cells: dir / blocks / tail / cap (blocks null: not kept for this world; dir null: a direct world), liquid: the 256-bit is_liquid mask they are
-// built with.  launch_accel_cells leaves the number of blocks the chunks need in *total_blocks (+ 2: blocks 0 and 1).
-void launch_accel_cells(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                        uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *total, uint32_t *tail,
-                        uint32_t *chunk_needs, uint32_t *dir, uint32_t *block_tail, uint32_t *total_blocks, hipStream_t st) {
-    const uint32_t n = S * S * S;
-    hipLaunchKernelGGL(accel_cells_kernel, dim3(n), dim3(512), 0, st, nodes, n_nodes, roots, S, grid, chunk_bricks, chunk_needs);
-    hipLaunchKernelGGL(accel_scan_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t *)chunk_bricks, chunk_bases, chunk_caps, n, total, tail);
-    if (chunk_needs) {   // (the directory: block 1 is filled by the bricks pass' launcher once the blocks exist)
-        const MarchCells mc{dir, nullptr, block_tail, 0u, 0u};
-        hipLaunchKernelGGL(accel_dir_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t *)chunk_needs, S, mc, total_blocks);
-    }
+// The march cells of a table set as the kernels take them (blocks null: not kept for this world; dir null: a direct world).
+static MarchCells march_cells(const TableView &tv) { return {tv.cdir, tv.mblk, tv.mblk_tail, tv.mblk_cap, tv.cdir ? 0u : 1u}; }
+
+// The launchers unpack the views (the kernels' own parameter lists are what accel_chunks_kernel's code was sized with).  launch_accel_cells
+// leaves the bricks of all chunk regions in totals[0] and, with a directory, the blocks the chunks need in totals[1] (+ 2: blocks 0 and 1)
+void launch_accel_cells(const PoolView &pool, const TableView &tv, uint32_t *totals, uint32_t *chunk_needs, hipStream_t st) {
+    const uint32_t S = pool.S, n = S * S * S;
+    if (!tv.cdir) chunk_needs = nullptr;
+    hipLaunchKernelGGL(accel_cells_kernel, dim3(n), dim3(512), 0, st, pool.nodes, pool.n_nodes, pool.roots, S, tv.grid, tv.chunk_bricks, chunk_needs);
+    hipLaunchKernelGGL(accel_scan_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t *)tv.chunk_bricks, tv.chunk_bases, tv.chunk_caps, n, totals, tv.brick_tail);
+    if (chunk_needs)   // (the directory: block 1 is filled by the bricks pass' launcher once the blocks exist)
+        hipLaunchKernelGGL(accel_dir_kernel, dim3(1), dim3(1024), 0, st, (const uint32_t *)chunk_needs, S, march_cells(tv), totals + 1);
 }
 
 __global__ void __launch_bounds__(512) accel_air_block_kernel(uint4 *blocks) {
     blocks[512u + threadIdx.x] = make_uint4(31u, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu);   // block 1: one air leaf
 }
 
-void launch_accel_bricks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                         const uint32_t *chunk_bases, uint16_t *bricks, uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail,
-                         uint32_t block_cap, const uint32_t liquid[8], hipStream_t st) {
-    if (blocks && dir) hipLaunchKernelGGL(accel_air_block_kernel, dim3(1), dim3(512), 0, st, blocks);
-    const MarchCells mc{dir, blocks, block_tail, block_cap, dir ? 0u : 1u};
-    hipLaunchKernelGGL(accel_bricks_kernel, dim3(S * S * S), dim3(512), 0, st, nodes, n_nodes, roots, S, grid, chunk_bases, bricks,
-                       brick_cap, mc, liquid_mask(liquid));
+void launch_accel_bricks(const PoolView &pool, const TableView &tv, const uint32_t liquid[8], hipStream_t st) {
+    if (tv.mblk && tv.cdir) hipLaunchKernelGGL(accel_air_block_kernel, dim3(1), dim3(512), 0, st, tv.mblk);
+    hipLaunchKernelGGL(accel_bricks_kernel, dim3(pool.S * pool.S * pool.S), dim3(512), 0, st, pool.nodes, pool.n_nodes, pool.roots, pool.S, tv.grid,
+                       (const uint32_t *)tv.chunk_bases, tv.bricks, tv.brick_cap, march_cells(tv), liquid_mask(liquid));
 }
 
-void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                         uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *tail, uint16_t *bricks,
-                         uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail, uint32_t block_cap, const uint32_t liquid[8],
-                         const uint32_t *chunks, const uint32_t *extents, const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done) {
+void launch_accel_chunks(const PoolView &pool, const TableView &tv, const uint32_t liquid[8], const uint32_t *chunks, const uint32_t *extents,
+                         const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done) {
     // 64 KiB + of dynamic LDS needs opting in (the CU has 160 KiB); per device, and any thread may be the first
     const size_t lds = (size_t)(kChunkNodesMax + 16u) * sizeof(uint16_t);
     {   // (once per device: the call is a few microseconds of every edit's frame otherwise)
@@ -854,18 +586,18 @@ void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t
             hipFuncSetAttribute(reinterpret_cast<const void *>(accel_chunks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)
             opted_in.fetch_or(bit, std::memory_order_relaxed);
     }
-    const MarchCells mc{dir, blocks, block_tail, block_cap, dir ? 0u : 1u};
+    const MarchCells mc = march_cells(tv);
     for (uint32_t i = 0; i < n; i += 64u) {
         ChunkList list;
         const uint32_t m = n - i < 64u ? n - i : 64u;
         for (uint32_t k = 0; k < m; k++) { list.chunk[k] = chunks[i + k]; list.extent[k] = extents[i + k]; list.root[k] = chunk_roots_host[i + k]; }
         // `done` (may be null): an event the LAST launch completes — the launch's own completion signal, no marker packet behind it
         if (done && i + 64u >= n)
-            hipExtLaunchKernelGGL(accel_chunks_kernel, dim3(m), dim3(512), (uint32_t)lds, st, nullptr, done, 0, nodes, n_nodes, roots, S, grid, chunk_bricks,
-                                  chunk_bases, chunk_caps, tail, bricks, brick_cap, mc, liquid_mask(liquid), list);
+            hipExtLaunchKernelGGL(accel_chunks_kernel, dim3(m), dim3(512), (uint32_t)lds, st, nullptr, done, 0, pool.nodes, pool.n_nodes, pool.roots, pool.S,
+                                  tv.grid, tv.chunk_bricks, tv.chunk_bases, tv.chunk_caps, tv.brick_tail, tv.bricks, tv.brick_cap, mc, liquid_mask(liquid), list);
         else
-            hipLaunchKernelGGL(accel_chunks_kernel, dim3(m), dim3(512), lds, st, nodes, n_nodes, roots, S, grid, chunk_bricks, chunk_bases,
-                               chunk_caps, tail, bricks, brick_cap, mc, liquid_mask(liquid), list);
+            hipLaunchKernelGGL(accel_chunks_kernel, dim3(m), dim3(512), lds, st, pool.nodes, pool.n_nodes, pool.roots, pool.S, tv.grid, tv.chunk_bricks,
+                               tv.chunk_bases, tv.chunk_caps, tv.brick_tail, tv.bricks, tv.brick_cap, mc, liquid_mask(liquid), list);
     }
 }
 

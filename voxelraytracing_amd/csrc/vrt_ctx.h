@@ -3,6 +3,7 @@
 // the context, the kernels' launchers, and the helpers that cross a file boundary.
 //   vrt_frames.hip   contexts, uniforms, frame sets, vrt_render, read-backs, stats
 //   vrt_uploads.hip  uploads without draining, which chunks a write touched, the derived tables
+//   vrt_lit.hip      the sun marks of a table set: their kernels, the frame's hook, the read-backs
 //   vrt_present.hip  the presentation blit and the gather root's assembly
 //   vrt_group.hip    one context over several devices
 //   vrt_cast.hip, vrt_clip.hip   the world queries (vrt_cast_rays, vrt_clip_moves) over vrt_query.h: the world as a kernel
@@ -109,21 +110,14 @@ void launch_present(const Texel *out, uint32_t w, uint32_t h, uint32_t screen_w,
                     uint8_t *rgba8, bool one_to_one, const uint32_t box[4], hipStream_t st, const ToneBlit *tone = nullptr);
 void launch_assemble_shade(const FrameParams &P, const void *gathered, Texel *dst, uint32_t root_weight, uint32_t period,
                            uint64_t rank_stride, hipStream_t st);
-void launch_accel_cells(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                        uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *total, uint32_t *tail,
-                        uint32_t *chunk_needs, uint32_t *dir, uint32_t *block_tail, uint32_t *total_blocks, hipStream_t st);
-void launch_accel_bricks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                         const uint32_t *chunk_bases, uint16_t *bricks, uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail,
-                         uint32_t block_cap, const uint32_t liquid[8], hipStream_t st);
+// vrt_accel.hip's table builders over the node pool and a table set (vrt_device.h PoolView / TableView; vrt_ctx::Tables::view);
+// liquid: the 256-bit is_liquid mask the march cells are built with
+void launch_accel_cells(const PoolView &pool, const TableView &tv, uint32_t *totals, uint32_t *chunk_needs, hipStream_t st);
+void launch_accel_bricks(const PoolView &pool, const TableView &tv, const uint32_t liquid[8], hipStream_t st);
+void launch_accel_chunks(const PoolView &pool, const TableView &tv, const uint32_t liquid[8], const uint32_t *chunks, const uint32_t *extents,
+                         const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done);
 void launch_upload_words(void *dst, const void *pinned_src, uint32_t n_words, hipStream_t st);
 void launch_upload_batch(void *dst0, void *dst1, const void *pinned_ring, const UploadBatch &batch, uint32_t n_pieces, hipStream_t st);
-void launch_accel_chunks(const uint16_t *nodes, uint32_t n_nodes, const uint32_t *roots, uint32_t S, uint32_t *grid,
-                         uint32_t *chunk_bricks, uint32_t *chunk_bases, uint32_t *chunk_caps, uint32_t *tail, uint16_t *bricks,
-                         uint32_t brick_cap, uint32_t *dir, uint4 *blocks, uint32_t *block_tail, uint32_t block_cap, const uint32_t liquid[8],
-                         const uint32_t *chunks, const uint32_t *extents, const uint32_t *chunk_roots_host, uint32_t n, hipStream_t st, hipEvent_t done);
-void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32_t min_lo, const float sun[3], uint32_t depth, hipStream_t st);
-void launch_accel_lit_voxels(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, uint32_t entries, uint32_t G, uint32_t axis, bool up,
-                             const float sun[3], uint32_t layers, uint32_t *clash, hipStream_t st);
 }  // namespace vrt
 
 // Host-time profile of the frame path (VRT_HOST_PROF=1: printed at process exit): where the calling thread's microseconds per
@@ -282,40 +276,60 @@ struct vrt_ctx {
         uint32_t mblk_cap() const { return (uint32_t)(d_mblk.cap() / 512u); }     // in 512-cell blocks, as the kernels take it
         Buf<uint32_t> d_mblk_tail;
         Buf<uint32_t> d_chunk_bricks, d_chunk_bases, d_chunk_caps, d_brick_tail;
-        bool live = false;            // a copy of tabs[0] as of the last whole-world build, plus its own chunk updates since
+        // what vrt_accel.hip's builders take of the set as it is allocated now; direct: a world without the chunk directory
+        vrt::TableView view(bool direct) const {
+            return {d_grid, d_bricks, brick_cap(), d_chunk_bricks, d_chunk_bases, d_chunk_caps, d_brick_tail, direct ? nullptr : d_cdir.get(), d_mblk, d_mblk_tail, mblk_cap()};
+        }
+        bool live = false;           // a copy of tabs[0] as of the last whole-world build, plus its own chunk updates since
         std::vector<uint32_t> dirty_chunks;     // chunk slots whose nodes or root changed since this set was last brought up to date
         std::vector<uint8_t> chunk_is_dirty;    // ... as flags, [n_roots]
         std::vector<uint8_t> chunk_may_have_moved;  // rebuilt alone since the last whole-world build: may sit in the pool's tail
         uint32_t chunks_moved = 0;
         uint32_t chunk_builds = 0;              // chunks this set has rebuilt alone (vrt_accel_info reports the most advanced set's)
         uint64_t gen = 0;                       // what the set's device tables hold: a new value of c->tables_gen with every build, copy and chunk update (the lamp lists' key)
-        // the sun marks in d_grid's air leaves (vrt_accel.hip: the lit pass): what they were made for.  They hold while the set's
-        // tables are the ones they were made from (gen), the sun stands where it stood and the smallest marked leaf is the same
-        bool lit_valid = false;
-        uint64_t lit_gen = 0;
-        float lit_sun[3] = {0.f, 0.f, 0.f};
-        uint32_t lit_min_lo = 0;
-        // the voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): the shadow pool — d_bricks entry for entry, a lit air voxel of a
-        // split cell holding vrt::kLitVoxel — made behind the lit pass that made the cell marks and held exactly as long as they
-        // are; a copy of the set does not take it along.  Allocated by the set's first pass that builds voxel marks
-        Buf<uint16_t> d_lit_bricks;
-        Buf<uint32_t> d_lit_clash;              // one word: the world holds kLitVoxel in a brick (the pool is then a plain copy)
-        bool lit_voxels_valid = false;
-        uint64_t lit_pool_gen = ~0ull;          // the tables the pool was last written from (vrt_read_lit_voxels reads it back, marks or none)
-        // the flag comes back to the host behind the pass, without a wait: a frame that finds the pass over reads it, and where it is set
-        // goes back to the plain bricks; the tables it was set for get no voxel pass again (a moved sun: the world still holds the id)
-        Pinned h_lit_clash;
-        bool lit_clash_pending = false;
-        uint64_t lit_clash_gen = ~0ull;
-        uint32_t lit_voxel_layers = 0;          // K the pool was made with
-        // ... and what the frames ask for: the pass runs once kLitSettleFrames frames in a row have asked for the same marks
-        uint64_t want_gen = 0;
-        float want_sun[3] = {0.f, 0.f, 0.f};
-        uint32_t want_min_lo = 0, want_frames = 0;
-        Event ev_lit;                           // behind the set's last lit pass: a frame on another stream that reads the marks waits for it
-        bool lit_pending = false;               // ... recorded and not yet known to be over
-        hipStream_t lit_stream = nullptr;       // the stream the pass ran on (frames on it are ordered behind it as they are)
-        Event ev_lit_guard;                     // what the context's stream held when a pass on another stream was enqueued
+        // the sun marks in d_grid's air leaves and the shadow pool (vrt_lit.hip, which alone writes this record but for take_from)
+        struct SunMarks {
+            // What marks are made for: they hold while the set's tables are the ones they were made from (gen), the sun stands where
+            // it stood and the smallest marked leaf is the same.  (The sun is compared bit for bit: -0.0f is another sun than 0.0f.)
+            struct Key {
+                uint64_t gen = 0;
+                float sun[3] = {0.f, 0.f, 0.f};
+                uint32_t min_lo = 0;
+                bool same(const Key &o) const { return gen == o.gen && memcmp(sun, o.sun, sizeof sun) == 0 && min_lo == o.min_lo; }
+            } made, want;                       // what the marks in the grid were made for; what the frames ask for:
+            uint32_t want_frames = 0;           // the pass runs once kLitSettleFrames frames in a row have asked for the same marks
+            bool valid = false;                 // the grid holds marks, made for `made`
+            // the voxel marks (vrt_lit.hip: accel_lit_voxels_kernel): the shadow pool — d_bricks entry for entry, a lit air voxel of a
+            // split cell holding vrt::kLitVoxel — made behind the lit pass that made the cell marks and held exactly as long as they
+            // are; a copy of the set does not take it along.  Allocated by the set's first pass that builds voxel marks
+            Buf<uint16_t> d_pool;
+            Buf<uint32_t> d_clash;              // one word: the world holds kLitVoxel in a brick (the pool is then a plain copy)
+            bool voxels_valid = false;
+            uint64_t pool_gen = ~0ull;          // the tables the pool was last written from (vrt_read_lit_voxels reads it back, marks or none)
+            // the flag comes back to the host behind the pass, without a wait: a frame that finds the pass over reads it, and where it is set
+            // goes back to the plain bricks; the tables it was set for get no voxel pass again (a moved sun: the world still holds the id)
+            Pinned h_clash;
+            bool clash_pending = false;
+            uint64_t clash_gen = ~0ull;
+            uint32_t voxel_layers = 0;          // K the pool was made with
+            Event ev;                           // behind the set's last lit pass: a frame on another stream that reads the marks waits for it
+            bool pending = false;               // ... recorded and not yet known to be over
+            hipStream_t stream = nullptr;       // the stream the pass ran on (frames on it are ordered behind it as they are)
+            Event ev_guard;                     // what the context's stream held when a pass on another stream was enqueued
+            // do the marks in the grid hold for the set's tables as they are now (T.gen), whatever the sun?
+            bool holds(uint64_t gen) const { return valid && made.gen == gen; }
+            // is the shadow pool one of `entries` entries, and the one written from these tables by the pass whose marks hold?
+            bool pool_fits(size_t entries) const { return d_pool && d_pool.cap() == entries; }
+            bool pool_is_of(uint64_t gen, size_t entries) const { return pool_gen == gen && holds(gen) && pool_fits(entries); }
+            // What a copy of a table set (of `gen`; the original's: A of a_gen) takes along: the grid's copy carries A's cell marks,
+            // which hold for the copy if they held for the original; whoever reads the copy is ordered behind the copy; the shadow
+            // pool stays behind (a copy is made for edits, whose chunk updates drop every mark)
+            void take_from(const SunMarks &A, uint64_t a_gen, uint64_t gen) {
+                valid = A.holds(a_gen);
+                made = A.made; made.gen = gen;
+                pending = voxels_valid = false;
+            }
+        } lit;
         Event ev_updated;                       // behind this set's last chunk update (a reader of the node pool and chunk_roots)
         bool update_pending = false;            // ... recorded and not yet known to be over
     };
@@ -347,10 +361,10 @@ struct vrt_ctx {
     uint32_t path_refill = 0;      // VRT_PATH_POOL_REFILL: idle lanes that send a bounce wave back to its pool (0: the default, 16)
     uint32_t accel_builds = 0;
     bool sun_marks = true;         // VRT_SUN_MARKS=0: shadow rays never stop at lit cells (the A/B of profiles/DECISIONS.md)
-    uint32_t lit_slab = 0;         // VRT_LIT_SLAB: layers a launch of the lit pass tests a cell's corridor over (1: layer by layer; 0: by grid size, vrt_uploads.hip)
+    uint32_t lit_slab = 0;         // VRT_LIT_SLAB: layers a launch of the lit pass tests a cell's corridor over (1: layer by layer; 0: by grid size, vrt_lit.hip)
     uint32_t lit_passes = 0;       // lit passes launched (vrt_get_sun_marks)
     bool lit_voxels = true;        // VRT_LIT_VOXELS=0: the cell marks alone (the A/B of profiles/lit_voxels_ab.txt); VRT_SUN_MARKS=0 switches both off
-    int lit_voxel_layers = -1;     // VRT_LIT_VOXEL_LAYERS: voxel layers a voxel's walk may take (0: no voxel marks; -1: by grid size, vrt_uploads.hip)
+    int lit_voxel_layers = -1;     // VRT_LIT_VOXEL_LAYERS: voxel layers a voxel's walk may take (0: no voxel marks; -1: by grid size, vrt_lit.hip)
     uint32_t lit_voxel_passes = 0; // voxel-mark passes launched (vrt_read_lit_voxels)
     uint32_t lit_last_voxel_layers = 0, lit_last_voxel_trips = 0;   // of the last one-launch shadow frame: 0 = it read the plain bricks
     uint32_t lit_last_min_leaf = 0, lit_last_trips = 0;   // of the last one-launch shadow frame: 0 = its marks were off
@@ -628,13 +642,18 @@ VRT_HIDDEN int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes
 VRT_HIDDEN void mark_all_dirty(vrt_ctx *c);
 VRT_HIDDEN int ensure_accel_world(vrt_ctx *c);
 VRT_HIDDEN int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st);
-// The sun marks of table set k for the sun at `sun_local`, made on `st` if the set does not hold them; *below / *trips: what the
-// frame's shadow rays are given (FrameParams.shadow_below / lit_trips) — vrt::kAirLeaf / 0 when this world and sun get no marks
-// `shares`: the frame is of another frame set than the table set's own (tabs[0] read from a second stream)
-VRT_HIDDEN int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips,
-                                const uint16_t **shadow_bricks, uint32_t *voxel_trips);
+// wait for the frames in flight; the frame being enqueued has been announced on its stream already (alt_pending / own_pending) and stays so
+VRT_HIDDEN int quiesce_before_frame(vrt_ctx *c);
+VRT_HIDDEN size_t grid_entries(uint32_t S);   // the cell grid with its zero border: [8S][8S+1][8S+1]
 VRT_HIDDEN size_t chunk_dir_entries(uint32_t S);
 VRT_HIDDEN size_t direct_cell_entries(uint32_t S);
+// the G^3 cells (G = 8 accel_S) of a device grid of the context, without the border, on c->stream; waits for the copy
+VRT_HIDDEN int read_grid_cells(vrt_ctx *c, const uint32_t *d_grid, uint32_t *cells);
+// vrt_lit.hip: the sun marks of table set `tab` for the sun at P.sun_local, made on `st` if the set does not hold them; fills what the
+// frame's shadow rays are given (P.shadow_below, lit_trips, shadow_bricks, lit_voxel_trips: left as they are — kAirLeaf, 0, null, 0 —
+// when this world and sun get no marks or c->sun_marks is off) and c->lit_last_*, what the read-backs report of the frame.
+// `shares`: the frame is of another frame set than the table set's own (tabs[0] read from a second stream)
+VRT_HIDDEN int sun_marks_for_frame(vrt_ctx *c, uint32_t tab, hipStream_t st, bool shares, vrt::FrameParams &P);
 // vrt_lamp.hip: the frame set's lamp list, rebuilt on `st` if what it was built from has changed (the frame's tables are up to date
 // on `st` and it waits for the uploads so far); fills M.list and M.n
 VRT_HIDDEN int lamp_list_for_frame(vrt_ctx *c, uint32_t slot, uint32_t tab, hipStream_t st, vrt::LampLaunch &M);

@@ -29,14 +29,14 @@ constexpr uint32_t kCamNotFinite = 1u, kCamOnPlane = 2u, kCamOutside = 4u;   // 
 constexpr uint32_t kAirLeaf = 0xFF800000u;
 // ... of a cell split at depth 3: 0x80000000 | brick * 64 — below the air leaves: the pool holds fewer than 0x1FE0000 bricks
 __host__ __device__ inline bool is_split_entry(uint32_t e) { return (int32_t)e < 0 && e < kAirLeaf; }
-// Bit 22 of an air leaf's entry is the sun mark (vrt_accel.hip: the lit pass): SET = not known to be lit, CLEAR = every ray from
+// Bit 22 of an air leaf's entry is the sun mark (vrt_lit.hip: the lit pass): SET = not known to be lit, CLEAR = every ray from
 // this cell towards the sun meets nothing.  The builds write air leaves with the bit set; the lit pass clears it.  Nothing else reads
 // it: a voxel coordinate never reaches bit 12 (grid_dim <= 800), the direction masks of the exit-plane insert carry a zero there,
 // and everyone who asks `e >= kAirLeaf` or `e & 31` gets the answer they got.  A shadow ray asks `e < kLitBelow` instead of
 // `e < kAirLeaf` (FrameParams.shadow_below), which a lit air leaf answers like a split cell: the lane leaves the fast path, and stops.
 constexpr uint32_t kAirUnlit = 1u << 22;
 constexpr uint32_t kLitBelow = kAirLeaf | kAirUnlit;
-// The voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): a table set's SHADOW POOL is a copy of its brick pool in which a lit air
+// The voxel marks (vrt_lit.hip: accel_lit_voxels_kernel): a table set's SHADOW POOL is a copy of its brick pool in which a lit air
 // voxel of a split cell holds this voxel id — the highest a brick's 16-bit entry (voxel << 1 | lo) can carry.  Not air and, by the
 // host's check of the liquid table, not a liquid: the march loop's "solid: stop" parks a shadow lane on it as on any solid voxel, and
 // the code behind the loop tells it by the id (vrt_march.h (u)).  A world one of whose bricks holds the id gets a shadow pool without marks.
@@ -249,6 +249,19 @@ __host__ __device__ __forceinline__ uint32_t shard_tile(uint32_t t_local, uint32
 constexpr uint32_t kUploadPieceWords = 4096, kUploadBatchPieces = 128;
 struct UploadPiece { uint32_t dst_word, src_word, n_words; };
 struct UploadBatch { UploadPiece piece[kUploadBatchPieces]; };
+
+// What the table builders (vrt_accel.hip: launch_accel_*) take: the node pool, and a table set as vrt_ctx::Tables::view hands it out
+// (cdir .. mblk_cap: the march cells; the kernels' own MarchCells stays vrt_accel.hip's: it is part of three kernels' symbol names)
+struct PoolView { const uint16_t *nodes; uint32_t n_nodes; const uint32_t *roots; uint32_t S; };
+struct TableView {
+    uint32_t *grid;
+    uint16_t *bricks;
+    uint32_t brick_cap;          // in bricks
+    uint32_t *chunk_bricks, *chunk_bases, *chunk_caps, *brick_tail;
+    uint32_t *cdir;              // null: a direct world, no directory
+    uint4 *mblk;                 // null: no march cells kept for this world
+    uint32_t *mblk_tail, mblk_cap;   // ... in blocks of 512 cells
+};
 
 // A finished pixel is stored NON-TEMPORALLY (global_store ... nt): nothing on this device reads a frame's texels while the frame is
 // traced, and 33 MB of them per 1080p frame written through the L2 with the default policy push the derived tables' lines out of

@@ -738,8 +738,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         P.grid = T.d_grid;
         P.bricks = T.d_bricks;
         P.grid_dim = c->accel_S * 8u;
-        const size_t G = (size_t)c->accel_S * 8u;
-        P.grid_bytes = (uint32_t)(G * (G + 1u) * (G + 1u) * sizeof(uint32_t));  // [8S][8S+1][8S+1]: the zero border
+        P.grid_bytes = (uint32_t)(grid_entries(c->accel_S) * sizeof(uint32_t));  // [8S][8S+1][8S+1]: the zero border
         P.brick_bytes = (uint32_t)((size_t)T.brick_cap() * 64u * sizeof(uint16_t));
         if (T.d_mblk) {
             P.cdir = T.d_cdir;
@@ -762,12 +761,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
     P.clock = o.stats == 2u ? c->d_clock : nullptr;
     fill_uniforms(c, P);
     // the shadow rays of the one-launch frame stop at lit cells: this set's sun marks, made now if the tables or the sun changed
-    if (P.grid && plan.shadow && plan.variant == 0u && !plan.kstats) {
-        c->lit_last_min_leaf = c->lit_last_trips = 0u;
-        if (c->sun_marks) VRT_TRY(ensure_sun_marks(c, tab, f.st, shares, P.sun_local, &P.shadow_below, &P.lit_trips, &P.shadow_bricks, &P.lit_voxel_trips));
-        c->lit_last_voxel_layers = P.shadow_bricks ? c->tabs[tab].lit_voxel_layers : 0u;   // (vrt_read_lit_voxels)
-        c->lit_last_voxel_trips = P.lit_voxel_trips;
-    }
+    if (P.grid && plan.shadow && plan.variant == 0u && !plan.kstats) VRT_TRY(sun_marks_for_frame(c, tab, f.st, shares, P));
     if (plan.fuse_present) {
         VRT_TRY(screen_buffer_for_frame(c, f.slot, f.st, c->width, c->height));
         P.screen = reinterpret_cast<uint32_t *>(c->d_screen[f.slot].get());

@@ -652,7 +652,7 @@ __device__ __forceinline__ bool finite3(V3 v) {
 
 // CAMERA: `origin` is the camera's (a primary ray): what the march asks of the origin alone is FrameParams.cam_origin_facts, the host's.
 // SHADOW: the ray is the one-launch frame's shadow ray, of which the frame reads `hit` and nothing else (vrt_tile.h: trace_tile).  Such a
-// ray may stop at a lit air leaf (t): every ray from that cell towards the sun leaves the world through air (vrt_accel.hip: the lit
+// ray may stop at a lit air leaf (t): every ray from that cell towards the sun leaves the world through air (vrt_lit.hip: the lit
 // pass), so the reference's ray misses — provided it does not run out of its kMaxSteps lookups on the way, which P.lit_trips sees
 // to (docs/NUMERICS.md, "Lit stops").  The counting kernels (STATS) never stop early: their counts are the reference's.
 // LITVOX: ... and reads its bricks from the frame's shadow pool, where a lit air voxel of a split cell stops it (u): the kernel of the

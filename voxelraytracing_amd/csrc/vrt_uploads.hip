@@ -4,16 +4,14 @@
 
 #include "vrt_ctx.h"
 
+size_t grid_entries(uint32_t S) { const size_t G = (size_t)S * 8u; return G * (G + 1u) * (G + 1u); }
 size_t chunk_dir_entries(uint32_t S) { return (size_t)S * (S + 1u) * (S + 1u); }
 size_t direct_cell_entries(uint32_t S) { const size_t B = (size_t)S * 4u; return B * (B + 1u) * (B + 1u) * 8u; }
 
 int alloc_roots(vrt_ctx *c, uint32_t world_size) {
     const uint64_t n = (uint64_t)world_size * world_size * world_size;
     if (world_size == 0 || n > (1ull << 28)) return fail(c, VRT_ERR_INVALID_ARG, "world_size_chunks %u out of range", world_size);
-    {   // uploads into the table that goes away: launched, then waited for
-        const int rc = flush_staged(c);
-        if (rc) return rc;
-    }
+    VRT_TRY(flush_staged(c));   // uploads into the table that goes away: launched, then waited for
     if (c->up_stream) HIP_TRY(c, hipStreamSynchronize(c->up_stream));
     c->roots_tag = 0;
     c->d_roots.release();
@@ -57,6 +55,15 @@ int order_after_frames(vrt_ctx *c, hipStream_t target) {
 }
 int order_after_frames(vrt_ctx *c) { return order_after_frames(c, c->stream); }
 
+// The one host wait of the frame path, before a table set that frames in flight still read is rewritten: wait for them; the frame
+// about to be enqueued has already been announced on its stream, and stays so.
+int quiesce_before_frame(vrt_ctx *c) {
+    const bool alt = c->alt_pending, own = c->own_pending;
+    QUIESCE(c);
+    c->alt_pending = alt; c->own_pending = own;
+    return VRT_OK;
+}
+
 // Everything enqueued on c->stream so far (an upload, a table rebuild) happens before later frames on other streams.
 int publish_upload(vrt_ctx *c) {
     HIP_TRY(c, c->ev_upload.ensure());
@@ -67,10 +74,7 @@ int publish_upload(vrt_ctx *c) {
 
 // `st` (a frame stream's slot, or kMaxInFlight for c->stream) waits for the node-pool / chunk_roots uploads so far.
 int wait_for_pool_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot) {
-    {
-        const int rc = flush_staged(c);   // (what vrt_write_nodes / vrt_write_chunk_roots staged since the last flush: one launch)
-        if (rc) return rc;
-    }
+    VRT_TRY(flush_staged(c));   // (what vrt_write_nodes / vrt_write_chunk_roots staged since the last flush: one launch)
     if (!c->ev_pool_upload || c->seen_pool_gen[slot] == c->pool_gen) return VRT_OK;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_pool_upload, 0));
     c->seen_pool_gen[slot] = c->pool_gen;
@@ -79,8 +83,7 @@ int wait_for_pool_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot) {
 
 // Called before a frame is enqueued on frame stream `st` (slot 0 = own_stream, k = extra_stream[k - 1]).
 int frame_waits_for_uploads(vrt_ctx *c, hipStream_t st, uint32_t slot) {
-    const int rc = wait_for_pool_uploads(c, st, st == c->stream ? vrt_ctx::kMaxInFlight : slot);
-    if (rc) return rc;
+    VRT_TRY(wait_for_pool_uploads(c, st, st == c->stream ? vrt_ctx::kMaxInFlight : slot));
     if (st == c->stream || c->seen_gen[slot] == c->upload_gen) return VRT_OK;
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_upload, 0));
     c->seen_gen[slot] = c->upload_gen;
@@ -101,8 +104,7 @@ static int ring_place(vrt_ctx *c, size_t bytes, size_t *at) {
         // staged ranges have no event until they are flushed: a segment that still holds some (only possible when uploads that
         // are not staged — materials, ndc tables — have walked the ring round since) is flushed before it is written again
         if (c->staged_seg[next]) {
-            const int rc = flush_staged(c);
-            if (rc) return rc;
+            VRT_TRY(flush_staged(c));
         }
         c->ring_seg = next;
         c->ring_off = 0;
@@ -134,10 +136,7 @@ static int upload_waits_for_pool_readers(vrt_ctx *c) {
 int flush_staged(vrt_ctx *c) {
     if (c->staged.empty()) return VRT_OK;
     hipStream_t st = c->up_stream;
-    {
-        const int rc = upload_waits_for_pool_readers(c);
-        if (rc) return rc;
-    }
+    VRT_TRY(upload_waits_for_pool_readers(c));
     vrt::UploadBatch batch;
     uint32_t n = 0;
     auto launch = [&]() -> int {
@@ -184,8 +183,7 @@ static int stage_pool_upload(vrt_ctx *c, uint32_t buf, uint32_t dst_word, const 
             if (!(s.dst_word >= dst_word && s.dst_word + s.n_words <= end_word)) partial = true;
         }
         if (partial) {
-            const int rc = flush_staged(c);
-            if (rc) return rc;
+            VRT_TRY(flush_staged(c));
         } else {
             for (auto &s : c->staged)   // covered ones: dropped (their ring bytes are simply not copied)
                 if (s.buf == buf && s.n_words && s.dst_word >= dst_word && s.dst_word + s.n_words <= end_word) { c->staged_bytes -= (size_t)s.n_words * 4u; s.n_words = 0u; }
@@ -194,12 +192,10 @@ static int stage_pool_upload(vrt_ctx *c, uint32_t buf, uint32_t dst_word, const 
     // (half the ring: staged data is never overwritten by what follows; and no more ranges than the scan above looks through in a
     // microsecond — a host that writes node by node would otherwise pay for every range staged before it, quadratically)
     if (c->staged_bytes + bytes > 4u * vrt_ctx::kRingSegBytes || c->staged.size() >= 512u) {
-        const int rc = flush_staged(c);
-        if (rc) return rc;
+        VRT_TRY(flush_staged(c));
     }
     size_t at = 0;
-    const int rc = ring_place(c, bytes, &at);
-    if (rc) return rc;
+    VRT_TRY(ring_place(c, bytes, &at));
     memcpy(c->h_ring + at, src, bytes);
     c->staged.push_back({buf, dst_word, (uint32_t)(bytes / 4u), at});
     c->staged_bytes += bytes;
@@ -229,12 +225,10 @@ int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes, bool pool
             return stage_pool_upload(c, is_roots ? 1u : 0u,
                                      (uint32_t)(((uintptr_t)dst - (uintptr_t)(is_roots ? (void *)c->d_roots : (void *)c->d_nodes)) / 4u), src, bytes);
         // (the whole pool at join time: the synchronous route below, behind what is staged and the pool's readers)
-        int rc = flush_staged(c);
-        if (!rc) rc = upload_waits_for_pool_readers(c);
-        if (rc) return rc;
+        VRT_TRY(flush_staged(c));
+        VRT_TRY(upload_waits_for_pool_readers(c));
     } else {
-        const int rc = order_after_frames(c);
-        if (rc) return rc;
+        VRT_TRY(order_after_frames(c));
     }
     auto publish = [&]() -> int {
         if (!pool) return publish_upload(c);
@@ -248,10 +242,7 @@ int stage_upload(vrt_ctx *c, void *dst, const void *src, size_t bytes, bool pool
         return publish();
     }
     size_t at = 0;
-    {
-        const int rc = ring_place(c, bytes, &at);
-        if (rc) return rc;
-    }
+    VRT_TRY(ring_place(c, bytes, &at));
     memcpy(c->h_ring + at, src, bytes);
     vrt::launch_upload_words(dst, c->d_ring + at, (uint32_t)(bytes / 4u), st);
     HIP_TRY(c, hipGetLastError());
@@ -331,8 +322,7 @@ static int alloc_tables_like_first(vrt_ctx *c, uint32_t k) {
     auto &A = c->tabs[0];
     auto &T = c->tabs[k];
     const uint32_t S = c->accel_S, n_chunks = S * S * S;
-    const size_t G = (size_t)S * 8u, entries = G * (G + 1u) * (G + 1u);
-    HIP_TRY(c, T.d_grid.grow(entries));
+    HIP_TRY(c, T.d_grid.grow(grid_entries(S)));
     if (A.d_mblk) {
         HIP_TRY(c, T.d_cdir.grow(chunk_dir_entries(S)));
         HIP_TRY(c, T.d_mblk.exactly(A.d_mblk.cap()));
@@ -352,13 +342,9 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     auto &A = c->tabs[0];
     auto &T = c->tabs[k];
     const uint32_t S = c->accel_S, n_chunks = S * S * S;
-    const size_t G = (size_t)S * 8u, entries = G * (G + 1u) * (G + 1u);
-    {
-        const int rc = alloc_tables_like_first(c, k);
-        if (rc) return rc;
-    }
-    if (A.lit_pending && A.lit_stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, A.ev_lit, 0));   // (the marks travel with the grid)
-    HIP_TRY(c, hipMemcpyAsync(T.d_grid, A.d_grid, entries * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    VRT_TRY(alloc_tables_like_first(c, k));
+    if (A.lit.pending && A.lit.stream != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, A.lit.ev, 0));   // (the marks travel with the grid)
+    HIP_TRY(c, hipMemcpyAsync(T.d_grid, A.d_grid, grid_entries(S) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     if (A.d_mblk) {
         HIP_TRY(c, hipMemcpyAsync(T.d_cdir, A.d_cdir, chunk_dir_entries(S) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(T.d_mblk, A.d_mblk, A.d_mblk.cap() * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
@@ -377,13 +363,7 @@ static int copy_tables_from_first(vrt_ctx *c, uint32_t k) {
     T.update_pending = false;
     T.live = true;
     T.gen = ++c->tables_gen;
-    // (the grid's copy carries tabs[0]'s sun marks: they hold for the copy if they held for the original)
-    T.lit_valid = A.lit_valid && A.lit_gen == A.gen;
-    T.lit_gen = T.gen;
-    memcpy(T.lit_sun, A.lit_sun, sizeof T.lit_sun);
-    T.lit_min_lo = A.lit_min_lo;
-    T.lit_pending = false;   // (whoever reads the copy is ordered behind the copy)
-    T.lit_voxels_valid = false;   // (the shadow pool stays behind: a copy is made for edits, whose chunk updates drop every mark)
+    T.lit.take_from(A.lit, A.gen, T.gen);   // (the grid's copy carries tabs[0]'s sun marks)
     return VRT_OK;
 }
 
@@ -413,17 +393,13 @@ int ensure_accel_world(vrt_ctx *c) {
     }
     mark_all_dirty(c);   // (clears the chunk lists: a whole-world build covers them)
     QUIESCE(c);  // frames on the other streams may still be reading the old tables; this path reads a count back anyway
-    {   // ... and the node pool and chunk_roots as uploaded so far
-        const int rc = wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight);
-        if (rc) return rc;
-    }
+    VRT_TRY(wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight));   // ... and the node pool and chunk_roots as uploaded so far
     auto &A = c->tabs[0];
     c->accel_ok = false;
     c->accel_S = S;
     c->accel_dirty = false;
     const uint32_t n_chunks = S * S * S;
-    const size_t G = (size_t)S * 8u;
-    const size_t entries = G * (G + 1u) * (G + 1u);
+    const size_t entries = grid_entries(S);
     HIP_TRY(c, A.d_grid.grow(entries));
     // the border rows / entries are never written by the kernels: zero = "outside the world"
     HIP_TRY(c, hipMemsetAsync(A.d_grid, 0, entries * sizeof(uint32_t), c->stream));
@@ -441,10 +417,10 @@ int ensure_accel_world(vrt_ctx *c) {
     HIP_TRY(c, e1.ensure(hipEventDefault));
     const bool direct = S <= c->march_direct_max_s;
     c->march_direct = direct;
+    const vrt::PoolView pool{c->d_nodes, c->max_nodes, c->d_roots, S};
     auto body = [&]() -> int {
         HIP_TRY(c, hipEventRecord(e0, c->stream));
-        vrt::launch_accel_cells(c->d_nodes, c->max_nodes, c->d_roots, S, A.d_grid, A.d_chunk_bricks, A.d_chunk_bases, A.d_chunk_caps,
-                                c->d_brick_total, A.d_brick_tail, direct ? nullptr : c->d_chunk_needs.get(), A.d_cdir, A.d_mblk_tail, c->d_brick_total + 1, c->stream);
+        vrt::launch_accel_cells(pool, A.view(direct), c->d_brick_total, c->d_chunk_needs, c->stream);
         HIP_TRY(c, hipGetLastError());
         uint32_t totals[2] = {0, 0};  // bricks in all chunk regions (counts + slack); chunks that need a block of march cells
         HIP_TRY(c, hipMemcpyAsync(totals, c->d_brick_total, sizeof totals, hipMemcpyDeviceToHost, c->stream));
@@ -471,8 +447,7 @@ int ensure_accel_world(vrt_ctx *c) {
             if (cap > kAccelMaxBricks) cap = kAccelMaxBricks;
             HIP_TRY(c, A.d_bricks.grow((size_t)cap * 64u));
         }
-        vrt::launch_accel_bricks(c->d_nodes, c->max_nodes, c->d_roots, S, A.d_grid, A.d_chunk_bases, A.d_bricks, A.brick_cap(), direct ? nullptr : A.d_cdir.get(), A.d_mblk,
-                                 A.d_mblk_tail, A.mblk_cap(), c->liquid_mask, c->stream);
+        vrt::launch_accel_bricks(pool, A.view(direct), c->liquid_mask, c->stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(e1, c->stream));
         HIP_TRY(c, hipEventSynchronize(e1));
@@ -486,13 +461,8 @@ int ensure_accel_world(vrt_ctx *c) {
         A.live = true;
         A.gen = ++c->tables_gen;
         for (uint32_t k = 1; k < vrt_ctx::kMaxInFlight; k++) {   // the other sets in use start over as copies
-            if (c->tabs[k].live) {
-                const int rc = copy_tables_from_first(c, k);
-                if (rc) return rc;
-            } else if (k < c->in_flight) {   // (memory for the sets the first edit will want: an allocation is milliseconds)
-                const int rc = alloc_tables_like_first(c, k);
-                if (rc) return rc;
-            }
+            if (c->tabs[k].live) VRT_TRY(copy_tables_from_first(c, k));
+            else if (k < c->in_flight) VRT_TRY(alloc_tables_like_first(c, k));   // (memory for the sets the first edit will want: an allocation is milliseconds)
         }
         return publish_upload(c);
     };
@@ -507,29 +477,16 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
     if (!c->accel_ok || c->accel_dirty) return VRT_OK;
     auto &T = c->tabs[k];
     if (!T.live) {   // this frame set's first frame since the last whole-world build of a smaller crowd: a copy of tabs[0]
-        // (wait for the frames in flight; the frame about to be enqueued has already been announced on its stream)
-        const bool alt = c->alt_pending, own = c->own_pending;
-        QUIESCE(c);
-        c->alt_pending = alt;
-        c->own_pending = own;
-        {
-            const int rc = wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight);
-            if (rc) return rc;
-        }
+        VRT_TRY(quiesce_before_frame(c));
+        VRT_TRY(wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight));
         if (c->tabs[0].update_pending) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->tabs[0].ev_updated, 0));
-        int rc = copy_tables_from_first(c, k);
-        if (rc) return rc;
-        rc = publish_upload(c);
-        if (rc) return rc;
+        VRT_TRY(copy_tables_from_first(c, k));
+        VRT_TRY(publish_upload(c));
         if (st != c->stream) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_upload, 0));
     }
     if (T.dirty_chunks.empty()) return VRT_OK;
-    if (k == 0u && c->shared_readers_in_flight) {   // frames of other frame sets still read this set (it was shared until now)
-        const bool alt = c->alt_pending, own = c->own_pending;
-        QUIESCE(c);
-        c->alt_pending = alt;
-        c->own_pending = own;
-    }
+    // frames of other frame sets still read this set (it was shared until now)
+    if (k == 0u && c->shared_readers_in_flight) VRT_TRY(quiesce_before_frame(c));
     // how far each chunk's nodes can reach: up to the next chunk's root (ChunkAlloc's ranges are disjoint); the kernel
     // stages that much of the pool and reads anything beyond from the pool itself
     refresh_roots_index(c);
@@ -544,9 +501,8 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
     HIP_TRY(c, T.ev_updated.ensure());
     // (the next upload of nodes or roots waits for this reader: ev_updated is the completion signal of the launch itself — a
     // record behind it is one more packet between the rebuild and the frame that waits for it)
-    vrt::launch_accel_chunks(c->d_nodes, c->max_nodes, c->d_roots, c->accel_S, T.d_grid, T.d_chunk_bricks, T.d_chunk_bases, T.d_chunk_caps,
-                             T.d_brick_tail, T.d_bricks, T.brick_cap(), c->march_direct ? nullptr : T.d_cdir.get(), T.d_mblk, T.d_mblk_tail, T.mblk_cap(), c->liquid_mask,
-                             T.dirty_chunks.data(), extents.data(), roots_now.data(), (uint32_t)T.dirty_chunks.size(), st, T.ev_updated);
+    vrt::launch_accel_chunks({c->d_nodes, c->max_nodes, c->d_roots, c->accel_S}, T.view(c->march_direct), c->liquid_mask, T.dirty_chunks.data(), extents.data(),
+                             roots_now.data(), (uint32_t)T.dirty_chunks.size(), st, T.ev_updated);
     HIP_TRY(c, hipGetLastError());
     T.update_pending = true;
     T.gen = ++c->tables_gen;
@@ -559,172 +515,26 @@ int update_tables(vrt_ctx *c, uint32_t k, hipStream_t st) {
     return VRT_OK;
 }
 
-// ---- the sun marks (vrt_accel.hip: the lit pass; docs/NUMERICS.md "Lit stops") ----
-// Whether this world and this sun get marks, and which: the axis on which the sun lies beyond the world, the smallest leaf that is
-// marked, and the wave trip count up to which a mark may stop a shadow ray.
-struct LitPlan { uint32_t axis; bool up; uint32_t min_lo, trips; };
-static constexpr uint32_t kLitSettleFrames = 4;
-static bool lit_plan(uint32_t world_size, const float sun[3], LitPlan *lp) {
-    for (int k = 0; k < 3; k++)
-        if (!std::isfinite(sun[k])) return false;
-    // every ray's line passes within one voxel of the cells it is in: the directions are those from the box widened by a voxel
-    const float lo = -1.0f, hi = (float)world_size + 1.0f;
-    float best = 0.0f;
-    for (uint32_t a = 0; a < 3; a++)
-        for (int up = 0; up < 2; up++) {
-            const float clear = up ? sun[a] - hi : lo - sun[a];   // the sun's distance beyond the face, along the axis
-            if (clear > best) { best = clear; lp->axis = a; lp->up = up != 0; }
-        }
-    if (!(best > 0.0f)) return false;   // the sun is inside the world (or within a voxel of it on every axis)
-    for (uint32_t b = 0; b < 3; b++) {
-        if (b == lp->axis) continue;
-        const float lateral = std::max(std::fabs(sun[b] - lo), std::fabs(sun[b] - hi));
-        if (!(lateral <= 0.99f * best)) return false;   // some ray could cross more than a cell sideways per layer
-    }
-    // The step budget: through air leaves of at least L voxels a ray takes at most B = 6 (W / L + 1) + 2 steps to the world's face
-    // (docs/NUMERICS.md); a lit entry stops a lane only while the wave's trip count leaves the reference's ray B + 1 of its 500
-    for (uint32_t L = 4u; L <= 32u; L *= 2u) {
-        const uint32_t B = 6u * (world_size / L + 1u) + 2u;
-        if (B + 2u <= vrt::kMaxSteps) { lp->min_lo = L - 1u; lp->trips = vrt::kMaxSteps - B - 1u; return true; }
-    }
-    return false;
-}
-
-// How many layers a launch of the lit pass tests a cell's corridor over before it relies on the marks behind (vrt_accel.hip): the
-// largest depth whose pass pays for itself within 100 frames of the world it is built for, measured per grid size
-// (profiles/lit_corridor_ab.txt).  Up to 64 cells a side the whole corridor: one launch, 97 us where the sweep layer by layer took
-// 305, and 5.7 us off every frame.  Larger grids gain no frame time at any depth (their marks sit on leaves of 8 or 16 voxels, high
-// over the terrain), so a depth qualifies while its pass is no dearer than the layer-by-layer sweep's, for a sun on any axis:
-// 32 up to 128 cells a side (312 us against 494; the whole corridor: 769), 8 above (313 us against 696 for 240 cells; 16 is dearer
-// than the sweep for a sun on x).  VRT_LIT_SLAB overrides: the A/B, and the tests' comparison of the rules inside one build
-// (1: the reach of a sweep layer by layer).
-static uint32_t lit_slab_depth(const vrt_ctx *c, uint32_t G) {
-    const uint32_t depth = c->lit_slab ? c->lit_slab : G <= 64u ? G : G <= 128u ? 32u : 8u;
-    return depth < G ? depth : G;
-}
-
-// The voxel marks (vrt_accel.hip: accel_lit_voxels_kernel): how many voxel layers K a voxel's walk may take before it gives up, per
-// grid size, by the slab depth's rule — the largest K whose pass pays for itself within 100 frames (profiles/lit_voxels_ab.txt);
-// 0: no voxel marks at that size.  Up to 64 cells a side 8 layers: 99 us on the pass for 2.1 us off every frame (4: 59 us for 1.2; 12: 134
-// us for the same 2.1).  128 cells a side: the frames gain 2.0 us at 8 layers, but the pass costs 376 us more: 185 frames, so none; 240: the
-// frames get slower with the second pool, none.  VRT_LIT_VOXEL_LAYERS overrides.  And what K costs the step budget (docs/NUMERICS.md "Lit
-// stops"): from a lit voxel to the first lit cell a ray crosses at most K + 1 voxel planes of the sun's axis and, its slopes below
-// one over a rise of at most K + 2, K + 3 of each other axis with the widened voxel's — 3 K + 6 in all, allowed for in full —
-// and one re-step per plane.
-static uint32_t lit_voxel_layers(const vrt_ctx *c, uint32_t G) {
-    if (!c->lit_voxels) return 0u;
-    if (c->lit_voxel_layers >= 0) return (uint32_t)c->lit_voxel_layers;
-    return G <= 64u ? 8u : 0u;
-}
-static uint32_t lit_voxel_budget(uint32_t layers) { return 2u * (3u * layers + 6u); }
-
-// Ordered like the chunk updates of update_tables, which it follows on the frame's stream `st`: the pass is one launch per slab (ceil(G / depth): 1, 4 or 30 for the bench's worlds)
-// on `st`, behind the set's chunk update and before the frame; nothing waits for it on the host.  Whoever else reads the set:
-//   - frames of the set's own frame set run on `st` too: stream order;
-//   - a split set (edits arriving: every frame set its own tables) has no other readers;
-//   - the shared set tabs[0], read from several streams: frames of OTHER frame sets still in flight are waited for as update_tables
-//     waits for them before it rewrites a shared set (quiesce: the one host wait, of at most the frames in flight, and only when the
-//     sun moved or the world was built — an edit splits the sets first); what the context's own stream holds is waited for by an event;
-//     and every later frame on another stream waits for the pass by the event behind it (ev_lit), as it waits for ev_updated.
-int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, const float sun_local[3], uint32_t *below, uint32_t *trips,
-                     const uint16_t **shadow_bricks, uint32_t *voxel_trips) {
-    *below = vrt::kAirLeaf;
-    *trips = 0u;
-    *shadow_bricks = nullptr;
-    *voxel_trips = 0u;
-    auto &T = c->tabs[k];
-    LitPlan lp{};
-    if (!c->accel_ok || !T.live || !T.d_grid || !lit_plan(c->world.size, sun_local, &lp)) return VRT_OK;
-    const bool held = T.lit_valid && T.lit_gen == T.gen && memcmp(T.lit_sun, sun_local, sizeof T.lit_sun) == 0 && T.lit_min_lo == lp.min_lo;
-    if (held) T.want_frames = 0u;   // (a sun that swings between two places must not collect its four frames one at a time)
-    if (!held) {
-        // Marks are worth a pass (0.4 ms for 64^3 cells, 0.9 ms for the client's 240^3: profiles/sun_marks_edit_cost.txt) once what
-        // they are made from stands still: while edits arrive or the sun moves from frame to frame, the frames run without marks,
-        // as they always did, and the pass follows kLitSettleFrames frames after the last change
-        if (T.want_frames && T.want_gen == T.gen && memcmp(T.want_sun, sun_local, sizeof T.want_sun) == 0 && T.want_min_lo == lp.min_lo) {
-            T.want_frames += 1u;
-        } else {
-            T.want_gen = T.gen;
-            memcpy(T.want_sun, sun_local, sizeof T.want_sun);
-            T.want_min_lo = lp.min_lo;
-            T.want_frames = 1u;
-        }
-        if (T.want_frames < kLitSettleFrames) return VRT_OK;
-        T.want_frames = 0u;
-        if (k == 0u && (shares || c->shared_readers_in_flight)) {   // (the frame about to be enqueued has been announced on its stream already)
-            const bool alt = c->alt_pending, own = c->own_pending;
-            QUIESCE(c);
-            c->alt_pending = alt;
-            c->own_pending = own;
-            if (st != c->stream) {
-                HIP_TRY(c, T.ev_lit_guard.ensure());
-                HIP_TRY(c, hipEventRecord(T.ev_lit_guard, c->stream));
-                HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit_guard, 0));
-            }
-        }
-        if (T.lit_pending && T.lit_stream != st) HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));   // (a pass behind a pass)
-        T.lit_valid = false;
-        T.lit_voxels_valid = false;
-        vrt::launch_accel_lit(T.d_grid, c->accel_S * 8u, lp.axis, lp.up, lp.min_lo, sun_local, lit_slab_depth(c, c->accel_S * 8u), st);
-        HIP_TRY(c, hipGetLastError());
-        // the voxel marks, behind the cell marks they hand over to: not where the reserved id could be a liquid (a liquid table that is
-        // not a range below 255 covers it: ids above 255 are material 255), and not where their step budget leaves the marks no trips
-        const uint32_t layers = lit_voxel_layers(c, c->accel_S * 8u);
-        T.lit_clash_pending = false;
-        if (layers && c->liquid_is_range && lit_voxel_budget(layers) < lp.trips && T.d_bricks.cap() >= 64u && T.lit_clash_gen != T.gen) {
-            HIP_TRY(c, T.d_lit_bricks.exactly(T.d_bricks.cap()));
-            HIP_TRY(c, T.d_lit_clash.once(1));
-            HIP_TRY(c, T.h_lit_clash.ensure((size_t)64));
-            vrt::launch_accel_lit_voxels(T.d_grid, T.d_bricks, T.d_lit_bricks, (uint32_t)T.d_bricks.cap(), c->accel_S * 8u, lp.axis, lp.up, sun_local, layers,
-                                         T.d_lit_clash, st);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(T.h_lit_clash, T.d_lit_clash, sizeof(uint32_t), hipMemcpyDeviceToHost, st));   // (pinned: nothing waits; ev_lit is behind it)
-            T.lit_clash_pending = true;
-            T.lit_pool_gen = T.gen;
-            T.lit_voxels_valid = true;
-            T.lit_voxel_layers = layers;
-            c->lit_voxel_passes += 1u;
-        }
-        HIP_TRY(c, T.ev_lit.ensure());
-        HIP_TRY(c, hipEventRecord(T.ev_lit, st));
-        T.lit_pending = true;
-        T.lit_stream = st;
-        T.lit_valid = true;
-        T.lit_gen = T.gen;
-        memcpy(T.lit_sun, sun_local, sizeof T.lit_sun);
-        T.lit_min_lo = lp.min_lo;
-        c->lit_passes += 1u;
-    }
-    if (T.lit_pending && T.lit_stream != st) {   // the marks this frame reads were made on another stream
-        if (hipEventQuery(T.ev_lit) == hipSuccess) T.lit_pending = false;
-        else HIP_TRY(c, hipStreamWaitEvent(st, T.ev_lit, 0));
-    }
-    *below = vrt::kLitBelow;
-    *trips = lp.trips;
-    c->lit_last_min_leaf = lp.min_lo + 1u;
-    c->lit_last_trips = lp.trips;
-    if (T.lit_clash_pending && hipEventQuery(T.ev_lit) == hipSuccess) {   // the pass is over: did it meet the reserved id in a brick of the world?
-        T.lit_clash_pending = false;
-        if (*reinterpret_cast<volatile uint32_t *>(T.h_lit_clash.get())) { T.lit_voxels_valid = false; T.lit_clash_gen = T.gen; }   // the plain bricks from here on
-    }
-    if (T.lit_voxels_valid && T.d_lit_bricks && T.d_lit_bricks.cap() == T.d_bricks.cap() && lit_voxel_budget(T.lit_voxel_layers) < lp.trips) {
-        *shadow_bricks = T.d_lit_bricks;
-        *voxel_trips = lp.trips - lit_voxel_budget(T.lit_voxel_layers);
-    }
-    return VRT_OK;
-}
-
 // tabs[0] is what vrt_get_accel_info / vrt_read_accel report: apply what it has not caught up with (the frames since may
 // have run on other frame sets).  Waits for the frames in flight.
 static int first_tables_up_to_date(vrt_ctx *c) {
     if (!c->accel_ok || c->accel_dirty || !c->tabs[0].live) return VRT_OK;
     QUIESCE(c);
-    int rc = wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight);
-    if (rc) return rc;
+    VRT_TRY(wait_for_pool_uploads(c, c->stream, vrt_ctx::kMaxInFlight));
     if (c->ev_upload && c->stream != c->own_stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
-    rc = update_tables(c, 0, c->stream);
-    if (rc) return rc;
+    VRT_TRY(update_tables(c, 0, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+// the device layout carries a zero border row / entry ([G][G+1][G+1]); a caller gets the G^3 cells
+int read_grid_cells(vrt_ctx *c, const uint32_t *d_grid, uint32_t *cells) {
+    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u;
+    std::vector<uint32_t> t(grid_entries(c->accel_S));
+    HIP_TRY(c, hipMemcpyAsync(t.data(), d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t z = 0; z < G; z++)
+        for (size_t y = 0; y < G; y++) memcpy(cells + (z * G + y) * G, t.data() + (z * G1 + y) * G1, G * sizeof(uint32_t));
     return VRT_OK;
 }
 
@@ -755,8 +565,7 @@ int vrt_write_nodes(vrt_ctx *c, const uint16_t *pool, uint32_t start, uint32_t e
     HIP_TRY(c, hipSetDevice(c->device));
     // copy-at-call-time (write_buffer semantics: the caller may reuse `pool` as soon as this returns) through the pinned
     // ring, ordered after the frames in flight without waiting for them
-    const int rc = stage_upload(c, c->d_nodes + root, pool + root, (size_t)count * sizeof(uint16_t), true);
-    if (rc) return rc;
+    VRT_TRY(stage_upload(c, c->d_nodes + root, pool + root, (size_t)count * sizeof(uint16_t), true));
     mark_node_range_dirty(c, start, end);   // (the widening repeats a neighbour's node: nothing of its octree changes)
     if (end > start) c->accum_restart = true;
     return VRT_OK;
@@ -779,8 +588,7 @@ int vrt_write_chunk_roots_tagged(vrt_ctx *c, uint32_t offset, const uint32_t *ro
     // ... an identical rewrite changes nothing
     if (memcmp(c->h_roots.data() + offset, roots, (size_t)cut * sizeof(uint32_t)) == 0) { remember(); return VRT_OK; }
     HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = stage_upload(c, c->d_roots + offset, roots, (size_t)cut * sizeof(uint32_t), true);
-    if (rc) return rc;
+    VRT_TRY(stage_upload(c, c->d_roots + offset, roots, (size_t)cut * sizeof(uint32_t), true));
     // the slots whose root changed are the chunks to rebuild (a chunk arrived or was dropped); a recentred grid changes
     // nearly all of them and becomes a whole-world build
     for (uint32_t i = 0; i < cut && !c->accel_dirty; i++)
@@ -911,11 +719,9 @@ int vrt_get_accel_info(vrt_ctx *c, vrt_accel_info *out) {
     out->world_size_chunks = c->accel_S;
     out->cells = (uint64_t)c->accel_S * c->accel_S * c->accel_S * 512u;
     uint32_t used = 0;
-    const int rc = bricks_in_use(c, L, &used);
-    if (rc) return rc;
+    VRT_TRY(bricks_in_use(c, L, &used));
     out->bricks = used;
-    const uint64_t G = (uint64_t)c->accel_S * 8u;
-    out->bytes = G * (G + 1u) * (G + 1u) * sizeof(uint32_t) + (uint64_t)used * 64u * sizeof(uint16_t);
+    out->bytes = (uint64_t)grid_entries(c->accel_S) * sizeof(uint32_t) + (uint64_t)used * 64u * sizeof(uint16_t);
     out->builds = c->accel_builds;
     out->last_build_ms = c->accel_last_ms;
     out->ordered_frames = c->ordered_frames;
@@ -930,89 +736,19 @@ int vrt_read_accel(vrt_ctx *c, uint32_t *grid, uint16_t *bricks) {
     if (!c->accel_ok || c->accel_dirty)
         return fail(c, VRT_ERR_STATE, "vrt_read_accel: the tables are not up to date (render a frame first)");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        const int rc = first_tables_up_to_date(c);   // (the last frame may have used another frame set's tables)
-        if (rc) return rc;
-    }
-    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u;
-    if (grid) {  // the device layout carries a zero border row / entry ([G][G+1][G+1]); the caller gets the G^3 cells
-        std::vector<uint32_t> t(G * G1 * G1);
-        HIP_TRY(c, hipMemcpyAsync(t.data(), c->tabs[0].d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (size_t z = 0; z < G; z++)
-            for (size_t y = 0; y < G; y++) memcpy(grid + (z * G + y) * G, t.data() + (z * G1 + y) * G1, G * sizeof(uint32_t));
+    VRT_TRY(first_tables_up_to_date(c));   // (the last frame may have used another frame set's tables)
+    if (grid) {
+        const size_t G = (size_t)c->accel_S * 8u;
+        VRT_TRY(read_grid_cells(c, c->tabs[0].d_grid, grid));
         // the caller gets canonical entries: an air leaf without its sun mark (vrt_device.h kAirUnlit; vrt_get_sun_marks reads the marks)
         for (size_t i = 0; i < G * G * G; i++)
             if (grid[i] >= vrt::kAirLeaf) grid[i] &= ~vrt::kAirUnlit;
     }
     uint32_t used = 0;
-    const int rc = bricks_in_use(c, c->tabs[0], &used);
-    if (rc) return rc;
+    VRT_TRY(bricks_in_use(c, c->tabs[0], &used));
     if (bricks && used)
         HIP_TRY(c, hipMemcpyAsync(bricks, c->tabs[0].d_bricks, (size_t)used * 64u * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return VRT_OK;
-}
-
-int vrt_get_sun_marks(vrt_ctx *c, uint32_t *passes, uint32_t *min_leaf, uint32_t *lit_trips, uint8_t *lit) {
-    GRP_ROOT(c, vrt_get_sun_marks(d, passes, min_leaf, lit_trips, lit));
-    if (!c) return VRT_ERR_INVALID_ARG;
-    if (passes) *passes = c->lit_passes;
-    if (min_leaf) *min_leaf = c->lit_last_min_leaf;
-    if (lit_trips) *lit_trips = c->lit_last_trips;
-    if (!lit) return VRT_OK;
-    if (!c->accel_ok || c->accel_dirty || !c->tabs[c->last.tab].live)
-        return fail(c, VRT_ERR_STATE, "vrt_get_sun_marks: the tables are not up to date (render a frame first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    QUIESCE(c);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    vrt_ctx::Tables &T = c->tabs[c->last.tab];   // the table set the last frame used
-    if (T.lit_pending) { HIP_TRY(c, hipEventSynchronize(T.ev_lit)); T.lit_pending = false; }
-    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u;
-    std::vector<uint32_t> t(G * G1 * G1);
-    HIP_TRY(c, hipMemcpy(t.data(), T.d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const bool held = T.lit_valid && T.lit_gen == T.gen;
-    for (size_t z = 0; z < G; z++)
-        for (size_t y = 0; y < G; y++)
-            for (size_t x = 0; x < G; x++) {
-                const uint32_t e = t[(z * G1 + y) * G1 + x];
-                lit[(z * G + y) * G + x] = (held && e >= vrt::kAirLeaf && !(e & vrt::kAirUnlit)) ? 1u : 0u;
-            }
-    return VRT_OK;
-}
-
-int vrt_read_lit_voxels(vrt_ctx *c, uint32_t *passes, uint32_t *layers, uint32_t *lit_trips, uint8_t *lit) {
-    GRP_ROOT(c, vrt_read_lit_voxels(d, passes, layers, lit_trips, lit));
-    if (!c) return VRT_ERR_INVALID_ARG;
-    if (passes) *passes = c->lit_voxel_passes;
-    if (layers) *layers = c->lit_last_voxel_layers;
-    if (lit_trips) *lit_trips = c->lit_last_voxel_trips;
-    if (!lit) return VRT_OK;
-    if (!c->accel_ok || c->accel_dirty || !c->tabs[c->last.tab].live)
-        return fail(c, VRT_ERR_STATE, "vrt_read_lit_voxels: the tables are not up to date (render a frame first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    QUIESCE(c);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    vrt_ctx::Tables &T = c->tabs[c->last.tab];   // the table set the last frame used
-    if (T.lit_pending) { HIP_TRY(c, hipEventSynchronize(T.ev_lit)); T.lit_pending = false; }
-    const size_t G = (size_t)c->accel_S * 8u, G1 = G + 1u, W = G * 4u;
-    memset(lit, 0, W * W * W);
-    // (the pool as the last pass left it, in use or not: where the world holds the reserved id in a brick it is a copy without a mark)
-    if (!(T.lit_pool_gen == T.gen && T.lit_valid && T.lit_gen == T.gen && T.d_lit_bricks && T.d_lit_bricks.cap() == T.d_bricks.cap())) return VRT_OK;
-    std::vector<uint32_t> t(G * G1 * G1);
-    std::vector<uint16_t> pool(T.d_lit_bricks.cap());
-    HIP_TRY(c, hipMemcpy(t.data(), T.d_grid, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(pool.data(), T.d_lit_bricks, pool.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    for (size_t z = 0; z < G; z++)
-        for (size_t y = 0; y < G; y++)
-            for (size_t x = 0; x < G; x++) {
-                const uint32_t e = t[(z * G1 + y) * G1 + x];
-                const size_t at = e & 0x7FFFFFC0u;
-                if (!vrt::is_split_entry(e) || at + 64u > pool.size()) continue;
-                for (size_t u = 0; u < 64u; u++)
-                    if ((uint32_t)(pool[at + u] >> 1) == vrt::kLitVoxel)
-                        lit[((z * 4u + (u >> 4)) * W + (y * 4u + ((u >> 2) & 3u))) * W + (x * 4u + (u & 3u))] = 1u;
-            }
     return VRT_OK;
 }
 
@@ -1022,10 +758,7 @@ int vrt_read_march_cells(vrt_ctx *c, uint32_t *cells, uint32_t *direct) {
     if (!c->accel_ok || c->accel_dirty || !c->tabs[0].d_mblk)
         return fail(c, VRT_ERR_STATE, "vrt_read_march_cells: no march cells, or not up to date (render a frame first)");
     HIP_TRY(c, hipSetDevice(c->device));
-    {
-        const int rc = first_tables_up_to_date(c);   // (the last frame may have used another frame set's tables)
-        if (rc) return rc;
-    }
+    VRT_TRY(first_tables_up_to_date(c));   // (the last frame may have used another frame set's tables)
     const auto &T = c->tabs[0];
     const uint32_t S = c->accel_S;
     const size_t G = (size_t)S * 8u;
