@@ -705,8 +705,68 @@ int vrt_get_issue_profile(vrt_ctx *ctx, vrt_issue_profile *out);
 /* Self-test of the kernels' exact-arithmetic shortcuts (csrc/vrt_march.h: division and square root without the general
  * case's scaling and special-value handling, taken when every operand's magnitude is in [2^-30, 2^30]): n pseudo-random
  * operand sets (seed) on `device`, each computed both ways; *mismatches = results whose bits differ (0 on a correct
- * build).  Diagnostic only; no context needed. */
+ * build).  The composites choose their form per wave of 64 consecutive sets: seven waves of eight lie wholly in the band
+ * (its two ends included) and run the refined form against the general text, the eighth holds the sets outside it.
+ * Diagnostic only; no context needed. */
 int vrt_selftest_exact_math(int32_t device, uint32_t n, uint32_t seed, uint64_t *mismatches);
+
+/* The values themselves: what the kernels' exact-arithmetic functions return for operands the caller chose, for a
+ * reference that is not the GPU.  Diagnostic only; no context needed.  The kernel calls the functions the frame kernels
+ * call (csrc/vrt_march.h, vrt_path_common.h).
+ *   Operand set i runs on lane i % 64 of wave i / 64, and lanes past n are inactive: several of these functions choose
+ *   their form per wave (one ballot), so THE CALLER COMPOSES WHOLE WAVES — what set i returns may depend on sets
+ *   64 * (i / 64) .. 64 * (i / 64) + 63.  Words are 32-bit patterns (floats by their bits), in planes of n:
+ *   word k of set i is in[k * n + i], result word k is out[k * n + i].  `flag` is 1 when the set's wave took the refined
+ *   form, from the predicate and constants the function itself uses.
+ *     op                       in                 out
+ *     VRT_MATH_DIV             n, d               div_refined(n, d, rcp_refined(d)): n / d for d inside the band, n inside it or +-0
+ *     VRT_MATH_SQRT            x                  sqrt_banded(x)
+ *     VRT_MATH_UNIT_STEPS      x, y, z            unit_steps: x, y, z, flag
+ *     VRT_MATH_NORMALIZE       x, y, z            normalize_wave: x, y, z, flag
+ *     VRT_MATH_LENS_DIV        n, d               the lens ray's divide (lens_div), flag
+ *     VRT_MATH_LENS_SQRT       x                  the lens ray's square root (lens_sqrt_of), flag
+ *     VRT_MATH_RNG_NEXT        state              state after the draw, the uniform
+ *     VRT_MATH_RNG_NEXT_U2     state              state after the draw, the uniform clamped to 1e-10
+ *     VRT_MATH_LOG_BANDED      x                  vlog_t<true>(x) (what the kernels call: vlog)
+ *     VRT_MATH_LOG_GENERAL     x                  vlog_t<false>(x)
+ *     VRT_MATH_COS2PI          u                  vcos2pi(u)
+ *     VRT_MATH_RNG_DIR         state              state after the six draws, x, y, z, flags: bit 0 the three square roots',
+ *                                                 bit 1 the normalisation's
+ *     VRT_MATH_TRUNC2I         x                  trunc2i(x)
+ *     VRT_MATH_FLR2I           x                  flr2i(x)
+ *     VRT_MATH_ABS_MUL         a, b               |a| * b
+ *     VRT_MATH_MIN3_F32        a, b, c            min3_f32(a, b, c)
+ *     VRT_MATH_MIN3_BITS       a, b, c            min3_u32(a - 1, b - 1, c - 1) + 1 (the step's branch tree on bit patterns)
+ *     VRT_MATH_BFI             mask, a, b         (mask & a) | (~mask & b)
+ *     VRT_MATH_LOW_BITS        a, b               low_bits_of<3>, <7>, <15>, <31>(a, b)
+ *     VRT_MATH_OR_AND          a, b, c            a | (b & c)
+ *     VRT_MATH_MAD_I24         a, b, c            mad_i24(a, b, c); b is a scalar operand: every set of a wave uses the b of
+ *                                                 the wave's first set
+ * Returns VRT_ERR_INVALID_ARG, and writes nothing, for a null pointer, n == 0, n > VRT_MATH_MAX_SETS or an unknown op. */
+#define VRT_MATH_DIV 0u
+#define VRT_MATH_SQRT 1u
+#define VRT_MATH_UNIT_STEPS 2u
+#define VRT_MATH_NORMALIZE 3u
+#define VRT_MATH_LENS_DIV 4u
+#define VRT_MATH_LENS_SQRT 5u
+#define VRT_MATH_RNG_NEXT 6u
+#define VRT_MATH_RNG_NEXT_U2 7u
+#define VRT_MATH_LOG_BANDED 8u
+#define VRT_MATH_LOG_GENERAL 9u
+#define VRT_MATH_COS2PI 10u
+#define VRT_MATH_RNG_DIR 11u
+#define VRT_MATH_TRUNC2I 12u
+#define VRT_MATH_FLR2I 13u
+#define VRT_MATH_ABS_MUL 14u
+#define VRT_MATH_MIN3_F32 15u
+#define VRT_MATH_MIN3_BITS 16u
+#define VRT_MATH_BFI 17u
+#define VRT_MATH_LOW_BITS 18u
+#define VRT_MATH_OR_AND 19u
+#define VRT_MATH_MAD_I24 20u
+#define VRT_MATH_OPS 21u
+#define VRT_MATH_MAX_SETS (1u << 26)
+int vrt_selftest_math_values(int32_t device, uint32_t op, uint32_t n, const uint32_t *in, uint32_t *out);
 
 /* New relative to the reference: the lookup tables the default march derives on the device from the node pool
  * and chunk_roots (brought up to date before the next frame: only the chunks a vrt_write_nodes range or a changed

@@ -105,6 +105,11 @@ def lib() -> C.CDLL:
         L.orc_test_cos2pi.argtypes = [C.c_float]
         L.orc_test_cos2pi.restype = C.c_float
         L.orc_test_rng_dir.argtypes = [C.POINTER(u32), f32p]
+        L.orc_test_rng_dir.restype = None
+        for name, args in (("orc_rng_next_n", [vp, u32, vp, vp]), ("orc_test_log_n", [vp, u32, vp]),
+                           ("orc_test_cos2pi_n", [vp, u32, vp]), ("orc_test_rng_dir_n", [vp, u32, vp, vp])):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = None
         L.orc_node_alloc_init.argtypes = [C.POINTER(NodeAlloc), u32, u32, u32, u32]
         L.orc_node_alloc_destroy.argtypes = [C.POINTER(NodeAlloc)]
         L.orc_node_alloc_next.argtypes = [C.POINTER(NodeAlloc), C.POINTER(u32)]
@@ -219,6 +224,44 @@ def axis_rot_to_ray(rot_rad):
     out = (C.c_float * 3)()
     lib().orc_axis_rot_to_ray(_f(rot_rad, 3), out)
     return tuple(out)
+
+
+def _words(a, dtype):
+    a = np.ascontiguousarray(a).reshape(-1)
+    assert a.dtype.itemsize == 4, a.dtype
+    return a.view(dtype)
+
+
+def rng_next_n(states):
+    """orc_rng_next over an array of states: (states after the draw [n] uint32, uniforms [n] float32)."""
+    s = _words(states, np.uint32)
+    out, u = np.empty_like(s), np.empty(s.size, dtype=np.float32)
+    lib().orc_rng_next_n(s.ctypes.data, s.size, out.ctypes.data, u.ctypes.data)
+    return out, u
+
+
+def log_n(x):
+    """orc_test_log over an array of float32 (or their bit patterns)."""
+    x = _words(x, np.float32)
+    out = np.empty_like(x)
+    lib().orc_test_log_n(x.ctypes.data, x.size, out.ctypes.data)
+    return out
+
+
+def cos2pi_n(u):
+    """orc_test_cos2pi over an array of float32 (or their bit patterns)."""
+    u = _words(u, np.float32)
+    out = np.empty_like(u)
+    lib().orc_test_cos2pi_n(u.ctypes.data, u.size, out.ctypes.data)
+    return out
+
+
+def rng_dir_n(states):
+    """orc_test_rng_dir over an array of states: (states after the six draws [n] uint32, directions [n, 3] float32)."""
+    s = _words(states, np.uint32)
+    out, d = np.empty_like(s), np.empty((s.size, 3), dtype=np.float32)
+    lib().orc_test_rng_dir_n(s.ctypes.data, s.size, out.ctypes.data, d.ctypes.data)
+    return out, d
 
 
 def build_chunk_by_set_node(dense: np.ndarray, cap: int = 37449 + 64) -> np.ndarray:

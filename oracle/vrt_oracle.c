@@ -844,6 +844,28 @@ float orc_rng_next(uint32_t *state) {
     return (float)result / 4294967295.0f;
 }
 
+/* the array forms of the four above: the scalar functions themselves, called n times */
+void orc_rng_next_n(const uint32_t *state_in, uint32_t n, uint32_t *state_out, float *u) {
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t s = state_in[i];
+        u[i] = orc_rng_next(&s);
+        state_out[i] = s;
+    }
+}
+void orc_test_log_n(const float *x, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = orc_test_log(x[i]);
+}
+void orc_test_cos2pi_n(const float *u, uint32_t n, float *out) {
+    for (uint32_t i = 0; i < n; i++) out[i] = orc_test_cos2pi(u[i]);
+}
+void orc_test_rng_dir_n(const uint32_t *state_in, uint32_t n, uint32_t *state_out, float *out3) {
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t s = state_in[i];
+        orc_test_rng_dir(&s, out3 + 3u * (size_t)i);
+        state_out[i] = s;
+    }
+}
+
 /* ------------------------------------------------------------------------------------------ */
 /* NodeAlloc: common/src/world/mod.rs:213-313                                                  */
 /* ------------------------------------------------------------------------------------------ */

@@ -181,6 +181,17 @@ void orc_axis_rot_to_ray(const float rot[3], float *out3);
 /* PCG step of path_tracer.wgsl:56-61: advances *state, returns the f32 in [0,1]. */
 float orc_rng_next(uint32_t *state);
 
+/* The path trace's log, cos(2 pi u) and direction draw for tests: one value, and the same functions over arrays of n
+ * (tests/math_ref.py: 2^23 values in milliseconds; tests/test_math_ref.py holds the array forms to the scalar ones).
+ * state_out[i] is state_in[i] after the draw(s); out3 is [n][3]. */
+float orc_test_log(float x);
+float orc_test_cos2pi(float u);
+void orc_test_rng_dir(uint32_t *state, float *out3);
+void orc_rng_next_n(const uint32_t *state_in, uint32_t n, uint32_t *state_out, float *u);
+void orc_test_log_n(const float *x, uint32_t n, float *out);
+void orc_test_cos2pi_n(const float *u, uint32_t n, float *out);
+void orc_test_rng_dir_n(const uint32_t *state_in, uint32_t n, uint32_t *state_out, float *out3);
+
 /* ---- SVO data model (common/src/world/mod.rs) ---- */
 
 /* NodeAlloc, common/src/world/mod.rs:213-313. */

@@ -273,6 +273,7 @@ VRT_SYMBOLS = {
     "vrt_read_output": (C.c_int, [_P, _P, _P, _P]),
     "vrt_present": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, _P]),
     "vrt_selftest_exact_math": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "vrt_selftest_math_values": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, _P, _P]),
     "vrt_present_device": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "vrt_set_presentation": (C.c_int, [_P, C.POINTER(Crosshair), C.c_uint32, C.c_uint32, C.c_uint32]),
     "vrt_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),

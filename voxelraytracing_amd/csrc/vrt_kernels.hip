@@ -16,6 +16,7 @@
 #include <hip/hip_ext.h>
 
 #include <atomic>
+#include <utility>
 
 #include "vrt_tile.h"
 #include "both/tone_math.h"   // (the mapped blits: vrt_set_tone_map)
@@ -849,9 +850,16 @@ __global__ void selftest_exact_math_kernel(uint32_t n, uint32_t seed, unsigned l
     uint32_t bad = 0u;
     if (i < n) {
         const uint32_t h0 = st_hash(i * 4u + seed), h1 = st_hash(i * 4u + 1u + seed * 0x9E3779B9u), h2 = st_hash(i * 4u + 2u + seed), h3 = st_hash(i * 4u + 3u + seed);
-        // exponent fields 97 .. 157 = the band [2^-30, 2^31); every 16th operand set sits on the band's edges
+        // The band is [2^-30, 2^30] (in_band: bit patterns 0x30800000 .. 0x4E800000, both ends included), and unit_steps and
+        // normalize_wave choose per WAVE.  Seven waves of eight (of 64 consecutive operand sets) lie wholly in it — exponent fields
+        // 97 .. 156, and every 16th set at the two ends exactly — so the composites below run their refined branch there; the
+        // eighth holds what is outside: fields up to 157 (every 16th set with v.y in [2^30, 2^31)), and takes the general one.
         const bool edge = (i & 15u) == 0u;
-        const V3 v{st_float(h0, edge ? 97u : 97u, edge ? 97u : 157u), st_float(h1, edge ? 157u : 97u, 157u), st_float(h2, 97u, 157u)};
+        const bool outside = ((i >> 6) & 7u) == 7u;
+        V3 v;
+        if (outside) v = V3{st_float(h0, 97u, edge ? 97u : 157u), st_float(h1, edge ? 157u : 97u, 157u), st_float(h2, 97u, 157u)};
+        else if (edge) v = V3{__uint_as_float((h0 & 0x80000000u) | kBandLo), __uint_as_float((h1 & 0x80000000u) | (kBandLo + kBandSpan)), st_float(h2, 97u, 156u)};
+        else v = V3{st_float(h0, 97u, 156u), st_float(h1, 97u, 156u), st_float(h2, 97u, 156u)};
         // one division, bit for bit
         const float q_fast = div_refined(v.x, v.y, rcp_refined(v.y)), q_gen = st_div_general(v.x, v.y);
         bad += __float_as_uint(q_fast) != __float_as_uint(q_gen);
@@ -881,6 +889,107 @@ __global__ void selftest_exact_math_kernel(uint32_t n, uint32_t seed, unsigned l
     if (bad) atomicAdd(mismatches, (unsigned long long)bad);
 }
 
+// ------------------------------------------------------------------------------------------------
+// vrt_selftest_math_values: what the functions above and the one-instruction helpers of vrt_march.h return, word for word, for
+// operands the caller chose — the values themselves, for a reference that is not this GPU (tests/test_gpu_math_values.py).
+// The kernel calls the functions the frame kernels call.  Operand set i is lane i % 64 of wave i / 64 (256 threads a block);
+// lanes past n have left, so a ballot sees the sets of its own wave and nothing else.  Words are planes of n: in[k * n + i].
+// ------------------------------------------------------------------------------------------------
+struct MathWords { uint8_t in, out; };
+constexpr MathWords kMathWords[VRT_MATH_OPS] = {
+    {2, 1}, {1, 1}, {3, 4}, {3, 4}, {2, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 1}, {1, 1}, {1, 1}, {1, 5},
+    {1, 1}, {1, 1}, {2, 1}, {3, 1}, {3, 1}, {3, 1}, {2, 4}, {3, 1}, {3, 1}};
+
+template <uint32_t OP>
+__global__ void __launch_bounds__(256) selftest_math_values_kernel(uint32_t n, const uint32_t *in, uint32_t *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    auto U = [&](uint32_t k) { return in[(size_t)k * n + i]; };
+    auto F = [&](uint32_t k) { return __uint_as_float(in[(size_t)k * n + i]); };
+    auto put = [&](uint32_t k, uint32_t w) { out[(size_t)k * n + i] = w; };
+    auto putf = [&](uint32_t k, float f) { out[(size_t)k * n + i] = __float_as_uint(f); };
+    auto put3 = [&](const V3 &v) { putf(0, v.x); putf(1, v.y); putf(2, v.z); };
+    if constexpr (OP == VRT_MATH_DIV) {
+        putf(0, div_refined(F(0), F(1), rcp_refined(F(1))));
+    } else if constexpr (OP == VRT_MATH_SQRT) {
+        putf(0, sqrt_banded(F(0)));
+    } else if constexpr (OP == VRT_MATH_UNIT_STEPS) {
+        const V3 v{F(0), F(1), F(2)};
+        put3(unit_steps(v));
+        put(3, __ballot(!in_band3(v)) == 0ull ? 1u : 0u);
+    } else if constexpr (OP == VRT_MATH_NORMALIZE) {
+        const V3 v{F(0), F(1), F(2)};
+        put3(normalize_wave(v));
+        put(3, __ballot(!in_band3(v)) == 0ull ? 1u : 0u);
+    } else if constexpr (OP == VRT_MATH_LENS_DIV) {
+        const float a = F(0), d = F(1);
+        putf(0, lens_div(a, d));
+        put(1, __ballot(!((a == 0.0f || in_band(a)) && in_band(d))) == 0ull ? 1u : 0u);
+    } else if constexpr (OP == VRT_MATH_LENS_SQRT) {
+        const float x = F(0);
+        putf(0, lens_sqrt_of(x));
+        put(1, __ballot(!(x >= kSqrtBandLo)) == 0ull ? 1u : 0u);
+    } else if constexpr (OP == VRT_MATH_RNG_NEXT) {
+        uint32_t s = U(0);
+        const float u = rng_next(s);
+        put(0, s); putf(1, u);
+    } else if constexpr (OP == VRT_MATH_RNG_NEXT_U2) {
+        uint32_t s = U(0);
+        const float u = rng_next_u2(s);
+        put(0, s); putf(1, u);
+    } else if constexpr (OP == VRT_MATH_LOG_BANDED) {
+        putf(0, vlog_t<true>(F(0)));
+    } else if constexpr (OP == VRT_MATH_LOG_GENERAL) {
+        putf(0, vlog_t<false>(F(0)));
+    } else if constexpr (OP == VRT_MATH_COS2PI) {
+        putf(0, vcos2pi(F(0)));
+    } else if constexpr (OP == VRT_MATH_RNG_DIR) {
+        uint32_t s = U(0), t = s;
+        const V3 d = rng_next_dir(s);
+        put(0, s); putf(1, d.x); putf(2, d.y); putf(3, d.z);
+        // the two choices rng_next_dir made for this wave, from its own draws: bit 0 the square roots', bit 1 the normalisation's
+        // (whose vector is the same from either square root)
+        const float u1x = rng_next(t), tx = -2.0f * vlog(rng_next_u2(t));
+        const float u1y = rng_next(t), ty = -2.0f * vlog(rng_next_u2(t));
+        const float u1z = rng_next(t), tz = -2.0f * vlog(rng_next_u2(t));
+        const uint32_t roots = __ballot(!(min3_f32(tx, ty, tz) >= kSqrtBandLo)) == 0ull ? 1u : 0u;
+        const V3 v{sqrtf(tx) * vcos2pi(u1x), sqrtf(ty) * vcos2pi(u1y), sqrtf(tz) * vcos2pi(u1z)};
+        put(4, roots | (__ballot(!in_band3(v)) == 0ull ? 2u : 0u));
+    } else if constexpr (OP == VRT_MATH_TRUNC2I) {
+        put(0, (uint32_t)trunc2i(F(0)));
+    } else if constexpr (OP == VRT_MATH_FLR2I) {
+        put(0, (uint32_t)flr2i(F(0)));
+    } else if constexpr (OP == VRT_MATH_ABS_MUL) {
+        putf(0, abs_mul(F(0), F(1)));
+    } else if constexpr (OP == VRT_MATH_MIN3_F32) {
+        putf(0, min3_f32(F(0), F(1), F(2)));
+    } else if constexpr (OP == VRT_MATH_MIN3_BITS) {
+        put(0, min3_u32(U(0) - 1u, U(1) - 1u, U(2) - 1u) + 1u);
+    } else if constexpr (OP == VRT_MATH_BFI) {
+        put(0, bfi(U(0), U(1), U(2)));
+    } else if constexpr (OP == VRT_MATH_LOW_BITS) {
+        const uint32_t a = U(0), b = U(1);
+        put(0, low_bits_of<3u>(a, b)); put(1, low_bits_of<7u>(a, b)); put(2, low_bits_of<15u>(a, b)); put(3, low_bits_of<31u>(a, b));
+    } else if constexpr (OP == VRT_MATH_OR_AND) {
+        put(0, or_and(U(0), U(1), U(2)));
+    } else {
+        static_assert(OP == VRT_MATH_MAD_I24, "an op of include/vrt.h");
+        // (the second factor is wave-uniform in the march — a scalar operand: the wave's is its first set's.  A scalar register that a
+        // vector instruction wrote needs two wait states before a vector instruction reads it, and the compiler adds none in front
+        // of an asm statement: tests/test_isa_hazards.py.  The march's strides come from scalar instructions.)
+        uint32_t b = __builtin_amdgcn_readfirstlane(U(1));
+        asm volatile("s_nop 1" : "+s"(b));
+        put(0, mad_i24((int)U(0), b, U(2)));
+    }
+}
+
+using MathKernel = void (*)(uint32_t, const uint32_t *, uint32_t *);
+template <uint32_t... OP>
+static MathKernel math_kernel(uint32_t op, std::integer_sequence<uint32_t, OP...>) {
+    static const MathKernel table[] = {selftest_math_values_kernel<OP>...};
+    return table[op];
+}
+
 }  // namespace vrt
 
 extern "C" int vrt_selftest_exact_math(int32_t device, uint32_t n, uint32_t seed, uint64_t *mismatches) {
@@ -897,5 +1006,25 @@ extern "C" int vrt_selftest_exact_math(int32_t device, uint32_t n, uint32_t seed
     }
     (void)hipFree(d);
     *mismatches = h;
+    return rc;
+}
+
+extern "C" int vrt_selftest_math_values(int32_t device, uint32_t op, uint32_t n, const uint32_t *in, uint32_t *out) {
+    if (!in || !out || n == 0u || n > VRT_MATH_MAX_SETS || op >= VRT_MATH_OPS) return VRT_ERR_INVALID_ARG;
+    if (hipSetDevice(device) != hipSuccess) return VRT_ERR_DEVICE;
+    const size_t in_bytes = (size_t)vrt::kMathWords[op].in * n * 4u, out_bytes = (size_t)vrt::kMathWords[op].out * n * 4u;
+    uint32_t *din = nullptr, *dout = nullptr;
+    int rc = VRT_OK;
+    if (hipMalloc(&din, in_bytes) != hipSuccess || hipMalloc(&dout, out_bytes) != hipSuccess) rc = VRT_ERR_DEVICE;
+    if (rc == VRT_OK && hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = VRT_ERR_DEVICE;
+    if (rc == VRT_OK) {
+        hipLaunchKernelGGL(vrt::math_kernel(op, std::make_integer_sequence<uint32_t, VRT_MATH_OPS>{}), dim3((n + 255u) / 256u), dim3(256), 0,
+                           nullptr, n, (const uint32_t *)din, dout);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = VRT_ERR_DEVICE;
+    }
+    // (every word of out is written by its own set's lane: a copy of the whole of it, and only behind a kernel that ran)
+    if (rc == VRT_OK && hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = VRT_ERR_DEVICE;
+    if (din) (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
     return rc;
 }

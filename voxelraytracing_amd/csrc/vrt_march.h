@@ -10,7 +10,8 @@ namespace vrt {
 
 // f32 -> i32 with the hardware's own NaN -> 0 (v_cvt_i32_f32; what WGSL's i32(f32) specifies), truncating.
 // For x >= 0 this is floor(x); the march never uses it for a negative coordinate (it has left the world).
-// Measured on MI355X: NaN -> 0, +-inf and |x| >= 2^31 saturate.  (v_cvt_flr_i32_f32 maps NaN to INT_MAX.)
+// Measured on MI355X: NaN -> 0, +-inf and |x| >= 2^31 saturate.  (v_cvt_flr_i32_f32 saturates a NaN by its sign bit: INT_MAX, or
+// INT_MIN for a NaN with the sign set — flr2i below; tests/test_gpu_math_values.py holds both conversions.)
 __device__ __forceinline__ int trunc2i(float x) {
     int r;
     asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(x));
@@ -47,14 +48,20 @@ __device__ __forceinline__ float rcp_refined(float d) {
     const float e = __builtin_fmaf(-d, r, 1.0f);
     return __builtin_fmaf(e, r, r);
 }
-// n / d given r = rcp_refined(d): the expansion's multiply and four FMAs
-__device__ __forceinline__ float div_refined(float n, float d, float r) {
+// n / d given r = rcp_refined(d), both inside the band: the expansion's multiply and four FMAs.  What unit_steps and normalize_wave
+// call — their ballot admits nothing else — and vlog, whose numerator m - 1 may also be +0 over a denominator above zero: +0, from
+// this as from the general form.  NOT for a zero numerator otherwise: the exact residual -d * q + n is +0 and +0 + -0 is +0, so
+// -0 / d comes out +0 for d > 0 (tests/test_gpu_math_values.py found it, in the form lens_div called until then).
+__device__ __forceinline__ float div_in_band(float n, float d, float r) {
     const float q0 = n * r;
     const float e0 = __builtin_fmaf(-d, q0, n);
     const float q1 = __builtin_fmaf(e0, r, q0);
     const float e1 = __builtin_fmaf(-d, q1, n);
     return __builtin_fmaf(e1, r, q1);
 }
+// ... and for a numerator that may also be +-0 over either sign (lens_div's pixel coordinate): the expansion's v_div_fixup behind it,
+// which returns its first operand inside the band and gives a zero quotient the sign of n / d, as the general sequence does
+__device__ __forceinline__ float div_refined(float n, float d, float r) { return __builtin_amdgcn_div_fixupf(div_in_band(n, d, r), d, n); }
 // sqrt(x) for 2^-96 <= x < inf: v_sqrt_f32, then one ulp down / up if the residual says so
 __device__ __forceinline__ float sqrt_banded(float x) {
     const float s = __builtin_amdgcn_sqrtf(x);
@@ -69,9 +76,9 @@ __device__ __forceinline__ V3 unit_steps(V3 dir) {
     if (__ballot(!in_band3(dir)) == 0ull) {
         // (ratios within 2^+-60, their squares within 2^+-120: the sums are finite and >= 1)
         const float rx = rcp_refined(dir.x), ry = rcp_refined(dir.y), rz = rcp_refined(dir.z);
-        const float yx = div_refined(dir.y, dir.x, rx), zx = div_refined(dir.z, dir.x, rx);
-        const float xy = div_refined(dir.x, dir.y, ry), zy = div_refined(dir.z, dir.y, ry);
-        const float xz = div_refined(dir.x, dir.z, rz), yz = div_refined(dir.y, dir.z, rz);
+        const float yx = div_in_band(dir.y, dir.x, rx), zx = div_in_band(dir.z, dir.x, rx);
+        const float xy = div_in_band(dir.x, dir.y, ry), zy = div_in_band(dir.z, dir.y, ry);
+        const float xz = div_in_band(dir.x, dir.z, rz), yz = div_in_band(dir.y, dir.z, rz);
         return V3{fabsf(sqrt_banded(1.0f + yx * yx + zx * zx)), fabsf(sqrt_banded(1.0f + xy * xy + zy * zy)),
                   fabsf(sqrt_banded(1.0f + xz * xz + yz * yz))};
     }
@@ -84,7 +91,7 @@ __device__ __forceinline__ V3 normalize_wave(V3 v) {
     if (__ballot(!in_band3(v)) == 0ull) {
         const float len = sqrt_banded(vdot(v, v));   // in [2^-30, 2^31]
         const float r = rcp_refined(len);
-        return V3{div_refined(v.x, len, r), div_refined(v.y, len, r), div_refined(v.z, len, r)};
+        return V3{div_in_band(v.x, len, r), div_in_band(v.y, len, r), div_in_band(v.z, len, r)};
     }
     return vnormalize(v);
 }
@@ -480,7 +487,8 @@ __device__ __forceinline__ float abs_mul(float a, float b) {
 }
 
 // f32 -> i32 rounding towards -inf (v_cvt_flr_i32_f32): the integer part of every coordinate inside the world, -1 for
-// the positions just beyond a low face (a step overshoots a face by 0.001 |dir|).
+// the positions just beyond a low face (a step overshoots a face by 0.001 |dir|).  +-inf and |x| >= 2^31 saturate, and so does
+// a NaN, by its sign bit (INT_MAX / INT_MIN: not 0, as trunc2i) — a wave that may hold one is `careful` and asks the shader's own test.
 __device__ __forceinline__ int flr2i(float x) {
     int r;
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));

@@ -16,7 +16,7 @@ __device__ __forceinline__ float rng_next(uint32_t &state) {
 }
 
 // ln(x), x normal > 0: x = m * 2^e with m in (sqrt(1/2), sqrt(2)], ln m = 2 atanh((m-1)/(m+1))
-// BANDED: the one division without the general sequence's scaffolding (vrt_march.h: rcp_refined / div_refined).  Its operands are
+// BANDED: the one division without the general sequence's scaffolding (vrt_march.h: rcp_refined / div_in_band).  Its operands are
 // always inside what that needs: m + 1 in [1.70, 2.42]; m - 1 is zero — +0 / d is +0 from either form — or of magnitude >= 2^-24
 // (m is a binary32 in (0.707, 1.4143]).  So there is no choice to make per wave: 8 instructions for 11, 25 issue cycles for 40.
 // vrt_selftest_exact_math runs both forms over every mantissa.
@@ -27,7 +27,7 @@ __device__ __forceinline__ float vlog_t(float x) {
     float m = __uint_as_float((b & 0x007FFFFFu) | 0x3F800000u);
     if (m > 1.41421354f) { m = m * 0.5f; e += 1; }
     const float num = m - 1.0f, den = m + 1.0f;
-    const float s = BANDED ? div_refined(num, den, rcp_refined(den)) : num / den;
+    const float s = BANDED ? div_in_band(num, den, rcp_refined(den)) : num / den;
     const float z = s * s;
     const float p = z * (0.333333343f + z * (0.2f + z * (0.142857149f + z * (0.111111112f + z * 0.0909090936f))));
     return (float)e * 0.693147182f + (s + s * p) * 2.0f;
@@ -54,18 +54,33 @@ __device__ __forceinline__ float rng_next_u2(uint32_t &state) {
     const float u2 = rng_next(state);
     return u2 < 1.0e-10f ? 1.0e-10f : u2;
 }
+// what a wave's square-root arguments must all reach to take sqrt_banded (its range is [2^-96, inf); !(x >= this) also sends
+// -0 and NaN to sqrtf): rng_next_dir below and lens_sqrt_of
+constexpr float kSqrtBandLo = 1.0e-28f;
 __device__ __forceinline__ V3 rng_next_dir(uint32_t &state) {
     const float u1x = rng_next(state), tx = -2.0f * vlog(rng_next_u2(state));
     const float u1y = rng_next(state), ty = -2.0f * vlog(rng_next_u2(state));
     const float u1z = rng_next(state), tz = -2.0f * vlog(rng_next_u2(state));
-    constexpr float kSqrtBandLo = 1.0e-28f;   // (sqrt_banded's range is [2^-96, inf); the arguments are <= 46.1)
-    float rx, ry, rz;
+    float rx, ry, rz;   // (the arguments are <= 46.1)
     if (__ballot(!(min3_f32(tx, ty, tz) >= kSqrtBandLo)) == 0ull) {
         rx = sqrt_banded(tx); ry = sqrt_banded(ty); rz = sqrt_banded(tz);
     } else {
         rx = sqrtf(tx); ry = sqrtf(ty); rz = sqrtf(tz);
     }
     return normalize_wave(V3{rx * vcos2pi(u1x), ry * vcos2pi(u1y), rz * vcos2pi(u1z)});
+}
+
+// The IEEE divide and square root of a lens sample's ray (vrt_path_lens.h: lens_ray hands them to both/lens_math.h) in vrt_march.h's
+// refined forms when every lane's operands are in their range — a ballot each; a zero numerator is: +-0 / d is +-0 from either form
+// (div_refined's fix-up: vrt_march.h).
+// Named, not lambdas of lens_ray, so that vrt_selftest_math_values calls the same text.
+__device__ __forceinline__ float lens_div(float n, float d) {
+    if (__ballot(!((n == 0.0f || in_band(n)) && in_band(d))) == 0ull) return div_refined(n, d, rcp_refined(d));
+    return n / d;
+}
+__device__ __forceinline__ float lens_sqrt_of(float x) {
+    if (__ballot(!(x >= kSqrtBandLo)) == 0ull) return sqrt_banded(x);
+    return sqrtf(x);
 }
 
 // The material colour of a hit after face shading (ray_tracer.wgsl:296-314) — shade()'s first half.

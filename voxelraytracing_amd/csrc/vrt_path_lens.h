@@ -26,19 +26,12 @@ __device__ __forceinline__ void lens_ray(const FrameParams &P, const LensLaunch 
     const float *proj_size = P.cam.proj_size, *ip = P.cam.inv_proj_mat, *iv = P.cam.inv_view_mat;
     const V3 cam{P.cam_origin[0], P.cam_origin[1], P.cam_origin[2]};
     const float u1 = rng_next(rng), u2 = rng_next(rng), u3 = rng_next(rng), u4 = rng_next(rng);
-    auto div = [](float n, float d) {
-        if (__ballot(!((n == 0.0f || in_band(n)) && in_band(d))) == 0ull) return div_refined(n, d, rcp_refined(d));
-        return n / d;
-    };
+    auto div = [](float n, float d) { return lens_div(n, d); };   // (vrt_path_common.h)
     const LensV3 w = lens_pixel_dir(px, py, u1, u2, L.pixel_spread, proj_size, ip, iv, div);
     dir = normalize_wave(V3{w.x, w.y, w.z});
     origin = cam;
     if (L.aperture != 0.0f) {   // (the launch's: a scalar branch)
-        auto sqrt_of = [](float x) {
-            constexpr float kSqrtBandLo = 1.0e-28f;   // (sqrt_banded's range is [2^-96, inf))
-            if (__ballot(!(x >= kSqrtBandLo)) == 0ull) return sqrt_banded(x);
-            return sqrtf(x);
-        };
+        auto sqrt_of = [](float x) { return lens_sqrt_of(x); };
         LensV3 o, v;
         lens_thin(LensV3{cam.x, cam.y, cam.z}, LensV3{dir.x, dir.y, dir.z}, u3, u4, L.aperture, L.focus_distance, iv, sqrt_of, o, v);
         origin = V3{o.x, o.y, o.z};

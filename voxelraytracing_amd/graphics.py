@@ -79,6 +79,36 @@ def selftest_tile_order(cost, tiles_x: int, tiles_y: int, radius: int, device: i
     return order
 
 
+# vrt_selftest_math_values' ops (include/vrt.h VRT_MATH_*): name -> (op, input words, output words per operand set)
+MATH_OPS = {name: (op, n_in, n_out) for op, (name, n_in, n_out) in enumerate([
+    ("div", 2, 1), ("sqrt", 1, 1), ("unit_steps", 3, 4), ("normalize", 3, 4), ("lens_div", 2, 2), ("lens_sqrt", 1, 2),
+    ("rng_next", 1, 2), ("rng_next_u2", 1, 2), ("log_banded", 1, 1), ("log_general", 1, 1), ("cos2pi", 1, 1), ("rng_dir", 1, 5),
+    ("trunc2i", 1, 1), ("flr2i", 1, 1), ("abs_mul", 2, 1), ("min3_f32", 3, 1), ("min3_bits", 3, 1), ("bfi", 3, 1),
+    ("low_bits", 2, 4), ("or_and", 3, 1), ("mad_i24", 3, 1)])}
+
+
+def selftest_math_values(op: str, *words, device: int = 0) -> np.ndarray:
+    """out[output words, n] (uint32 bit patterns) of the kernels' exact-arithmetic function `op` (a key of MATH_OPS) over n operand
+    sets, one array of n 32-bit words (uint32, int32 or float32: taken by their bits) per input word — see vrt_selftest_math_values
+    in include/vrt.h.  Set i runs on lane i % 64 of wave i / 64: the caller composes whole waves.  A refused call raises."""
+    code, n_in, n_out = MATH_OPS[op]
+    if len(words) != n_in:
+        raise ValueError(f"{op} takes {n_in} input words, not {len(words)}")
+    planes = []
+    for w in words:
+        w = np.ascontiguousarray(w).reshape(-1)
+        if w.dtype.itemsize != 4:
+            raise ValueError(f"{op}: 32-bit words, not {w.dtype}")
+        planes.append(w.view(np.uint32))
+    src = np.ascontiguousarray(np.stack(planes))
+    n = src.shape[1]
+    out = np.zeros((n_out, n), dtype=np.uint32)
+    rc = _ffi.vrt().vrt_selftest_math_values(device, code, n, src.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise VrtError(rc, "vrt_selftest_math_values refused the call")
+    return out
+
+
 class Gpu:
     """Owns one backend context; stands where the reference passes `&Gpu` (mod.rs:227-304).
 
