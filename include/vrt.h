@@ -827,6 +827,14 @@ int vrt_get_sun_marks(vrt_ctx *ctx, uint32_t *passes, uint32_t *min_leaf, uint32
  * bytes either way, *layers of the frames in between is K or 0.  Every pointer may be NULL. */
 int vrt_read_lit_voxels(vrt_ctx *ctx, uint32_t *passes, uint32_t *layers, uint32_t *lit_trips, uint8_t *lit);
 
+/* The dark marks (docs/NUMERICS.md "Dark stops"): behind every lit pass the all-air cells from which every ray towards the sun meets
+ * a closed layer of solid voxels are marked too, and a shadow ray of such a frame that stands in one stops there as occluded
+ * (VRT_DARK_MARKS=0: no such marks; VRT_DARK_DEPTH: the layers a cell's corridor is walked over).  The marks depend on which
+ * materials are liquids: a change of the liquid set makes them again, like a moved sun.  *passes: dark passes launched so far; *count:
+ * the dark cells of the table set the last frame used; *used: 1 when that frame's shadow rays stopped at them; dark[(8S)^3], indexed
+ * like vrt_get_sun_marks' lit: 1 for a dark cell (count and dark synchronise).  Every pointer may be NULL. */
+int vrt_get_dark_marks(vrt_ctx *ctx, uint32_t *passes, uint32_t *count, uint32_t *used, uint8_t *dark);
+
 /* The trips the last frame that noted them took per tile (longest tiles first, above: a context that renders one frame at a time
  * notes them on the second plain frame of a view at rest): cost[tiles], the wave's trips through its primary and its shadow march
  * loop; cost[t] is tile t of this context's tiles, counted row by row over the screen's 8 x 8 tiles (a sharded context: its own tiles in that

@@ -43,7 +43,7 @@ def leaf_sizes(dense):
 
 def march(dense, size, liquid, origin, sun, stops, max_steps=500):
     """Lookups per ray until it ends (hit, left the world, ran out), and per stop mask the lookup at which the ray first stands on
-    a marked voxel (0: never)."""
+    a marked voxel (0: never); and whether the ray is occluded (it ended on a solid voxel, or ran out: march_literal's `hit`)."""
     n = dense.shape[0]
     N = len(origin)
     d = (sun[None, :] - origin).astype(F)
@@ -57,6 +57,7 @@ def march(dense, size, liquid, origin, sun, stops, max_steps=500):
     up = d >= 0
     total = np.zeros(N, np.int32)
     first = [np.zeros(N, np.int32) for _ in stops]
+    hit = np.zeros(N, bool)
     act = np.nonzero(((pos > 0) & (pos < n)).all(axis=1))[0]
     it = 0
     while len(act) and it < max_steps:
@@ -70,6 +71,7 @@ def march(dense, size, liquid, origin, sun, stops, max_steps=500):
             here = m[v[:, 2], v[:, 1], v[:, 0]] & (f[act] == 0)
             f[act[here]] = it
         go = (vox == 0) | liq
+        hit[act[~go]] = True
         act, p, v = act[go], p[go], v[go]
         s = size[v[:, 2], v[:, 1], v[:, 0]].astype(np.int64)
         lo = v & ~(s[:, None] - 1)
@@ -85,7 +87,8 @@ def march(dense, size, liquid, origin, sun, stops, max_steps=500):
         pos[act] = p
         inside = ((p >= 0) & (np.floor(p) < n)).all(axis=1)
         act = act[inside]
-    return total, first
+    hit[act] = True   # (still marching after max_steps lookups)
+    return total, first, hit
 
 
 def main():
@@ -119,7 +122,7 @@ def main():
                     origins.append([F(out[a]) + F(out[3 + a]) * F(0.002) for a in range(3)])
                     lanes.append(ti)
     origins, lanes = np.array(origins, F), np.array(lanes)
-    total, first = march(dense, leaf_sizes(dense), liquid, origins, sun, stops)
+    total, first, _ = march(dense, leaf_sizes(dense), liquid, origins, sun, stops)
 
     def wave_trips(f, limit):
         stop = np.where((f > 0) & (f <= limit), f, total)

@@ -295,7 +295,10 @@ struct vrt_ctx {
                 uint64_t gen = 0;
                 float sun[3] = {0.f, 0.f, 0.f};
                 uint32_t min_lo = 0;
-                bool same(const Key &o) const { return gen == o.gen && memcmp(sun, o.sun, sizeof sun) == 0 && min_lo == o.min_lo; }
+                uint32_t liquid[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the liquid ids the dark marks' blockers were judged by (all 0 while the dark marks are off)
+                bool same(const Key &o) const {
+                    return gen == o.gen && memcmp(sun, o.sun, sizeof sun) == 0 && min_lo == o.min_lo && memcmp(liquid, o.liquid, sizeof liquid) == 0;
+                }
             } made, want;                       // what the marks in the grid were made for; what the frames ask for:
             uint32_t want_frames = 0;           // the pass runs once kLitSettleFrames frames in a row have asked for the same marks
             bool valid = false;                 // the grid holds marks, made for `made`
@@ -312,6 +315,11 @@ struct vrt_ctx {
             bool clash_pending = false;
             uint64_t clash_gen = ~0ull;
             uint32_t voxel_layers = 0;          // K the pool was made with
+            // the dark marks (vrt_lit.hip: accel_dark_kernel): bit 21 of the grid's air leaves, made behind the lit passes and held
+            // exactly as long as the cell marks are; a copy of the set carries them in its grid.  d_floors: a byte per grid entry,
+            // which of the cell's four voxel layers across the sun's axis are closed (the pass's scratch; no frame reads it)
+            Buf<uint8_t> d_floors;
+            bool dark_valid = false;
             Event ev;                           // behind the set's last lit pass: a frame on another stream that reads the marks waits for it
             bool pending = false;               // ... recorded and not yet known to be over
             hipStream_t stream = nullptr;       // the stream the pass ran on (frames on it are ordered behind it as they are)
@@ -328,6 +336,7 @@ struct vrt_ctx {
                 valid = A.holds(a_gen);
                 made = A.made; made.gen = gen;
                 pending = voxels_valid = false;
+                dark_valid = valid && A.dark_valid;
             }
         } lit;
         Event ev_updated;                       // behind this set's last chunk update (a reader of the node pool and chunk_roots)
@@ -368,6 +377,10 @@ struct vrt_ctx {
     uint32_t lit_voxel_passes = 0; // voxel-mark passes launched (vrt_read_lit_voxels)
     uint32_t lit_last_voxel_layers = 0, lit_last_voxel_trips = 0;   // of the last one-launch shadow frame: 0 = it read the plain bricks
     uint32_t lit_last_min_leaf = 0, lit_last_trips = 0;   // of the last one-launch shadow frame: 0 = its marks were off
+    bool dark_marks = true;        // VRT_DARK_MARKS=0: no dark pass, shadow rays never stop at dark cells (the A/B of profiles/dark_marks_ab.txt)
+    int dark_depth = -1;           // VRT_DARK_DEPTH: layers the dark pass walks a corridor over (0: no dark marks; -1: by grid size, vrt_lit.hip)
+    uint32_t dark_passes = 0;      // dark passes launched
+    bool dark_last_used = false;   // the last one-launch shadow frame's shadow rays stopped at dark cells (vrt_get_dark_marks)
     // longest tiles first (vrt_kernels.hip: tile_order_*), for a context that renders one frame at a time
     // (vrt_set_frames_in_flight(1)) and whose view is at rest: the second plain frame of an unchanged view (camera, settings,
     // world, materials) notes its tiles' march-loop trips, right behind it on the stream four small launches turn them into the

@@ -36,6 +36,12 @@ __host__ __device__ inline bool is_split_entry(uint32_t e) { return (int32_t)e <
 // `e < kAirLeaf` (FrameParams.shadow_below), which a lit air leaf answers like a split cell: the lane leaves the fast path, and stops.
 constexpr uint32_t kAirUnlit = 1u << 22;
 constexpr uint32_t kLitBelow = kAirLeaf | kAirUnlit;
+// Bit 21 is the dark mark (vrt_lit.hip: the dark pass): a DARK air leaf is kAirLeaf | kAirDark | lo with bit 22 clear — every shadow ray
+// with a position in the cell hits.  It lies below kLitBelow, so a shadow lane meets it where it meets a lit leaf, parks with the
+// entry kept, and the code behind the loop reads the bit: hit, not miss (vrt_march.h (t)).  To everyone else it is an air leaf: the
+// direction masks of the exit-plane insert carry a zero there too (a voxel coordinate stays below 2^21), `e >= kAirLeaf` and
+// `e & 31` answer as ever.  An air leaf is LIT when bits 22 and 21 are both clear.
+constexpr uint32_t kAirDark = 1u << 21;
 // The voxel marks (vrt_lit.hip: accel_lit_voxels_kernel): a table set's SHADOW POOL is a copy of its brick pool in which a lit air
 // voxel of a split cell holds this voxel id — the highest a brick's 16-bit entry (voxel << 1 | lo) can carry.  Not air and, by the
 // host's check of the liquid table, not a liquid: the march loop's "solid: stop" parks a shadow lane on it as on any solid voxel, and

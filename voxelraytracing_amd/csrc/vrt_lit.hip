@@ -1,11 +1,12 @@
 // vrt_lit.hip — the sun marks of a table set (docs/NUMERICS.md "Lit stops"): the lit bits on the cell grid's air leaves
 // (vrt_device.h kAirUnlit) and the shadow pool of lit voxels (kLitVoxel), which let a shadow ray of the one-launch frame stop where
 // nothing can lie between it and the sun.  Everything about them is here:
-//   the kernels      accel_lit_kernel (the cell marks, a launch per slab), accel_lit_voxels_kernel and its undo (the voxel marks)
+//   the kernels      accel_lit_kernel (the cell marks, a launch per slab), accel_lit_voxels_kernel and its undo (the voxel marks),
+//                    accel_floor_masks_kernel and accel_dark_kernel (the dark marks: kAirDark, "Dark stops")
 //   the plan         whether this world and sun get marks and which (lit_plan), the slab depth and the voxel layers by grid size
 //   the frame hook   sun_marks_for_frame: vrt_render calls it for a one-launch shadow frame whose table set is up to date on its
 //                    stream; it makes the marks there once they are due (ensure_sun_marks) and hands the frame its stops
-//   the read-backs   vrt_get_sun_marks, vrt_read_lit_voxels
+//   the read-backs   vrt_get_sun_marks, vrt_read_lit_voxels, vrt_get_dark_marks
 // The state is vrt_ctx::Tables::SunMarks (vrt_ctx.h).  vrt_accel.hip builds the grid with every mark set, vrt_uploads.hip asks the
 // record what a copy of a set takes along; nothing else touches the marks.
 #include "vrt_ctx.h"
@@ -115,7 +116,8 @@ __global__ void __launch_bounds__(256) accel_lit_kernel(uint32_t *grid, LitPass 
                     lit = lit && nx >= kAirLeaf && !(nx & kAirUnlit);
                 }
     }
-    grid[at] = lit ? (e & ~kAirUnlit) : (e | kAirUnlit);
+    // (a new pass re-arms the dark mark with the lit one: the dark pass behind this one sets it again where it holds)
+    grid[at] = lit ? (e & ~(kAirUnlit | kAirDark)) : ((e & ~kAirDark) | kAirUnlit);
 }
 
 // The voxel marks: the lit rule carried down to the air voxels of SPLIT cells (docs/NUMERICS.md "Lit stops", the voxels of split
@@ -189,7 +191,7 @@ __device__ inline bool lit_voxel_walk(const uint32_t *grid, const uint16_t *bric
                 uint32_t voxel = 1u;   // (a brick beyond the pool: not air)
                 if (split && at < lp.entries) voxel = (uint32_t)bricks[at] >> 1;
                 all_air = all_air && (e >= kAirLeaf || (split && voxel == 0u));   // (an air-leaf cell is air throughout)
-                all_lit = all_lit && e >= kAirLeaf && !(e & kAirUnlit);
+                all_lit = all_lit && e >= kAirLeaf && !(e & (kAirUnlit | kAirDark));   // (a dark leaf has bit 22 clear too.  None is here today: accel_lit_kernel has just cleared bit 21 and the dark pass runs behind this one; the test holds should the passes be reordered)
             }
         open = all_air && !all_lit;
         lit = all_air && all_lit;
@@ -264,6 +266,112 @@ void launch_accel_lit(uint32_t *grid, uint32_t G, uint32_t axis, bool up, uint32
     }
 }
 
+// The dark pass: the dark marks of the cell grid's air leaves (vrt_device.h kAirDark; docs/NUMERICS.md "Dark stops";
+// tests/dark_cell_ref.py states the rule in numpy).  An all-air cell C of layer c_a is DARK when for some k >= 1 (c_a + k inside the
+// world, k <= depth) REACH_j(C) lies wholly inside the world for every j = 0 .. k — no ray of C can have left it sideways — and the
+// cells of REACH_k(C) share a closed voxel layer: one of the four voxel layers across `a` in which every one of them holds 16 solid
+// voxels that are no liquid.  A ray of C rises monotonely through adjacent leaves, so unless it ends before (a hit, or its lookups
+// spent, which the reference reports as a hit) it looks up a voxel of that layer in one of those cells.  REACH is the lit rule's,
+// but computed in binary64 in the order tests/dark_cell_ref.py computes it: the marks are the reference's cell for cell.
+// Two launches behind the lit passes: the floor masks (a byte per cell, bit j: voxel layer j across `a` is closed), then a thread per
+// cell, which walks its corridor until the rule holds or the corridor touches the world's side.  Only air leaves that are not lit are
+// walked, and each gets its two bits written: dark, or unlit.
+struct DarkPass {
+    uint32_t G, axis, up, depth;
+    float sun[3];
+    uint32_t liquid[8];   // bit v: material v is a liquid (ids above 255 are material 255)
+};
+
+__global__ void __launch_bounds__(256) accel_floor_masks_kernel(const uint32_t *grid, const uint16_t *bricks, uint32_t entries, uint8_t *floors, DarkPass dp) {
+    const uint32_t G = dp.G, G1 = G + 1u;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= G * G * G) return;
+    const size_t at = ((size_t)(t / (G * G)) * G1 + (t / G) % G) * G1 + t % G;
+    const uint32_t e = grid[at];
+    auto blocks = [&](uint32_t voxel) {
+        const uint32_t id = voxel < 255u ? voxel : 255u;
+        return voxel != 0u && !((dp.liquid[id >> 5] >> (id & 31u)) & 1u);
+    };
+    uint32_t m = 0u;
+    if (is_split_entry(e)) {
+        const uint32_t base = e & 0x7FFFFFC0u, sh = 2u * dp.axis;
+        if (base + 64u <= entries) {   // (a brick beyond the pool is never read by the march either)
+            m = 15u;
+            for (uint32_t i = 0; i < 64u; i++)
+                if (!blocks((uint32_t)bricks[base + i] >> 1)) m &= ~(1u << ((i >> sh) & 3u));
+        }
+    } else if (e < kAirLeaf && e != 0u) {
+        m = blocks(e >> 16) ? 15u : 0u;
+    }
+    floors[at] = (uint8_t)m;
+}
+
+// The cells of axis `b` of REACH, as [lo, hi]; false: some lie beyond the world (tests/dark_cell_ref.py: _reach)
+__device__ inline bool dark_reach(double c4, double s_min, double s_max, double r_lo, double r_hi, double allow, int G, int *lo, int *hi) {
+    const double b_lo = c4 + (s_min < 0.0 ? r_hi : r_lo) * s_min - allow;
+    const double b_hi = c4 + 4.0 + (s_max > 0.0 ? r_hi : r_lo) * s_max + allow;
+    int l = (int)floor(b_lo / 4.0), h = (int)floor(b_hi / 4.0);
+    const int own = (int)(c4 / 4.0);
+    if (!(s_min < 0.0)) l = max(l, own);   // (monotone coordinates, as lit_reach)
+    if (!(s_max > 0.0)) h = min(h, own);
+    *lo = l;
+    *hi = h;
+    return l >= 0 && h < G;
+}
+
+__device__ inline void dark_slopes(double n_lo, double n_hi, double d_lo, double d_hi, double *s_min, double *s_max) {
+    *s_min = n_lo / (n_lo < 0.0 ? d_lo : d_hi);
+    *s_max = n_hi / (n_hi > 0.0 ? d_lo : d_hi);
+}
+
+__global__ void __launch_bounds__(256) accel_dark_kernel(uint32_t *grid, const uint8_t *floors, DarkPass dp) {
+    const uint32_t G = dp.G, G1 = G + 1u;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= G * G * G) return;
+    const uint32_t a = dp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;   // as accel_lit_kernel
+    const size_t row = G1, slab = (size_t)G1 * G1;
+    const size_t sa = a == 0u ? 1u : a == 1u ? row : slab, su = u == 0u ? 1u : row, sv = v == 1u ? row : slab;
+    const uint32_t cu = t % G, cv = (t / G) % G, i = t / (G * G);   // i: the cell's layer in the pass's frame, which grows towards the sun
+    const uint32_t ca = dp.up ? i : G - 1u - i;
+    const size_t at = ca * sa + cu * su + cv * sv;
+    const uint32_t e = grid[at];
+    if (e < kAirLeaf || !(e & (kAirUnlit | kAirDark))) return;   // not an air leaf, or a lit one
+    const double W = (double)(G * 4u);
+    const double sun_a = dp.up ? (double)dp.sun[a] : W - (double)dp.sun[a], sun_u = (double)dp.sun[u], sun_v = (double)dp.sun[v];
+    const double a4 = 4.0 * (double)i, u4 = 4.0 * (double)cu, v4 = 4.0 * (double)cv;
+    const double d_lo = sun_a - (a4 + 5.0), d_hi = sun_a - (a4 - 1.0);
+    double us_min, us_max, vs_min, vs_max;
+    dark_slopes(sun_u - (u4 + 5.0), sun_u - (u4 - 1.0), d_lo, d_hi, &us_min, &us_max);
+    dark_slopes(sun_v - (v4 + 5.0), sun_v - (v4 - 1.0), d_lo, d_hi, &vs_min, &vs_max);
+    const size_t step = dp.up ? sa : (size_t)0 - sa;   // one layer towards the sun
+    const uint32_t k_max = min(dp.depth, G - 1u - i);
+    bool dark = false;
+    size_t layer = ca * sa;
+    for (uint32_t k = 0; k <= k_max; k++, layer += step) {
+        const double r_lo = k >= 2u ? 4.0 * (double)k - 5.0 : 0.0, r_hi = 4.0 * (double)k + 5.0;
+        const double allow = fmin(0.015 * (double)(k + 1u), 1.0) + 0.01;
+        int ul, uh, vl, vh;
+        if (!dark_reach(u4, us_min, us_max, r_lo, r_hi, allow, (int)G, &ul, &uh) || !dark_reach(v4, vs_min, vs_max, r_lo, r_hi, allow, (int)G, &vl, &vh))
+            break;   // a ray of C may leave the world sideways from here on
+        if (k == 0u) continue;
+        uint32_t m = 15u;
+        for (int nv = vl; nv <= vh; nv++)
+            for (int nu = ul; nu <= uh; nu++) m &= floors[layer + (size_t)nu * su + (size_t)nv * sv];
+        if (m) { dark = true; break; }
+    }
+    grid[at] = dark ? ((e & ~kAirUnlit) | kAirDark) : ((e & ~kAirDark) | kAirUnlit);
+}
+
+// The dark pass of a table set, on `st` behind the lit passes: `floors` (a byte per entry of the bordered grid) is its scratch.
+void launch_accel_dark(uint32_t *grid, const uint16_t *bricks, uint32_t entries, uint8_t *floors, uint32_t G, uint32_t axis, bool up, const float sun[3],
+                       uint32_t depth, const uint32_t liquid[8], hipStream_t st) {
+    DarkPass dp{G, axis, up ? 1u : 0u, depth, {sun[0], sun[1], sun[2]}, {}};
+    for (int i = 0; i < 8; i++) dp.liquid[i] = liquid[i];
+    const uint32_t blocks = (G * G * G + 255u) / 256u;
+    hipLaunchKernelGGL(accel_floor_masks_kernel, dim3(blocks), dim3(256), 0, st, grid, bricks, entries, floors, dp);
+    hipLaunchKernelGGL(accel_dark_kernel, dim3(blocks), dim3(256), 0, st, grid, floors, dp);
+}
+
 }  // namespace
 
 }  // namespace vrt
@@ -331,6 +439,17 @@ uint32_t lit_voxel_layers(const vrt_ctx *c, uint32_t G) {
 }
 uint32_t lit_voxel_budget(uint32_t layers) { return 2u * (3u * layers + 6u); }
 
+// The dark marks (accel_dark_kernel): how many layers a cell's corridor is walked over before the cell is left unmarked, per grid
+// size, by the slab depth's rule — the largest depth whose pass pays for itself within 100 frames, each step up paying for its own
+// extra (profiles/dark_marks_ab.txt); 0: no dark marks at that size.  Up to 64 cells a side 32 layers: 60 us on the pass for 5.7 us off
+// every frame of the standing view (16: 40 us for 4.3; 64: 76 us for the same 5.8, the same 179 cells).  128 cells a side: 130 us for
+// 0.3 us, inside the spread: none; larger grids were not measured: none.  VRT_DARK_DEPTH overrides, VRT_DARK_MARKS=0 switches them off.
+uint32_t dark_depth(const vrt_ctx *c, uint32_t G) {
+    if (!c->dark_marks) return 0u;
+    const uint32_t depth = c->dark_depth >= 0 ? (uint32_t)c->dark_depth : G <= 64u ? 32u : 0u;
+    return depth < G ? depth : G;
+}
+
 // Marks are worth a pass (0.4 ms for 64^3 cells, 0.9 ms for the client's 240^3: profiles/sun_marks_edit_cost.txt) once what
 // they are made from stands still: while edits arrive or the sun moves from frame to frame, the frames run without marks,
 // as they always did, and the pass follows kLitSettleFrames frames after the last change.  True: this frame is that one.
@@ -386,6 +505,15 @@ int launch_passes(vrt_ctx *c, Tables &T, const LitPlan &lp, const SunMarks::Key 
         L.voxel_layers = layers;
         c->lit_voxel_passes += 1u;
     }
+    // the dark marks, behind the lit ones: on every air leaf the passes above left unlit, whatever the plan's smallest leaf is
+    L.dark_valid = false;
+    if (const uint32_t depth = dark_depth(c, G)) {
+        HIP_TRY(c, L.d_floors.exactly(T.d_grid.cap()));
+        vrt::launch_accel_dark(T.d_grid, T.d_bricks, (uint32_t)T.d_bricks.cap(), L.d_floors, G, lp.axis, lp.up, now.sun, depth, now.liquid, st);
+        HIP_TRY(c, hipGetLastError());
+        L.dark_valid = true;
+        c->dark_passes += 1u;
+    }
     HIP_TRY(c, L.ev.ensure());
     HIP_TRY(c, hipEventRecord(L.ev, st));
     L.pending = true;
@@ -407,6 +535,7 @@ int hand_out(vrt_ctx *c, Tables &T, const LitPlan &lp, hipStream_t st, vrt::Fram
     P.lit_trips = lp.trips;
     c->lit_last_min_leaf = lp.min_lo + 1u;
     c->lit_last_trips = lp.trips;
+    c->dark_last_used = L.dark_valid;   // (the frame's threshold is kLitBelow: a dark leaf stops its shadow rays as a lit one does)
     if (L.clash_pending && hipEventQuery(L.ev) == hipSuccess) {   // the pass is over: did it meet the reserved id in a brick of the world?
         L.clash_pending = false;
         if (*reinterpret_cast<volatile uint32_t *>(L.h_clash.get())) { L.voxels_valid = false; L.clash_gen = T.gen; }   // the plain bricks from here on
@@ -426,7 +555,9 @@ int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, vrt::F
     Tables &T = c->tabs[k];
     LitPlan lp{};
     if (!c->accel_ok || !T.live || !T.d_grid || !lit_plan(c->world.size, P.sun_local, &lp)) return VRT_OK;
-    const SunMarks::Key now{T.gen, {P.sun_local[0], P.sun_local[1], P.sun_local[2]}, lp.min_lo};
+    SunMarks::Key now{T.gen, {P.sun_local[0], P.sun_local[1], P.sun_local[2]}, lp.min_lo, {}};
+    // (the dark marks' blockers are solid voxels that are no liquid: another liquid set, other marks)
+    if (dark_depth(c, c->accel_S * 8u)) memcpy(now.liquid, c->liquid_mask, sizeof now.liquid);
     if (T.lit.valid && T.lit.made.same(now)) {
         T.lit.want_frames = 0u;   // (a sun that swings between two places must not collect its four frames one at a time)
     } else {
@@ -455,6 +586,7 @@ int marks_of_last_frame(vrt_ctx *c, const char *who, std::vector<uint32_t> &cell
 
 int sun_marks_for_frame(vrt_ctx *c, uint32_t tab, hipStream_t st, bool shares, vrt::FrameParams &P) {
     c->lit_last_min_leaf = c->lit_last_trips = c->lit_last_voxel_layers = c->lit_last_voxel_trips = 0u;
+    c->dark_last_used = false;
     return c->sun_marks ? ensure_sun_marks(c, tab, st, shares, P) : VRT_OK;
 }
 
@@ -470,7 +602,27 @@ int vrt_get_sun_marks(vrt_ctx *c, uint32_t *passes, uint32_t *min_leaf, uint32_t
     std::vector<uint32_t> cells;
     VRT_TRY(marks_of_last_frame(c, "vrt_get_sun_marks", cells));
     const bool held = c->tabs[c->last.tab].lit.holds(c->tabs[c->last.tab].gen);
-    for (size_t i = 0; i < cells.size(); i++) lit[i] = (held && cells[i] >= vrt::kAirLeaf && !(cells[i] & vrt::kAirUnlit)) ? 1u : 0u;
+    for (size_t i = 0; i < cells.size(); i++) lit[i] = (held && cells[i] >= vrt::kAirLeaf && !(cells[i] & (vrt::kAirUnlit | vrt::kAirDark))) ? 1u : 0u;
+    return VRT_OK;
+}
+
+int vrt_get_dark_marks(vrt_ctx *c, uint32_t *passes, uint32_t *count, uint32_t *used, uint8_t *dark) {
+    GRP_ROOT(c, vrt_get_dark_marks(d, passes, count, used, dark));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    if (passes) *passes = c->dark_passes;
+    if (used) *used = c->dark_last_used ? 1u : 0u;
+    if (!count && !dark) return VRT_OK;
+    std::vector<uint32_t> cells;
+    VRT_TRY(marks_of_last_frame(c, "vrt_get_dark_marks", cells));
+    const Tables &T = c->tabs[c->last.tab];
+    const bool held = T.lit.holds(T.gen) && T.lit.dark_valid;
+    uint32_t n = 0;
+    for (size_t i = 0; i < cells.size(); i++) {
+        const bool d = held && cells[i] >= vrt::kAirLeaf && (cells[i] & vrt::kAirDark);
+        n += d ? 1u : 0u;
+        if (dark) dark[i] = d ? 1u : 0u;
+    }
+    if (count) *count = n;
     return VRT_OK;
 }
 

@@ -706,9 +706,9 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // is exact (integers below 2^24).  Two full-rate instructions for v_cvt_f32_i32's half-rate one and the integer increment.
     // (Until round 6 the "+ 1" and the exponent were an integer subtraction of their own: three instructions per step.)
     constexpr uint32_t kTwo23 = 0x4B000000u;
-    // (bit 22 of the masks is zero: an air leaf's entry may carry the sun mark there — vrt_device.h kAirUnlit — and the insert must
-    // not take it for a bit of the plane; only the selector's low five bits and its top nine ever select anything)
-    uint32_t mxm = kTwo23 | (mx ? 0x003FFFFFu : 0u), mym = kTwo23 | (my ? 0x003FFFFFu : 0u), mzm = kTwo23 | (mz ? 0x003FFFFFu : 0u);
+    // (bits 22 and 21 of the masks are zero: an air leaf's entry may carry the sun marks there — vrt_device.h kAirUnlit, kAirDark — and
+    // the insert must not take them for bits of the plane; only the selector's low five bits and its top nine ever select anything)
+    uint32_t mxm = kTwo23 | (mx ? 0x001FFFFFu : 0u), mym = kTwo23 | (my ? 0x001FFFFFu : 0u), mzm = kTwo23 | (mz ? 0x001FFFFFu : 0u);
     float cx = mx ? -8388607.0f : -8388608.0f, cy = my ? -8388607.0f : -8388608.0f, cz = mz ? -8388607.0f : -8388608.0f;
     asm("" : "+v"(mxm), "+v"(mym), "+v"(mzm));   // (held in registers)
 
@@ -753,7 +753,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // budget: `limit` is the trip count at which the next of the two ends
     bool lit_voxels = kLitStops && LITVOX && P.shadow_bricks != nullptr && P.lit_voxel_trips < cells_limit;
     uint32_t limit = lit_voxels ? P.lit_voxel_trips : cells_limit;
-    bool lit_stop = false;
+    bool lit_stop = false, dark_stop = false;   // (dark_stop: the air leaf a lane stopped at carries kAirDark — every ray from it hits)
     uint32_t slow_below = careful ? kSlow : plain_below;
     float total_len = 0.0f;
     uint32_t iter = 0u;      // wave-uniform trip count (loop control)
@@ -841,6 +841,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             if (parked) {                   // stopped in the loop: border, the solid voxel now in `voxel`, or (t) a lit air leaf, still in `e`
                 // (u) ... or a lit voxel of a split cell's brick (a leaf of that id in the cell grid is a solid leaf: the pass does not see those)
                 if (kLitStops) lit_stop = e >= kAirLeaf || (lit_pool && voxel == kLitVoxel && is_split_entry(e));
+                if (kLitStops) dark_stop = e >= kAirLeaf && (e & kAirDark) != 0u;
                 break;
             }
             if (iter >= kMaxSteps) break;   // (wave-uniform) at most kMaxSteps lookups (:220)
@@ -873,7 +874,7 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
             }
             stop = e == 0u;  // border, or past either end of the grid: the position is outside the world
             // (t) a lit air leaf under a plain shadow lane (a lane in water, a careful wave: kSlow — they march on)
-            if (kLitStops && e >= kAirLeaf && slow_below != kSlow) { lit_stop = true; stop = true; }
+            if (kLitStops && e >= kAirLeaf && slow_below != kSlow) { lit_stop = true; stop = true; dark_stop = (e & kAirDark) != 0u; }
             if (!stop) {
                 voxel = 0u;
                 if (is_split_entry(e)) {
@@ -910,7 +911,9 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     // per-lane lookup counts are kept by the STATS kernels only (counters, step-count debug view)
     R.iters = STATS ? looked_up : 0u;
     R.trips = iter;
-    if (kLitStops && lit_stop) return R;   // (t) from here the reference's ray leaves the world through air: a miss, whatever the position says
+    // (t) from here the reference's ray leaves the world through air: a miss, whatever the position says — or, from a DARK leaf, meets
+    // a solid voxel or runs out of lookups on the way to one: a hit, of which the frame reads nothing but that it is one
+    if (kLitStops && lit_stop) { R.hit = dark_stop; return R; }
     if (dew != -1.0f) R.water_dist += total_len - dew;
     // (i): "left the world" (:285-290) from the position itself; a lane that left through a solid leaf or by exhaustion
     // holds a position that passes this test

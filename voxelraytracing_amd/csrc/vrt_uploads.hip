@@ -740,9 +740,10 @@ int vrt_read_accel(vrt_ctx *c, uint32_t *grid, uint16_t *bricks) {
     if (grid) {
         const size_t G = (size_t)c->accel_S * 8u;
         VRT_TRY(read_grid_cells(c, c->tabs[0].d_grid, grid));
-        // the caller gets canonical entries: an air leaf without its sun mark (vrt_device.h kAirUnlit; vrt_get_sun_marks reads the marks)
+        // the caller gets canonical entries: an air leaf without its sun marks (vrt_device.h kAirUnlit, kAirDark; vrt_get_sun_marks and
+        // vrt_get_dark_marks read the marks)
         for (size_t i = 0; i < G * G * G; i++)
-            if (grid[i] >= vrt::kAirLeaf) grid[i] &= ~vrt::kAirUnlit;
+            if (grid[i] >= vrt::kAirLeaf) grid[i] &= ~(vrt::kAirUnlit | vrt::kAirDark);
     }
     uint32_t used = 0;
     VRT_TRY(bricks_in_use(c, c->tabs[0], &used));

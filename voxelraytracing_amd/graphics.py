@@ -409,6 +409,19 @@ class Gpu:
             out["lit"] = lit
         return out
 
+    def dark_marks(self, cells: bool = False):
+        """{passes, count, used[, dark[G,G,G] indexed [z,y,x]]} — see vrt_get_dark_marks in include/vrt.h."""
+        p, n, u = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        dark = None
+        if cells:
+            g = self.accel_info().world_size_chunks * 8
+            dark = np.empty((g, g, g), dtype=np.uint8)
+        self._ck(self._lib.vrt_get_dark_marks(self._h, C.byref(p), C.byref(n), C.byref(u), dark.ctypes.data_as(C.c_void_p) if cells else None))
+        out = dict(passes=p.value, count=n.value, used=bool(u.value))
+        if cells:
+            out["dark"] = dark
+        return out
+
     def sun_marks(self, cells: bool = False):
         """{passes, min_leaf, lit_trips[, lit[G,G,G] indexed [z,y,x]]} — see vrt_get_sun_marks in include/vrt.h."""
         p, m, t = C.c_uint32(), C.c_uint32(), C.c_uint32()
