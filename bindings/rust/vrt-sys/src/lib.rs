@@ -472,6 +472,7 @@ extern "C" {
     pub fn vrt_selftest_tile_order(device: i32, cost: *const u32, tiles_x: u32, tiles_y: u32, radius: i32, order: *mut u32) -> c_int;
     pub fn vrt_get_sun_marks(ctx: *mut vrt_ctx, passes: *mut u32, min_leaf: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
     pub fn vrt_read_lit_voxels(ctx: *mut vrt_ctx, passes: *mut u32, layers: *mut u32, lit_trips: *mut u32, lit: *mut u8) -> c_int;
+    pub fn vrt_read_dark_voxels(ctx: *mut vrt_ctx, passes: *mut u32, layers: *mut u32, dark: *mut u8) -> c_int;
     pub fn vrt_get_dark_marks(ctx: *mut vrt_ctx, passes: *mut u32, count: *mut u32, used: *mut u32, dark: *mut u8) -> c_int;
     pub fn vrt_read_steps(ctx: *mut vrt_ctx, steps: *mut u32) -> c_int;
     pub fn vrt_set_stream(ctx: *mut vrt_ctx, hip_stream: *mut c_void) -> c_int;

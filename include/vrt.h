@@ -827,6 +827,16 @@ int vrt_get_sun_marks(vrt_ctx *ctx, uint32_t *passes, uint32_t *min_leaf, uint32
  * bytes either way, *layers of the frames in between is K or 0.  Every pointer may be NULL. */
 int vrt_read_lit_voxels(vrt_ctx *ctx, uint32_t *passes, uint32_t *layers, uint32_t *lit_trips, uint8_t *lit);
 
+/* The dark voxel marks, for inspection (docs/NUMERICS.md "Dark stops", the voxels of split cells): where a pass makes the copy of the
+ * brick pool above, the air voxels of split cells from which every ray towards the sun meets solid voxels, or cells with the dark
+ * mark below, within a few voxel layers hold a solid voxel id (0x7FFE) in the copy, and a shadow ray that reads it there is
+ * occluded (VRT_DARK_VOXEL_LAYERS: the voxel layers a voxel's walk may take; 0: no such marks).  Like the dark marks they depend on
+ * which materials are liquids.  *passes: such passes launched
+ * so far; *layers: those layers of the copy the last frame's shadow rays read, 0 when it held no such marks or the frame read the
+ * plain bricks; dark[(32S)^3], indexed like vrt_read_lit_voxels' lit: 1 for a voxel that is air in the bricks and holds the mark in
+ * the copy (synchronises).  vrt_read_accel returns the bricks themselves as ever.  Every pointer may be NULL. */
+int vrt_read_dark_voxels(vrt_ctx *ctx, uint32_t *passes, uint32_t *layers, uint8_t *dark);
+
 /* The dark marks (docs/NUMERICS.md "Dark stops"): behind every lit pass the all-air cells from which every ray towards the sun meets
  * a closed layer of solid voxels are marked too, and a shadow ray of such a frame that stands in one stops there as occluded
  * (VRT_DARK_MARKS=0: no such marks; VRT_DARK_DEPTH: the layers a cell's corridor is walked over).  The marks depend on which

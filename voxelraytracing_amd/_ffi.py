@@ -283,6 +283,7 @@ VRT_SYMBOLS = {
     "vrt_read_march_cells": (C.c_int, [_P, _P, _P]),
     "vrt_get_sun_marks": (C.c_int, [_P, _P, _P, _P, _P]),
     "vrt_read_lit_voxels": (C.c_int, [_P, _P, _P, _P, _P]),
+    "vrt_read_dark_voxels": (C.c_int, [_P, _P, _P, _P]),
     "vrt_get_dark_marks": (C.c_int, [_P, _P, _P, _P, _P]),
     "vrt_read_tile_cost": (C.c_int, [_P, _P]),
     "vrt_read_tile_order": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),

@@ -320,6 +320,7 @@ struct vrt_ctx {
             // which of the cell's four voxel layers across the sun's axis are closed (the pass's scratch; no frame reads it)
             Buf<uint8_t> d_floors;
             bool dark_valid = false;
+            uint32_t dark_voxel_layers = 0;     // K_d the pool's dark voxel marks were made with (accel_dark_voxels_kernel); 0: it holds none
             Event ev;                           // behind the set's last lit pass: a frame on another stream that reads the marks waits for it
             bool pending = false;               // ... recorded and not yet known to be over
             hipStream_t stream = nullptr;       // the stream the pass ran on (frames on it are ordered behind it as they are)
@@ -380,6 +381,9 @@ struct vrt_ctx {
     bool dark_marks = true;        // VRT_DARK_MARKS=0: no dark pass, shadow rays never stop at dark cells (the A/B of profiles/dark_marks_ab.txt)
     int dark_depth = -1;           // VRT_DARK_DEPTH: layers the dark pass walks a corridor over (0: no dark marks; -1: by grid size, vrt_lit.hip)
     uint32_t dark_passes = 0;      // dark passes launched
+    int dark_voxel_layers = -1;    // VRT_DARK_VOXEL_LAYERS: voxel layers a dark voxel's walk may take (0: no dark voxel marks; -1: by grid size, vrt_lit.hip)
+    uint32_t dark_voxel_passes = 0;        // dark voxel passes launched (vrt_read_dark_voxels)
+    uint32_t dark_last_voxel_layers = 0;   // of the last one-launch shadow frame: 0 = its pool held no dark voxel marks, or it read the plain bricks
     bool dark_last_used = false;   // the last one-launch shadow frame's shadow rays stopped at dark cells (vrt_get_dark_marks)
     // longest tiles first (vrt_kernels.hip: tile_order_*), for a context that renders one frame at a time
     // (vrt_set_frames_in_flight(1)) and whose view is at rest: the second plain frame of an unchanged view (camera, settings,

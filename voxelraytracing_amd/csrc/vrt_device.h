@@ -47,6 +47,10 @@ constexpr uint32_t kAirDark = 1u << 21;
 // host's check of the liquid table, not a liquid: the march loop's "solid: stop" parks a shadow lane on it as on any solid voxel, and
 // the code behind the loop tells it by the id (vrt_march.h (u)).  A world one of whose bricks holds the id gets a shadow pool without marks.
 constexpr uint32_t kLitVoxel = 0x7FFFu;
+// ... and a DARK air voxel of a split cell — every shadow ray with a point of its path in it hits (vrt_lit.hip:
+// accel_dark_voxels_kernel) — holds the id below: a solid voxel that is no liquid, and nothing more.  The loop parks a shadow lane
+// on it, the code behind the loop finds no lit stop, and the ray is a hit.  A world that holds the id itself holds a solid voxel there.
+constexpr uint32_t kDarkVoxel = 0x7FFEu;
 // a march cell's first word (lo of an air leaf, voxel << 16 | lo, 0x80000000 | brick * 64) as the cell grid holds it
 __host__ __device__ inline uint32_t grid_entry(uint32_t x) { return x - 1u < 31u ? (kAirLeaf | kAirUnlit | x) : x; }
 

@@ -526,6 +526,7 @@ int vrt_create(const vrt_config *cfg, vrt_ctx **out) {
     if (const char *e = getenv("VRT_LIT_VOXELS")) c->lit_voxels = e[0] != '0';
     if (const char *e = getenv("VRT_LIT_VOXEL_LAYERS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c->lit_voxel_layers = (int)v; }
     if (const char *e = getenv("VRT_DARK_MARKS")) c->dark_marks = e[0] != '0';
+    if (const char *e = getenv("VRT_DARK_VOXEL_LAYERS")) { const long v = atol(e); if (v >= 0 && v <= 4096) c->dark_voxel_layers = (int)v; }
     if (const char *e = getenv("VRT_DARK_DEPTH")) { const long v = atol(e); if (v >= 0 && v <= 4096) c->dark_depth = (int)v; }
     if (const char *e = getenv("VRT_LIT_SLAB")) { const long v = atol(e); if (v >= 1 && v <= 4096) c->lit_slab = (uint32_t)v; }
     // (0: screen order while the view moves — profiles/r05_tile_order_moving.txt)

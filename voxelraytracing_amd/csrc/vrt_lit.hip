@@ -2,11 +2,12 @@
 // (vrt_device.h kAirUnlit) and the shadow pool of lit voxels (kLitVoxel), which let a shadow ray of the one-launch frame stop where
 // nothing can lie between it and the sun.  Everything about them is here:
 //   the kernels      accel_lit_kernel (the cell marks, a launch per slab), accel_lit_voxels_kernel and its undo (the voxel marks),
-//                    accel_floor_masks_kernel and accel_dark_kernel (the dark marks: kAirDark, "Dark stops")
+//                    accel_floor_masks_kernel and accel_dark_kernel (the dark marks: kAirDark, "Dark stops"), accel_dark_voxels_kernel
+//                    (the dark marks of the shadow pool: kDarkVoxel)
 //   the plan         whether this world and sun get marks and which (lit_plan), the slab depth and the voxel layers by grid size
 //   the frame hook   sun_marks_for_frame: vrt_render calls it for a one-launch shadow frame whose table set is up to date on its
 //                    stream; it makes the marks there once they are due (ensure_sun_marks) and hands the frame its stops
-//   the read-backs   vrt_get_sun_marks, vrt_read_lit_voxels, vrt_get_dark_marks
+//   the read-backs   vrt_get_sun_marks, vrt_read_lit_voxels, vrt_get_dark_marks, vrt_read_dark_voxels
 // The state is vrt_ctx::Tables::SunMarks (vrt_ctx.h).  vrt_accel.hip builds the grid with every mark set, vrt_uploads.hip asks the
 // record what a copy of a set takes along; nothing else touches the marks.
 #include "vrt_ctx.h"
@@ -372,6 +373,127 @@ void launch_accel_dark(uint32_t *grid, const uint16_t *bricks, uint32_t entries,
     hipLaunchKernelGGL(accel_dark_kernel, dim3(blocks), dim3(256), 0, st, grid, floors, dp);
 }
 
+// The dark voxel marks: the dark rule carried down to the air voxels of SPLIT cells (docs/NUMERICS.md "Dark stops", the voxels of
+// split cells; tests/dark_voxel_ref.py states it in numpy).  An occluded shadow ray starts a hair above a surface voxel, inside a
+// split cell, and walks bricks voxel by voxel until it hits or reaches a dark cell.  An air voxel of a split cell that holds no lit
+// mark is DARK when for some k, 1 <= k <= layers, REACH_j lies wholly inside the world for every j = 0 .. k, voxel layer i_a + k with
+// it, and every voxel of REACH_k is CLOSED: a solid voxel that is no liquid (a solid leaf cell is solid throughout), or a voxel of a
+// cell with the dark cell mark.  REACH is the lit voxel rule's — the voxel widened by a voxel, a rise of max(0, k - 2) .. k + 2, the
+// cell rule's allowance, one-sided intervals — but computed in binary64 in the order tests/dark_voxel_ref.py computes it: the marks
+// are the reference's voxel for voxel.  A ray with a point in the voxel rises monotonely, so it looks up a voxel of REACH_k unless it
+// ends before, and every way to end before is a hit (a solid voxel, or its lookups spent): no step budget.  The pass writes
+// kDarkVoxel (the entry's lo kept) into the shadow pool, which the march takes for the solid voxel it is.
+// Runs behind accel_dark_kernel (the cell marks it reads are final; where that pass is off no leaf carries kAirDark and solid voxels
+// alone close a corridor) and behind accel_lit_voxels_undo_kernel, whose *clash it reads: a
+// pool that was made a plain copy gets no mark.  The work distribution is accel_lit_voxels_kernel's; only the wave's own pool
+// entries are written, and only the grid and the plain bricks are read beside them.
+struct DarkVoxelPass {
+    uint32_t G, axis, up;
+    uint32_t layers;     // K_d: voxel layers beyond the voxel's own
+    uint32_t entries;    // 16-bit entries of either pool
+    float sun[3];
+    uint32_t liquid[8];  // as DarkPass
+};
+
+// The voxels of axis `b` of REACH, as [lo, hi]; false: some lie beyond the world (tests/lit_voxel_ref.py: _reach)
+__device__ inline bool dark_voxel_reach(double i, double s_min, double s_max, double r_lo, double r_hi, double allow, int W, int *lo, int *hi) {
+    const double b_lo = i + (s_min < 0.0 ? r_hi : r_lo) * s_min - allow;
+    const double b_hi = i + 1.0 + (s_max > 0.0 ? r_hi : r_lo) * s_max + allow;
+    int l = (int)floor(b_lo), h = (int)floor(b_hi);
+    const int own = (int)i;
+    if (!(s_min < 0.0)) l = max(l, own);   // (monotone coordinates, as lit_reach)
+    if (!(s_max > 0.0)) h = min(h, own);
+    *lo = l;
+    *hi = h;
+    return l >= 0 && h < W;
+}
+
+// The walk of one air voxel, in the pass's own frame (as lit_voxel_walk).  One exit: the loops carry flags, not returns.
+__device__ inline bool dark_voxel_walk(const uint32_t *grid, const uint16_t *bricks, const DarkVoxelPass &dp, int ia, int iu, int iv, uint32_t ca,
+                                       uint32_t cu, uint32_t cv, uint32_t ha, uint32_t hu, uint32_t hv) {
+    const int W = (int)(dp.G * 4u);
+    const uint32_t a = dp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;
+    const double fa = (double)ia, fu = (double)iu, fv = (double)iv;
+    const double sun_a = dp.up ? (double)dp.sun[a] : (double)W - (double)dp.sun[a], sun_u = (double)dp.sun[u], sun_v = (double)dp.sun[v];
+    const double d_lo = sun_a - (fa + 2.0), d_hi = sun_a - (fa - 1.0);
+    double us_min, us_max, vs_min, vs_max;
+    dark_slopes(sun_u - (fu + 2.0), sun_u - (fu - 1.0), d_lo, d_hi, &us_min, &us_max);
+    dark_slopes(sun_v - (fv + 2.0), sun_v - (fv - 1.0), d_lo, d_hi, &vs_min, &vs_max);
+    auto blocks = [&](uint32_t voxel) {
+        const uint32_t id = voxel < 255u ? voxel : 255u;
+        return voxel != 0u && !((dp.liquid[id >> 5] >> (id & 31u)) & 1u);
+    };
+    bool inside = true, dark = false;
+    for (uint32_t k = 0; k <= dp.layers && inside && !dark; k++) {
+        const int la = ia + (int)k;
+        const double r_lo = k >= 2u ? (double)k - 2.0 : 0.0, r_hi = (double)k + 2.0;
+        const double allow = fmin(0.015 * (double)(k + 1u), 1.0) + 0.01;
+        int ul, uh, vl, vh;
+        const bool in_u = dark_voxel_reach(fu, us_min, us_max, r_lo, r_hi, allow, W, &ul, &uh);
+        const bool in_v = dark_voxel_reach(fv, vs_min, vs_max, r_lo, r_hi, allow, W, &vl, &vh);
+        inside = in_u && in_v && la < W;   // false: a ray of the voxel may leave the world from here on
+        if (!inside || k == 0u) continue;
+        const uint32_t qa = (uint32_t)(dp.up ? la : W - 1 - la);
+        const uint32_t cell_a = (qa >> 2) * ca, bit_a = (qa & 3u) << ha;
+        bool shut = true;
+        for (int nv = vl; nv <= vh && shut; nv++)
+            for (int nu = ul; nu <= uh && shut; nu++) {
+                // (every coordinate is inside the world here: the cell is one of the grid's G^3)
+                const uint32_t e = grid[cell_a + ((uint32_t)nu >> 2) * cu + ((uint32_t)nv >> 2) * cv];
+                if (e >= kAirLeaf) {
+                    shut = (e & kAirDark) != 0u;   // an air leaf: closed where every ray of the cell hits
+                } else if (is_split_entry(e)) {
+                    const uint32_t at = (e & 0x7FFFFFC0u) + (bit_a | (((uint32_t)nu & 3u) << hu) | (((uint32_t)nv & 3u) << hv));
+                    shut = at < dp.entries && blocks((uint32_t)bricks[at] >> 1);   // (a brick beyond the pool: not closed)
+                } else {
+                    shut = e != 0u && blocks(e >> 16);
+                }
+            }
+        dark = shut;
+    }
+    return dark;
+}
+
+__global__ void __launch_bounds__(256) accel_dark_voxels_kernel(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, DarkVoxelPass dp,
+                                                                const uint32_t *clash) {
+    if (*clash != 0u) return;   // the world holds kLitVoxel in a brick: the pool is a plain copy, and stays one
+    const uint32_t G = dp.G, G1 = G + 1u, lane = threadIdx.x & 63u;
+    const uint32_t cells = G * G * G, waves = (cells + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave >= waves) return;   // (wave-uniform)
+    const uint32_t mine = wave + lane * waves;   // (as accel_lit_voxels_kernel: the cells at 16 heights, numbered with y slowest)
+    uint32_t e_mine = 0u;
+    if (lane < kLitVoxelCellsPerWave && mine < cells) e_mine = grid[(((mine / G) % G) * G1 + mine / (G * G)) * G1 + mine % G];
+    const uint32_t a = dp.axis, u = a == 0u ? 1u : 0u, v = a == 2u ? 1u : 2u;
+    const uint32_t cs[3] = {1u, G1, G1 * G1};
+    const uint32_t ca = cs[a], cu = cs[u], cv = cs[v], ha = 2u * a, hu = 2u * u, hv = 2u * v;
+    const int W = (int)(G * 4u);
+    unsigned long long todo = __ballot(is_split_entry(e_mine));
+    while (todo) {
+        const uint32_t i = (uint32_t)__ffsll((long long)todo) - 1u;
+        todo &= todo - 1ull;
+        const uint32_t e = (uint32_t)__shfl((int)e_mine, (int)i, 64), cell = wave + i * waves;
+        if ((e & 0x7FFFFFC0u) + 64u > dp.entries) continue;   // (wave-uniform: the lit voxel pass wrote no such brick either)
+        const uint32_t at = (e & 0x7FFFFFC0u) + lane;
+        const int px = (int)((cell % G) * 4u + (lane & 3u)), py = (int)((cell / (G * G)) * 4u + ((lane >> 2) & 3u)), pz = (int)(((cell / G) % G) * 4u + (lane >> 4));
+        const int pa = a == 0u ? px : a == 1u ? py : pz, pu = u == 0u ? px : py, pv = v == 1u ? py : pz;
+        const uint32_t b = bricks[at];
+        // an air voxel of the world that the lit voxel pass, which wrote this entry of the pool, left without its mark
+        if ((b >> 1) == 0u && ((uint32_t)lit_bricks[at] >> 1) != kLitVoxel &&
+            dark_voxel_walk(grid, bricks, dp, dp.up ? pa : W - 1 - pa, pu, pv, ca, cu, cv, ha, hu, hv))
+            lit_bricks[at] = (uint16_t)((kDarkVoxel << 1) | (b & 1u));
+    }
+}
+
+// The dark voxel marks of a table set, on `st` behind launch_accel_lit_voxels and launch_accel_dark.
+void launch_accel_dark_voxels(const uint32_t *grid, const uint16_t *bricks, uint16_t *lit_bricks, uint32_t entries, uint32_t G, uint32_t axis, bool up,
+                              const float sun[3], uint32_t layers, const uint32_t liquid[8], const uint32_t *clash, hipStream_t st) {
+    DarkVoxelPass dp{G, axis, up ? 1u : 0u, layers, entries, {sun[0], sun[1], sun[2]}, {}};
+    for (int i = 0; i < 8; i++) dp.liquid[i] = liquid[i];
+    const uint32_t waves = (G * G * G + kLitVoxelCellsPerWave - 1u) / kLitVoxelCellsPerWave;
+    hipLaunchKernelGGL(accel_dark_voxels_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, st, grid, bricks, lit_bricks, dp, clash);
+}
+
 }  // namespace
 
 }  // namespace vrt
@@ -450,6 +572,17 @@ uint32_t dark_depth(const vrt_ctx *c, uint32_t G) {
     return depth < G ? depth : G;
 }
 
+// The dark voxel marks (accel_dark_voxels_kernel): how many voxel layers K_d a voxel's walk may take, per grid size, by the same rule —
+// the largest K_d whose pass pays for itself within 100 frames, each step up paying for its own extra (profiles/dark_voxels_ab.txt);
+// 0: no dark voxel marks.  Up to 64 cells a side 16 layers: 97 us on the pass for 1.2 to 1.4 us off every frame of the standing view
+// (two / one in flight), 70 to 82 frames (8: 53 us for 0.24 to 0.35, 150 to 220 frames, but the step from 8 to 16 buys 1.0 us for
+// 44 us; 32: 185 us for 1.95 to 2.21, whose 88 us over 16 buy 0.8 us: 107 to 114 frames, so not 32).  Above 64 cells a side the lit voxel marks are off and there is no shadow pool to mark: none; not measured.
+// VRT_DARK_VOXEL_LAYERS overrides; 0 switches the marks off: the frames then run as they did before these marks.
+uint32_t dark_voxel_layers(const vrt_ctx *c, uint32_t G) {
+    if (c->dark_voxel_layers >= 0) return (uint32_t)c->dark_voxel_layers;
+    return G <= 64u ? 16u : 0u;
+}
+
 // Marks are worth a pass (0.4 ms for 64^3 cells, 0.9 ms for the client's 240^3: profiles/sun_marks_edit_cost.txt) once what
 // they are made from stands still: while edits arrive or the sun moves from frame to frame, the frames run without marks,
 // as they always did, and the pass follows kLitSettleFrames frames after the last change.  True: this frame is that one.
@@ -505,6 +638,7 @@ int launch_passes(vrt_ctx *c, Tables &T, const LitPlan &lp, const SunMarks::Key 
         L.voxel_layers = layers;
         c->lit_voxel_passes += 1u;
     }
+    const bool pool_made = L.voxels_valid;
     // the dark marks, behind the lit ones: on every air leaf the passes above left unlit, whatever the plan's smallest leaf is
     L.dark_valid = false;
     if (const uint32_t depth = dark_depth(c, G)) {
@@ -513,6 +647,16 @@ int launch_passes(vrt_ctx *c, Tables &T, const LitPlan &lp, const SunMarks::Key 
         HIP_TRY(c, hipGetLastError());
         L.dark_valid = true;
         c->dark_passes += 1u;
+    }
+    // the dark voxel marks, into the pool this pass has just made, behind the dark cell marks they lean on: under the conditions of the
+    // lit voxel pass (the liquids a range: kDarkVoxel is material 255, no liquid).  Where the dark pass did not run no leaf carries
+    // kAirDark (accel_lit_kernel has cleared it): solid voxels alone close a corridor then, which is the rule with no dark cell
+    L.dark_voxel_layers = 0u;
+    if (const uint32_t layers = pool_made ? dark_voxel_layers(c, G) : 0u) {
+        vrt::launch_accel_dark_voxels(T.d_grid, T.d_bricks, L.d_pool, (uint32_t)T.d_bricks.cap(), G, lp.axis, lp.up, now.sun, layers, c->liquid_mask, L.d_clash, st);
+        HIP_TRY(c, hipGetLastError());
+        L.dark_voxel_layers = layers;
+        c->dark_voxel_passes += 1u;
     }
     HIP_TRY(c, L.ev.ensure());
     HIP_TRY(c, hipEventRecord(L.ev, st));
@@ -545,6 +689,7 @@ int hand_out(vrt_ctx *c, Tables &T, const LitPlan &lp, hipStream_t st, vrt::Fram
         P.lit_voxel_trips = lp.trips - lit_voxel_budget(L.voxel_layers);
         c->lit_last_voxel_layers = L.voxel_layers;
         c->lit_last_voxel_trips = P.lit_voxel_trips;
+        c->dark_last_voxel_layers = L.dark_voxel_layers;
     }
     return VRT_OK;
 }
@@ -556,8 +701,9 @@ int ensure_sun_marks(vrt_ctx *c, uint32_t k, hipStream_t st, bool shares, vrt::F
     LitPlan lp{};
     if (!c->accel_ok || !T.live || !T.d_grid || !lit_plan(c->world.size, P.sun_local, &lp)) return VRT_OK;
     SunMarks::Key now{T.gen, {P.sun_local[0], P.sun_local[1], P.sun_local[2]}, lp.min_lo, {}};
-    // (the dark marks' blockers are solid voxels that are no liquid: another liquid set, other marks)
-    if (dark_depth(c, c->accel_S * 8u)) memcpy(now.liquid, c->liquid_mask, sizeof now.liquid);
+    // (the dark marks' blockers, the cells' and the voxels', are solid voxels that are no liquid: another liquid set, other marks)
+    if (dark_depth(c, c->accel_S * 8u) || (lit_voxel_layers(c, c->accel_S * 8u) && dark_voxel_layers(c, c->accel_S * 8u)))
+        memcpy(now.liquid, c->liquid_mask, sizeof now.liquid);
     if (T.lit.valid && T.lit.made.same(now)) {
         T.lit.want_frames = 0u;   // (a sun that swings between two places must not collect its four frames one at a time)
     } else {
@@ -587,6 +733,7 @@ int marks_of_last_frame(vrt_ctx *c, const char *who, std::vector<uint32_t> &cell
 int sun_marks_for_frame(vrt_ctx *c, uint32_t tab, hipStream_t st, bool shares, vrt::FrameParams &P) {
     c->lit_last_min_leaf = c->lit_last_trips = c->lit_last_voxel_layers = c->lit_last_voxel_trips = 0u;
     c->dark_last_used = false;
+    c->dark_last_voxel_layers = 0u;
     return c->sun_marks ? ensure_sun_marks(c, tab, st, shares, P) : VRT_OK;
 }
 
@@ -651,6 +798,35 @@ int vrt_read_lit_voxels(vrt_ctx *c, uint32_t *passes, uint32_t *layers, uint32_t
                 for (size_t u = 0; u < 64u; u++)
                     if ((uint32_t)(pool[at + u] >> 1) == vrt::kLitVoxel)
                         lit[((z * 4u + (u >> 4)) * W + (y * 4u + ((u >> 2) & 3u))) * W + (x * 4u + (u & 3u))] = 1u;
+            }
+    return VRT_OK;
+}
+
+int vrt_read_dark_voxels(vrt_ctx *c, uint32_t *passes, uint32_t *layers, uint8_t *dark) {
+    GRP_ROOT(c, vrt_read_dark_voxels(d, passes, layers, dark));
+    if (!c) return VRT_ERR_INVALID_ARG;
+    if (passes) *passes = c->dark_voxel_passes;
+    if (layers) *layers = c->dark_last_voxel_layers;
+    if (!dark) return VRT_OK;
+    std::vector<uint32_t> cells;
+    VRT_TRY(marks_of_last_frame(c, "vrt_read_dark_voxels", cells));
+    const Tables &T = c->tabs[c->last.tab];
+    const size_t G = (size_t)c->accel_S * 8u, W = G * 4u;
+    memset(dark, 0, W * W * W);
+    if (!T.lit.pool_is_of(T.gen, T.d_bricks.cap())) return VRT_OK;
+    // (a mark is kDarkVoxel in the pool where the world's own brick holds air: a world that holds the id itself has no mark there)
+    std::vector<uint16_t> pool(T.lit.d_pool.cap()), plain(T.d_bricks.cap());
+    HIP_TRY(c, hipMemcpy(pool.data(), T.lit.d_pool, pool.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(plain.data(), T.d_bricks, plain.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (size_t z = 0; z < G; z++)
+        for (size_t y = 0; y < G; y++)
+            for (size_t x = 0; x < G; x++) {
+                const uint32_t e = cells[(z * G + y) * G + x];
+                const size_t at = e & 0x7FFFFFC0u;
+                if (!vrt::is_split_entry(e) || at + 64u > pool.size()) continue;
+                for (size_t u = 0; u < 64u; u++)
+                    if ((uint32_t)(pool[at + u] >> 1) == vrt::kDarkVoxel && (plain[at + u] >> 1) == 0u)
+                        dark[((z * 4u + (u >> 4)) * W + (y * 4u + ((u >> 2) & 3u))) * W + (x * 4u + (u & 3u))] = 1u;
             }
     return VRT_OK;
 }

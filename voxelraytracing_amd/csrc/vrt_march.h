@@ -751,7 +751,9 @@ __device__ __forceinline__ MarchResult march_grid(const FrameParams &P, const ui
     const uint32_t cells_limit = (kLitStops && plain_below != kAirLeaf) ? P.lit_trips : kMaxSteps;
     // (u) ... and the voxel marks only while it has made fewer than P.lit_voxel_trips, below the cell marks' count by their own step
     // budget: `limit` is the trip count at which the next of the two ends
-    bool lit_voxels = kLitStops && LITVOX && P.shadow_bricks != nullptr && P.lit_voxel_trips < cells_limit;
+    // (a careful wave reads the plain bricks: its lanes' paths are not rays the marks' proofs speak for, so a lit voxel and a dark one
+    // (kDarkVoxel: a solid id in the pool) are the air they are in the world — and a voxel of the world that holds either id is itself)
+    bool lit_voxels = kLitStops && LITVOX && !careful && P.shadow_bricks != nullptr && P.lit_voxel_trips < cells_limit;
     uint32_t limit = lit_voxels ? P.lit_voxel_trips : cells_limit;
     bool lit_stop = false, dark_stop = false;   // (dark_stop: the air leaf a lane stopped at carries kAirDark — every ray from it hits)
     uint32_t slow_below = careful ? kSlow : plain_below;

@@ -409,6 +409,19 @@ class Gpu:
             out["lit"] = lit
         return out
 
+    def dark_voxels(self, voxels: bool = False):
+        """{passes, layers[, dark[n,n,n] indexed [z,y,x], n = 32 S]} — see vrt_read_dark_voxels in include/vrt.h."""
+        p, k = C.c_uint32(), C.c_uint32()
+        dark = None
+        if voxels:
+            n = self.accel_info().world_size_chunks * 32
+            dark = np.empty((n, n, n), dtype=np.uint8)
+        self._ck(self._lib.vrt_read_dark_voxels(self._h, C.byref(p), C.byref(k), dark.ctypes.data_as(C.c_void_p) if voxels else None))
+        out = dict(passes=p.value, layers=k.value)
+        if voxels:
+            out["dark"] = dark
+        return out
+
     def dark_marks(self, cells: bool = False):
         """{passes, count, used[, dark[G,G,G] indexed [z,y,x]]} — see vrt_get_dark_marks in include/vrt.h."""
         p, n, u = C.c_uint32(), C.c_uint32(), C.c_uint32()
