@@ -340,6 +340,18 @@ pub struct vrt_sun_light {
     pub _reserved: [u32; 2],
 }
 
+/// vrt_set_water_optics: water for the path trace — absorption per voxel length and channel inside a liquid, the surface's
+/// reflectance at normal incidence (flags 0 = off, VRT_WATER_ON = on).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_water_optics {
+    pub absorb: [f32; 3],
+    pub reflectance: f32,
+    pub flags: u32,
+    pub _reserved: [u32; 3],
+}
+pub const VRT_WATER_ON: u32 = 1;
+
 /// vrt_set_camera_sampling: pixel jitter and a thin lens for the path trace (pixel_spread and aperture both 0 = off).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -450,6 +462,7 @@ extern "C" {
     pub fn vrt_get_tone_info(ctx: *mut vrt_ctx, out: *mut vrt_tone_info) -> c_int;
     pub fn vrt_read_tone_histogram(ctx: *mut vrt_ctx, bins: *mut u32) -> c_int;
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
+    pub fn vrt_set_water_optics(ctx: *mut vrt_ctx, opts: *const vrt_water_optics) -> c_int;
     pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
     pub fn vrt_set_lamp_light(ctx: *mut vrt_ctx, opts: *const vrt_lamp_light) -> c_int;
     pub fn vrt_get_lamp_info(ctx: *mut vrt_ctx, out: *mut vrt_lamp_info) -> c_int;
@@ -458,7 +471,7 @@ extern "C" {
     pub fn vrt_read_output(ctx: *mut vrt_ctx, rgb: *mut f32, ids: *mut u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_present(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8: *mut u8) -> c_int;
     pub fn vrt_selftest_exact_math(device: i32, n: u32, seed: u32, mismatches: *mut u64) -> c_int;
-    /// `op`: 0 .. 20, the VRT_MATH_* of include/vrt.h, which also gives the words per operand set of `input` and `out`.
+    /// `op`: 0 .. 21, the VRT_MATH_* of include/vrt.h, which also gives the words per operand set of `input` and `out`.
     pub fn vrt_selftest_math_values(device: i32, op: u32, n: u32, input: *const u32, out: *mut u32) -> c_int;
     pub fn vrt_present_device(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, rgba8_device: *mut *mut c_void, bytes: *mut u64) -> c_int;
     pub fn vrt_set_presentation(ctx: *mut vrt_ctx, crosshair: *const vrt_crosshair, screen_w: u32, screen_h: u32, flags: u32) -> c_int;
@@ -519,6 +532,7 @@ mod layout {
         assert!(size_of::<vrt_tone_map>() == 48);
         assert!(size_of::<vrt_tone_info>() == 40);
         assert!(size_of::<vrt_sun_light>() == 16);
+        assert!(size_of::<vrt_water_optics>() == 32);
         assert!(size_of::<vrt_camera_sampling>() == 16);
         assert!(size_of::<vrt_lamp_light>() == 16);
         assert!(size_of::<vrt_lamp>() == 16);

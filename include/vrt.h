@@ -528,6 +528,60 @@ typedef struct {
 } vrt_sun_light;            /* 16 B */
 int vrt_set_sun_light(vrt_ctx *ctx, const vrt_sun_light *opts);
 
+/* Water for VRT_MODE_PATH: a surface that reflects, a body that absorbs.  Without the setting every segment of a path passes the
+ * material table's liquids as if they were air, and all a frame keeps of a lake is VRT_ID_WATER in the id word.  The primary modes
+ * ignore the setting and stay byte for byte what they are.  Build-defined, and defined exactly — per path segment with origin o
+ * (world-local), direction d and throughput thr, in strict binary32, nothing contracted:
+ *   1  wet or dry, decided afresh at the start of every segment, the primary's included (there is no per-path state): the segment
+ *      is wet when the voxel at floor(o) is a liquid of the context's material table (ids >= 255 share entry 255).  The voxel is
+ *      vrt_get_voxels' answer: 0 outside the world box (a NaN is outside), 0 where chunk_roots holds no chunk
+ *   2  a dry segment is marched with the empty liquid set: a liquid voxel stops the ray like a solid, and the hit carries that
+ *      voxel, its position and its face normal.  water_dist is 0
+ *   3  a wet segment is marched with the table's liquid set, as every segment is without the setting.  w = its water_dist.  Before
+ *      anything else of the segment — the sky's weight, the emission and sun terms, the lobes:
+ *        thr.ch *= vexp_neg(absorb[ch] * w)        always, w == 0 included
+ *      vexp_neg(t) = e^-t in + - *, floor and integer operations (csrc/both/water_math.h states it operation for operation; the
+ *      host's vrth_water_transmittance compiles the same text): exactly 1 for t = 0, +0 from t = 128 on and already where e^-t
+ *      rounds to it (t above about 103.98), a NaN for a NaN; results below 2^-126 are rounded to nearest even like any other
+ *   4  the surface event — a dry segment's hit whose voxel is a liquid of the table:
+ *        u = rng_next(rng)                          the event's only draw
+ *        c = |dot(norm, d)|;  m = 1 - c;  m5 = (m * m) * (m * m) * m;  F = reflectance + (1 - reflectance) * m5
+ *        u < F:      d'.k = d.k - 2 * norm.k * dot(norm, d);  o'.k = pos.k + norm.k * bias      (the bounce origin)
+ *        otherwise:  d' = d;  o' = pos
+ *      thr is unchanged.  The event gives off no emission, sends no sun ray and draws nothing else (no pass-through draw, no coat
+ *      draw).  It costs one of the path's max_ray_bounces segments, as a pass through a translucent voxel does
+ *   5  every other hit and every miss: the text of the frame without the setting, word for word — emission term, sun term
+ *      (vrt_set_sun_light: its ray passes liquids and is not attenuated), pass-through draw, coat draw, direction, thr *= tint; a
+ *      later miss of a sun-lit frame takes the sky without the disc
+ *   6  the texel's id word is that of the primary segment's own march: a dry camera that looks at a lake gets the water voxel and
+ *      its face (vrt_cast_rays picks the same voxel: liquids stop cast_ray), VRT_ID_WATER clear; a wet camera gets what it got
+ *      before.  The denoiser's guide is taken from the same march, so key and guide agree: the guide of a lake seen from above is
+ *      the water face's plane
+ *   7  a sample's light is its terms in segment order, the sky last; a frame's, its samples' in sample order, / spp.
+ *      VRT_RENDER_ACCUMULATE keeps its identity (K frames of s spp are one frame of K * s spp, bit for bit).  vrt_stats.
+ *      secondary_rays counts a surface event's continuation as the bounce segment it is; vrt_set_denoise, vrt_set_tone_map, the
+ *      emission, polish and translucency tables, shard and multi-device contexts compose
+ * A water frame runs one lane = path launch per segment, one sample per chain, as a sun-lit frame does: the pool kernel's march
+ * cells have the table's liquid set baked in.  Not built: refraction, the surface seen from below and total internal reflection (a
+ * wet segment leaves the water silently), absorption along sun rays, caustics.
+ * Does not compose yet: with the setting on, vrt_render of a VRT_MODE_PATH frame (max_ray_bounces > 0) while vrt_set_lamp_light or
+ * vrt_set_camera_sampling is on returns VRT_ERR_STATE, names the pair in vrt_last_error, enqueues nothing and leaves the last frame
+ * readable.
+ * opts NULL or flags == 0: off, the default — frames are byte for byte those of a context that never called this, the same kernels
+ * run, and nothing is launched, planned or allocated differently.  A null context, an absorb that is negative, NaN or infinite,
+ * a reflectance outside [0, 1] or NaN (the floats are checked whatever flags says), a flag bit other than VRT_WATER_ON,
+ * _reserved not 0: VRT_ERR_INVALID_ARG; a refused call changes nothing.  A call that changes the setting (off is 32 zero bytes; -0
+ * is kept as +0) restarts the accumulation; one that does not, does not.  A multi-device context replicates the setting; a shard
+ * context keeps its own. */
+typedef struct {
+    float    absorb[3];     /* absorption per voxel length, per channel: finite, >= 0 */
+    float    reflectance;   /* the surface's reflectance at normal incidence, in [0, 1] */
+    uint32_t flags;         /* 0 = off (the default), VRT_WATER_ON */
+    uint32_t _reserved[3];  /* 0 */
+} vrt_water_optics;         /* 32 B */
+#define VRT_WATER_ON 1u
+int vrt_set_water_optics(vrt_ctx *ctx, const vrt_water_optics *opts);
+
 /* Camera sampling for VRT_MODE_PATH: a primary ray of its own for every sample — sub-pixel jitter (a box pixel filter, which
  * is what removes the stair steps of voxel edges as samples accumulate) and a thin lens (depth of field).  Without it every
  * sample of a pixel starts with the pixel's one ray.  The primary modes ignore the setting and stay byte for byte what they
@@ -740,6 +794,8 @@ int vrt_selftest_exact_math(int32_t device, uint32_t n, uint32_t seed, uint64_t 
  *     VRT_MATH_BFI             mask, a, b         (mask & a) | (~mask & b)
  *     VRT_MATH_LOW_BITS        a, b               low_bits_of<3>, <7>, <15>, <31>(a, b)
  *     VRT_MATH_OR_AND          a, b, c            a | (b & c)
+ *     VRT_MATH_EXP_NEG         a, w               vexp_neg(a * w): vrt_set_water_optics' transmittance of absorb a over water_dist w,
+ *                                                 the product formed in binary32 as the kernels form it (csrc/both/water_math.h)
  *     VRT_MATH_MAD_I24         a, b, c            mad_i24(a, b, c); b is a scalar operand: every set of a wave uses the b of
  *                                                 the wave's first set
  * Returns VRT_ERR_INVALID_ARG, and writes nothing, for a null pointer, n == 0, n > VRT_MATH_MAX_SETS or an unknown op. */
@@ -764,7 +820,8 @@ int vrt_selftest_exact_math(int32_t device, uint32_t n, uint32_t seed, uint64_t 
 #define VRT_MATH_LOW_BITS 18u
 #define VRT_MATH_OR_AND 19u
 #define VRT_MATH_MAD_I24 20u
-#define VRT_MATH_OPS 21u
+#define VRT_MATH_EXP_NEG 21u
+#define VRT_MATH_OPS 22u
 #define VRT_MATH_MAX_SETS (1u << 26)
 int vrt_selftest_math_values(int32_t device, uint32_t op, uint32_t n, const uint32_t *in, uint32_t *out);
 

@@ -218,6 +218,12 @@ int vrth_tone_meter(const float *rgb, uint32_t w, uint32_t h, const vrt_tone_map
  * may alias rgb_in.  Returns 0, or -1 as vrth_tone_meter does (VRT_TONE_OFF copies). */
 int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, float exposure, float *rgb_out);
 
+/* ---- water optics (include/vrt.h: vrt_set_water_optics) on the host ---- */
+/* out[i] = vexp_neg(absorb[i] * dist[i]), i < n: the transmittance of a wet segment's channel in the text the water kernels compile
+ * (csrc/both/water_math.h), the product formed in binary32 as they form it.  out may alias either input.  Returns 0, or -1 for a
+ * null pointer. */
+int vrth_water_transmittance(const float *absorb, const float *dist, uint64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,87 @@
+"""vrt_set_water_optics (include/vrt.h) without a GPU: the header declares the struct and the function, the struct is 32 bytes as
+ctypes and the Rust crate have it, the library exports the function, a null context is refused, and the water kernels are a pair
+of their own that keeps everything in registers."""
+import ctypes as C
+import inspect
+import os
+import re
+import subprocess
+
+from voxelraytracing_amd import _ffi, graphics
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _read(*parts):
+    with open(os.path.join(ROOT, *parts)) as f:
+        return f.read()
+
+
+def test_header_declares_the_struct_and_the_function():
+    h = _read("include", "vrt.h")
+    assert re.search(r"typedef\s+struct\s*\{\s*float\s+absorb\[3\];[^}]*float\s+reflectance;[^}]*uint32_t\s+flags;[^}]*uint32_t\s+_reserved\[3\];[^}]*\}"
+                     r"\s*vrt_water_optics\s*;", h)
+    assert re.search(r"#define VRT_WATER_ON 1u", h)
+    assert re.search(r"int\s+vrt_set_water_optics\s*\(\s*vrt_ctx\s*\*\s*ctx\s*,\s*const\s+vrt_water_optics\s*\*\s*opts\s*\)\s*;", h)
+    # the contract names what does not compose and what is out of scope
+    doc = h[h.index("Water for VRT_MODE_PATH"):h.index("} vrt_water_optics;")]
+    for word in ("vexp_neg", "VRT_ERR_STATE", "vrt_set_lamp_light", "vrt_set_camera_sampling", "refraction", "total internal reflection", "caustics"):
+        assert word in doc, word
+
+
+def test_the_struct_is_32_bytes(tmp_path):
+    src = tmp_path / "size.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "vrt.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(vrt_water_optics), offsetof(vrt_water_optics, absorb), '
+                   'offsetof(vrt_water_optics, reflectance), offsetof(vrt_water_optics, flags), offsetof(vrt_water_optics, _reserved)); return 0; }\n')
+    exe = tmp_path / "size"
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    assert subprocess.check_output([str(exe)], text=True).split() == ["32", "0", "12", "16", "20"]
+    assert C.sizeof(_ffi.WaterOptics) == 32
+    assert [(n, getattr(_ffi.WaterOptics, n).offset) for n, _ in _ffi.WaterOptics._fields_] == [("absorb", 0), ("reflectance", 12), ("flags", 16),
+                                                                                              ("_reserved", 20)]
+    assert _ffi.WATER_ON == 1
+
+
+def test_the_library_exports_it():
+    lib = _ffi.vrt()
+    assert hasattr(lib, "vrt_set_water_optics")
+    assert _ffi.VRT_SYMBOLS["vrt_set_water_optics"] == (C.c_int, [C.c_void_p, C.POINTER(_ffi.WaterOptics)])
+    assert hasattr(_ffi.host(), "vrth_water_transmittance")
+
+
+def test_null_context_is_refused_without_a_device():
+    lib = _ffi.vrt()
+    o = _ffi.WaterOptics((C.c_float * 3)(0.1, 0.1, 0.1), 0.02, _ffi.WATER_ON, (C.c_uint32 * 3)(0, 0, 0))
+    assert lib.vrt_set_water_optics(None, C.byref(o)) == _ffi.VRT_ERR_INVALID_ARG
+    assert lib.vrt_set_water_optics(None, None) == _ffi.VRT_ERR_INVALID_ARG
+
+
+def test_python_binding():
+    assert list(inspect.signature(graphics.Gpu.set_water_optics).parameters) == ["self", "absorb", "reflectance"]
+    assert graphics.MATH_OPS["exp_neg"] == (21, 2, 1)
+
+
+def test_rust_binding():
+    rs = _read("bindings", "rust", "vrt-sys", "src", "lib.rs")
+    assert re.search(r"pub struct vrt_water_optics \{\s*pub absorb: \[f32; 3\],\s*pub reflectance: f32,\s*pub flags: u32,\s*pub _reserved: \[u32; 3\],\s*\}", rs)
+    assert re.search(r"pub const VRT_WATER_ON: u32 = 1;", rs)
+    assert re.search(r"pub fn vrt_set_water_optics\(ctx: \*mut vrt_ctx, opts: \*const vrt_water_optics\) -> c_int;", rs)
+    assert re.search(r"size_of::<vrt_water_optics>\(\) == 32", rs)
+
+
+def test_the_water_kernels_are_a_pair_of_their_own_without_scratch():
+    """One pair of trace kernels — the ten march forms each (docs/KERNELS.md, "Water"), coat, pass-through and sunlight read from
+    the launch — and the guide kernel's three marches; code-object metadata: no scratch, nothing spilled."""
+    regs = _ffi.kernel_registers()
+    water = {k: v for k, v in regs.items() if "water" in k}
+    assert sum(1 for k in water if "path_water_primary_kernel" in k) == 10
+    assert sum(1 for k in water if "path_water_bounce_kernel" in k) == 10
+    assert sum(1 for k in water if "denoise_guide_water_kernel" in k) == 3
+    assert len(water) == 23
+    # march form by march form: the literal walk and the ancestor-cache walk with and without the root table in LDS, the grid
+    # march without; each counting and not
+    forms = sorted(re.search(r"path_water_bounce_kernelI(Li\dELb\dELb\dE)", k).group(1) for k in water if "path_water_bounce_kernel" in k)
+    assert forms == sorted(f"Li{m}ELb{r}ELb{s}E" for m, rs in ((0, (0,)), (1, (0, 1)), (2, (0, 1))) for r in rs for s in (0, 1))
+    bad = {k: v for k, v in water.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
+    assert not bad, bad

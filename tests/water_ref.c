@@ -1,0 +1,272 @@
+/* tests/water_ref.c — the path trace with water optics (vrt_set_water_optics, include/vrt.h), for the tests: the contract's seven
+ * steps on top of the emission, polish and translucency tables and direct sunlight.  TEST INFRASTRUCTURE ONLY: compiled by
+ * tests/water_ref.py with oracle/Makefile's CFLAGS into a temporary directory.
+ *
+ * tests/path_ref.c's loop is a static function without a hook between its march and what follows it, so the loop is restated here
+ * with camera sampling and lamp light left out (a water frame has neither).  The march, the sky and the RNG are the oracle's own
+ * functions (this file includes it): a wet segment is ray_world over the scene, a dry one ray_world over a copy of the scene whose
+ * materials have every is_liquid cleared.  vexp_neg is written out again here, operation for operation, not taken from
+ * csrc/both/water_math.h: tests/test_water_math.py holds that text to a third statement in numpy.  Compiled without contraction.
+ * With the setting off (on == 0) the loop is path_ref.c's with those two terms off: tests/test_water_ref.py holds it to that. */
+#include "../oracle/vrt_oracle.c"
+
+typedef struct {   /* include/vrt.h: vrt_polish */
+    float color[3];
+    float chance;
+    float scatter;
+    uint32_t _reserved[3];
+} ref_polish;
+
+typedef struct {   /* include/vrt.h: vrt_translucency */
+    float color[3];
+    float chance;
+} ref_translucency;
+
+typedef struct {   /* include/vrt.h: vrt_water_optics */
+    float absorb[3];
+    float reflectance;
+    uint32_t flags;
+    uint32_t _reserved[3];
+} ref_water_optics;
+
+/* What a frame or a sample counts (tests/water_ref.py: Counts, in this order).  steps: the lookups of every march, path segments
+ * and sun rays; bounce segments: the segments behind the primary ones (a surface event's continuation is one); surface events and
+ * how many of them reflected and went through; wet segments with water_dist > 0; wet segments that hit; primary segments that
+ * start wet with water_dist > 0; bounce segments that start wet; hits on a solid voxel at the end of a wet segment (the bed seen
+ * through water) */
+enum { N_STEPS, N_BOUNCE_SEGMENTS, N_SUN_RAYS, N_SUN_UNOCCLUDED, N_SURFACE, N_REFLECTED, N_TRANSMITTED, N_WET_W, N_WET_HIT, N_WET_PRIMARY_W,
+       N_WET_BOUNCES, N_PASSES, N_POLISHED, N_COUNTS };
+
+static float ref_exp_neg(float t) {
+    if (!(t >= 0.0f)) return t != t ? t : 1.0f;
+    if (t >= 128.0f) return 0.0f;
+    const float x = -t;
+    const float kf = floorf(x * 1.44269502f + 0.5f);
+    const float r = (x - kf * 0.693359375f) - kf * -2.12194442e-4f;
+    const float q = 0.5f + r * (0.166666672f + r * (0.0416666679f + r * (0.00833333377f + r * (0.00138888892f + r * 1.98412701e-4f))));
+    const float p = (1.0f + r) + (r * r) * q;
+    const int32_t k = (int32_t)kf;
+    const uint32_t bp = orc_f2bits(p);
+    const int32_t E = (int32_t)(bp >> 23) + k;
+    if (E >= 1) return orc_bits2f(bp + ((uint32_t)k << 23));
+    const uint32_t shift = (uint32_t)(1 - E);
+    if (shift > 24u) return 0.0f;
+    const uint32_t m = (bp & 0x007FFFFFu) | 0x00800000u;
+    const uint32_t half = 1u << (shift - 1u), rem = m & ((half << 1) - 1u);
+    uint32_t bits = m >> shift;
+    if (rem > half || (rem == half && (bits & 1u))) bits += 1u;
+    return orc_bits2f(bits);
+}
+
+float ref_water_exp_neg(float t) { return ref_exp_neg(t); }
+
+/* step 1: the voxel at floor(o) as vrt_get_voxels answers — 0 outside the world box, 0 where there is no chunk */
+static uint32_t voxel_at_floor(const orc_scene *s, v3 o) {
+    const float fx = floorf(o.x), fy = floorf(o.y), fz = floorf(o.z);
+    const float size = (float)s->world.size;
+    if (!(fx >= 0.0f && fy >= 0.0f && fz >= 0.0f && fx < size && fy < size && fz < size)) return 0u;
+    const uint32_t x = (uint32_t)fx, y = (uint32_t)fy, z = (uint32_t)fz, w = s->world.size_in_chunks;
+    const uint32_t ch = (x >> 5) + w * ((y >> 5) + w * (z >> 5));
+    const uint32_t root = ch < s->n_chunk_roots ? s->chunk_roots[ch] : 0u;
+    if (root == 0u) return 0u;
+    const v3 min = V3((float)((x >> 5) * 32u), (float)((y >> 5) * 32u), (float)((z >> 5) * 32u));
+    const found_node f = find_chunk_node(s, V3(fx + 0.5f, fy + 0.5f, fz + 0.5f), 5u, min, root);
+    return node_voxel(node_at(s, f.root + f.idx));
+}
+
+static int is_table_liquid(const orc_scene *s, uint32_t voxel) { return mat_at(s, voxel)->is_liquid == 1u; }
+
+typedef struct {
+    const orc_scene *scene, *dry, *no_disc;   /* dry: every is_liquid cleared; no_disc: sun_intensity 0 */
+    const float *emission;
+    const ref_polish *polish;
+    const ref_translucency *tr;
+    int polished_frame, translucent_frame;
+    float sun_strength;
+    const ref_water_optics *wo;
+} water_settings;
+
+static float exit_t(float pos, float dir) {
+    const float c = floorf(pos);
+    const float far = dir > 0.0f ? c + 1.0f : c;
+    return dir != 0.0f ? (far - pos) / dir : INFINITY;
+}
+
+/* One sample: its light; *id: the id word of its primary segment's own march; n[N_COUNTS] grows; thr_bed: NULL, or where the
+ * throughput at the sample's first hit on a solid voxel at the end of a wet segment is kept (untouched if there is none). */
+static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n, float *thr_bed) {
+    const orc_scene *s = p->scene;
+    const int on = p->wo->flags != 0u;
+    v3 light = V3(0.0f, 0.0f, 0.0f);
+    v3 origin, dir;
+    create_ray_from_screen(s, (int32_t)px, (int32_t)py, &origin, &dir);
+    v3 thr = V3(1.0f, 1.0f, 1.0f);
+    const int sun_lit = p->sun_strength != 0.0f;
+    int bed_seen = 0;
+    for (uint32_t bounce = 0; bounce < s->settings.max_ray_bounces; bounce++) {
+        /* steps 1 to 3 */
+        const int wet = !on || is_table_liquid(s, voxel_at_floor(s, origin));
+        hit_result rs = ray_world(wet ? s : p->dry, origin, dir);
+        n[N_STEPS] += rs.iter_count;
+        if (bounce != 0) n[N_BOUNCE_SEGMENTS] += 1u;
+        if (bounce == 0) *id = id_word(&rs);
+        if (on && wet) {
+            const float w = rs.water_dist;
+            thr.x *= ref_exp_neg(p->wo->absorb[0] * w);
+            thr.y *= ref_exp_neg(p->wo->absorb[1] * w);
+            thr.z *= ref_exp_neg(p->wo->absorb[2] * w);
+            if (w > 0.0f) n[N_WET_W] += 1u;
+            if (rs.hit) n[N_WET_HIT] += 1u;
+            if (bounce == 0 && w > 0.0f) n[N_WET_PRIMARY_W] += 1u;
+            if (bounce != 0) n[N_WET_BOUNCES] += 1u;
+            if (rs.hit && is_solid_hit(s, &rs) && thr_bed && !bed_seen) {
+                thr_bed[0] = thr.x; thr_bed[1] = thr.y; thr_bed[2] = thr.z;
+                bed_seen = 1;
+            }
+        }
+        if (!rs.hit) {
+            const v3 sky = ray_sky((sun_lit && bounce != 0) ? p->no_disc : s, origin, dir);
+            light.x += sky.x * thr.x;
+            light.y += sky.y * thr.y;
+            light.z += sky.z * thr.z;
+            break;
+        }
+        if (on && !wet && is_table_liquid(s, rs.voxel)) {
+            /* step 4, the surface event.  (On the last allowed segment nothing of it is observed, so nothing is drawn.) */
+            n[N_SURFACE] += 1u;
+            if (bounce + 1 == s->settings.max_ray_bounces) break;
+            const float u = orc_rng_next(&rng);
+            const float dn = orc_dot(rs.norm, dir);
+            const float c = fabsf(dn), m = 1.0f - c, m5 = (m * m) * (m * m) * m;
+            const float F = p->wo->reflectance + (1.0f - p->wo->reflectance) * m5;
+            if (u < F) {
+                origin = V3(rs.pos.x + rs.norm.x * ORC_SHADOW_BIAS, rs.pos.y + rs.norm.y * ORC_SHADOW_BIAS, rs.pos.z + rs.norm.z * ORC_SHADOW_BIAS);
+                dir = V3(dir.x - 2.0f * rs.norm.x * dn, dir.y - 2.0f * rs.norm.y * dn, dir.z - 2.0f * rs.norm.z * dn);
+                n[N_REFLECTED] += 1u;
+            } else {
+                origin = rs.pos;
+                n[N_TRANSMITTED] += 1u;
+            }
+            continue;
+        }
+        /* step 5: path_ref.c's text */
+        const v3 so = V3(rs.pos.x + rs.norm.x * ORC_SHADOW_BIAS, rs.pos.y + rs.norm.y * ORC_SHADOW_BIAS, rs.pos.z + rs.norm.z * ORC_SHADOW_BIAS);
+        const uint32_t entry = rs.voxel > 255u ? 255u : rs.voxel;
+        const float e = p->emission[entry];
+        if (e != 0.0f) {
+            light.x += (rs.color.x * e) * thr.x;
+            light.y += (rs.color.y * e) * thr.y;
+            light.z += (rs.color.z * e) * thr.z;
+        }
+        if (sun_lit && is_solid_hit(s, &rs)) {
+            const v3 sd = orc_normalize(V3(s->settings.sun_pos[0] - (float)s->world.min[0] - so.x,
+                                           s->settings.sun_pos[1] - (float)s->world.min[1] - so.y,
+                                           s->settings.sun_pos[2] - (float)s->world.min[2] - so.z));
+            const float c = orc_dot(rs.norm, sd);
+            if (c > 0.0f) {
+                const hit_result sh = ray_world(s, so, sd);   /* liquids passed, unattenuated */
+                n[N_SUN_RAYS] += 1u;
+                n[N_STEPS] += sh.iter_count;
+                if (!sh.hit) {
+                    const float k = s->settings.sun_intensity * p->sun_strength;
+                    const float w = k * c;
+                    n[N_SUN_UNOCCLUDED] += 1u;
+                    light.x += (rs.color.x * w) * thr.x;
+                    light.y += (rs.color.y * w) * thr.y;
+                    light.z += (rs.color.z * w) * thr.z;
+                }
+            }
+        }
+        if (bounce + 1 == s->settings.max_ray_bounces) break;
+        if (p->translucent_frame && orc_rng_next(&rng) < p->tr[entry].chance) {
+            const float tx = exit_t(rs.pos.x, dir.x), ty = exit_t(rs.pos.y, dir.y), tz = exit_t(rs.pos.z, dir.z);
+            float t = tx;
+            if (ty < t) t = ty;
+            if (tz < t) t = tz;
+            const float ts = t + 0.001f;
+            thr.x *= p->tr[entry].color[0]; thr.y *= p->tr[entry].color[1]; thr.z *= p->tr[entry].color[2];
+            origin = V3(rs.pos.x + dir.x * ts, rs.pos.y + dir.y * ts, rs.pos.z + dir.z * ts);
+            n[N_PASSES] += 1u;
+            continue;
+        }
+        int polished = 0;
+        if (p->polished_frame) polished = orc_rng_next(&rng) < p->polish[entry].chance;
+        const float d = orc_dot(rs.norm, dir);
+        const v3 spec = V3(dir.x - 2.0f * rs.norm.x * d, dir.y - 2.0f * rs.norm.y * d, dir.z - 2.0f * rs.norm.z * d);
+        const v3 rd = rng_next_dir(&rng);
+        const v3 sc = orc_normalize(V3(rs.norm.x + rd.x, rs.norm.y + rd.y, rs.norm.z + rd.z));
+        const float scatter = polished ? p->polish[entry].scatter : mat_at(s, rs.voxel)->scatter;
+        const v3 nd = orc_normalize(V3(orc_mix(spec.x, sc.x, scatter), orc_mix(spec.y, sc.y, scatter), orc_mix(spec.z, sc.z, scatter)));
+        const v3 tint = polished ? V3(p->polish[entry].color[0], p->polish[entry].color[1], p->polish[entry].color[2]) : rs.color;
+        thr.x *= tint.x; thr.y *= tint.y; thr.z *= tint.z;
+        origin = so;
+        dir = nd;
+        n[N_POLISHED] += polished ? 1u : 0u;
+    }
+    return light;
+}
+
+typedef struct {
+    orc_scene dry, no_disc;
+    orc_material dry_mats[256];
+} water_scenes;
+
+static water_settings settings_of(const orc_scene *scene, water_scenes *ws, const float *emission, const ref_polish *polish, const ref_translucency *tr,
+                                  float sun_strength, const ref_water_optics *wo) {
+    water_settings p = {scene, &ws->dry, &ws->no_disc, emission, polish, tr, 0, 0, sun_strength, wo};
+    for (uint32_t i = 0; i < 256u; i++) {
+        p.polished_frame |= polish[i].chance != 0.0f;
+        p.translucent_frame |= tr[i].chance != 0.0f;
+        ws->dry_mats[i] = scene->materials[i];
+        ws->dry_mats[i].is_liquid = 0u;
+    }
+    ws->dry = *scene;
+    ws->dry.materials = ws->dry_mats;
+    ws->no_disc = *scene;
+    ws->no_disc.settings.sun_intensity = 0.0f;
+    return p;
+}
+
+/* A w x h frame of samples sample_base .. sample_base + spp - 1, their mean in rgb[h][w][3], the id word of the first sample's
+ * primary segment in ids[h][w], counts[N_COUNTS].  Like orc_render, pixels beyond the last whole 8 x 8 tile are not traced: the
+ * caller passes zeroed arrays. */
+void ref_render_water(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
+                      const ref_water_optics *wo, uint32_t w, uint32_t h, uint32_t seed, uint32_t spp, uint32_t sample_base, float *rgb, uint32_t *ids,
+                      uint64_t *counts) {
+    const uint32_t x1 = w & ~7u, y1 = h & ~7u, nspp = spp ? spp : 1u;
+    water_scenes ws;
+    const water_settings p = settings_of(scene, &ws, emission, polish, tr, sun_strength, wo);
+    uint64_t n[N_COUNTS] = {0};
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : n[:N_COUNTS])
+    for (int32_t py = 0; py < (int32_t)y1; py++) {
+        for (uint32_t px = 0; px < x1; px++) {
+            const size_t o = (size_t)py * w + px;
+            v3 sum = V3(0.0f, 0.0f, 0.0f);
+            uint32_t id = 0;
+            for (uint32_t sm = 0; sm < nspp; sm++) {
+                uint32_t sid = 0;
+                const v3 l = trace_path_water(&p, px, (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, NULL);
+                sum.x += l.x; sum.y += l.y; sum.z += l.z;
+                if (sm == 0) id = sid;
+            }
+            rgb[o * 3 + 0] = sum.x / (float)nspp;
+            rgb[o * 3 + 1] = sum.y / (float)nspp;
+            rgb[o * 3 + 2] = sum.z / (float)nspp;
+            ids[o] = id;
+        }
+    }
+    memcpy(counts, n, sizeof n);
+}
+
+/* one pixel's one sample: its light, the id word of its primary segment, its counts, and thr_bed[3]: the throughput at its first
+ * hit on a solid voxel at the end of a wet segment (left as passed in if there is none) */
+void ref_trace_pixel_water(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
+                           const ref_water_optics *wo, uint32_t w, uint32_t h, uint32_t seed, uint32_t px, uint32_t py, uint32_t sample, float *light,
+                           uint32_t *id, uint64_t *counts, float *thr_bed) {
+    water_scenes ws;
+    const water_settings p = settings_of(scene, &ws, emission, polish, tr, sun_strength, wo);
+    memset(counts, 0, N_COUNTS * sizeof *counts);
+    *id = 0;
+    const v3 l = trace_path_water(&p, px, py, path_seed(px, py, w, h, sample, seed), id, counts, thr_bed);
+    light[0] = l.x; light[1] = l.y; light[2] = l.z;
+}

@@ -198,6 +198,9 @@ static PathRecord new_path_frame(const PathFacts &F) {
             case vrt::kStepLampPrimary: case vrt::kStepLampBounce: case vrt::kStepLampRays:
                 CHECK(!"a frame without vrt_set_lamp_light has no lamp-lit step");
                 break;
+            case vrt::kStepWaterPrimary: case vrt::kStepWaterBounce:
+                CHECK(!"a frame without vrt_set_water_optics has no water step");
+                break;
             case vrt::kStepChainFinish:
                 r.launches.emplace_back(kChainFinish, s.sample, s.chain, -1, -1, -1, -1, -1, 0u, 0u, 0u, s.first, s.last, s.count, sum_chain, kFrame);
                 break;
@@ -420,6 +423,72 @@ static void check_lamp_frames() {
     std::printf("check_lamp_plan: ok (%ld lamp-lit frames, %ld launches)\n", frames, launches);
 }
 
+// vrt_set_water_optics: a water frame is planned like a sun-lit one — the same chains, launch numbers and finishing passes, no pool
+// kernel, one sample per chain — with the water kinds in the place of the trace launches' and a kStepSunRays behind each only when
+// the frame is sun-lit too.  The kinds from before keep their values.  (F.water false is every frame above: the plan is what it was.)
+static void check_water_frames() {
+    static_assert(vrt::kStepLampPrimary == 9 && vrt::kStepLampBounce == 10 && vrt::kStepLampRays == 11,
+                  "the step kinds from before vrt_set_water_optics keep their values");
+    long frames = 0, launches = 0;
+    const uint32_t spps[] = {1, 2, 3, 12, 17}, per_chain[] = {1, 4, 16};
+    const int accums[] = {-1, 0, 7};
+    for (uint32_t spp : spps)
+    for (uint32_t bounces = 0; bounces <= 5; bounces++)
+    for (uint32_t bits = 0; bits < 1024; bits++)
+    for (int accum : accums)
+    for (uint32_t samples : per_chain) {
+        PathFacts F;
+        F.spp = spp; F.seed = 11u; F.bounces = bounces; F.water = true;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u; F.sun = bits & 512u;
+        F.march_direct = F.has_cells;
+        F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
+        F.path_samples = samples; F.hit_seg_cap = 512u;
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) continue;
+        std::snprintf(g_case, sizeof g_case, "water: spp %u bounces %u bits %u accum %d per chain %u", spp, bounces, bits, accum, samples);
+        const PathPlan p = vrt::plan_path(F);
+        PathFacts E = F;   // the same frame with the water off and the sun on: the structure a water frame takes
+        E.water = false; E.sun = true;
+        const PathPlan e = vrt::plan_path(E);
+        PathFacts O = F;   // ... and with the water off: what the setting must not change when it is off
+        O.water = false;
+        const PathPlan o = vrt::plan_path(O);
+        CHECK(!o.water && p.water == (bounces > 0u) && p.sun == (F.sun && bounces > 0u) && p.sun_cells == o.sun_cells && !p.lamp && !p.lens);
+        CHECK(p.polish == F.polished && p.translucent == F.translucent);
+        if (!p.water) continue;
+        CHECK(p.emit && !p.cells && p.samples == 1u && !p.planes);
+        CHECK(p.finish == e.finish && p.own_sum == e.own_sum && p.seg_cap == e.seg_cap && p.cap == e.cap && p.divide_at_end == e.divide_at_end &&
+              p.needs_acc_planes == e.needs_acc_planes && p.needs_accum_sum == e.needs_accum_sum && p.sample_base == e.sample_base &&
+              p.accum_count == e.accum_count && p.finish_into_accum == e.finish_into_accum);
+        std::vector<PathStep> ps, es;
+        vrt::for_each_path_step(p, [&](const PathStep &s) { ps.push_back(s); });
+        vrt::for_each_path_step(e, [&](const PathStep &s) { es.push_back(s); });
+        size_t i = 0;
+        for (const PathStep &s : es) {
+            if (s.kind == vrt::kStepSunRays) {   // (the sun's launch: only in a frame that is sun-lit too, checked below)
+                continue;
+            }
+            CHECK(i < ps.size());
+            const PathStep &t = ps[i++];
+            CHECK(t.sample == s.sample && t.chain == s.chain && t.launch == s.launch &&
+                  t.segments == s.segments && t.last_bounce == s.last_bounce && t.first == s.first && t.last == s.last && t.count == s.count);
+            if (s.kind == vrt::kStepSunlitPrimary || s.kind == vrt::kStepSunlitBounce) {
+                CHECK(t.kind == (s.kind == vrt::kStepSunlitPrimary ? vrt::kStepWaterPrimary : vrt::kStepWaterBounce) && vrt::traces_paths(t.kind));
+                if (p.sun) {
+                    CHECK(i < ps.size() && ps[i].kind == vrt::kStepSunRays && ps[i].launch == t.launch);
+                    i++;
+                }
+            } else {
+                CHECK(t.kind == s.kind && !vrt::traces_paths(t.kind));
+            }
+        }
+        CHECK(i == ps.size());
+        frames++;
+        launches += (long)ps.size();
+    }
+    std::printf("check_water_plan: ok (%ld water frames, %ld launches)\n", frames, launches);
+}
+
 int main() {
     long compared[3][4] = {}, skipped = 0;
     const uint32_t flag_sets[4] = {0u, VRT_RENDER_OWN_STREAMS, VRT_RENDER_ACCUMULATE, VRT_RENDER_OWN_STREAMS | VRT_RENDER_ACCUMULATE};
@@ -484,5 +553,6 @@ int main() {
     check_sun_frames();
     check_lamp_frames();
     check_lens_frames();
+    check_water_frames();
     return 0;
 }

@@ -111,6 +111,14 @@ class SunLight(C.Structure):
     _fields_ = [("strength", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 2)]
 
 
+class WaterOptics(C.Structure):
+    """include/vrt.h vrt_water_optics: the path trace's water (vrt_set_water_optics)"""
+    _fields_ = [("absorb", C.c_float * 3), ("reflectance", C.c_float), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
+
+
+WATER_ON = 1   # vrt_water_optics.flags (VRT_WATER_ON)
+
+
 class CameraSampling(C.Structure):
     """include/vrt.h vrt_camera_sampling: the path trace's pixel jitter and thin lens (vrt_set_camera_sampling)"""
     _fields_ = [("pixel_spread", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32)]
@@ -265,6 +273,7 @@ VRT_SYMBOLS = {
     "vrt_get_tone_info": (C.c_int, [_P, C.POINTER(ToneInfo)]),
     "vrt_read_tone_histogram": (C.c_int, [_P, _P]),
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
+    "vrt_set_water_optics": (C.c_int, [_P, C.POINTER(WaterOptics)]),
     "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
     "vrt_set_lamp_light": (C.c_int, [_P, C.POINTER(LampLight)]),
     "vrt_get_lamp_info": (C.c_int, [_P, C.POINTER(LampInfo)]),
@@ -470,6 +479,7 @@ VRTH_SYMBOLS = {
     "vrth_lens_ray": (C.c_int, [_P, _I32P, C.POINTER(CameraSampling), C.c_uint32, C.c_uint32, _P, _P]),
     "vrth_tone_meter": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(ToneMap), C.c_int, C.c_float, C.POINTER(ToneInfo), _P]),
     "vrth_tone_map": (C.c_int, [_P, C.c_uint64, C.POINTER(ToneMap), C.c_float, _P]),
+    "vrth_water_transmittance": (C.c_int, [_P, _P, C.c_uint64, _P]),
 }
 
 # Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)
@@ -527,4 +537,15 @@ def tone_map(rgb, opts: ToneMap, exposure: float) -> np.ndarray:
     out = np.empty_like(rgb)
     if host().vrth_tone_map(rgb.ctypes.data, rgb.size, C.byref(opts), float(exposure), out.ctypes.data):
         raise ValueError("tone_map: a setting vrt_set_tone_map refuses")
+    return out
+
+
+def water_transmittance(absorb, dist) -> np.ndarray:
+    """vrth_water_transmittance: vexp_neg(absorb * dist) elementwise (f32, broadcast against each other), in the text the water
+    kernels compile (csrc/both/water_math.h) — the factor vrt_set_water_optics puts on a wet segment's throughput."""
+    a, d = np.broadcast_arrays(np.asarray(absorb, dtype=np.float32), np.asarray(dist, dtype=np.float32))
+    a, d = np.ascontiguousarray(a), np.ascontiguousarray(d)
+    out = np.empty(a.shape, dtype=np.float32)
+    if host().vrth_water_transmittance(a.ctypes.data, d.ctypes.data, a.size, out.ctypes.data):
+        raise ValueError("vrth_water_transmittance refused the arguments")
     return out

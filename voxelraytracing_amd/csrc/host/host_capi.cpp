@@ -14,6 +14,7 @@
 #include "../both/lens_math.h"
 #include "../both/shape_math.h"
 #include "../both/tone_math.h"
+#include "../both/water_math.h"
 #include "collide.hpp"
 #include "edit_check.hpp"
 #include "graphics.hpp"
@@ -727,3 +728,11 @@ int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, flo
 }
 
 }  // extern "C"
+
+// vrt_set_water_optics' transmittance of n segments: csrc/both/water_math.h's vexp_neg of the binary32 product absorb * dist, the
+// text and the product the water kernels compile
+int vrth_water_transmittance(const float *absorb, const float *dist, uint64_t n, float *out) {
+    if (!absorb || !dist || !out) return -1;
+    for (uint64_t i = 0; i < n; i++) out[i] = vrt::vexp_neg(absorb[i] * dist[i]);
+    return 0;
+}

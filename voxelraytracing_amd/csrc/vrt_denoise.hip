@@ -18,6 +18,7 @@
 // both/denoise_math.h's, the text libvrt_host.so's vrth_denoise compiles too.
 #include "vrt_ctx.h"
 #include "vrt_march.h"
+#include "vrt_water.h"
 #include "both/denoise_math.h"
 
 namespace vrt {
@@ -41,6 +42,34 @@ __global__ void __launch_bounds__(256) denoise_guide_kernel(FrameParams P, uint3
     V3 origin, dir;
     create_ray(P, (int)px, (int)py, origin, dir);
     const MarchResult R = march<MARCH, false, false, true>(P, nullptr, s_liquid, origin, dir);
+    uint32_t id = 0u;
+    if (R.hit) id |= VRT_ID_HIT;
+    if (R.norm.x != 0.0f) id |= VRT_ID_NX;
+    if (R.norm.y != 0.0f) id |= VRT_ID_NY;
+    if (R.norm.z != 0.0f) id |= VRT_ID_NZ;
+    guide[py * P.width + px] = denoise_filterable(id) ? denoise_guide(R.pos.x, R.pos.y, R.pos.z, id) : 0u;
+}
+
+// ... of a frame with vrt_set_water_optics on: the primary ray marched as path_water_primary_kernel marches it — with the empty
+// liquid set when the camera is not in a liquid, so that the guide of a pixel that sees a lake is the water face's plane, as its
+// id word is the water voxel's
+template <int MARCH>
+__global__ void __launch_bounds__(256) denoise_guide_water_kernel(FrameParams P, FrameParams D, uint32_t *guide) {
+    __shared__ uint32_t smem[32];
+    uint32_t *s_liquid = smem, *s_dry = smem + 24;
+    if (threadIdx.x < 8) s_dry[threadIdx.x] = 0u;
+    stage_lds(P, nullptr, s_liquid, false);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= P.tiles_total) return;
+    uint32_t px, py;
+    tile_pixel(P, tile, lane, px, py);
+    V3 origin, dir;
+    create_ray(P, (int)px, (int)py, origin, dir);
+    const bool wet = __builtin_amdgcn_readfirstlane((uint32_t)is_liquid(s_liquid, water_voxel_at(P, origin))) != 0u;
+    MarchResult R;
+    if (wet) R = march<MARCH, false, false, true>(P, nullptr, s_liquid, origin, dir);
+    else R = march<MARCH, false, false, true>(D, nullptr, s_dry, origin, dir);
     uint32_t id = 0u;
     if (R.hit) id |= VRT_ID_HIT;
     if (R.norm.x != 0.0f) id |= VRT_ID_NX;
@@ -136,8 +165,15 @@ __global__ void __launch_bounds__(256) denoise_pass_kernel(DenoisePass D) {
     D.out[p] = t;
 }
 
-void launch_denoise_guide(const FrameParams &P, bool literal, uint32_t *guide, hipStream_t st) {
+void launch_denoise_guide(const FrameParams &P, bool literal, bool water, uint32_t *guide, hipStream_t st) {
     const dim3 grid((P.tiles_total + 3u) / 4u), block(256);
+    if (water) {   // vrt_set_water_optics
+        const FrameParams D = dry_params(P);
+        if (literal) hipLaunchKernelGGL(denoise_guide_water_kernel<1>, grid, block, 0, st, P, D, guide);
+        else if (P.grid) hipLaunchKernelGGL(denoise_guide_water_kernel<0>, grid, block, 0, st, P, D, guide);
+        else hipLaunchKernelGGL(denoise_guide_water_kernel<2>, grid, block, 0, st, P, D, guide);
+        return;
+    }
     if (literal) hipLaunchKernelGGL(denoise_guide_kernel<1>, grid, block, 0, st, P, guide);
     else if (P.grid) hipLaunchKernelGGL(denoise_guide_kernel<0>, grid, block, 0, st, P, guide);
     else hipLaunchKernelGGL(denoise_guide_kernel<2>, grid, block, 0, st, P, guide);
@@ -178,7 +214,7 @@ int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, const vrt::FrameP
                         hipEvent_t closing) {
     const uint32_t passes = c->denoise.passes;
     if (!passes || !c->tiles_total) return VRT_OK;
-    vrt::launch_denoise_guide(P, plan.literal, c->sz.dn_guide[slot], st);
+    vrt::launch_denoise_guide(P, plan.literal, c->water.flags != 0u && c->settings.max_ray_bounces > 0u, c->sz.dn_guide[slot], st);
     HIP_TRY(c, hipGetLastError());
     vrt::Texel *a = (passes & 1u) ? c->sz.dn_scratch[slot] : frame_out, *b = (passes & 1u) ? frame_out : c->sz.dn_scratch[slot];
     for (uint32_t i = 0; i < passes; i++) {

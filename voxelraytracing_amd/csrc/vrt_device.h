@@ -207,6 +207,16 @@ struct LampLaunch {
     uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun term, and the later misses' sky without the disc
 };
 
+// vrt_set_water_optics (vrt_path_water.h): what the kernels of a water frame are given besides FrameParams and a SunLaunch (whose
+// buffers are null and whose k is 0 when the sun is off).  The table's liquid set stays FrameParams' own; the empty one a dry
+// segment is marched with is a constant of the kernels
+struct WaterLaunch {
+    float absorb[3];      // the setting
+    float reflectance;
+    uint32_t lobes;       // kSunLobePolish | kSunLobeTranslucent, as SunLaunch::lobes
+    uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun term, and the later misses' sky without the disc
+};
+
 // vrt_set_tone_map: what the blit of a mapped frame is given besides the unmapped blit's arguments (both/tone_math.h's
 // ToneCurve, flat).  E_dev: the frame set's exposure word on the device (a metered frame: nothing of it comes back to the host);
 // null: E, the setting's own

@@ -363,6 +363,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
         M.max_geometry = c->lamp.max_geometry;
         M.sun = plan.sun ? 1u : 0u;
     }
+    // vrt_set_water_optics: the setting as the kernels of vrt_path_water.h take it
+    const vrt::WaterLaunch W{{c->water.absorb[0], c->water.absorb[1], c->water.absorb[2]}, c->water.reflectance, lobes, plan.sun ? 1u : 0u};
     // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
     const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance, lobes};
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
@@ -422,6 +424,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             case kStepLampPrimary: launch_path_primary_lamp(P, L, S, M, plan.lens, plan.kstats, plan.literal, f.st); break;
             case kStepLampBounce: launch_path_bounce_lamp(P, S, M, plan.kstats, plan.literal, f.st); break;
             case kStepLampRays: launch_path_lamp_rays(P, M, plan.kstats, plan.literal, f.st); break;
+            case kStepWaterPrimary: launch_path_primary_water(P, W, S, plan.kstats, plan.literal, f.st); break;
+            case kStepWaterBounce: launch_path_bounce_water(P, W, S, plan.kstats, plan.literal, f.st); break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -688,6 +692,12 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         return fail(c, VRT_ERR_STATE, "vrt_render: materials[0].is_liquid == 1 (air flagged liquid) is traced by the literal march only");
     // vrt_set_lamp_light: a lamp-lit path frame reads the derived tables for its lamp list, whatever it marches with
     const bool lamp_lit = o.mode == VRT_MODE_PATH && c->lamp.strength != 0.0f && c->settings.max_ray_bounces > 0u;
+    // vrt_set_water_optics: a water frame's kernels have no lamp term and no lens (include/vrt.h); refused before anything is enqueued
+    const bool water_frame = o.mode == VRT_MODE_PATH && c->water.flags != 0u && c->settings.max_ray_bounces > 0u;
+    if (water_frame && c->lamp.strength != 0.0f)
+        return fail(c, VRT_ERR_STATE, "vrt_render: water optics (vrt_set_water_optics) and lamp light (vrt_set_lamp_light) do not compose yet");
+    if (water_frame && (c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f))
+        return fail(c, VRT_ERR_STATE, "vrt_render: water optics (vrt_set_water_optics) and camera sampling (vrt_set_camera_sampling) do not compose yet");
     if (vrt::asks_for_tables(F) || lamp_lit) {
         VRT_PROF(9, "  ensure_accel_world");
         VRT_TRY(ensure_accel_world(c));
@@ -753,7 +763,8 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         }
     }
     // what reads the node pool and chunk_roots: uploads then wait for the frames in flight
-    if (!P.grid || plan.walks_octree) c->walkers_in_flight = true;
+    // (a water frame's kernels read chunk_roots for the voxel a segment starts in: vrt_water.h)
+    if (!P.grid || plan.walks_octree || water_frame) c->walkers_in_flight = true;
     P.out = f.out;
     P.hits = c->sz.d_hits;
     P.blk_counts = f.blk;
@@ -814,6 +825,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.accum = accum; PF.accum_from = accum_from; PF.emissive = c->n_emissive != 0u; PF.polished = c->n_polished != 0u; PF.translucent = c->n_translucent != 0u;
             PF.sun = c->sun.strength != 0.0f;
             PF.lamp = c->lamp.strength != 0.0f;
+            PF.water = c->water.flags != 0u;
             PF.camera_sampling = c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
@@ -859,6 +871,29 @@ int vrt_set_sun_light(vrt_ctx *c, const vrt_sun_light *opts) {
     if (o.strength == 0.0f) memset(&o, 0, sizeof o);   // (-0: off is 16 zero bytes)
     if (memcmp(&c->sun, &o, sizeof o) != 0) c->accum_restart = true;
     c->sun = o;
+    return VRT_OK;
+}
+
+int vrt_set_water_optics(vrt_ctx *c, const vrt_water_optics *opts) {
+    if (!c) return VRT_ERR_INVALID_ARG;
+    vrt_water_optics o;
+    memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if (o.flags & ~VRT_WATER_ON) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_optics: flags %#x (0 or VRT_WATER_ON)", o.flags);
+    if (o._reserved[0] || o._reserved[1] || o._reserved[2]) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_optics: _reserved must be 0");
+    for (float a : o.absorb)   // (checked whatever the flags say)
+        if (!(a >= 0.0f) || std::isinf(a))
+            return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_optics: absorb %g %g %g (each finite and >= 0)", (double)o.absorb[0], (double)o.absorb[1],
+                        (double)o.absorb[2]);
+    if (!(o.reflectance >= 0.0f && o.reflectance <= 1.0f))
+        return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_optics: reflectance %g (in [0, 1])", (double)o.reflectance);
+    GRP_EACH(c, vrt_set_water_optics(d, opts));
+    // what is kept: off is 32 zero bytes, -0 is +0
+    if (!o.flags) memset(&o, 0, sizeof o);
+    for (float &a : o.absorb) if (a == 0.0f) a = 0.0f;
+    if (o.reflectance == 0.0f) o.reflectance = 0.0f;
+    if (memcmp(&c->water, &o, sizeof o) != 0) c->accum_restart = true;
+    c->water = o;
     return VRT_OK;
 }
 

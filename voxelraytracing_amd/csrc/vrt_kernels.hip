@@ -20,6 +20,7 @@
 
 #include "vrt_tile.h"
 #include "both/tone_math.h"   // (the mapped blits: vrt_set_tone_map)
+#include "both/water_math.h"  // (vrt_selftest_math_values: vrt_set_water_optics' transmittance)
 #include "vrt_path_common.h"   // (vrt_selftest_exact_math: the RNG's logarithm and direction, both forms)
 
 namespace vrt {
@@ -898,7 +899,7 @@ __global__ void selftest_exact_math_kernel(uint32_t n, uint32_t seed, unsigned l
 struct MathWords { uint8_t in, out; };
 constexpr MathWords kMathWords[VRT_MATH_OPS] = {
     {2, 1}, {1, 1}, {3, 4}, {3, 4}, {2, 2}, {1, 2}, {1, 2}, {1, 2}, {1, 1}, {1, 1}, {1, 1}, {1, 5},
-    {1, 1}, {1, 1}, {2, 1}, {3, 1}, {3, 1}, {3, 1}, {2, 4}, {3, 1}, {3, 1}};
+    {1, 1}, {1, 1}, {2, 1}, {3, 1}, {3, 1}, {3, 1}, {2, 4}, {3, 1}, {3, 1}, {2, 1}};
 
 template <uint32_t OP>
 __global__ void __launch_bounds__(256) selftest_math_values_kernel(uint32_t n, const uint32_t *in, uint32_t *out) {
@@ -972,6 +973,8 @@ __global__ void __launch_bounds__(256) selftest_math_values_kernel(uint32_t n, c
         put(0, low_bits_of<3u>(a, b)); put(1, low_bits_of<7u>(a, b)); put(2, low_bits_of<15u>(a, b)); put(3, low_bits_of<31u>(a, b));
     } else if constexpr (OP == VRT_MATH_OR_AND) {
         put(0, or_and(U(0), U(1), U(2)));
+    } else if constexpr (OP == VRT_MATH_EXP_NEG) {
+        putf(0, vexp_neg(F(0) * F(1)));   // (the product is the kernels': absorb * water_dist)
     } else {
         static_assert(OP == VRT_MATH_MAD_I24, "an op of include/vrt.h");
         // (the second factor is wave-uniform in the march — a scalar operand: the wave's is its first set's.  A scalar register that a

@@ -29,6 +29,7 @@
 #include "vrt_path_sun.h"
 #include "vrt_path_lens.h"
 #include "vrt_path_lamp.h"   // (vrt_set_lamp_light: kernels of their own, behind everything they share with the others)
+#include "vrt_path_water.h"  // (vrt_set_water_optics: a pair of their own again)
 
 namespace vrt {
 
@@ -292,6 +293,28 @@ void launch_path_lamp_rays(const FrameParams &P, const LampLaunch &M, bool stats
     with_march_build(P, stats, literal, [&](auto build, size_t sh) {
         using B = decltype(build);
         hipLaunchKernelGGL((path_lamp_rays_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh, st, P, M);
+    });
+}
+
+// vrt_set_water_optics (vrt_path_water.h): a water frame is one lane = path launch per segment, as a sun-lit one; each is followed by
+// the sun launch if the sun is on as well (S then has buffers).  Its LDS holds the empty liquid set besides the table's
+void launch_path_primary_water(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_tiles(P), block(256);
+    const FrameParams D = dry_params(P);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_water_primary_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S);
+    });
+}
+
+void launch_path_bounce_water(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_records(P.hit_seg_cap), block(256);
+    const FrameParams D = dry_params(P);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_water_bounce_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S);
     });
 }
 

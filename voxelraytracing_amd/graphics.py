@@ -84,7 +84,7 @@ MATH_OPS = {name: (op, n_in, n_out) for op, (name, n_in, n_out) in enumerate([
     ("div", 2, 1), ("sqrt", 1, 1), ("unit_steps", 3, 4), ("normalize", 3, 4), ("lens_div", 2, 2), ("lens_sqrt", 1, 2),
     ("rng_next", 1, 2), ("rng_next_u2", 1, 2), ("log_banded", 1, 1), ("log_general", 1, 1), ("cos2pi", 1, 1), ("rng_dir", 1, 5),
     ("trunc2i", 1, 1), ("flr2i", 1, 1), ("abs_mul", 2, 1), ("min3_f32", 3, 1), ("min3_bits", 3, 1), ("bfi", 3, 1),
-    ("low_bits", 2, 4), ("or_and", 3, 1), ("mad_i24", 3, 1)])}
+    ("low_bits", 2, 4), ("or_and", 3, 1), ("mad_i24", 3, 1), ("exp_neg", 2, 1)])}
 
 
 def selftest_math_values(op: str, *words, device: int = 0) -> np.ndarray:
@@ -273,6 +273,19 @@ class Gpu:
         modes ignore it; changing it restarts the accumulation."""
         o = _ffi.SunLight(strength, 0, (C.c_uint32 * 2)(0, 0))
         self._ck(self._lib.vrt_set_sun_light(self._h, C.byref(o)))
+
+    def set_water_optics(self, absorb=None, reflectance: float = 0.0):
+        """vrt_set_water_optics: later MODE_PATH frames see water — a segment that starts outside a liquid stops at a liquid voxel
+        and is reflected with Schlick's probability (reflectance: at normal incidence, in [0, 1]) or goes on into it; a segment
+        that starts inside one loses exp(-absorb * length in the liquid) per channel (absorb: three floats per voxel length, or
+        one for all three).  absorb None = off, the default.  The primary modes ignore it; changing it restarts the accumulation.
+        Not yet together with set_lamp_light or set_camera_sampling: such a frame is refused."""
+        if absorb is None:
+            self._ck(self._lib.vrt_set_water_optics(self._h, None))
+            return
+        a = np.broadcast_to(np.asarray(absorb, dtype=np.float32), (3,))
+        o = _ffi.WaterOptics((C.c_float * 3)(*(float(x) for x in a)), reflectance, _ffi.WATER_ON, (C.c_uint32 * 3)(0, 0, 0))
+        self._ck(self._lib.vrt_set_water_optics(self._h, C.byref(o)))
 
     def set_camera_sampling(self, pixel_spread: float, aperture: float = 0.0, focus_distance: float = 0.0):
         """vrt_set_camera_sampling: every sample of a later MODE_PATH frame gets a primary ray of its own — through a point of
