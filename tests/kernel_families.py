@@ -6,10 +6,16 @@ the word the family's kernels had in their names while each family was a set of 
     path_bounce_kernel<MARCH, LDS_ROOTS, STATS, EMIT, POLISH, TRANSLUCENT, SUN...>(FrameParams, SUN...)
     path_bounce_cells_kernel<DIRECT, KB, EMIT, POLISH, TRANSLUCENT>(CellsLaunch)
     path_lens_primary_kernel<MARCH, LDS_ROOTS, STATS, MULTI, SUN...>(FrameParams, LensLaunch, SUN...)
+
+and the pair of a water frame, a family of its own ("water") whose lobes and sun are read from the launch:
+
+    path_water_primary_kernel<MARCH, LDS_ROOTS, STATS>(FrameParams, FrameParams, WaterLaunch, SunLaunch)
+    path_water_bounce_kernel<MARCH, LDS_ROOTS, STATS>(FrameParams, FrameParams, WaterLaunch, SunLaunch)
 """
 import re
 
 _SYMBOL = re.compile(r"^_ZN3vrt\d+path_(primary|bounce|bounce_cells|lens_primary)_kernelI((?:L[ibj]\d+E)+)(?:J(NS_9SunLaunchE)?E)?EEv")
+_WATER = re.compile(r"^_ZN3vrt\d+path_water_(primary|bounce)_kernelI(Li\dELb\dELb\dE)EEv")
 _FLAGS = {"primary": ("multi", "emit", "polish", "translucent"), "bounce": ("emit", "polish", "translucent"),
           "bounce_cells": ("emit", "polish", "translucent"), "lens_primary": ("multi",)}
 
@@ -32,9 +38,25 @@ def path_kernel(symbol):
     return k
 
 
+def water_kernel(symbol):
+    """None, or {"template": "water_primary" | "water_bounce", "build", "march", "lds_roots", "stats"} of a symbol of the water pair."""
+    m = _WATER.match(symbol)
+    if not m:
+        return None
+    march, roots, stats = re.findall(r"L[ib](\d)E", m.group(2))
+    return {"template": "water_" + m.group(1), "build": m.group(2), "march": int(march), "lds_roots": roots == "1", "stats": stats == "1"}
+
+
+# the march builds vrt_path.hip's with_march_build chooses between: the grid march (0) never stages the root table in LDS, the
+# literal march (1) and the octree walk (2) do where it fits; each counting (STATS) and not
+MARCH_BUILDS = tuple(f"Li{m}ELb{r}ELb{s}E" for m, roots in ((0, (0,)), (1, (0, 1)), (2, (0, 1))) for r in roots for s in (0, 1))
+
+
 def families(symbol):
     """The families a kernel is counted in: "polished", "translucent", "sunlit" (the trace kernels that take a SunLaunch behind
-    FrameParams alone), "emissive" (the pool kernel with the emission term and no lobe besides), "lens"."""
+    FrameParams alone), "emissive" (the pool kernel with the emission term and no lobe besides), "lens"; "water": the water pair."""
+    if water_kernel(symbol) is not None:
+        return frozenset({"water"})
     k = path_kernel(symbol)
     if k is None:
         return frozenset()

@@ -7,6 +7,7 @@ import os
 import re
 import subprocess
 
+from kernel_families import MARCH_BUILDS, families, in_family, path_kernel, water_kernel
 from voxelraytracing_amd import _ffi, graphics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,3 +86,21 @@ def test_the_water_kernels_are_a_pair_of_their_own_without_scratch():
     assert forms == sorted(f"Li{m}ELb{r}ELb{s}E" for m, rs in ((0, (0,)), (1, (0, 1)), (2, (0, 1))) for r in rs for s in (0, 1))
     bad = {k: v for k, v in water.items() if v["scratch_bytes"] or v["sgpr_spills"] or v["vgpr_spills"]}
     assert not bad, bad
+
+
+def test_the_library_holds_exactly_the_ten_march_builds_of_each_water_kernel():
+    """Three marches x the root table in LDS where it applies x counting, as vrt_path.hip's with_march_build enumerates them: a
+    dropped instantiation fails here, where the library is inspected, and not as a missing kernel on some route on the GPU."""
+    assert len(MARCH_BUILDS) == 10 and len(set(MARCH_BUILDS)) == 10
+    regs = _ffi.kernel_registers()
+    water = {k: water_kernel(k) for k in regs if in_family(k, "water")}
+    assert len(water) == 20 and all(families(k) == {"water"} and path_kernel(k) is None for k in water)
+    for template in ("water_primary", "water_bounce"):
+        builds = sorted(w["build"] for w in water.values() if w["template"] == template)
+        assert builds == sorted(MARCH_BUILDS), (template, builds)
+    # every symbol that names a water trace kernel is recognised, and no other kernel is counted in the family
+    assert set(water) == {k for k in regs if "path_water_" in k}
+    assert {(w["march"], w["lds_roots"]) for w in water.values()} == {(0, False), (1, False), (1, True), (2, False), (2, True)}
+    for sym, fam in (("_ZN3vrt24path_water_bounce_kernelILi2ELb1ELb0EEEvNS_11FrameParamsES1_NS_11WaterLaunchENS_9SunLaunchE", {"water"}),
+                     ("_ZN3vrt26denoise_guide_water_kernelILi2EEEvNS_11FrameParamsES1_NS_11GuideLaunchE", set())):
+        assert families(sym) == fam, sym

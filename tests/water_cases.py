@@ -1,15 +1,22 @@
-"""The scenes of the water tests (tests/test_water_ref.py, tests/test_gpu_water.py): a hand-built pool in a 2^3-chunk world and
-C4's scene from its two lake cameras.  TEST INFRASTRUCTURE ONLY.
+"""The scenes of the water tests (tests/test_water_ref.py, tests/test_water_cases.py, tests/test_gpu_water.py,
+tests/test_gpu_water_edges.py): a hand-built pool in a 2^3-chunk world, the same pool with half of its water a second liquid whose
+id is above 255, and C4's scene from its two lake cameras.  TEST INFRASTRUCTURE ONLY.
 
 The pool: a slate floor (id 5) to y = 8 over the whole world; on it a basin with walls one voxel thick around x, z in [20, 44),
 three voxels deep in water (id 3, y = 9, 10, 11: the surface is the plane y = 12, the walls' tops too); a slate pillar at
-x, z in [30, 32) from the bed to y = 15, through the surface."""
+x, z in [30, 32) from the bed to y = 15, through the surface.
+
+"Two liquids": the basin's half x in [32, 44) holds voxel id 300 in water's place.  Ids >= 255 share material entry 255; with
+materials[255].is_liquid = 1 the liquid set is {3, 255} — not one id range, and 255 in it — and the body of water has a
+liquid-to-liquid boundary at x = 32; with is_liquid = 0 the half is a solid block with an id above 255, seen through water."""
 import numpy as np
 
 from voxelraytracing_amd import graphics as g, scenes
 from voxelraytracing_amd.world import ClientWorld
 
 WATER, SLATE = 3, 5
+OTHER = 300                        # the two-liquids world's second id: material entry 255
+OTHER_X0 = 32                      # ... fills the basin's x in [32, 44)
 FLOOR_TOP, DEPTH = 9, 3            # the bed is the plane y = 9; water fills y in [9, 12)
 SURFACE = FLOOR_TOP + DEPTH
 X0, X1 = 20, 44                    # the water's x and z extent; the walls are the voxels around it
@@ -22,60 +29,125 @@ SEED = 11
 OPTICS = ((0.30, 0.12, 0.05), 0.04)   # (absorb, reflectance): red goes first; a little more mirror than real water's 0.02
 
 # name -> (eye, rot): across the surface at a grazing angle; straight down from above the middle of one half of the basin; from
-# inside the water down at the bed; from inside the water up and out through the surface
+# inside the water down at the bed; from inside the water up and out through the surface; straight down from inside the world
+# box in a chunk the generator left out (chunk_roots holds 0 for it: 1819 water pixels at 128 x 72); from inside the water of
+# the basin's low-x half across at the other half (the two-liquids worlds: 1688 pixels of id 300 through water at 128 x 72)
 CAMERAS = {
     "grazing": ((12.5, 13.5, 32.5), (6.0, 270.0, 0.0)),
     "down": ((37.5, 20.5, 37.5), (90.0, 0.0, 0.0)),
     "under_bed": ((37.5, 11.5, 37.5), (60.0, 30.0, 0.0)),
     "under_up": ((37.5, 10.5, 37.5), (-50.0, 200.0, 0.0)),
+    "above": ((37.5, 40.5, 37.5), (90.0, 0.0, 0.0)),
+    "across": ((25.5, 10.5, 25.5), (10.0, 315.0, 0.0)),
 }
 
-_world = None
+_worlds = {}
+
+
+def _build(other: int) -> ClientWorld:
+    """The pool's world built by set_voxel (2^3 chunks, world.min = (0, 0, 0)); other: the id of the basin's x >= OTHER_X0 half."""
+    w = ClientWorld((1, 1, 1), 1 << 20, 2)
+    w.generate(1, 0)   # Superflat, as C1's world: every chunk exists
+    n = 64
+    # clear what the generator put there, then build (whole columns: the generator's ground is replaced)
+    for x in range(n):
+        for z in range(n):
+            for y in range(0, 32):   # (the chunks above hold nothing: Superflat leaves them out, chunk_roots 0)
+                inside = X0 <= x < X1 and X0 <= z < X1
+                wall = (X0 - 1 <= x <= X1 and X0 - 1 <= z <= X1) and not inside
+                pillar = PILLAR[0] <= x < PILLAR[1] and PILLAR[0] <= z < PILLAR[1]
+                if y < FLOOR_TOP:
+                    v = SLATE
+                elif pillar and y < 16:
+                    v = SLATE
+                elif y < SURFACE and inside:
+                    v = other if x >= OTHER_X0 else WATER
+                elif y < SURFACE and wall:
+                    v = SLATE
+                else:
+                    v = 0
+                if w.get_voxel((x, y, z)) != v:
+                    w.set_voxel((x, y, z), v)
+    return w
 
 
 def pool_world() -> ClientWorld:
-    """The pool's world, built once by set_voxel (2^3 chunks, world.min = (0, 0, 0))."""
-    global _world
-    if _world is None:
-        w = ClientWorld((1, 1, 1), 1 << 20, 2)
-        w.generate(1, 0)   # Superflat, as C1's world: every chunk exists
-        n = 64
-        # clear what the generator put there, then build (whole columns: the generator's ground is replaced)
-        for x in range(n):
-            for z in range(n):
-                for y in range(0, 32):   # (the chunks above hold nothing: Superflat leaves them out, chunk_roots 0)
-                    inside = X0 <= x < X1 and X0 <= z < X1
-                    wall = (X0 - 1 <= x <= X1 and X0 - 1 <= z <= X1) and not inside
-                    pillar = PILLAR[0] <= x < PILLAR[1] and PILLAR[0] <= z < PILLAR[1]
-                    if y < FLOOR_TOP:
-                        v = SLATE
-                    elif pillar and y < 16:
-                        v = SLATE
-                    elif y < SURFACE and inside:
-                        v = WATER
-                    elif y < SURFACE and wall:
-                        v = SLATE
-                    else:
-                        v = 0
-                    if w.get_voxel((x, y, z)) != v:
-                        w.set_voxel((x, y, z), v)
-        _world = w
-    return _world
+    """The pool's world, built once."""
+    if "pool" not in _worlds:
+        _worlds["pool"] = _build(WATER)
+    return _worlds["pool"]
 
 
-def pool(camera: str, size, bounces=4) -> "scenes.Scene":
+def fresh_pool_world() -> ClientWorld:
+    """A pool world of the caller's own, for tests that edit it."""
+    return _build(WATER)
+
+
+def two_liquids_world() -> ClientWorld:
+    """The two-liquids world, built once: a world of its own, not the pool's edited."""
+    if "two" not in _worlds:
+        _worlds["two"] = _build(OTHER)
+    return _worlds["two"]
+
+
+def pool(camera: str, size, bounces=4, world=None) -> "scenes.Scene":
     eye, rot = CAMERAS[camera]
-    sc = scenes._scene(f"pool {camera} {size[0]}x{size[1]}", pool_world(), size, eye, rot, g.MODE_PATH)
+    sc = scenes._scene(f"pool {camera} {size[0]}x{size[1]}", world if world is not None else pool_world(), size, eye, rot, g.MODE_PATH)
     sc.settings.max_ray_bounces = bounces
     scenes._diffuse(sc.materials)
     return sc
 
 
+def two_liquids(camera: str, size, bounces=4, liquid=True) -> "scenes.Scene":
+    """The two-liquids world; liquid: materials[255].is_liquid (entry 255 otherwise as the pack has it: not empty, so that a
+    voxel of it is a voxel)."""
+    sc = pool(camera, size, bounces, two_liquids_world())
+    sc.name = f"two liquids {'liquid' if liquid else 'solid'} {camera} {size[0]}x{size[1]}"
+    m = sc.materials[255]
+    m.is_empty = 0
+    m.is_liquid = 1 if liquid else 0
+    m.color[0], m.color[1], m.color[2] = 0.2, 0.7, 0.4
+    return sc
+
+
+def liquid_ids(materials) -> list:
+    """The material entries flagged liquid."""
+    return [i for i in range(256) if materials[i].is_liquid == 1]
+
+
+def is_one_range_below_255(ids) -> bool:
+    """What the uploads ask before they hand the march a liquid set as a range: no liquid, or contiguous ids without entry 255."""
+    return not ids or (ids[-1] - ids[0] + 1 == len(ids) and ids[-1] < 255)
+
+
 def c4_lake(camera: str, size=(128, 72), bounces=4) -> "scenes.Scene":
     """C4's scene from tests/golden/make_wgsl_fixtures.py's lake cameras: "water" (c2_water_40x24: just above the lake) or
-    "underwater" (c2_underwater_24x16: the eye inside it)."""
-    eye, rot = {"water": ((24.5, 76.5, 84.5), (30.0, 150.0, 0.0)), "underwater": ((22.5, 55.5, 80.5), (-20.0, 40.0, 0.0))}[camera]
+    "underwater" (c2_underwater_24x16: the eye inside it); "water down": from the first one's eye steeply down at the lake, so that
+    every primary ray ends in a surface event."""
+    eye, rot = {"water": ((24.5, 76.5, 84.5), (30.0, 150.0, 0.0)), "underwater": ((22.5, 55.5, 80.5), (-20.0, 40.0, 0.0)),
+                "water down": ((24.5, 76.5, 84.5), (75.0, 330.0, 0.0))}[camera]
     sc = scenes.c4(size, bounces=bounces)
     sc.cam = g.cam_data_create(rot, eye, 70.0, (float(size[0]), float(size[1])))
     sc.eye, sc.rot = eye, rot
     return sc
+
+
+# The water frames past 256 primary workgroups (tests/test_gpu_water_edges.py): tests/segment_cases.py's sizes, each from a lake
+# camera.  Measured by tests/test_water_cases.py from the reference's load planes at 4 bounces, 1 spp, the sun on:
+#
+#   case             camera       bounce segments  surface events  sun rays  wet bounce segments
+#   one_over         water down           145 343          66 016    58 522              139 825
+#   one_over_ragged  water down           145 414          66 053    58 975              139 857
+#   three_parts      water                319 558         104 288   124 149              222 593
+#   four_parts       water                456 677         179 876   140 675              300 357
+#
+# one_over, one_over_ragged: segment 0 alone has a second producer — the frame's top-left four tiles and its last one.  From
+#   "water" (143 743 / 50 262 / 51 678 / 100 362 at 328 x 200) those tiles' primary rays end on the lake, which sends no sun ray,
+#   and the fullest sun segment of any launch holds 224 records; so these two look down.  Every primary ray is then a surface
+#   event: segment 0 hands the second launch 320 paths and the third 293 (296), and the second launch appends 285 sun rays to it (294
+#   in the ragged frame); 62 792 second segments start wet and 2808 dry, 960 tiles (977) hold both kinds.
+# three_parts: the second launch reads 768 paths of a segment (all 256 segments over 256, four over 512), the third 671, the
+#   fourth 450; the second launch appends up to 462 sun rays to a segment (62 segments over 256); 1365 tiles hold both kinds.
+# four_parts: 1024, 994 and 682 paths (195 segments over 512); 296 sun rays of a segment from the primary launch, 650 from the
+#   second (24 segments over 512), 383 from the third; 2503 tiles hold both kinds.
+SEGMENT_CASES = {"one_over": "water down", "one_over_ragged": "water down", "three_parts": "water", "four_parts": "water"}

@@ -37,6 +37,11 @@ typedef struct {   /* include/vrt.h: vrt_water_optics */
 enum { N_STEPS, N_BOUNCE_SEGMENTS, N_SUN_RAYS, N_SUN_UNOCCLUDED, N_SURFACE, N_REFLECTED, N_TRANSMITTED, N_WET_W, N_WET_HIT, N_WET_PRIMARY_W,
        N_WET_BOUNCES, N_PASSES, N_POLISHED, N_COUNTS };
 
+/* what segment b of a sample hands to the launches behind it, where the caller asks for load planes (tests/path_ref.c's LOAD_
+ * bits, with the wet start in the lamp ray's place — a water frame has no lamp rays): the path goes on into segment b + 1 (a
+ * surface event's continuation is one); a sun ray was marched from segment b's hit; segment b started in a liquid of the table */
+enum { LOAD_PATH = 1, LOAD_SUN = 2, LOAD_WET = 4 };
+
 static float ref_exp_neg(float t) {
     if (!(t >= 0.0f)) return t != t ? t : 1.0f;
     if (t >= 128.0f) return 0.0f;
@@ -74,6 +79,8 @@ static uint32_t voxel_at_floor(const orc_scene *s, v3 o) {
     return node_voxel(node_at(s, f.root + f.idx));
 }
 
+uint32_t ref_voxel_at_floor(const orc_scene *s, float x, float y, float z) { return voxel_at_floor(s, V3(x, y, z)); }
+
 static int is_table_liquid(const orc_scene *s, uint32_t voxel) { return mat_at(s, voxel)->is_liquid == 1u; }
 
 typedef struct {
@@ -93,8 +100,10 @@ static float exit_t(float pos, float dir) {
 }
 
 /* One sample: its light; *id: the id word of its primary segment's own march; n[N_COUNTS] grows; thr_bed: NULL, or where the
- * throughput at the sample's first hit on a solid voxel at the end of a wet segment is kept (untouched if there is none). */
-static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n, float *thr_bed) {
+ * throughput at the sample's first hit on a solid voxel at the end of a wet segment is kept (untouched if there is none); load:
+ * NULL, or the sample's LOAD_ bits, segment b's at load[b * load_stride]. */
+static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, uint32_t rng, uint32_t *id, uint64_t *n, float *thr_bed, uint8_t *load,
+                           size_t load_stride) {
     const orc_scene *s = p->scene;
     const int on = p->wo->flags != 0u;
     v3 light = V3(0.0f, 0.0f, 0.0f);
@@ -112,6 +121,7 @@ static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, ui
         if (bounce == 0) *id = id_word(&rs);
         if (on && wet) {
             const float w = rs.water_dist;
+            if (load) load[bounce * load_stride] |= LOAD_WET;
             thr.x *= ref_exp_neg(p->wo->absorb[0] * w);
             thr.y *= ref_exp_neg(p->wo->absorb[1] * w);
             thr.z *= ref_exp_neg(p->wo->absorb[2] * w);
@@ -147,6 +157,7 @@ static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, ui
                 origin = rs.pos;
                 n[N_TRANSMITTED] += 1u;
             }
+            if (load) load[bounce * load_stride] |= LOAD_PATH;
             continue;
         }
         /* step 5: path_ref.c's text */
@@ -166,6 +177,7 @@ static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, ui
             if (c > 0.0f) {
                 const hit_result sh = ray_world(s, so, sd);   /* liquids passed, unattenuated */
                 n[N_SUN_RAYS] += 1u;
+                if (load) load[bounce * load_stride] |= LOAD_SUN;
                 n[N_STEPS] += sh.iter_count;
                 if (!sh.hit) {
                     const float k = s->settings.sun_intensity * p->sun_strength;
@@ -187,6 +199,7 @@ static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, ui
             thr.x *= p->tr[entry].color[0]; thr.y *= p->tr[entry].color[1]; thr.z *= p->tr[entry].color[2];
             origin = V3(rs.pos.x + dir.x * ts, rs.pos.y + dir.y * ts, rs.pos.z + dir.z * ts);
             n[N_PASSES] += 1u;
+            if (load) load[bounce * load_stride] |= LOAD_PATH;
             continue;
         }
         int polished = 0;
@@ -202,6 +215,7 @@ static v3 trace_path_water(const water_settings *p, uint32_t px, uint32_t py, ui
         origin = so;
         dir = nd;
         n[N_POLISHED] += polished ? 1u : 0u;
+        if (load) load[bounce * load_stride] |= LOAD_PATH;
     }
     return light;
 }
@@ -229,11 +243,12 @@ static water_settings settings_of(const orc_scene *scene, water_scenes *ws, cons
 
 /* A w x h frame of samples sample_base .. sample_base + spp - 1, their mean in rgb[h][w][3], the id word of the first sample's
  * primary segment in ids[h][w], counts[N_COUNTS].  Like orc_render, pixels beyond the last whole 8 x 8 tile are not traced: the
- * caller passes zeroed arrays. */
+ * caller passes zeroed arrays.  load: NULL, or load[spp][max_ray_bounces][h][w] bytes, zero on entry: the LOAD_ bits. */
 void ref_render_water(const orc_scene *scene, const float *emission, const ref_polish *polish, const ref_translucency *tr, float sun_strength,
                       const ref_water_optics *wo, uint32_t w, uint32_t h, uint32_t seed, uint32_t spp, uint32_t sample_base, float *rgb, uint32_t *ids,
-                      uint64_t *counts) {
+                      uint64_t *counts, uint8_t *load) {
     const uint32_t x1 = w & ~7u, y1 = h & ~7u, nspp = spp ? spp : 1u;
+    const size_t plane = (size_t)w * h;
     water_scenes ws;
     const water_settings p = settings_of(scene, &ws, emission, polish, tr, sun_strength, wo);
     uint64_t n[N_COUNTS] = {0};
@@ -245,7 +260,8 @@ void ref_render_water(const orc_scene *scene, const float *emission, const ref_p
             uint32_t id = 0;
             for (uint32_t sm = 0; sm < nspp; sm++) {
                 uint32_t sid = 0;
-                const v3 l = trace_path_water(&p, px, (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, NULL);
+                const v3 l = trace_path_water(&p, px, (uint32_t)py, path_seed(px, (uint32_t)py, w, h, sample_base + sm, seed), &sid, n, NULL,
+                                              load ? load + ((size_t)sm * scene->settings.max_ray_bounces) * plane + o : NULL, plane);
                 sum.x += l.x; sum.y += l.y; sum.z += l.z;
                 if (sm == 0) id = sid;
             }
@@ -267,6 +283,6 @@ void ref_trace_pixel_water(const orc_scene *scene, const float *emission, const 
     const water_settings p = settings_of(scene, &ws, emission, polish, tr, sun_strength, wo);
     memset(counts, 0, N_COUNTS * sizeof *counts);
     *id = 0;
-    const v3 l = trace_path_water(&p, px, py, path_seed(px, py, w, h, sample, seed), id, counts, thr_bed);
+    const v3 l = trace_path_water(&p, px, py, path_seed(px, py, w, h, sample, seed), id, counts, thr_bed, NULL, 0);
     light[0] = l.x; light[1] = l.y; light[2] = l.z;
 }

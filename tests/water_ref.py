@@ -27,6 +27,7 @@ Counts = namedtuple("Counts", "steps bounce_segments sun_rays sun_unoccluded sur
                               "passes polished_bounces")
 
 OFF = None   # the setting off
+LOAD_PATH, LOAD_SUN, LOAD_WET = 1, 2, 4   # water_ref.c's load bits
 
 
 def optics(setting) -> WaterOptics:
@@ -43,11 +44,13 @@ class WaterRef:
         u32, f32, ptr = C.c_uint32, C.c_float, C.c_void_p
         settings = [C.POINTER(orc.Scene), ptr, ptr, ptr, f32, C.POINTER(WaterOptics), u32, u32, u32]   # scene, tables, sun, optics, w, h, seed
         L.ref_render_water.restype = None
-        L.ref_render_water.argtypes = settings + [u32, u32, ptr, ptr, ptr]               # spp, sample_base, rgb, ids, counts
+        L.ref_render_water.argtypes = settings + [u32, u32, ptr, ptr, ptr, ptr]          # spp, sample_base, rgb, ids, counts, load
         L.ref_trace_pixel_water.restype = None
         L.ref_trace_pixel_water.argtypes = settings + [u32, u32, u32, ptr, ptr, ptr, ptr]  # px, py, sample, light, id, counts, thr_bed
         L.ref_water_exp_neg.restype = f32
         L.ref_water_exp_neg.argtypes = [f32]
+        L.ref_voxel_at_floor.restype = u32
+        L.ref_voxel_at_floor.argtypes = [C.POINTER(orc.Scene), f32, f32, f32]
         self._lib = L
 
     @staticmethod
@@ -57,14 +60,17 @@ class WaterRef:
         return (e, p, t, wo), (C.byref(scene.c), e.ctypes.data, p.ctypes.data, t.ctypes.data, sun, C.byref(wo), w, h, seed)
 
     def render(self, scene: "orc.OracleScene", w: int, h: int, water=OFF, spp: int = 1, seed: int = 0, sample_base: int = 0, sun: float = 0.0,
-               emission=None, polish=None, translucency=None):
+               emission=None, polish=None, translucency=None, load=None):
         """(rgb [h, w, 3] f32, ids [h, w] u32, Counts) of samples sample_base .. sample_base + spp - 1.  water: None or (absorb,
-        reflectance); sun: vrt_set_sun_light's strength; the three 256-entry tables (None = zeros)."""
+        reflectance); sun: vrt_set_sun_light's strength; the three 256-entry tables (None = zeros); load: None, or a zeroed uint8
+        array [spp, bounces, h, w] that receives the LOAD_ bits of every sample's every segment."""
         keep, args = self._settings(scene, w, h, seed, water, sun, emission, polish, translucency)
         rgb = np.zeros((h, w, 3), dtype=np.float32)
         ids = np.zeros((h, w), dtype=np.uint32)
         n = np.zeros(len(Counts._fields), dtype=np.uint64)
-        self._lib.ref_render_water(*args, spp, sample_base, rgb.ctypes.data, ids.ctypes.data, n.ctypes.data)
+        if load is not None:
+            assert load.dtype == np.uint8 and load.flags.c_contiguous and load.shape == (spp, scene.c.settings.max_ray_bounces, h, w), load.shape
+        self._lib.ref_render_water(*args, spp, sample_base, rgb.ctypes.data, ids.ctypes.data, n.ctypes.data, load.ctypes.data if load is not None else None)
         return rgb, ids, Counts(*(int(x) for x in n))
 
     def trace_pixel(self, scene: "orc.OracleScene", w: int, h: int, px: int, py: int, water=OFF, sample: int = 0, seed: int = 0, sun: float = 0.0,
@@ -79,10 +85,35 @@ class WaterRef:
         self._lib.ref_trace_pixel_water(*args, px, py, sample, light.ctypes.data, C.byref(idw), n.ctypes.data, thr.ctypes.data)
         return light, int(idw.value), Counts(*(int(x) for x in n)), thr
 
+    def voxel_at_floor(self, scene: "orc.OracleScene", o) -> int:
+        """Step 1 of the contract: the voxel at floor(o), o world-local — 0 outside the world box and where there is no chunk."""
+        return int(self._lib.ref_voxel_at_floor(C.byref(scene.c), float(o[0]), float(o[1]), float(o[2])))
+
+    def eye_is_wet(self, scene: "orc.OracleScene") -> bool:
+        """Whether the camera's voxel is a liquid of the scene's material table (ids >= 255 share entry 255)."""
+        origin = [scene.c.cam.pos[a] - float(scene.c.world.min[a]) for a in range(3)]   # create_ray_from_screen's: world-local
+        return scene.mats[min(self.voxel_at_floor(scene, origin), 255)].is_liquid == 1
+
+    def guide(self, dref, scene: "orc.OracleScene", w: int, h: int, water=OFF):
+        """(guide [h, w] u32, ids [h, w] u32) of a frame's primary segments, by tests/denoise_ref.py's ref_guide (dref: its
+        library): over the scene as it is with the setting off or the camera's voxel a liquid of the table, over a copy with every
+        is_liquid cleared otherwise — the march a water frame gives its primary rays."""
+        if water is None or self.eye_is_wet(scene):
+            return dref.guide(scene, w, h)
+        return dref.guide(dry_copy(scene), w, h)
+
     def exp_neg(self, t) -> np.ndarray:
         """water_ref.c's own statement of vexp_neg, value by value."""
         t = np.asarray(t, dtype=np.float32)
         return np.array([self._lib.ref_water_exp_neg(float(x)) for x in t.reshape(-1)], dtype=np.float32).reshape(t.shape)
+
+
+def dry_copy(scene: "orc.OracleScene") -> "orc.OracleScene":
+    """The scene with every is_liquid cleared (the nodes and roots shared, the materials its own)."""
+    dry = orc.OracleScene(scene.nodes, scene.roots, scene.mats, scene.c.cam, scene.c.settings, scene.c.world)
+    for m in dry.mats:
+        m.is_liquid = 0
+    return dry
 
 
 _loaded = None
