@@ -458,6 +458,7 @@ extern "C" {
     pub fn vrt_get_accumulation(ctx: *mut vrt_ctx, samples: *mut u32, seed: *mut u32) -> c_int;
     pub fn vrt_set_denoise(ctx: *mut vrt_ctx, opts: *const vrt_denoise_opts) -> c_int;
     pub fn vrt_read_guide(ctx: *mut vrt_ctx, guide: *mut u32) -> c_int;
+    pub fn vrt_selftest_denoise(device: i32, rgb: *const f32, ids: *const u32, guide: *const u32, w: u32, h: u32, opts: *const vrt_denoise_opts, rgb_out: *mut f32, ids_out: *mut u32) -> c_int;
     pub fn vrt_set_tone_map(ctx: *mut vrt_ctx, opts: *const vrt_tone_map) -> c_int;
     pub fn vrt_get_tone_info(ctx: *mut vrt_ctx, out: *mut vrt_tone_info) -> c_int;
     pub fn vrt_read_tone_histogram(ctx: *mut vrt_ctx, bins: *mut u32) -> c_int;

@@ -414,6 +414,19 @@ int vrt_set_denoise(vrt_ctx *ctx, const vrt_denoise_opts *opts);
 /* Diagnostic: the guide words of the last denoised frame, width * height of them row-major (0 beyond the traced area).
  * Synchronises.  VRT_ERR_STATE before the first denoised frame (and after a resize until the next one). */
 int vrt_read_guide(vrt_ctx *ctx, uint32_t *guide);
+/* Self-test of the filter's pass kernels on a frame of the caller's choosing.  The arguments are vrth_denoise's (vrt_host.h):
+ * rgb w*h*3 f32, ids and guide w*h words, row-major, w the stride of a row; the traced area is the first 8 (w / 8) x 8 (h / 8)
+ * pixels.  The arrays go to `device` as one frame of texels (r, g, b, id word) and a second copy of it, and opts->passes passes run
+ * between the two through the launcher a frame uses, with a frame's tap spacings, kernels per spacing and sigma per pass;
+ * rgb_out w*h*3 f32 and ids_out w*h words (may be NULL) receive the colours and the id words of the copy the last pass wrote —
+ * with passes == 0 the input.  By the definition above that is vrth_denoise's output to the bit (a NaN's sign and payload aside),
+ * every id word is the caller's, all 32 bits of it, and a pixel no pass stores to — beyond the traced area, or everywhere when w or h
+ * is below 8, which is legal — comes back with the caller's bytes whatever they are.  A null pointer other than ids_out, w or h
+ * of 0, or options vrt_set_denoise refuses: VRT_ERR_INVALID_ARG; w * h above 2^24: VRT_ERR_OUT_OF_RANGE; a refused call writes
+ * nothing.  Buffers and a stream of its own, freed on every path; synchronises.  Diagnostic only: no context needed, never part
+ * of a frame. */
+int vrt_selftest_denoise(int32_t device, const float *rgb, const uint32_t *ids, const uint32_t *guide, uint32_t w, uint32_t h,
+                         const vrt_denoise_opts *opts, float *rgb_out, uint32_t *ids_out);
 
 /* Exposure and tone mapping of presented path frames.  A path frame's radiance lies well outside [0, 1] (emission, the sun
  * term, the lamps); vrt_present / vrt_present_device quantise unorm8(clamp(c, 0, 1)), the live shader's textureStore, which is

@@ -18,6 +18,7 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import denoise_ref
+from denoise_cases import random_frame, striped_frame   # (the table of crafted frames: the GPU comparison takes its frames from it too)
 from voxelraytracing_amd import _ffi, scenes
 
 HIT, NX, NY, NZ, WATER = _ffi.ID_HIT, _ffi.ID_NX, _ffi.ID_NY, _ffi.ID_NZ, _ffi.ID_WATER
@@ -33,43 +34,6 @@ def ref(tmp_path_factory):
 def same_bits(a, b):
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
     return bool(np.all((denoise_ref.bits(a) == denoise_ref.bits(b)) | (np.isnan(a) & np.isnan(b))))
-
-
-def random_frame(rng, w, h, special=True, n_keys=5, n_guides=3):
-    """A frame of random colours, keys and guides: a few surfaces so that taps agree often, sky and no-normal hits in between,
-    bits outside the key (the shadow bits) set at random, and — special — zeros, denormals, infinities and NaNs among the colours."""
-    vox = rng.integers(1, 200, n_keys).astype(np.uint32)
-    face = rng.choice(np.array([NX, NY, NZ, NX | NY, NY | NZ | WATER], np.uint32), n_keys)
-    k = rng.integers(0, n_keys, (h, w))
-    ids = (vox[k] | HIT | face[k]).astype(np.uint32)
-    kind = rng.random((h, w))
-    ids[kind < 0.12] = 0                                            # sky
-    ids[(kind >= 0.12) & (kind < 0.2)] = HIT | 7                     # a hit without a normal
-    ids |= (rng.integers(0, 4, (h, w)).astype(np.uint32) << 21)      # bits the key leaves out
-    guide = rng.integers(10, 10 + n_guides, (h, w)).astype(np.uint32)
-    guide[(ids & HIT == 0) | (ids & (NX | NY | NZ) == 0)] = 0
-    rgb = (rng.random((h, w, 3), dtype=np.float32) * np.float32(3.0)).astype(np.float32)
-    if special:
-        pick = rng.random((h, w, 3))
-        rgb[pick < 0.03] = 0.0
-        rgb[(pick >= 0.03) & (pick < 0.05)] = np.float32(1e-41)      # a denormal
-        rgb[(pick >= 0.05) & (pick < 0.06)] = np.inf
-        rgb[(pick >= 0.06) & (pick < 0.07)] = np.nan
-        rgb[(pick >= 0.07) & (pick < 0.08)] = np.float32(3e38)
-    return rgb, ids, guide
-
-
-def striped_frame(rng, w, h):
-    """Keys in 1-pixel stripes (columns alternate between two surfaces) with isolated pixels of a third sprinkled in."""
-    rgb, _, _ = random_frame(rng, w, h)
-    ids = np.empty((h, w), np.uint32)
-    ids[:, 0::2] = 3 | HIT | NX
-    ids[:, 1::2] = 4 | HIT | NY
-    lone = rng.random((h, w)) < 0.05
-    ids[lone] = 9 | HIT | NZ
-    guide = np.full((h, w), 20, np.uint32)
-    guide[lone] = (21 + np.arange(int(lone.sum()))).astype(np.uint32)   # no two of them on one plane
-    return rgb, ids, guide
 
 
 @pytest.mark.parametrize("sigma", SIGMAS)

@@ -269,6 +269,7 @@ VRT_SYMBOLS = {
     "vrt_get_accumulation": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "vrt_set_denoise": (C.c_int, [_P, C.POINTER(DenoiseOpts)]),
     "vrt_read_guide": (C.c_int, [_P, _P]),
+    "vrt_selftest_denoise": (C.c_int, [C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.POINTER(DenoiseOpts), _P, _P]),
     "vrt_set_tone_map": (C.c_int, [_P, C.POINTER(ToneMap)]),
     "vrt_get_tone_info": (C.c_int, [_P, C.POINTER(ToneInfo)]),
     "vrt_read_tone_histogram": (C.c_int, [_P, _P]),
@@ -508,6 +509,23 @@ def denoise(rgb, ids, guide, passes: int = DENOISE_PASSES, sigma_color: float = 
     if host().vrth_denoise(rgb.ctypes.data, ids.ctypes.data, guide.ctypes.data, w, h, C.byref(o), out.ctypes.data):
         raise ValueError(f"denoise: passes {passes} (0..5), sigma_color {sigma_color} (finite, >= 0)")
     return out
+
+
+def selftest_denoise(rgb, ids, guide, passes: int, sigma_color: float, device: int = 0):
+    """vrt_selftest_denoise: the pass kernels of vrt_set_denoise on a frame of the caller's choosing, through the launcher a frame
+    uses (include/vrt.h).  Arguments as denoise() above -> (the filtered rgb [h, w, 3] f32, the id words [h, w] u32 the last pass
+    wrote).  A refused call raises VrtError."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = rgb.shape[:2]
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(h, w)
+    guide = np.ascontiguousarray(guide, dtype=np.uint32).reshape(h, w)
+    out, ids_out = np.empty_like(rgb), np.empty_like(ids)
+    o = DenoiseOpts(passes, sigma_color, 0, 0)
+    rc = vrt().vrt_selftest_denoise(device, rgb.ctypes.data, ids.ctypes.data, guide.ctypes.data, w, h, C.byref(o), out.ctypes.data, ids_out.ctypes.data)
+    if rc:
+        from .graphics import VrtError
+        raise VrtError(rc, f"vrt_selftest_denoise refused {w} x {h}, passes {passes}, sigma_color {sigma_color}")
+    return out, ids_out
 
 
 def tone_setting(curve: int = TONE_FILMIC, exposure: float = 1.0, auto: bool = False, gamma2: bool = False, white: float = 0.0,

@@ -192,6 +192,22 @@ void launch_denoise_pass(const DenoisePass &D, hipStream_t st) {
     else hipLaunchKernelGGL(denoise_pass_kernel<16>, grid, block, 0, st, D);
 }
 
+// Pass i over a frame of width x height texels, from `in` to `out`: what a frame (denoise_after_frame) and vrt_selftest_denoise
+// both launch
+DenoisePass denoise_pass_of(const Texel *in, Texel *out, const uint32_t *guide, uint32_t width, uint32_t height, uint32_t i, float sigma_color) {
+    DenoisePass D;
+    D.in = in;
+    D.out = out;
+    D.guide = guide;
+    D.stride = width;
+    D.wt = (int)(width & ~7u);
+    D.ht = (int)(height & ~7u);
+    D.s = 1 << i;
+    D.stop = sigma_color != 0.0f ? 1u : 0u;
+    D.sg2 = denoise_sigma2(sigma_color, i);
+    return D;
+}
+
 }  // namespace
 
 }  // namespace vrt
@@ -218,17 +234,7 @@ int denoise_after_frame(vrt_ctx *c, const vrt::FrameParams &P, const vrt::FrameP
     HIP_TRY(c, hipGetLastError());
     vrt::Texel *a = (passes & 1u) ? c->sz.dn_scratch[slot] : frame_out, *b = (passes & 1u) ? frame_out : c->sz.dn_scratch[slot];
     for (uint32_t i = 0; i < passes; i++) {
-        vrt::DenoisePass D;
-        D.in = a;
-        D.out = b;
-        D.guide = c->sz.dn_guide[slot];
-        D.stride = c->width;
-        D.wt = (int)(c->width & ~7u);
-        D.ht = (int)(c->height & ~7u);
-        D.s = 1 << i;
-        D.stop = c->denoise.sigma_color != 0.0f ? 1u : 0u;
-        D.sg2 = vrt::denoise_sigma2(c->denoise.sigma_color, i);
-        vrt::launch_denoise_pass(D, st);
+        vrt::launch_denoise_pass(vrt::denoise_pass_of(a, b, c->sz.dn_guide[slot], c->width, c->height, i, c->denoise.sigma_color), st);
         HIP_TRY(c, hipGetLastError());
         std::swap(a, b);
     }
@@ -267,6 +273,62 @@ int vrt_read_guide(vrt_ctx *c, uint32_t *guide) {
     QUIESCE(c);
     HIP_TRY(c, hipMemcpyAsync(guide, c->sz.dn_last_guide, (size_t)c->width * c->height * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VRT_OK;
+}
+
+// The passes of a frame — denoise_pass_of and launch_denoise_pass, as denoise_after_frame calls them — over a frame of the
+// caller's choosing: the arrays packed into texels on the host, two copies of that frame on the device (vrth_denoise starts both of
+// its buffers from the input too: a pass never stores to a pixel beyond the traced area), buffers and a stream of its own, no context.
+int vrt_selftest_denoise(int32_t device, const float *rgb, const uint32_t *ids, const uint32_t *guide, uint32_t w, uint32_t h, const vrt_denoise_opts *opts,
+                         float *rgb_out, uint32_t *ids_out) {
+    if (!rgb || !ids || !guide || !opts || !rgb_out || !w || !h) return VRT_ERR_INVALID_ARG;
+    if (opts->passes > vrt::kDnMaxPasses || !(opts->sigma_color >= 0.0f) || std::isinf(opts->sigma_color) || opts->flags || opts->_reserved)
+        return VRT_ERR_INVALID_ARG;
+    const uint64_t n64 = (uint64_t)w * h;
+    if (n64 > (1ull << 24)) return VRT_ERR_OUT_OF_RANGE;
+    const size_t n = (size_t)n64;
+    const uint32_t passes = (w & ~7u) && (h & ~7u) ? opts->passes : 0u;   // (no traced area: nothing to launch)
+    std::vector<vrt::Texel> host;
+    try {
+        host.resize(n);
+    } catch (const std::bad_alloc &) {
+        return VRT_ERR_OOM;
+    }
+    for (size_t p = 0; p < n; p++) {
+        uint32_t c[3];
+        memcpy(c, rgb + p * 3, sizeof c);   // (bits: a NaN keeps its payload)
+        host[p] = make_uint4(c[0], c[1], c[2], ids[p]);
+    }
+    if (hipSetDevice(device) != hipSuccess) return VRT_ERR_DEVICE;
+    vrt::Texel *d_a = nullptr, *d_b = nullptr;
+    uint32_t *d_guide = nullptr;
+    hipStream_t st = nullptr;
+    int rc = VRT_OK;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { st = nullptr; rc = VRT_ERR_DEVICE; }
+    if (rc == VRT_OK && (hipMalloc(&d_a, n * sizeof(vrt::Texel)) != hipSuccess || hipMalloc(&d_b, n * sizeof(vrt::Texel)) != hipSuccess ||
+                         hipMalloc(&d_guide, n * sizeof(uint32_t)) != hipSuccess)) rc = VRT_ERR_OOM;
+    if (rc == VRT_OK && (hipMemcpyAsync(d_a, host.data(), n * sizeof(vrt::Texel), hipMemcpyHostToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(d_b, host.data(), n * sizeof(vrt::Texel), hipMemcpyHostToDevice, st) != hipSuccess ||
+                         hipMemcpyAsync(d_guide, guide, n * sizeof(uint32_t), hipMemcpyHostToDevice, st) != hipSuccess)) rc = VRT_ERR_DEVICE;
+    vrt::Texel *a = d_a, *b = d_b;
+    for (uint32_t i = 0; rc == VRT_OK && i < passes; i++) {
+        vrt::launch_denoise_pass(vrt::denoise_pass_of(a, b, d_guide, w, h, i, opts->sigma_color), st);
+        if (hipGetLastError() != hipSuccess) rc = VRT_ERR_DEVICE;
+        std::swap(a, b);
+    }
+    // (a: the buffer the last pass wrote; the input when there was none)
+    if (rc == VRT_OK && hipMemcpyAsync(host.data(), a, n * sizeof(vrt::Texel), hipMemcpyDeviceToHost, st) != hipSuccess) rc = VRT_ERR_DEVICE;
+    if (st && hipStreamSynchronize(st) != hipSuccess && rc == VRT_OK) rc = VRT_ERR_DEVICE;
+    (void)hipFree(d_guide);
+    (void)hipFree(d_b);
+    (void)hipFree(d_a);
+    if (st) (void)hipStreamDestroy(st);
+    if (rc != VRT_OK) return rc;
+    for (size_t p = 0; p < n; p++) {
+        const uint32_t c[3] = {host[p].x, host[p].y, host[p].z};
+        memcpy(rgb_out + p * 3, c, sizeof c);
+        if (ids_out) ids_out[p] = host[p].w;
+    }
     return VRT_OK;
 }
 
