@@ -350,6 +350,17 @@ pub struct vrt_water_optics {
     pub flags: u32,
     pub _reserved: [u32; 3],
 }
+
+/// vrt_set_water_refraction: Snell's law at the water's surface and the surface seen from below, in frames with water optics on
+/// (ior 0 = off; otherwise in [1, 4]; max_span: the unit voxels a wet segment's span walk may cross, 0 = 64, at most 1024).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_water_refraction {
+    pub ior: f32,
+    pub max_span: u32,
+    pub flags: u32,
+    pub _reserved: u32,
+}
 pub const VRT_WATER_ON: u32 = 1;
 
 /// vrt_set_camera_sampling: pixel jitter and a thin lens for the path trace (pixel_spread and aperture both 0 = off).
@@ -464,6 +475,7 @@ extern "C" {
     pub fn vrt_read_tone_histogram(ctx: *mut vrt_ctx, bins: *mut u32) -> c_int;
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
     pub fn vrt_set_water_optics(ctx: *mut vrt_ctx, opts: *const vrt_water_optics) -> c_int;
+    pub fn vrt_set_water_refraction(ctx: *mut vrt_ctx, opts: *const vrt_water_refraction) -> c_int;
     pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
     pub fn vrt_set_lamp_light(ctx: *mut vrt_ctx, opts: *const vrt_lamp_light) -> c_int;
     pub fn vrt_get_lamp_info(ctx: *mut vrt_ctx, out: *mut vrt_lamp_info) -> c_int;
@@ -534,6 +546,7 @@ mod layout {
         assert!(size_of::<vrt_tone_info>() == 40);
         assert!(size_of::<vrt_sun_light>() == 16);
         assert!(size_of::<vrt_water_optics>() == 32);
+        assert!(size_of::<vrt_water_refraction>() == 16);
         assert!(size_of::<vrt_camera_sampling>() == 16);
         assert!(size_of::<vrt_lamp_light>() == 16);
         assert!(size_of::<vrt_lamp>() == 16);

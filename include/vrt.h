@@ -595,6 +595,62 @@ typedef struct {
 #define VRT_WATER_ON 1u
 int vrt_set_water_optics(vrt_ctx *ctx, const vrt_water_optics *opts);
 
+/* Refraction for water: Snell's law at the surface, and the surface seen from below.  The setting acts only in frames in which
+ * vrt_set_water_optics is on (a water frame); with water optics off it is kept and changes nothing.  With it, a path that enters
+ * the water is bent, and a wet segment that reaches the water's face from inside ends there: it is mirrored back (always, past the
+ * critical angle: total internal reflection) or bent out into the air.  Build-defined, and defined exactly — in a water frame with
+ * ior != 0, in strict binary32, nothing contracted, sqrt correctly rounded; eta = 1.0f / ior is formed once on the host;
+ * normalize(v) = v / sqrt(dot(v, v)) is the path kernels' own; dot(a, b) = a.x * b.x + a.y * b.y + a.z * b.z, summed left to right;
+ * bias = 0.002 (the bounce origin's):
+ *   A  entering.  In the transmitted branch of the water contract's step 4 (u >= F), and only there, the direction is bent; the
+ *      draw, F, the reflected branch and o' = pos are unchanged:
+ *        dn = dot(norm, d);  c = |dn|;  nn.k = dn < 0 ? norm.k : -norm.k
+ *        s2 = (eta * eta) * (1 - c * c);  ct = sqrt(1 - s2);  g = eta * c - ct
+ *        d' = normalize(eta * d.k + g * nn.k)       per component a multiply, a multiply, an add
+ *      With ior >= 1 the radicand is never negative.  A zero normal (a dry segment whose start nudge lands it in a liquid) gives
+ *      d' = normalize(eta * d).  ior = 1 gives normalize(d): such a frame may differ from the frame without the setting in last bits
+ *   B  the span walk, on every wet segment, ahead of the absorption of step 3.  cast_ray's DDA as vrt_cast_rays runs it
+ *      (csrc/both/cast_dda.h: cast_setup(o, d), then cast_step), quirks included, from the segment's origin o along d; its first
+ *      voxel is floor(o), the liquid that made the segment wet.  Up to max_span steps; after each, v is the voxel at the DDA's
+ *      position as vrt_get_voxels answers (0 outside the world box, 0 where there is no chunk).  The walk ends at the first v that
+ *      is not a liquid of the table; dist is that step's dist.  There is an underside event when the walk ended within max_span
+ *      steps, v == 0, and dist is finite and >= 0.  In every other case — the walk ended on a solid voxel, it was still in liquid
+ *      after max_span steps, dist was not finite — there is none, and the segment is word for word what it is with the setting off
+ *   C  the underside event.  n.k = (float)(prev.k - m.k), m the air voxel and prev the voxel before it: the face's normal, back
+ *      into the water.  x.k = o.k + d.k * dist (a multiply, then an add).  The segment's march is still the frame's own: a primary
+ *      segment's id word, vrt_read_steps and a stats frame's steps, node_visits and hits are that march's, and the walk's steps are
+ *      counted nowhere (the kernels may skip the march of a later segment that ends in an event where nothing counts it).  Nothing
+ *      else of the march is used:
+ *        thr.ch *= vexp_neg(absorb[ch] * dist)      in place of the march's water_dist
+ *        on the path's last allowed segment: the path ends, nothing is drawn, no light is added
+ *        u = rng_next(rng)                          the event's only draw
+ *        dn = dot(n, d);  c = |dn|;  s2 = (ior * ior) * (1 - c * c)
+ *        !(s2 < 1): total internal reflection (also for a NaN);  otherwise
+ *            ct = sqrt(1 - s2);  mm = 1 - ct;  m5 = (mm * mm) * (mm * mm) * mm;  F = reflectance + (1 - reflectance) * m5
+ *        reflected (total, or u < F):  d'.k = d.k - 2 * n.k * dn;  o'.k = x.k + n.k * bias          (back into the water)
+ *        otherwise:  g = ior * c - ct;  d' = normalize(ior * d.k + g * n.k);  o'.k = x.k - n.k * bias  (out into the air)
+ *      The event adds no emission, sends no sun ray and draws nothing else; thr is otherwise unchanged.  It costs one of the path's
+ *      segments; vrt_stats.secondary_rays counts its continuation as the bounce segment it is.  The next segment decides wet or
+ *      dry afresh from floor(o'), as every segment does
+ *   D  everything else is the water contract's.  The sun term is unchanged: its ray passes liquids, unbent and unattenuated.  The
+ *      sums, VRT_RENDER_ACCUMULATE's identity, the denoiser's key and guide (both from the primary segment's own march), tone
+ *      mapping, the three tables, shard and multi-device contexts compose as they do for a water frame, and the pairs a water
+ *      frame refuses (vrt_set_lamp_light, vrt_set_camera_sampling) are refused exactly as without the setting
+ * A refracting frame is planned and launched as a water frame; its two trace launches run a pair of kernels of their own.  Still
+ * not built: caustics, absorption along sun rays, dispersion.
+ * opts NULL or ior +0 / -0: off, the default — frames are byte for byte those of a context that never called this, the same
+ * kernels run, and nothing is launched, planned or allocated differently.  A null context, an ior that is NaN, negative, infinite,
+ * or not 0 and outside [1, 4], max_span above 1024, flags or _reserved not 0: VRT_ERR_INVALID_ARG; a refused call changes nothing.
+ * A call that changes the setting (off is 16 zero bytes; max_span 0 and 64 are the same setting) restarts the accumulation; one
+ * that does not, does not.  A multi-device context replicates the setting; a shard context keeps its own. */
+typedef struct {
+    float    ior;           /* 0 = off (the default); otherwise the water's index of refraction relative to air, in [1, 4] */
+    uint32_t max_span;      /* the unit voxels a wet segment's span walk may cross; 0 = 64; at most 1024 */
+    uint32_t flags;         /* 0 */
+    uint32_t _reserved;     /* 0 */
+} vrt_water_refraction;     /* 16 B */
+int vrt_set_water_refraction(vrt_ctx *ctx, const vrt_water_refraction *opts);
+
 /* Camera sampling for VRT_MODE_PATH: a primary ray of its own for every sample — sub-pixel jitter (a box pixel filter, which
  * is what removes the stair steps of voxel edges as samples accumulate) and a thin lens (depth of field).  Without it every
  * sample of a pixel starts with the pixel's one ray.  The primary modes ignore the setting and stay byte for byte what they

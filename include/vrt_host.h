@@ -224,6 +224,29 @@ int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, flo
  * null pointer. */
 int vrth_water_transmittance(const float *absorb, const float *dist, uint64_t n, float *out);
 
+/* ---- refraction for water (include/vrt.h: vrt_set_water_refraction) on the host ---- */
+#define VRTH_REFRACT_ENTERED  0 /* A: the transmitted branch of a surface event, bent */
+#define VRTH_REFRACT_TOTAL    1 /* C: total internal reflection */
+#define VRTH_REFRACT_MIRRORED 2 /* C: reflected by the draw (u < F) */
+#define VRTH_REFRACT_LEFT     3 /* C: bent out into the air */
+/* The direction behind a water face in the text the refracting kernels compile (csrc/both/refract_math.h).  leaving == 0: A of the
+ * contract — d bent into the water at a face whose normal is `normal` (eta = 1.0f / ior as the context forms it; reflectance and u
+ * are not read: the draw against F is the water contract's own); leaving != 0: C — `normal` is the face's normal back into the
+ * water, u the event's draw.  d_out[3]: d'.  Returns the branch taken, or -1 for a null pointer or an ior outside [1, 4]. */
+int vrth_water_refract(float ior, float reflectance, const float d[3], const float normal[3], float u, int leaving, float d_out[3]);
+/* B of the contract over a host world: the span walk from o (world-local, as the kernels' origins are) along d, at most max_span
+ * steps (0 = 64), liquids by mats256[min(id, 255)].is_liquid == 1. */
+typedef struct {
+    float    dist;      /* the last step's dist, its bits as the walk left them */
+    int32_t  prev[3];   /* the voxel before the last one, world-local */
+    int32_t  m[3];      /* the voxel the walk ended in */
+    uint32_t v;         /* the voxel there: 0 outside the world box and where there is no chunk */
+    uint32_t event;     /* 1: the underside event */
+    uint32_t steps;     /* the steps taken */
+} vrth_water_span;      /* 40 B */
+/* Returns 0, or -1 for a null pointer or max_span above 1024. */
+int vrth_world_water_span(const vrth_world *w, const vrt_material *mats256, const float o[3], const float d[3], uint32_t max_span, vrth_water_span *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,19 @@ class WaterOptics(C.Structure):
 WATER_ON = 1   # vrt_water_optics.flags (VRT_WATER_ON)
 
 
+class WaterRefraction(C.Structure):
+    """include/vrt.h vrt_water_refraction: Snell's law at the water's surface, the surface from below (vrt_set_water_refraction)"""
+    _fields_ = [("ior", C.c_float), ("max_span", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class WaterSpan(C.Structure):
+    """include/vrt_host.h vrth_water_span: what vrth_world_water_span's walk found"""
+    _fields_ = [("dist", C.c_float), ("prev", C.c_int32 * 3), ("m", C.c_int32 * 3), ("v", C.c_uint32), ("event", C.c_uint32), ("steps", C.c_uint32)]
+
+
+REFRACT_ENTERED, REFRACT_TOTAL, REFRACT_MIRRORED, REFRACT_LEFT = 0, 1, 2, 3   # vrth_water_refract's branches (VRTH_REFRACT_*)
+
+
 class CameraSampling(C.Structure):
     """include/vrt.h vrt_camera_sampling: the path trace's pixel jitter and thin lens (vrt_set_camera_sampling)"""
     _fields_ = [("pixel_spread", C.c_float), ("aperture", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32)]
@@ -275,6 +288,7 @@ VRT_SYMBOLS = {
     "vrt_read_tone_histogram": (C.c_int, [_P, _P]),
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
     "vrt_set_water_optics": (C.c_int, [_P, C.POINTER(WaterOptics)]),
+    "vrt_set_water_refraction": (C.c_int, [_P, C.POINTER(WaterRefraction)]),
     "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
     "vrt_set_lamp_light": (C.c_int, [_P, C.POINTER(LampLight)]),
     "vrt_get_lamp_info": (C.c_int, [_P, C.POINTER(LampInfo)]),
@@ -481,6 +495,8 @@ VRTH_SYMBOLS = {
     "vrth_tone_meter": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(ToneMap), C.c_int, C.c_float, C.POINTER(ToneInfo), _P]),
     "vrth_tone_map": (C.c_int, [_P, C.c_uint64, C.POINTER(ToneMap), C.c_float, _P]),
     "vrth_water_transmittance": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "vrth_water_refract": (C.c_int, [C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.POINTER(C.c_float)]),
+    "vrth_world_water_span": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(WaterSpan)]),
 }
 
 # Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)
@@ -566,4 +582,25 @@ def water_transmittance(absorb, dist) -> np.ndarray:
     out = np.empty(a.shape, dtype=np.float32)
     if host().vrth_water_transmittance(a.ctypes.data, d.ctypes.data, a.size, out.ctypes.data):
         raise ValueError("vrth_water_transmittance refused the arguments")
+    return out
+
+
+def water_refract(ior: float, reflectance: float, d, normal, u: float = 0.0, leaving: bool = False):
+    """vrth_water_refract: (d' [3] f32, the branch: REFRACT_*) of vrt_set_water_refraction's bend into the water (leaving False: A of
+    the contract) or of the underside event (leaving True: C; normal points back into the water, u is the event's draw)."""
+    f3 = C.c_float * 3
+    out = f3()
+    branch = host().vrth_water_refract(ior, reflectance, f3(*(float(x) for x in d)), f3(*(float(x) for x in normal)), u, 1 if leaving else 0, out)
+    if branch < 0:
+        raise ValueError("vrth_water_refract refused the arguments")
+    return np.array(out[:], dtype=np.float32), branch
+
+
+def world_water_span(world_handle, materials, o, d, max_span: int = 0) -> WaterSpan:
+    """vrth_world_water_span: the span walk (B of vrt_set_water_refraction's contract) over a host world from o (world-local)
+    along d.  materials: the 256-entry table (a ctypes array of Material)."""
+    f3 = C.c_float * 3
+    out = WaterSpan()
+    if host().vrth_world_water_span(world_handle, C.addressof(materials), f3(*(float(x) for x in o)), f3(*(float(x) for x in d)), max_span, C.byref(out)):
+        raise ValueError("vrth_world_water_span refused the arguments")
     return out

@@ -12,6 +12,7 @@
 #include "../both/column_top.h"
 #include "../both/denoise_math.h"
 #include "../both/lens_math.h"
+#include "../both/refract_math.h"
 #include "../both/shape_math.h"
 #include "../both/tone_math.h"
 #include "../both/water_math.h"
@@ -734,5 +735,35 @@ int vrth_tone_map(const float *rgb_in, uint64_t n, const vrt_tone_map *opts, flo
 int vrth_water_transmittance(const float *absorb, const float *dist, uint64_t n, float *out) {
     if (!absorb || !dist || !out) return -1;
     for (uint64_t i = 0; i < n; i++) out[i] = vrt::vexp_neg(absorb[i] * dist[i]);
+    return 0;
+}
+
+// vrt_set_water_refraction's bends (csrc/both/refract_math.h, the text the refracting kernels compile): A for leaving == 0, C otherwise
+int vrth_water_refract(float ior, float reflectance, const float d[3], const float normal[3], float u, int leaving, float d_out[3]) {
+    if (!d || !normal || !d_out || !(ior >= 1.0f && ior <= 4.0f)) return -1;
+    if (leaving) return vrt::refract_leave(ior, reflectance, d, normal, u, d_out);
+    vrt::refract_enter(1.0f / ior, d, normal, d_out);   // (eta as the context forms it)
+    return VRTH_REFRACT_ENTERED;
+}
+
+// ... and its span walk over a host world: the voxel as vrth_world_get_voxels records it (0 outside the box, 0 without a chunk)
+int vrth_world_water_span(const vrth_world *w, const vrt_material *mats256, const float o[3], const float d[3], uint32_t max_span, vrth_water_span *out) {
+    if (!w || !mats256 || !o || !d || !out || max_span > vrt::kRefractSpanMax) return -1;
+    const VoxelPos lo = w->w.min_voxel();
+    const uint32_t W = w->w.size_in_voxels();
+    const vrt::WaterSpan s = vrt::water_span(
+        o, d, max_span ? max_span : vrt::kRefractSpanDefault,
+        [&](int32_t x, int32_t y, int32_t z) -> uint32_t {
+            if (!((uint32_t)x < W && (uint32_t)y < W && (uint32_t)z < W)) return 0u;
+            Voxel v;
+            return w->w.get_voxel(VoxelPos{lo.x + x, lo.y + y, lo.z + z}, v) == SetVoxelErr::Ok ? (uint32_t)v.as_data() : 0u;
+        },
+        [&](uint32_t v) { return mats256[v < 255u ? v : 255u].is_liquid == 1u; });
+    memset(out, 0, sizeof *out);
+    out->dist = s.dist;
+    for (int k = 0; k < 3; k++) { out->prev[k] = s.prev[k]; out->m[k] = s.m[k]; }
+    out->v = s.v;
+    out->event = s.event ? 1u : 0u;
+    out->steps = s.steps;
     return 0;
 }

@@ -217,6 +217,14 @@ struct WaterLaunch {
     uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun term, and the later misses' sky without the disc
 };
 
+// vrt_set_water_refraction (vrt_path_refract.h): what the kernels of a refracting water frame are given behind a water frame's
+// arguments
+struct RefractLaunch {
+    float ior, eta;       // the setting (never 0 here), and 1.0f / ior, formed once on the host
+    uint32_t max_span;    // the steps a wet segment's span walk may take (the setting's 0 is 64 here)
+    uint32_t _pad;
+};
+
 // vrt_set_tone_map: what the blit of a mapped frame is given besides the unmapped blit's arguments (both/tone_math.h's
 // ToneCurve, flat).  E_dev: the frame set's exposure word on the device (a metered frame: nothing of it comes back to the host);
 // null: E, the setting's own

@@ -2,6 +2,7 @@
 // shader.rs:371-379; callers main.rs:211-223, 426-454): contexts, the per-frame uniforms, frames in flight, vrt_render,
 // read-backs and statistics.  Device memory layout: DESIGN.md section 4.
 #include "vrt_ctx.h"
+#include "both/refract_math.h"  // (vrt_set_water_refraction: max_span's default and limit)
 
 thread_local std::string g_create_err;
 
@@ -365,6 +366,10 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     }
     // vrt_set_water_optics: the setting as the kernels of vrt_path_water.h take it
     const vrt::WaterLaunch W{{c->water.absorb[0], c->water.absorb[1], c->water.absorb[2]}, c->water.reflectance, lobes, plan.sun ? 1u : 0u};
+    // vrt_set_water_refraction: the setting as the kernels of vrt_path_refract.h take it (a water frame's launches go to them).  Off:
+    // X is built all the same and nothing reads it — no launch below takes it unless `refracts`
+    const bool refracts = c->refraction.ior != 0.0f;
+    const vrt::RefractLaunch X{c->refraction.ior, refracts ? 1.0f / c->refraction.ior : 0.0f, c->refraction.max_span, 0u};
     // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
     const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance, lobes};
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
@@ -424,8 +429,14 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
             case kStepLampPrimary: launch_path_primary_lamp(P, L, S, M, plan.lens, plan.kstats, plan.literal, f.st); break;
             case kStepLampBounce: launch_path_bounce_lamp(P, S, M, plan.kstats, plan.literal, f.st); break;
             case kStepLampRays: launch_path_lamp_rays(P, M, plan.kstats, plan.literal, f.st); break;
-            case kStepWaterPrimary: launch_path_primary_water(P, W, S, plan.kstats, plan.literal, f.st); break;
-            case kStepWaterBounce: launch_path_bounce_water(P, W, S, plan.kstats, plan.literal, f.st); break;
+            case kStepWaterPrimary:
+                if (refracts) launch_path_primary_refract(P, W, S, X, plan.kstats, plan.literal, f.st);
+                else launch_path_primary_water(P, W, S, plan.kstats, plan.literal, f.st);
+                break;
+            case kStepWaterBounce:
+                if (refracts) launch_path_bounce_refract(P, W, S, X, plan.kstats, plan.literal, f.st);
+                else launch_path_bounce_water(P, W, S, plan.kstats, plan.literal, f.st);
+                break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -894,6 +905,26 @@ int vrt_set_water_optics(vrt_ctx *c, const vrt_water_optics *opts) {
     if (o.reflectance == 0.0f) o.reflectance = 0.0f;
     if (memcmp(&c->water, &o, sizeof o) != 0) c->accum_restart = true;
     c->water = o;
+    return VRT_OK;
+}
+
+int vrt_set_water_refraction(vrt_ctx *c, const vrt_water_refraction *opts) {
+    if (!c) return VRT_ERR_INVALID_ARG;
+    vrt_water_refraction o;
+    memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if (!(o.ior == 0.0f || (o.ior >= 1.0f && o.ior <= 4.0f)))
+        return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_refraction: ior %g (0 = off, or in [1, 4])", (double)o.ior);
+    if (o.max_span > vrt::kRefractSpanMax)
+        return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_refraction: max_span %u (0 = %u; at most %u)", o.max_span, vrt::kRefractSpanDefault,
+                    vrt::kRefractSpanMax);
+    if (o.flags || o._reserved) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_water_refraction: flags and _reserved must be 0");
+    GRP_EACH(c, vrt_set_water_refraction(d, opts));
+    // what is kept: off is 16 zero bytes, max_span 0 is 64
+    if (o.ior == 0.0f) memset(&o, 0, sizeof o);
+    else if (o.max_span == 0u) o.max_span = vrt::kRefractSpanDefault;
+    if (memcmp(&c->refraction, &o, sizeof o) != 0) c->accum_restart = true;
+    c->refraction = o;
     return VRT_OK;
 }
 

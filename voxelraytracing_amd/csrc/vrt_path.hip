@@ -30,6 +30,7 @@
 #include "vrt_path_lens.h"
 #include "vrt_path_lamp.h"   // (vrt_set_lamp_light: kernels of their own, behind everything they share with the others)
 #include "vrt_path_water.h"  // (vrt_set_water_optics: a pair of their own again)
+#include "vrt_path_refract.h"  // (vrt_set_water_refraction: that pair with the span walk and the bends)
 
 namespace vrt {
 
@@ -315,6 +316,29 @@ void launch_path_bounce_water(const FrameParams &P, const WaterLaunch &W, const 
     with_march_build(P, stats, literal, [&](auto build, size_t sh) {
         using B = decltype(build);
         hipLaunchKernelGGL((path_water_bounce_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S);
+    });
+}
+
+// vrt_set_water_refraction (vrt_path_refract.h): the same two launches of a water frame whose context has an index of refraction
+void launch_path_primary_refract(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, const RefractLaunch &X, bool stats, bool literal,
+                                 hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_tiles(P), block(256);
+    const FrameParams D = dry_params(P);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_refract_primary_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S, X);
+    });
+}
+
+void launch_path_bounce_refract(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, const RefractLaunch &X, bool stats, bool literal,
+                                hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_records(P.hit_seg_cap), block(256);
+    const FrameParams D = dry_params(P);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_refract_bounce_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S, X);
     });
 }
 

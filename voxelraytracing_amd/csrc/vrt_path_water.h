@@ -37,6 +37,8 @@ __device__ __forceinline__ WaterLds water_lds() {
 // What follows a segment's march in a water frame (steps 3 to 5 of vrt_set_water_optics' contract).  wet: the segment started in a
 // liquid.  Called by every lane that marched; true: the path goes on (st updated).  LATER: a segment behind the primary one —
 // its miss takes the sky without the disc when the frame is sun-lit.  wants .. term: the sun ray's record, if the frame is sun-lit.
+// (vrt_path_refract.h: refract_after_march restates this text behind its underside event, with the bend in the transmitted branch — a
+// change here is made there too; the refracting frames with ior = 1 and the reference hold the two together.)
 template <bool LATER>
 __device__ __forceinline__ bool water_after_march(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, const uint32_t *s_liquid, bool wet,
                                                   PathState &st, const MarchResult &R, V3 &light, bool &lit, bool &wants, V3 &so, V3 &sd, V3 &term) {

@@ -287,6 +287,15 @@ class Gpu:
         o = _ffi.WaterOptics((C.c_float * 3)(*(float(x) for x in a)), reflectance, _ffi.WATER_ON, (C.c_uint32 * 3)(0, 0, 0))
         self._ck(self._lib.vrt_set_water_optics(self._h, C.byref(o)))
 
+    def set_water_refraction(self, ior: float, max_span: int = 0):
+        """vrt_set_water_refraction: in later MODE_PATH frames with set_water_optics on, a path that enters the water is bent by
+        Snell's law (ior: the water's index of refraction relative to air, in [1, 4]; 1.33 is water's), and a segment inside the
+        water that reaches its surface from below is mirrored back (always, past the critical angle) or bent out into the air.
+        max_span: the unit voxels such a segment's walk to the surface may cross (0 = 64, at most 1024).  ior 0 = off, the
+        default.  With water optics off the setting is kept and changes nothing; changing it restarts the accumulation."""
+        o = _ffi.WaterRefraction(ior, max_span, 0, 0)
+        self._ck(self._lib.vrt_set_water_refraction(self._h, C.byref(o)))
+
     def set_camera_sampling(self, pixel_spread: float, aperture: float = 0.0, focus_distance: float = 0.0):
         """vrt_set_camera_sampling: every sample of a later MODE_PATH frame gets a primary ray of its own — through a point of
         the pixel_spread-wide box around the pixel's centre (1: the pixel itself; 0: no jitter) and, with aperture != 0, from
