@@ -351,6 +351,17 @@ pub struct vrt_water_optics {
     pub _reserved: [u32; 3],
 }
 
+/// vrt_set_haze: air that scatters light in the path trace — extinction per voxel length (density 0 = off; otherwise in
+/// [2^-20, 64]) and what a scatter event keeps of the throughput per channel (albedo, in [0, 1]).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct vrt_haze {
+    pub density: f32,
+    pub albedo: [f32; 3],
+    pub flags: u32,
+    pub _reserved: [u32; 3],
+}
+
 /// vrt_set_water_refraction: Snell's law at the water's surface and the surface seen from below, in frames with water optics on
 /// (ior 0 = off; otherwise in [1, 4]; max_span: the unit voxels a wet segment's span walk may cross, 0 = 64, at most 1024).
 #[repr(C)]
@@ -476,6 +487,7 @@ extern "C" {
     pub fn vrt_set_sun_light(ctx: *mut vrt_ctx, opts: *const vrt_sun_light) -> c_int;
     pub fn vrt_set_water_optics(ctx: *mut vrt_ctx, opts: *const vrt_water_optics) -> c_int;
     pub fn vrt_set_water_refraction(ctx: *mut vrt_ctx, opts: *const vrt_water_refraction) -> c_int;
+    pub fn vrt_set_haze(ctx: *mut vrt_ctx, opts: *const vrt_haze) -> c_int;
     pub fn vrt_set_camera_sampling(ctx: *mut vrt_ctx, opts: *const vrt_camera_sampling) -> c_int;
     pub fn vrt_set_lamp_light(ctx: *mut vrt_ctx, opts: *const vrt_lamp_light) -> c_int;
     pub fn vrt_get_lamp_info(ctx: *mut vrt_ctx, out: *mut vrt_lamp_info) -> c_int;
@@ -547,6 +559,7 @@ mod layout {
         assert!(size_of::<vrt_sun_light>() == 16);
         assert!(size_of::<vrt_water_optics>() == 32);
         assert!(size_of::<vrt_water_refraction>() == 16);
+        assert!(size_of::<vrt_haze>() == 32);
         assert!(size_of::<vrt_camera_sampling>() == 16);
         assert!(size_of::<vrt_lamp_light>() == 16);
         assert!(size_of::<vrt_lamp>() == 16);

@@ -651,6 +651,61 @@ typedef struct {
 } vrt_water_refraction;     /* 16 B */
 int vrt_set_water_refraction(vrt_ctx *ctx, const vrt_water_refraction *opts);
 
+/* Haze for VRT_MODE_PATH: air that scatters light.  Without the setting the space between surfaces is a vacuum; with it every
+ * segment of a path may end in a scatter event before it reaches what its march found, and a sun-lit frame sends a sun ray from
+ * there: fog, aerial perspective, shafts of light.  The medium is homogeneous and fills the world box; its phase function is
+ * isotropic.  The primary modes ignore the setting and stay byte for byte what they are.  Build-defined, and defined exactly — in
+ * a haze frame (density != 0 and max_ray_bounces > 0), per path segment with origin o (world-local), direction d and throughput
+ * thr, in strict binary32, nothing contracted, sqrt and division correctly rounded:
+ *   1  the march is unchanged.  The segment is marched as the frame without the setting marches it: R.  The primary segment's id
+ *      word, vrt_read_steps, the denoiser's key and guide, vrt_stats.hits and a stats frame's counts are that march's
+ *   2  the distance draw.  u = rng_next(rng) on every segment, the primary and the last allowed one included, ahead of every other
+ *      draw of the segment, whatever follows:
+ *        uc = u < 1e-10f ? 1e-10f : u               (rng_next_u2's clamp)
+ *        t = (-vlog(uc)) * inv                      inv = 1.0f / density, formed once on the host
+ *      vlog is the path kernels' logarithm (csrc/both/haze_math.h states it operation for operation; the host's vrth_haze_distance
+ *      compiles the same text)
+ *   3  the segment's length in the haze, L:
+ *        on R.hit (running out of steps is a hit, as in ray_world):  v.k = R.pos.k - o.k;  L = sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)
+ *        on a miss, the exit from the world box:  e.k = (world_max - o.k) / d.k where d.k > 0, (0.0f - o.k) / d.k where d.k < 0,
+ *        +inf otherwise;  L = min(e.x, min(e.y, e.z)) with fminf's semantics        (vrth_haze_exit)
+ *        L = 0 if any o.k is <= 0 or >= world_max or a NaN: the origin ray_world treats as outside
+ *   4  the scatter event happens iff t < L (a NaN gives none).  x.k = o.k + d.k * t (a multiply, an add).  The march's hit is not
+ *      used: no emission term, no sun ray of the hit, no pass-through or coat draw, no sky.
+ *        thr'.ch = thr.ch * albedo[ch]
+ *        if vrt_set_sun_light is on:  sd = normalize(sun_pos - f32(world.min) - x);  q = (sd.x*sd.x + sd.y*sd.y) + sd.z*sd.z;
+ *          only if q > 0.5f (a zero or a NaN gives no ray): march ray_world(x, sd), start nudge included, exactly as a hit's sun
+ *          ray; if unoccluded:  k = settings.sun_intensity * strength;  w = k * 0.25f;  light.ch += (albedo[ch] * w) * thr.ch
+ *          with thr the throughput before the event (the isotropic phase function against the sun term's Lambert convention: k / 4).
+ *          The ray is sent on the last allowed segment too
+ *        d' = rng_next_dir(rng) (its six draws);  o' = x
+ *      The event costs one of the path's max_ray_bounces segments; vrt_stats.secondary_rays counts its continuation as the bounce
+ *      segment it is and its sun ray as a sun ray
+ *   5  no event: behind the draw, the segment is word for word the segment of the frame without the setting — sun-lit, emissive,
+ *      polished or translucent as that frame is.  A sun-lit frame's later misses take the sky without the disc; that covers the
+ *      segment behind a scatter event, whose sun was sampled at the event
+ *   6  a sample's light is its terms in segment order; a frame's, its samples' in sample order, / spp.  VRT_RENDER_ACCUMULATE keeps
+ *      its identity (K frames of s spp are one frame of K * s spp, bit for bit).  vrt_set_denoise, vrt_set_tone_map, the emission,
+ *      polish and translucency tables, shard and multi-device contexts compose as for a water frame
+ * A haze frame runs one lane = path launch per segment, one sample per chain, as a sun-lit frame does.  Not built: height falloff,
+ * an anisotropic phase function, haze along sun rays (they are not attenuated), a march cut short at t.
+ * Does not compose yet: with the setting on, vrt_render of a VRT_MODE_PATH frame (max_ray_bounces > 0) while vrt_set_water_optics,
+ * vrt_set_lamp_light or vrt_set_camera_sampling is on returns VRT_ERR_STATE, names vrt_set_haze and the other setter in
+ * vrt_last_error, enqueues nothing and leaves the last frame readable.  With haze off the refusals that exist are what they are.
+ * opts NULL or density +0 / -0: off, the default — frames are byte for byte those of a context that never called this, the same
+ * kernels run, and nothing is launched, planned or allocated differently.  A null context, a density that is NaN, negative,
+ * infinite, or not 0 and outside [2^-20, 64], an albedo outside [0, 1] or NaN (checked whatever density is), flags or _reserved
+ * not 0: VRT_ERR_INVALID_ARG; a refused call changes nothing.  A call that changes the setting (off is 32 zero bytes; -0 is kept
+ * as +0) restarts the accumulation; one that does not, does not.  A multi-device context replicates the setting; a shard context
+ * keeps its own. */
+typedef struct {
+    float    density;       /* 0 = off (the default); extinction per voxel length */
+    float    albedo[3];     /* per channel, in [0, 1]: what a scatter event keeps */
+    uint32_t flags;         /* 0 */
+    uint32_t _reserved[3];  /* 0 */
+} vrt_haze;                 /* 32 B */
+int vrt_set_haze(vrt_ctx *ctx, const vrt_haze *opts);
+
 /* Camera sampling for VRT_MODE_PATH: a primary ray of its own for every sample — sub-pixel jitter (a box pixel filter, which
  * is what removes the stair steps of voxel edges as samples accumulate) and a thin lens (depth of field).  Without it every
  * sample of a pixel starts with the pixel's one ray.  The primary modes ignore the setting and stay byte for byte what they

@@ -247,6 +247,14 @@ typedef struct {
 /* Returns 0, or -1 for a null pointer or max_span above 1024. */
 int vrth_world_water_span(const vrth_world *w, const vrt_material *mats256, const float o[3], const float d[3], uint32_t max_span, vrth_water_span *out);
 
+/* ---- haze (include/vrt.h: vrt_set_haze) on the host ---- */
+/* out[i] = step 2 of the contract for the draw u[i], i < n: (-vlog(max(u, 1e-10))) * inv in the text the haze kernels compile
+ * (csrc/both/haze_math.h); inv = 1.0f / density as the context forms it.  out may alias u.  Returns 0, or -1 for a null pointer. */
+int vrth_haze_distance(const float *u, uint64_t n, float inv, float *out);
+/* Step 3's length of a segment that hits nothing: where the ray from o (world-local) along d leaves the box (0, world_max)^3; 0 for
+ * an origin on or beyond a face, or a NaN.  *out: L.  Returns 0, or -1 for a null pointer. */
+int vrth_haze_exit(const float o[3], const float d[3], float world_max, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -489,6 +489,111 @@ static void check_water_frames() {
     std::printf("check_water_plan: ok (%ld water frames, %ld launches)\n", frames, launches);
 }
 
+// vrt_set_haze: a haze frame is planned like a sun-lit one as well — the same chains, launch numbers and finishing passes, no pool
+// kernel, one sample per chain — with the haze kinds in the place of the trace launches' and a kStepSunRays behind each only when
+// the frame is sun-lit too; sun_cells is the sun-lit frame's.  The kinds from before keep their values.  haze = false leaves every
+// plan what it was: every check above plans with F.haze false and still holds, against the loop plan_path replaced and against each
+// setting's own structure; here a frame without a traced segment is the plan without the setting, field by field, and no plan with
+// haze false has a haze step.
+static bool same_plan(const PathPlan &a, const PathPlan &b) {
+    return a.spp == b.spp && a.seed == b.seed && a.bounces == b.bounces && a.kstats == b.kstats && a.literal == b.literal && a.emit == b.emit &&
+           a.polish == b.polish && a.translucent == b.translucent && a.sun == b.sun && a.sun_cells == b.sun_cells && a.lens == b.lens && a.lamp == b.lamp &&
+           a.water == b.water && a.haze == b.haze && a.samples == b.samples && a.planes == b.planes && a.own_sum == b.own_sum && a.cells == b.cells &&
+           a.seg_cap == b.seg_cap && a.cap == b.cap && a.pool_batches == b.pool_batches && a.refill == b.refill && a.zero_output == b.zero_output &&
+           a.finish == b.finish && a.finish_into_accum == b.finish_into_accum && a.divide_at_end == b.divide_at_end &&
+           a.needs_acc_planes == b.needs_acc_planes && a.needs_accum_sum == b.needs_accum_sum && a.sample_base == b.sample_base &&
+           a.accum_count == b.accum_count;
+}
+
+static void check_haze_frames() {
+    static_assert(vrt::kStepWaterPrimary == 12 && vrt::kStepWaterBounce == 13 && vrt::kStepHazePrimary == 14 && vrt::kStepHazeBounce == 15,
+                  "the step kinds from before vrt_set_haze keep their values; the haze kinds are appended");
+    long frames = 0, launches = 0;
+    const uint32_t spps[] = {1, 2, 3, 12, 17}, per_chain[] = {1, 4, 16};
+    const int accums[] = {-1, 0, 7};
+    for (uint32_t spp : spps)
+    for (uint32_t bounces = 0; bounces <= 5; bounces++)
+    for (uint32_t bits = 0; bits < 1024; bits++)
+    for (int accum : accums)
+    for (uint32_t samples : per_chain) {
+        PathFacts F;
+        F.spp = spp; F.seed = 11u; F.bounces = bounces; F.haze = true;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u; F.sun = bits & 512u;
+        F.march_direct = F.has_cells;
+        F.accum = accum >= 0; F.accum_from = accum >= 0 ? (uint32_t)accum : 0u;
+        F.path_samples = samples; F.hit_seg_cap = 512u;
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid)) continue;
+        std::snprintf(g_case, sizeof g_case, "haze: spp %u bounces %u bits %u accum %d per chain %u", spp, bounces, bits, accum, samples);
+        const PathPlan p = vrt::plan_path(F);
+        PathFacts E = F;   // the same frame with the haze off and the sun on: the structure a haze frame takes
+        E.haze = false; E.sun = true;
+        const PathPlan e = vrt::plan_path(E);
+        PathFacts O = F;   // ... and with the haze off: what the setting must not change when it is off
+        O.haze = false;
+        const PathPlan o = vrt::plan_path(O);
+        CHECK(!o.haze && !e.haze && p.haze == (bounces > 0u) && p.sun == (F.sun && bounces > 0u) && p.sun == o.sun && p.sun_cells == o.sun_cells &&
+              !p.lamp && !p.lens && !p.water);
+        CHECK(p.polish == F.polished && p.translucent == F.translucent);
+        if (!p.haze) {   // no segment is traced: the plan is the plan without the setting
+            CHECK(same_plan(p, o));
+            continue;
+        }
+        // off leaves the kinds of every other frame alone: a frame with haze off has no haze step
+        {
+            bool any = false;
+            vrt::for_each_path_step(o, [&](const PathStep &s) { any = any || s.kind == vrt::kStepHazePrimary || s.kind == vrt::kStepHazeBounce; });
+            CHECK(!any);
+        }
+        CHECK(p.emit && !p.cells && p.samples == 1u && !p.planes);
+        CHECK(p.sun_cells == (p.sun && e.sun_cells));
+        CHECK(p.finish == e.finish && p.own_sum == e.own_sum && p.seg_cap == e.seg_cap && p.cap == e.cap && p.divide_at_end == e.divide_at_end &&
+              p.needs_acc_planes == e.needs_acc_planes && p.needs_accum_sum == e.needs_accum_sum && p.sample_base == e.sample_base &&
+              p.accum_count == e.accum_count && p.finish_into_accum == e.finish_into_accum && p.zero_output == e.zero_output);
+        std::vector<PathStep> ps, es;
+        vrt::for_each_path_step(p, [&](const PathStep &s) { ps.push_back(s); });
+        vrt::for_each_path_step(e, [&](const PathStep &s) { es.push_back(s); });
+        size_t i = 0;
+        for (const PathStep &s : es) {
+            if (s.kind == vrt::kStepSunRays) {   // (the sun's launch: only in a frame that is sun-lit too, checked below)
+                continue;
+            }
+            CHECK(i < ps.size());
+            const PathStep &t = ps[i++];
+            CHECK(t.sample == s.sample && t.chain == s.chain && t.launch == s.launch &&
+                  t.segments == s.segments && t.last_bounce == s.last_bounce && t.first == s.first && t.last == s.last && t.count == s.count);
+            if (s.kind == vrt::kStepSunlitPrimary || s.kind == vrt::kStepSunlitBounce) {
+                CHECK(t.kind == (s.kind == vrt::kStepSunlitPrimary ? vrt::kStepHazePrimary : vrt::kStepHazeBounce) && vrt::traces_paths(t.kind));
+                if (p.sun) {
+                    CHECK(i < ps.size() && ps[i].kind == vrt::kStepSunRays && ps[i].launch == t.launch);
+                    i++;
+                }
+            } else {
+                CHECK(t.kind == s.kind && !vrt::traces_paths(t.kind));
+            }
+        }
+        CHECK(i == ps.size());
+        frames++;
+        launches += (long)ps.size();
+    }
+    // haze = false, with every other setting: the plan does not read the field's neighbours differently (water, lamp and camera
+    // sampling never meet haze = true: vrt_render refuses the pairs)
+    for (uint32_t bits = 0; bits < 4096; bits++)
+    for (uint32_t bounces = 0; bounces <= 3; bounces++) {
+        PathFacts F;
+        F.spp = 3u; F.bounces = bounces;
+        F.kstats = bits & 1u; F.literal = bits & 2u; F.has_grid = bits & 4u; F.has_cells = bits & 8u; F.emissive = bits & 16u;
+        F.path_pool = bits & 32u; F.path_cells = bits & 64u; F.polished = bits & 128u; F.translucent = bits & 256u; F.sun = bits & 512u;
+        F.water = bits & 1024u; F.lamp = bits & 2048u;
+        if ((F.literal && F.has_grid) || (F.has_cells && !F.has_grid) || (F.water && F.lamp)) continue;
+        std::snprintf(g_case, sizeof g_case, "haze off: bounces %u bits %u", bounces, bits);
+        const PathPlan p = vrt::plan_path(F);
+        CHECK(!p.haze);
+        vrt::for_each_path_step(p, [&](const PathStep &s) { CHECK(s.kind != vrt::kStepHazePrimary && s.kind != vrt::kStepHazeBounce); });
+    }
+    std::printf("check_haze_plan: ok (%ld haze frames, %ld launches)\n", frames, launches);
+}
+
 int main() {
     long compared[3][4] = {}, skipped = 0;
     const uint32_t flag_sets[4] = {0u, VRT_RENDER_OWN_STREAMS, VRT_RENDER_ACCUMULATE, VRT_RENDER_OWN_STREAMS | VRT_RENDER_ACCUMULATE};
@@ -554,5 +659,6 @@ int main() {
     check_lamp_frames();
     check_lens_frames();
     check_water_frames();
+    check_haze_frames();
     return 0;
 }

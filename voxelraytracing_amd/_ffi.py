@@ -119,6 +119,11 @@ class WaterOptics(C.Structure):
 WATER_ON = 1   # vrt_water_optics.flags (VRT_WATER_ON)
 
 
+class Haze(C.Structure):
+    """include/vrt.h vrt_haze: air that scatters light in the path trace (vrt_set_haze)"""
+    _fields_ = [("density", C.c_float), ("albedo", C.c_float * 3), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
+
+
 class WaterRefraction(C.Structure):
     """include/vrt.h vrt_water_refraction: Snell's law at the water's surface, the surface from below (vrt_set_water_refraction)"""
     _fields_ = [("ior", C.c_float), ("max_span", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
@@ -289,6 +294,7 @@ VRT_SYMBOLS = {
     "vrt_set_sun_light": (C.c_int, [_P, C.POINTER(SunLight)]),
     "vrt_set_water_optics": (C.c_int, [_P, C.POINTER(WaterOptics)]),
     "vrt_set_water_refraction": (C.c_int, [_P, C.POINTER(WaterRefraction)]),
+    "vrt_set_haze": (C.c_int, [_P, C.POINTER(Haze)]),
     "vrt_set_camera_sampling": (C.c_int, [_P, C.POINTER(CameraSampling)]),
     "vrt_set_lamp_light": (C.c_int, [_P, C.POINTER(LampLight)]),
     "vrt_get_lamp_info": (C.c_int, [_P, C.POINTER(LampInfo)]),
@@ -497,6 +503,8 @@ VRTH_SYMBOLS = {
     "vrth_water_transmittance": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "vrth_water_refract": (C.c_int, [C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.POINTER(C.c_float)]),
     "vrth_world_water_span": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(WaterSpan)]),
+    "vrth_haze_distance": (C.c_int, [_P, C.c_uint64, C.c_float, _P]),
+    "vrth_haze_exit": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]),
 }
 
 # Gpu.set_denoise's suggested setting (docs/KERNELS.md: the sweep they come from)
@@ -583,6 +591,26 @@ def water_transmittance(absorb, dist) -> np.ndarray:
     if host().vrth_water_transmittance(a.ctypes.data, d.ctypes.data, a.size, out.ctypes.data):
         raise ValueError("vrth_water_transmittance refused the arguments")
     return out
+
+
+def haze_distance(u, inv: float) -> np.ndarray:
+    """vrth_haze_distance: (-vlog(max(u, 1e-10))) * inv elementwise (f32), in the text the haze kernels compile
+    (csrc/both/haze_math.h) — how far vrt_set_haze's draw u reaches; inv = 1.0f / density."""
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float32))
+    out = np.empty(u.shape, dtype=np.float32)
+    if host().vrth_haze_distance(u.ctypes.data, u.size, float(inv), out.ctypes.data):
+        raise ValueError("vrth_haze_distance refused the arguments")
+    return out
+
+
+def haze_exit(o, d, world_max: float) -> np.float32:
+    """vrth_haze_exit: where the ray from o (world-local) along d leaves the box (0, world_max)^3 — the length in the haze of a
+    segment that hits nothing; 0 for an origin on or beyond a face, or a NaN."""
+    f3 = C.c_float * 3
+    out = C.c_float()
+    if host().vrth_haze_exit(f3(*(float(np.float32(x)) for x in o)), f3(*(float(np.float32(x)) for x in d)), float(np.float32(world_max)), C.byref(out)):
+        raise ValueError("vrth_haze_exit refused the arguments")
+    return np.float32(out.value)
 
 
 def water_refract(ior: float, reflectance: float, d, normal, u: float = 0.0, leaving: bool = False):

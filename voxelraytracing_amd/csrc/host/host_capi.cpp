@@ -12,6 +12,7 @@
 #include "../both/column_top.h"
 #include "../both/denoise_math.h"
 #include "../both/lens_math.h"
+#include "../both/haze_math.h"
 #include "../both/refract_math.h"
 #include "../both/shape_math.h"
 #include "../both/tone_math.h"
@@ -746,7 +747,20 @@ int vrth_water_refract(float ior, float reflectance, const float d[3], const flo
     return VRTH_REFRACT_ENTERED;
 }
 
-// ... and its span walk over a host world: the voxel as vrth_world_get_voxels records it (0 outside the box, 0 without a chunk)
+// vrt_set_haze's distance draw and box exit: csrc/both/haze_math.h, the text the haze kernels compile
+int vrth_haze_distance(const float *u, uint64_t n, float inv, float *out) {
+    if (!u || !out) return -1;
+    for (uint64_t i = 0; i < n; i++) out[i] = vrt::haze_distance(u[i], inv);
+    return 0;
+}
+
+int vrth_haze_exit(const float o[3], const float d[3], float world_max, float *out) {
+    if (!o || !d || !out) return -1;
+    *out = vrt::haze_exit(o, d, world_max);
+    return 0;
+}
+
+// ... and vrt_set_water_refraction's span walk over a host world: the voxel as vrth_world_get_voxels records it (0 outside the box, 0 without a chunk)
 int vrth_world_water_span(const vrth_world *w, const vrt_material *mats256, const float o[3], const float d[3], uint32_t max_span, vrth_water_span *out) {
     if (!w || !mats256 || !o || !d || !out || max_span > vrt::kRefractSpanMax) return -1;
     const VoxelPos lo = w->w.min_voxel();

@@ -103,6 +103,9 @@ void launch_path_primary_refract(const FrameParams &P, const WaterLaunch &W, con
                                  hipStream_t st);
 void launch_path_bounce_refract(const FrameParams &P, const WaterLaunch &W, const SunLaunch &S, const RefractLaunch &X, bool stats, bool literal,
                                 hipStream_t st);
+// vrt_set_haze (vrt_path_haze.h): a haze frame's trace launches (S: with buffers when the frame is sun-lit too)
+void launch_path_primary_haze(const FrameParams &P, const HazeLaunch &H, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
+void launch_path_bounce_haze(const FrameParams &P, const HazeLaunch &H, const SunLaunch &S, bool stats, bool literal, hipStream_t st);
 void launch_path_finish(Texel *out, uint32_t n, uint32_t spp, hipStream_t st);
 void launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t shift, uint32_t *scratch, uint32_t *order, hipStream_t st);
 bool launch_tile_order_blocks(const uint32_t *cost, uint32_t tiles_x, uint32_t tiles_y, uint32_t shift, uint32_t radius, uint32_t *order, hipStream_t st, uint32_t threads);
@@ -543,6 +546,7 @@ struct vrt_ctx {
     vrt_sun_light sun{};      // vrt_set_sun_light: the setting (16 zero bytes: off); the sun-ray buffers are sz.sun_recs / sz.sun_counts
     vrt_water_optics water{}; // vrt_set_water_optics: the setting (32 zero bytes: off)
     vrt_water_refraction refraction{};   // vrt_set_water_refraction: the setting (16 zero bytes: off; max_span never 0 beside an ior)
+    vrt_haze haze{};          // vrt_set_haze: the setting (32 zero bytes: off)
     vrt_camera_sampling lens{};   // vrt_set_camera_sampling: the setting (16 zero bytes: off)
     // vrt_set_lamp_light (vrt_lamp.hip): the setting (16 zero bytes: off), the cap (VRT_LAMP_CAP) and one lamp list per frame set,
     // built on that set's stream by the lamp-lit frame that finds it out of date: what it was built from is kept beside it

@@ -225,6 +225,15 @@ struct RefractLaunch {
     uint32_t _pad;
 };
 
+// vrt_set_haze (vrt_path_haze.h): what the kernels of a haze frame are given besides FrameParams and a SunLaunch (whose buffers are
+// null and whose k is 0 when the sun is off)
+struct HazeLaunch {
+    float inv;            // 1.0f / density, formed once on the host (the density is never 0 here)
+    float albedo[3];      // the setting
+    uint32_t lobes;       // kSunLobePolish | kSunLobeTranslucent, as SunLaunch::lobes
+    uint32_t sun;         // 1: vrt_set_sun_light is on as well — the sun terms, and the later misses' sky without the disc
+};
+
 // vrt_set_tone_map: what the blit of a mapped frame is given besides the unmapped blit's arguments (both/tone_math.h's
 // ToneCurve, flat).  E_dev: the frame set's exposure word on the device (a metered frame: nothing of it comes back to the host);
 // null: E, the setting's own

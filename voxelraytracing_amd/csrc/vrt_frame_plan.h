@@ -94,6 +94,7 @@ struct PathFacts {   // copied out of the options, the context and the frame's p
     bool camera_sampling = false;   // vrt_set_camera_sampling: pixel_spread or aperture is not 0
     bool lamp = false;              // vrt_set_lamp_light: the strength is not 0
     bool water = false;             // vrt_set_water_optics: VRT_WATER_ON (never with lamp or camera_sampling: vrt_render refuses the pair)
+    bool haze = false;              // vrt_set_haze: the density is not 0 (never with water, lamp or camera_sampling: vrt_render refuses the pair)
     // the context's switches (vrt_create reads them from the environment)
     uint32_t path_samples = 8;      // VRT_PATH_SAMPLES_PER_CHAIN
     bool path_pool = true, path_cells = true;   // VRT_PATH_POOL, VRT_PATH_CELLS
@@ -112,7 +113,7 @@ enum PathFinish : uint32_t {   // the pass behind each chain of samples
 
 struct PathPlan {   // each field is explained where plan_path sets it
     uint32_t spp = 1, seed = 0, bounces = 0;
-    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false, lens = false, lamp = false, water = false;
+    bool kstats = false, literal = false, emit = false, polish = false, translucent = false, sun = false, sun_cells = false, lens = false, lamp = false, water = false, haze = false;
     uint32_t samples = 1;
     bool planes = false, own_sum = false, cells = false;
     uint32_t seg_cap = 0;
@@ -152,7 +153,11 @@ inline PathPlan plan_path(const PathFacts &F) {
     // bounce, planned as a sun-lit frame is.  Sun-lit too, its sun launches are the sun-lit frame's own (sun_cells included: sun rays
     // pass liquids as they always have)
     p.water = F.water && F.bounces > 0u;
-    p.samples = (F.spp > 1u && fast && F.bounces > 0u && !p.sun && !p.lamp && !p.water) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
+    // vrt_set_haze: a haze frame's kernels draw a distance behind every march and may append a sun ray from a point in the air
+    // (vrt_path_haze.h); the pool kernel has neither, so such a frame is once more one sample per chain, one lane = path launch per
+    // bounce, planned as a sun-lit frame is.  Sun-lit too, its sun launches are the sun-lit frame's own (sun_cells included)
+    p.haze = F.haze && F.bounces > 0u;
+    p.samples = (F.spp > 1u && fast && F.bounces > 0u && !p.sun && !p.lamp && !p.water && !p.haze) ? (F.spp < F.path_samples ? F.spp : F.path_samples) : 1u;
     p.planes = p.samples > 1u;
     // vrt_write_emission: a sample's light is then several terms (emissive hits, the sky), summed by themselves before they
     // join the frame.  The planes do that, and so does a one-sample chain whose texel holds that sample alone: an accumulating
@@ -165,7 +170,7 @@ inline PathPlan plan_path(const PathFacts &F) {
     // (they take the coat's draw under a word the uploads keep on the device), so translucent is what the launchers look at first
     // vrt_set_sun_light: and again — a sample is then several terms (the sun terms, the sky).  Its kernels are one pair, which reads
     // from its launch whether there is a coat or a pass-through draw
-    p.emit = F.emissive || F.polished || F.translucent || p.sun || p.lamp || p.water;
+    p.emit = F.emissive || F.polished || F.translucent || p.sun || p.lamp || p.water || p.haze;
     p.polish = F.polished;
     p.translucent = F.translucent;
     // vrt_set_camera_sampling: the frame's kStepPrimary / kStepSunlitPrimary launches are the kernels of vrt_path_lens.h, which give
@@ -177,7 +182,7 @@ inline PathPlan plan_path(const PathFacts &F) {
     p.cap = (size_t)kPlanHitSegments * p.seg_cap;
     // Bounce launches over the march cells: every later segment of a chain in ONE launch of the pool kernel (vrt_path.hip);
     // worlds without march cells, or with the pool switched off: one lane = path launch per bounce.
-    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells && !p.sun && !p.lamp && !p.water;
+    p.cells = fast && F.bounces > 1u && F.path_pool && F.has_cells && F.path_cells && !p.sun && !p.lamp && !p.water && !p.haze;
     // the pool's batches of 64 rays per wave: 5 with two frames in flight (the launcher grants them to direct worlds only), else 4
     p.pool_batches = F.path_pool_batches ? F.path_pool_batches : (F.in_flight > 1u ? 5u : 4u);
     p.refill = F.path_refill;
@@ -201,12 +206,13 @@ inline PathPlan plan_path(const PathFacts &F) {
 // kStepSunlitPrimary / kStepSunlitBounce are a sun-lit frame's, each followed by a kStepSunRays with its launch number;
 // kStepLampPrimary / kStepLampBounce, appended behind the others, are a lamp-lit frame's, sun-lit or not: each is followed by a
 // kStepSunRays, if the frame is sun-lit too, and then by a kStepLampRays; kStepWaterPrimary / kStepWaterBounce, behind those again,
-// are a water frame's, each followed by a kStepSunRays if the frame is sun-lit too)
+// are a water frame's, each followed by a kStepSunRays if the frame is sun-lit too; kStepHazePrimary / kStepHazeBounce, last, are a
+// haze frame's, followed in the same way)
 enum PathStepKind : uint32_t { kStepPrimary, kStepLaneBounce, kStepCellsBounce, kStepSunlitPrimary, kStepSunlitBounce, kStepSunRays,
                                kStepChainFinish, kStepResolve, kStepFinalDivide, kStepLampPrimary, kStepLampBounce, kStepLampRays,
-                               kStepWaterPrimary, kStepWaterBounce };
+                               kStepWaterPrimary, kStepWaterBounce, kStepHazePrimary, kStepHazeBounce };
 inline bool traces_paths(PathStepKind k) { return k <= kStepSunlitBounce || k == kStepLampPrimary || k == kStepLampBounce || k == kStepWaterPrimary ||
-                                                      k == kStepWaterBounce; }
+                                                      k == kStepWaterBounce || k == kStepHazePrimary || k == kStepHazeBounce; }
 
 struct PathStep {   // one launch of the frame
     PathStepKind kind;
@@ -236,6 +242,7 @@ void for_each_path_step(const PathPlan &p, F &&f) {
             if (p.sun) s.kind = b == 0u ? kStepSunlitPrimary : kStepSunlitBounce;
             if (p.lamp) s.kind = b == 0u ? kStepLampPrimary : kStepLampBounce;
             if (p.water) s.kind = b == 0u ? kStepWaterPrimary : kStepWaterBounce;
+            if (p.haze) s.kind = b == 0u ? kStepHazePrimary : kStepHazeBounce;
             f(s);
             if (p.sun) {   // the records that launch appended: cursor set launch & 1 of the sun buffer
                 s.kind = kStepSunRays;

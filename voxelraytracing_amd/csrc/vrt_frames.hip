@@ -370,6 +370,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
     // X is built all the same and nothing reads it — no launch below takes it unless `refracts`
     const bool refracts = c->refraction.ior != 0.0f;
     const vrt::RefractLaunch X{c->refraction.ior, refracts ? 1.0f / c->refraction.ior : 0.0f, c->refraction.max_span, 0u};
+    // vrt_set_haze: the setting as the kernels of vrt_path_haze.h take it.  Off: H is built all the same and nothing reads it
+    const vrt::HazeLaunch H{plan.haze ? 1.0f / c->haze.density : 0.0f, {c->haze.albedo[0], c->haze.albedo[1], c->haze.albedo[2]}, lobes, plan.sun ? 1u : 0u};
     // vrt_set_camera_sampling: the setting as the primary kernels of vrt_path_lens.h take it
     const vrt::LensLaunch L{c->lens.pixel_spread, c->lens.aperture, c->lens.focus_distance, lobes};
     vrt::Texel *const frame_out = P.out, *const acc = c->sz.path_acc[f.slot];
@@ -437,6 +439,8 @@ static int launch_path_frame(vrt_ctx *c, vrt::FrameParams &P, const FrameSet &f,
                 if (refracts) launch_path_bounce_refract(P, W, S, X, plan.kstats, plan.literal, f.st);
                 else launch_path_bounce_water(P, W, S, plan.kstats, plan.literal, f.st);
                 break;
+            case kStepHazePrimary: launch_path_primary_haze(P, H, S, plan.kstats, plan.literal, f.st); break;
+            case kStepHazeBounce: launch_path_bounce_haze(P, H, S, plan.kstats, plan.literal, f.st); break;
             case kStepChainFinish:
                 launch_path_chain_finish(plan.finish_into_accum ? c->sz.d_accum.get() : frame_out, frame_out, acc, c->slots, s.chain, s.first, s.last, s.count, f.st);
                 break;
@@ -709,6 +713,14 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
         return fail(c, VRT_ERR_STATE, "vrt_render: water optics (vrt_set_water_optics) and lamp light (vrt_set_lamp_light) do not compose yet");
     if (water_frame && (c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f))
         return fail(c, VRT_ERR_STATE, "vrt_render: water optics (vrt_set_water_optics) and camera sampling (vrt_set_camera_sampling) do not compose yet");
+    // vrt_set_haze: a haze frame's kernels have no water, no lamp term and no lens (include/vrt.h); refused in the same way
+    const bool haze_frame = o.mode == VRT_MODE_PATH && c->haze.density != 0.0f && c->settings.max_ray_bounces > 0u;
+    if (haze_frame && c->water.flags != 0u)
+        return fail(c, VRT_ERR_STATE, "vrt_render: haze (vrt_set_haze) and water optics (vrt_set_water_optics) do not compose yet");
+    if (haze_frame && c->lamp.strength != 0.0f)
+        return fail(c, VRT_ERR_STATE, "vrt_render: haze (vrt_set_haze) and lamp light (vrt_set_lamp_light) do not compose yet");
+    if (haze_frame && (c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f))
+        return fail(c, VRT_ERR_STATE, "vrt_render: haze (vrt_set_haze) and camera sampling (vrt_set_camera_sampling) do not compose yet");
     if (vrt::asks_for_tables(F) || lamp_lit) {
         VRT_PROF(9, "  ensure_accel_world");
         VRT_TRY(ensure_accel_world(c));
@@ -837,6 +849,7 @@ int vrt_render(vrt_ctx *c, const vrt_render_opts *opts) {
             PF.sun = c->sun.strength != 0.0f;
             PF.lamp = c->lamp.strength != 0.0f;
             PF.water = c->water.flags != 0u;
+            PF.haze = c->haze.density != 0.0f;
             PF.camera_sampling = c->lens.pixel_spread != 0.0f || c->lens.aperture != 0.0f;
             PF.path_samples = c->path_samples; PF.path_pool = c->path_pool; PF.path_cells = c->path_cells;
             PF.path_pool_batches = c->path_pool_batches; PF.path_refill = c->path_refill;
@@ -905,6 +918,26 @@ int vrt_set_water_optics(vrt_ctx *c, const vrt_water_optics *opts) {
     if (o.reflectance == 0.0f) o.reflectance = 0.0f;
     if (memcmp(&c->water, &o, sizeof o) != 0) c->accum_restart = true;
     c->water = o;
+    return VRT_OK;
+}
+
+int vrt_set_haze(vrt_ctx *c, const vrt_haze *opts) {
+    if (!c) return VRT_ERR_INVALID_ARG;
+    vrt_haze o;
+    memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    if (!(o.density == 0.0f || (o.density >= 0x1p-20f && o.density <= 64.0f)))
+        return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_haze: density %g (0 = off, or in [2^-20, 64])", (double)o.density);
+    for (float a : o.albedo)   // (checked whatever the density is)
+        if (!(a >= 0.0f && a <= 1.0f))
+            return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_haze: albedo %g %g %g (each in [0, 1])", (double)o.albedo[0], (double)o.albedo[1], (double)o.albedo[2]);
+    if (o.flags || o._reserved[0] || o._reserved[1] || o._reserved[2]) return fail(c, VRT_ERR_INVALID_ARG, "vrt_set_haze: flags and _reserved must be 0");
+    GRP_EACH(c, vrt_set_haze(d, opts));
+    // what is kept: off is 32 zero bytes, -0 is +0
+    if (o.density == 0.0f) memset(&o, 0, sizeof o);
+    for (float &a : o.albedo) if (a == 0.0f) a = 0.0f;
+    if (memcmp(&c->haze, &o, sizeof o) != 0) c->accum_restart = true;
+    c->haze = o;
     return VRT_OK;
 }
 

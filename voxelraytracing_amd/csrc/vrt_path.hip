@@ -31,6 +31,7 @@
 #include "vrt_path_lamp.h"   // (vrt_set_lamp_light: kernels of their own, behind everything they share with the others)
 #include "vrt_path_water.h"  // (vrt_set_water_optics: a pair of their own again)
 #include "vrt_path_refract.h"  // (vrt_set_water_refraction: that pair with the span walk and the bends)
+#include "vrt_path_haze.h"   // (vrt_set_haze: a pair of their own with the distance draw behind the march)
 
 namespace vrt {
 
@@ -339,6 +340,26 @@ void launch_path_bounce_refract(const FrameParams &P, const WaterLaunch &W, cons
     with_march_build(P, stats, literal, [&](auto build, size_t sh) {
         using B = decltype(build);
         hipLaunchKernelGGL((path_refract_bounce_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh + 8u * 4u, st, P, D, W, S, X);
+    });
+}
+
+// vrt_set_haze (vrt_path_haze.h): a haze frame is one lane = path launch per segment, as a sun-lit one; each is followed by the sun
+// launch if the sun is on as well (S then has buffers)
+void launch_path_primary_haze(const FrameParams &P, const HazeLaunch &H, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_tiles(P), block(256);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_haze_primary_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh, st, P, H, S);
+    });
+}
+
+void launch_path_bounce_haze(const FrameParams &P, const HazeLaunch &H, const SunLaunch &S, bool stats, bool literal, hipStream_t st) {
+    if (P.tiles_local == 0) return;
+    const dim3 grid = grid_of_records(P.hit_seg_cap), block(256);
+    with_march_build(P, stats, literal, [&](auto build, size_t sh) {
+        using B = decltype(build);
+        hipLaunchKernelGGL((path_haze_bounce_kernel<B::march, B::lds_roots, B::stats>), grid, block, sh, st, P, H, S);
     });
 }
 

@@ -296,6 +296,16 @@ class Gpu:
         o = _ffi.WaterRefraction(ior, max_span, 0, 0)
         self._ck(self._lib.vrt_set_water_refraction(self._h, C.byref(o)))
 
+    def set_haze(self, density: float, albedo=1.0):
+        """vrt_set_haze: later MODE_PATH frames have air that scatters light — every segment of a path may end in a scatter event
+        (density: extinction per voxel length, in [2^-20, 64]) that keeps albedo of the throughput (three floats in [0, 1], or one
+        for all three), sends a sun ray from there when set_sun_light is on, and goes on in a uniformly drawn direction.
+        density 0 = off, the default.  The primary modes ignore it; changing it restarts the accumulation.  With it on, a path
+        frame is refused (VRT_ERR_STATE) while set_water_optics, set_lamp_light or set_camera_sampling is on."""
+        a = np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,))
+        o = _ffi.Haze(density, (C.c_float * 3)(*(float(x) for x in a)), 0, (C.c_uint32 * 3)(0, 0, 0))
+        self._ck(self._lib.vrt_set_haze(self._h, C.byref(o)))
+
     def set_camera_sampling(self, pixel_spread: float, aperture: float = 0.0, focus_distance: float = 0.0):
         """vrt_set_camera_sampling: every sample of a later MODE_PATH frame gets a primary ray of its own — through a point of
         the pixel_spread-wide box around the pixel's centre (1: the pixel itself; 0: no jitter) and, with aperture != 0, from
